@@ -1,6 +1,6 @@
 """bench.py - training samples/sec of the VAE posterior-consistency step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,13 +15,22 @@ way the per-step gradient all-reduce (RCCL) is inside the timed region, ranks sh
 are keyed by the global row.
 Warm-up: the W requested steps, then "settle" steps in groups of 8 until the dominant kernel's HIP-event time of two
 consecutive groups agrees within 1.5 % (clock ramp after idle; at most 40 groups, all untimed; reported as
-`settle_steps`), then EXACTLY K timed steps.
+`settle_steps`), then EXACTLY K timed steps.  The settle steps only warm the clocks: the trainer state (parameters, Adam
+moments, step count, Philox offset, batch rotation) is put back to where the W warm-up steps left it before the timed
+steps, so that the timed steps compute the same thing whatever number of settle steps a run needed.
 
 Prints ONE JSON line (rank 0) with the contract's fields plus
   roofline     - dominant kernel (vpc_decoder_fused: reparam + decoder fwd + loss + decoder bwd): algorithmic
                  FLOP per launch / HIP-event duration measured live on the launch stream, vs the f32 MFMA peak
-  cpu_baseline - the oracle's op-for-op torch port of the reference CPU path (oracle/vae_oracle.py), timed on
-                 this box's host cores on a bounded sample (rank 0, N=1 only).
+--full adds what takes runs of its own:
+  kernels_ms of the other launches (16 steps after the timed region), per_step_sync_ms (the step with the reference's
+  per-step `.item()`), with N > 1 the other scaling mode, and with N = 1
+  extra_configs - BASELINE configs 2, 3 and 5 and the headline shape in bf16 (--no-extra-configs skips them)
+  cpu_baseline  - the oracle's op-for-op torch port of the reference CPU path (oracle/vae_oracle.py), timed on
+                  the host cores on a bounded sample (--no-cpu-baseline skips it).
+--dump-outputs DIR writes what the last timed step left for its caller (rank 0), as float32 .npy files: loss_terms (the
+step's loss and its 8 terms), grad (the flat gradient), params (the flat parameters after the Adam update), exp_avg and
+exp_avg_sq (the Adam moments).  Inputs, initial weights and draws are seeded: the same arguments give the same inputs.
 """
 import argparse
 import gc
@@ -31,6 +40,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -188,9 +198,19 @@ def ranks_seen(vpc, tr, world, dev):
     return int(round(float(one.item())))
 
 
-def measure(vpc, args, rank, world, dev, scaling):
+def dump_outputs(tr, model, out_dir):
+    """What the last step left for its caller (module docstring), as float32 .npy files in out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_terms": tr.out9, "grad": tr.grad, "params": model._flat, "exp_avg": tr.exp_avg,
+              "exp_avg_sq": tr.exp_avg_sq}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def measure(vpc, args, rank, world, dev, scaling, dump_dir=None):
     """Warm-up, settle, EXACTLY args.steps timed steps (barrier + synchronize on both sides, MAX over ranks) of the
-    headline step in one scaling mode; returns the raw numbers (every rank) - rank 0 formats them."""
+    headline step in one scaling mode; returns the raw numbers (every rank) - rank 0 formats them.  dump_dir: where rank 0
+    writes the last timed step's outputs."""
     d, Ld = args.dim, args.latent
     if scaling == "strong":
         Bg = args.batch
@@ -224,6 +244,8 @@ def measure(vpc, args, rank, world, dev, scaling):
     for _ in range(args.warmup):
         step()
     sync()
+    # the state the timed steps start from, put back after the settle steps (module docstring)
+    warm = (flat.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone(), tr.step_count, tr.rng_offset, it[0])
     dom = tr.dominant_launch()  # "decoder_fused", or "step_fused" when the three MFMA kernels are one launch
     # CPython's generation-2 garbage collection fires once around step 70 of the timed loop (the ctypes argument arrays of
     # ~350 launches) and, with torch's millions of live objects, pauses the host for 20-40 ms - longer than the work
@@ -253,11 +275,19 @@ def measure(vpc, args, rank, world, dev, scaling):
                 break
             prev = cur
         tr.timers, tr.timer_every = None, 8
+        for dst, src in zip((flat, tr.exp_avg, tr.exp_avg_sq), warm[:3]):
+            dst.copy_(src)
+        tr.step_count, tr.rng_offset, it[0] = warm[3:]
+        # the weight images follow the flat parameters: re-packed from the restored ones by the next step
+        model.invalidate_images()
+        if tr.prec:
+            tr._stale = {"pair": True, "step": True}
         sync()
+    del warm
     tr.epoch_total()  # reset the device-side loss accumulator: loss_mean below covers the timed steps only
-    # Inside the timed region only the dominant kernel is bracketed by HIP events (every 8th step); the other launches
-    # are sampled right after the region.
-    tr.timers, tr.timer_names = {}, {dom}
+    # Inside the timed region only the dominant kernel is bracketed by HIP events (every 8th step; every K-th when K < 8, so
+    # that a short region holds a sample too); with --full the other launches are sampled right after the region.
+    tr.timers, tr.timer_names, tr.timer_every = {}, {dom}, max(1, min(8, args.steps))
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -266,27 +296,34 @@ def measure(vpc, args, rank, world, dev, scaling):
     elapsed = time.perf_counter() - t0
     gc.enable()
     total = tr.epoch_total()  # one host read per "epoch", as train.py:118 (the timed steps only)
-    timers, tr.timers = tr.timers, {}
-    tr.timer_names, tr.timer_every = {"encoder_fwd", "encoder_bwd", "draw_step", "reduce_step"}, 2
-    for _ in range(16):
-        step()
-    sync()
-    timers.update(tr.timers)
-    tr.timers = None
-    # the reference reads the loss on the host every step (train.py:117 `.item()`): the same steps with that sync
-    n_sync = min(args.steps, 50)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(n_sync):
-        step()
-        tr.loss_value()
-    sync()
-    per_step_sync_ms = (time.perf_counter() - t1) / n_sync * 1e3
+    if dump_dir is not None and rank == 0:
+        dump_outputs(tr, model, dump_dir)
+    timers, tr.timers = tr.timers, None
+    per_step_sync_ms = None
+    if args.full:
+        tr.timers = {}
+        tr.timer_names, tr.timer_every = {"encoder_fwd", "encoder_bwd", "draw_step", "reduce_step"}, 2
+        for _ in range(16):
+            step()
+        sync()
+        timers.update(tr.timers)
+        tr.timers = None
+        # the reference reads the loss on the host every step (train.py:117 `.item()`): the same steps with that sync
+        n_sync = min(args.steps, 50)
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(n_sync):
+            step()
+            tr.loss_value()
+        sync()
+        per_step_sync_ms = (time.perf_counter() - t1) / n_sync * 1e3
     seen = ranks_seen(vpc, tr, world, dev)
     if world > 1:
-        t = torch.tensor([elapsed, per_step_sync_ms], device=dev, dtype=torch.float64)
+        t = torch.tensor([elapsed, per_step_sync_ms or 0.0], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed, per_step_sync_ms = float(t[0].item()), float(t[1].item())
+        elapsed = float(t[0].item())
+        if args.full:
+            per_step_sync_ms = float(t[1].item())
         torch.distributed.barrier()
     kern_ms = {k: statistics.mean(a.elapsed_time(b) for a, b in v) for k, v in timers.items()}
     return dict(B=B, Bg=Bg, elapsed=elapsed, per_step_sync_ms=per_step_sync_ms, total=total, settle=settle, kern_ms=kern_ms,
@@ -429,12 +466,18 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--latent", type=int, default=10)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
-                    help="which reading `value` reports; with more than one GPU both are measured and printed")
+                    help="which reading `value` reports; with more than one GPU and --full both are measured and printed")
     ap.add_argument("--precision", choices=["f32", "bf16x3", "bf16"], default="f32",
                     help="f32 = the headline (exact fp32 MFMA); bf16x3 / bf16 = extra lines on v_mfma_f32_16x16x32_bf16")
     ap.add_argument("--batches", type=int, default=8, help="distinct resident batches the loop rotates over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the configs 2 / 3 / 5 lines (extra_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the other launches' kernels_ms, per_step_sync_ms, the "
+                         "other scaling mode (N > 1), extra_configs and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra-configs", action="store_true",
+                    help="with --full: skip the configs 2 / 3 / 5 lines (extra_configs)")
     ap.add_argument("--no-settle", action="store_true", help="skip the settle steps after the W warm-up steps")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=None)
@@ -465,8 +508,9 @@ def main():
     torch.cuda.set_device(dev)
     d, Ld = args.dim, args.latent
 
-    modes = [args.scaling] if world == 1 else [args.scaling, "strong" if args.scaling == "weak" else "weak"]
-    res = {mode: measure(vpc, args, rank, world, dev, mode) for mode in modes}
+    modes = [args.scaling] if world == 1 or not args.full else [args.scaling, "strong" if args.scaling == "weak" else "weak"]
+    res = {mode: measure(vpc, args, rank, world, dev, mode, args.dump_outputs if mode == args.scaling else None)
+           for mode in modes}
     if rank != 0:
         vpc.dp.shutdown()
         return
@@ -506,17 +550,18 @@ def main():
             "compulsory_bytes_per_step": 768 * B})(measured_step_traffic(B, d, Ld, args.precision, dom)),
         "step_tflops_algorithmic": fl["total"] * B * world / (ms_step * 1e-3) / 1e12,
         "settle_steps": r["settle"],
-        "per_step_sync_ms": r["per_step_sync_ms"],
         "loss_mean": r["total"] / args.steps,
     }
-    for mode in modes[1:] if world > 1 else []:
+    if args.full:
+        out["per_step_sync_ms"] = r["per_step_sync_ms"]
+    for mode in modes[1:]:
         o = res[mode]
         out[mode] = {"value": o["value"], "unit": "samples/s", "ms_per_step": o["ms_step"], "rows_per_gpu": o["B"],
                      "global_batch": o["Bg"], "n_gpus": o["seen"], "kernels_ms": o["kern_ms"],
                      "small_batch_shape": o["small"]}
-    if world == 1 and not args.no_extra_configs:
+    if args.full and world == 1 and not args.no_extra_configs:
         out["extra_configs"] = extra_configs(vpc, dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(B, d, Ld, args.cpu_seconds, args.cpu_threads)
         out["cpu_baseline"] = cb
         out["speedup_vs_cpu"] = value / cb["value"]

@@ -11,9 +11,9 @@ for p in f32 bf16x3; do
   bash tools/pmc_r02.sh $p > $O/pmc_$p.log 2>&1
   for x in fetch write sq; do python3 tools/rocpd_pmc.py gpurun_out/pmc_${p}_$x 3 > $O/summary_${p}_$x.txt; done
 done
-python3 bench.py > $O/r02_bench_default.json 2> $O/bench_default.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/r02_bench_driverlike_w5_s20.json 2>> $O/bench_default.err
-for p in bf16x3 bf16; do python3 bench.py --no-cpu-baseline --precision $p > $O/r02_bench_$p.json 2>> $O/bench_default.err; done
+python3 bench.py --full > $O/r02_bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/r02_bench_driverlike_w5_s20.json 2>> $O/bench_default.err
+for p in bf16x3 bf16; do python3 bench.py --full --no-cpu-baseline --precision $p > $O/r02_bench_$p.json 2>> $O/bench_default.err; done
 python3 tools/bench_prec_small.py > $O/r02_small_prec.jsonl 2>> $O/bench_default.err
 python3 tools/bench_small.py --graph --steps 600 > $O/r02_small_batch_steps.jsonl 2>> $O/bench_default.err
 rm -rf gpurun_out/prof_* gpurun_out/pmc_*   # the rocpd databases are large; the summaries are what is kept
