@@ -641,3 +641,13 @@ def test_graph_replay_matches_eager_steps_d128(prec, tile, B, monkeypatch):
     assert all(not torch.equal(a, b) for a, b in zip(seen, seen[1:]))
     assert torch.equal(m1._flat, m2._flat)
     assert int(t2.state[0]) == 6  # steps done: one eager warm-up + five replays
+    # the model's own forward follows the replays: replay, forward, replay, forward - each equal to the eager model's
+    for i in range(2):
+        t1.step(xd, md, alpha=0.9, beta=0.8)
+        t2.step_graph(xd, md, alpha=0.9, beta=0.8)
+        outs = []
+        for m in (m1, m2):
+            torch.manual_seed(11)
+            with torch.no_grad():
+                outs.append(m.forward(xd, md, md))
+        assert all(torch.equal(a, b) for a, b in zip(*outs)), i

@@ -1,0 +1,185 @@
+"""The trainers' shared plumbing (trainer.py) and the one freshness rule of the packed weight images (images.py):
+the launch sequence of a steady-state step on every path, and the bf16 whole-step image following parameter writes made
+outside the trainer."""
+import weakref
+
+import pytest
+import torch
+
+import vpc_amd as vpc
+from vpc_amd import _lib
+from vpc_amd import eddi as ed
+from vpc_amd import notmiwae as nm
+
+pytestmark = pytest.mark.gpu
+
+
+def _data(B, d, seed, float_mask=False):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(B, d, generator=g)
+    m = torch.rand(B, d, generator=g) < 0.7
+    return x.cuda(), (m.float() if float_mask else m).cuda()
+
+
+def _fused(prec, B):
+    torch.manual_seed(0)
+    m = vpc.Reg_VAE(128, 500, 10, 10, {"batch_size": B, "patience": 1}, "exp", "kl_reg").cuda()
+    tr = vpc.FusedTrainer(m, seed=3, precision=prec)
+    x, mk = _data(B, 128, 4)
+    return lambda: tr.step(x, mk, alpha=0.9, beta=0.8)
+
+
+def _nm(prec):
+    torch.manual_seed(12)
+    m = nm.REG_notMIWAE_v2(128, 128, 10, 10, {"batch_size": 96, "patience": 1}, 20, 1).cuda()
+    tr = nm.NMTrainer(m, lr=1e-3, seed=5, precision=prec)
+    x, mk = _data(96, 128, 5, float_mask=True)
+    return lambda: tr.step(x, mk, alpha=0.5, p_missingness=50)
+
+
+def _eddi():
+    torch.manual_seed(3)
+    m = ed.Reg_EDDI(100, 500, 20, 10, {"batch_size": 256, "patience": 1}, "exp", "kl_reg").cuda()
+    tr = ed.EDDITrainer(m, seed=9)
+    x, mk = _data(256, 100, 6)
+    return lambda: tr.step(x, mk, alpha=0.5, p_missingness=30)
+
+
+def _wide():
+    torch.manual_seed(7)
+    m = vpc.Reg_VAE(200, 500, 10, 10, {"batch_size": 96, "patience": 1}, "exp", "kl_reg").cuda()
+    tr = vpc.WideTrainer(m, seed=2)
+    x, mk = _data(96, 200, 8)
+    return lambda: tr.step(x, mk, alpha=0.8, beta=0.9)
+
+
+_SMALL = ["vpc_step_small_max_rows"]
+_FUSED3 = ["vpc_draw_step", "vpc_encoder_fwd", "vpc_decoder_fused", "vpc_encoder_bwd"]
+_GEMM_BWD = ["vpc_linear_wgrad", "vpc_linear_dgrad"] * 3
+_WIDE_FWD = ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"] + ["vpc_linear_fwd"] * 3
+_SWD = ["vpc_linear_wgrad_scratch", "vpc_linear_wgrad", "vpc_linear_dgrad"]
+_WIDE_BWD = _SWD * 3 + ["vpc_nm_sample_bwd"] + _SWD * 2 + _SWD[:2]  # decoder, rsample, encoder of one pass
+# (path, VPC_TILE, step factory, the vpc_* symbols the 3rd step fetches in order: launches and the host-side queries)
+LAUNCHES = [
+    ("fused_f32_b64", None, lambda: _fused("f32", 64),
+     _SMALL + ["vpc_step_small_draw_f32", "vpc_reduce_step_adam"]),
+    ("fused_f32_tile128_b300", "128", lambda: _fused("f32", 300),
+     _SMALL + _FUSED3 + ["vpc_reduce_step_adam"]),
+    ("fused_bf16_pair_tile64_b300", "64", lambda: _fused("bf16", 300),
+     _SMALL + ["vpc_step_fused_applicable", "vpc_pack_weights_bf16"] + _FUSED3 + ["vpc_reduce_step_adam"]),
+    ("fused_bf16_step_tile128_b300", "128", lambda: _fused("bf16", 300),
+     _SMALL + ["vpc_step_fused_applicable", "vpc_draw_step", "vpc_step_workspace_floats", "vpc_step_fused_bf16",
+               "vpc_reduce_step_adam_bf16c"]),
+    ("nm_bf16_fused_tail", None, lambda: _nm("bf16"),
+     ["vpc_nm_prep", "vpc_nmenc_fwd", "vpc_nm_fused_bwd_step"]),
+    ("nm_f32_gemm", None, lambda: _nm("f32"),
+     ["vpc_nm_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_loss"] + _GEMM_BWD +
+     ["vpc_nm_sample_bwd"] + _GEMM_BWD[:-1] + ["vpc_linear_wgrad_reduce", "vpc_adam_step"]),
+    ("eddi", None, _eddi,
+     ["vpc_pack_weights", "vpc_draw_step", "vpc_eddi_fold", "vpc_eddi_front_fwd"] + ["vpc_linear_fwd"] * 3 +
+     ["vpc_decoder_fused", "vpc_reduce_partials", "vpc_loss_finalize"] + _GEMM_BWD +
+     ["vpc_linear_wgrad_reduce", "vpc_eddi_front_scratch", "vpc_eddi_front_bwd", "vpc_adam_step"]),
+    ("wide", None, _wide,
+     ["vpc_draw_mask", "vpc_fill_normal"] + _WIDE_FWD * 2 + ["vpc_loss_fwd_bwd", "vpc_loss_finalize"] + _WIDE_BWD * 2 +
+     ["vpc_adam_step"]),
+]
+
+
+class _Recorder:
+    """Stands in for the loaded library: records every vpc_* symbol fetched, hands out the real one."""
+
+    def __init__(self, real):
+        self.real, self.names = real, []
+
+    def __getattr__(self, name):
+        if name.startswith("vpc_"):
+            self.names.append(name)
+        return getattr(self.real, name)
+
+
+@pytest.mark.parametrize("path,tile,make,expected", LAUNCHES, ids=[p[0] for p in LAUNCHES])
+def test_steady_state_launch_sequence(path, tile, make, expected, monkeypatch):
+    """A steady-state step issues the same launches as before the trainers shared one base class, on every path.  The
+    EDDI step re-packs the decoder image lazily at its start (the previous step's Adam left it stale)."""
+    if tile:
+        monkeypatch.setenv("VPC_TILE", tile)
+    else:
+        monkeypatch.delenv("VPC_TILE", raising=False)
+    step = make()
+    step()
+    step()
+    rec = _Recorder(_lib.lib())
+    monkeypatch.setattr(_lib, "_lib", rec)
+    step()
+    monkeypatch.undo()
+    assert rec.names == expected
+
+
+def _reg_vae(B):
+    return vpc.Reg_VAE(128, 500, 10, 10, {"batch_size": B, "patience": 1}, "exp", "kl_reg").cuda()
+
+
+@pytest.mark.parametrize("write", ["torch", "data", "load_state_dict"])
+def test_fused_bf16_whole_step_follows_outside_writes(write, monkeypatch):
+    """FusedTrainer(precision="bf16") on the whole-step kernel: a parameter write between steps reaches the compact bf16
+    image - through the version counters (`p.mul_()` under no_grad, load_state_dict) or through invalidate_image() (a
+    `.data` write).  The steps that follow are bit-equal to those of a fresh trainer built on the written weights with
+    the same optimiser state."""
+    monkeypatch.setenv("VPC_TILE", "128")
+    B = 300
+    x, mk = _data(B, 128, 4)
+    kw = dict(alpha=0.9, beta=0.8)
+    torch.manual_seed(0)
+    m = _reg_vae(B)
+    tr = vpc.FusedTrainer(m, seed=3, precision="bf16")
+    for _ in range(3):
+        tr.step(x, mk, **kw)
+    assert tr._used_step_fused
+    before = m._flat.clone()
+    if write == "torch":
+        with torch.no_grad():
+            m.seq_decoder[2].weight.mul_(0.5)
+    elif write == "data":
+        m.seq_encoder[0].weight.data.mul_(0.5)
+        tr.invalidate_image()
+    else:
+        sd = m.state_dict()
+        sd["seq_decoder.4.weight"] = sd["seq_decoder.4.weight"] * 0.5
+        m.load_state_dict(sd)
+    assert not torch.equal(before, m._flat)
+    m2 = _reg_vae(B)
+    m2.load_state_dict(m.state_dict())
+    tr2 = vpc.FusedTrainer(m2, seed=3, precision="bf16")
+    tr2.exp_avg.copy_(tr.exp_avg)
+    tr2.exp_avg_sq.copy_(tr.exp_avg_sq)
+    tr2.step_count, tr2.rng_offset = tr.step_count, tr.rng_offset
+    for i in range(3):
+        tr.step(x, mk, **kw)
+        tr2.step(x, mk, **kw)
+        assert tr.loss_value() == tr2.loss_value(), (write, i)
+    assert torch.equal(m._flat, m2._flat)
+    assert torch.equal(tr.exp_avg_sq, tr2.exp_avg_sq)
+
+
+def test_trainers_are_freed_by_reference_count(monkeypatch):
+    """No trainer sits in a reference cycle (the images' pack functions hold none): one that holds a captured graph goes
+    when its last reference does, not in a garbage collection that may run while another graph is being captured."""
+    monkeypatch.setenv("VPC_TILE", "128")
+    x, mk = _data(300, 128, 4)
+    for prec in ("f32", "bf16"):
+        tr = vpc.FusedTrainer(_reg_vae(300), seed=3, precision=prec)
+        for _ in range(2):
+            tr.step_graph(x, mk)
+        ref = weakref.ref(tr)
+        del tr
+        assert ref() is None, prec
+    xf, mf = _data(96, 128, 5, float_mask=True)
+    for prec in ("f32", "bf16"):
+        tr = nm.NMTrainer(nm.REG_notMIWAE_v2(128, 128, 10, 10, {"batch_size": 96, "patience": 1}, 20, 1).cuda(),
+                          precision=prec)
+        tr.step(xf, mf)
+        for _ in range(2):
+            tr.step_graph(xf, mf)
+        ref = weakref.ref(tr)
+        del tr
+        assert ref() is None, prec

@@ -50,11 +50,11 @@ def shard_rows(n_rows: int, rank: int, world: int):
 
 
 def broadcast_parameters(flat: torch.Tensor, src=0, group=None, model=None):
-    """Make every replica start from rank `src`'s weights.  Pass `model` so that its packed weight images are
-    re-packed on the next forward (the flat buffer is written behind the parameters' backs)."""
+    """Make every replica start from rank `src`'s weights.  Pass `model` so that its packed weight images (its trainers'
+    included) are re-packed before their next use (the flat buffer is written behind the parameters' backs)."""
     if dist.is_initialized() and dist.get_world_size(group) > 1:
         dist.broadcast(flat, src=src, group=group)
-    if model is not None and hasattr(model, "invalidate_images"):
+    if model is not None:
         model.invalidate_images()
 
 

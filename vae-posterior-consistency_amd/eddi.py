@@ -18,9 +18,12 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .fused import loss_coefficients
+from .images import PackedImage
 from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .notmiwae import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad, nm_sample, nm_sample_bwd, wgrad_reduce
 from .ops import as_mask_u8
+from .trainer import _FlatAdamTrainer
 
 H1, H2 = 100, 50  # VAE.py:694-698 hard-codes 100 / 50
 
@@ -127,7 +130,6 @@ class _EDDIBase:
         self.max_epoch = MAX_EPOCH
         self._layout = None
         self._img = None
-        self._img_version = None
         self._part = {}
 
     # flat order: [pnp_encoder2 (6) | seq_decoder (6) | type_pars1, type_bias1, pnp_encoder1 (2)] - the decoder sits at
@@ -140,25 +142,14 @@ class _EDDIBase:
             out += [mod.weight, mod.bias]
         return out + [self.type_pars1, self.type_bias1, self.pnp_encoder1[0].weight, self.pnp_encoder1[0].bias]
 
-    def _versions(self):
-        return tuple(p._version for p in self.trainable()) + (self.seq_decoder[0].weight.data_ptr(),)
-
-    def _images(self):
+    def _new_image(self, device):
         """Only the DECODER half of the packed image is used (the encoder is the front-end + GEMM trunk)."""
         lay = self._lay()
-        flat = self.flatten_parameters()
-        L.require_cuda(flat)
-        v = self._versions()
-        if self._img is None or self._img.device != flat.device:
-            self._img = torch.from_numpy(lay.img_template).to(flat.device)
-            self._img_version = None
-        if self._img_version != v:
-            pidx, _ = lay.device_tables(flat.device)
-            n_trunk = sum(p.numel() for p in self.trainable()[:6])
-            n_dec = lay.n_params - lay.n_enc
-            ops.pack_weights(flat[n_trunk:n_trunk + n_dec], pidx[lay.n_enc:], self._img)
-            self._img_version = v
-        return self._img
+        pidx = lay.device_tables(device)[0][lay.n_enc:]
+        lo = sum(p.numel() for p in self.trainable()[:6])
+        hi = lo + lay.n_params - lay.n_enc
+        return PackedImage(torch.from_numpy(lay.img_template).to(device),
+                           lambda flat, buf: ops.pack_weights(flat[lo:hi], pidx, buf))
 
     def decoder(self, z_int):
         """VAE.py:743-747: the Reg_VAE decoder kernels on this class's seq_decoder (trainable()[6:12])."""
@@ -218,48 +209,31 @@ class vanilla_EDDI(_EDDIBase, vanilla_VAE):
 LP = 16  # row pitch of the padded latent workspaces of the fused decoder kernel
 
 
-class EDDITrainer:
+class EDDITrainer(_FlatAdamTrainer):
     """The EDDI training step (train.py:28-117 for 'reg_EDDI*' / 'vanilla_EDDI*') as a fixed launch sequence without
-    host synchronisation: mask_p + eps draws -> fold -> front-end (both passes) -> pnp_encoder2 GEMMs on the stacked
-    passes -> the SAME fused decoder + loss + decoder-backward kernel as the VAE step (nothing of size B x d is
-    materialised) -> trunk backward GEMMs -> front-end backward -> [one all-reduce of [grads | loss terms]] -> flat
-    Adam + decoder image re-pack."""
+    host synchronisation: [decoder image re-pack] -> mask_p + eps draws -> fold -> front-end (both passes) ->
+    pnp_encoder2 GEMMs on the stacked passes -> the SAME fused decoder + loss + decoder-backward kernel as the VAE step
+    (nothing of size B x d is materialised) -> trunk backward GEMMs -> front-end backward -> [one all-reduce of
+    [grads | loss terms]] -> flat Adam."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
         if not isinstance(model, _EDDIBase):
             raise TypeError("EDDITrainer supports Reg_EDDI and vanilla_EDDI")
-        from .fused import FusedTrainer
-        self.model = model
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 9)
         self.vanilla = isinstance(model, vanilla_VAE)
-        self.coefficients = lambda *a: FusedTrainer.coefficients(self, *a)
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.seed, self.rng_offset, self.step_count = seed, 0, 0
-        self.pg, self.world_size, self.rank = process_group, world_size, rank
         self.lay = model._lay()
-        flat = model.flatten_parameters()
-        L.require_cuda(flat)
-        self.dev = flat.device
-        n = flat.numel()
-        self.bucket = torch.zeros(n + 9, device=self.dev)
-        self.grad, self.out9 = self.bucket[:n], self.bucket[n:]
-        self.exp_avg = torch.zeros(n, device=self.dev)
-        self.exp_avg_sq = torch.zeros(n, device=self.dev)
-        self.accum = torch.zeros(1, device=self.dev)
+        self.out9 = self.tail
         ncu = L.max_blocks()  # partial blocks any kernel may write
         self.partD = torch.empty(ncu * self.lay.dec_part, device=self.dev)
         self.loss_part = torch.empty(ncu, 8, dtype=torch.float64, device=self.dev)
-        self.pidx, self.gidx = self.lay.device_tables(self.dev)
-        # gradient views in flat order: trunk (6) | decoder (6) | front-end (4)
-        self.g, off = [], 0
-        for p in model.trainable():
-            v = self.grad[off:off + p.numel()].view_as(p)
-            p.grad = v
-            self.g.append(v)
-            off += p.numel()
-        self.n_trunk = sum(p.numel() for p in model.trainable()[:6])
+        _, self.gidx = self.lay.device_tables(self.dev)
+        self.g = [p.grad for p in self._plist]  # gradient views in flat order: trunk (6) | decoder (6) | front-end (4)
+        self.n_trunk = sum(p.numel() for p in self._plist[:6])
         self.n_dec = self.lay.n_params - self.lay.n_enc
         self._B = None
-        self._flat_dec = None
+
+    def coefficients(self, epoch, alpha, beta, beta_annealing):
+        return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
 
     def _ws(self, B):
         if self._B == B:
@@ -287,8 +261,7 @@ class EDDITrainer:
                         eps=[self.eps_buf[p_] for p_ in range(3)], lat_dst=self.lat[..., :Ld],
                         heads_src=self.heads.view(P, B, 2, Ld).permute(0, 2, 1, 3), dheads_dst=self.dheads.view(P, B, 2, Ld),
                         dlat_src=self.dlat[..., :Ld].permute(0, 2, 1, 3),
-                        gdec=self.grad[self.n_trunk:self.n_trunk + self.n_dec], gidx_dec=self.gidx[self.lay.n_enc:],
-                        pidx_dec=self.pidx[self.lay.n_enc:])
+                        gdec=self.grad[self.n_trunk:self.n_trunk + self.n_dec], gidx_dec=self.gidx[self.lay.n_enc:])
         self._B = B
 
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=0.5, beta=1.0,
@@ -304,10 +277,10 @@ class EDDITrainer:
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
         two = not self.vanilla
         P = 2 if two else 1
-        t = m.trainable()
+        t = self._plist
         W1, b1, W2, b2, W3, b3 = t[:6]
         E, tb, Wp, cp = t[12:]
-        dec_img = m._dec_img()
+        dec_img = m._images(m._param_key(t))[lay.enc_img:]  # re-packed after the previous step's Adam
         # ---- draws
         need_ml = two and co["wml"] != 0.0
         eps_view = self.eps_buf[: (3 if need_ml else 2 if two else 1)]
@@ -373,27 +346,10 @@ class EDDITrainer:
                       (sc[2], R, H1, K, g[0], g[1], False)], self._wg_cache)
         eddi_front_bwd(x, masks[0], self.AC, self.dagg, E, tb, Wp, g[12], g[13], g[14], g[15], B, d, K,
                        mask2_u8=masks[1] if two else None, scratch=self.front_scratch)
-        if self.world_size > 1:  # ONE collective per step: RCCL on the compute stream, or torch.distributed (dist.py)
-            from . import dist as dp_mod
-            if not getattr(self, "_coll_ready", False):
-                self.collective = dp_mod.make_collective(self.world_size, self.rank, self.dev, self.pg)
-                self._coll_ready = True
-            dp_mod.allreduce_bucket(self.bucket, self.pg, self.collective)
+        if self.world_size > 1:
+            self._allreduce()
         self.step_count += 1
         dp = self.world_size > 1  # the Adam launch also adds the all-reduced loss to the epoch accumulator
         ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.eps, loss_in=self.out9 if dp else None, accum=self.accum if dp else None)
-        # keep the packed decoder image in step with the parameters (the version check would re-pack it anyway)
-        if self._flat_dec is None or self._flat_dec[0] is not m._flat:
-            self._flat_dec = (m._flat, m._flat[self.n_trunk:self.n_trunk + self.n_dec])
-        ops.pack_weights(self._flat_dec[1], sl["pidx_dec"], m._img)
-        m._img_version = m._versions()
-
-    def loss_value(self) -> float:
-        return float(self.out9[0].item())
-
-    def epoch_total(self, reset=True) -> float:
-        v = float(self.accum.item())
-        if reset:
-            self.accum.zero_()
-        return v
+                      self.betas[1], self.adam_eps, loss_in=self.out9 if dp else None, accum=self.accum if dp else None)
+        self._flat_written(None)

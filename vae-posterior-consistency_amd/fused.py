@@ -27,18 +27,38 @@ import torch
 from . import _lib as L
 from . import dist as dp_mod
 from . import ops
+from .images import PackedImage
 from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .ops import H1P, H2P, as_mask_u8
+from .trainer import _FlatAdamTrainer
 
 LP = 16  # row pitch of the padded latent workspaces
 
 
-class FusedTrainer:
+def loss_coefficients(model, epoch, alpha, beta, beta_annealing):
+    """Loss coefficients of the generic form in csrc/vpc_dec.hip (VAE.py:425-446 / 1183-1195)."""
+    bw = (epoch / MAX_EPOCH) * beta if beta_annealing else beta
+    if isinstance(model, vanilla_VAE):
+        return dict(cA=[1.0], cE=[0.0], bq=bw, bp=0.0, cr=0.0, wml=0.0)
+    rt = model.reg_type
+    if rt == "kl_reg":
+        return dict(cA=[1.0 - alpha, alpha], cE=[alpha, 0.0], bq=(1.0 - alpha) * bw, bp=alpha * bw, cr=alpha, wml=0.0)
+    if rt == "ml_reg":
+        return dict(cA=[1.0, 0.0], cE=[0.0, 0.0], bq=bw, bp=0.0, cr=0.0, wml=(epoch / MAX_EPOCH) * alpha)
+    print("Not implemented!")  # VAE.py:447-449
+    raise NotImplementedError(f"reg_type {rt!r}")
+
+
+class FusedTrainer(_FlatAdamTrainer):
+    timer_every = 8  # an event pair costs ~5 us of GPU idle time per kernel: bench.py brackets every 8th step only
+
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0,
                  precision="f32", collective=None):
         """precision: "f32" (v_mfma_f32_16x16x4_f32, the parity path), "bf16x3" (split-bf16 products on
         v_mfma_f32_16x16x32_bf16: fp32-class accuracy) or "bf16" (plain bf16 inputs, fp32 accumulation and loss math);
         the bf16 forms exist for Reg_VAE / vanilla_VAE with obs_dim % 4 == 0, both workgroup shapes (csrc/vpc_bf16.h).
+        `precision` bounds the rounding a step may use; it does not choose the kernel: small batches run the fp32
+        N-split kernel in every precision.
         collective: carrier of the per-step bucket under data parallelism (dist.FlatAllReduce = ncclAllReduce on the
         compute stream); None = chosen on the first multi-rank step by dist.make_collective (RCCL when the process group
         is NCCL, torch.distributed.all_reduce otherwise)."""
@@ -47,49 +67,32 @@ class FusedTrainer:
         if getattr(model, "_wide", False):
             raise L.VpcError("FusedTrainer covers encoder inputs <= 128 wide and latent_dim <= 15; use wide.WideTrainer "
                              "(harness.train does) for wider models")
-        self.model = model
+        if precision not in ops.PRECISIONS:
+            raise ValueError(f"precision {precision!r}: expected one of {sorted(ops.PRECISIONS)}")
+        # data parallel: this rank's rows are [rank * B, (rank + 1) * B) of the global batch by default
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 9, collective)
         self.vanilla = isinstance(model, vanilla_VAE)
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.seed = seed
-        self.rng_offset = 0
-        self.step_count = 0
-        self.pg = process_group
-        self.world_size = world_size
-        self.rank = rank  # data parallel: this rank's rows are [rank * B, (rank + 1) * B) of the global batch by default
-        self.collective = collective
-        self._coll_ready = collective is not None
         # the data-parallel tail (reduce_step -> all-reduce -> adam_step) instead of the single fused launch
         self.dp = world_size > 1 or collective is not None
         self.lay = model._lay()
-        flat = model.flatten_parameters()
-        L.require_cuda(flat)
-        self.dev = flat.device
-        if precision not in ops.PRECISIONS:
-            raise ValueError(f"precision {precision!r}: expected one of {sorted(ops.PRECISIONS)}")
         self.precision = precision
         self.prec = ops.PRECISIONS[precision]
         if self.prec:
             lay = self.lay
             if lay.mask_augm or lay.d % 4:
                 raise L.VpcError("the bf16 / bf16x3 kernels cover the plain encoder with obs_dim % 4 == 0 (<= 128)")
-            self.pidx_bf, tmpl, self.enc_img_bf = lay.bf16_tables(self.dev)
-            self.img_bf = torch.from_numpy(tmpl).to(self.dev)
+            pidx_bf, tmpl, self.enc_img_bf = lay.bf16_tables(self.dev)
+            # bf16 images, packed lazily from the flat parameters under the model's parameter key (images.py)
+            self._pair = PackedImage(torch.from_numpy(tmpl).to(self.dev),
+                                     lambda flat, buf: ops.pack_weights_bf16(flat, pidx_bf, buf))
             # plain bf16, obs_dim in (64, 128]: the whole-step kernel (csrc/vpc_step.hip) with its own compact image
             self._step_ok = self.prec == 2 and 64 < lay.d <= 128
             if self._step_ok:
-                self.pidx_c, tmpl_c = lay.step_tables(self.dev)
-                self.img_c = torch.from_numpy(tmpl_c).to(self.dev)
-            # the bf16 images follow the flat parameters lazily: an optimiser step marks them stale, the next launch that
-            # needs one re-packs it (one pack launch per step while the batch shape does not change)
-            self._stale = {"pair": True, "step": True}
-        n = self.lay.n_params
-        # one flat bucket: [grads (n) | loss terms (9 floats)] -> a single all-reduce per step under DP
-        self.bucket = torch.zeros(n + 9, device=self.dev)
-        self.grad = self.bucket[:n]
-        self.out9 = self.bucket[n:]
-        self.exp_avg = torch.zeros(n, device=self.dev)
-        self.exp_avg_sq = torch.zeros(n, device=self.dev)
-        self.accum = torch.zeros(1, device=self.dev)
+                pidx_c, tmpl_c = lay.step_tables(self.dev)
+                self.pidx_c = pidx_c  # (the pack functions hold no reference to the trainer: no cycle, freed by refcount)
+                self._whole = PackedImage(torch.from_numpy(tmpl_c).to(self.dev),
+                                          lambda flat, buf: ops.step_pack_weights_bf16(flat, pidx_c, buf))
+        self.out9 = self.tail  # the loss terms of the step
         ncu = L.max_blocks()  # partial blocks any kernel may write (2 x CUs: small-batch shape)
         self.partE = torch.empty(ncu * self.lay.enc_part, device=self.dev)
         self.partD = torch.empty(ncu * self.lay.dec_part, device=self.dev)
@@ -98,15 +101,10 @@ class FusedTrainer:
         self.inv = self.lay.inverse_maps(self.dev)  # caller-owned maps for the layout-order gradient reduction
         self._ws_B = None
         self._pads = {}
-        self.timers = None  # bench.py sets this to {} to collect per-kernel HIP event pairs
-        self.timer_every = 8  # ... on every 8th step only: an event pair costs ~5 us of GPU idle time per kernel
-        self._timer_tick = 0
-        self.timer_names = None  # restrict the event pairs to these launches (None = all)
-        # make trainable tensors' .grad views of the flat gradient, so state is inspectable like torch's
-        off = 0
-        for p in model.trainable():
-            p.grad = self.grad[off:off + p.numel()].view_as(p)
-            off += p.numel()
+
+    def invalidate_image(self):
+        """Alias of model.invalidate_images(): after writing parameters behind torch's version counters."""
+        self.model.invalidate_images()
 
     # ------------------------------------------------------------------
     def _pad_cols(self, t, dk, slot):
@@ -141,18 +139,6 @@ class FusedTrainer:
             self._ws_step = torch.empty(n, device=self.dev)
         return self._ws_step
 
-    def _timed(self, name, fn, *args):
-        """Run one launch; with timers enabled bracket it with events on the launch stream."""
-        if self.timers is None or self._timer_tick % self.timer_every or \
-                (self.timer_names is not None and name not in self.timer_names):
-            return fn(*args)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*args)
-        e1.record()
-        self.timers.setdefault(name, []).append((e0, e1))
-        return r
-
     def dominant_launch(self):
         """Name (as in `timers`) of the launch that carries most of the step's FLOPs in the shape last stepped."""
         if getattr(self, "_used_step_small", False):
@@ -160,18 +146,7 @@ class FusedTrainer:
         return "step_fused" if getattr(self, "_used_step_fused", False) else "decoder_fused"
 
     def coefficients(self, epoch, alpha, beta, beta_annealing):
-        """Loss coefficients of the generic form in csrc/vpc_dec.hip (VAE.py:425-446 / 1183-1195)."""
-        bw = (epoch / MAX_EPOCH) * beta if beta_annealing else beta
-        if self.vanilla:
-            return dict(cA=[1.0], cE=[0.0], bq=bw, bp=0.0, cr=0.0, wml=0.0)
-        rt = self.model.reg_type
-        if rt == "kl_reg":
-            return dict(cA=[1.0 - alpha, alpha], cE=[alpha, 0.0], bq=(1.0 - alpha) * bw, bp=alpha * bw, cr=alpha,
-                        wml=0.0)
-        if rt == "ml_reg":
-            return dict(cA=[1.0, 0.0], cE=[0.0, 0.0], bq=bw, bp=0.0, cr=0.0, wml=(epoch / MAX_EPOCH) * alpha)
-        print("Not implemented!")  # VAE.py:447-449
-        raise NotImplementedError(f"reg_type {rt!r}")
+        return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
 
     # ------------------------------------------------------------------
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=1.0, beta=1.0,
@@ -213,19 +188,16 @@ class FusedTrainer:
         self._used_step_small = use_small
         use_step = (not use_small) and bool(self.prec) and self._step_ok and ops.step_fused_applicable(B, dk, Ld, 2 if two else 1)
         self._used_step_fused = use_step
-        # the model's fp32 images (what the fp32 kernels read and the Adam launches re-pack); the whole-step bf16 kernel has its
-        # own image and leaves these stale (invalidate_images below), so it must not ask for them every step
-        img = None if use_step else m._images()
+        # every image is checked against ONE parameter key per step (images.py).  The model's fp32 images are what the fp32
+        # kernels read and the Adam launches re-pack; the whole-step bf16 kernel has its own image and leaves them stale
+        key = m._param_key(self._plist)
+        img = None if use_step else m._images(key)
         enc_img, dec_img = (None, None) if use_step else (img[:lay.enc_img], img[lay.enc_img:])
-        if self.prec and not use_small:  # bf16 images, re-packed from the flat parameters after an optimiser step (lazily, see __init__)
-            enc_img, dec_img = self.img_bf[:self.enc_img_bf], self.img_bf[self.enc_img_bf:]
-            kind = "step" if use_step else "pair"
-            if self._stale[kind]:
-                if use_step:
-                    ops.step_pack_weights_bf16(m._flat, self.pidx_c, self.img_c)
-                else:
-                    ops.pack_weights_bf16(m._flat, self.pidx_bf, self.img_bf)
-                self._stale[kind] = False
+        if use_step:
+            img_c = self._whole.get(key, m._flat)
+        elif self.prec and not use_small:
+            img_bf = self._pair.get(key, m._flat)
+            enc_img, dec_img = img_bf[:self.enc_img_bf], img_bf[self.enc_img_bf:]
         rng0 = self.rng_offset
         # ---- random draws (mask_p and eps in ONE launch when both are drawn on the device)
         need_ml = two and co["wml"] != 0.0
@@ -289,7 +261,7 @@ class FusedTrainer:
                                         self.partE, self.partD, self.loss_part, dk, Ld)
         elif use_step:
             # ---- plain bf16, throughput shape: encoder forward + decoder + loss + all backward in ONE launch
-            nbE = nbD = self._timed("step_fused", ops.step_fused_bf16, x, self.img_c, masks, maskB, co["cA"], co["cE"], epss,
+            nbE = nbD = self._timed("step_fused", ops.step_fused_bf16, x, img_c, masks, maskB, co["cA"], co["cE"], epss,
                                     eml, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value, self.partE,
                                     self.partD, self.loss_part, self._step_ws(B), dk, Ld)
         else:
@@ -306,24 +278,15 @@ class FusedTrainer:
         self.last_blocks = (nbE, nbD)
         if update and not self.dp and _state is None:
             self.step_count += 1
-            if use_step:
-                # the fused Adam re-packs the whole-step kernel's compact bf16 image itself (no pack launch); the model's fp32
-                # images and the pair-slot bf16 image go stale and are re-packed by whoever needs them next
-                self._timed("reduce_step", ops.reduce_step_adam, self.partE, nbE, lay.enc_part, self.partD, nbD,
-                            lay.dec_part, self.gidx, self.grad, lay.n_enc, self.loss_part, nbD, co["cA"][0], co["cE"][0],
-                            cA1, co["bq"], co["bp"], co["cr"], co["wml"], B, Bg, d, self.out9, self.accum, m._flat,
-                            self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                            self.step_count, self.pidx_c, self.img_c, self.inv, True)
-                m.invalidate_images()
-                self._stale = {"pair": True, "step": False}
-                return
+            # the fused Adam re-packs the image the step read: the whole-step kernel's compact bf16 image, else the model's
+            # fp32 images (the pair-slot bf16 image goes stale and is re-packed by whoever needs it next)
             self._timed("reduce_step", ops.reduce_step_adam, self.partE, nbE, lay.enc_part, self.partD, nbD,
                         lay.dec_part, self.gidx, self.grad, lay.n_enc, self.loss_part, nbD, co["cA"][0], co["cE"][0],
                         cA1, co["bq"], co["bp"], co["cr"], co["wml"], B, Bg, d, self.out9, self.accum, m._flat,
-                        self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                        self.step_count, self.pidx, img, self.inv)
-            if self.prec:
-                self._stale = {"pair": True, "step": True}
+                        self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.adam_eps,
+                        self.step_count, self.pidx_c if use_step else self.pidx, img_c if use_step else img, self.inv,
+                        use_step)
+            self._flat_written(key, self._whole if use_step else m._img)
             return
         ops.reduce_step(self.partE, nbE, lay.enc_part, self.partD, nbD, lay.dec_part,
                     self.gidx, self.grad, lay.n_enc, self.loss_part, nbD, co["cA"][0], co["cE"][0], cA1, co["bq"],
@@ -335,19 +298,19 @@ class FusedTrainer:
         if update:
             self.step_count += 1
             # under data parallelism the Adam launch also adds the all-reduced loss to the epoch accumulator
-            if use_step:
-                m.invalidate_images()
             ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count,
-                        self.lr, self.betas[0], self.betas[1], self.eps, None if use_step else self.pidx, img,
+                        self.lr, self.betas[0], self.betas[1], self.adam_eps, None if use_step else self.pidx, img,
                         None if _state is None else _state[0:1],
                         loss_in=self.out9 if self.dp else None, accum=self.accum if self.dp else None)
-            if self.prec:
-                self._stale = {"pair": True, "step": True}
-            if use_step and _state is not None:
+            if not use_step:
+                self._flat_written(key, m._img)
+            elif _state is not None:
                 # graph capture: the lazy re-pack at the start of the next eager step is not part of a replay - the compact
                 # image of the whole-step kernel is re-packed here, inside the captured sequence
-                ops.step_pack_weights_bf16(m._flat, self.pidx_c, self.img_c)
-                self._stale["step"] = False
+                self._whole.pack(m._flat, img_c)
+                self._flat_written(key, self._whole)
+            else:
+                self._flat_written(key)
         elif self.dp:
             self.accum += self.out9[0]
 
@@ -369,49 +332,4 @@ class FusedTrainer:
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
         key = (tuple(x.shape), p_missingness, tuple(co["cA"]), tuple(co["cE"]), co["bq"], co["bp"], co["cr"], co["wml"])
         kw = dict(epoch=epoch, alpha=alpha, beta=beta, beta_annealing=beta_annealing, p_missingness=p_missingness)
-        if getattr(self, "_graph_key", None) != key:
-            self.step(x, mask, **kw)  # eager warm-up: also sets the LDS attributes, workspaces, packed image
-            self._gx, self._gmask = x.clone(), mask.clone()
-            self.state = torch.tensor([self.step_count, 0], dtype=torch.int64, device=self.dev)
-            timers, self.timers = self.timers, None
-            base_rng, base_step = self.rng_offset, self.step_count
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step(self._gx, self._gmask, _state=self.state, **kw)
-            self._graph_rng_inc = self.rng_offset - base_rng
-            self.rng_offset, self.step_count = base_rng, base_step  # capture executed nothing
-            self._timer_tick -= 1
-            self.timers = timers
-            self._graph, self._graph_key = g, key
-            return
-        if x.data_ptr() != self._gx.data_ptr():
-            self._gx.copy_(x)
-        if mask.data_ptr() != self._gmask.data_ptr():
-            self._gmask.copy_(mask)
-        self._graph.replay()
-        self.step_count += 1
-        self.rng_offset += self._graph_rng_inc
-
-    def _collective(self):
-        if not self._coll_ready:
-            self.collective = dp_mod.make_collective(self.world_size, self.rank, self.dev, self.pg)
-            self._coll_ready = True
-        return self.collective
-
-    def _allreduce(self):
-        """ONE collective per step over the flat bucket [grads | loss terms]: ncclAllReduce (RCCL over xGMI) on the
-        compute stream when the process group is NCCL, torch.distributed.all_reduce otherwise (dist.py).  Every term
-        is already normalised by the GLOBAL batch, so a plain SUM is the result of the concatenated batch."""
-        dp_mod.allreduce_bucket(self.bucket, self.pg, self._collective())
-
-    def loss_value(self) -> float:
-        """Loss of the last step (host sync)."""
-        return float(self.out9[0].item())
-
-    def epoch_total(self, reset=True) -> float:
-        """Sum of train_loss over the steps since the last reset (train.py:117-118; one host sync per epoch)."""
-        v = float(self.accum.item())
-        if reset:
-            self.accum.zero_()
-        return v
+        self._graph_step(key, (x, mask), lambda *a, **k: self.step(*a, **kw, **k))

@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .images import PackedImage, ParamKeyMixin
 from .ops import DecoderFn, EncoderFn, LossFn, as_mask_u8
 
 MAX_EPOCH = 2800  # VAE.py:384
@@ -33,7 +34,7 @@ _ENC = ("seq_encoder.0", "seq_encoder.2", "seq_encoder.4")
 _DEC = ("seq_decoder.0", "seq_decoder.2", "seq_decoder.4")
 
 
-class _VAEBase(nn.Module):
+class _VAEBase(ParamKeyMixin, nn.Module):
     mask_augm = False  # True: encoder input is [x*mask | mask] (the reference's *_mask classes)
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples=1,
@@ -67,7 +68,6 @@ class _VAEBase(nn.Module):
         self.max_epoch = MAX_EPOCH
         self._layout = None
         self._img = None
-        self._img_version = None
         self._part = {}
 
     # ------------------------------------------------------------------ parameter plumbing
@@ -113,35 +113,22 @@ class _VAEBase(nn.Module):
                 p.data = flat[off:off + p.numel()].view_as(p)
                 off += p.numel()
             self._flat = flat
-            self._img_version = None
+            self.invalidate_images()
         return self._flat
 
-    def _versions(self):
-        """What the packed image was built from: the version counters of the 12 parameters AND of the flat buffer they
-        are views of (an in-place write through `_flat` - dist.broadcast, a raw kernel - bumps only the latter).  Writes
-        through `p.data` bump neither: call invalidate_images() after those."""
-        flat = self.__dict__.get("_flat")
-        ps = self.trainable()
-        return tuple(p._version for p in ps) + (ps[0].data_ptr(), -1 if flat is None else flat._version)
-
-    def invalidate_images(self):
-        """Force a re-pack of the weight images on the next forward (after writing parameters through `.data`)."""
-        self._img_version = None
-
-    def _images(self):
-        """Packed weight images [enc | dec], re-packed when any parameter changed (in-place version counters)."""
+    def _new_image(self, device):
         lay = self._lay()
+        pidx, _ = lay.device_tables(device)
+        return PackedImage(torch.from_numpy(lay.img_template).to(device), lambda flat, buf: ops.pack_weights(flat, pidx, buf))
+
+    def _images(self, key=None):
+        """Packed weight images [enc | dec], re-packed when the parameter key changed (images.py).  `key`: the current
+        parameter key, when the caller has it."""
         flat = self.flatten_parameters()
         L.require_cuda(flat)
-        v = self._versions()
-        if self._img is None or self._img.device != flat.device:
-            self._img = torch.from_numpy(lay.img_template).to(flat.device)
-            self._img_version = None
-        if self._img_version != v:
-            pidx, _ = lay.device_tables(flat.device)
-            ops.pack_weights(flat, pidx, self._img)
-            self._img_version = v
-        return self._img
+        if self._img is None or self._img.buf.device != flat.device:
+            self._img = self._new_image(flat.device)
+        return self._img.get(self._param_key() if key is None else key, flat)
 
     def _enc_img(self):
         return self._images()[: self._lay().enc_img]

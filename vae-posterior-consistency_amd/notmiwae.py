@@ -20,6 +20,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .images import PackedImage, ParamKeyMixin
+from .trainer import _FlatAdamTrainer
 
 HID = 128  # VAE.py:2343-2363 hard-codes 128 (hid_dim is ignored by the reference too)
 ACT_NONE, ACT_ELU, ACT_SIGMOID_HARDTANH, ACT_RELU = 0, 1, 2, 3
@@ -346,7 +348,7 @@ class NMLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ model classes
-class _NMBase(nn.Module):
+class _NMBase(ParamKeyMixin, nn.Module):
     regularised = False
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
@@ -580,7 +582,7 @@ class notMIWAE_myversion(_NMBase):
 
 
 # ------------------------------------------------------------------------------------------------ fused step
-class NMTrainer:
+class NMTrainer(_FlatAdamTrainer):
     """The whole training step of the MNAR path (train.py:28-117 for 'reg_notMIWAE*' / 'vanilla_notMIWAE*') as a
     fixed sequence of HIP launches, no host synchronisation: float mask_p draw + stacked encoder input, Philox
     normals, encoder / decoder GEMM chains with the q and p passes STACKED along the batch (one GEMM per layer for
@@ -590,46 +592,27 @@ class NMTrainer:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0,
                  precision="f32"):
         """precision: "f32", "bf16x3" or "bf16" for the 17 GEMMs of the step (csrc/vpc_bf16.h; operands stay fp32 in
-        memory and are converted in registers); the loss kernel and Adam are fp32 in every mode."""
+        memory and are converted in registers); the loss kernel and Adam are fp32 in every mode.  (`eps` is Adam's
+        epsilon, `self.adam_eps`; `self.eps` is the step's workspace of normals.)"""
         if not isinstance(model, _NMBase):
             raise TypeError("NMTrainer supports REG_notMIWAE_v2 and notMIWAE_myversion")
-        self.model, self.reg = model, model.regularised
-        self.lr, self.betas, self.eps_adam = lr, betas, eps
-        self.seed, self.rng_offset, self.step_count = seed, 0, 0
-        self.pg, self.world_size, self.rank = process_group, world_size, rank
         from .ops import PRECISIONS
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r}: expected one of {sorted(PRECISIONS)}")
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
+        self.reg = model.regularised
         self.precision, self.prec = precision, PRECISIONS[precision]
-        flat = model.flatten_parameters()
-        L.require_cuda(flat)
-        self.dev = flat.device
-        n = flat.numel()
-        self.bucket = torch.zeros(n + 1, device=self.dev)  # [grads | loss] -> ONE all-reduce per step
-        self.grad, self.loss = self.bucket[:n], self.bucket[n:]
-        self.exp_avg = torch.zeros(n, device=self.dev)
-        self.exp_avg_sq = torch.zeros(n, device=self.dev)
-        self.accum = torch.zeros(1, device=self.dev)
+        self.loss = self.tail  # [grads | loss] -> ONE all-reduce per step
         self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
         d = model.obs_dim
         self.g = model._segment_views(self.grad[:2 * d], "wb")
         self.g.update(model._segment_views(self.grad[2 * d:2 * d + model._n_enc], "enc"))
         self.g.update(model._segment_views(self.grad[2 * d + model._n_enc:], "dec"))
-        off = 0
-        for p in model.trainable():
-            p.grad = self.grad[off:off + p.numel()].view_as(p)
-            off += p.numel()
         self._B = None
-        self.timers = None
-        # the bf16 image of the layer-fused path is current when nothing has written the parameters since the launch that packed it
-        # (the fused tail of a single-device step re-packs what its Adam updates): the flat buffer's address + the parameters'
-        # version counters at that time.  Writes torch does not count (p.data.copy_, raw kernels): call invalidate_image().
-        self._plist = model.trainable()
-        self._img_key = None
 
     def invalidate_image(self):
-        """Force a re-pack of the bf16 weight image at the next step (after writing parameters behind torch's version counters)."""
-        self._img_key = None
+        """Alias of model.invalidate_images(): after writing parameters behind torch's version counters."""
+        self.model.invalidate_images()
 
     def _ws(self, B):
         if self._B == B:
@@ -676,20 +659,14 @@ class NMTrainer:
             if getattr(self, "_nd_tables", None) is None:
                 self._nd_tables = nmdec_tables(m, dev)
                 self.nd_img = torch.zeros(nimg.value, device=dev)
+                # ONE image (decoder, missingness model, encoder), packed lazily under the model's parameter key (images.py)
+                from .ops import step_pack_weights_bf16
+                pidx = self._nd_tables[0]
+                self._nd = PackedImage(self.nd_img, lambda flat, buf: step_pack_weights_bf16(flat, pidx, buf))
             self.nd_part = e(nblk.value * npart.value)
             self.ne_part = e(nblk.value * int(self._nd_tables[3].numel()))  # the encoder-backward kernel's blocks (fused tail)
             self.nd_stat = torch.empty(nblk.value * 5, dtype=torch.float64, device=dev)
         self._B = B
-
-    def _t(self, name, fn, *a, **kw):
-        if self.timers is None:
-            return fn(*a, **kw)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **kw)
-        e1.record()
-        self.timers.setdefault(name, []).append((e0, e1))
-        return r
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30, global_batch=None, row_lo=None,
              _state=None):
@@ -708,7 +685,7 @@ class NMTrainer:
         reg = self.reg
         P = 2 if reg else 1
         R, M, BK = P * B, P * B * K, B * K
-        t = self._t
+        t = self._timed
         if row_lo is None:
             row_lo = self.rank * B if self.world_size > 1 else 0
         rng_inc = (2 * Bg * K * Ld + 3) // 4 + (Bg * d + 3) // 4 + 1  # what the GLOBAL batch consumes
@@ -737,13 +714,12 @@ class NMTrainer:
         # that reduces both sets of blocks, applies Adam and re-packs the image: vpc_nm_fused_bwd_step) and the pack launch goes
         fuse_tail = self.use_nmdec and self.world_size == 1 and _state is None and self.timers is None
         if self.use_nmdec:
-            # plain bf16 at obs_dim 128: ONE image (decoder, missingness model, encoder) packed by one launch, the encoder forward
-            # as one kernel (csrc/vpc_nmdec.hip: nmenc_fwd_kernel) instead of three GEMM launches
-            key = (m._flat.data_ptr(), tuple(p._version for p in self._plist)) if fuse_tail else None
-            if key is None or key != self._img_key:
-                from .ops import step_pack_weights_bf16
-                t("pack", step_pack_weights_bf16, m._flat, self._nd_tables[0], self.nd_img)
-            self._img_key = None  # (whoever updates the parameters below says whether the image followed)
+            # plain bf16 at obs_dim 128: the encoder forward as one kernel (csrc/vpc_nmdec.hip: nmenc_fwd_kernel) instead of three
+            # GEMM launches, on the image the fused tail of the previous step re-packed (or re-packed here)
+            key = m._param_key(self._plist)
+            if _state is not None:
+                self._nd.stamp(None)  # graph capture: every replay re-packs
+            t("pack", self._nd.get, key, m._flat)
             t("enc_fwd", nmenc_fwd, self.nd_img, self.xin, self.h1, self.h2, self.heads, R, d, Ld)
         else:
             t("enc_fwd", linear_fwd, self.xin, v["We1"], v["be1"], self.h1, R, HID, d, ACT_ELU, precision=self.prec)
@@ -771,8 +747,8 @@ class NMTrainer:
                 nm_fused_bwd_step(self.nd_img, xf, mf, mp, self.xin, self.h1, self.h2, self.heads, self.eps, self.dht, self.nd_part,
                                   self.nd_stat, self.ne_part, ginv, einv, self.grad, self.out8, self.loss, self.accum, B, Bg, K, d,
                                   Ld, alpha, m._flat, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1],
-                                  self.eps_adam, self.step_count, pidx)
-                self._img_key = key
+                                  self.adam_eps, self.step_count, pidx)
+                self._flat_written(key, self._nd)
                 return
             t("dec_fused", nmdec_step, self.nd_img, xf, mf, mp, self.heads, self.eps, self.dht, self.nd_part, self.nd_stat,
               gidx, ginv, self.grad, self.out8, self.loss, self.accum if self.world_size == 1 else None, B, Bg, K, d, Ld, alpha,
@@ -797,17 +773,14 @@ class NMTrainer:
 
     def _step_tail(self, t, _state):
         m = self.model
-        if self.world_size > 1:  # ONE collective per step: RCCL on the compute stream, or torch.distributed (dist.py)
-            from . import dist as dp_mod
-            if not getattr(self, "_coll_ready", False):
-                self.collective = dp_mod.make_collective(self.world_size, self.rank, self.dev, self.pg)
-                self._coll_ready = True
-            dp_mod.allreduce_bucket(self.bucket, self.pg, self.collective)
+        if self.world_size > 1:
+            self._allreduce()
         self.step_count += 1
         from .ops import adam_step
         t("adam", adam_step, m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr,
-          self.betas[0], self.betas[1], self.eps_adam, None, None, None if _state is None else _state[0:1],
+          self.betas[0], self.betas[1], self.adam_eps, None, None, None if _state is None else _state[0:1],
           loss_in=self.loss if self.world_size > 1 else None, accum=self.accum if self.world_size > 1 else None)
+        self._flat_written(None)
 
     def _step_decoder_gemms(self, xf, mf, mp, B, Bg, alpha, _state, rng_inc, t, v, wgrad):
         """Decoder forward, loss and decoder backward as the GEMM chain (every precision, both model classes)."""
@@ -850,35 +823,5 @@ class NMTrainer:
         d = self.model.obs_dim
         xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
         L.require_cuda(xf, mf)
-        key = (tuple(xf.shape), float(alpha), p_missingness)
-        if getattr(self, "_graph_key", None) != key:
-            self.step(xf, mf, alpha=alpha, p_missingness=p_missingness)  # eager warm-up (LDS attributes, workspaces)
-            self._gx, self._gm = xf.clone(), mf.clone()
-            self.state = torch.tensor([self.step_count, 0], dtype=torch.int64, device=self.dev)
-            timers, self.timers = self.timers, None
-            base_rng, base_step = self.rng_offset, self.step_count
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step(self._gx, self._gm, alpha=alpha, p_missingness=p_missingness, _state=self.state)
-            self._graph_rng_inc = self.rng_offset - base_rng
-            self.rng_offset, self.step_count = base_rng, base_step  # capture executed nothing
-            self.timers = timers
-            self._graph, self._graph_key = g, key
-            return
-        if xf.data_ptr() != self._gx.data_ptr():
-            self._gx.copy_(xf)
-        if mf.data_ptr() != self._gm.data_ptr():
-            self._gm.copy_(mf)
-        self._graph.replay()
-        self.step_count += 1
-        self.rng_offset += self._graph_rng_inc
-
-    def loss_value(self) -> float:
-        return float(self.loss.item())
-
-    def epoch_total(self, reset=True) -> float:
-        v = float(self.accum.item())
-        if reset:
-            self.accum.zero_()
-        return v
+        self._graph_step((tuple(xf.shape), float(alpha), p_missingness), (xf, mf),
+                         lambda *a, **k: self.step(*a, alpha=alpha, p_missingness=p_missingness, **k))

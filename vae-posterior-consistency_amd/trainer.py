@@ -1,0 +1,110 @@
+"""What the step trainers (FusedTrainer, NMTrainer, EDDITrainer, WideTrainer) share: Adam state on one flat parameter
+buffer, the flat bucket [grads | loss tail] that data parallelism all-reduces in ONE collective, timers, the loss readers
+and the capture / replay of a step as a HIP graph."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from . import dist as dp_mod
+from .images import flat_written
+
+
+class _FlatAdamTrainer:
+    timer_every = 1  # with timers enabled: bracket the launches of every timer_every-th step only
+
+    def __init__(self, model, lr, betas, eps, seed, process_group, world_size, rank, tail, collective=None):
+        self.model = model
+        self.lr, self.betas, self.adam_eps = lr, betas, eps
+        self.seed, self.rng_offset, self.step_count = seed, 0, 0
+        self.pg, self.world_size, self.rank = process_group, world_size, rank
+        self.collective = collective
+        self._coll_ready = collective is not None
+        flat = model.flatten_parameters()
+        L.require_cuda(flat)
+        self.dev = flat.device
+        n = flat.numel()
+        # one flat bucket: [grads (n) | loss terms (tail)] -> a single all-reduce per step under DP
+        self.bucket = torch.zeros(n + tail, device=self.dev)
+        self.grad, self.tail = self.bucket[:n], self.bucket[n:]
+        self.exp_avg = torch.zeros(n, device=self.dev)
+        self.exp_avg_sq = torch.zeros(n, device=self.dev)
+        self.accum = torch.zeros(1, device=self.dev)
+        self.timers = None  # bench.py sets this to {} to collect per-kernel HIP event pairs
+        self.timer_names = None  # restrict the event pairs to these launches (None = all)
+        self._timer_tick = 0
+        self._plist = model.trainable()
+        self._repacked = ()
+        # the trainable tensors' .grad are views of the flat gradient, so state is inspectable like torch's
+        off = 0
+        for p in self._plist:
+            p.grad = self.grad[off:off + p.numel()].view_as(p)
+            off += p.numel()
+
+    def _timed(self, name, fn, *args, **kw):
+        """Run one launch; with timers enabled bracket it with events on the launch stream."""
+        if self.timers is None or self._timer_tick % self.timer_every or \
+                (self.timer_names is not None and name not in self.timer_names):
+            return fn(*args, **kw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn(*args, **kw)
+        e1.record()
+        self.timers.setdefault(name, []).append((e0, e1))
+        return r
+
+    def _flat_written(self, key, *repacked):
+        """After a launch that wrote the flat parameters (Adam): images.py's rule.  `key`: this step's parameter key."""
+        flat_written(self.model, self._plist, key, repacked)
+        self._repacked = repacked
+
+    def _collective(self):
+        if not self._coll_ready:
+            self.collective = dp_mod.make_collective(self.world_size, self.rank, self.dev, self.pg)
+            self._coll_ready = True
+        return self.collective
+
+    def _allreduce(self):
+        """ONE collective per step over the flat bucket [grads | loss terms]: ncclAllReduce (RCCL over xGMI) on the
+        compute stream when the process group is NCCL, torch.distributed.all_reduce otherwise (dist.py).  Every term
+        is already normalised by the GLOBAL batch, so a plain SUM is the result of the concatenated batch."""
+        dp_mod.allreduce_bucket(self.bucket, self.pg, self._collective())
+
+    def _graph_step(self, key, inputs, step):
+        """step_graph's body.  The first call with a new `key` runs step(*inputs) eagerly (LDS attributes, workspaces,
+        packed images) and captures step(*copies of inputs, _state=self.state); later calls copy the inputs into the
+        captured buffers and replay.  Step count and Philox offsets live on the device (`state`): kernel arguments are
+        frozen in a graph."""
+        if getattr(self, "_graph_key", None) != key:
+            step(*inputs)
+            self._ginputs = [t.clone() for t in inputs]
+            self.state = torch.tensor([self.step_count, 0], dtype=torch.int64, device=self.dev)
+            timers, self.timers = self.timers, None
+            host = (self.rng_offset, self.step_count, self._timer_tick)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step(*self._ginputs, _state=self.state)
+            self._graph_rng_inc = self.rng_offset - host[0]
+            self.rng_offset, self.step_count, self._timer_tick = host  # capture executed nothing
+            self.timers = timers
+            self._graph, self._graph_key, self._graph_repacked = g, key, self._repacked
+            return
+        for src, dst in zip(inputs, self._ginputs):
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src)
+        self._graph.replay()
+        self.step_count += 1
+        self.rng_offset += self._graph_rng_inc
+        self._flat_written(None, *self._graph_repacked)
+
+    def loss_value(self) -> float:
+        """Loss of the last step (host sync)."""
+        return float(self.tail[0].item())
+
+    def epoch_total(self, reset=True) -> float:
+        """Sum of train_loss over the steps since the last reset (train.py:117-118; one host sync per epoch)."""
+        v = float(self.accum.item())
+        if reset:
+            self.accum.zero_()
+        return v

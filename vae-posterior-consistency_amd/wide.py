@@ -19,6 +19,7 @@ from . import ops
 from .notmiwae import (ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, linear_dgrad, linear_fwd, linear_wgrad, nm_mul,
                        nm_sample, nm_sample_bwd)
 from .ops import _f32c, as_mask_u8
+from .trainer import _FlatAdamTrainer
 
 H1, H2 = 100, 50
 
@@ -112,23 +113,14 @@ class WideDecoderFn(torch.autograd.Function):
         return None, dz, gW4, gb4, gW5, gb5, gW6, gb6
 
 
-class WideTrainer:
+class WideTrainer(_FlatAdamTrainer):
     """Training step (train.py:53-117) for the wide models: on-device mask_p / eps draws, the API-path forward and K4
     loss, backward, flat Adam (vpc_adam_step on the flat parameter buffer), loss accumulated on the device.  Mirrors
     FusedTrainer's interface (step / loss_value / epoch_total); data parallel as there: ONE all-reduce of [grads | loss]."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
-        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
-        self.seed, self.rng_offset, self.step_count = seed, 0, 0
-        self.pg, self.world_size, self.rank = process_group, world_size, rank
-        flat = model.flatten_parameters()
-        L.require_cuda(flat)
-        self.dev = flat.device
-        n = flat.numel()
-        self.bucket = torch.zeros(n + 1, device=self.dev)
-        self.grad, self.loss = self.bucket[:n], self.bucket[n:]
-        self.exp_avg, self.exp_avg_sq = torch.zeros(n, device=self.dev), torch.zeros(n, device=self.dev)
-        self.accum = torch.zeros(1, device=self.dev)
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
+        self.loss = self.tail
         self.vanilla = not hasattr(model, "reg_type")
 
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False,
@@ -172,21 +164,9 @@ class WideTrainer:
             self.grad[off:off + p.numel()].copy_(p.grad.reshape(-1))
             off += p.numel()
         self.loss.copy_(tl.detach().reshape(1))
-        if self.world_size > 1:  # ONE collective per step: RCCL on the compute stream, or torch.distributed (dist.py)
-            from . import dist as dp_mod
-            if not getattr(self, "_coll_ready", False):
-                self.collective = dp_mod.make_collective(self.world_size, self.rank, self.dev, self.pg)
-                self._coll_ready = True
-            dp_mod.allreduce_bucket(self.bucket, self.pg, self.collective)
+        if self.world_size > 1:
+            self._allreduce()
         self.step_count += 1
         ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.eps, loss_in=self.loss, accum=self.accum)
-
-    def loss_value(self) -> float:
-        return float(self.loss.item())
-
-    def epoch_total(self, reset=True) -> float:
-        v = float(self.accum.item())
-        if reset:
-            self.accum.zero_()
-        return v
+                      self.betas[1], self.adam_eps, loss_in=self.loss, accum=self.accum)
+        self._flat_written(None)
