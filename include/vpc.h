@@ -247,6 +247,23 @@ int vpc_reward_matrix(const float* x, const uint8_t* mask, const float* im, cons
                       const float* enc_img, float* pre, float* stat, float* w1t, float* R, int n, int d, int L, int M,
                       void* stream);
 
+/* The same reward for the other encoder families of active_learning_func (evaluate.py:374-378, 403-409, 444-448: every
+ * 'reg_vae*' / 'vanilla_vae*' / '*_EDDI*' model), selected by `kind` = the encoder's first layer:
+ *   VPC_REWARD_DENSE       Reg_VAE / vanilla_VAE (VAE.py:366-395) of any width d <= 4096: W1 [100][d]
+ *   VPC_REWARD_DENSE_MASK  Reg_VAE_mask / vanilla_VAE_mask (input [x*mask | mask], VAE.py:545-548): W1 [100][2d]
+ *   VPC_REWARD_POINTNET    Reg_EDDI / vanilla_EDDI (VAE.py:713-741): W1 [100][K] / b1 = pnp_encoder2.0, AC [2][K][d] the
+ *                          folded front-end of vpc_eddi_fold, 1 <= K <= 32 (AC and K are ignored by the other kinds)
+ * w23_img = [W2 | W3] of a packed encoder image (the part from EncImg::oW2 on, 10240 floats, the same for every input width:
+ * the image of layout(K, L) for the point-net trunk, 16-byte aligned).  pre / stat / w1t: vpc_reward_scratch_ex's sizes.
+ * The DENSE kind at d <= 128 runs the kernels of vpc_reward_matrix.  L <= 15 (one latent tile) for every kind. */
+#define VPC_REWARD_DENSE 0
+#define VPC_REWARD_DENSE_MASK 1
+#define VPC_REWARD_POINTNET 2
+int vpc_reward_scratch_ex(int kind, int n, int d, int M, int K, long* pre_floats, long* stat_floats, long* w1t_floats);
+int vpc_reward_matrix_ex(int kind, const float* x, const uint8_t* mask, const float* im, const float* W1, const float* b1,
+                         const float* AC, int K, const float* w23_img, float* pre, float* stat, float* w1t, float* R, int n,
+                         int d, int L, int M, void* stream);
+
 /* ---- MNAR path (config 3): REG_notMIWAE_v2 / notMIWAE_myversion --------------------------------------
  * Reference: src/models/VAE.py:2327-2505 and :2691-2847 (encoder d->128->128 ELU + heads, K-fold replicated
  * draw, decoder L->128->128 ELU + Sigmoid / Hardtanh(-10,0) heads, self-masking missingness model).  The

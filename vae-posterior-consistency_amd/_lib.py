@@ -77,6 +77,8 @@ _PROTOS = {
     "vpc_rccl_comm_destroy": [P],
     "vpc_reward_scratch": [I, I, I, C.POINTER(L_), C.POINTER(L_), C.POINTER(L_)],
     "vpc_reward_matrix": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "vpc_reward_scratch_ex": [I, I, I, I, I, C.POINTER(L_), C.POINTER(L_), C.POINTER(L_)],
+    "vpc_reward_matrix_ex": [I, P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, P],
     # MNAR path (config 3)
     "vpc_linear_fwd": [P, L_, P, P, P, L_, L_, I, I, I, I, I, P],
     "vpc_linear_dgrad": [P, L_, P, L_, I, I, P, P, L_, I, P, L_, L_, I, I, I, P],

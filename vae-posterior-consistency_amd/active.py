@@ -2,8 +2,9 @@
 src/experiment_main/evaluate.py:514-634 on the GPU.
 
 `reward_matrix` replaces the whole candidate loop of active_learning_func (evaluate.py:424-433) by three kernel
-launches (vpc_reward_matrix); `R_lindley_chain`, `chaini_I`, `chaini_II` keep the reference's signatures so that
-evaluate.py can call them unchanged.
+launches (vpc_reward_matrix for the plain Reg_VAE / vanilla_VAE with obs_dim <= 128; vpc_reward_matrix_ex for the
+mask-augmented, the wide and the EDDI models); `R_lindley_chain`, `chaini_I`, `chaini_II` keep the reference's
+signatures so that evaluate.py can call them unchanged.
 """
 from __future__ import annotations
 
@@ -14,15 +15,54 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib, ptr, stream_ptr
-from .ops import _f32c, as_mask_u8
+from .images import PackedImage
+from .ops import _f32c, as_mask_u8, pack_weights
+
+
+# first-layer kinds of vpc_reward_matrix_ex (include/vpc.h)
+REWARD_DENSE, REWARD_DENSE_MASK, REWARD_POINTNET = 0, 1, 2
+W23_FLOATS = 64 * 128 + 32 * 64  # [W2 | W3] of a packed encoder image (csrc/vpc_layout.h EncImg, oW2 .. total), any width
+_H1, _H2 = 100, 50
+
+
+def _is_pointnet(vae):
+    from .eddi import _EDDIBase
+    return isinstance(vae, _EDDIBase)
+
+
+def _w23_image(vae):
+    """[W2 | W3] of the encoder, packed as the encoder kernels' image holds it.  Models with an encoder image (plain and
+    mask-augmented VAEs with an input of <= 128 columns) lend theirs; the wide models and the EDDI trunk (pnp_encoder2,
+    whose own image is never packed) get a W2/W3-only image of their own, re-packed when the parameter key changes
+    (images.py).  Layers 2-3 do not depend on the input width, so the tables of any small layout pack it."""
+    flat = vae.flatten_parameters()
+    L.require_cuda(flat)
+    if not _is_pointnet(vae) and not vae._wide:
+        return vae._enc_img()[vae._lay().enc_img - W23_FLOATS:]
+    img = vae.__dict__.get("_w23_img")
+    if img is None or img.buf.device != flat.device:
+        lay = L.layout(16, vae.latent_dim)
+        o = lay.enc_img - W23_FLOATS
+        w2 = _H1 * 16 + _H1  # flat offset of seq_encoder.2.weight in that layout
+        n23 = _H2 * _H1 + _H2 + 2 * vae.latent_dim * (_H2 + 1)
+        idx = torch.from_numpy(lay.pack_idx[w2:w2 + n23] - o).to(flat.device)
+        lo = sum(p.numel() for p in vae.trainable()[:2])
+        img = PackedImage(torch.from_numpy(lay.img_template[o:lay.enc_img].copy()).to(flat.device),
+                          lambda fl, buf: pack_weights(fl[lo:lo + n23], idx, buf))
+        vae.__dict__["_w23_img"] = img
+    return img.get(vae._param_key(), flat)
 
 
 def reward_matrix(vae, x, mask, im):
     """R [n, d-1]: reward of revealing feature u for row n (-1e4 where already observed).
-    x [n, d]; mask [n, d] (bool / float 0-1 / uint8); im [M, n, d] MC imputations; target = last column."""
+    x [n, d]; mask [n, d] (bool / float 0-1 / uint8); im [M, n, d] MC imputations; target = last column.
+    Every 'reg_vae*' / 'vanilla_vae*' (mask-augmented and wide included) and '*_EDDI*' model of model_loader with
+    latent_dim <= 15."""
     L.require_cuda(x, im)
-    if vae.mask_augm:
-        raise NotImplementedError("reward_matrix: mask-augmented encoders are not supported")
+    if vae.latent_dim > 15:
+        raise L.VpcError("reward_matrix: latent_dim <= 15 is supported (the mean / logvar heads are one 16-row tile)")
+    if _is_pointnet(vae) or vae.mask_augm or vae._wide:
+        return _reward_matrix_ex(vae, x, mask, im)
     n, d = x.shape
     M = im.shape[0]
     lay = vae._lay()
@@ -38,6 +78,34 @@ def reward_matrix(vae, x, mask, im):
     check(lib().vpc_reward_matrix(ptr(_f32c(x)), ptr(as_mask_u8(mask.to(dev))), ptr(_f32c(im)), ptr(w1.data), ptr(b1.data),
                                   ptr(vae._enc_img()), ptr(pre), ptr(stat), ptr(w1t), ptr(R), n, d, lay.L, M,
                                   stream_ptr()), "vpc_reward_matrix")
+    return R
+
+
+def _reward_matrix_ex(vae, x, mask, im):
+    """reward_matrix for the mask-augmented, wide and EDDI encoders (vpc_reward_matrix_ex)."""
+    n, d = x.shape
+    M = im.shape[0]
+    dev = x.device
+    w23 = _w23_image(vae)
+    t = vae.trainable()
+    w1, b1 = t[0], t[1]
+    K, AC = 0, None
+    if _is_pointnet(vae):
+        from .eddi import eddi_fold
+        kind, K = REWARD_POINTNET, vae.emb_dim
+        AC = torch.empty(2, K, d, device=dev)
+        eddi_fold(*[p.data for p in t[12:16]], AC, d, K)
+    else:
+        kind = REWARD_DENSE_MASK if vae.mask_augm else REWARD_DENSE
+    sizes = [C.c_long() for _ in range(3)]
+    check(lib().vpc_reward_scratch_ex(kind, n, d, M, K, *[C.byref(s) for s in sizes]), "vpc_reward_scratch_ex")
+    pre = torch.empty(sizes[0].value, device=dev)
+    stat = torch.empty(sizes[1].value, device=dev)
+    w1t = torch.empty(sizes[2].value, device=dev)
+    R = torch.empty(n, d - 1, device=dev)
+    check(lib().vpc_reward_matrix_ex(kind, ptr(_f32c(x)), ptr(as_mask_u8(mask.to(dev))), ptr(_f32c(im)), ptr(w1.data),
+                                     ptr(b1.data), ptr(AC), K, ptr(w23), ptr(pre), ptr(stat), ptr(w1t), ptr(R), n, d,
+                                     vae.latent_dim, M, stream_ptr()), "vpc_reward_matrix_ex")
     return R
 
 
