@@ -468,6 +468,44 @@ int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* d
                             long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
                             void* stream);
 
+/* ---- MIWAE path: MIWAE / Reg_MIWAE (csrc/vpc_miw.hip) ------------------------------------------------------------
+ * Reference: src/models/VAE.py:3011-3134 and :3137-3301.  Encoder d->128->128 ReLU -> [mean L | raw L] and decoder
+ * L->128->128 ReLU -> [mean d | scale d | df d] run on vpc_linear_fwd / dgrad / wgrad (ACT_RELU, last layer ACT_NONE);
+ * these entry points add the softplus scale of the sampler, the Student-t decoder heads and the importance-weighted
+ * bound.  fp32 throughout; masks are float 0/1; `R` = data rows of the stacked passes, `S` = num_samples. */
+
+/* z[r*S+s][:] = mean[r] + softplus(raw[r]) * eps[r][s][:] (eps NULL -> z = mean), heads [R][mean L | raw L] the encoder
+ * head GEMM; hact (optional) [R][mean L | softplus(raw) L].  VAE.py:3059-3070 / :3188-3200 (Normal(mean, scale).rsample()). */
+int vpc_miw_sample(const float* heads, float* hact, const float* eps, float* z, long R, int S, int L, void* stream);
+/* out [R][2L] = d / d heads: mean <- sum_s dz + g_hact[mean]; raw <- (sum_s dz * eps + g_hact[scale]) * softplus'(raw).
+ * dz [R*S][L] and g_hact [R][2L] may each be NULL. */
+int vpc_miw_sample_bwd(const float* dz, const float* eps, const float* heads, const float* g_hact, float* out, long R,
+                       int S, int L, void* stream);
+/* y_act[m] = (sigmoid | softplus + 0.001 | softplus + 3) of y_raw[m] = [mean d | scale d | df d], [M][3d] each (decoder,
+ * VAE.py:3072-3076; Softplus with beta 1, threshold 20); the backward maps d / d y_act to d / d y_raw. */
+int vpc_miw_heads(const float* y_raw, float* y_act, long M, int d, void* stream);
+int vpc_miw_heads_bwd(const float* y_raw, const float* g_act, float* g_raw, long M, int d, void* stream);
+
+/* Loss of Reg_MIWAE (mask_p != NULL; VAE.py:3204-3265) or MIWAE (mask_p == NULL; :3078-3100) and, when g_y_q != NULL,
+ * its gradients with respect to the decoder heads (rows b*S+s, pitch ldg; raw != 0: the y_* are the raw head GEMM output
+ * and the gradients are w.r.t. it, raw == 0: the activated (mean | scale | df)) and the ACTIVATED encoder heads
+ * [B][mean L | scale L] (heads_*, g_heads_*).  eps_* [B][S][L] = the fresh draws of loss() (:3087 / :3216 / :3237).
+ * pairing VPC_MIW_PAIR_REFERENCE reproduces the reference's [S, B] reshape of the (row, sample)-ordered likelihood sums
+ * against the permuted prior / posterior terms (:3078-3091, :3209-3240): slot (i, j) pairs the likelihood of flat row
+ * i*B + j with the prior / posterior term of row j, sample i.  VPC_MIW_PAIR_PER_ROW pairs both terms of row j, sample i
+ * (equal to B single-row calls; the batched eval_miwae).  out8 (device doubles) = loss, nb_q, nb_p, KL_reg, reg_like,
+ * sum logpxobsgivenz_imp / (B * 5000), sum lse_q, sum lse_p.  xm_imp != NULL: [B][d] llh_eval imputation with the q
+ * weights (:3096-3098 / :3267-3269).  loss_f32 / accum optional as in vpc_nm_loss.  Three launches (per-row sums, per-slot
+ * log-sum-exp, gradients + fixed-order loss reduction) through `scratch` (vpc_miw_loss_scratch bytes, 8-byte aligned). */
+#define VPC_MIW_PAIR_REFERENCE 0
+#define VPC_MIW_PAIR_PER_ROW 1
+long vpc_miw_loss_scratch(long B, int S);
+int vpc_miw_loss(const float* x, const float* mask, const float* mask_p, const float* y_q, const float* y_p, long ldy,
+                 int raw, const float* heads_q, const float* heads_p, const float* eps_q, const float* eps_p,
+                 float* g_y_q, float* g_y_p, long ldg, float* g_heads_q, float* g_heads_p, float* xm_imp,
+                 void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum, long B, int S, int d,
+                 int L, double alpha, int pairing, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

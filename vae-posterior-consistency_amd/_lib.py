@@ -102,13 +102,20 @@ _PROTOS = {
     "vpc_nm_fused_bwd_step": [P, P, P, P, P, P, P, P, L_, P, P, P, P, P, L_, P, P, P, I, P, P, P, L_, L_, I, I, I, C.c_double,
                               P, P, P, F, F, F, F, L_, P, P],
     "vpc_nmdec_step": [P, P, P, P, P, L_, P, P, P, P, P, P, P, I, P, P, P, P, C.c_longlong, L_, L_, I, I, I, C.c_double, P],
+    # MIWAE path (csrc/vpc_miw.hip)
+    "vpc_miw_sample": [P, P, P, P, L_, I, I, P],
+    "vpc_miw_sample_bwd": [P, P, P, P, P, L_, I, I, P],
+    "vpc_miw_heads": [P, P, L_, I, P],
+    "vpc_miw_heads_bwd": [P, P, P, L_, I, P],
+    "vpc_miw_loss_scratch": [L_, I],
+    "vpc_miw_loss": [P, P, P, P, P, L_, I, P, P, P, P, P, P, L_, P, P, P, P, L_, P, P, P, L_, I, I, I, C.c_double, I, P],
     # PNP / EDDI encoder front-end
     "vpc_eddi_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
     "vpc_eddi_front_scratch": [L_, I, I],
     "vpc_eddi_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch"}
 
 _lib = None
 

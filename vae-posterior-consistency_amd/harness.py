@@ -6,10 +6,11 @@
   train                src/experiment_main/train.py:13-133   epoch / batch loop, Adam(lr=1e-3), save at end
   eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL
   eval_vae_mnar        src/experiment_main/evaluate.py:13-69    importance-weighted imputation RMSE (MNAR path)
+  eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
-Only the classes named by the hot path are built (Reg_VAE, vanilla_VAE and their *_mask variants,
-REG_notMIWAE_v2, notMIWAE_myversion); other vae_type families raise NotImplementedError (out of scope,
-SURVEY.md section 8).
+The families built are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI, REG_notMIWAE_v2,
+notMIWAE_myversion and MIWAE / Reg_MIWAE; the flow models raise NotImplementedError (out of scope, SURVEY.md
+section 8).
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, notMIWAE_myversion
 from .eddi import EDDITrainer, Reg_EDDI, vanilla_EDDI
+from .miwae import MIWAE, MIWTrainer, Reg_MIWAE
 
 _seed_counter = [0]
 
@@ -64,15 +66,18 @@ def model_loader(stage, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type
                  num_samples, num_estimates, experiment_type, reg_type, vae_type="vae", alpha=1.0, p_missingness=30,
                  beta=0.5, beta_annealing=True, alpha_annealing=True, not_miwae_type="changed"):
     """Same positional signature and substring dispatch as loaders.py:13-246 for the in-scope families."""
-    if "flow" in vae_type or ("MIWAE" in vae_type and "notMIWAE" not in vae_type) or \
-            ("EDDI" in vae_type and data_type == "mnist"):
-        raise NotImplementedError(f"vae_type {vae_type!r}: only reg_vae* / vanilla_vae* / *_notMIWAE* / *_EDDI* (UCI) "
-                                  "are on the accelerated path")
+    if "flow" in vae_type or ("EDDI" in vae_type and data_type == "mnist"):
+        raise NotImplementedError(f"vae_type {vae_type!r}: only reg_vae* / vanilla_vae* / *_notMIWAE* / *MIWAE* / *_EDDI* "
+                                  "(UCI) are on the accelerated path")
     augm = "mask_augm" in vae_type  # loaders.py:47, 143
     if "reg_notMIWAE" in vae_type:  # loaders.py:89-103
         model = REG_notMIWAE_v2(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
     elif "vanilla_notMIWAE" in vae_type:  # loaders.py:219-233
         model = notMIWAE_myversion(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
+    elif "reg_MIWAE" in vae_type:  # loaders.py:135-148
+        model = Reg_MIWAE(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
+    elif "MIWAE" in vae_type and "notMIWAE" not in vae_type:  # loaders.py:234-244 (the final else: vanilla_MIWAE*)
+        model = MIWAE(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
     elif "reg_EDDI" in vae_type:  # loaders.py:104-131 (UCI branch)
         model = Reg_EDDI(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, reg_type, num_samples,
                          num_estimates)
@@ -100,7 +105,7 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
           experiment_type, vae_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), alpha=1.0,
           stage="train", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True,
           not_miwae_type="changed", fused=True, seed=0, save=True, verbose=True):
-    """train.py:13-133 for reg_vae* / vanilla_vae* / reg_notMIWAE* / vanilla_notMIWAE*.  With fused=True every batch is one FusedTrainer.step (no
+    """train.py:13-133 for reg_vae* / vanilla_vae* / *_notMIWAE* / *_EDDI* / *MIWAE*.  With fused=True every batch is one trainer step (no
     per-step host sync: the epoch total is read once per epoch, as the reference only prints it per epoch);
     with fused=False it is the reference's own sequence model.forward -> model.loss -> backward -> optim.Adam
     on the API path.  Returns the trained model."""
@@ -112,6 +117,7 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
     loader = data_loader_train if nm else data_loader_train[0]  # train.py:22-25
     is_reg = "reg" in vae_type
     eddi = "EDDI" in vae_type
+    miw = isinstance(model, (MIWAE, Reg_MIWAE))
     # 'with_drop' variants (train.py:32-37, 50-51; vanilla classes only - the reference's regularised branch never draws mask_p
     # beside it): the model sees mask * mask_drop, the keep-mask of create_missing_uci_drop_eddi (utils.py:42-45)
     drop = "with_drop" in vae_type and not is_reg
@@ -120,7 +126,8 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
             from .wide import WideTrainer
             trainer = WideTrainer(model, lr=0.001, seed=seed)
         else:
-            trainer = (NMTrainer if nm else EDDITrainer if eddi else FusedTrainer)(model, lr=0.001, seed=seed)
+            trainer = (MIWTrainer if miw else NMTrainer if nm else EDDITrainer if eddi else FusedTrainer)(model, lr=0.001,
+                                                                                                        seed=seed)
     else:
         model.flatten_parameters()
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001)  # train.py:21
@@ -131,8 +138,22 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
             mask = mask.to(device)
             if fused and drop:  # the fused vanilla step on the thinned mask (one more elementwise launch, no host sync)
                 mask = mask.to(torch.float32) * create_missing_uci_drop_eddi(data_sample.shape, device=device)
-            if fused and nm:
+            if fused and (nm or miw):
                 trainer.step(data_sample, mask, alpha=alpha, p_missingness=p_missingness)
+                continue
+            if miw:
+                if is_reg:  # train.py:53-55, 102-108
+                    mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
+                    o = model.forward(data_sample, mask, mask_p)
+                    _, train_loss = model.loss(data_sample, o[2], o[3], o[4], o[0], o[1], o[7], o[8], o[9], o[5], o[6],
+                                               mask, mask_p, i + 1, beta_annealing=beta_annealing, beta=beta, alpha=alpha)
+                else:  # train.py:109-113
+                    o = model.forward(data_sample, mask)
+                    _, train_loss = model.loss(data_sample, o[2], o[3], o[4], o[0], o[1], mask, i + 1)
+                optimizer.zero_grad()
+                train_loss.backward()
+                optimizer.step()
+                total_loss += train_loss.item()
                 continue
             if fused:
                 trainer.step(data_sample, mask, epoch=i + 1, alpha=alpha, beta=beta, beta_annealing=beta_annealing,
@@ -302,3 +323,54 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
             os.makedirs(os.path.dirname(pth), exist_ok=True)
             torch.save(recon, pth)
     return recon
+
+
+def miwae_result_path(experiment_type, data_type, vae_type, loader_stage, alpha=0.5, p_missingness=30, reg_type="ml_reg"):
+    """File eval_miwae writes (evaluate.py:120-133): the literal '50_missing_rate' whatever the missing rate."""
+    rest = os.path.join("experiments", experiment_type, data_type, "rest", _family(vae_type))
+    if "vanilla" in vae_type:
+        return os.path.join(rest, f"{loader_stage}_{vae_type}_rmse_50_missing_rate_test.pt")
+    return os.path.join(rest, f"{loader_stage}_{vae_type}_rmse_{alpha}_{p_missingness}_{reg_type}"
+                              "_full_reg_50_missing_rate_test.pt")
+
+
+def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
+               experiment_type, vae_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), alpha=0.5,
+               stage="evaluate", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False,
+               alpha_annealing=True, model=None, save=True, max_decoder_rows=1 << 23):
+    """evaluate.py:72-133: for every (loader, loader_stage), M repetitions; per batch a mask_p draw (Reg_MIWAE) and the
+    llh_eval imputation of every row with valid_k samples; the RMSE on ~mask per BATCH, averaged over the batches, then
+    over the repetitions.  The reference imputes one row per forward; here max_decoder_rows // valid_k rows go through
+    one launch sequence with the per-row pairing, which equals the single-row calls.  Returns {loader_stage: rmse} (0-dim
+    CPU tensors) and, with save=True, writes the reference's result files (miwae_result_path)."""
+    out = {}
+    with torch.no_grad():
+        if model is None:
+            model = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                                 p_missingness=p_missingness)
+        model.to(device)
+        is_reg = "reg_MIWAE" in vae_type
+        rows = max(1, max_decoder_rows // max(1, valid_k))
+        for loader, loader_stage in list_loaders:
+            recon = []
+            for _ in range(M):
+                XM = []
+                for data_sample, mask in loader:
+                    x = data_sample.to(device).float().reshape(-1, obs_dim)
+                    mask = mask.to(device).reshape(-1, obs_dim)
+                    mp = create_missing_uci(x.shape, p_missingness, device=device) * mask if is_reg else None
+                    xm = torch.empty_like(x)
+                    for lo in range(0, x.shape[0], rows):
+                        xm[lo:lo + rows] = model.impute(x[lo:lo + rows], mask[lo:lo + rows],
+                                                        None if mp is None else mp[lo:lo + rows], num_samples=valid_k)
+                    inv = ~mask if mask.dtype == torch.bool else (mask == 0)
+                    XM.append(torch.sqrt(torch.sum(torch.square(xm * inv - x * inv)) / torch.sum(inv)))
+                recon.append(torch.stack(XM).mean())
+            out[loader_stage] = torch.stack(recon).mean().cpu()
+            if save:
+                pth = miwae_result_path(experiment_type, data_type, vae_type, loader_stage, alpha, p_missingness,
+                                        reg_type)
+                os.makedirs(os.path.dirname(pth), exist_ok=True)
+                torch.save(out[loader_stage], pth)
+    return out

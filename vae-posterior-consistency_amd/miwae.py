@@ -1,0 +1,548 @@
+"""MIWAE path (Data/imputation_args.json runs reg_MIWAE* / vanilla_MIWAE*): drop-in classes for the reference's
+
+    MIWAE       src/models/VAE.py:3011-3134
+    Reg_MIWAE   src/models/VAE.py:3137-3301
+
+with the same constructor arguments, `encoder` / `decoder` / `forward` / `loss` signatures, return order and state_dict
+keys (seq_encoder.{0,2,4}, seq_decoder.{0,2,4}).  The six layers run as fp32 MFMA GEMMs (csrc/vpc_gemm.hip, ReLU
+between layers); the softplus sampler, the Student-t decoder heads and the importance-weighted bound with all of its
+gradients are csrc/vpc_miw.hip.  All twelve trainable tensors are views of one flat fp32 buffer.  No CPU fallback: CPU
+tensors raise.
+
+The reference's row / sample mix-up is reproduced, not fixed.  `logpxobsgivenz` is built in (row, sample) order and
+reshaped to [S, B] (VAE.py:3078-3081, :3209-3212, :3230-3233), while `logpz - logq` is [B, S].permute(1, 0)
+(:3089-3090, :3218-3219, :3239-3240).  For B > 1 and S > 1, slot (i, j) of the bound therefore pairs the likelihood of
+data row (i*B + j) // S, sample (i*B + j) % S with the prior / posterior terms of row j, sample i; the loss, its gradients
+and the llh_eval weights (applied to the un-mixed x_mean, :3096-3098 / :3267-3269) are those of this pairing.  With
+B == 1 (eval_miwae, one row per call) the pairing is the natural one, and the batched eval_miwae uses the per-row pairing
+(VPC_MIW_PAIR_PER_ROW), which equals N single-row calls.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .images import ParamKeyMixin
+from .notmiwae import ACT_NONE, ACT_RELU, _f32c, linear_dgrad, linear_fwd, linear_wgrad, nm_mul, nm_prep, wgrad_reduce
+from .trainer import _FlatAdamTrainer
+
+HID = 128  # VAE.py:3027-3042 / :3153-3168 hard-code 128 (hid_dim is ignored by the reference too)
+PAIR_REFERENCE, PAIR_PER_ROW = 0, 1
+
+
+# ------------------------------------------------------------------------------------------------ raw ops
+def miw_sample(heads, hact, eps, z, R, S, Ld):
+    check(lib().vpc_miw_sample(ptr(heads), ptr(hact), ptr(eps), ptr(z), int(R), int(S), int(Ld), stream_ptr()),
+          "vpc_miw_sample")
+
+
+def miw_sample_bwd(dz, eps, heads, g_hact, out, R, S, Ld):
+    check(lib().vpc_miw_sample_bwd(ptr(dz), ptr(eps), ptr(heads), ptr(g_hact), ptr(out), int(R), int(S), int(Ld),
+                                   stream_ptr()), "vpc_miw_sample_bwd")
+
+
+def miw_heads(y_raw, y_act, M, d):
+    check(lib().vpc_miw_heads(ptr(y_raw), ptr(y_act), int(M), int(d), stream_ptr()), "vpc_miw_heads")
+
+
+def miw_heads_bwd(y_raw, g_act, g_raw, M, d):
+    check(lib().vpc_miw_heads_bwd(ptr(y_raw), ptr(g_act), ptr(g_raw), int(M), int(d), stream_ptr()), "vpc_miw_heads_bwd")
+
+
+def miw_loss_scratch(B, S, device):
+    nbytes = int(lib().vpc_miw_loss_scratch(int(B), int(S)))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def miw_loss(x, mask, mask_p, y_q, y_p, ldy, raw, hq, hp, eq, ep, g_q, g_p, ldg, ghq, ghp, xm_imp, scratch, out8,
+             loss_f32, accum, B, S, d, Ld, alpha, pairing=PAIR_REFERENCE):
+    check(lib().vpc_miw_loss(ptr(x), ptr(mask), ptr(mask_p), ptr(y_q), ptr(y_p), int(ldy), int(raw), ptr(hq), ptr(hp),
+                             ptr(eq), ptr(ep), ptr(g_q), ptr(g_p), int(ldg), ptr(ghq), ptr(ghp), ptr(xm_imp),
+                             ptr(scratch), scratch.numel() * scratch.element_size(), ptr(out8), ptr(loss_f32),
+                             ptr(accum), int(B), int(S), int(d), int(Ld), float(alpha), int(pairing), stream_ptr()),
+          "vpc_miw_loss")
+
+
+def _joined(parts, M, W):
+    """Three [.., W] tensors that are the adjacent column blocks of ONE [M, 3W] buffer -> that buffer, else None."""
+    a, b, c = parts
+    if not all(t.dtype == torch.float32 and t.is_cuda for t in parts):
+        return None
+    if not (a.stride() == b.stride() == c.stride() and a.stride(-1) == 1 and a.stride(-2) == 3 * W and
+            b.data_ptr() == a.data_ptr() + 4 * W and c.data_ptr() == a.data_ptr() + 8 * W and
+            all(a.stride(i) == a.stride(i + 1) * a.shape[i + 1] for i in range(a.dim() - 2))):
+        return None
+    return a.as_strided((M, 3 * W), (3 * W, 1))
+
+
+# ------------------------------------------------------------------------------------------------ autograd
+class MIWEncoderFn(torch.autograd.Function):
+    """(x, mask, eps) -> (z [B,S,L], hact [B, mean L | scale L]).  VAE.py:3059-3070 / :3188-3200."""
+
+    @staticmethod
+    def forward(ctx, model, x, mask, eps, S, *weights):
+        require_cuda(x, mask, eps, *weights)
+        v = model._views()
+        d, Ld = model.obs_dim, model.latent_dim
+        B, dev = x.shape[0], x.device
+        xin = torch.empty(B, d, device=dev)
+        nm_mul(x, mask, xin)
+        h1, h2 = torch.empty(B, HID, device=dev), torch.empty(B, HID, device=dev)
+        heads, hact = torch.empty(B, 2 * Ld, device=dev), torch.empty(B, 2 * Ld, device=dev)
+        linear_fwd(xin, v["We1"], v["be1"], h1, B, HID, d, ACT_RELU)
+        linear_fwd(h1, v["We2"], v["be2"], h2, B, HID, HID, ACT_RELU)
+        linear_fwd(h2, v["Wh"], v["bh"], heads, B, 2 * Ld, HID, ACT_NONE)
+        z = torch.empty(B * S, Ld, device=dev)
+        miw_sample(heads, hact, eps, z, B, S, Ld)
+        ctx.model, ctx.S, ctx.has_eps = model, S, eps is not None
+        ctx.save_for_backward(xin, h1, h2, heads, eps if eps is not None else torch.empty(0, device=dev))
+        return z.view(B, S, Ld), hact
+
+    @staticmethod
+    def backward(ctx, dz, dhact):
+        model, S = ctx.model, ctx.S
+        xin, h1, h2, heads, eps = ctx.saved_tensors
+        v = model._views()
+        d, Ld = model.obs_dim, model.latent_dim
+        B, dev = xin.shape[0], xin.device
+        dht = torch.empty(B, 2 * Ld, device=dev)
+        miw_sample_bwd(None if dz is None else _f32c(dz).reshape(B * S, Ld), eps if ctx.has_eps else None, heads,
+                       None if dhact is None else _f32c(dhact), dht, B, S, Ld)
+        g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
+        dh2, dh1 = torch.empty(B, HID, device=dev), torch.empty(B, HID, device=dev)
+        linear_wgrad(dht, h2, g["Wh"], g["bh"], B, 2 * Ld, HID)
+        linear_dgrad(dht, v["Wh"], dh2, B, 2 * Ld, HID, x_out=h2, act_prev=ACT_RELU)
+        linear_wgrad(dh2, h1, g["We2"], g["be2"], B, HID, HID)
+        linear_dgrad(dh2, v["We2"], dh1, B, HID, HID, x_out=h1, act_prev=ACT_RELU)
+        linear_wgrad(dh1, xin, g["We1"], g["be1"], B, HID, d)
+        return (None, None, None, None, None, g["We1"], g["be1"], g["We2"], g["be2"], g["Wh"], g["bh"])
+
+
+class MIWDecoderFn(torch.autograd.Function):
+    """z [.., L] -> (mean, scale, df) as the three column blocks of ONE activated [M, 3d] buffer.  VAE.py:3072-3076."""
+
+    @staticmethod
+    def forward(ctx, model, z, *weights):
+        require_cuda(z, *weights)
+        v = model._views()
+        d, Ld = model.obs_dim, model.latent_dim
+        lead = z.shape[:-1]
+        z2 = _f32c(z).reshape(-1, Ld)
+        M, dev = z2.shape[0], z2.device
+        g1, g2 = torch.empty(M, HID, device=dev), torch.empty(M, HID, device=dev)
+        Y, Ya = torch.empty(M, 3 * d, device=dev), torch.empty(M, 3 * d, device=dev)
+        linear_fwd(z2, v["Wd1"], v["bd1"], g1, M, HID, Ld, ACT_RELU)
+        linear_fwd(g1, v["Wd2"], v["bd2"], g2, M, HID, HID, ACT_RELU)
+        linear_fwd(g2, v["Wx"], v["bx"], Y, M, 3 * d, HID, ACT_NONE)
+        miw_heads(Y, Ya, M, d)
+        ctx.model, ctx.lead = model, lead
+        ctx.save_for_backward(z2, g1, g2, Y)
+        Y3 = Ya.view(*lead, 3 * d)
+        return Y3[..., :d], Y3[..., d:2 * d], Y3[..., 2 * d:]
+
+    @staticmethod
+    def backward(ctx, gm, gs, gv):
+        model = ctx.model
+        z2, g1, g2, Y = ctx.saved_tensors
+        v = model._views()
+        d, Ld = model.obs_dim, model.latent_dim
+        M, dev = z2.shape[0], z2.device
+        parts = [torch.zeros(M, d, device=dev) if t is None else t for t in (gm, gs, gv)]
+        Ga = _joined(parts, M, d)
+        if Ga is None:
+            Ga = torch.cat([_f32c(t).reshape(M, d) for t in parts], 1)
+        G = torch.empty(M, 3 * d, device=dev)
+        miw_heads_bwd(Y, Ga, G, M, d)
+        g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
+        dg2, dg1, dz = torch.empty(M, HID, device=dev), torch.empty(M, HID, device=dev), torch.empty(M, Ld, device=dev)
+        linear_wgrad(G, g2, g["Wx"], g["bx"], M, 3 * d, HID)
+        linear_dgrad(G, v["Wx"], dg2, M, 3 * d, HID, x_out=g2, act_prev=ACT_RELU)
+        linear_wgrad(dg2, g1, g["Wd2"], g["bd2"], M, HID, HID)
+        linear_dgrad(dg2, v["Wd2"], dg1, M, HID, HID, x_out=g1, act_prev=ACT_RELU)
+        linear_wgrad(dg1, z2, g["Wd1"], g["bd1"], M, HID, Ld)
+        linear_dgrad(dg1, v["Wd1"], dz, M, HID, Ld)
+        return (None, dz.view(*ctx.lead, Ld), g["Wd1"], g["bd1"], g["Wd2"], g["bd2"], g["Wx"], g["bx"])
+
+
+class MIWLossFn(torch.autograd.Function):
+    """The bound on activated heads + every gradient (vpc_miw_loss, raw = 0).  Returns (loss fp32, out8, xm_imp)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, mask, mask_p, Yq, hq, eq, Yp, hp, ep):
+        reg = mask_p is not None
+        require_cuda(x, mask, mask_p, Yq, hq, eq, Yp, hp, ep)
+        B, S, d, Ld = cfg["B"], cfg["S"], cfg["d"], cfg["L"]
+        dev = x.device
+        need_grad = cfg["grad"] and any(ctx.needs_input_grad)
+        Gq = Gp = ghq = ghp = None
+        if need_grad:
+            Gq, ghq = torch.empty(B * S, 3 * d, device=dev), torch.empty(B, 2 * Ld, device=dev)
+            if reg:
+                Gp, ghp = torch.empty(B * S, 3 * d, device=dev), torch.empty(B, 2 * Ld, device=dev)
+        xm_imp = torch.empty(B, d, device=dev) if cfg["impute"] else None
+        out8 = torch.empty(8, dtype=torch.float64, device=dev)
+        miw_loss(x, mask, mask_p, Yq, Yp, 3 * d, 0, hq, hp, eq, ep, Gq, Gp, 3 * d, ghq, ghp, xm_imp,
+                 miw_loss_scratch(B, S, dev), out8, None, None, B, S, d, Ld, cfg["alpha"], cfg["pairing"])
+        ctx.reg, ctx.need_grad = reg, need_grad
+        if need_grad:
+            ctx.save_for_backward(*[t for t in (Gq, ghq, Gp, ghp) if t is not None])
+        imp = xm_imp if xm_imp is not None else torch.empty(0, device=dev)
+        ctx.mark_non_differentiable(out8, imp)
+        return out8[0].float(), out8, imp
+
+    @staticmethod
+    def backward(ctx, gloss, _g8, _gi):
+        if not ctx.need_grad:
+            return (None,) * 10
+        t = [u * gloss for u in ctx.saved_tensors]
+        if ctx.reg:
+            return None, None, None, None, t[0], t[1], None, t[2], t[3], None
+        return None, None, None, None, t[0], t[1], None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ model classes
+class _MIWBase(ParamKeyMixin, nn.Module):
+    regularised = False
+
+    def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
+        super().__init__()
+        if obs_dim > 256 or latent_dim > 64:
+            raise L.VpcError("the MIWAE-path kernels support obs_dim <= 256 and latent_dim <= 64")
+        self.obs_dim = obs_dim
+        self.hid_dim = hid_dim
+        self.emb_dim = 10
+        self.num_samples = num_samples
+        self.num_estimates = num_estimates
+        self.latent_dim = latent_dim
+        self.batch_size = training_parameters["batch_size"]
+        self.K = K
+        self.obs_std = 0.1
+        self.number_components = 500
+        self.training_paramters = training_parameters  # (sic) VAE.py:3024
+        d, Ld = obs_dim, latent_dim
+        # created in the reference's order (same seed -> same initial weights)
+        self.seq_encoder = nn.Sequential(nn.Linear(d, HID), nn.ReLU(), nn.Linear(HID, HID), nn.ReLU(),
+                                         nn.Linear(HID, 2 * Ld))
+        self.seq_decoder = nn.Sequential(nn.Linear(Ld, HID), nn.ReLU(), nn.Linear(HID, HID), nn.ReLU(),
+                                         nn.Linear(HID, 3 * d))
+        self.max_epoch = 2800
+        self._flat = None
+        self._view_cache = None
+        self._n_enc = HID * d + HID + HID * HID + HID + 2 * Ld * HID + 2 * Ld
+        self._n_dec = HID * Ld + HID + HID * HID + HID + 3 * d * HID + 3 * d
+
+    @property
+    def prior(self):  # VAE.py:3047 (a CPU distribution in the reference; kept for attribute parity)
+        return torch.distributions.Normal(torch.zeros(self.latent_dim), torch.ones(self.latent_dim))
+
+    # ---- flat parameter buffer: [We1 be1 We2 be2 Wh bh | Wd1 bd1 Wd2 bd2 Wx bx] = state_dict order
+    def trainable(self):
+        se, sd = self.seq_encoder, self.seq_decoder
+        return [se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias,
+                sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, sd[4].weight, sd[4].bias]
+
+    def flatten_parameters(self):
+        """Make the 12 trainable tensors views of ONE flat fp32 buffer.  Idempotent; call again after .to()."""
+        ps = self.trainable()
+        flat = self._flat
+        ok = flat is not None and flat.device == ps[0].device
+        off = 0
+        if ok:
+            for p in ps:
+                if p.data.data_ptr() != flat.data_ptr() + 4 * off or not p.data.is_contiguous():
+                    ok = False
+                    break
+                off += p.numel()
+        if not ok:
+            flat = torch.cat([p.data.detach().reshape(-1).float() for p in ps]).contiguous()
+            off = 0
+            for p in ps:
+                p.data = flat[off:off + p.numel()].view_as(p)
+                off += p.numel()
+            self._flat = flat
+            self._view_cache = None
+        return self._flat
+
+    def _segment_views(self, buf, which):
+        d, Ld = self.obs_dim, self.latent_dim
+        spec = {"enc": [("We1", (HID, d)), ("be1", (HID,)), ("We2", (HID, HID)), ("be2", (HID,)), ("Wh", (2 * Ld, HID)),
+                        ("bh", (2 * Ld,))],
+                "dec": [("Wd1", (HID, Ld)), ("bd1", (HID,)), ("Wd2", (HID, HID)), ("bd2", (HID,)), ("Wx", (3 * d, HID)),
+                        ("bx", (3 * d,))]}[which]
+        out, off = {}, 0
+        for name, shp in spec:
+            n = math.prod(shp)
+            out[name] = buf[off:off + n].view(shp)
+            off += n
+        return out
+
+    def _views(self):
+        vc, flat = self._view_cache, self._flat
+        if vc is not None and flat is not None and vc[0] is flat and \
+                self.seq_encoder[0].weight.data.data_ptr() == flat.data_ptr() and \
+                self.seq_decoder[4].bias.data.data_ptr() == flat.data_ptr() + 4 * (flat.numel() - 3 * self.obs_dim):
+            return vc[1]
+        flat = self.flatten_parameters()
+        L.require_cuda(flat)
+        v = self._segment_views(flat[:self._n_enc], "enc")
+        v.update(self._segment_views(flat[self._n_enc:], "dec"))
+        self._view_cache = (flat, v)
+        return v
+
+    def _enc_weights(self):
+        se = self.seq_encoder
+        return (se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias)
+
+    def _dec_weights(self):
+        sd = self.seq_decoder
+        return (sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, sd[4].weight, sd[4].bias)
+
+    # ---- reference API
+    def _encode(self, x, mask, sample=True, eps=None, S=None):
+        L.require_cuda(x)
+        d, Ld = self.obs_dim, self.latent_dim
+        S = self.num_samples if S is None else S
+        xf = _f32c(x.reshape(-1, d))
+        mf = _f32c(mask.reshape(-1, d).to(xf.device))
+        B = xf.shape[0]
+        if sample and eps is None:
+            eps = torch.randn(B, S, Ld, device=xf.device)  # Normal(mean, scale).rsample()
+        z, hact = MIWEncoderFn.apply(self, xf, mf, _f32c(eps) if sample else None, S, *self._enc_weights())
+        mean = hact[:, :Ld].unsqueeze(1).expand(B, S, Ld)
+        scale = hact[:, Ld:].unsqueeze(1).expand(B, S, Ld)
+        mean._vpc_hact = hact
+        scale._vpc_hact = hact
+        return z, mean, scale
+
+    def encoder(self, x, mask, sample=True):
+        """VAE.py:3049-3070 / :3178-3200 -> (z, mean, scale), each [B, num_samples, latent_dim]."""
+        return self._encode(x, mask, sample)
+
+    def decoder(self, z_int):
+        """VAE.py:3072-3076 / :3202-3206 -> (mean, scale, deg_free)."""
+        L.require_cuda(z_int)
+        return MIWDecoderFn.apply(self, z_int, *self._dec_weights())
+
+    @staticmethod
+    def _hact_of(mean, scale):
+        h = getattr(mean, "_vpc_hact", None)
+        if h is not None and h is getattr(scale, "_vpc_hact", None):
+            return h
+        return torch.cat([mean[:, 0, :], scale[:, 0, :]], 1)  # any [B,S,L] pair replicated over S
+
+    def _heads_Y(self, xm, xs, df, M):
+        d = self.obs_dim
+        # the decoder's three outputs are column blocks of one buffer: without autograd, pass that buffer itself (an
+        # as_strided view under autograd would route the whole gradient to the first output)
+        Y = None if torch.is_grad_enabled() else _joined((xm, xs, df), M, d)
+        return Y if Y is not None else torch.cat([_f32c(t).reshape(M, d) for t in (xm, xs, df)], 1)
+
+    def _loss(self, x, mask, mask_p, outs_q, outs_p, alpha, eps, llh_eval, pairing=PAIR_REFERENCE, S=None):
+        d, Ld = self.obs_dim, self.latent_dim
+        S = self.num_samples if S is None else S
+        xf = _f32c(x.reshape(-1, d))
+        B = xf.shape[0]
+        if eps is None:  # the fresh rsample() of loss(): q pass, then p pass (VAE.py:3216, :3237)
+            eps = [torch.randn(B, S, Ld, device=xf.device) for _ in range(1 if mask_p is None else 2)]
+        cfg = dict(B=B, S=S, d=d, L=Ld, alpha=alpha, grad=torch.is_grad_enabled(), impute=bool(llh_eval),
+                   pairing=pairing)
+        mf = _f32c(mask.reshape(-1, d).to(xf.device))
+        xm, xs, df, mean, scale = outs_q
+        Yq, hq = self._heads_Y(xm, xs, df, B * S), self._hact_of(mean, scale)
+        Yp = hp = mpf = ep = None
+        if outs_p is not None:
+            xm, xs, df, mean, scale = outs_p
+            Yp, hp = self._heads_Y(xm, xs, df, B * S), self._hact_of(mean, scale)
+            mpf = _f32c(mask_p.reshape(-1, d).to(xf.device))
+            ep = _f32c(eps[1])
+        return MIWLossFn.apply(cfg, xf, mf, mpf, Yq, hq, _f32c(eps[0]), Yp, hp, ep)
+
+    @torch.no_grad()
+    def impute(self, x, mask, mask_p=None, num_samples=None, pairing=PAIR_PER_ROW):
+        """llh_eval imputation of every row of x with num_samples draws, rows independent (per-row pairing): what
+        eval_miwae computes one row at a time (evaluate.py:89-111), for a whole chunk of rows in one launch sequence."""
+        S = self.num_samples if num_samples is None else num_samples
+        z_q, mean_q, scale_q = self._encode(x, mask, S=S)
+        outs_q = (*self.decoder(z_q), mean_q, scale_q)
+        outs_p = None
+        if self.regularised:
+            z_p, mean_p, scale_p = self._encode(x, mask_p, S=S)
+            outs_p = (*self.decoder(z_p), mean_p, scale_p)
+        _, _, xm = self._loss(x, mask, mask_p if self.regularised else None, outs_q, outs_p, 0.5, None, True, pairing, S)
+        return xm
+
+
+class MIWAE(_MIWBase):
+    """MIWAE with a Student-t decoder.  Reference: src/models/VAE.py:3011-3134."""
+
+    def forward(self, data, mask):
+        z, mean, scale = self.encoder(data, mask)
+        x_mean, x_scale, deg_free = self.decoder(z)
+        return mean, scale, x_mean, x_scale, deg_free
+
+    def loss(self, x, x_mean, x_scale, deg_free, mean, scale, mask, epoch, vae_elbo=False, llh_eval=False, MI=False,
+             beta_annealing=True, beta=1.0, stage="train", eps=None):
+        """VAE.py:3078-3114; draws the fresh z of :3087 on the device unless eps [B,S,L] is given."""
+        if MI:
+            raise NotImplementedError("the MI branch of the reference reads undefined names (VAE.py:3101-3106)")
+        loss, out8, xm = self._loss(x, mask, None, (x_mean, x_scale, deg_free, mean, scale), None, 0.0,
+                                    None if eps is None else [eps], llh_eval)
+        if llh_eval:  # VAE.py:3095-3099
+            return xm, loss, out8[5].float()
+        return loss, loss  # (print_loss, train_loss)
+
+
+class Reg_MIWAE(_MIWBase):
+    """Posterior-consistency regularised MIWAE.  Reference: src/models/VAE.py:3137-3301."""
+    regularised = True
+
+    def forward(self, data, mask, mask_p, stage="train"):
+        # VAE.py:3295-3301: q pass first (RNG order), p outputs returned first
+        z_q, mean_q, scale_q = self.encoder(data, mask)
+        x_mean_q, x_scale_q, deg_free_q = self.decoder(z_q)
+        z_p, mean_p, scale_p = self.encoder(data, mask_p)
+        x_mean_p, x_scale_p, deg_free_p = self.decoder(z_p)
+        return mean_p, scale_p, x_mean_p, x_scale_p, deg_free_p, mean_q, scale_q, x_mean_q, x_scale_q, deg_free_q
+
+    def loss(self, x, x_mean_p, x_scale_p, deg_free_p, mean_p, scale_p, x_mean_q, x_scale_q, deg_free_q, mean_q,
+             scale_q, mask, mask_p, epoch, vae_elbo=False, llh_eval=False, MI=False, beta_annealing=True, beta=1.0,
+             alpha=1.0, stage="train", eps=None):
+        """VAE.py:3208-3265; eps = (eps_q, eps_p) [B,S,L] for the two fresh draws of :3216 / :3237 (device draws
+        otherwise).  loss = nb_q + alpha * (KL_reg - nb_q + nb_p - reg_like)."""
+        if MI:
+            raise NotImplementedError("the MI branch of the reference reads undefined names (VAE.py:3271-3276)")
+        loss, out8, xm = self._loss(x, mask, mask_p, (x_mean_q, x_scale_q, deg_free_q, mean_q, scale_q),
+                                    (x_mean_p, x_scale_p, deg_free_p, mean_p, scale_p), alpha, eps, llh_eval)
+        if llh_eval:  # VAE.py:3266-3270
+            return xm, loss, loss
+        return loss, loss
+
+
+# ------------------------------------------------------------------------------------------------ fused step
+class MIWTrainer(_FlatAdamTrainer):
+    """The whole training step of the MIWAE path (train.py:102-117 for 'reg_MIWAE*' / the final branch for
+    'vanilla_MIWAE*') as a fixed sequence of HIP launches with no host synchronisation: mask_p draw + stacked encoder
+    input + Philox normals (one launch), the encoder and decoder GEMM chains with the q and p passes stacked along the
+    batch (one GEMM per layer), the three loss launches on the raw decoder heads, the backward GEMM chain into one flat
+    gradient, flat Adam.  fp32 only.
+
+    Single process only: the reference's row / sample pairing (module docstring) couples rows across the whole batch, so
+    a step sharded over ranks cannot equal the single-process step without an all-gather of the per-row sums."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
+        if not isinstance(model, _MIWBase):
+            raise TypeError("MIWTrainer supports MIWAE and Reg_MIWAE")
+        if world_size != 1:
+            raise L.VpcError("MIWTrainer is single-process: the reference's row/sample pairing couples rows across the "
+                             "global batch (no data-parallel form without an all-gather)")
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
+        self.reg = model.regularised
+        self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
+        self.g = model._segment_views(self.grad[:model._n_enc], "enc")
+        self.g.update(model._segment_views(self.grad[model._n_enc:], "dec"))
+        self._B = None
+
+    def _ws(self, B):
+        if self._B == B:
+            return
+        m, dev = self.model, self.dev
+        d, Ld, S = m.obs_dim, m.latent_dim, m.num_samples
+        P = 2 if self.reg else 1
+        R, M = P * B, P * B * S
+        e = lambda *s: torch.empty(*s, device=dev)
+        self.xin, self.mask_p = e(R, d), e(B, d)
+        self.h1, self.h2, self.heads, self.hact = e(R, HID), e(R, HID), e(R, 2 * Ld), e(R, 2 * Ld)
+        self.eps = e(2 * P, B, S, Ld)  # sampling draws of the P passes, then the loss-time draws
+        self.z, self.g1, self.g2, self.Y = e(M, Ld), e(M, HID), e(M, HID), e(M, 3 * d)
+        self.G, self.gh, self.dht = e(M, 3 * d), e(R, 2 * Ld), e(R, 2 * Ld)
+        self.dg2, self.dg1, self.dz, self.dh2, self.dh1 = e(M, HID), e(M, HID), e(M, Ld), e(R, HID), e(R, HID)
+        self.wg_shapes = [(M, 3 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)]
+        sizes = [int(lib().vpc_linear_wgrad_scratch(*sh)) for sh in self.wg_shapes]
+        buf = e(sum(sizes))
+        self.wg_scratch, o = [], 0
+        for n in sizes:
+            self.wg_scratch.append(buf[o:o + n])
+            o += n
+        self._wg_cache = {}
+        self.scratch = miw_loss_scratch(B, S, dev)
+        BS = B * S
+        self._sl = dict(Yp=self.Y[BS:] if self.reg else None, Gp=self.G[BS:] if self.reg else None,
+                        hp=self.hact[B:] if self.reg else None, ghp=self.gh[B:] if self.reg else None,
+                        eq=self.eps[P], ep=self.eps[P + 1] if self.reg else None, es=self.eps[:P])
+        self._B = B
+
+    def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30):
+        """One optimiser step.  mask_p [B,d] and eps ([4,B,S,L] = forward q, forward p, loss q, loss p for Reg_MIWAE;
+        [2,B,S,L] = forward, loss for MIWAE) may be injected for parity tests; otherwise they are drawn on the device."""
+        m = self.model
+        v = m._views()
+        d, Ld, S = m.obs_dim, m.latent_dim, m.num_samples
+        xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
+        L.require_cuda(xf, mf)
+        B = xf.shape[0]
+        self._ws(B)
+        reg = self.reg
+        P = 2 if reg else 1
+        R, M = P * B, P * B * S
+        t, sl, g = self._timed, self._sl, self.g
+        rng_inc = (self.eps.numel() + 3) // 4 + (B * d + 3) // 4 + 1
+        if reg and mask_p is not None:
+            mp = _f32c(mask_p.reshape(-1, d))
+            nm_mul(xf, mf, self.xin[:B])
+            nm_mul(xf, mp, self.xin[B:])
+            if eps is None:
+                from .ops import fill_normal
+                fill_normal(self.eps, self.seed, self.rng_offset + (1 << 40))
+        else:
+            mp = self.mask_p if reg else None
+            t("prep", nm_prep, xf, mf, mp, self.xin, B, d, 1.0 - p_missingness / 100.0, self.seed, self.rng_offset,
+              self.eps if eps is None else None, self.rng_offset + (1 << 40))
+        if eps is not None:
+            self.eps.copy_(eps.reshape(self.eps.shape))
+        self.rng_offset += rng_inc
+        # ---- forward
+        t("enc_fwd", linear_fwd, self.xin, v["We1"], v["be1"], self.h1, R, HID, d, ACT_RELU)
+        t("enc_fwd", linear_fwd, self.h1, v["We2"], v["be2"], self.h2, R, HID, HID, ACT_RELU)
+        t("enc_fwd", linear_fwd, self.h2, v["Wh"], v["bh"], self.heads, R, 2 * Ld, HID, ACT_NONE)
+        t("sample", miw_sample, self.heads, self.hact, sl["es"], self.z, R, S, Ld)
+        t("dec_fwd", linear_fwd, self.z, v["Wd1"], v["bd1"], self.g1, M, HID, Ld, ACT_RELU)
+        t("dec_fwd", linear_fwd, self.g1, v["Wd2"], v["bd2"], self.g2, M, HID, HID, ACT_RELU)
+        t("dec_fwd", linear_fwd, self.g2, v["Wx"], v["bx"], self.Y, M, 3 * d, HID, ACT_NONE)
+        # ---- loss on the raw heads: G = d loss / d raw decoder heads, gh = d loss / d (mean | scale)
+        t("loss", miw_loss, xf, mf, mp, self.Y, sl["Yp"], 3 * d, 1, self.hact, sl["hp"], sl["eq"], sl["ep"], self.G,
+          sl["Gp"], 3 * d, self.gh, sl["ghp"], None, self.scratch, self.out8, self.tail, self.accum, B, S, d, Ld, alpha,
+          PAIR_REFERENCE)
+        # ---- backward: weight-gradient partials per layer, all summed by one launch
+        defer = self.timers is None
+        pend = []
+
+        def wgrad(name, i, dy, xx, dw, db):
+            Mi, Ni, Ki = self.wg_shapes[i]
+            if not defer:
+                return t(name, linear_wgrad, dy, xx, dw, db, Mi, Ni, Ki)
+            linear_wgrad(dy, xx, None, None, Mi, Ni, Ki, scratch=self.wg_scratch[i])
+            pend.append((self.wg_scratch[i], Mi, Ni, Ki, dw, db, False))
+
+        wgrad("dec_bwd", 0, self.G, self.g2, g["Wx"], g["bx"])
+        t("dec_bwd", linear_dgrad, self.G, v["Wx"], self.dg2, M, 3 * d, HID, x_out=self.g2, act_prev=ACT_RELU)
+        wgrad("dec_bwd", 1, self.dg2, self.g1, g["Wd2"], g["bd2"])
+        t("dec_bwd", linear_dgrad, self.dg2, v["Wd2"], self.dg1, M, HID, HID, x_out=self.g1, act_prev=ACT_RELU)
+        wgrad("dec_bwd", 2, self.dg1, self.z, g["Wd1"], g["bd1"])
+        t("dec_bwd", linear_dgrad, self.dg1, v["Wd1"], self.dz, M, HID, Ld)
+        t("sample_bwd", miw_sample_bwd, self.dz, sl["es"], self.heads, self.gh, self.dht, R, S, Ld)
+        wgrad("enc_bwd", 3, self.dht, self.h2, g["Wh"], g["bh"])
+        t("enc_bwd", linear_dgrad, self.dht, v["Wh"], self.dh2, R, 2 * Ld, HID, x_out=self.h2, act_prev=ACT_RELU)
+        wgrad("enc_bwd", 4, self.dh2, self.h1, g["We2"], g["be2"])
+        t("enc_bwd", linear_dgrad, self.dh2, v["We2"], self.dh1, R, HID, HID, x_out=self.h1, act_prev=ACT_RELU)
+        wgrad("enc_bwd", 5, self.dh1, self.xin, g["We1"], g["be1"])
+        if pend:
+            wgrad_reduce(pend, self._wg_cache)
+        self.step_count += 1
+        from .ops import adam_step
+        t("adam", adam_step, m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
+          self.betas[1], self.adam_eps)
+        self._flat_written(None)
