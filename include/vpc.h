@@ -506,6 +506,48 @@ int vpc_miw_loss(const float* x, const float* mask, const float* mask_p, const f
                  void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum, long B, int S, int d,
                  int L, double alpha, int pairing, void* stream);
 
+/* ---- flow path: VAEFlow / REG_VAEFlow (csrc/vpc_flow.hip) -------------------------------------------------------
+ * Reference: src/models/VAE.py:1860-1996 and :1999-2124, posterior Flow :1816-1854 (three PiecewiseLinearCDF layers,
+ * tails "linear", tail_bound 1, context t.reshape(B, 10, 10), :1781-1813, spline :1680-1774).  Encoder
+ * [x*m | m] (2d) -> hid -> hid ELU -> 100 and decoder 10 -> hid x4 ELU -> d Sigmoid run on vpc_linear_fwd / dgrad /
+ * wgrad; these entry points add the per-step draws, the flow and the loss.  fp32; masks are float 0/1; the latent
+ * dimension is fixed at VPC_FLOW_LATENT (the reference's hard-coded 10 x 10 reshape).  `R` = rows of the stacked
+ * passes (R = B or 2 B), `B` = rows of one pass: the reference's torch.any(inside) (:1698) is taken per pass. */
+#define VPC_FLOW_LATENT 10
+#define VPC_FLOW_TRAIN 0
+#define VPC_FLOW_EVAL 1
+
+/* Per-step inputs in one launch (train.py:53-55 + VAE.py:1924-1931): xin[0:B] = [x * mask | mask] ([R][2d]) and, with
+ * a second pass, xin[B:2B] = [x * mask_p | mask_p] where mask_p = mask_p_in, or (mask_p_in NULL, mask_p_out != NULL) a
+ * fresh draw mask * (U < keep_prob) written to mask_p_out (the Philox counters of vpc_nm_prep's draw: element index / 4
+ * + offset).  n_eps > 0: eps_out[0:n_eps] ~ N(0, 1) (counter offset_eps; Flow.forward's rsample, :1824-1827). */
+int vpc_flow_prep(const float* x, const float* mask, const float* mask_p_in, float* mask_p_out, float* xin,
+                  float* eps_out, long n_eps, long B, int d, float keep_prob, unsigned long long seed,
+                  unsigned long long offset, unsigned long long offset_eps, void* stream);
+/* z, z_log_prob [R][10] = Flow.forward with the draws eps [R][10] and the contexts t [R][ldt >= 100] (:1816-1831,
+ * :1680-1774), the reference's quirks reproduced: context bins masked in place with the latent mask, outside inputs
+ * zeroed and splined, the identity when no draw of the pass is inside [-1, 1]. */
+int vpc_flow_fwd(const float* t, long ldt, const float* eps, float* z, float* z_log_prob, long R, long B, void* stream);
+/* dt [R][lddt >= 100] = d / d t given d / d z = dz + dz2 and d / d z_log_prob (each may be NULL); the forward is
+ * recomputed from (t, eps).  dt = 0 on masked bins and in a pass with no inside draw. */
+int vpc_flow_bwd(const float* t, long ldt, const float* eps, const float* dz, const float* dz2, const float* dz_log_prob,
+                 float* dt, long lddt, long R, long B, void* stream);
+/* Loss of REG_VAEFlow (mask_p != NULL; :2075-2111) or VAEFlow (mask_p == NULL; :1950-1969) at `stage`
+ * (VPC_FLOW_TRAIN / VPC_FLOW_EVAL, REG only; the evaluate stage reads no p-pass input) and, when g_x_mean_q != NULL,
+ * gscale * its gradients w.r.t. x_mean ([B][ldg] per pass; gated != 0: w.r.t. the decoder_mean PRE-activation, already
+ * through Sigmoid', so vpc_linear_dgrad / wgrad take y_gate = NULL), z and z_log_prob ([B][10] per pass; p-pass
+ * gradients are zero in the evaluate stage).  x_mean_* [B][ldxm] = the decoder's Sigmoid outputs; x_logvar is the
+ * constant -8 of :1946-1947.  out8 (device doubles) = loss (the unscaled sum; train_loss = loss / B), RE_q, RE_p, KL_q,
+ * KL_p, KL_reg, NLL of x*mask*~mask_p, RE_q_imputed (NLL on ~mask).  loss_f32 / accum (optional): train_loss as a
+ * float, and accum[0] += train_loss.  Two launches (per-row terms and gradients, fixed-order reduction of the
+ * per-workgroup partials) through `scratch` (vpc_flow_loss_scratch bytes, 8-byte aligned). */
+long vpc_flow_loss_scratch(long B);
+int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const float* x_mean_q, const float* x_mean_p,
+                  long ldxm, const float* z_q, const float* z_p, const float* z_log_prob_q, const float* z_log_prob_p,
+                  float* g_x_mean_q, float* g_x_mean_p, long ldg, float* g_z_q, float* g_z_p, float* g_z_log_prob_q,
+                  float* g_z_log_prob_p, void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum,
+                  long B, int d, int stage, float alpha, float beta, float gscale, int gated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

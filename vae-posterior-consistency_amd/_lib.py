@@ -109,13 +109,19 @@ _PROTOS = {
     "vpc_miw_heads_bwd": [P, P, P, L_, I, P],
     "vpc_miw_loss_scratch": [L_, I],
     "vpc_miw_loss": [P, P, P, P, P, L_, I, P, P, P, P, P, P, L_, P, P, P, P, L_, P, P, P, L_, I, I, I, C.c_double, I, P],
+    # flow path (csrc/vpc_flow.hip)
+    "vpc_flow_prep": [P, P, P, P, P, P, L_, L_, I, F, ULL, ULL, ULL, P],
+    "vpc_flow_fwd": [P, L_, P, P, P, L_, L_, P],
+    "vpc_flow_bwd": [P, L_, P, P, P, P, P, L_, L_, L_, P],
+    "vpc_flow_loss_scratch": [L_],
+    "vpc_flow_loss": [P, P, P, P, P, L_, P, P, P, P, P, P, L_, P, P, P, P, P, L_, P, P, P, L_, I, I, F, F, F, I, P],
     # PNP / EDDI encoder front-end
     "vpc_eddi_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
     "vpc_eddi_front_scratch": [L_, I, I],
     "vpc_eddi_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch"}
 
 _lib = None
 

@@ -186,6 +186,10 @@ def active_learning_func(data_loader_train, test_data, test_mask, missing_rate, 
     Returns dict(information_curve_CHAI [Repeat, n, d], action_CHAI [Repeat, n, d-1], R_hist_CHAI [Repeat, d-1, n, d-1],
     im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the reference's four files."""
     from .harness import create_missing_uci, model_loader
+    from .flow import _FlowBase
+    if isinstance(model, _FlowBase):
+        raise NotImplementedError("active_learning_func: the flow models' reward (R_lindley_chain_ratio_version, "
+                                  "evaluate.py) is not on the accelerated path")
     dev = torch.device(device) if device is not None else torch.device("cuda")
     n_test, d = test_data.shape[0], obs_dim
     info = torch.zeros(Repeat, n_test, d)

@@ -8,9 +8,10 @@
   eval_vae_mnar        src/experiment_main/evaluate.py:13-69    importance-weighted imputation RMSE (MNAR path)
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
-The families built are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI, REG_notMIWAE_v2,
-notMIWAE_myversion and MIWAE / Reg_MIWAE; the flow models raise NotImplementedError (out of scope, SURVEY.md
-section 8).
+The families model_loader builds are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI,
+REG_notMIWAE_v2, notMIWAE_myversion and MIWAE / Reg_MIWAE.  The flow models (VAEFlow / REG_VAEFlow, flow.py) are reached
+through their classes and the `model=` keyword of train() and eval_vae() (which then take the reference's flow branches,
+train.py:77-86 and evaluate.py:189-200); model_loader itself still raises NotImplementedError for flow vae_types.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ from .models import Reg_VAE, Reg_VAE_mask, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, notMIWAE_myversion
 from .eddi import EDDITrainer, Reg_EDDI, vanilla_EDDI
 from .miwae import MIWAE, MIWTrainer, Reg_MIWAE
+from .flow import FlowTrainer, _FlowBase
 
 _seed_counter = [0]
 
@@ -104,20 +106,24 @@ def model_loader(stage, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type
 def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
           experiment_type, vae_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), alpha=1.0,
           stage="train", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True,
-          not_miwae_type="changed", fused=True, seed=0, save=True, verbose=True):
-    """train.py:13-133 for reg_vae* / vanilla_vae* / *_notMIWAE* / *_EDDI* / *MIWAE*.  With fused=True every batch is one trainer step (no
-    per-step host sync: the epoch total is read once per epoch, as the reference only prints it per epoch);
+          not_miwae_type="changed", fused=True, seed=0, save=True, verbose=True, model=None):
+    """train.py:13-133 for reg_vae* / vanilla_vae* / *_notMIWAE* / *_EDDI* / *MIWAE*, and for a VAEFlow / REG_VAEFlow
+    passed as `model` (train.py:77-86; model_loader does not build flows).  With fused=True every batch is one trainer
+    step (no per-step host sync: the epoch total is read once per epoch, as the reference only prints it per epoch);
     with fused=False it is the reference's own sequence model.forward -> model.loss -> backward -> optim.Adam
-    on the API path.  Returns the trained model."""
-    model = model_loader("train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                         max_epochs, train_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
-                         p_missingness=p_missingness)
+    on the API path.  `model` (optional): train this model instead of a fresh one from model_loader.  Returns the
+    trained model."""
+    if model is None:
+        model = model_loader("train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                             max_epochs, train_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                             p_missingness=p_missingness)
     model.to(device)
     nm = "notMIWAE" in vae_type
     loader = data_loader_train if nm else data_loader_train[0]  # train.py:22-25
     is_reg = "reg" in vae_type
     eddi = "EDDI" in vae_type
     miw = isinstance(model, (MIWAE, Reg_MIWAE))
+    flow = isinstance(model, _FlowBase)
     # 'with_drop' variants (train.py:32-37, 50-51; vanilla classes only - the reference's regularised branch never draws mask_p
     # beside it): the model sees mask * mask_drop, the keep-mask of create_missing_uci_drop_eddi (utils.py:42-45)
     drop = "with_drop" in vae_type and not is_reg
@@ -126,8 +132,8 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
             from .wide import WideTrainer
             trainer = WideTrainer(model, lr=0.001, seed=seed)
         else:
-            trainer = (MIWTrainer if miw else NMTrainer if nm else EDDITrainer if eddi else FusedTrainer)(model, lr=0.001,
-                                                                                                        seed=seed)
+            trainer = (FlowTrainer if flow else MIWTrainer if miw else NMTrainer if nm else EDDITrainer if eddi else
+                       FusedTrainer)(model, lr=0.001, seed=seed)
     else:
         model.flatten_parameters()
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001)  # train.py:21
@@ -138,8 +144,25 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
             mask = mask.to(device)
             if fused and drop:  # the fused vanilla step on the thinned mask (one more elementwise launch, no host sync)
                 mask = mask.to(torch.float32) * create_missing_uci_drop_eddi(data_sample.shape, device=device)
+            if fused and flow:
+                trainer.step(data_sample, mask, alpha=alpha, p_missingness=p_missingness, stage=stage)
+                continue
             if fused and (nm or miw):
                 trainer.step(data_sample, mask, alpha=alpha, p_missingness=p_missingness)
+                continue
+            if flow:
+                if model.regularised:  # train.py:53-55, 77-81
+                    mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
+                    o = model.forward(data_sample, mask, mask_p)
+                    _, train_loss = model.loss(data_sample, o[6], o[7], o[4], o[5], o[2], o[3], o[0], o[1], mask,
+                                               mask_p, alpha, stage=stage)
+                else:  # train.py:82-85
+                    o = model.forward(data_sample, mask)
+                    _, train_loss = model.loss(data_sample, o[2], o[3], o[0], o[1], mask)
+                optimizer.zero_grad()
+                train_loss.backward()
+                optimizer.step()
+                total_loss += train_loss.item()
                 continue
             if miw:
                 if is_reg:  # train.py:53-55, 102-108
@@ -213,7 +236,8 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
              experiment_type, vae_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), alpha=0.5,
              stage="evaluate", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False,
              alpha_annealing=True, model=None, save=True):
-    """evaluate.py:136-297 for reg_vae* / vanilla_vae*: reload the checkpoint (or use `model`), and for every
+    """evaluate.py:136-297 for reg_vae* / vanilla_vae* and, given as `model`, VAEFlow / REG_VAEFlow (the flow branch,
+    evaluate.py:189-200): reload the checkpoint (or use `model`), and for every
     (loader, loader_stage): M Monte-Carlo passes of forward + loss(llh_eval=True, stage) per batch; RMSE of the
     imputations on the UNobserved entries, mean ELBO, NLL on observed and on imputed entries.  Returns
     {loader_stage: dict(rmse, elbo, negll, negll_imp)} and (save=True) writes the reference's four files."""
@@ -232,7 +256,20 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
                 elbos, negls, negls_imp, temp_recon = [], [], [], []
                 for data_sample, mask in loader:
                     data_sample, mask = data_sample.to(device), mask.to(device)
-                    if is_reg:  # evaluate.py:172-173, 210-216
+                    if isinstance(model, _FlowBase):  # evaluate.py:172-173, 189-200
+                        if model.regularised:
+                            mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
+                            o = model.forward(data_sample, mask, mask_p)
+                            _, train_loss, negl, negl_imp = model.loss(data_sample, o[6], o[7], o[4], o[5], o[2], o[3],
+                                                                       o[0], o[1], mask, mask_p, alpha, llh_eval=True,
+                                                                       stage=stage)
+                            x_mean = o[6]
+                        else:
+                            o = model.forward(data_sample, mask)
+                            _, train_loss, negl, negl_imp = model.loss(data_sample, o[2], o[3], o[0], o[1], mask,
+                                                                       llh_eval=True)
+                            x_mean = o[2]
+                    elif is_reg:  # evaluate.py:172-173, 210-216
                         mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
                         o = model.forward(data_sample, mask, mask_p, stage=stage)
                         _, train_loss, negl, negl_imp = model.loss(
