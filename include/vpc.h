@@ -413,6 +413,20 @@ int vpc_eddi_front_bwd(const float* x, const uint8_t* mask, const uint8_t* mask2
                        const float* E, const float* tb, const float* Wp, float* scratch, long scratch_floats, float* gE,
                        float* gtb, float* gWp, float* gcp, int accumulate, long B, int d, int K, void* stream);
 
+/* ---- the same front-end at image width (Reg_EDDI_mnist / vanilla_EDDI_mnist, src/models/VAE.py:62-77, 255-270) -------
+ * Same arguments, layouts and meaning as the four entry points above, for any d <= 1024 (784: MNIST), K <= 32
+ * (csrc/vpc_eddiw.hip: the folded table is tiled along k, 4 rows of A and C per workgroup over all d features, because
+ * [2][K][d] no longer fits LDS).  vpc_eddiw_front_bwd recomputes the ReLU gates and sums its per-workgroup partial blocks in a
+ * fixed order: the same inputs give bitwise the same gradients.  scratch: vpc_eddiw_front_scratch(rows, d, K) floats. */
+int vpc_eddiw_fold(const float* E, const float* tb, const float* Wp, const float* cp, float* AC, int d, int K,
+                   void* stream);
+int vpc_eddiw_front_fwd(const float* x, const uint8_t* mask, const uint8_t* mask2, const float* AC, float* agg, long B,
+                        int d, int K, void* stream);
+long vpc_eddiw_front_scratch(long rows, int d, int K);
+int vpc_eddiw_front_bwd(const float* x, const uint8_t* mask, const uint8_t* mask2, const float* AC, const float* dagg,
+                        const float* E, const float* tb, const float* Wp, float* scratch, long scratch_floats, float* gE,
+                        float* gtb, float* gWp, float* gcp, int accumulate, long B, int d, int K, void* stream);
+
 /* ---- whole-step kernel, plain bf16 (csrc/vpc_step.hip): vpc_encoder_fwd + vpc_decoder_fused + vpc_encoder_bwd with
  * precision 2 as ONE launch per 128-row tile - the step body of src/experiment_main/train.py:87-115 for Reg_VAE /
  * vanilla_VAE (src/models/VAE.py:496-507 forward, :403-467 loss, autograd backward) with nothing but x, the masks and eps

@@ -18,6 +18,8 @@ from .flow import VAEFlow, REG_VAEFlow, FlowTrainer
 from . import notmiwae
 from . import eddi
 from .eddi import Reg_EDDI, vanilla_EDDI, EDDITrainer
+from . import eddi_mnist
+from .eddi_mnist import Reg_EDDI_mnist, vanilla_EDDI_mnist, EDDIMnistTrainer
 from . import ops
 from . import dist as dp
 from . import active
@@ -29,4 +31,5 @@ from .active import (reward_matrix, R_lindley_chain, chaini_I, chaini_II, active
 __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedTrainer", "REG_notMIWAE_v2",
            "notMIWAE_myversion", "NMTrainer", "notmiwae", "eddi", "Reg_EDDI", "vanilla_EDDI", "EDDITrainer", "eval_vae_mnar", "mnar_result_path", "create_missing_uci", "create_missing_uci_drop_eddi", "model_loader", "checkpoint_path", "train", "eval_vae", "result_paths",
            "VpcError", "ops", "dp", "LIB_PATH", "MAX_EPOCH", "active", "reward_matrix", "R_lindley_chain", "chaini_I",
-           "chaini_II", "miwae", "MIWAE", "Reg_MIWAE", "MIWTrainer", "eval_miwae", "miwae_result_path", "flow", "VAEFlow", "REG_VAEFlow", "FlowTrainer"]
+           "chaini_II", "miwae", "MIWAE", "Reg_MIWAE", "MIWTrainer", "eval_miwae", "miwae_result_path", "flow", "VAEFlow", "REG_VAEFlow", "FlowTrainer",
+           "eddi_mnist", "Reg_EDDI_mnist", "vanilla_EDDI_mnist", "EDDIMnistTrainer"]

@@ -120,8 +120,13 @@ _PROTOS = {
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
     "vpc_eddi_front_scratch": [L_, I, I],
     "vpc_eddi_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
+    # the same front-end at image width (csrc/vpc_eddiw.hip)
+    "vpc_eddiw_fold": [P, P, P, P, P, I, I, P],
+    "vpc_eddiw_front_fwd": [P, P, P, P, P, L_, I, I, P],
+    "vpc_eddiw_front_scratch": [L_, I, I],
+    "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch"}
 
 _lib = None
 

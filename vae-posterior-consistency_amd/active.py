@@ -59,6 +59,9 @@ def reward_matrix(vae, x, mask, im):
     Every 'reg_vae*' / 'vanilla_vae*' (mask-augmented and wide included) and '*_EDDI*' model of model_loader with
     latent_dim <= 15."""
     L.require_cuda(x, im)
+    if getattr(vae, "_eddi_mnist", False):
+        raise L.VpcError("reward_matrix: Reg_EDDI_mnist / vanilla_EDDI_mnist are not supported (active learning at image "
+                         "width is not a reference configuration)")
     if vae.latent_dim > 15:
         raise L.VpcError("reward_matrix: latent_dim <= 15 is supported (the mean / logvar heads are one 16-row tile)")
     if _is_pointnet(vae) or vae.mask_augm or vae._wide:

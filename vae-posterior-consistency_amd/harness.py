@@ -8,8 +8,8 @@
   eval_vae_mnar        src/experiment_main/evaluate.py:13-69    importance-weighted imputation RMSE (MNAR path)
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
-The families model_loader builds are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI,
-REG_notMIWAE_v2, notMIWAE_myversion and MIWAE / Reg_MIWAE.  The flow models (VAEFlow / REG_VAEFlow, flow.py) are reached
+The families model_loader builds are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI (and, for
+data_type == 'mnist', Reg_EDDI_mnist / vanilla_EDDI_mnist), REG_notMIWAE_v2, notMIWAE_myversion and MIWAE / Reg_MIWAE.  The flow models (VAEFlow / REG_VAEFlow, flow.py) are reached
 through their classes and the `model=` keyword of train() and eval_vae() (which then take the reference's flow branches,
 train.py:77-86 and evaluate.py:189-200); model_loader itself still raises NotImplementedError for flow vae_types.
 """
@@ -25,6 +25,7 @@ from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, notMIWAE_myversion
 from .eddi import EDDITrainer, Reg_EDDI, vanilla_EDDI
+from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _EDDIMnistBase
 from .miwae import MIWAE, MIWTrainer, Reg_MIWAE
 from .flow import FlowTrainer, _FlowBase
 
@@ -68,9 +69,9 @@ def model_loader(stage, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type
                  num_samples, num_estimates, experiment_type, reg_type, vae_type="vae", alpha=1.0, p_missingness=30,
                  beta=0.5, beta_annealing=True, alpha_annealing=True, not_miwae_type="changed"):
     """Same positional signature and substring dispatch as loaders.py:13-246 for the in-scope families."""
-    if "flow" in vae_type or ("EDDI" in vae_type and data_type == "mnist"):
+    if "flow" in vae_type:
         raise NotImplementedError(f"vae_type {vae_type!r}: only reg_vae* / vanilla_vae* / *_notMIWAE* / *MIWAE* / *_EDDI* "
-                                  "(UCI) are on the accelerated path")
+                                  "are on the accelerated path")
     augm = "mask_augm" in vae_type  # loaders.py:47, 143
     if "reg_notMIWAE" in vae_type:  # loaders.py:89-103
         model = REG_notMIWAE_v2(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
@@ -80,6 +81,12 @@ def model_loader(stage, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type
         model = Reg_MIWAE(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
     elif "MIWAE" in vae_type and "notMIWAE" not in vae_type:  # loaders.py:234-244 (the final else: vanilla_MIWAE*)
         model = MIWAE(obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
+    elif "reg_EDDI" in vae_type and data_type == "mnist":  # loaders.py:104-109
+        model = Reg_EDDI_mnist(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, reg_type, num_samples,
+                               num_estimates)
+    elif "vanilla_EDDI" in vae_type and data_type == "mnist":  # loaders.py:185-190
+        model = vanilla_EDDI_mnist(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples,
+                                   num_estimates)
     elif "reg_EDDI" in vae_type:  # loaders.py:104-131 (UCI branch)
         model = Reg_EDDI(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, reg_type, num_samples,
                          num_estimates)
@@ -128,7 +135,9 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
     # beside it): the model sees mask * mask_drop, the keep-mask of create_missing_uci_drop_eddi (utils.py:42-45)
     drop = "with_drop" in vae_type and not is_reg
     if fused:
-        if getattr(model, "_wide", False):  # encoder input > 128 columns: the generic-GEMM step (wide.py)
+        if isinstance(model, _EDDIMnistBase):  # data_type == 'mnist' (train.py:31-47): the image-width point-net step
+            trainer = EDDIMnistTrainer(model, lr=0.001, seed=seed)
+        elif getattr(model, "_wide", False):  # encoder input > 128 columns: the generic-GEMM step (wide.py)
             from .wide import WideTrainer
             trainer = WideTrainer(model, lr=0.001, seed=seed)
         else:
