@@ -562,6 +562,28 @@ int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const 
                   float* g_z_log_prob_p, void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum,
                   long B, int d, int stage, float alpha, float beta, float gscale, int gated, void* stream);
 
+/* ---- config 5 reward of the flow models (csrc/vpc_flowreward.hip) ------------------------------------------------
+ * Replaces the flow branch of active_learning_func's candidate loop (src/experiment_main/evaluate.py:416-422) and the
+ * functions it calls: R_lindley_chain_ratio_version (:637-665), chaini_I_ratio_version (:669-684),
+ * chaini_II_ratio_version (:688-708).  For every row n and candidate u < d-1 with mask[n][u] == 0
+ *     R[n][u] = 1/M sum_m [ sum_l |lp_Ia - lp_Ib| - sum_l |lp_IIa - lp_IIb| ]       (-1e4 where mask[n][u] != 0)
+ * where each lp is the z_log_prob [10] of one VAEFlow.encoder call (VAE.py:1924-1931) on the rows loc(u) =
+ * {n : mask[n][u] == 0} with its own draw, in the call order Ia, Ib, IIa, IIb inside the m loop; the carry-over of the
+ * imputed target between samples (:653-658) and the per-call torch.any(inside) (VAE.py:1698, over loc(u) x 10) are
+ * reproduced.  x [n][d], mask [n][d] float 0/1, im [M][n][d]; We1 [hid][2d] .. be3 [100] = seq_encoder.{0,2,4};
+ * eps = the draws as a dense [d-1][M][4][n][10] tensor (rows outside loc(u) ignored; 16-byte aligned) or NULL: then
+ * they come from Philox(seed), the counter of a value being its index in that tensor.  R [n][d-1].
+ * Candidates are processed `chunk` at a time through `scratch` (vpc_flow_reward_scratch floats, 16-byte aligned); R does
+ * not depend on `chunk`.  d >= 2, 1 <= hid <= 512, M >= 1, chunk >= 1; anything else returns an error before any launch. */
+int vpc_flow_reward_scratch(int n, int d, int hid, int M, int chunk, long* scratch_floats);
+int vpc_flow_reward_matrix(const float* x, const float* mask, const float* im, const float* We1, const float* be1,
+                           const float* We2, const float* be2, const float* We3, const float* be3, const float* eps,
+                           unsigned long long seed, float* scratch, long scratch_floats, float* R, int n, int d, int hid,
+                           int M, int chunk, void* stream);
+/* eps [d-1][M][4][n][10] ~ N(0, 1): the draws vpc_flow_reward_matrix(eps = NULL, seed) uses (Flow.forward's rsample,
+ * VAE.py:1824-1827, one per encoder call of evaluate.py:680-682, 704-706). */
+int vpc_flow_reward_draws(float* eps, int n, int d, int M, unsigned long long seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,10 @@ _PROTOS = {
     "vpc_flow_bwd": [P, L_, P, P, P, P, P, L_, L_, L_, P],
     "vpc_flow_loss_scratch": [L_],
     "vpc_flow_loss": [P, P, P, P, P, L_, P, P, P, P, P, P, L_, P, P, P, P, P, L_, P, P, P, L_, I, I, F, F, F, I, P],
+    # config 5 reward of the flow models (csrc/vpc_flowreward.hip)
+    "vpc_flow_reward_scratch": [I, I, I, I, I, C.POINTER(L_)],
+    "vpc_flow_reward_matrix": [P, P, P, P, P, P, P, P, P, P, ULL, P, L_, P, I, I, I, I, I, P],
+    "vpc_flow_reward_draws": [P, I, I, I, ULL, P],
     # PNP / EDDI encoder front-end
     "vpc_eddi_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],

@@ -5,6 +5,10 @@ src/experiment_main/evaluate.py:514-634 on the GPU.
 launches (vpc_reward_matrix for the plain Reg_VAE / vanilla_VAE with obs_dim <= 128; vpc_reward_matrix_ex for the
 mask-augmented, the wide and the EDDI models); `R_lindley_chain`, `chaini_I`, `chaini_II` keep the reference's
 signatures so that evaluate.py can call them unchanged.
+
+The flow models (VAEFlow / REG_VAEFlow) take the ratio-version reward of evaluate.py:637-708 instead:
+`flow_reward_matrix` (vpc_flow_reward_matrix, csrc/vpc_flowreward.hip), the drop-ins `R_lindley_chain_ratio_version`,
+`chaini_I_ratio_version`, `chaini_II_ratio_version`, and the loop `active_learning_flow`.
 """
 from __future__ import annotations
 
@@ -28,6 +32,11 @@ _H1, _H2 = 100, 50
 def _is_pointnet(vae):
     from .eddi import _EDDIBase
     return isinstance(vae, _EDDIBase)
+
+
+def _is_flow(vae):
+    from .flow import _FlowBase
+    return isinstance(vae, _FlowBase)
 
 
 def _w23_image(vae):
@@ -59,6 +68,8 @@ def reward_matrix(vae, x, mask, im):
     Every 'reg_vae*' / 'vanilla_vae*' (mask-augmented and wide included) and '*_EDDI*' model of model_loader with
     latent_dim <= 15."""
     L.require_cuda(x, im)
+    if _is_flow(vae):
+        return flow_reward_matrix(vae, x, mask, im)
     if getattr(vae, "_eddi_mnist", False):
         raise L.VpcError("reward_matrix: Reg_EDDI_mnist / vanilla_EDDI_mnist are not supported (active learning at image "
                          "width is not a reference configuration)")
@@ -110,6 +121,94 @@ def _reward_matrix_ex(vae, x, mask, im):
                                      ptr(b1.data), ptr(AC), K, ptr(w23), ptr(pre), ptr(stat), ptr(w1t), ptr(R), n, d,
                                      vae.latent_dim, M, stream_ptr()), "vpc_reward_matrix_ex")
     return R
+
+
+# ------------------------------------------------------------------------------------------------ flow models
+FLOW_REWARD_WS_FLOATS = 64 << 20  # default bound of the per-chunk workspace (256 MB)
+
+
+def flow_reward_chunk(n, d, hid, M, budget_floats=FLOW_REWARD_WS_FLOATS):
+    """Candidates per chunk so that the chunk's part of the workspace stays within `budget_floats`."""
+    per_u = 2 * M * n * (((hid + 3) & ~3) + 100 + 20) + M * n + 4 * M
+    return max(1, min(d - 1, budget_floats // per_u))
+
+
+def flow_reward_draws(n, d, M, seed, device=None):
+    """eps [d-1, M, 4, n, 10] ~ N(0, 1): the draws flow_reward_matrix(seed=seed) uses (vpc_flow_reward_draws)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    eps = torch.empty(d - 1, M, 4, n, 10, device=dev)
+    check(lib().vpc_flow_reward_draws(ptr(eps), n, d, M, int(seed), stream_ptr()), "vpc_flow_reward_draws")
+    return eps
+
+
+def flow_reward_matrix(vae, x, mask, im, eps=None, seed=None, chunk=None):
+    """R [n, d-1] of a VAEFlow / REG_VAEFlow: the reward of evaluate.py:637-708 for every candidate of every row
+    (-1e4 where already observed), vpc_flow_reward_matrix.  x [n, d]; mask [n, d]; im [M, n, d]; target = last column.
+    eps: the draws of the 4 encoder calls per (candidate, sample) as a dense [d-1, M, 4, n, 10] tensor (call order Ia,
+    Ib, IIa, IIb; rows outside loc(u) ignored); None: drawn on the device from `seed` (None: torch's generator picks
+    one).  chunk: candidates per pass through the workspace (None: flow_reward_chunk); R does not depend on it."""
+    if not _is_flow(vae):
+        raise TypeError("flow_reward_matrix supports VAEFlow and REG_VAEFlow")
+    L.require_cuda(x, im, eps)
+    n, d = x.shape
+    M = im.shape[0]
+    hid = vae.hid_dim
+    dev = x.device
+    if d != vae.obs_dim or tuple(im.shape) != (M, n, d) or tuple(mask.shape) != (n, d):
+        raise L.VpcError(f"flow_reward_matrix: x {tuple(x.shape)}, mask {tuple(mask.shape)}, im {tuple(im.shape)} do "
+                         f"not fit obs_dim {vae.obs_dim}")
+    if hid > 512:
+        raise L.VpcError(f"flow_reward_matrix: hid_dim {hid} > 512 is not supported")
+    if eps is not None and tuple(eps.shape) != (d - 1, M, 4, n, 10):
+        raise L.VpcError(f"flow_reward_matrix: eps {tuple(eps.shape)}, expected {(d - 1, M, 4, n, 10)}")
+    if eps is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    chunk = flow_reward_chunk(n, d, hid, M) if chunk is None else int(chunk)
+    v = vae._views()
+    size = C.c_long()
+    check(lib().vpc_flow_reward_scratch(n, d, hid, M, chunk, C.byref(size)), "vpc_flow_reward_scratch")
+    ws = torch.empty(size.value, device=dev)
+    R = torch.empty(n, d - 1, device=dev)
+    mf = _f32c((mask.to(dev) != 0))
+    check(lib().vpc_flow_reward_matrix(ptr(_f32c(x)), ptr(mf), ptr(_f32c(im)), *[ptr(v[k]) for k in vae._ENC_NAMES],
+                                       ptr(None if eps is None else _f32c(eps)), int(seed or 0), ptr(ws), size.value,
+                                       ptr(R), n, d, hid, M, chunk, stream_ptr()), "vpc_flow_reward_matrix")
+    return R
+
+
+def R_lindley_chain_ratio_version(i, x, mask, M, vae, im, loc, eps=None):
+    """Same signature / result as evaluate.py:637-665 (rows `loc`, candidate `i`).  Prefer flow_reward_matrix: it
+    returns every candidate of every row for the price of this one call.  eps (an addition): the candidate's draws
+    [M, 4, len(loc), 10] in call order."""
+    loc_t = torch.as_tensor(loc, device=x.device, dtype=torch.long)
+    dense = None
+    if eps is not None:
+        dense = torch.zeros(x.shape[1] - 1, *eps.shape, device=x.device)
+        dense[i] = eps
+    R = flow_reward_matrix(vae, x[loc_t].float(), mask[loc_t], im[:M][:, loc_t].float(), eps=dense)
+    return R[:, i]
+
+
+def _ratio(x, mask, i, vae, eps, target_observed):
+    tm = mask.clone().float()
+    if target_observed:
+        tm[:, -1] = 1
+    e = (None, None) if eps is None else eps
+    with torch.no_grad():
+        _, lp = vae._encode(x, tm, eps=e[0])
+        tm[:, i] = 1
+        _, lp_i = vae._encode(x, tm, eps=e[1])
+    return torch.abs(lp - lp_i).sum(1)
+
+
+def chaini_I_ratio_version(x, mask, i, vae, eps=None):
+    """evaluate.py:669-684 on the API path: two vae.encoder calls.  eps (an addition): their draws [2, rows, 10]."""
+    return _ratio(x, mask, i, vae, eps, False)
+
+
+def chaini_II_ratio_version(x, mask, i, vae, eps=None):
+    """evaluate.py:688-708: the same with the target marked observed."""
+    return _ratio(x, mask, i, vae, eps, True)
 
 
 def R_lindley_chain(i, x, mask, M, vae, im, loc):
@@ -188,11 +287,32 @@ def active_learning_func(data_loader_train, test_data, test_mask, missing_rate, 
     pass (tests replay the outputs recorded from the reference, whose eps come from the global RNG).
     Returns dict(information_curve_CHAI [Repeat, n, d], action_CHAI [Repeat, n, d-1], R_hist_CHAI [Repeat, d-1, n, d-1],
     im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the reference's four files."""
-    from .harness import create_missing_uci, model_loader
-    from .flow import _FlowBase
-    if isinstance(model, _FlowBase):
+    from .harness import model_loader
+    if _is_flow(model):
         raise NotImplementedError("active_learning_func: the flow models' reward (R_lindley_chain_ratio_version, "
                                   "evaluate.py) is not on the accelerated path")
+
+    def load():
+        return model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                            max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                            p_missingness=p_missingness, alpha_annealing=alpha_annealing)
+
+    def passes(mdl, x, cur_mask, mask_p):
+        if _forward is not None:
+            return torch.stack([_forward(cur_mask).to(x.device) for _ in range(M)], 0)
+        return mc_forward(mdl, x, cur_mask, mask_p, M, stage)
+
+    out = _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, Repeat, model, load, passes,
+                            lambda mdl, x, mask, im, t: reward_matrix(mdl, x, mask, im), verbose, max_steps)
+    return _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
+
+
+def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, Repeat, model, load, passes, reward,
+                      verbose, max_steps):
+    """The loop body of evaluate.py:340-455 shared by active_learning_func and active_learning_flow.
+    load() -> a model for a repeat without one; passes(mdl, x, mask, mask_p) -> x_mean [M, n, d];
+    reward(mdl, x, mask, im, step) -> R [n, d-1]."""
+    from .harness import create_missing_uci
     dev = torch.device(device) if device is not None else torch.device("cuda")
     n_test, d = test_data.shape[0], obs_dim
     info = torch.zeros(Repeat, n_test, d)
@@ -204,39 +324,64 @@ def active_learning_func(data_loader_train, test_data, test_mask, missing_rate, 
     eye = torch.eye(d, device=dev)
     with torch.no_grad():
         for r in range(Repeat):
-            if model is None or r > 0:
-                mdl = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                                   max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
-                                   p_missingness=p_missingness, alpha_annealing=alpha_annealing).to(dev)
-            else:
-                mdl = model.to(dev)
+            mdl = (load() if model is None or r > 0 else model).to(dev)
             mask_p = tmask * create_missing_uci(tuple(test_data.shape), p_missingness, device=dev)  # evaluate.py:349-350
             mask = torch.zeros(n_test, d, device=dev)
-
-            def passes(cur_mask):
-                if _forward is not None:
-                    return torch.stack([_forward(cur_mask).to(dev) for _ in range(M)], 0)
-                return mc_forward(mdl, x, cur_mask, mask_p, M, stage)
 
             def target_mse(xm):  # mean over the M passes of F.mse_loss on the target column (evaluate.py:390-392)
                 return ((xm[:, :, -1] - x[None, :, -1]) ** 2).mean(1).mean()
 
-            info[r, :, 0] = target_mse(passes(mask)).cpu()
+            info[r, :, 0] = target_mse(passes(mdl, x, mask, mask_p)).cpu()
             for t in range(d - 1 if max_steps is None else min(max_steps, d - 1)):
                 if verbose:
                     print("Repeat = {:.1f}".format(r)); print("Strategy = {:.1f}".format(2)); print("Step = {:.1f}".format(t))
-                im = passes(mask)
-                R = reward_matrix(mdl, x, mask, im)
+                im = passes(mdl, x, mask, mask_p)
+                R = reward(mdl, x, mask, im, t)
                 i_opt = R.argmax(1)
                 mask = mask + eye[i_opt]
-                info[r, :, t + 1] = target_mse(passes(mask)).cpu()
+                info[r, :, t + 1] = target_mse(passes(mdl, x, mask, mask_p)).cpu()
                 action[r, :, t] = i_opt.cpu().float()
                 R_hist[r, t] = R.cpu()
                 im_hist[r, t] = im.cpu()
-    out = dict(information_curve_CHAI=info, action_CHAI=action, R_hist_CHAI=R_hist, im_CHAI=im_hist)
+    return dict(information_curve_CHAI=info, action_CHAI=action, R_hist_CHAI=R_hist, im_CHAI=im_hist)
+
+
+def _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
     if save:
         paths = active_result_paths(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
         for k, pth in paths.items():
             os.makedirs(os.path.dirname(pth), exist_ok=True)
             torch.save(out[k], pth)
     return out
+
+
+def active_learning_flow(data_loader_train, test_data, test_mask, missing_rate, obs_dim, hid_dim, K, M, latent_dim,
+                         data_type, training_parameters, experiment_type, vae_type, max_epochs, valid_k, num_estimates,
+                         device=None, alpha=1.0, stage="evaluate", p_missingness=30, reg_type="ml_reg", beta=1.0,
+                         beta_annealing=False, alpha_annealing=True, Repeat=5, model=None, save=True, verbose=False,
+                         _forward=None, max_steps=None, _reward_eps=None, seed=None):
+    """The flow branch of active_learning_func (evaluate.py:300-511 with 'flow' in vae_type: forwards :395-402, reward
+    :420-422): same positional signature, outputs and file names, for a VAEFlow / REG_VAEFlow passed as `model=` (every
+    repeat uses it: model_loader does not build flow models).  The reward of all candidates is one flow_reward_matrix call
+    per step.  The M Monte-Carlo forwards are M model.forward calls (torch.any(inside) is per encoder call).
+    `_forward(mask) -> x_mean [n, d]` replaces one forward; `_reward_eps(step) -> eps [d-1, M, 4, n, 10]` replaces the
+    reward's draws of an acquisition step (tests replay the reference's); `seed` seeds the device draws otherwise."""
+    if not _is_flow(model):
+        raise TypeError("active_learning_flow needs a VAEFlow / REG_VAEFlow as model=")
+    steps = [0]
+
+    def passes(mdl, x, cur_mask, mask_p):
+        if _forward is not None:
+            return torch.stack([_forward(cur_mask).to(x.device) for _ in range(M)], 0)
+        if mdl.regularised:  # evaluate.py:396-399
+            return torch.stack([mdl.forward(x, cur_mask, mask_p)[6] for _ in range(M)], 0)
+        return torch.stack([mdl.forward(x, cur_mask)[2] for _ in range(M)], 0)
+
+    def reward(mdl, x, mask, im, t):
+        steps[0] += 1
+        eps = None if _reward_eps is None else _reward_eps(t).to(x.device)
+        return flow_reward_matrix(mdl, x, mask, im, eps=eps, seed=None if seed is None else seed + steps[0])
+
+    out = _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, Repeat, model, lambda: model, passes,
+                            reward, verbose, max_steps)
+    return _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
