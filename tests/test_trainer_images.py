@@ -53,6 +53,31 @@ def _wide():
     return lambda: tr.step(x, mk, alpha=0.8, beta=0.9)
 
 
+def _miw():
+    torch.manual_seed(0)
+    m = vpc.Reg_MIWAE(12, 500, 10, 10, {"batch_size": 64, "patience": 1}, 20, 1).cuda()
+    tr = vpc.MIWTrainer(m, lr=1e-3, seed=1)
+    x, mk = _data(64, 12, 0)
+    return lambda: tr.step(x, mk, alpha=0.5, p_missingness=30)
+
+
+def _flow():
+    torch.manual_seed(0)
+    m = vpc.REG_VAEFlow(12, 500, 10, 10, {"batch_size": 64, "patience": 1}).cuda()
+    tr = vpc.FlowTrainer(m, lr=1e-3, seed=1)
+    x, mk = _data(64, 12, 0)
+    return lambda: tr.step(x, mk, alpha=0.5, p_missingness=30)
+
+
+def _mnist():
+    torch.manual_seed(0)
+    m = vpc.Reg_EDDI_mnist(784, 500, 20, 10, {"batch_size": 64, "patience": 1}, "exp", "kl_reg").cuda()
+    tr = vpc.EDDIMnistTrainer(m, lr=1e-3, seed=1)
+    g = torch.Generator().manual_seed(0)
+    x, mk = torch.rand(64, 28, 28, generator=g).cuda(), (torch.rand(64, 28, 28, generator=g) < 0.7).cuda()
+    return lambda: tr.step(x, mk, epoch=1, alpha=0.5, p_missingness=30)
+
+
 _SMALL = ["vpc_step_small_max_rows"]
 _FUSED3 = ["vpc_draw_step", "vpc_encoder_fwd", "vpc_decoder_fused", "vpc_encoder_bwd"]
 _GEMM_BWD = ["vpc_linear_wgrad", "vpc_linear_dgrad"] * 3
@@ -82,6 +107,22 @@ LAUNCHES = [
     ("wide", None, _wide,
      ["vpc_draw_mask", "vpc_fill_normal"] + _WIDE_FWD * 2 + ["vpc_loss_fwd_bwd", "vpc_loss_finalize"] + _WIDE_BWD * 2 +
      ["vpc_adam_step"]),
+    # the three rows below were recorded with this test's _Recorder on the commit before the trainers moved onto the shared
+    # chain walkers (config-file shapes: B = 64; wine d = 12; MNIST d = 784).  The lists hold C ABI calls: vpc_flow_loss is two
+    # kernel launches (29 calls = the 30 launches of the flow step), and the MNIST step's 40 launches are these 35 calls (the
+    # scratch query is host-side) plus torch's own copy kernels between them.
+    ("miw_reg_b64", None, _miw,
+     ["vpc_nm_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_miw_sample"] + ["vpc_linear_fwd"] * 3 + ["vpc_miw_loss"] + _GEMM_BWD +
+     ["vpc_miw_sample_bwd"] + _GEMM_BWD[:-1] + ["vpc_linear_wgrad_reduce", "vpc_adam_step"]),
+    ("flow_reg_b64", None, _flow,
+     ["vpc_flow_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_flow_fwd"] + ["vpc_linear_fwd"] * 5 + ["vpc_flow_loss"] +
+     ["vpc_linear_wgrad", "vpc_linear_dgrad"] * 5 + ["vpc_flow_bwd"] + _GEMM_BWD[:-1] +
+     ["vpc_linear_wgrad_reduce", "vpc_adam_step"]),
+    ("eddi_mnist_reg_b64", None, _mnist,
+     ["vpc_draw_mask", "vpc_fill_normal", "vpc_eddiw_fold", "vpc_eddiw_front_fwd"] + ["vpc_linear_fwd"] * 4 + ["vpc_nm_sample"] +
+     ["vpc_linear_fwd"] * 4 + ["vpc_loss_fwd_bwd", "vpc_loss_finalize"] + ["vpc_linear_wgrad", "vpc_linear_dgrad"] * 4 +
+     ["vpc_nm_sample_bwd"] + ["vpc_linear_wgrad", "vpc_linear_dgrad"] * 4 +
+     ["vpc_linear_wgrad_reduce", "vpc_eddiw_front_scratch", "vpc_eddiw_front_bwd", "vpc_adam_step"]),
 ]
 
 

@@ -19,9 +19,10 @@ from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
 from .fused import loss_coefficients
-from .images import PackedImage
-from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
-from .notmiwae import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad, nm_sample, nm_sample_bwd, wgrad_reduce
+from .images import PackedImage, mlp_spec
+from .models import _W6, MAX_EPOCH, Reg_VAE, vanilla_VAE
+from .linear import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad
+from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer
 
@@ -134,13 +135,8 @@ class _EDDIBase:
 
     # flat order: [pnp_encoder2 (6) | seq_decoder (6) | type_pars1, type_bias1, pnp_encoder1 (2)] - the decoder sits at
     # indices 6..11 as in the VAE classes, which is what DecoderFn's gradient split assumes
-    def trainable(self):
-        out = []
-        for name in ("pnp_encoder2.0", "pnp_encoder2.2", "pnp_encoder2.4", "seq_decoder.0", "seq_decoder.2",
-                     "seq_decoder.4"):
-            mod = self.get_submodule(name)
-            out += [mod.weight, mod.bias]
-        return out + [self.type_pars1, self.type_bias1, self.pnp_encoder1[0].weight, self.pnp_encoder1[0].bias]
+    _flat_spec = mlp_spec(_W6[:6], "pnp_encoder2", "enc") + mlp_spec(_W6[6:], "seq_decoder", "dec") + \
+        (("E", "type_pars1", "front"), ("tb", "type_bias1", "front")) + mlp_spec(("Wp", "cp"), "pnp_encoder1", "front")
 
     def _new_image(self, device):
         """Only the DECODER half of the packed image is used (the encoder is the front-end + GEMM trunk)."""
@@ -251,10 +247,8 @@ class EDDITrainer(_FlatAdamTrainer):
         self.mask_p_buf = torch.empty(B, d, dtype=torch.uint8, device=dev)
         self.front_scratch = e(int(lib().vpc_eddi_front_scratch(P * B, d, K)))
         # per-layer partial buffers of the trunk's three weight gradients: summed by ONE launch (vpc_linear_wgrad_reduce)
-        R = P * B
-        self.wg_shapes = [(R, 2 * m.latent_dim, H2), (R, H2, H1), (R, H1, K)]
-        self.wg_scratch = [e(int(lib().vpc_linear_wgrad_scratch(*sh))) for sh in self.wg_shapes]
-        self._wg_cache = {}
+        R, g = P * B, self.g
+        self._wgrad_workspace([(R, 2 * Ld, H2), (R, H2, H1), (R, H1, K)], [(g[4], g[5]), (g[2], g[3]), (g[0], g[1])])
         # the slices the step passes to its launches, made once per batch size (1-3 us of host time each; the step is host-paced)
         self._sl = dict(mean=[self.lat[p_, 0] for p_ in range(P)], logvar=[self.lat[p_, 1] for p_ in range(P)],
                         dmean=[self.dlat[p_, 0] for p_ in range(P)], dlogvar=[self.dlat[p_, 1] for p_ in range(P)],
@@ -335,21 +329,16 @@ class EDDITrainer(_FlatAdamTrainer):
         sl["dheads_dst"].copy_(sl["dlat_src"])
         g = self.g
         # (the three weight gradients leave their GEMMs as partials and are summed by ONE launch: two launches less per step)
-        sc = self.wg_scratch
-        linear_wgrad(self.dheads, self.h2, None, None, R, 2 * Ld, H2, scratch=sc[0])
+        self._wgrad((None, 0), self.dheads, self.h2)
         linear_dgrad(self.dheads, W3, self.dh2, R, 2 * Ld, H2, x_out=self.h2, act_prev=ACT_RELU)
-        linear_wgrad(self.dh2, self.h1, None, None, R, H2, H1, scratch=sc[1])
+        self._wgrad((None, 1), self.dh2, self.h1)
         linear_dgrad(self.dh2, W2, self.dh1, R, H2, H1, x_out=self.h1, act_prev=ACT_RELU)
-        linear_wgrad(self.dh1, self.agg, None, None, R, H1, K, scratch=sc[2])
+        self._wgrad((None, 2), self.dh1, self.agg)
         linear_dgrad(self.dh1, W1, self.dagg, R, H1, K)
-        wgrad_reduce([(sc[0], R, 2 * Ld, H2, g[4], g[5], False), (sc[1], R, H2, H1, g[2], g[3], False),
-                      (sc[2], R, H1, K, g[0], g[1], False)], self._wg_cache)
+        self._wgrad_reduce()
         eddi_front_bwd(x, masks[0], self.AC, self.dagg, E, tb, Wp, g[12], g[13], g[14], g[15], B, d, K,
                        mask2_u8=masks[1] if two else None, scratch=self.front_scratch)
         if self.world_size > 1:
             self._allreduce()
-        self.step_count += 1
         dp = self.world_size > 1  # the Adam launch also adds the all-reduced loss to the epoch accumulator
-        ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.adam_eps, loss_in=self.out9 if dp else None, accum=self.accum if dp else None)
-        self._flat_written(None)
+        self._adam(None, self.out9 if dp else None, self.accum if dp else None)

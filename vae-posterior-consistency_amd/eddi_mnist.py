@@ -42,17 +42,18 @@ from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
 from .fused import loss_coefficients
+from .images import mlp_spec
+from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now
 from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
-from .notmiwae import (ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, linear_dgrad, linear_fwd, linear_wgrad, nm_sample,
-                       nm_sample_bwd, wgrad_reduce)
+from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer
 
 H1, H2, H3 = 500, 500, 200  # VAE.py:32-44 hard-codes the widths: trunk K-500-500-200-2L, decoder L-200-500-500-d
 MAX_D, MAX_K, MAX_L = 1024, 32, 15
 
-_TRUNK = ("pnp_encoder2.0", "pnp_encoder2.2", "pnp_encoder2.4", "pnp_encoder2.6")
-_DEC = ("seq_decoder.0", "seq_decoder.2", "seq_decoder.4", "seq_decoder.6")
+_TRUNK_NAMES = ("We1", "be1", "We2", "be2", "We3", "be3", "We4", "be4")
+_DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wd3", "bd3", "Wd4", "bd4")
 
 
 def eddiw_fold(E, tb, Wp, cp, AC, d, K):
@@ -75,12 +76,17 @@ def eddiw_front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K,
                                     stream_ptr()), "vpc_eddiw_front_bwd")
 
 
-def _trunk_dims(K, Ld):
-    return [(K, H1), (H1, H2), (H2, H3), (H3, 2 * Ld)]  # (in, out) of pnp_encoder2.{0,2,4,6}
+def _chains(trunk, dec):
+    """(trunk, decoder) chains on [W1, b1, ..]: pnp_encoder2.{0,2,4,6} = K-500-500-200-2L with ReLU between layers, seq_decoder
+    L-200-500-500-d with a Sigmoid on every output (split = d)."""
+    return (chain(trunk, (ACT_RELU, ACT_RELU, ACT_RELU, ACT_NONE)),
+            chain(dec, (ACT_RELU, ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), dec[6].shape[0]))
 
 
-def _dec_dims(d, Ld):
-    return [(Ld, H3), (H3, H2), (H2, H1), (H1, d)]  # seq_decoder.{0,2,4,6}
+def _fresh_grads(layers, M, device):
+    """New (dw, db) per layer as wgrad_now keys, and the flat list [dw1, db1, dw2, ..] an autograd backward returns."""
+    keys = [(torch.empty(l[3], l[2], device=device), torch.empty(l[3], device=device), M, l[3], l[2]) for l in layers]
+    return keys, [t for k in keys for t in k[:2]]
 
 
 class EDDIMnistEncoderFn(torch.autograd.Function):
@@ -93,26 +99,22 @@ class EDDIMnistEncoderFn(torch.autograd.Function):
         B, dev = x.shape[0], x.device
         AC = torch.empty(2, K, d, device=dev)
         eddiw_fold(E, tb, Wp, cp, AC, d, K)
-        agg = torch.empty(B, K, device=dev)
-        eddiw_front_fwd(x, mask_u8, AC, agg, B, d, K)
-        acts = [agg]
-        for i, (kin, nout) in enumerate(_trunk_dims(K, Ld)):
-            y = torch.empty(B, nout, device=dev)
-            linear_fwd(acts[-1], trunk[2 * i], trunk[2 * i + 1], y, B, nout, kin, ACT_RELU if i < 3 else ACT_NONE)
-            acts.append(y)
+        layers = model._chains()[0]
+        acts = chain_buffers(layers, B, dev)
+        eddiw_front_fwd(x, mask_u8, AC, acts[0], B, d, K)
+        chain_fwd(layers, acts, B)
         heads = acts[-1]
         z = torch.empty(B, Ld, device=dev)
         nm_sample(heads, eps, z, B, 1, Ld)  # z = mean + eps * exp(logvar / 2); eps None -> z = mean
         ctx.model = model
         ctx.has_eps = eps is not None
-        ctx.save_for_backward(x, mask_u8, AC, *acts, eps if eps is not None else torch.empty(0, device=dev), E, tb, Wp,
-                              *trunk[0::2])
+        ctx.save_for_backward(x, mask_u8, AC, *acts, eps if eps is not None else torch.empty(0, device=dev), E, tb, Wp)
         return z, heads[:, :Ld], heads[:, Ld:]
 
     @staticmethod
     def backward(ctx, dz, dmean, dlogvar):
         model = ctx.model
-        x, mask_u8, AC, agg, h1, h2, h3, heads, eps, E, tb, Wp, W1, W2, W3, W4 = ctx.saved_tensors
+        x, mask_u8, AC, agg, h1, h2, h3, heads, eps, E, tb, Wp = ctx.saved_tensors
         eps = eps if ctx.has_eps else None
         d, Ld, K = model.obs_dim, model.latent_dim, model.emb_dim
         B, dev = x.shape[0], x.device
@@ -122,26 +124,14 @@ class EDDIMnistEncoderFn(torch.autograd.Function):
             gh[:, :Ld] += dmean
         if dlogvar is not None:
             gh[:, Ld:] += dlogvar
-        dht = e(B, 2 * Ld)
+        layers = model._chains()[0]
+        dacts = chain_buffers(layers, B, dev)
         dzc = ops._f32c(dz) if dz is not None else torch.zeros(B, Ld, device=dev)
-        nm_sample_bwd(dzc, eps, heads, gh, dht, B, 1, Ld)
-        acts, Ws = [agg, h1, h2, h3], [W1, W2, W3, W4]
-        dims = _trunk_dims(K, Ld)
-        grads = [None] * 8
-        dy = dht
-        for i in (3, 2, 1, 0):
-            kin, nout = dims[i]
-            gW, gb = e(nout, kin), e(nout)
-            linear_wgrad(dy, acts[i], gW, gb, B, nout, kin)
-            dx = e(B, kin)
-            if i > 0:
-                linear_dgrad(dy, Ws[i], dx, B, nout, kin, x_out=acts[i], act_prev=ACT_RELU)
-            else:
-                linear_dgrad(dy, Ws[i], dx, B, nout, kin)  # agg is a sum of ReLUs, not a ReLU output
-            grads[2 * i], grads[2 * i + 1] = gW, gb
-            dy = dx
+        nm_sample_bwd(dzc, eps, heads, gh, dacts[-1], B, 1, Ld)
+        keys, grads = _fresh_grads(layers, B, dev)
+        chain_bwd(layers, [agg, h1, h2, h3], dacts, B, wgrad_now, keys)  # (agg is a sum of ReLUs, not a ReLU output: no gate)
         gE, gtb, gWp, gcp = e(d, K), e(d, 1), e(K, 2 + K), e(K)
-        eddiw_front_bwd(x, mask_u8, AC, dy, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K)
+        eddiw_front_bwd(x, mask_u8, AC, dacts[0], E, tb, Wp, gE, gtb, gWp, gcp, B, d, K)
         return (None, None, None, None, gE, gtb, gWp, gcp, *grads)
 
 
@@ -152,40 +142,24 @@ class EDDIMnistDecoderFn(torch.autograd.Function):
     def forward(ctx, model, z, *w):
         require_cuda(z, w[0])
         z = ops._f32c(z)
-        B, dev, d, Ld = z.shape[0], z.device, model.obs_dim, model.latent_dim
-        acts = [z]
-        for i, (kin, nout) in enumerate(_dec_dims(d, Ld)):
-            y = torch.empty(B, nout, device=dev)
-            if i < 3:
-                linear_fwd(acts[-1], w[2 * i], w[2 * i + 1], y, B, nout, kin, ACT_RELU)
-            else:
-                linear_fwd(acts[-1], w[2 * i], w[2 * i + 1], y, B, nout, kin, ACT_SIGMOID_HARDTANH, d)  # split = d: all Sigmoid
-            acts.append(y)
-        ctx.save_for_backward(*acts, *w[0::2])
+        B = z.shape[0]
+        layers = model._chains()[1]
+        acts = chain_buffers(layers, B, z.device, first=z)
+        chain_fwd(layers, acts, B)
+        ctx.model = model
+        ctx.save_for_backward(*acts)
         return acts[-1]
 
     @staticmethod
     def backward(ctx, dxhat):
-        z, g1, g2, g3, xhat, W1, W2, W3, W4 = ctx.saved_tensors
-        B, dev, d, Ld = z.shape[0], z.device, xhat.shape[1], z.shape[1]
-        e = lambda *s: torch.empty(*s, device=dev)
-        acts, Ws = [z, g1, g2, g3], [W1, W2, W3, W4]
-        dims = _dec_dims(d, Ld)
-        grads = [None] * 8
-        dy = ops._f32c(dxhat)
-        for i in (3, 2, 1, 0):
-            kin, nout = dims[i]
-            gate = dict(y_gate=xhat, gate=ACT_SIGMOID_HARDTANH, gate_split=d) if i == 3 else {}  # dpre = dxhat xhat (1 - xhat)
-            gW, gb = e(nout, kin), e(nout)
-            linear_wgrad(dy, acts[i], gW, gb, B, nout, kin, **gate)
-            dx = e(B, kin)
-            if i > 0:
-                linear_dgrad(dy, Ws[i], dx, B, nout, kin, x_out=acts[i], act_prev=ACT_RELU, **gate)
-            else:
-                linear_dgrad(dy, Ws[i], dx, B, nout, kin)
-            grads[2 * i], grads[2 * i + 1] = gW, gb
-            dy = dx
-        return (None, dy, *grads)
+        z, g1, g2, g3, xhat = ctx.saved_tensors
+        B, dev, d = z.shape[0], z.device, xhat.shape[1]
+        layers = ctx.model._chains()[1]
+        dacts = chain_buffers(layers, B, dev, last=ops._f32c(dxhat))
+        keys, grads = _fresh_grads(layers, B, dev)
+        chain_bwd(layers, [z, g1, g2, g3], dacts, B, wgrad_now, keys, y_gate=xhat, gate=ACT_SIGMOID_HARDTANH,
+                  gate_split=d)  # dpre = dxhat xhat (1 - xhat)
+        return (None, dacts[0], *grads)
 
 
 class _EDDIMnistBase:
@@ -193,6 +167,14 @@ class _EDDIMnistBase:
     it) and flat-parameter plumbing are reused unchanged."""
     _wide = False
     _eddi_mnist = True  # active.reward_matrix refuses these classes (d = 784 active learning is not a reference configuration)
+    # the 20 trainable tensors in state_dict (= flat) order: front-end (4) | trunk (8) | decoder (8)
+    _flat_spec = (("E", "type_pars1", "front"), ("tb", "type_bias1", "front")) + \
+        mlp_spec(("Wp", "cp"), "pnp_encoder1", "front") + \
+        mlp_spec(_TRUNK_NAMES, "pnp_encoder2", "enc") + mlp_spec(_DEC_NAMES, "seq_decoder", "dec")
+
+    @staticmethod
+    def _build_chains(v):
+        return _chains([v[k] for k in _TRUNK_NAMES], [v[k] for k in _DEC_NAMES])
 
     def _build(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples, num_estimates):
         nn.Module.__init__(self)
@@ -227,17 +209,6 @@ class _EDDIMnistBase:
         self._layout = None
         self._img = None
         self._part = {}
-
-    def trainable(self):
-        """The 20 trainable tensors in state_dict (= flat) order: front-end (4) | trunk (8) | decoder (8)."""
-        out = self.__dict__.get("_trainable_cache")
-        if out is None or out[0] is not self.type_pars1:
-            out = [self.type_pars1, self.type_bias1, self.pnp_encoder1[0].weight, self.pnp_encoder1[0].bias]
-            for name in _TRUNK + _DEC:
-                mod = self.get_submodule(name)
-                out += [mod.weight, mod.bias]
-            self.__dict__["_trainable_cache"] = out
-        return out
 
     def _images(self, key=None):  # no packed weight images: every layer reads the flat parameters
         return None
@@ -314,6 +285,9 @@ class vanilla_EDDI_mnist(_EDDIMnistBase, vanilla_VAE):
 
 
 # ------------------------------------------------------------------------------------------------ fused step
+_TRUNK_WKEYS, _DEC_WKEYS = tuple((None, i) for i in range(4)), tuple((None, 4 + i) for i in range(4))  # (no timer, workspace index)
+
+
 class EDDIMnistTrainer(_FlatAdamTrainer):
     """The training step of train.py:28-117 for data_type == 'mnist' as a fixed launch sequence without host synchronisation:
     mask_p + eps draws -> fold -> front-end (q and p passes stacked, one launch) -> the four trunk GEMMs on the stacked passes
@@ -357,10 +331,11 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         self.eps_ml = e(B, Ld)
         self.mask_p_buf = torch.empty(B, d, dtype=torch.uint8, device=dev)
         self.front_scratch = e(int(lib().vpc_eddiw_front_scratch(R, d, K)))
-        # per-layer partial buffers of the eight weight gradients: summed by ONE launch (vpc_linear_wgrad_reduce)
-        self.wg_shapes = [(R, n, k) for k, n in _trunk_dims(K, Ld) + _dec_dims(d, Ld)]
-        self.wg_scratch = [e(int(lib().vpc_linear_wgrad_scratch(*sh))) for sh in self.wg_shapes]
-        self._wg_cache = {}
+        # the two GEMM chains, and the per-layer partial buffers of their eight weight gradients: summed by ONE launch
+        t, g = self._plist, self.g
+        self.trunk, self.dec_layers = _chains(t[4:12], t[12:20])
+        self._wgrad_workspace([(R, l[3], l[2]) for l in self.trunk + self.dec_layers],
+                              [(g[4 + 2 * i], g[5 + 2 * i]) for i in range(8)])
         self._sl = dict(mean=[self.lat[p_, 0] for p_ in range(P)], logvar=[self.lat[p_, 1] for p_ in range(P)],
                         dmean=[self.dlat[p_, 0] for p_ in range(P)], dlogvar=[self.dlat[p_, 1] for p_ in range(P)],
                         heads_src=self.enc[4].view(P, B, 2, Ld).permute(0, 2, 1, 3), gh_dst=self.gh.view(P, B, 2, Ld),
@@ -389,7 +364,6 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         sl = self._sl
         t = self._plist
         E, tb, Wp, cp = t[:4]
-        trunk, dec = t[4:12], t[12:20]
         # ---- draws
         need_ml = two and co["wml"] != 0.0
         if two:
@@ -412,18 +386,11 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         # ---- encoder: front-end on both passes in one launch, trunk on the stacked passes
         eddiw_fold(E, tb, Wp, cp, self.AC, d, K)
         eddiw_front_fwd(x, masks[0], self.AC, self.enc[0], B, d, K, masks[1] if two else None)
-        tdims, ddims = _trunk_dims(K, Ld), _dec_dims(d, Ld)
-        for i, (kin, nout) in enumerate(tdims):
-            linear_fwd(self.enc[i], trunk[2 * i], trunk[2 * i + 1], self.enc[i + 1], R, nout, kin,
-                       ACT_RELU if i < 3 else ACT_NONE)
+        chain_fwd(self.trunk, self.enc, R)
         heads = self.enc[4]
         nm_sample(heads, self.eps, self.dec[0], R, 1, Ld)
         # ---- decoder
-        for i, (kin, nout) in enumerate(ddims):
-            if i < 3:
-                linear_fwd(self.dec[i], dec[2 * i], dec[2 * i + 1], self.dec[i + 1], R, nout, kin, ACT_RELU)
-            else:
-                linear_fwd(self.dec[i], dec[2 * i], dec[2 * i + 1], self.dec[i + 1], R, nout, kin, ACT_SIGMOID_HARDTANH, d)
+        chain_fwd(self.dec_layers, self.dec, R)
         # ---- loss + seeds (K4 on the materialised xhat; the statistics as [pass][mean | logvar][B][L])
         self.lat.copy_(sl["heads_src"])
         maskB = [mask_p, None] if (two and co["cE"][0] != 0.0) else [None] * P
@@ -433,35 +400,15 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         ops.loss_finalize(self.loss_part, nb, co["cA"][0], co["cE"][0], co["cA"][1] if two else 0.0, co["bq"], co["bp"],
                           co["cr"], co["wml"], B, B, d, self.out9, self.accum)
         # ---- decoder backward (weight gradients stay partials until the one reduce launch)
-        sc = self.wg_scratch
-        xhat = self.dec[4]
-        sig = dict(y_gate=xhat, gate=ACT_SIGMOID_HARDTANH, gate_split=d)
-        for i in (3, 2, 1, 0):
-            kin, nout = ddims[i]
-            gate = sig if i == 3 else {}
-            linear_wgrad(self.ddec[i + 1], self.dec[i], None, None, R, nout, kin, scratch=sc[4 + i], **gate)
-            if i > 0:
-                linear_dgrad(self.ddec[i + 1], dec[2 * i], self.ddec[i], R, nout, kin, x_out=self.dec[i], act_prev=ACT_RELU,
-                             **gate)
-            else:
-                linear_dgrad(self.ddec[i + 1], dec[2 * i], self.ddec[i], R, nout, kin)
+        chain_bwd(self.dec_layers, self.dec, self.ddec, R, self._wgrad, _DEC_WKEYS, y_gate=self.dec[4],
+                  gate=ACT_SIGMOID_HARDTANH, gate_split=d)
         # ---- rsample backward: d heads = K4's seeds + the path through z
         sl["gh_dst"].copy_(sl["dlat_src"])
         nm_sample_bwd(self.ddec[0], self.eps, heads, self.gh, self.denc[4], R, 1, Ld)
         # ---- trunk backward
-        for i in (3, 2, 1, 0):
-            kin, nout = tdims[i]
-            linear_wgrad(self.denc[i + 1], self.enc[i], None, None, R, nout, kin, scratch=sc[i])
-            if i > 0:
-                linear_dgrad(self.denc[i + 1], trunk[2 * i], self.denc[i], R, nout, kin, x_out=self.enc[i],
-                             act_prev=ACT_RELU)
-            else:
-                linear_dgrad(self.denc[i + 1], trunk[2 * i], self.denc[i], R, nout, kin)
+        chain_bwd(self.trunk, self.enc, self.denc, R, self._wgrad, _TRUNK_WKEYS)
+        self._wgrad_reduce()
         g = self.g
-        wgrad_reduce([(sc[i], *self.wg_shapes[i], g[4 + 2 * i], g[5 + 2 * i], False) for i in range(8)], self._wg_cache)
         eddiw_front_bwd(x, masks[0], self.AC, self.denc[0], E, tb, Wp, g[0], g[1], g[2], g[3], B, d, K,
                         mask2_u8=masks[1] if two else None, scratch=self.front_scratch)
-        self.step_count += 1
-        ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.adam_eps)
-        self._flat_written(None)
+        self._adam()

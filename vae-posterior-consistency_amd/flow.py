@@ -18,15 +18,14 @@ identity.  latent_dim must be 10 (the reference's hard-coded 10 x 10 reshape).
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .images import ParamKeyMixin
-from .notmiwae import ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, linear_dgrad, linear_fwd, linear_wgrad, wgrad_reduce
+from .images import FlatParams, mlp_spec
+from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now,
+                     wgrad_now_keys)
 from .trainer import _FlatAdamTrainer
 
 FLOW_L = 10      # VPC_FLOW_LATENT: latent dim = spline bins
@@ -72,44 +71,45 @@ def _mask_f32(m, d, device):
 
 
 # ------------------------------------------------------------------------------------------------ autograd
+_ENC_NAMES = ("We1", "be1", "We2", "be2", "We3", "be3")
+_DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wd3", "bd3", "Wd4", "bd4", "Wm", "bm")
+
+
+def _chains(v):
+    """(encoder, decoder) chains on the named views v: ELU between layers, raw contexts, Sigmoid on decoder_mean."""
+    return (chain([v[k] for k in _ENC_NAMES], (ACT_ELU, ACT_ELU, ACT_NONE)),
+            chain([v[k] for k in _DEC_NAMES], (ACT_ELU,) * 4 + (ACT_SIGMOID_HARDTANH,), v["Wm"].shape[0]))
+
+
 class FlowEncoderFn(torch.autograd.Function):
     """(x, mask, eps) -> (z, z_log_prob) [B, 10].  seq_encoder(cat[x*mask, mask]) then Flow.forward (VAE.py:1924-1931)."""
 
     @staticmethod
     def forward(ctx, model, x, mask, eps, *weights):
         require_cuda(x, mask, eps, *weights)
-        v = model._views()
-        d, H = model.obs_dim, model.hid_dim
+        d = model.obs_dim
         B, dev = x.shape[0], x.device
-        xin = torch.empty(B, 2 * d, device=dev)
-        flow_prep(x, mask, None, None, xin, None, B, d)
-        h1, h2, t = torch.empty(B, H, device=dev), torch.empty(B, H, device=dev), torch.empty(B, CTX, device=dev)
-        linear_fwd(xin, v["We1"], v["be1"], h1, B, H, 2 * d, ACT_ELU)
-        linear_fwd(h1, v["We2"], v["be2"], h2, B, H, H, ACT_ELU)
-        linear_fwd(h2, v["We3"], v["be3"], t, B, CTX, H, ACT_NONE)
+        layers = model._chains()[0]
+        acts = chain_buffers(layers, B, dev)
+        flow_prep(x, mask, None, None, acts[0], None, B, d)
+        chain_fwd(layers, acts, B)
         z, zlp = torch.empty(B, FLOW_L, device=dev), torch.empty(B, FLOW_L, device=dev)
-        flow_fwd(t, eps, z, zlp, B, B)
+        flow_fwd(acts[3], eps, z, zlp, B, B)
         ctx.model = model
-        ctx.save_for_backward(xin, h1, h2, t, eps)
+        ctx.save_for_backward(*acts, eps)
         return z, zlp
 
     @staticmethod
     def backward(ctx, dz, dzlp):
         model = ctx.model
-        xin, h1, h2, t, eps = ctx.saved_tensors
-        v = model._views()
-        d, H = model.obs_dim, model.hid_dim
-        B, dev = xin.shape[0], xin.device
-        dt = torch.empty(B, CTX, device=dev)
-        flow_bwd(t, eps, None if dz is None else _f32c(dz), None, None if dzlp is None else _f32c(dzlp), dt, B, B)
+        *acts, eps = ctx.saved_tensors
+        B, dev = acts[0].shape[0], acts[0].device
+        layers = model._chains()[0]
+        dacts = chain_buffers(layers, B, dev, first=False)
+        flow_bwd(acts[3], eps, None if dz is None else _f32c(dz), None, None if dzlp is None else _f32c(dzlp), dacts[3], B, B)
         g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        dh2, dh1 = torch.empty(B, H, device=dev), torch.empty(B, H, device=dev)
-        linear_wgrad(dt, h2, g["We3"], g["be3"], B, CTX, H)
-        linear_dgrad(dt, v["We3"], dh2, B, CTX, H, x_out=h2, act_prev=ACT_ELU)
-        linear_wgrad(dh2, h1, g["We2"], g["be2"], B, H, H)
-        linear_dgrad(dh2, v["We2"], dh1, B, H, H, x_out=h1, act_prev=ACT_ELU)
-        linear_wgrad(dh1, xin, g["We1"], g["be1"], B, H, 2 * d)
-        return (None, None, None, None, g["We1"], g["be1"], g["We2"], g["be2"], g["We3"], g["be3"])
+        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, _ENC_NAMES, B), input_grad=False)
+        return (None, None, None, None, *[g[k] for k in _ENC_NAMES])
 
 
 class FlowDecoderFn(torch.autograd.Function):
@@ -118,42 +118,29 @@ class FlowDecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, z, *weights):
         require_cuda(z, *weights)
-        v = model._views()
-        d, H = model.obs_dim, model.hid_dim
+        d = model.obs_dim
         lead = z.shape[:-1]
         z2 = _f32c(z).reshape(-1, FLOW_L)
-        M, dev = z2.shape[0], z2.device
-        gs = [torch.empty(M, H, device=dev) for _ in range(4)]
-        Y = torch.empty(M, d, device=dev)
-        linear_fwd(z2, v["Wd1"], v["bd1"], gs[0], M, H, FLOW_L, ACT_ELU)
-        for i in range(1, 4):
-            linear_fwd(gs[i - 1], v[f"Wd{i + 1}"], v[f"bd{i + 1}"], gs[i], M, H, H, ACT_ELU)
-        linear_fwd(gs[3], v["Wm"], v["bm"], Y, M, d, H, ACT_SIGMOID_HARDTANH, d)
+        M = z2.shape[0]
+        layers = model._chains()[1]
+        acts = chain_buffers(layers, M, z2.device, first=z2)
+        chain_fwd(layers, acts, M)
         ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(z2, *gs, Y)
-        return Y.view(*lead, d)
+        ctx.save_for_backward(*acts)
+        return acts[5].view(*lead, d)
 
     @staticmethod
     def backward(ctx, gy):
         model = ctx.model
-        z2, g1, g2, g3, g4, Y = ctx.saved_tensors
-        gs = [g1, g2, g3, g4]
-        v = model._views()
-        d, H = model.obs_dim, model.hid_dim
-        M, dev = z2.shape[0], z2.device
-        G = _f32c(gy).reshape(M, d)
+        acts = ctx.saved_tensors
+        d = model.obs_dim
+        M, dev = acts[0].shape[0], acts[0].device
+        layers = model._chains()[1]
+        dacts = chain_buffers(layers, M, dev, last=_f32c(gy).reshape(M, d))
         g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
-        dg = [torch.empty(M, H, device=dev) for _ in range(4)]
-        dz = torch.empty(M, FLOW_L, device=dev)
-        linear_wgrad(G, g4, g["Wm"], g["bm"], M, d, H, y_gate=Y, gate=ACT_SIGMOID_HARDTANH, gate_split=d)
-        linear_dgrad(G, v["Wm"], dg[3], M, d, H, y_gate=Y, gate=ACT_SIGMOID_HARDTANH, gate_split=d, x_out=g4,
-                     act_prev=ACT_ELU)
-        for i in range(3, 0, -1):  # seq_decoder.{6,4,2}
-            linear_wgrad(dg[i], gs[i - 1], g[f"Wd{i + 1}"], g[f"bd{i + 1}"], M, H, H)
-            linear_dgrad(dg[i], v[f"Wd{i + 1}"], dg[i - 1], M, H, H, x_out=gs[i - 1], act_prev=ACT_ELU)
-        linear_wgrad(dg[0], z2, g["Wd1"], g["bd1"], M, H, FLOW_L)
-        linear_dgrad(dg[0], v["Wd1"], dz, M, H, FLOW_L)
-        return (None, dz.view(*ctx.lead, FLOW_L), *[g[k] for k in model._DEC_NAMES])
+        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, _DEC_NAMES, M), y_gate=acts[5],
+                  gate=ACT_SIGMOID_HARDTANH, gate_split=d)
+        return (None, dacts[0].view(*ctx.lead, FLOW_L), *[g[k] for k in _DEC_NAMES])
 
 
 class FlowLossFn(torch.autograd.Function):
@@ -206,10 +193,14 @@ class _Flow(nn.Module):
         self.flows = nn.ModuleList([_PiecewiseLinearCDF((dim,)) for _ in range(3)])
 
 
-class _FlowBase(ParamKeyMixin, nn.Module):
+class _FlowBase(FlatParams, nn.Module):
     regularised = False
-    _ENC_NAMES = ("We1", "be1", "We2", "be2", "We3", "be3")
-    _DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wd3", "bd3", "Wd4", "bd4", "Wm", "bm")
+    _ENC_NAMES, _DEC_NAMES = _ENC_NAMES, _DEC_NAMES
+    # flat parameter buffer: [We1 be1 We2 be2 We3 be3 | Wd1 bd1 .. Wd4 bd4 Wm bm] = state_dict order of the 16 tensors that get
+    # a gradient; the other 9 stay ordinary parameters outside it
+    _flat_spec = mlp_spec(_ENC_NAMES, "seq_encoder", "enc") + mlp_spec(_DEC_NAMES[:8], "seq_decoder", "dec") + \
+        mlp_spec(_DEC_NAMES[8:], "decoder_mean", "dec")
+    _build_chains = staticmethod(_chains)
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples=1, num_estimates=1):
         super().__init__()
@@ -237,79 +228,10 @@ class _FlowBase(ParamKeyMixin, nn.Module):
         self.prior_mean = nn.Parameter(torch.zeros(Ld), requires_grad=False)
         self.prior_std = nn.Parameter(torch.ones(Ld), requires_grad=False)
         self._flat = None
-        self._view_cache = None
-        self._n_enc = H * 2 * d + H + H * H + H + CTX * H + CTX
-        self._n_dec = H * Ld + H + 3 * (H * H + H) + d * H + d
 
     @property
     def prior(self):  # VAE.py:1920 (Normal(prior_mean, prior_std))
         return torch.distributions.Normal(self.prior_mean, self.prior_std)
-
-    # ---- flat parameter buffer: [We1 be1 We2 be2 We3 be3 | Wd1 bd1 .. Wd4 bd4 Wm bm] = state_dict order
-    def trainable(self):
-        se, sd, dm = self.seq_encoder, self.seq_decoder, self.decoder_mean[0]
-        return [se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias,
-                sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, sd[4].weight, sd[4].bias, sd[6].weight, sd[6].bias,
-                dm.weight, dm.bias]
-
-    def flatten_parameters(self):
-        """Make the 16 trainable tensors views of ONE flat fp32 buffer.  Idempotent; call again after .to()."""
-        ps = self.trainable()
-        flat = self._flat
-        ok = flat is not None and flat.device == ps[0].device
-        off = 0
-        if ok:
-            for p in ps:
-                if p.data.data_ptr() != flat.data_ptr() + 4 * off or not p.data.is_contiguous():
-                    ok = False
-                    break
-                off += p.numel()
-        if not ok:
-            flat = torch.cat([p.data.detach().reshape(-1).float() for p in ps]).contiguous()
-            off = 0
-            for p in ps:
-                p.data = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-            self._flat = flat
-            self._view_cache = None
-        return self._flat
-
-    def _segment_views(self, buf, which):
-        d, H = self.obs_dim, self.hid_dim
-        if which == "enc":
-            spec = [("We1", (H, 2 * d)), ("be1", (H,)), ("We2", (H, H)), ("be2", (H,)), ("We3", (CTX, H)),
-                    ("be3", (CTX,))]
-        else:
-            spec = [("Wd1", (H, FLOW_L)), ("bd1", (H,))]
-            for i in (2, 3, 4):
-                spec += [(f"Wd{i}", (H, H)), (f"bd{i}", (H,))]
-            spec += [("Wm", (d, H)), ("bm", (d,))]
-        out, off = {}, 0
-        for name, shp in spec:
-            n = math.prod(shp)
-            out[name] = buf[off:off + n].view(shp)
-            off += n
-        return out
-
-    def _views(self):
-        vc, flat = self._view_cache, self._flat
-        if vc is not None and flat is not None and vc[0] is flat and \
-                self.seq_encoder[0].weight.data.data_ptr() == flat.data_ptr() and \
-                self.decoder_mean[0].bias.data.data_ptr() == flat.data_ptr() + 4 * (flat.numel() - self.obs_dim):
-            return vc[1]
-        flat = self.flatten_parameters()
-        L.require_cuda(flat)
-        v = self._segment_views(flat[:self._n_enc], "enc")
-        v.update(self._segment_views(flat[self._n_enc:], "dec"))
-        self._view_cache = (flat, v)
-        return v
-
-    def _enc_weights(self):
-        se = self.seq_encoder
-        return (se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias)
-
-    def _dec_weights(self):
-        return tuple(self.trainable()[6:])
 
     # ---- reference API
     def _encode(self, x, mask, sample=True, eps=None):
@@ -402,6 +324,12 @@ class REG_VAEFlow(_FlowBase):
 
 
 # ------------------------------------------------------------------------------------------------ fused step
+# timer names of the chain launches, per layer, and the weight gradients' (timer name, index in the trainer's workspace)
+_T_ENC_FWD, _T_ENC_BWD, _T_DEC_FWD, _T_DEC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) * 3, ("dec_fwd",) * 5, ("dec_bwd",) * 5
+_DEC_WKEYS = tuple(("dec_bwd", 4 - i) for i in range(5))
+_ENC_WKEYS = tuple(("enc_bwd", 7 - i) for i in range(3))
+
+
 class FlowTrainer(_FlatAdamTrainer):
     """The whole training step of the flow path (train.py:77-86 + :114-116) as a fixed sequence of HIP launches with no
     host synchronisation: mask_p draw + stacked encoder input + eps draws (one launch), the encoder GEMMs with the q and
@@ -411,6 +339,7 @@ class FlowTrainer(_FlatAdamTrainer):
 
     Single process only: the reference's torch.any(inside) (VAE.py:1698) is a predicate over the whole batch of an
     encoder call, so a sharded step would need a cross-rank vote before the flow."""
+    step_timers = True
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
         if not isinstance(model, _FlowBase):
@@ -421,12 +350,12 @@ class FlowTrainer(_FlatAdamTrainer):
         super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
         self.reg = model.regularised
         self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        self.g = model._segment_views(self.grad[:model._n_enc], "enc")
-        self.g.update(model._segment_views(self.grad[model._n_enc:], "dec"))
-        self._B = None
+        self.g = model._named_views(self.grad)
+        self._B = self._v = None
 
-    def _ws(self, B):
-        if self._B == B:
+    def _ws(self, B, v=None):
+        v = self.model._views() if v is None else v
+        if self._B == B and self._v is v:
             return
         m, dev = self.model, self.dev
         d, H = m.obs_dim, m.hid_dim
@@ -441,20 +370,19 @@ class FlowTrainer(_FlatAdamTrainer):
         self.gz, self.gzlp, self.dzd = e(R, FLOW_L), e(R, FLOW_L), e(R, FLOW_L)
         self.dgd = [e(R, H) for _ in range(4)]
         self.dt, self.dh2, self.dh1 = e(R, CTX), e(R, H), e(R, H)
-        self.wg_shapes = [(R, d, H), (R, H, H), (R, H, H), (R, H, H), (R, H, FLOW_L), (R, CTX, H), (R, H, H),
-                          (R, H, 2 * d)]
-        sizes = [int(lib().vpc_linear_wgrad_scratch(*sh)) for sh in self.wg_shapes]
-        buf = e(sum(sizes))
-        self.wg_scratch, o = [], 0
-        for n in sizes:
-            self.wg_scratch.append(buf[o:o + n])
-            o += n
-        self._wg_cache = {}
+        # the two GEMM chains on their workspaces, and the per-layer partials of the eight weight gradients in launch order
+        self.enc_layers, self.dec_layers = m._chains()
+        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.t], [None, self.dh1, self.dh2, self.dt]
+        self.dec_acts, self.dec_dacts = [self.z, *self.gd, self.Y], [self.dzd, *self.dgd, self.G]
+        g = self.g
+        back = self.dec_layers[::-1] + self.enc_layers[::-1]  # the backward pass's launch order: decoder_mean first
+        names = _DEC_NAMES[::-1] + _ENC_NAMES[::-1]           # bm, Wm, bd4, Wd4, ..
+        self._wgrad_workspace([(R, l[3], l[2]) for l in back], [(g[w], g[b]) for w, b in zip(names[1::2], names[0::2])])
         self.scratch = flow_loss_scratch(B, dev)
         pq = lambda a: (a[:B], a[B:] if self.reg else None)
         self._sl = dict(xm=pq(self.Y), z=pq(self.z), zlp=pq(self.zlp),
                         g=(*pq(self.G), *pq(self.gz), *pq(self.gzlp)))
-        self._B = B
+        self._B, self._v = B, v
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, beta=1.0, p_missingness=30, stage="train"):
         """One optimiser step.  mask_p [B,d] (REG_VAEFlow) and eps [P,B,10] (the q pass, then the p pass) may be
@@ -466,10 +394,10 @@ class FlowTrainer(_FlatAdamTrainer):
         L.require_cuda(xf)
         mf = _mask_f32(mask, d, xf.device)
         B = xf.shape[0]
-        self._ws(B)
+        self._ws(B, v)
         reg = self.reg
         R = (2 if reg else 1) * B
-        t, sl, g = self._timed, self._sl, self.g
+        t, sl = self._timed, self._sl
         mp_in = _mask_f32(mask_p, d, xf.device) if (reg and mask_p is not None) else None
         mp = mp_in if mp_in is not None else (self.mask_p if reg else None)
         t("prep", flow_prep, xf, mf, mp_in, self.mask_p if (reg and mp_in is None) else None, self.xin,
@@ -479,46 +407,17 @@ class FlowTrainer(_FlatAdamTrainer):
             self.eps.copy_(eps.reshape(self.eps.shape))
         self.rng_offset += (self.eps.numel() + 3) // 4 + (B * d + 3) // 4 + 1
         # ---- forward
-        t("enc_fwd", linear_fwd, self.xin, v["We1"], v["be1"], self.h1, R, H, 2 * d, ACT_ELU)
-        t("enc_fwd", linear_fwd, self.h1, v["We2"], v["be2"], self.h2, R, H, H, ACT_ELU)
-        t("enc_fwd", linear_fwd, self.h2, v["We3"], v["be3"], self.t, R, CTX, H, ACT_NONE)
+        chain_fwd(self.enc_layers, self.enc_acts, R, 0, t, _T_ENC_FWD)
         t("flow", flow_fwd, self.t, self.eps, self.z, self.zlp, R, B)
-        gd, dgd = self.gd, self.dgd
-        t("dec_fwd", linear_fwd, self.z, v["Wd1"], v["bd1"], gd[0], R, H, FLOW_L, ACT_ELU)
-        for i in range(1, 4):
-            t("dec_fwd", linear_fwd, gd[i - 1], v[f"Wd{i + 1}"], v[f"bd{i + 1}"], gd[i], R, H, H, ACT_ELU)
-        t("dec_fwd", linear_fwd, gd[3], v["Wm"], v["bm"], self.Y, R, d, H, ACT_SIGMOID_HARDTANH, d)
+        chain_fwd(self.dec_layers, self.dec_acts, R, 0, t, _T_DEC_FWD)
         # ---- loss: G = d train_loss / d decoder_mean pre-activation, gz / gzlp = d train_loss / d (z, z_log_prob)
         t("loss", flow_loss, xf, mf, mp, sl["xm"], sl["z"], sl["zlp"], sl["g"], self.scratch, self.out8, self.tail,
           self.accum, B, d, STAGE_TRAIN if stage == "train" else STAGE_EVAL, alpha, beta, 1.0 / B, 1)
         # ---- backward: weight-gradient partials per layer, all summed by one launch
-        defer = self.timers is None
-        pend = []
-
-        def wgrad(name, i, dy, xx, dw, db):
-            Mi, Ni, Ki = self.wg_shapes[i]
-            if not defer:
-                return t(name, linear_wgrad, dy, xx, dw, db, Mi, Ni, Ki)
-            linear_wgrad(dy, xx, None, None, Mi, Ni, Ki, scratch=self.wg_scratch[i])
-            pend.append((self.wg_scratch[i], Mi, Ni, Ki, dw, db, False))
-
-        wgrad("dec_bwd", 0, self.G, gd[3], g["Wm"], g["bm"])
-        t("dec_bwd", linear_dgrad, self.G, v["Wm"], dgd[3], R, d, H, x_out=gd[3], act_prev=ACT_ELU)
-        for i in range(3, 0, -1):
-            wgrad("dec_bwd", 4 - i, dgd[i], gd[i - 1], g[f"Wd{i + 1}"], g[f"bd{i + 1}"])
-            t("dec_bwd", linear_dgrad, dgd[i], v[f"Wd{i + 1}"], dgd[i - 1], R, H, H, x_out=gd[i - 1], act_prev=ACT_ELU)
-        wgrad("dec_bwd", 4, dgd[0], self.z, g["Wd1"], g["bd1"])
-        t("dec_bwd", linear_dgrad, dgd[0], v["Wd1"], self.dzd, R, H, FLOW_L)
+        # (G already holds the gradient of decoder_mean's pre-activation: no gate pass over Y)
+        chain_bwd(self.dec_layers, self.dec_acts, self.dec_dacts, R, self._wgrad, _DEC_WKEYS, run=t, names=_T_DEC_BWD)
         t("flow_bwd", flow_bwd, self.t, self.eps, self.dzd, self.gz, self.gzlp, self.dt, R, B)
-        wgrad("enc_bwd", 5, self.dt, self.h2, g["We3"], g["be3"])
-        t("enc_bwd", linear_dgrad, self.dt, v["We3"], self.dh2, R, CTX, H, x_out=self.h2, act_prev=ACT_ELU)
-        wgrad("enc_bwd", 6, self.dh2, self.h1, g["We2"], g["be2"])
-        t("enc_bwd", linear_dgrad, self.dh2, v["We2"], self.dh1, R, H, H, x_out=self.h1, act_prev=ACT_ELU)
-        wgrad("enc_bwd", 7, self.dh1, self.xin, g["We1"], g["be1"])
-        if pend:
-            wgrad_reduce(pend, self._wg_cache)
-        self.step_count += 1
-        from .ops import adam_step
-        t("adam", adam_step, m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-          self.betas[1], self.adam_eps)
-        self._flat_written(None)
+        chain_bwd(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._wgrad, _ENC_WKEYS, input_grad=False, run=t,
+                  names=_T_ENC_BWD)
+        self._wgrad_reduce()
+        self._adam()

@@ -19,15 +19,15 @@ B == 1 (eval_miwae, one row per call) the pairing is the natural one, and the ba
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .images import ParamKeyMixin
-from .notmiwae import ACT_NONE, ACT_RELU, _f32c, linear_dgrad, linear_fwd, linear_wgrad, nm_mul, nm_prep, wgrad_reduce
+from .images import FlatParams, mlp_spec
+from .linear import ACT_NONE, ACT_RELU, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now, wgrad_now_keys
+from .notmiwae import nm_mul, nm_prep
+from .ops import fill_normal
 from .trainer import _FlatAdamTrainer
 
 HID = 128  # VAE.py:3027-3042 / :3153-3168 hard-code 128 (hid_dim is ignored by the reference too)
@@ -80,46 +80,48 @@ def _joined(parts, M, W):
 
 
 # ------------------------------------------------------------------------------------------------ autograd
+_ENC_NAMES = ("We1", "be1", "We2", "be2", "Wh", "bh")
+_DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wx", "bx")
+
+
+def _chains(v):
+    """(encoder, decoder) chains on the named views v: ReLU between layers, raw heads."""
+    return (chain([v[k] for k in _ENC_NAMES], (ACT_RELU, ACT_RELU, ACT_NONE)),
+            chain([v[k] for k in _DEC_NAMES], (ACT_RELU, ACT_RELU, ACT_NONE)))
+
+
 class MIWEncoderFn(torch.autograd.Function):
     """(x, mask, eps) -> (z [B,S,L], hact [B, mean L | scale L]).  VAE.py:3059-3070 / :3188-3200."""
 
     @staticmethod
     def forward(ctx, model, x, mask, eps, S, *weights):
         require_cuda(x, mask, eps, *weights)
-        v = model._views()
-        d, Ld = model.obs_dim, model.latent_dim
+        Ld = model.latent_dim
         B, dev = x.shape[0], x.device
-        xin = torch.empty(B, d, device=dev)
-        nm_mul(x, mask, xin)
-        h1, h2 = torch.empty(B, HID, device=dev), torch.empty(B, HID, device=dev)
-        heads, hact = torch.empty(B, 2 * Ld, device=dev), torch.empty(B, 2 * Ld, device=dev)
-        linear_fwd(xin, v["We1"], v["be1"], h1, B, HID, d, ACT_RELU)
-        linear_fwd(h1, v["We2"], v["be2"], h2, B, HID, HID, ACT_RELU)
-        linear_fwd(h2, v["Wh"], v["bh"], heads, B, 2 * Ld, HID, ACT_NONE)
+        layers = model._chains()[0]
+        acts = chain_buffers(layers, B, dev)
+        nm_mul(x, mask, acts[0])
+        hact = torch.empty(B, 2 * Ld, device=dev)
+        chain_fwd(layers, acts, B)
         z = torch.empty(B * S, Ld, device=dev)
-        miw_sample(heads, hact, eps, z, B, S, Ld)
+        miw_sample(acts[3], hact, eps, z, B, S, Ld)
         ctx.model, ctx.S, ctx.has_eps = model, S, eps is not None
-        ctx.save_for_backward(xin, h1, h2, heads, eps if eps is not None else torch.empty(0, device=dev))
+        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev))
         return z.view(B, S, Ld), hact
 
     @staticmethod
     def backward(ctx, dz, dhact):
         model, S = ctx.model, ctx.S
-        xin, h1, h2, heads, eps = ctx.saved_tensors
-        v = model._views()
-        d, Ld = model.obs_dim, model.latent_dim
-        B, dev = xin.shape[0], xin.device
-        dht = torch.empty(B, 2 * Ld, device=dev)
-        miw_sample_bwd(None if dz is None else _f32c(dz).reshape(B * S, Ld), eps if ctx.has_eps else None, heads,
-                       None if dhact is None else _f32c(dhact), dht, B, S, Ld)
+        *acts, eps = ctx.saved_tensors
+        Ld = model.latent_dim
+        B, dev = acts[0].shape[0], acts[0].device
+        layers = model._chains()[0]
+        dacts = chain_buffers(layers, B, dev, first=False)
+        miw_sample_bwd(None if dz is None else _f32c(dz).reshape(B * S, Ld), eps if ctx.has_eps else None, acts[3],
+                       None if dhact is None else _f32c(dhact), dacts[3], B, S, Ld)
         g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        dh2, dh1 = torch.empty(B, HID, device=dev), torch.empty(B, HID, device=dev)
-        linear_wgrad(dht, h2, g["Wh"], g["bh"], B, 2 * Ld, HID)
-        linear_dgrad(dht, v["Wh"], dh2, B, 2 * Ld, HID, x_out=h2, act_prev=ACT_RELU)
-        linear_wgrad(dh2, h1, g["We2"], g["be2"], B, HID, HID)
-        linear_dgrad(dh2, v["We2"], dh1, B, HID, HID, x_out=h1, act_prev=ACT_RELU)
-        linear_wgrad(dh1, xin, g["We1"], g["be1"], B, HID, d)
-        return (None, None, None, None, None, g["We1"], g["be1"], g["We2"], g["be2"], g["Wh"], g["bh"])
+        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, _ENC_NAMES, B), input_grad=False)
+        return (None, None, None, None, None, *[g[k] for k in _ENC_NAMES])
 
 
 class MIWDecoderFn(torch.autograd.Function):
@@ -128,44 +130,36 @@ class MIWDecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, z, *weights):
         require_cuda(z, *weights)
-        v = model._views()
         d, Ld = model.obs_dim, model.latent_dim
         lead = z.shape[:-1]
         z2 = _f32c(z).reshape(-1, Ld)
         M, dev = z2.shape[0], z2.device
-        g1, g2 = torch.empty(M, HID, device=dev), torch.empty(M, HID, device=dev)
-        Y, Ya = torch.empty(M, 3 * d, device=dev), torch.empty(M, 3 * d, device=dev)
-        linear_fwd(z2, v["Wd1"], v["bd1"], g1, M, HID, Ld, ACT_RELU)
-        linear_fwd(g1, v["Wd2"], v["bd2"], g2, M, HID, HID, ACT_RELU)
-        linear_fwd(g2, v["Wx"], v["bx"], Y, M, 3 * d, HID, ACT_NONE)
-        miw_heads(Y, Ya, M, d)
+        layers = model._chains()[1]
+        acts = chain_buffers(layers, M, dev, first=z2)
+        Ya = torch.empty(M, 3 * d, device=dev)
+        chain_fwd(layers, acts, M)
+        miw_heads(acts[3], Ya, M, d)
         ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(z2, g1, g2, Y)
+        ctx.save_for_backward(*acts)
         Y3 = Ya.view(*lead, 3 * d)
         return Y3[..., :d], Y3[..., d:2 * d], Y3[..., 2 * d:]
 
     @staticmethod
     def backward(ctx, gm, gs, gv):
         model = ctx.model
-        z2, g1, g2, Y = ctx.saved_tensors
-        v = model._views()
+        acts = ctx.saved_tensors
         d, Ld = model.obs_dim, model.latent_dim
-        M, dev = z2.shape[0], z2.device
+        M, dev = acts[0].shape[0], acts[0].device
         parts = [torch.zeros(M, d, device=dev) if t is None else t for t in (gm, gs, gv)]
         Ga = _joined(parts, M, d)
         if Ga is None:
             Ga = torch.cat([_f32c(t).reshape(M, d) for t in parts], 1)
-        G = torch.empty(M, 3 * d, device=dev)
-        miw_heads_bwd(Y, Ga, G, M, d)
+        layers = model._chains()[1]
+        dacts = chain_buffers(layers, M, dev)
+        miw_heads_bwd(acts[3], Ga, dacts[3], M, d)
         g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
-        dg2, dg1, dz = torch.empty(M, HID, device=dev), torch.empty(M, HID, device=dev), torch.empty(M, Ld, device=dev)
-        linear_wgrad(G, g2, g["Wx"], g["bx"], M, 3 * d, HID)
-        linear_dgrad(G, v["Wx"], dg2, M, 3 * d, HID, x_out=g2, act_prev=ACT_RELU)
-        linear_wgrad(dg2, g1, g["Wd2"], g["bd2"], M, HID, HID)
-        linear_dgrad(dg2, v["Wd2"], dg1, M, HID, HID, x_out=g1, act_prev=ACT_RELU)
-        linear_wgrad(dg1, z2, g["Wd1"], g["bd1"], M, HID, Ld)
-        linear_dgrad(dg1, v["Wd1"], dz, M, HID, Ld)
-        return (None, dz.view(*ctx.lead, Ld), g["Wd1"], g["bd1"], g["Wd2"], g["bd2"], g["Wx"], g["bx"])
+        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, _DEC_NAMES, M))
+        return (None, dacts[0].view(*ctx.lead, Ld), *[g[k] for k in _DEC_NAMES])
 
 
 class MIWLossFn(torch.autograd.Function):
@@ -205,8 +199,11 @@ class MIWLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ model classes
-class _MIWBase(ParamKeyMixin, nn.Module):
+class _MIWBase(FlatParams, nn.Module):
     regularised = False
+    # flat parameter buffer: [We1 be1 We2 be2 Wh bh | Wd1 bd1 Wd2 bd2 Wx bx] = state_dict order
+    _flat_spec = mlp_spec(_ENC_NAMES, "seq_encoder", "enc") + mlp_spec(_DEC_NAMES, "seq_decoder", "dec")
+    _build_chains = staticmethod(_chains)
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
         super().__init__()
@@ -231,75 +228,10 @@ class _MIWBase(ParamKeyMixin, nn.Module):
                                          nn.Linear(HID, 3 * d))
         self.max_epoch = 2800
         self._flat = None
-        self._view_cache = None
-        self._n_enc = HID * d + HID + HID * HID + HID + 2 * Ld * HID + 2 * Ld
-        self._n_dec = HID * Ld + HID + HID * HID + HID + 3 * d * HID + 3 * d
 
     @property
     def prior(self):  # VAE.py:3047 (a CPU distribution in the reference; kept for attribute parity)
         return torch.distributions.Normal(torch.zeros(self.latent_dim), torch.ones(self.latent_dim))
-
-    # ---- flat parameter buffer: [We1 be1 We2 be2 Wh bh | Wd1 bd1 Wd2 bd2 Wx bx] = state_dict order
-    def trainable(self):
-        se, sd = self.seq_encoder, self.seq_decoder
-        return [se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias,
-                sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, sd[4].weight, sd[4].bias]
-
-    def flatten_parameters(self):
-        """Make the 12 trainable tensors views of ONE flat fp32 buffer.  Idempotent; call again after .to()."""
-        ps = self.trainable()
-        flat = self._flat
-        ok = flat is not None and flat.device == ps[0].device
-        off = 0
-        if ok:
-            for p in ps:
-                if p.data.data_ptr() != flat.data_ptr() + 4 * off or not p.data.is_contiguous():
-                    ok = False
-                    break
-                off += p.numel()
-        if not ok:
-            flat = torch.cat([p.data.detach().reshape(-1).float() for p in ps]).contiguous()
-            off = 0
-            for p in ps:
-                p.data = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-            self._flat = flat
-            self._view_cache = None
-        return self._flat
-
-    def _segment_views(self, buf, which):
-        d, Ld = self.obs_dim, self.latent_dim
-        spec = {"enc": [("We1", (HID, d)), ("be1", (HID,)), ("We2", (HID, HID)), ("be2", (HID,)), ("Wh", (2 * Ld, HID)),
-                        ("bh", (2 * Ld,))],
-                "dec": [("Wd1", (HID, Ld)), ("bd1", (HID,)), ("Wd2", (HID, HID)), ("bd2", (HID,)), ("Wx", (3 * d, HID)),
-                        ("bx", (3 * d,))]}[which]
-        out, off = {}, 0
-        for name, shp in spec:
-            n = math.prod(shp)
-            out[name] = buf[off:off + n].view(shp)
-            off += n
-        return out
-
-    def _views(self):
-        vc, flat = self._view_cache, self._flat
-        if vc is not None and flat is not None and vc[0] is flat and \
-                self.seq_encoder[0].weight.data.data_ptr() == flat.data_ptr() and \
-                self.seq_decoder[4].bias.data.data_ptr() == flat.data_ptr() + 4 * (flat.numel() - 3 * self.obs_dim):
-            return vc[1]
-        flat = self.flatten_parameters()
-        L.require_cuda(flat)
-        v = self._segment_views(flat[:self._n_enc], "enc")
-        v.update(self._segment_views(flat[self._n_enc:], "dec"))
-        self._view_cache = (flat, v)
-        return v
-
-    def _enc_weights(self):
-        se = self.seq_encoder
-        return (se[0].weight, se[0].bias, se[2].weight, se[2].bias, se[4].weight, se[4].bias)
-
-    def _dec_weights(self):
-        sd = self.seq_decoder
-        return (sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, sd[4].weight, sd[4].bias)
 
     # ---- reference API
     def _encode(self, x, mask, sample=True, eps=None, S=None):
@@ -423,6 +355,12 @@ class Reg_MIWAE(_MIWBase):
 
 
 # ------------------------------------------------------------------------------------------------ fused step
+# timer names of the chain launches, per layer, and the weight gradients' (timer name, index in the trainer's workspace)
+_T_ENC_FWD, _T_ENC_BWD, _T_DEC_FWD, _T_DEC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) * 3, ("dec_fwd",) * 3, ("dec_bwd",) * 3
+_DEC_WKEYS = (("dec_bwd", 2), ("dec_bwd", 1), ("dec_bwd", 0))
+_ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
+
+
 class MIWTrainer(_FlatAdamTrainer):
     """The whole training step of the MIWAE path (train.py:102-117 for 'reg_MIWAE*' / the final branch for
     'vanilla_MIWAE*') as a fixed sequence of HIP launches with no host synchronisation: mask_p draw + stacked encoder
@@ -432,6 +370,7 @@ class MIWTrainer(_FlatAdamTrainer):
 
     Single process only: the reference's row / sample pairing (module docstring) couples rows across the whole batch, so
     a step sharded over ranks cannot equal the single-process step without an all-gather of the per-row sums."""
+    step_timers = True
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
         if not isinstance(model, _MIWBase):
@@ -442,12 +381,12 @@ class MIWTrainer(_FlatAdamTrainer):
         super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
         self.reg = model.regularised
         self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        self.g = model._segment_views(self.grad[:model._n_enc], "enc")
-        self.g.update(model._segment_views(self.grad[model._n_enc:], "dec"))
-        self._B = None
+        self.g = model._named_views(self.grad)
+        self._B = self._v = None
 
-    def _ws(self, B):
-        if self._B == B:
+    def _ws(self, B, v=None):
+        v = self.model._views() if v is None else v
+        if self._B == B and self._v is v:
             return
         m, dev = self.model, self.dev
         d, Ld, S = m.obs_dim, m.latent_dim, m.num_samples
@@ -460,20 +399,20 @@ class MIWTrainer(_FlatAdamTrainer):
         self.z, self.g1, self.g2, self.Y = e(M, Ld), e(M, HID), e(M, HID), e(M, 3 * d)
         self.G, self.gh, self.dht = e(M, 3 * d), e(R, 2 * Ld), e(R, 2 * Ld)
         self.dg2, self.dg1, self.dz, self.dh2, self.dh1 = e(M, HID), e(M, HID), e(M, Ld), e(R, HID), e(R, HID)
-        self.wg_shapes = [(M, 3 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)]
-        sizes = [int(lib().vpc_linear_wgrad_scratch(*sh)) for sh in self.wg_shapes]
-        buf = e(sum(sizes))
-        self.wg_scratch, o = [], 0
-        for n in sizes:
-            self.wg_scratch.append(buf[o:o + n])
-            o += n
-        self._wg_cache = {}
+        # the two GEMM chains on their workspaces, and the per-layer partials of the six weight gradients in launch order
+        self.enc_layers, self.dec_layers = m._chains()
+        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht]
+        self.dec_acts, self.dec_dacts = [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G]
+        g = self.g
+        self._wgrad_workspace([(M, 3 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)],
+                              [(g[w], g[b]) for w, b in (("Wx", "bx"), ("Wd2", "bd2"), ("Wd1", "bd1"), ("Wh", "bh"),
+                                                         ("We2", "be2"), ("We1", "be1"))])
         self.scratch = miw_loss_scratch(B, S, dev)
         BS = B * S
         self._sl = dict(Yp=self.Y[BS:] if self.reg else None, Gp=self.G[BS:] if self.reg else None,
                         hp=self.hact[B:] if self.reg else None, ghp=self.gh[B:] if self.reg else None,
                         eq=self.eps[P], ep=self.eps[P + 1] if self.reg else None, es=self.eps[:P])
-        self._B = B
+        self._B, self._v = B, v
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30):
         """One optimiser step.  mask_p [B,d] and eps ([4,B,S,L] = forward q, forward p, loss q, loss p for Reg_MIWAE;
@@ -484,18 +423,17 @@ class MIWTrainer(_FlatAdamTrainer):
         xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
         L.require_cuda(xf, mf)
         B = xf.shape[0]
-        self._ws(B)
+        self._ws(B, v)
         reg = self.reg
         P = 2 if reg else 1
         R, M = P * B, P * B * S
-        t, sl, g = self._timed, self._sl, self.g
+        t, sl = self._timed, self._sl
         rng_inc = (self.eps.numel() + 3) // 4 + (B * d + 3) // 4 + 1
         if reg and mask_p is not None:
             mp = _f32c(mask_p.reshape(-1, d))
             nm_mul(xf, mf, self.xin[:B])
             nm_mul(xf, mp, self.xin[B:])
             if eps is None:
-                from .ops import fill_normal
                 fill_normal(self.eps, self.seed, self.rng_offset + (1 << 40))
         else:
             mp = self.mask_p if reg else None
@@ -505,44 +443,17 @@ class MIWTrainer(_FlatAdamTrainer):
             self.eps.copy_(eps.reshape(self.eps.shape))
         self.rng_offset += rng_inc
         # ---- forward
-        t("enc_fwd", linear_fwd, self.xin, v["We1"], v["be1"], self.h1, R, HID, d, ACT_RELU)
-        t("enc_fwd", linear_fwd, self.h1, v["We2"], v["be2"], self.h2, R, HID, HID, ACT_RELU)
-        t("enc_fwd", linear_fwd, self.h2, v["Wh"], v["bh"], self.heads, R, 2 * Ld, HID, ACT_NONE)
+        chain_fwd(self.enc_layers, self.enc_acts, R, 0, t, _T_ENC_FWD)
         t("sample", miw_sample, self.heads, self.hact, sl["es"], self.z, R, S, Ld)
-        t("dec_fwd", linear_fwd, self.z, v["Wd1"], v["bd1"], self.g1, M, HID, Ld, ACT_RELU)
-        t("dec_fwd", linear_fwd, self.g1, v["Wd2"], v["bd2"], self.g2, M, HID, HID, ACT_RELU)
-        t("dec_fwd", linear_fwd, self.g2, v["Wx"], v["bx"], self.Y, M, 3 * d, HID, ACT_NONE)
+        chain_fwd(self.dec_layers, self.dec_acts, M, 0, t, _T_DEC_FWD)
         # ---- loss on the raw heads: G = d loss / d raw decoder heads, gh = d loss / d (mean | scale)
         t("loss", miw_loss, xf, mf, mp, self.Y, sl["Yp"], 3 * d, 1, self.hact, sl["hp"], sl["eq"], sl["ep"], self.G,
           sl["Gp"], 3 * d, self.gh, sl["ghp"], None, self.scratch, self.out8, self.tail, self.accum, B, S, d, Ld, alpha,
           PAIR_REFERENCE)
         # ---- backward: weight-gradient partials per layer, all summed by one launch
-        defer = self.timers is None
-        pend = []
-
-        def wgrad(name, i, dy, xx, dw, db):
-            Mi, Ni, Ki = self.wg_shapes[i]
-            if not defer:
-                return t(name, linear_wgrad, dy, xx, dw, db, Mi, Ni, Ki)
-            linear_wgrad(dy, xx, None, None, Mi, Ni, Ki, scratch=self.wg_scratch[i])
-            pend.append((self.wg_scratch[i], Mi, Ni, Ki, dw, db, False))
-
-        wgrad("dec_bwd", 0, self.G, self.g2, g["Wx"], g["bx"])
-        t("dec_bwd", linear_dgrad, self.G, v["Wx"], self.dg2, M, 3 * d, HID, x_out=self.g2, act_prev=ACT_RELU)
-        wgrad("dec_bwd", 1, self.dg2, self.g1, g["Wd2"], g["bd2"])
-        t("dec_bwd", linear_dgrad, self.dg2, v["Wd2"], self.dg1, M, HID, HID, x_out=self.g1, act_prev=ACT_RELU)
-        wgrad("dec_bwd", 2, self.dg1, self.z, g["Wd1"], g["bd1"])
-        t("dec_bwd", linear_dgrad, self.dg1, v["Wd1"], self.dz, M, HID, Ld)
+        chain_bwd(self.dec_layers, self.dec_acts, self.dec_dacts, M, self._wgrad, _DEC_WKEYS, run=t, names=_T_DEC_BWD)
         t("sample_bwd", miw_sample_bwd, self.dz, sl["es"], self.heads, self.gh, self.dht, R, S, Ld)
-        wgrad("enc_bwd", 3, self.dht, self.h2, g["Wh"], g["bh"])
-        t("enc_bwd", linear_dgrad, self.dht, v["Wh"], self.dh2, R, 2 * Ld, HID, x_out=self.h2, act_prev=ACT_RELU)
-        wgrad("enc_bwd", 4, self.dh2, self.h1, g["We2"], g["be2"])
-        t("enc_bwd", linear_dgrad, self.dh2, v["We2"], self.dh1, R, HID, HID, x_out=self.h1, act_prev=ACT_RELU)
-        wgrad("enc_bwd", 5, self.dh1, self.xin, g["We1"], g["be1"])
-        if pend:
-            wgrad_reduce(pend, self._wg_cache)
-        self.step_count += 1
-        from .ops import adam_step
-        t("adam", adam_step, m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-          self.betas[1], self.adam_eps)
-        self._flat_written(None)
+        chain_bwd(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._wgrad, _ENC_WKEYS, input_grad=False, run=t,
+                  names=_T_ENC_BWD)
+        self._wgrad_reduce()
+        self._adam()

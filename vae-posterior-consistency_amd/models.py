@@ -17,25 +17,24 @@ There is no CPU fallback: calling forward / loss with CPU tensors raises.
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .images import PackedImage, ParamKeyMixin
+from .images import FlatParams, PackedImage, mlp_spec
 from .ops import DecoderFn, EncoderFn, LossFn, as_mask_u8
 
 MAX_EPOCH = 2800  # VAE.py:384
 
-_ENC = ("seq_encoder.0", "seq_encoder.2", "seq_encoder.4")
-_DEC = ("seq_decoder.0", "seq_decoder.2", "seq_decoder.4")
+_W6 = ("W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4", "W5", "b5", "W6", "b6")
 
 
-class _VAEBase(ParamKeyMixin, nn.Module):
+class _VAEBase(FlatParams, nn.Module):
     mask_augm = False  # True: encoder input is [x*mask | mask] (the reference's *_mask classes)
+    # the 12 trainable tensors in state_dict (= flat) order
+    _flat_spec = mlp_spec(_W6[:6], "seq_encoder", "enc") + mlp_spec(_W6[6:], "seq_decoder", "dec")
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples=1,
                  num_estimates=1):
@@ -71,50 +70,10 @@ class _VAEBase(ParamKeyMixin, nn.Module):
         self._part = {}
 
     # ------------------------------------------------------------------ parameter plumbing
-    def trainable(self):
-        """The 12 trainable tensors in state_dict (= flat) order.  (Cached: nn.Module attribute lookups cost ~0.4 ms per
-        training step on the API path, which is host-bound at the reference's batch sizes; .to() / load_state_dict keep
-        the Parameter objects.)"""
-        out = self.__dict__.get("_trainable_cache")
-        if out is None or out[0] is not self.seq_encoder[0].weight:
-            out = []
-            for name in _ENC + _DEC:
-                mod = self.get_submodule(name)
-                out += [mod.weight, mod.bias]
-            self.__dict__["_trainable_cache"] = out
-        return out
-
     def _lay(self):
         if self._layout is None:
             self._layout = L.layout(self.obs_dim, self.latent_dim, self.mask_augm)
         return self._layout
-
-    def flatten_parameters(self):
-        """Make the 12 trainable tensors views of ONE flat fp32 buffer (state_dict order).  Idempotent; call again
-        after .to(device).  Returns the flat buffer."""
-        ps = self.trainable()
-        flat = self.__dict__.get("_flat")
-        # fast path: first and last parameter still sit where the flat buffer puts them
-        if flat is not None and ps[0].data_ptr() == flat.data_ptr() and \
-                ps[-1].data_ptr() == flat.data_ptr() + 4 * (flat.numel() - ps[-1].numel()) and flat.device == ps[0].device:
-            return flat
-        off = 0
-        ok = flat is not None and flat.device == ps[0].device
-        if ok:
-            for p in ps:
-                if p.data.data_ptr() != flat.data_ptr() + 4 * off or not p.data.is_contiguous():
-                    ok = False
-                    break
-                off += p.numel()
-        if not ok:
-            flat = torch.cat([p.data.detach().reshape(-1).float() for p in ps]).contiguous()
-            off = 0
-            for p in ps:
-                p.data = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-            self._flat = flat
-            self.invalidate_images()
-        return self._flat
 
     def _new_image(self, device):
         lay = self._lay()

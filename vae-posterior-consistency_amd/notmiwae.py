@@ -13,73 +13,24 @@ adjacent in one flat parameter buffer, so each pair is ONE GEMM.  No CPU fallbac
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .images import PackedImage, ParamKeyMixin
+from .images import FlatParams, PackedImage
+from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now,
+                     wgrad_now_keys)
+from .linear import ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad, wgrad_reduce  # noqa: F401  (the GEMM ops were first
+# reached as vpc_amd.notmiwae.linear_*: the names stay importable from here; they are defined in linear.py only)
+from .ops import PRECISIONS, fill_normal, step_pack_weights_bf16
 from .trainer import _FlatAdamTrainer
 
 HID = 128  # VAE.py:2343-2363 hard-codes 128 (hid_dim is ignored by the reference too)
-ACT_NONE, ACT_ELU, ACT_SIGMOID_HARDTANH, ACT_RELU = 0, 1, 2, 3
 
 
 # ------------------------------------------------------------------------------------------------ raw ops
-def linear_fwd(x, w, b, y, M, N, K, act=ACT_NONE, split=0, ldx=None, ldy=None, precision=0):
-    check(lib().vpc_linear_fwd(ptr(x), ldx or K, ptr(w), ptr(b), ptr(y), ldy or N, M, N, K, act, split, int(precision),
-                               stream_ptr()), "vpc_linear_fwd")
-
-
-def linear_dgrad(dy, w, dx, M, N, K, y_gate=None, gate=ACT_NONE, gate_split=0, x_out=None, act_prev=ACT_NONE,
-                 lddy=None, lddx=None, precision=0):
-    check(lib().vpc_linear_dgrad(ptr(dy), lddy or N, ptr(y_gate), lddy or N, gate, gate_split, ptr(w), ptr(x_out), K,
-                                 act_prev, ptr(dx), lddx or K, M, N, K, int(precision), stream_ptr()), "vpc_linear_dgrad")
-
-
-_scratch = {}
-
-
-def _wgrad_scratch(device, floats):
-    key = str(device)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < floats:
-        buf = torch.empty(max(floats, 1 << 20), device=device)
-        _scratch[key] = buf
-    return buf
-
-
-def linear_wgrad(dy, x, dw, db, M, N, K, y_gate=None, gate=ACT_NONE, gate_split=0, accumulate=False, lddy=None,
-                 ldx=None, precision=0, scratch=None):
-    """dw = None: write only the per-split partials into `scratch` (the caller's own buffer for this layer); they are summed
-    later, together with other layers', by wgrad_reduce (one launch)."""
-    sc = _wgrad_scratch(dy.device, int(lib().vpc_linear_wgrad_scratch(M, N, K))) if scratch is None else scratch
-    check(lib().vpc_linear_wgrad(ptr(dy), lddy or N, ptr(y_gate), lddy or N, gate, gate_split, ptr(x), ldx or K,
-                                 ptr(dw), ptr(db), ptr(sc), sc.numel(), M, N, K, int(accumulate), int(precision),
-                                 stream_ptr()), "vpc_linear_wgrad")
-
-
-def wgrad_reduce(layers, cache=None):
-    """layers: [(scratch, M, N, K, dw, db, accumulate)] of linear_wgrad(dw=None) calls -> all gradients in ONE launch.
-    `cache` (a dict owned by the caller): the argument arrays are built once per set of buffers, not per step."""
-    if cache is not None and "args" in cache:
-        check(lib().vpc_linear_wgrad_reduce(*cache["args"], stream_ptr()), "vpc_linear_wgrad_reduce")
-        return
-    n = len(layers)
-    sc = (C.c_void_p * n)(*[t[0].data_ptr() for t in layers])
-    Ms = (C.c_long * n)(*[int(t[1]) for t in layers])
-    Ns = (C.c_int * n)(*[int(t[2]) for t in layers])
-    Ks = (C.c_int * n)(*[int(t[3]) for t in layers])
-    dw = (C.c_void_p * n)(*[t[4].data_ptr() for t in layers])
-    db = (C.c_void_p * n)(*[None if t[5] is None else t[5].data_ptr() for t in layers])
-    acc = (C.c_int * n)(*[int(bool(t[6])) for t in layers])
-    if cache is not None:
-        cache["args"] = (n, sc, Ms, Ns, Ks, dw, db, acc)
-    check(lib().vpc_linear_wgrad_reduce(n, sc, Ms, Ns, Ks, dw, db, acc, stream_ptr()), "vpc_linear_wgrad_reduce")
-
-
 def nm_sample(heads, eps, z, B, K, Ld):
     check(lib().vpc_nm_sample(ptr(heads), 2 * Ld, ptr(eps), ptr(z), Ld, B, K, Ld, stream_ptr()), "vpc_nm_sample")
 
@@ -166,10 +117,6 @@ def nmdec_step(img, x, mask, mask_p, heads, eps, dht, part, stat, gidx, inv, gra
           "vpc_nmdec_step")
 
 
-def _f32c(t):
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
-
-
 def _rows_view(t, B, K, d):
     """[B, K, d] tensor -> (tensor to pass, row pitch) without copying when rows b*K+k are equally spaced."""
     if t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1 and t.stride(0) == K * t.stride(1) \
@@ -180,50 +127,47 @@ def _rows_view(t, B, K, d):
 
 
 # ------------------------------------------------------------------------------------------------ autograd
+def _chains(v):
+    """(encoder, decoder) chains on the named views v: ELU between layers, raw heads | Sigmoid on x_mean, Hardtanh on x_logvar."""
+    return (chain((v["We1"], v["be1"], v["We2"], v["be2"], v["Wh"], v["bh"]), (ACT_ELU, ACT_ELU, ACT_NONE)),
+            chain((v["Wd1"], v["bd1"], v["Wd2"], v["bd2"], v["Wx"], v["bx"]), (ACT_ELU, ACT_ELU, ACT_SIGMOID_HARDTANH),
+                  v["Wxm"].shape[0]))
+
+
 class NMEncoderFn(torch.autograd.Function):
     """(x, mask, eps) -> (z [B,K,L], heads [B, mean L | logvar L]).  VAE.py:2378-2391 / :2749-2765."""
 
     @staticmethod
     def forward(ctx, model, x, mask, eps, K, *weights):
         require_cuda(x, mask, eps, *weights)
-        v = model._views()
-        d, Ld = model.obs_dim, model.latent_dim
+        Ld = model.latent_dim
         B, dev = x.shape[0], x.device
-        xin = torch.empty(B, d, device=dev)
-        nm_mul(x, mask, xin)
-        h1 = torch.empty(B, HID, device=dev)
-        h2 = torch.empty(B, HID, device=dev)
-        heads = torch.empty(B, 2 * Ld, device=dev)
-        linear_fwd(xin, v["We1"], v["be1"], h1, B, HID, d, ACT_ELU)
-        linear_fwd(h1, v["We2"], v["be2"], h2, B, HID, HID, ACT_ELU)
-        linear_fwd(h2, v["Wh"], v["bh"], heads, B, 2 * Ld, HID, ACT_NONE)
+        layers = model._chains()[0]
+        acts = chain_buffers(layers, B, dev)
+        nm_mul(x, mask, acts[0])
+        chain_fwd(layers, acts, B)
+        heads = acts[3]
         z = torch.empty(B * K, Ld, device=dev)
         nm_sample(heads, eps, z, B, K, Ld)
         ctx.model, ctx.K = model, K
-        ctx.save_for_backward(xin, h1, h2, heads, eps if eps is not None else torch.empty(0, device=dev))
+        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev))
         ctx.has_eps = eps is not None
         return z.view(B, K, Ld), heads
 
     @staticmethod
     def backward(ctx, dz, dheads):
         model, K = ctx.model, ctx.K
-        xin, h1, h2, heads, eps = ctx.saved_tensors
+        *acts, eps = ctx.saved_tensors
         eps = eps if ctx.has_eps else None
-        v = model._views()
-        d, Ld = model.obs_dim, model.latent_dim
-        B, dev = xin.shape[0], xin.device
-        dht = torch.empty(B, 2 * Ld, device=dev)
-        nm_sample_bwd(_f32c(dz).reshape(B * K, Ld), eps, heads, _f32c(dheads), dht, B, K, Ld)
-        g = model._grad_views(torch.empty(model._n_enc, device=dev), "enc")
-        dh2 = torch.empty(B, HID, device=dev)
-        dh1 = torch.empty(B, HID, device=dev)
-        linear_wgrad(dht, h2, g["Wh"], g["bh"], B, 2 * Ld, HID)
-        linear_dgrad(dht, v["Wh"], dh2, B, 2 * Ld, HID, x_out=h2, act_prev=ACT_ELU)
-        linear_wgrad(dh2, h1, g["We2"], g["be2"], B, HID, HID)
-        linear_dgrad(dh2, v["We2"], dh1, B, HID, HID, x_out=h1, act_prev=ACT_ELU)
-        linear_wgrad(dh1, xin, g["We1"], g["be1"], B, HID, d)
-        return (None, None, None, None, None, g["We1"], g["be1"], g["We2"], g["be2"], g["Wmu"], g["bmu"], g["Wls"],
-                g["bls"])
+        Ld = model.latent_dim
+        B, dev = acts[0].shape[0], acts[0].device
+        layers = model._chains()[0]
+        dacts = chain_buffers(layers, B, dev, first=False)
+        nm_sample_bwd(_f32c(dz).reshape(B * K, Ld), eps, acts[3], _f32c(dheads), dacts[3], B, K, Ld)
+        g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
+        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, ("We1", "be1", "We2", "be2", "Wh", "bh"), B),
+                  input_grad=False)
+        return (None, None, None, None, None, *[g[k] for k in model._segment_names("enc")])
 
 
 class NMDecoderFn(torch.autograd.Function):
@@ -232,29 +176,24 @@ class NMDecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, z, *weights):
         require_cuda(z, *weights)
-        v = model._views()
         d, Ld = model.obs_dim, model.latent_dim
         lead = z.shape[:-1]
         z2 = _f32c(z).reshape(-1, Ld)
-        M, dev = z2.shape[0], z2.device
-        g1 = torch.empty(M, HID, device=dev)
-        g2 = torch.empty(M, HID, device=dev)
-        Y = torch.empty(M, 2 * d, device=dev)
-        linear_fwd(z2, v["Wd1"], v["bd1"], g1, M, HID, Ld, ACT_ELU)
-        linear_fwd(g1, v["Wd2"], v["bd2"], g2, M, HID, HID, ACT_ELU)
-        linear_fwd(g2, v["Wx"], v["bx"], Y, M, 2 * d, HID, ACT_SIGMOID_HARDTANH, d)
+        M = z2.shape[0]
+        layers = model._chains()[1]
+        acts = chain_buffers(layers, M, z2.device, first=z2)
+        chain_fwd(layers, acts, M)
         ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(z2, g1, g2, Y)
-        Y3 = Y.view(*lead, 2 * d)
+        ctx.save_for_backward(*acts)
+        Y3 = acts[3].view(*lead, 2 * d)
         return Y3[..., :d], Y3[..., d:]
 
     @staticmethod
     def backward(ctx, gxm, gxl):
         model = ctx.model
-        z2, g1, g2, Y = ctx.saved_tensors
-        v = model._views()
+        acts = ctx.saved_tensors
         d, Ld = model.obs_dim, model.latent_dim
-        M, dev = z2.shape[0], z2.device
+        M, dev = acts[0].shape[0], acts[0].device
         # the fused loss hands back the two halves of one [M, 2d] buffer: use it in place
         G = None
         if (gxm.dtype == torch.float32 and gxl.dtype == torch.float32 and gxm.dim() >= 2
@@ -264,19 +203,12 @@ class NMDecoderFn(torch.autograd.Function):
             G = gxm.as_strided((M, 2 * d), (2 * d, 1))
         if G is None:
             G = torch.cat([_f32c(gxm).reshape(M, d), _f32c(gxl).reshape(M, d)], 1)
-        g = model._grad_views(torch.empty(model._n_dec, device=dev), "dec")
-        dg2 = torch.empty(M, HID, device=dev)
-        dg1 = torch.empty(M, HID, device=dev)
-        dz = torch.empty(M, Ld, device=dev)
-        linear_wgrad(G, g2, g["Wx"], g["bx"], M, 2 * d, HID, y_gate=Y, gate=ACT_SIGMOID_HARDTANH, gate_split=d)
-        linear_dgrad(G, v["Wx"], dg2, M, 2 * d, HID, y_gate=Y, gate=ACT_SIGMOID_HARDTANH, gate_split=d, x_out=g2,
-                     act_prev=ACT_ELU)
-        linear_wgrad(dg2, g1, g["Wd2"], g["bd2"], M, HID, HID)
-        linear_dgrad(dg2, v["Wd2"], dg1, M, HID, HID, x_out=g1, act_prev=ACT_ELU)
-        linear_wgrad(dg1, z2, g["Wd1"], g["bd1"], M, HID, Ld)
-        linear_dgrad(dg1, v["Wd1"], dz, M, HID, Ld)
-        return (None, dz.view(*ctx.lead, Ld), g["Wd1"], g["bd1"], g["Wd2"], g["bd2"], g["Wxm"], g["bxm"], g["Wxl"],
-                g["bxl"])
+        layers = model._chains()[1]
+        dacts = chain_buffers(layers, M, dev, last=G)
+        g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
+        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, ("Wd1", "bd1", "Wd2", "bd2", "Wx", "bx"), M),
+                  y_gate=acts[3], gate=ACT_SIGMOID_HARDTANH, gate_split=d)
+        return (None, dacts[0].view(*ctx.lead, Ld), *[g[k] for k in model._segment_names("dec")])
 
 
 class NMLossFn(torch.autograd.Function):
@@ -348,8 +280,21 @@ class NMLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ model classes
-class _NMBase(ParamKeyMixin, nn.Module):
+class _NMBase(FlatParams, nn.Module):
     regularised = False
+    # flat parameter buffer: [W b | We1 be1 We2 be2 Wmu Wls bmu bls | Wd1 bd1 Wd2 bd2 Wxm Wxl bxm bxl]; the two heads of the
+    # encoder and of the decoder are adjacent, so each pair is one GEMM operand (Wh / bh, Wx / bx)
+    _flat_spec = (("W", "W", "wb", (-1,)), ("b", "b", "wb", (-1,)),
+                  ("We1", "seq_encoder.0.weight", "enc"), ("be1", "seq_encoder.0.bias", "enc"),
+                  ("We2", "seq_encoder.2.weight", "enc"), ("be2", "seq_encoder.2.bias", "enc"),
+                  ("Wmu", "q_mu.0.weight", "enc"), ("Wls", "q_logstd.0.weight", "enc"),
+                  ("bmu", "q_mu.0.bias", "enc"), ("bls", "q_logstd.0.bias", "enc"),
+                  ("Wd1", "seq_decoder.0.weight", "dec"), ("bd1", "seq_decoder.0.bias", "dec"),
+                  ("Wd2", "seq_decoder.2.weight", "dec"), ("bd2", "seq_decoder.2.bias", "dec"),
+                  ("Wxm", "x_mean.0.weight", "dec"), ("Wxl", "x_logvar.0.weight", "dec"),
+                  ("bxm", "x_mean.0.bias", "dec"), ("bxl", "x_logvar.0.bias", "dec"))
+    _flat_aliases = {"Wh": ("Wmu", "Wls"), "bh": ("bmu", "bls"), "Wx": ("Wxm", "Wxl"), "bx": ("bxm", "bxl")}
+    _build_chains = staticmethod(_chains)
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
         super().__init__()
@@ -382,102 +327,6 @@ class _NMBase(ParamKeyMixin, nn.Module):
         self.b = nn.Parameter(emb2)
         self.activation = nn.Softplus()
         self._flat = None
-        self._n_enc = HID * d + HID + HID * HID + HID + 2 * Ld * HID + 2 * Ld
-        self._n_dec = HID * Ld + HID + HID * HID + HID + 2 * d * HID + 2 * d
-
-    # ---- flat parameter buffer: [W b | We1 be1 We2 be2 Wmu Wls bmu bls | Wd1 bd1 Wd2 bd2 Wxm Wxl bxm bxl]
-    def _flat_order(self):
-        se, sd = self.seq_encoder, self.seq_decoder
-        return [("W", self.W), ("b", self.b),
-                ("We1", se[0].weight), ("be1", se[0].bias), ("We2", se[2].weight), ("be2", se[2].bias),
-                ("Wmu", self.q_mu[0].weight), ("Wls", self.q_logstd[0].weight),
-                ("bmu", self.q_mu[0].bias), ("bls", self.q_logstd[0].bias),
-                ("Wd1", sd[0].weight), ("bd1", sd[0].bias), ("Wd2", sd[2].weight), ("bd2", sd[2].bias),
-                ("Wxm", self.x_mean[0].weight), ("Wxl", self.x_logvar[0].weight),
-                ("bxm", self.x_mean[0].bias), ("bxl", self.x_logvar[0].bias)]
-
-    def trainable(self):
-        """The 18 trainable tensors in flat-buffer order."""
-        return [p for _, p in self._flat_order()]
-
-    def flatten_parameters(self):
-        """Make the 18 trainable tensors views of ONE flat fp32 buffer.  Idempotent; call again after .to()."""
-        order = self._flat_order()
-        flat = self._flat
-        ok = flat is not None and flat.device == order[0][1].device
-        off = 0
-        if ok:
-            for _, p in order:
-                if p.data.data_ptr() != flat.data_ptr() + 4 * off or not p.data.is_contiguous():
-                    ok = False
-                    break
-                off += p.numel()
-        if not ok:
-            flat = torch.cat([p.data.detach().reshape(-1).float() for _, p in order]).contiguous()
-            off = 0
-            for _, p in order:
-                p.data = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-            self._flat = flat
-            self._view_cache = None
-        return self._flat
-
-    def _segment_views(self, buf, which):
-        """Named views into a buffer laid out like the 'wb' / 'enc' / 'dec' segment of the flat buffer."""
-        d, Ld = self.obs_dim, self.latent_dim
-        spec = {"wb": [("W", (d,)), ("b", (d,))],
-                "enc": [("We1", (HID, d)), ("be1", (HID,)), ("We2", (HID, HID)), ("be2", (HID,)), ("Wmu", (Ld, HID)),
-                        ("Wls", (Ld, HID)), ("bmu", (Ld,)), ("bls", (Ld,))],
-                "dec": [("Wd1", (HID, Ld)), ("bd1", (HID,)), ("Wd2", (HID, HID)), ("bd2", (HID,)), ("Wxm", (d, HID)),
-                        ("Wxl", (d, HID)), ("bxm", (d,)), ("bxl", (d,))]}[which]
-        out, off = {}, 0
-        for name, shp in spec:
-            n = math.prod(shp)
-            out[name] = buf[off:off + n].view(shp)
-            off += n
-        if which == "enc":
-            o = out["Wmu"].storage_offset() - buf.storage_offset()
-            out["Wh"] = buf[o:o + 2 * Ld * HID].view(2 * Ld, HID)
-            o += 2 * Ld * HID
-            out["bh"] = buf[o:o + 2 * Ld]
-        elif which == "dec":
-            o = out["Wxm"].storage_offset() - buf.storage_offset()
-            out["Wx"] = buf[o:o + 2 * d * HID].view(2 * d, HID)
-            o += 2 * d * HID
-            out["bx"] = buf[o:o + 2 * d]
-        return out
-
-    def _views(self):
-        # fast path (every training step): the flat buffer and the cached views are current when the first and the last parameter
-        # still sit where the flat buffer has them - `.to()` / re-assignment moves all 18, in-place loads keep them (the full
-        # check of flatten_parameters walks every parameter: ~12 us of a host-paced 0.19 ms step)
-        vc = getattr(self, "_view_cache", None)
-        flat = self._flat
-        if vc is not None and flat is not None and vc[0] is flat and self.W.data.data_ptr() == flat.data_ptr() and \
-                self.x_logvar[0].bias.data.data_ptr() == flat.data_ptr() + 4 * (flat.numel() - self.obs_dim):
-            return vc[1]
-        flat = self.flatten_parameters()
-        L.require_cuda(flat)
-        if getattr(self, "_view_cache", None) is None or self._view_cache[0] is not flat:
-            d = self.obs_dim
-            v = self._segment_views(flat[:2 * d], "wb")
-            v.update(self._segment_views(flat[2 * d:2 * d + self._n_enc], "enc"))
-            v.update(self._segment_views(flat[2 * d + self._n_enc:], "dec"))
-            self._view_cache = (flat, v)
-        return self._view_cache[1]
-
-    def _grad_views(self, buf, which):
-        return self._segment_views(buf, which)
-
-    def _enc_weights(self):
-        se = self.seq_encoder
-        return (se[0].weight, se[0].bias, se[2].weight, se[2].bias, self.q_mu[0].weight, self.q_mu[0].bias,
-                self.q_logstd[0].weight, self.q_logstd[0].bias)
-
-    def _dec_weights(self):
-        sd = self.seq_decoder
-        return (sd[0].weight, sd[0].bias, sd[2].weight, sd[2].bias, self.x_mean[0].weight, self.x_mean[0].bias,
-                self.x_logvar[0].weight, self.x_logvar[0].bias)
 
     # ---- reference API
     def _encode(self, x, mask, sample=True, eps=None):
@@ -582,12 +431,20 @@ class notMIWAE_myversion(_NMBase):
 
 
 # ------------------------------------------------------------------------------------------------ fused step
+# timer names of the chain launches, per layer, and the weight gradients' (timer name, index in the trainer's workspace)
+_ENC_FWD, _ENC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) * 3
+_DEC_FWD, _DEC_DGRAD = ("dec_fwd1", "dec_fwd2", "dec_fwd3"), ("dec_dgrad1", "dec_dgrad2", "dec_dgrad3")
+_DEC_WKEYS = (("dec_wgrad1", 2), ("dec_wgrad2", 1), ("dec_wgrad3", 0))
+_ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
+
+
 class NMTrainer(_FlatAdamTrainer):
     """The whole training step of the MNAR path (train.py:28-117 for 'reg_notMIWAE*' / 'vanilla_notMIWAE*') as a
     fixed sequence of HIP launches, no host synchronisation: float mask_p draw + stacked encoder input, Philox
     normals, encoder / decoder GEMM chains with the q and p passes STACKED along the batch (one GEMM per layer for
     both passes), the fused loss kernel, the backward GEMM chain writing straight into one flat gradient buffer,
     one all-reduce of [grads | loss] under data parallelism, flat Adam."""
+    step_timers = True
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0,
                  precision="f32"):
@@ -596,7 +453,6 @@ class NMTrainer(_FlatAdamTrainer):
         epsilon, `self.adam_eps`; `self.eps` is the step's workspace of normals.)"""
         if not isinstance(model, _NMBase):
             raise TypeError("NMTrainer supports REG_notMIWAE_v2 and notMIWAE_myversion")
-        from .ops import PRECISIONS
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r}: expected one of {sorted(PRECISIONS)}")
         super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
@@ -604,18 +460,16 @@ class NMTrainer(_FlatAdamTrainer):
         self.precision, self.prec = precision, PRECISIONS[precision]
         self.loss = self.tail  # [grads | loss] -> ONE all-reduce per step
         self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        d = model.obs_dim
-        self.g = model._segment_views(self.grad[:2 * d], "wb")
-        self.g.update(model._segment_views(self.grad[2 * d:2 * d + model._n_enc], "enc"))
-        self.g.update(model._segment_views(self.grad[2 * d + model._n_enc:], "dec"))
-        self._B = None
+        self.g = model._named_views(self.grad)
+        self._B = self._v = None
 
     def invalidate_image(self):
         """Alias of model.invalidate_images(): after writing parameters behind torch's version counters."""
         self.model.invalidate_images()
 
-    def _ws(self, B):
-        if self._B == B:
+    def _ws(self, B, v=None):
+        v = self.model._views() if v is None else v
+        if self._B == B and self._v is v:
             return
         m, dev = self.model, self.dev
         d, Ld, K = m.obs_dim, m.latent_dim, m.num_samples
@@ -633,16 +487,14 @@ class NMTrainer(_FlatAdamTrainer):
         self.dg2, self.dg1, self.dz = e(Mg, HID), e(Mg, HID), e(Mg, Ld)
         Rg = 0 if self.use_nmdec else R     # (the fused path's encoder backward is one kernel too: nmenc_bwd)
         self.dh2, self.dh1 = e(Rg, HID), e(Rg, HID)
-        # per-layer partial buffers of the six weight gradients (summed by ONE launch at the end of the backward pass)
-        self.wg_shapes = [(M, 2 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)]
-        sizes = [0 if self.use_nmdec else int(lib().vpc_linear_wgrad_scratch(*sh))
-                 for i, sh in enumerate(self.wg_shapes)]
-        buf = e(sum(sizes))
-        self._wg_cache = {}
-        self.wg_scratch, o = [], 0
-        for n in sizes:
-            self.wg_scratch.append(buf[o:o + n])
-            o += n
+        # the two GEMM chains on their workspaces, and the per-layer partial buffers of the six weight gradients in launch order
+        self.enc_layers, self.dec_layers = m._chains()
+        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht]
+        self.dec_acts, self.dec_dacts = [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G]
+        g = self.g
+        self._wgrad_workspace([(M, 2 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)],
+                              [(g["Wx"], g["bx"]), (g["Wd2"], g["bd2"]), (g["Wd1"], g["bd1"]), (g["Wh"], g["bh"]),
+                               (g["We2"], g["be2"]), (g["We1"], g["be1"])], sized=not self.use_nmdec)
         nbytes = int(lib().vpc_nm_loss_scratch(B, d))
         self.scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         # the slices the step passes to its launches, made once per batch size (a tensor view costs 1-3 us of host time, and the
@@ -660,13 +512,12 @@ class NMTrainer(_FlatAdamTrainer):
                 self._nd_tables = nmdec_tables(m, dev)
                 self.nd_img = torch.zeros(nimg.value, device=dev)
                 # ONE image (decoder, missingness model, encoder), packed lazily under the model's parameter key (images.py)
-                from .ops import step_pack_weights_bf16
                 pidx = self._nd_tables[0]
                 self._nd = PackedImage(self.nd_img, lambda flat, buf: step_pack_weights_bf16(flat, pidx, buf))
             self.nd_part = e(nblk.value * npart.value)
             self.ne_part = e(nblk.value * int(self._nd_tables[3].numel()))  # the encoder-backward kernel's blocks (fused tail)
             self.nd_stat = torch.empty(nblk.value * 5, dtype=torch.float64, device=dev)
-        self._B = B
+        self._B, self._v = B, v
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30, global_batch=None, row_lo=None,
              _state=None):
@@ -681,7 +532,7 @@ class NMTrainer(_FlatAdamTrainer):
         L.require_cuda(xf, mf)
         B = xf.shape[0]
         Bg = global_batch or B * self.world_size  # every rank normalises by the GLOBAL batch: SUM over ranks = result
-        self._ws(B)
+        self._ws(B, v)
         reg = self.reg
         P = 2 if reg else 1
         R, M, BK = P * B, P * B * K, B * K
@@ -699,7 +550,6 @@ class NMTrainer(_FlatAdamTrainer):
             nm_mul(xf, mf, self.xin[:B])
             nm_mul(xf, mp, self.xin[B:])
             if eps is None:
-                from .ops import fill_normal
                 fill_normal(self.eps, self.seed, self.rng_offset + (1 << 40) + rank_off, _state, eps_shard)
         else:
             mp = self.mask_p if reg else None
@@ -722,22 +572,7 @@ class NMTrainer(_FlatAdamTrainer):
             t("pack", self._nd.get, key, m._flat)
             t("enc_fwd", nmenc_fwd, self.nd_img, self.xin, self.h1, self.h2, self.heads, R, d, Ld)
         else:
-            t("enc_fwd", linear_fwd, self.xin, v["We1"], v["be1"], self.h1, R, HID, d, ACT_ELU, precision=self.prec)
-            t("enc_fwd", linear_fwd, self.h1, v["We2"], v["be2"], self.h2, R, HID, HID, ACT_ELU, precision=self.prec)
-            t("enc_fwd", linear_fwd, self.h2, v["Wh"], v["bh"], self.heads, R, 2 * Ld, HID, ACT_NONE, precision=self.prec)
-        g = self.g
-        # weight gradients: partials per layer, all summed by one launch after the last one (6 reduction launches less;
-        # the timer mode keeps the per-layer form so that every entry brackets a complete gradient)
-        defer = self.timers is None
-        pend = []
-
-        def wgrad(name, i, dy, xx, dw, db):
-            Mi, Ni, Ki = self.wg_shapes[i]
-            if not defer:
-                return t(name, linear_wgrad, dy, xx, dw, db, Mi, Ni, Ki, precision=self.prec)
-            linear_wgrad(dy, xx, None, None, Mi, Ni, Ki, precision=self.prec, scratch=self.wg_scratch[i])
-            pend.append((self.wg_scratch[i], Mi, Ni, Ki, dw, db, False))
-
+            chain_fwd(self.enc_layers, self.enc_acts, R, self.prec, t, _ENC_FWD)
         if self.use_nmdec:
             # K-fold rsample, decoder, loss, decoder backward and the K-fold sum of dz in ONE kernel (csrc/vpc_nmdec.hip): the
             # decoder / missingness-model gradients land in self.grad, d loss / d heads in self.dht
@@ -756,33 +591,17 @@ class NMTrainer(_FlatAdamTrainer):
             # the encoder's backward in one kernel + its reduction (nmenc_bwd_kernel), through the decoder's partial-block buffer
             t("enc_bwd", nmenc_bwd, self.nd_img, self.xin, self.h1, self.h2, self.dht, self.nd_part, einv, self.grad, R, d, Ld)
         else:
-            self._step_decoder_gemms(xf, mf, mp, B, Bg, alpha, _state, rng_inc, t, v, wgrad)
-            self._step_encoder_bwd_gemms(R, t, v, wgrad)
-        if pend:
-            wgrad_reduce(pend, self._wg_cache)  # (buffers and gradient views are fixed for a batch size: arrays built once)
-        self._step_tail(t, _state)
-
-    def _step_encoder_bwd_gemms(self, R, t, v, wgrad):
-        m, g = self.model, self.g
-        d, Ld = m.obs_dim, m.latent_dim
-        wgrad("enc_bwd", 3, self.dht, self.h2, g["Wh"], g["bh"])
-        t("enc_bwd", linear_dgrad, self.dht, v["Wh"], self.dh2, R, 2 * Ld, HID, x_out=self.h2, act_prev=ACT_ELU, precision=self.prec)
-        wgrad("enc_bwd", 4, self.dh2, self.h1, g["We2"], g["be2"])
-        t("enc_bwd", linear_dgrad, self.dh2, v["We2"], self.dh1, R, HID, HID, x_out=self.h1, act_prev=ACT_ELU, precision=self.prec)
-        wgrad("enc_bwd", 5, self.dh1, self.xin, g["We1"], g["be1"])
-
-    def _step_tail(self, t, _state):
-        m = self.model
-        if self.world_size > 1:
+            # weight gradients: partials per layer, all summed by one launch after the last one (6 reduction launches less)
+            self._step_decoder_gemms(xf, mf, mp, B, Bg, alpha, _state, rng_inc, t, v)
+            chain_bwd(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._wgrad, _ENC_WKEYS, input_grad=False,
+                      precision=self.prec, run=t, names=_ENC_BWD)
+            self._wgrad_reduce()
+        dp = self.world_size > 1
+        if dp:
             self._allreduce()
-        self.step_count += 1
-        from .ops import adam_step
-        t("adam", adam_step, m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr,
-          self.betas[0], self.betas[1], self.adam_eps, None, None, None if _state is None else _state[0:1],
-          loss_in=self.loss if self.world_size > 1 else None, accum=self.accum if self.world_size > 1 else None)
-        self._flat_written(None)
+        self._adam(None if _state is None else _state[0:1], self.loss if dp else None, self.accum if dp else None)
 
-    def _step_decoder_gemms(self, xf, mf, mp, B, Bg, alpha, _state, rng_inc, t, v, wgrad):
+    def _step_decoder_gemms(self, xf, mf, mp, B, Bg, alpha, _state, rng_inc, t, v):
         """Decoder forward, loss and decoder backward as the GEMM chain (every precision, both model classes)."""
         m, reg = self.model, self.reg
         d, Ld, K = m.obs_dim, m.latent_dim, m.num_samples
@@ -790,9 +609,7 @@ class NMTrainer(_FlatAdamTrainer):
         R, M, BK = P * B, P * B * K, B * K
         sl = self._sl
         t("sample", nm_sample, self.heads, self.eps if reg else sl["eps0"], self.z, R, K, Ld)
-        t("dec_fwd1", linear_fwd, self.z, v["Wd1"], v["bd1"], self.g1, M, HID, Ld, ACT_ELU, precision=self.prec)
-        t("dec_fwd2", linear_fwd, self.g1, v["Wd2"], v["bd2"], self.g2, M, HID, HID, ACT_ELU, precision=self.prec)
-        t("dec_fwd3", linear_fwd, self.g2, v["Wx"], v["bx"], self.Y, M, 2 * d, HID, ACT_SIGMOID_HARDTANH, d, precision=self.prec)
+        chain_fwd(self.dec_layers, self.dec_acts, M, self.prec, t, _DEC_FWD)
         # ---- loss + output-side gradients
         Y, G = self.Y, self.G
         t("loss", nm_loss, xf, mf, mp, Y, sl["Yl"], 2 * d, sl["Yp"], sl["Ypl"], 2 * d,
@@ -802,13 +619,8 @@ class NMTrainer(_FlatAdamTrainer):
           self.accum if self.world_size == 1 else None,  # data parallel: the epoch total takes the ALL-REDUCED loss (below)
           B, Bg, K, d, Ld, alpha, _state, rng_inc, True)
         # ---- backward (G already holds the head pre-activation gradients: no gate pass over Y)
-        g = self.g
-        wgrad("dec_wgrad3", 0, G, self.g2, g["Wx"], g["bx"])
-        t("dec_dgrad3", linear_dgrad, G, v["Wx"], self.dg2, M, 2 * d, HID, x_out=self.g2, act_prev=ACT_ELU, precision=self.prec)
-        wgrad("dec_wgrad2", 1, self.dg2, self.g1, g["Wd2"], g["bd2"])
-        t("dec_dgrad2", linear_dgrad, self.dg2, v["Wd2"], self.dg1, M, HID, HID, x_out=self.g1, act_prev=ACT_ELU, precision=self.prec)
-        wgrad("dec_wgrad1", 2, self.dg1, self.z, g["Wd1"], g["bd1"])
-        t("dec_dgrad1", linear_dgrad, self.dg1, v["Wd1"], self.dz, M, HID, Ld, precision=self.prec)
+        chain_bwd(self.dec_layers, self.dec_acts, self.dec_dacts, M, self._wgrad, _DEC_WKEYS, precision=self.prec, run=t,
+                  names=_DEC_DGRAD)
         t("sample_bwd", nm_sample_bwd, self.dz, self.eps if reg else sl["eps0"], self.heads, self.gheads, self.dht, R,
           K, Ld)
 

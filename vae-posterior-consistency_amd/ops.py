@@ -11,6 +11,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, farray, lib, ptr, ptr_array, require_cuda, stream_ptr
+from .linear import _f32c  # noqa: F401  (also reached as ops._f32c)
 
 H1P, H2P = 112, 64  # padded hidden widths of the h1 / h2 workspaces (csrc/vpc_layout.h)
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -32,10 +33,6 @@ def as_mask_u8(mask: torch.Tensor) -> torch.Tensor:
     except Exception:
         pass
     return m
-
-
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ raw ops

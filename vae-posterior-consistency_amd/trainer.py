@@ -1,6 +1,7 @@
-"""What the step trainers (FusedTrainer, NMTrainer, EDDITrainer, WideTrainer) share: Adam state on one flat parameter
-buffer, the flat bucket [grads | loss tail] that data parallelism all-reduces in ONE collective, timers, the loss readers
-and the capture / replay of a step as a HIP graph."""
+"""What the step trainers (FusedTrainer, NMTrainer, EDDITrainer, WideTrainer, MIWTrainer, FlowTrainer, EDDIMnistTrainer)
+share: Adam state on one flat parameter buffer and the Adam launch that closes a step, the flat bucket [grads | loss tail]
+that data parallelism all-reduces in ONE collective, the deferred weight gradients of the GEMM chains (per-layer partials,
+one reduction launch), timers, the loss readers and the capture / replay of a step as a HIP graph."""
 from __future__ import annotations
 
 import torch
@@ -8,10 +9,15 @@ import torch
 from . import _lib as L
 from . import dist as dp_mod
 from .images import flat_written
+from .linear import linear_wgrad, wgrad_reduce
+from .ops import adam_step
 
 
 class _FlatAdamTrainer:
     timer_every = 1  # with timers enabled: bracket the launches of every timer_every-th step only
+    step_timers = False  # the step brackets its GEMM-chain launches and Adam (NMTrainer, MIWTrainer, FlowTrainer); with timers
+    # enabled its weight gradients then keep the per-layer form, so that every entry brackets a complete gradient
+    prec = 0  # GEMM precision of the chains (ops.PRECISIONS)
 
     def __init__(self, model, lr, betas, eps, seed, process_group, world_size, rank, tail, collective=None):
         self.model = model
@@ -52,6 +58,41 @@ class _FlatAdamTrainer:
         e1.record()
         self.timers.setdefault(name, []).append((e0, e1))
         return r
+
+    def _wgrad_workspace(self, shapes, grads, sized=True):
+        """The per-layer partial buffers of the weight gradients `grads` [(dw, db)] of GEMMs `shapes` [(M, N, K)]: one
+        buffer, sliced; summed by ONE launch at the end of the backward pass (_wgrad_reduce).  sized = False: empty slices
+        (a path that leaves the GEMM chain out)."""
+        sizes = [int(L.lib().vpc_linear_wgrad_scratch(*sh)) if sized else 0 for sh in shapes]
+        buf = torch.empty(sum(sizes), device=self.dev)
+        self._wg, o = [], 0
+        for n, sh, (dw, db) in zip(sizes, shapes, grads):
+            self._wg.append((buf[o:o + n], *sh, dw, db, False))
+            o += n
+        self._wg_cache = {}  # (buffers and gradient views are fixed for a batch size: the reduce's argument arrays are built once)
+
+    def _wgrad(self, key, dy, x, y_gate=None, gate=0, gate_split=0):
+        """Weight gradient key = (timer name, index in the workspace): partials now, summed by _wgrad_reduce; with timers on
+        (step_timers) the complete gradient in this launch."""
+        sc, M, N, K, dw, db, _ = self._wg[key[1]]
+        if self.timers is not None and self.step_timers:
+            return self._timed(key[0], linear_wgrad, dy, x, dw, db, M, N, K, y_gate, gate, gate_split, precision=self.prec)
+        linear_wgrad(dy, x, None, None, M, N, K, y_gate, gate, gate_split, precision=self.prec, scratch=sc)
+
+    def _wgrad_reduce(self):
+        if self.timers is None or not self.step_timers:
+            wgrad_reduce(self._wg, self._wg_cache)
+
+    def _adam(self, state=None, loss_in=None, accum=None):
+        """The step's tail: flat Adam on model._flat, then images.py's rule for a launch that wrote the parameters."""
+        self.step_count += 1
+        args = (self.model._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
+                self.betas[1], self.adam_eps, None, None, state, loss_in, accum)
+        if self.step_timers:
+            self._timed("adam", adam_step, *args)
+        else:
+            adam_step(*args)
+        self._flat_written(None)
 
     def _flat_written(self, key, *repacked):
         """After a launch that wrote the flat parameters (Adam): images.py's rule.  `key`: this step's parameter key."""

@@ -16,9 +16,9 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .notmiwae import (ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, linear_dgrad, linear_fwd, linear_wgrad, nm_mul,
-                       nm_sample, nm_sample_bwd)
-from .ops import _f32c, as_mask_u8
+from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, _f32c, linear_dgrad, linear_fwd, linear_wgrad
+from .notmiwae import nm_mul, nm_sample, nm_sample_bwd
+from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer
 
 H1, H2 = 100, 50
@@ -166,7 +166,4 @@ class WideTrainer(_FlatAdamTrainer):
         self.loss.copy_(tl.detach().reshape(1))
         if self.world_size > 1:
             self._allreduce()
-        self.step_count += 1
-        ops.adam_step(m._flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.adam_eps, loss_in=self.loss, accum=self.accum)
-        self._flat_written(None)
+        self._adam(None, self.loss, self.accum)
