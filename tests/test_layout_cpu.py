@@ -82,6 +82,26 @@ def test_bad_arguments_are_rejected_without_gpu():
     assert l.vpc_linear_fwd(None, 4, None, None, None, 4, 8, 4, 4, 0, 0, 0, None) == 1
     assert l.vpc_linear_dgrad(None, 4, None, 4, 0, 0, None, None, 4, 0, None, 4, 8, 4, 4, 0, None) == 1
     assert l.vpc_linear_wgrad(None, 4, None, 4, 0, 0, None, 4, None, None, None, 0, 8, 4, 4, 0, 0, None) == 1
+    # ... and so are, with every pointer given, a row pitch below the row's width, a precision code past bf16 (2) and a
+    # layer count outside 1 .. 8 of the deferred reduction (M = 8, N = 4, K = 5)
+    host = (ctypes.c_float * 64)()
+    p = ctypes.c_void_p(ctypes.addressof(host))
+    assert l.vpc_linear_fwd(p, 4, p, p, p, 4, 8, 4, 5, 0, 0, 0, None) == 1                                    # ldx < K
+    assert l.vpc_linear_fwd(p, 5, p, p, p, 3, 8, 4, 5, 0, 0, 0, None) == 1                                    # ldy < N
+    assert l.vpc_linear_fwd(p, 5, p, p, p, 4, 8, 4, 5, 0, 0, 3, None) == 1                                    # precision
+    assert l.vpc_linear_dgrad(p, 3, None, 4, 0, 0, p, None, 5, 0, p, 5, 8, 4, 5, 0, None) == 1                # lddy < N
+    assert l.vpc_linear_dgrad(p, 4, None, 4, 0, 0, p, None, 5, 0, p, 4, 8, 4, 5, 0, None) == 1                # lddx < K
+    assert l.vpc_linear_dgrad(p, 4, p, 3, 1, 0, p, None, 5, 0, p, 5, 8, 4, 5, 0, None) == 1                   # ldyg < N
+    assert l.vpc_linear_dgrad(p, 4, None, 4, 0, 0, p, p, 4, 1, p, 5, 8, 4, 5, 0, None) == 1                   # ldx < K
+    assert l.vpc_linear_dgrad(p, 4, None, 4, 0, 0, p, None, 5, 0, p, 5, 8, 4, 5, 3, None) == 1                # precision
+    assert l.vpc_linear_wgrad(p, 3, None, 4, 0, 0, p, 5, p, p, p, 1 << 20, 8, 4, 5, 0, 0, None) == 1          # lddy < N
+    assert l.vpc_linear_wgrad(p, 4, None, 4, 0, 0, p, 4, p, p, p, 1 << 20, 8, 4, 5, 0, 0, None) == 1          # ldx < K
+    assert l.vpc_linear_wgrad(p, 4, p, 3, 1, 0, p, 5, p, p, p, 1 << 20, 8, 4, 5, 0, 0, None) == 1             # ldyg < N
+    assert l.vpc_linear_wgrad(p, 4, None, 4, 0, 0, p, 5, p, p, p, 1 << 20, 8, 4, 5, 0, 3, None) == 1          # precision
+    ptrs = (ctypes.c_void_p * 9)(*[p.value] * 9)
+    Ms, Ns, Ks, acc = (ctypes.c_long * 9)(*[8] * 9), (ctypes.c_int * 9)(*[4] * 9), (ctypes.c_int * 9)(*[5] * 9), (ctypes.c_int * 9)()
+    assert l.vpc_linear_wgrad_reduce(0, ptrs, Ms, Ns, Ks, ptrs, ptrs, acc, None) == 1
+    assert l.vpc_linear_wgrad_reduce(9, ptrs, Ms, Ns, Ks, ptrs, ptrs, acc, None) == 1
     assert l.vpc_nm_sample(None, 20, None, None, 10, 4, 2, 10, None) == 1
     assert l.vpc_linear_wgrad_scratch(0, 4, 4) == 0 and l.vpc_nm_loss_scratch(0, 4) == 0
 

@@ -26,9 +26,11 @@ def linear_fwd(x, w, b, y, M, N, K, act=ACT_NONE, split=0, ldx=None, ldy=None, p
 
 
 def linear_dgrad(dy, w, dx, M, N, K, y_gate=None, gate=ACT_NONE, gate_split=0, x_out=None, act_prev=ACT_NONE,
-                 lddy=None, lddx=None, precision=0):
-    check(lib().vpc_linear_dgrad(ptr(dy), lddy or N, ptr(y_gate), lddy or N, gate, gate_split, ptr(w), ptr(x_out), K,
-                                 act_prev, ptr(dx), lddx or K, M, N, K, int(precision), stream_ptr()), "vpc_linear_dgrad")
+                 lddy=None, lddx=None, ldyg=None, ldxo=None, precision=0):
+    """Row pitches default to the dense width; ldyg (y_gate) defaults to dy's pitch, ldxo is x_out's."""
+    check(lib().vpc_linear_dgrad(ptr(dy), lddy or N, ptr(y_gate), ldyg or lddy or N, gate, gate_split, ptr(w), ptr(x_out),
+                                 ldxo or K, act_prev, ptr(dx), lddx or K, M, N, K, int(precision), stream_ptr()),
+          "vpc_linear_dgrad")
 
 
 _scratch = {}
@@ -44,11 +46,11 @@ def _wgrad_scratch(device, floats):
 
 
 def linear_wgrad(dy, x, dw, db, M, N, K, y_gate=None, gate=ACT_NONE, gate_split=0, accumulate=False, lddy=None,
-                 ldx=None, precision=0, scratch=None):
+                 ldx=None, ldyg=None, precision=0, scratch=None):
     """dw = None: write only the per-split partials into `scratch` (the caller's own buffer for this layer); they are summed
-    later, together with other layers', by wgrad_reduce (one launch)."""
+    later, together with other layers', by wgrad_reduce (one launch).  ldyg (y_gate's row pitch) defaults to dy's."""
     sc = _wgrad_scratch(dy.device, int(lib().vpc_linear_wgrad_scratch(M, N, K))) if scratch is None else scratch
-    check(lib().vpc_linear_wgrad(ptr(dy), lddy or N, ptr(y_gate), lddy or N, gate, gate_split, ptr(x), ldx or K,
+    check(lib().vpc_linear_wgrad(ptr(dy), lddy or N, ptr(y_gate), ldyg or lddy or N, gate, gate_split, ptr(x), ldx or K,
                                  ptr(dw), ptr(db), ptr(sc), sc.numel(), M, N, K, int(accumulate), int(precision),
                                  stream_ptr()), "vpc_linear_wgrad")
 
