@@ -584,6 +584,36 @@ int vpc_flow_reward_matrix(const float* x, const float* mask, const float* im, c
  * VAE.py:1824-1827, one per encoder call of evaluate.py:680-682, 704-706). */
 int vpc_flow_reward_draws(float* eps, int n, int d, int M, unsigned long long seed, void* stream);
 
+/* ---- annealed importance sampling with adaptive-step HMC (csrc/vpc_ais.hip) ----------------------------------------
+ * Replaces the chain arithmetic of src/utils/AIS.py: the temperature loop of ais_trajectory (:178-217) with log_f_i
+ * (:125-140), U / grad_U / normalized_kinetic (:187-204), hmc_trajectory (:237-262) and accept_reject (:265-304), for
+ * the decoders that are the latent -> 50 -> 100 -> d sigmoid chain with a constant x_logvar.  B = nb * n_sample chains
+ * in safe_repeat order (:28-29, 160): chain c belongs to row c % nb of x [nb][d].  The annealed density is
+ *     log f(z, t) = -|z|^2 / 2 + t * sign * NLL(x; decoder(z)),   NLL = sum over all d columns of -log N(x; mean, var)
+ * sign = +1: the reference as written (:125 passes neg_gaussian_log_likelihood as the log likelihood); sign = -1: the
+ * corrected target p(z) p(x|z)^t.  The step-size adaptation constants (0.65, 1.02, 0.98, [1e-4, 0.5]) are :295-297's. */
+
+/* 1 when vpc_ais_run covers the shape (d <= 128, L <= 15, 1 <= B < 2^30), else 0. */
+int vpc_ais_applicable(long B, int d, int L);
+/* Floats of the chain state of B chains: z [B][16] (columns >= L are 0) | epsilon [B] | accept_hist [B] | logw [B] |
+ * nll_current [B] (NLL at the current z).  16-byte aligned. */
+long vpc_ais_state_floats(long B);
+/* The schedule pairs (schedule[j-1], schedule[j]) for j = j0 .. j0 + nsteps - 1 (1-based as :178's enumerate;
+ * schedule = T device floats) in ONE persistent launch: a wave owns a 16-chain tile, the decoder image sits in LDS, the
+ * chain state stays in registers.  init != 0: the state is initialised first (:163-174: epsilon = init_step_size,
+ * accept_hist = logw = 0, z = z0), otherwise read from `state`; it is written back at the end, so a schedule may be
+ * split over any number of calls with bit-equal results.  Draws: z0 [B][L], v [T-1][B][L] (:185), u [T-1][B] (:289) are
+ * read where given; a NULL array is generated from Philox4x32-10 (seed; counter = chain, j, kind - independent of the
+ * split and of the launch geometry; vpc_ais_draws writes the same values).  Backward mode (:173) passes the repeated
+ * post_z as z0.  dec_img = the decoder image of vpc_pack_weights.  Returns 2 for d > 128 or L > 15. */
+int vpc_ais_run(const float* x, const float* dec_img, const float* schedule, int T, int j0, int nsteps, int init,
+                float* state, const float* z0, const float* v, const float* u, unsigned long long seed, float sign,
+                int leapfrog_steps, float init_step_size, float grad_clip, float x_logvar, long B, long nb, int d, int L,
+                void* stream);
+/* The draws vpc_ais_run(seed) generates, as dense arrays (each may be NULL): z0 [B][L] ~ N(0, 1) (:171),
+ * v [T-1][B][L] ~ N(0, 1) (:185), u [T-1][B] ~ U(0, 1) (:289). */
+int vpc_ais_draws(float* z0, float* v, float* u, long B, int L, int T, unsigned long long seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

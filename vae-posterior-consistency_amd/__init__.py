@@ -28,6 +28,8 @@ from .wide import WideTrainer
 from .active import (reward_matrix, R_lindley_chain, chaini_I, chaini_II, active_learning_func, active_result_paths,
                      mc_forward, flow_reward_matrix, flow_reward_draws, R_lindley_chain_ratio_version,
                      chaini_I_ratio_version, chaini_II_ratio_version, active_learning_flow)
+from . import ais
+from .ais import ais_chains, ais_trajectory, eval_ais
 
 __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedTrainer", "REG_notMIWAE_v2",
            "notMIWAE_myversion", "NMTrainer", "notmiwae", "eddi", "Reg_EDDI", "vanilla_EDDI", "EDDITrainer", "eval_vae_mnar", "mnar_result_path", "create_missing_uci", "create_missing_uci_drop_eddi", "model_loader", "checkpoint_path", "train", "eval_vae", "result_paths",
@@ -35,4 +37,4 @@ __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedT
            "chaini_II", "miwae", "MIWAE", "Reg_MIWAE", "MIWTrainer", "eval_miwae", "miwae_result_path", "flow", "VAEFlow", "REG_VAEFlow", "FlowTrainer",
            "eddi_mnist", "Reg_EDDI_mnist", "vanilla_EDDI_mnist", "EDDIMnistTrainer",
            "flow_reward_matrix", "flow_reward_draws", "R_lindley_chain_ratio_version", "chaini_I_ratio_version",
-           "chaini_II_ratio_version", "active_learning_flow"]
+           "chaini_II_ratio_version", "active_learning_flow", "ais", "ais_chains", "ais_trajectory", "eval_ais"]

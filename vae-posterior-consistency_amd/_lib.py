@@ -119,6 +119,11 @@ _PROTOS = {
     "vpc_flow_reward_scratch": [I, I, I, I, I, C.POINTER(L_)],
     "vpc_flow_reward_matrix": [P, P, P, P, P, P, P, P, P, P, ULL, P, L_, P, I, I, I, I, I, P],
     "vpc_flow_reward_draws": [P, I, I, I, ULL, P],
+    # annealed importance sampling (csrc/vpc_ais.hip)
+    "vpc_ais_applicable": [L_, I, I],
+    "vpc_ais_state_floats": [L_],
+    "vpc_ais_run": [P, P, P, I, I, I, I, P, P, P, P, ULL, F, I, F, F, F, L_, L_, I, I, P],
+    "vpc_ais_draws": [P, P, P, L_, I, I, ULL, P],
     # PNP / EDDI encoder front-end
     "vpc_eddi_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
@@ -130,7 +135,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats"}
 
 _lib = None
 
