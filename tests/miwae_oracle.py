@@ -20,21 +20,45 @@ def params64(src, prefix="param.", requires_grad=False):
     return {k: torch.as_tensor(src[prefix + k]).double().clone().requires_grad_(requires_grad) for k in KEYS}
 
 
-def _mlp(p, pre, h):
-    h = F.relu(F.linear(h, p[f"{pre}.0.weight"], p[f"{pre}.0.bias"]))
-    h = F.relu(F.linear(h, p[f"{pre}.2.weight"], p[f"{pre}.2.bias"]))
+KINK_BAND = 1e-5  # of a layer's max |pre-activation|: inside it fp32 and float64 may gate a ReLU unit differently
+
+
+def new_gate_stats():
+    return dict(units=0, in_band=0, taken_from_device=0, mismatch_outside=0)
+
+
+def _mlp(p, pre, h, gate=None):
+    """gate = (device gates {layer index: bool tensor}, or None; stats dict): the two hidden layers count their units
+    inside the kink band into stats and, given the device's gates, take those inside the band and their own pre > 0
+    everywhere else (a device gate that differs outside the band is counted as a mismatch, never taken)."""
+    for i in (0, 2):
+        a = F.linear(h, p[f"{pre}.{i}.weight"], p[f"{pre}.{i}.bias"])
+        if gate is None:
+            h = F.relu(a)
+            continue
+        dev, stats = gate
+        g = a.detach() > 0
+        inb = a.detach().abs() <= KINK_BAND * a.detach().abs().max()
+        stats["units"] += a.numel()
+        stats["in_band"] += int(inb.sum())
+        if dev is not None:
+            dg = dev[i].reshape(a.shape)
+            stats["taken_from_device"] += int((inb & (dg != g)).sum())
+            stats["mismatch_outside"] += int((~inb & (dg != g)).sum())
+            g = torch.where(inb, dg, g)
+        h = a * g
     return F.linear(h, p[f"{pre}.4.weight"], p[f"{pre}.4.bias"])
 
 
-def encode(p, x, mask, eps):
+def encode(p, x, mask, eps, gate=None):
     """-> mean, scale [B, L], z [B, S, L] (eps [B, S, L])."""
-    mean, raw = _mlp(p, "seq_encoder", x.double() * mask.double()).chunk(2, dim=1)
+    mean, raw = _mlp(p, "seq_encoder", x.double() * mask.double(), gate).chunk(2, dim=1)
     scale = F.softplus(raw)
     return mean, scale, mean[:, None, :] + scale[:, None, :] * eps.double()
 
 
-def decode(p, z):
-    mu, sc, v = _mlp(p, "seq_decoder", z).chunk(3, dim=-1)
+def decode(p, z, gate=None):
+    mu, sc, v = _mlp(p, "seq_decoder", z, gate).chunk(3, dim=-1)
     return torch.sigmoid(mu), F.softplus(sc) + 0.001, F.softplus(v) + 3
 
 
@@ -82,16 +106,19 @@ def impute(a_q, x_mean):
     return torch.einsum("ki,kij->ij", w, x_mean.permute(1, 0, 2))
 
 
-def run(p, x, mask, mask_p, eps, alpha=1.0, pairing="reference"):
-    """Whole forward + loss from parameters.  eps = [forward q, (forward p,) loss q, (loss p)] [B, S, L] each."""
+def run(p, x, mask, mask_p, eps, alpha=1.0, pairing="reference", gates=None, stats=None):
+    """Whole forward + loss from parameters.  eps = [forward q, (forward p,) loss q, (loss p)] [B, S, L] each.
+    stats (new_gate_stats()): count the hidden units inside the kink band; gates {"enc_q" | "dec_q" | "enc_p" | "dec_p":
+    {0: bool [rows, H], 2: ..}}: the gates a device step took, used inside the band only (_mlp)."""
     reg = mask_p is not None
     P = 2 if reg else 1
-    mq, sq, zq = encode(p, x, mask, eps[0])
-    q = (decode(p, zq), mq, sq)
+    gt = lambda k: None if stats is None else (None if gates is None else gates[k], stats)
+    mq, sq, zq = encode(p, x, mask, eps[0], gt("enc_q"))
+    q = (decode(p, zq, gt("dec_q")), mq, sq)
     pp = None
     if reg:
-        mp, sp, zp = encode(p, x, mask_p, eps[1])
-        pp = (decode(p, zp), mp, sp)
+        mp, sp, zp = encode(p, x, mask_p, eps[1], gt("enc_p"))
+        pp = (decode(p, zp, gt("dec_p")), mp, sp)
     lo, a_q = loss(x, mask, mask_p, q, pp, eps[P:], alpha, pairing)
     return lo, a_q, q, pp
 
@@ -138,3 +165,68 @@ def closed_form_grads(x, mask, mask_p, q, p, eps2, alpha=1.0, pairing="reference
                 gs = gs + c * (1 / sp - (sq ** 2 + (mq - mp_) ** 2) / sp ** 3)
         out.append((gmu, gsc, gv, gm, gs))
     return out
+
+
+def terms(x, mask, mask_p, q, p, eps2, alpha=1.0, pairing="reference"):
+    """The eight doubles vpc_miw_loss writes: [loss, nb_q, nb_p, kl, reg_like, sum(lp_q * (1 - mask)) / (B * 5000)
+    (VAE.py:3099, a literal 5000), sum_j logsumexp_i a_q, sum_j logsumexp_i a_p]; the p / regulariser entries are 0 for
+    MIWAE."""
+    B = x.shape[0]
+    z = torch.zeros((), dtype=torch.float64)
+    a_q = slot_matrix(x, mask, q[0], q[1], q[2], eps2[0], pairing)
+    lse_q = torch.logsumexp(a_q, 0).sum()
+    lp_q = student_lp(x.double()[:, None, :], *q[0])
+    third = (lp_q * (1 - mask.double())[:, None, :]).sum() / (B * 5000)
+    if p is None:
+        return torch.stack([-lse_q / B, -lse_q / B, z, z, z, third, lse_q, z])
+    lse_p = torch.logsumexp(slot_matrix(x, mask_p, p[0], p[1], p[2], eps2[1], pairing), 0).sum()
+    reg_like = (lp_q * mask.double()[:, None, :] * (1 - mask_p.double())[:, None, :]).sum(-1).mean()
+    vr = (q[2] / p[2]) ** 2
+    kl = (0.5 * (vr + ((q[1] - p[1]) / p[2]) ** 2 - 1 - torch.log(vr))).mean()
+    nb_q, nb_p = -lse_q / B, -lse_p / B
+    return torch.stack([nb_q + alpha * (kl - nb_q + nb_p - reg_like), nb_q, nb_p, kl, reg_like, third, lse_q, lse_p])
+
+
+# ---- the elementwise kernels (miw_sample, miw_sample_bwd, miw_heads, miw_heads_bwd), in the dtype of their inputs: the
+# GPU tests evaluate them in float64 (the reference) and in float32 (the error a correct fp32 evaluation has)
+def softplus_d(v):
+    """torch's Softplus backward (threshold 20): identity above the threshold, exp(v) / (exp(v) + 1) below."""
+    z = torch.exp(torch.clamp(v, max=20.0))
+    return torch.where(v > 20, torch.ones_like(v), z / (z + 1))
+
+
+def sample(heads, eps, S):
+    """heads [R, mean L | raw scale L], eps [R, S, L] or None (z = mean) -> z [R, S, L], hact [R, mean L | scale L]."""
+    L = heads.shape[1] // 2
+    mean, sc = heads[:, :L], F.softplus(heads[:, L:])
+    z = mean[:, None, :].expand(-1, S, -1)
+    if eps is not None:
+        z = z + eps * sc[:, None, :]
+    return z, torch.cat([mean, sc], 1)
+
+
+def sample_bwd(dz, eps, heads, g_hact, S):
+    """d / d heads of sample(): dz [R, S, L] and g_hact [R, 2L] are the gradients of its two outputs, either may be None."""
+    L = heads.shape[1] // 2
+    gm, gs = torch.zeros_like(heads[:, :L]), torch.zeros_like(heads[:, L:])
+    if g_hact is not None:
+        gm, gs = gm + g_hact[:, :L], gs + g_hact[:, L:]
+    if dz is not None:
+        gm = gm + dz.sum(1)
+        if eps is not None:
+            gs = gs + (dz * eps).sum(1)
+    return torch.cat([gm, gs * softplus_d(heads[:, L:])], 1)
+
+
+def heads_act(y):
+    """raw decoder heads [M, 3d] -> [sigmoid | softplus + 0.001 | softplus + 3] (VAE.py:3072-3076)."""
+    mu, sc, v = y.chunk(3, dim=1)
+    return torch.cat([torch.sigmoid(mu), F.softplus(sc) + 0.001, F.softplus(v) + 3], 1)
+
+
+def heads_bwd(y, g):
+    """d / d raw heads of heads_act().  The sigmoid's derivative is z / (1 + z)^2 with z = exp(-|mu|), the kernel's form:
+    s (1 - s) loses the digits of 1 - s once s is within rounding of 1."""
+    mu, sc, v = y.chunk(3, dim=1)
+    z = torch.exp(-mu.abs())
+    return g * torch.cat([z / ((1 + z) * (1 + z)), softplus_d(sc), softplus_d(v)], 1)

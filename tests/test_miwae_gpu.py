@@ -13,6 +13,7 @@ import torch
 
 import miwae_oracle as O
 from conftest import load_golden
+from miwae_cases import api_loss as _api_loss, rand_inputs as _rand_inputs, raw_to_act as _raw_to_act
 
 pytestmark = pytest.mark.gpu
 TP = {"batch_size": 64, "patience": 1}
@@ -40,23 +41,6 @@ def _load_model(mw, g, cls, prefix="param."):
     model = cls(g["x"].shape[1], 500, 10, int(g["L"]), TP, int(g["S"]), 1)
     model.load_state_dict({k[len(prefix):]: torch.from_numpy(v.copy()) for k, v in g.items() if k.startswith(prefix)})
     return model.cuda()
-
-
-def _api_loss(model, x, m, mp, eps, alpha):
-    """forward (with injected forward draws) + loss (with injected loss draws), as train.py:102-113."""
-    if mp is not None:
-        z_q, mean_q, scale_q = model._encode(x, m, eps=eps[0])
-        xm_q, xs_q, df_q = model.decoder(z_q)
-        z_p, mean_p, scale_p = model._encode(x, mp, eps=eps[1])
-        xm_p, xs_p, df_p = model.decoder(z_p)
-        outs = (mean_p, scale_p, xm_p, xs_p, df_p, mean_q, scale_q, xm_q, xs_q, df_q)
-        _, tl = model.loss(x, xm_p, xs_p, df_p, mean_p, scale_p, xm_q, xs_q, df_q, mean_q, scale_q, m, mp, 1,
-                           alpha=alpha, eps=[eps[2], eps[3]])
-        return tl, outs
-    z, mean, scale = model._encode(x, m, eps=eps[0])
-    xm, xs, df = model.decoder(z)
-    _, tl = model.loss(x, xm, xs, df, mean, scale, m, 1, eps=eps[1])
-    return tl, (mean, scale, xm, xs, df)
 
 
 @pytest.mark.parametrize("name", ["miwae_reg_d14", "miwae_reg_d40", "miwae_van_d14", "miwae_van_d40"])
@@ -91,23 +75,6 @@ def test_api_vs_reference(mw, name):
     assert abs(tl.item() - g["llh_loss"]) <= 1e-4 * abs(g["llh_loss"])
     assert abs(t3.item() - g["llh_third"]) <= 1e-4 * abs(g["llh_third"])
     _close(xm, torch.from_numpy(g["llh_xm"]), 2e-5, "llh_xm")
-
-
-def _rand_inputs(B, S, d, Ld, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.random((B, d)).astype(np.float32)
-    m = (rng.random((B, d)) < 0.7).astype(np.float32)
-    mp = m * (rng.random((B, d)) < 0.5).astype(np.float32)
-    mk = lambda: (rng.normal(size=(B * S, 3 * d)).astype(np.float32), rng.normal(size=(B, Ld)).astype(np.float32),
-                  (0.2 + rng.random((B, Ld))).astype(np.float32))
-    e = rng.normal(size=(2, B, S, Ld)).astype(np.float32)
-    return x, m, mp, mk(), mk(), e
-
-
-def _raw_to_act(Y, d):
-    t = torch.from_numpy(Y).double()
-    return (torch.sigmoid(t[:, :d]), torch.nn.functional.softplus(t[:, d:2 * d]) + 0.001,
-            torch.nn.functional.softplus(t[:, 2 * d:]) + 3)
 
 
 @pytest.mark.parametrize("pairing", ["reference", "per_row"])
@@ -160,7 +127,8 @@ def test_loss_kernel_vs_oracle(mw, pairing, raw):
         for k, (G, gh) in enumerate([(Gq, ghq), (Gp, ghp)][:2 if reg else 1]):
             ly, mean, scale = leaves[k]
             gref = ly.grad if raw else torch.cat([a.grad.reshape(B * S, d) for a in ly], 1)
-            _close(G, gref, 5e-5, ("dY", reg, k))
+            for i, head in enumerate(("mean", "scale", "df")):  # each head block on its own max: the df block is the smallest
+                _close(G[:, i * d:(i + 1) * d], gref[:, i * d:(i + 1) * d], 5e-5, ("dY", head, reg, k))
             _close(gh[:, :Ld], mean.grad, 5e-5, ("dmean", reg, k))
             _close(gh[:, Ld:], scale.grad, 5e-5, ("dscale", reg, k))
 

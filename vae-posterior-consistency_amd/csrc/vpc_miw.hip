@@ -28,6 +28,11 @@ __device__ __forceinline__ float miw_softplus_d(float v) {  // torch's Softplus 
     return z / (z + 1.f);
 }
 __device__ __forceinline__ float miw_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+// sigmoid'(v) = mu (1 - mu) without forming 1 - mu (which loses every digit of it once mu is within rounding of 1)
+__device__ __forceinline__ float miw_sigmoid_d(float v) {
+    const float z = expf(-fabsf(v));
+    return z / ((1.f + z) * (1.f + z));
+}
 
 __device__ __forceinline__ float miw_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -38,15 +43,22 @@ __device__ __forceinline__ float miw_wave_max(float v) {
     return v;
 }
 
-// digamma for x >= 1.5: recurrence up to x >= 6, then the asymptotic series
-__device__ __forceinline__ float miw_digamma(float x) {
-    float r = 0.f;
-    while (x < 6.f) {
-        r -= 1.f / x;
-        x += 1.f;
+// 0.5 * (digamma((v + 1) / 2) - digamma(v / 2)) for v >= 3, formed as ONE difference: two digammas near log(v / 2) would
+// cancel to about 1 / (2 v) and leave their rounding (1e-7 of log(v / 2)) behind, which the df gradient then loses a
+// further factor 2 v of against its - 0.5 / v term.  With x_b = v / 2, x_a = x_b + 1/2: the recurrence up to x_b >= 6
+// contributes 1 / x_b - 1 / x_a = 0.5 / (x_a x_b) per step, the logarithms of the asymptotic series log1p(0.5 / x_b),
+// its - 1 / (2 x) terms 0.25 / (x_a x_b); the remaining series terms are below 3e-3 each.
+__device__ __forceinline__ float miw_half_digamma_diff(float v) {
+    float xb = 0.5f * v, xa = xb + 0.5f, r = 0.f;
+    while (xb < 6.f) {
+        r += 0.5f / (xa * xb);
+        xa += 1.f;
+        xb += 1.f;
     }
-    const float i = 1.f / x, i2 = i * i;
-    return r + logf(x) - 0.5f * i - i2 * (1.f / 12.f - i2 * (1.f / 120.f - i2 * (1.f / 252.f)));
+    const float ia = 1.f / xa, ib = 1.f / xb, a2 = ia * ia, b2 = ib * ib;
+    const float sa = a2 * (1.f / 12.f - a2 * (1.f / 120.f - a2 * (1.f / 252.f)));
+    const float sb = b2 * (1.f / 12.f - b2 * (1.f / 120.f - b2 * (1.f / 252.f)));
+    return 0.5f * (r + log1pf(0.5f * ib) + 0.25f * ia * ib - (sa - sb));
 }
 
 // the three decoder heads of element k of one row: raw != 0 -> apply the transforms of VAE.py:3072-3076
@@ -243,10 +255,9 @@ __global__ void __launch_bounds__(256) miw_grad_kernel(MiwLossArgs a, int nblk_e
         const float tt = y * y / h.v, u = 1.f + tt;
         float gmu = g * (h.v + 1.f) * y / (h.v * h.sc * u);
         float gsc = g * (-1.f / h.sc + (h.v + 1.f) * tt / (h.sc * u));
-        float gv = g * (0.5f * miw_digamma(0.5f * (h.v + 1.f)) - 0.5f * miw_digamma(0.5f * h.v) - 0.5f / h.v -
-                        0.5f * log1pf(tt) + (h.v + 1.f) * tt / (2.f * h.v * u));
+        float gv = g * (miw_half_digamma_diff(h.v) - 0.5f / h.v - 0.5f * log1pf(tt) + (h.v + 1.f) * tt / (2.f * h.v * u));
         if (a.raw) {
-            gmu *= h.mu * (1.f - h.mu);
+            gmu *= miw_sigmoid_d(h.a0);
             gsc *= miw_softplus_d(h.a1);
             gv *= miw_softplus_d(h.a2);
         }
@@ -366,8 +377,7 @@ __global__ void miw_heads_kernel(const float* __restrict__ yr, const float* __re
         return;
     }
     const float* g = gact + m * 3 * d;
-    const float mu = miw_sigmoid(y[k]);
-    o[k] = g[k] * mu * (1.f - mu);
+    o[k] = g[k] * miw_sigmoid_d(y[k]);
     o[d + k] = g[d + k] * miw_softplus_d(y[d + k]);
     o[2 * d + k] = g[2 * d + k] * miw_softplus_d(y[2 * d + k]);
 }
