@@ -4,6 +4,10 @@ gradients (`step`), and the same mathematics in torch float64 for autograd (`tor
 
 The flow is restated per pass of B rows: m = [|eps| <= 1]; every layer reads the context c[b, i, j] = t[b, 10 i + j] *
 m[b, j] (the reference's in-place multiply); layer 1's input is eps * m; a pass with no inside draw is the identity.
+
+For the kernel-by-kernel parity tests (tests/test_flow_kernels_gpu.py) flow_fwd / flow_bwd return and take the per-element
+discrete decisions (the bin of layers 2 / 3, each layer's clamp gate), flow_flags / alternative name and switch the ones
+that are a tie in fp32, _torch_flow runs in fp32 on given decisions, and loss_terms restates vpc_flow_loss entry by entry.
 """
 import numpy as np
 import torch
@@ -62,8 +66,16 @@ def bin_of(x):
     return np.minimum(np.floor(bp).astype(np.int64), L - 1)
 
 
-def flow_fwd(t, eps):
-    """t [B, 100], eps [B, 10] of ONE pass -> z, z_log_prob, cache."""
+FLAG_BIN = 1e-5    # a layer-2 / 3 bin position this close to an integer (about ten fp32 ulp at 10) is a tie in fp32
+FLAG_GATE = 1e-6   # a layer's o this close to 0 or 1 (ten accumulated ulp at 1) likewise
+
+
+def flow_fwd(t, eps, decisions=None):
+    """t [B, 100], eps [B, 10] of ONE pass -> z, z_log_prob, cache.
+
+    decisions = dict(bins int [3, B, 10], gates bool [3, B, 10]): the per-element discrete decisions, taken as given
+    (bins[1:], gates) or, with None, taken here; cache[4] returns them.  bins[0] is never free: layer 1's bin is
+    bin_of(eps * m), exact fp32 arithmetic on the given draw.  The gate 0 <= o <= 1 only enters the backward."""
     B = eps.shape[0]
     lp = -eps ** 2 / 2 - HL
     if not np.any(np.abs(eps) <= 1):
@@ -75,31 +87,35 @@ def flow_fwd(t, eps):
     cdf = np.cumsum(pdf, -1) - pdf
     x = eps * m
     steps, ld = [], 0
+    bins, gates = np.zeros((3, B, L), np.int64), np.zeros((3, B, L), bool)
     bi, li = np.arange(B)[:, None], np.arange(L)[None, :]
-    for _ in range(3):
+    for l in range(3):
         bp = (x + 1) / 2 * L
-        b = bin_of(x)
+        b = bin_of(x) if decisions is None or l == 0 else np.asarray(decisions["bins"][l])
         al = bp - b
         pb, cb = pdf[bi, li, b], cdf[bi, li, b]
         o = cb + al * pb
         steps.append((b, al, pb, o))
+        bins[l] = b
+        gates[l] = (o >= 0) & (o <= 1) if decisions is None else decisions["gates"][l]
         x = np.clip(o, 0, 1) * 2 - 1
         ld = ld + np.log(pb) + np.log(L)
-    return x, lp - ld, (m, pdf, cdf, steps)
+    return x, lp - ld, (m, pdf, cdf, steps, dict(bins=bins, gates=gates))
 
 
 def flow_bwd(cache, dz, dzlp):
-    """d / d t [B, 100] given d / d z and d / d z_log_prob (cache of flow_fwd)."""
+    """d / d t [B, 100] given d / d z and d / d z_log_prob (cache of flow_fwd, its decisions included)."""
     B = dz.shape[0]
     if cache is None:
         return np.zeros((B, L * L))
-    m, pdf, cdf, steps = cache
+    m, pdf, cdf, steps, dec = cache
     bi, li = np.arange(B)[:, None], np.arange(L)[None, :]
     du = np.zeros((B, L, L))
     gout = dz.copy()
     glad = -dzlp
-    for b, al, pb, o in steps[::-1]:
-        go = np.where((o >= 0) & (o <= 1), 2 * gout, 0.0)
+    for l in (2, 1, 0):
+        b, al, pb, o = steps[l]
+        go = np.where(dec["gates"][l], 2 * gout, 0.0)
         cb = cdf[bi, li, b]
         onehot = (np.arange(L)[None, None, :] == b[..., None]).astype(np.float64)
         below = (np.arange(L)[None, None, :] < b[..., None]).astype(np.float64)
@@ -107,6 +123,44 @@ def flow_bwd(cache, dz, dzlp):
         du += glad[..., None] * (onehot - pdf)
         gout = go * L * 0.5 * pb
     return (du * m[:, None, :]).reshape(B, L * L)
+
+
+def flow_flags(cache):
+    """Which decisions of a flow_fwd cache fp32 may take the other way: dict(bins bool [3, B, 10] (layer 1 never),
+    gates bool [3, B, 10]), from the float64 bin positions (FLAG_BIN) and o (FLAG_GATE)."""
+    steps = cache[3]
+    fb, fg = np.zeros((3,) + steps[0][0].shape, bool), np.zeros((3,) + steps[0][0].shape, bool)
+    for l, (b, al, pb, o) in enumerate(steps):
+        bp = b + al
+        if l:
+            fb[l] = np.abs(bp - np.rint(bp)) < FLAG_BIN
+        fg[l] = np.minimum(np.abs(o), np.abs(o - 1)) < FLAG_GATE
+    return dict(bins=fb, gates=fg)
+
+
+def flagged(flags):
+    """[B, 10]: the elements with any flagged decision."""
+    return flags["bins"].any(0) | flags["gates"].any(0)
+
+
+N_ALTERNATIVES = 32  # two bins and three gates
+
+
+def alternative(cache, flags, c):
+    """The decisions of `cache` with the flagged ones among (bin 2, bin 3, gate 1, gate 2, gate 3) switched where bit
+    0 .. 4 of c is set: a flagged bin to the other bin at the knot (the same one at the ends 0 and 10), a flagged gate to
+    its negation.  c = 0 is the cache's own decisions."""
+    steps, dec = cache[3], cache[4]
+    bins, gates = dec["bins"].copy(), dec["gates"].copy()
+    for s, l in enumerate((1, 2)):
+        if c >> s & 1:
+            k = np.rint(steps[l][0] + steps[l][1]).astype(np.int64)  # the knot: the candidates are bins k - 1 and k
+            other = np.clip(2 * k - 1 - bins[l], 0, L - 1)
+            bins[l] = np.where(flags["bins"][l], other, bins[l])
+    for s, l in enumerate((0, 1, 2)):
+        if c >> (2 + s) & 1:
+            gates[l] = np.where(flags["gates"][l], ~gates[l], gates[l])
+    return dict(bins=bins, gates=gates)
 
 
 def nll(x, xr, w):
@@ -173,7 +227,9 @@ def step(P, x, mask, mask_p, eps, alpha=1.0, beta=1.0, stage="train"):
 
 
 # ------------------------------------------------------------------------------------------------ torch autograd
-def _torch_flow(t, eps):
+def _torch_flow(t, eps, decisions=None):
+    """In the dtype of t.  decisions (flow_fwd's): the bins of layers 2 / 3 and every clamp gate are taken from them,
+    so that an fp32 run differs from the float64 one by rounding only (the gate decides where autograd passes)."""
     B = eps.shape[0]
     lp = -eps ** 2 / 2 - HL
     if not bool(torch.any(eps.abs() <= 1)):
@@ -183,15 +239,63 @@ def _torch_flow(t, eps):
     cdf = torch.nn.functional.pad(torch.cumsum(pdf, -1)[..., :-1], (1, 0))
     x = eps * m
     ld = 0
-    for _ in range(3):
+    for l in range(3):
         bp = (x + 1) / 2 * L
-        b = torch.from_numpy(bin_of(x.detach().numpy()))
+        if decisions is None or l == 0:
+            b = torch.from_numpy(bin_of(x.detach().numpy()))
+        else:
+            b = torch.from_numpy(np.asarray(decisions["bins"][l]))
         al = bp - b.to(t.dtype)
         pb = pdf.gather(-1, b[..., None])[..., 0]
         o = cdf.gather(-1, b[..., None])[..., 0] + al * pb
-        x = torch.clamp(o, 0, 1) * 2 - 1
+        oc = torch.clamp(o, 0, 1)
+        if decisions is not None:  # the clamped value, the gradient of o where the gate is open
+            g = torch.from_numpy(np.asarray(decisions["gates"][l]))
+            oc = torch.where(g, o + (oc - o).detach(), oc.detach())
+        x = oc * 2 - 1
         ld = ld + torch.log(pb) + np.log(L)
     return x, lp - ld
+
+
+def loss_terms(x, m, mp, xm, z, zlp, alpha, beta, stage="train", gated=0, gscale=1.0):
+    """vpc_flow_loss restated in torch, in the dtype of x (float64: the oracle; fp32: the rounding yardstick).
+    xm, z, zlp: (q, p) pairs; mp None: VAEFlow (the p entries are not read).  Returns dict(out8 [8] = loss (unscaled),
+    RE_q, RE_p, KL_q, KL_p, KL_reg, NLL of x * mask * ~mask_p, RE_q on ~mask; abs8 [8] = the sum of the absolute values
+    of each entry's terms; grads = (gxm_q, gxm_p, gz_q, gz_p, gzlp_q, gzlp_p) of gscale * loss in closed form, the xm
+    pair times xm (1 - xm) when gated (the gradient of a Sigmoid's pre-activation), sign(0) = 0 at a z_log_prob tie)."""
+    reg = mp is not None
+    pp = reg and stage == "train"
+    sc = torch.exp(torch.tensor(LOGVAR / 2, dtype=x.dtype))
+    var, logs = sc * sc, torch.log(sc)
+
+    def nll_(xr, w):
+        return torch.where(w == 0, torch.full_like(x, HL), (x - xr) ** 2 / (2 * var) + logs + HL)
+
+    kl_ = lambda k: zlp[k] - (-(z[k] * z[k]) / 2 - HL)
+    zero = torch.zeros_like(x)
+    wr = m * (1 - mp) if reg else zero
+    terms = [nll_(xm[0], m), nll_(xm[1], mp) if pp else zero, kl_(0), kl_(1) if pp else torch.zeros_like(z[0]),
+             (zlp[0] - zlp[1]).abs() if pp else torch.zeros_like(z[0]), nll_(xm[0], wr) if reg else zero,
+             nll_(xm[0], 1 - m)]
+    s = [u.double().sum() for u in terms]
+    a = [u.double().abs().sum() for u in terms]
+    loss_q, abs_q = s[0] + beta * s[2], a[0] + beta * a[2]
+    loss, abs_l = loss_q, abs_q
+    if pp:
+        loss = loss_q + alpha * (s[4] - loss_q + (s[1] + beta * s[3]) + s[5])
+        abs_l = abs_q + alpha * (a[4] + abs_q + a[1] + beta * a[3] + a[5])
+    c_q, c_r, c_p = (1 - alpha, alpha, alpha) if pp else (1.0, 0.0, 0.0)
+    gs = gscale / var
+    gq = (c_q * m + c_r * wr) * (xm[0] - x) * gs
+    gp = c_p * mp * (xm[1] - x) * gs if pp else zero
+    if gated:
+        gq = gq * (xm[0] * (1 - xm[0]))
+        if pp:
+            gp = gp * (xm[1] * (1 - xm[1]))
+    sgn = torch.sign(zlp[0] - zlp[1]) if pp else torch.zeros_like(z[0])
+    grads = (gq, gp, gscale * c_q * beta * z[0], gscale * c_p * beta * z[1] if pp else torch.zeros_like(z[0]),
+             gscale * (c_q * beta + alpha * sgn), gscale * (c_p * beta - alpha * sgn) if pp else torch.zeros_like(z[0]))
+    return dict(out8=torch.stack([loss] + s), abs8=torch.stack([abs_l] + a), grads=grads)
 
 
 def torch_step(P, x, mask, mask_p, eps, alpha=1.0, beta=1.0, stage="train"):

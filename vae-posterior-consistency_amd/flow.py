@@ -41,12 +41,13 @@ def flow_prep(x, mask, mask_p_in, mask_p_out, xin, eps_out, B, d, keep_prob=1.0,
                               int(offset), int(offset_eps), stream_ptr()), "vpc_flow_prep")
 
 
-def flow_fwd(t, eps, z, zlp, R, B):
-    check(lib().vpc_flow_fwd(ptr(t), CTX, ptr(eps), ptr(z), ptr(zlp), int(R), int(B), stream_ptr()), "vpc_flow_fwd")
+def flow_fwd(t, eps, z, zlp, R, B, ldt=CTX):
+    check(lib().vpc_flow_fwd(ptr(t), int(ldt), ptr(eps), ptr(z), ptr(zlp), int(R), int(B), stream_ptr()), "vpc_flow_fwd")
 
 
-def flow_bwd(t, eps, dz, dz2, dzlp, dt, R, B):
-    check(lib().vpc_flow_bwd(ptr(t), CTX, ptr(eps), ptr(dz), ptr(dz2), ptr(dzlp), ptr(dt), CTX, int(R), int(B),
+def flow_bwd(t, eps, dz, dz2, dzlp, dt, R, B, ldt=CTX, lddt=CTX):
+    """ldt / lddt: row pitch in floats of t / dt (>= CTX)."""
+    check(lib().vpc_flow_bwd(ptr(t), int(ldt), ptr(eps), ptr(dz), ptr(dz2), ptr(dzlp), ptr(dt), int(lddt), int(R), int(B),
                              stream_ptr()), "vpc_flow_bwd")
 
 
