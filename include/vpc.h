@@ -415,7 +415,7 @@ int vpc_eddi_front_bwd(const float* x, const uint8_t* mask, const uint8_t* mask2
 
 /* ---- the same front-end at image width (Reg_EDDI_mnist / vanilla_EDDI_mnist, src/models/VAE.py:62-77, 255-270) -------
  * Same arguments, layouts and meaning as the four entry points above, for any d <= 1024 (784: MNIST), K <= 32
- * (csrc/vpc_eddiw.hip: the folded table is tiled along k, 4 rows of A and C per workgroup over all d features, because
+ * (csrc/vpc_eddi.hip: the folded table is tiled along k, 4 rows of A and C per workgroup over all d features, because
  * [2][K][d] no longer fits LDS).  vpc_eddiw_front_bwd recomputes the ReLU gates and sums its per-workgroup partial blocks in a
  * fixed order: the same inputs give bitwise the same gradients.  scratch: vpc_eddiw_front_scratch(rows, d, K) floats. */
 int vpc_eddiw_fold(const float* E, const float* tb, const float* Wp, const float* cp, float* AC, int d, int K,

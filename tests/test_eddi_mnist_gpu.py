@@ -1,4 +1,4 @@
-"""GPU parity of the MNIST point-net pair (Reg_EDDI_mnist / vanilla_EDDI_mnist, eddi_mnist.py + csrc/vpc_eddiw.hip) against
+"""GPU parity of the MNIST point-net pair (Reg_EDDI_mnist / vanilla_EDDI_mnist, eddi_mnist.py + the vpc_eddiw_* kernels of csrc/vpc_eddi.hip) against
 vectors captured from the reference itself (tests/golden/eddi_mnist_*.npz) and the float64 closed form of
 tests/eddi_mnist_oracle.py.
 

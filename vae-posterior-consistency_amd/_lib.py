@@ -129,7 +129,7 @@ _PROTOS = {
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
     "vpc_eddi_front_scratch": [L_, I, I],
     "vpc_eddi_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
-    # the same front-end at image width (csrc/vpc_eddiw.hip)
+    # the same front-end at image width (vpc_eddiw_*, csrc/vpc_eddi.hip)
     "vpc_eddiw_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddiw_front_fwd": [P, P, P, P, P, L_, I, I, P],
     "vpc_eddiw_front_scratch": [L_, I, I],

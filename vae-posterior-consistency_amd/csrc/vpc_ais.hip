@@ -17,7 +17,7 @@
 // of MINUS the Gaussian log-density: sign = +1 is the reference as written (AIS.py:125 passes neg_gaussian_log_likelihood
 // as the "log likelihood"), sign = -1 the corrected target p(z) p(x|z)^t.
 #include "vpc_abi_internal.h"
-#include "vpc_ais_tiles.h"
+#include "vpc_device.h"
 #include "vpc_rng.h"
 
 namespace vpc {
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_kernel(AisArgs a) {
 #pragma unroll
         for (int mt = 0; mt < H1T; ++mt) {
             __builtin_amdgcn_sched_barrier(0);
-            g2[mt] = relu4(ais_tile_fwd<H2T, 64, NK2>(W5, mt, g1, cc, qq));
+            g2[mt] = relu4(tile_fwd_p2<H2T, 64, NK2>(W5, mt, g1, cc, qq));
         }
         const uint32_t gm1 = relu_bits<H2T>(g1);
         launder(cc, qq);
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_kernel(AisArgs a) {
         float ss = 0.f;
 #pragma unroll
         for (int mt = 0; mt < DT; ++mt) {
-            const f32x4 pre = ais_tile_fwd<H1T, 128, NK1>(W6, mt, g2, cc, qq);
+            const f32x4 pre = tile_fwd_p2<H1T, 128, NK1>(W6, mt, g2, cc, qq);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float xh = fast_sigmoid(pre[j]);
@@ -170,14 +170,14 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_kernel(AisArgs a) {
 #pragma unroll
         for (int mt = 0; mt < H1T; ++mt) {
             __builtin_amdgcn_sched_barrier(0);
-            dg2[mt] = gate_bits(ais_tile_T<DT, 128>(W6, mt, dpre, cc, qq), gm2, mt);
+            dg2[mt] = gate_bits(tile_T_p2<DT, 128>(W6, mt, dpre, cc, qq), gm2, mt);
         }
         launder(cc, qq);
         f32x4 dg1[H2T];
 #pragma unroll
         for (int mt = 0; mt < H2T; ++mt) {
             __builtin_amdgcn_sched_barrier(0);
-            dg1[mt] = gate_bits(ais_tile_T<H1T, 64, NK1>(W5, mt, dg2, cc, qq), gm1, mt);
+            dg1[mt] = gate_bits(tile_T_p2<H1T, 64, NK1>(W5, mt, dg2, cc, qq), gm1, mt);
         }
         launder(cc, qq);
         const f32x4 t = tile_T<H2T, S4, NK2>(W4, 0, dg1, zero4(), cc, qq);

@@ -19,59 +19,11 @@ namespace vpc {
 
 constexpr int DEC8_WAVES = 8, DEC8_THREADS = 512;
 
-// Single-chain tile products with a 2-deep fragment pipeline: the second wave of the SIMD hides LDS latency here, so
-// only two A fragments are in flight (8 registers) instead of the whole tile's (up to 32) as in the 4-wave kernel.
 #ifdef VPC_ABLATE
 #define ABL(bit) VPC_DBG(bit)   // timing experiments (diagnostic build): 1 no staging writes, 2 no barriers, 4 no wgrad MFMAs
 #else
 #define ABL(bit) false
 #endif
-
-template <int KT, int S, int NK = 4 * KT>  // NK: k-steps to run (the rest multiply padding zeros)
-__device__ __forceinline__ f32x4 tile_fwd_p2(const float* W, int mt, const f32x4 (&in)[KT], int m, int q) {
-    constexpr int MASK = (S / 4 - 1) & 15;
-    const float* rowp = W + (16 * mt + m) * S;
-    f32x4 acc = zero4();
-    f32x4 fa = *reinterpret_cast<const f32x4*>(rowp + 4 * ((0 + q) ^ (m & MASK)));
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-        const int kn = kt + 1 < KT ? kt + 1 : kt;
-        const f32x4 fn = *reinterpret_cast<const f32x4*>(rowp + 4 * ((4 * kn + q) ^ (m & MASK)));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
-        fa = fn;
-    }
-    return acc;
-}
-template <int KT, int S, int NK = 4 * KT>
-__device__ __forceinline__ f32x4 tile_T_p2(const float* W, int mt, const f32x4 (&in)[KT], int m, int q) {
-    constexpr int MASK = (S / 4 - 1) & 15;
-    const int col = 16 * mt + m;
-    const int cs = col >> 2, cl = col & 3;
-    auto rd = [&](int kt) {
-        f32x4 f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = 4 * q + j;
-            f[j] = (4 * kt + j < NK) ? W[(16 * kt + r) * S + (((cs ^ (r & MASK)) << 2) | cl)] : 0.f;
-        }
-        return f;
-    };
-    f32x4 acc = zero4();
-    f32x4 fa = rd(0);
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-        const f32x4 fn = rd(kt + 1 < KT ? kt + 1 : kt);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
-        fa = fn;
-    }
-    return acc;
-}
 
 // PREC != PREC_F32: the bf16 engine of vpc_bf16.h on the bf16 decoder image (DecImgBf: W4 rows are 32 dwords).
 template <int DT, bool VEC, int PREC = PREC_F32>

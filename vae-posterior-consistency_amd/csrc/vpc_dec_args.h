@@ -43,15 +43,7 @@ constexpr int DEC_CH = 64;  // batch rows per wgrad staging chunk
 // (measured on MI355X: 326 us without the region cuts, 252 us with them).
 #ifdef VPC_ABLATE
 #define VPC_DBG(bit) ((a.dbg & (bit)) != 0)
-// phase timing (diagnostic build only): accumulate s_memtime deltas per phase, printed by block 0 / thread 0
-#define VPC_STAMP(i)                                        \
-    do {                                                    \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-        T[i] += t_ - tlast;                                 \
-        tlast = t_;                                         \
-    } while (0)
 #else
-#define VPC_STAMP(i) do {} while (0)
 __device__ __forceinline__ int opaque_zero() {
     int z;
     asm volatile("s_mov_b32 %0, 0" : "=s"(z));
@@ -64,9 +56,6 @@ __device__ __forceinline__ int opaque_zero() {
     do {                                                       \
         if (VPC_DBG(0x4000)) asm volatile("s_nop 0");          \
     } while (0)
-
-
-
 
 size_t dec8_lds(int DT, int prec);
 int dec8_dispatch(const DecArgs& a, bool vec, int grid, int prec, hipStream_t s);

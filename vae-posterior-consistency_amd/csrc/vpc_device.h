@@ -143,6 +143,56 @@ __device__ __forceinline__ f32x4 tile_T(const float* W, int mt, const f32x4 (&in
     return acc;
 }
 
+// ---- single-chain tile products with a 2-deep fragment pipeline (8-wave decoder kernel, AIS kernel): two waves share a SIMD and
+// hide each other's LDS latency, so only two A fragments are in flight (8 registers) instead of the whole tile's (up to 32) as in
+// tile_fwd / tile_T.  They start from a zero accumulator.
+template <int KT, int S, int NK = 4 * KT>  // NK: k-steps to run (the rest multiply padding zeros)
+__device__ __forceinline__ f32x4 tile_fwd_p2(const float* W, int mt, const f32x4 (&in)[KT], int m, int q) {
+    constexpr int MASK = (S / 4 - 1) & 15;
+    const float* rowp = W + (16 * mt + m) * S;
+    f32x4 acc = zero4();
+    f32x4 fa = *reinterpret_cast<const f32x4*>(rowp + 4 * ((0 + q) ^ (m & MASK)));
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+        const int kn = kt + 1 < KT ? kt + 1 : kt;
+        const f32x4 fn = *reinterpret_cast<const f32x4*>(rowp + 4 * ((4 * kn + q) ^ (m & MASK)));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
+        fa = fn;
+    }
+    return acc;
+}
+// (A fragment: 4 x ds_read_b32)
+template <int KT, int S, int NK = 4 * KT>
+__device__ __forceinline__ f32x4 tile_T_p2(const float* W, int mt, const f32x4 (&in)[KT], int m, int q) {
+    constexpr int MASK = (S / 4 - 1) & 15;
+    const int col = 16 * mt + m;
+    const int cs = col >> 2, cl = col & 3;
+    auto rd = [&](int kt) {
+        f32x4 f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = 4 * q + j;
+            f[j] = (4 * kt + j < NK) ? W[(16 * kt + r) * S + (((cs ^ (r & MASK)) << 2) | cl)] : 0.f;
+        }
+        return f;
+    };
+    f32x4 acc = zero4();
+    f32x4 fa = rd(0);
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+        const f32x4 fn = rd(kt + 1 < KT ? kt + 1 : kt);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
+        fa = fn;
+    }
+    return acc;
+}
+
 // ---- wgrad staging: stage[feat][CH] fp32, 16-byte slot XOR-swizzled with feat & (CH/4 - 1)
 template <int CH>
 __device__ __forceinline__ void stage_write(float* st, int t, f32x4 v, int colbase, int c, int q) {
@@ -342,6 +392,21 @@ __device__ __forceinline__ void launder(int& c, int& q) {
 // staging round also waited for whatever had been requested from global memory ahead of its use (next tile's x / mask words,
 // pass-end operands, the B fragments read straight from global memory in the encoder backward).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Diagnostic build (-DVPC_ABLATE; `a` is the kernel's argument block, T / tlast its phase clock): VPC_STAMP(i) adds the s_memtime
+// delta since the last stamp to phase i, and a.dbg & 2 times a kernel without its LDS barriers (wrong results).  Product build:
+// no stamps, the plain barrier.
+#ifdef VPC_ABLATE
+#define VPC_STAMP(i)                                        \
+    do {                                                    \
+        const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+        T[i] += t_ - tlast;                                 \
+        tlast = t_;                                         \
+    } while (0)
+#define VPC_LDS_BARRIER() do { if (!(a.dbg & 2)) lds_barrier(); } while (0)
+#else
+#define VPC_STAMP(i) do {} while (0)
+#define VPC_LDS_BARRIER() lds_barrier()
+#endif
 
 // 64-lane sum without LDS traffic: four DPP adds give every lane its 16-lane row sum, four v_readlane + adds the
 // total (uniform).  ~12 VALU instructions against 6 dependent ds_bpermute round trips for the shuffle version.

@@ -7,6 +7,19 @@
 // Backward: dA_j = sum_b g[b][j] x_bj, dC_j = sum_b g[b][j] with g = mask * 1[pre > 0] * dagg[b]; per-lane register
 // accumulators over a grid-stride loop of rows, per-workgroup partials, fixed-order reduction (deterministic), then
 // the chain rule back to (E, t, W, c) in one small workgroup.
+//
+// Image-width front-end of Reg_EDDI_mnist / vanilla_EDDI_mnist (reference src/models/VAE.py:62-77, 255-270): the
+// same formulation (per-feature fold  pre[b][j] = x_bj A_j + C_j,  ReLU, mask-weighted sum over the features;
+// nothing of size B*d*(2+K) is materialised) for any d <= 1024.  At d = 784, K = 20 the folded table [2][K][d] is 125 KB and
+// does not fit a workgroup's LDS, so the table is tiled - along k, not along the features: a workgroup stages the KT = 4 rows
+// A[k0..k0+4) / C[k0..k0+4) over ALL features (2 * 4 * 1024 floats = 32 KB at most) and its waves walk batch rows with a
+// whole row of x and its mask in registers.  agg[r][k] of different k are independent outputs, so the k-tiles (blockIdx.y)
+// need no reduction between them and every (row, k) costs ONE wave reduction over the 784 terms.  The feature index is
+// lane + 64 t: consecutive lanes read consecutive LDS banks (conflict-free) and consecutive global addresses.
+// Backward: dA[k][j] = sum_r g x, dC[k][j] = sum_r g with g = mask 1[pre > 0] dagg[r][k] (gates recomputed); per-lane register
+// accumulators [KT][T] over a grid-stride loop of rows, the four waves combined through LDS in wave order, per-workgroup
+// partial blocks summed in a fixed order (no float atomics: bitwise reproducible).  The fold kernel and the tail behind the
+// partial blocks (fixed-order reduction, chain rule to (E, t, W, c)) are the narrow front-end's.
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
 #include "../../include/vpc.h"
@@ -149,6 +162,134 @@ __global__ __launch_bounds__(256) void eddi_front_bwd_kernel(const float* __rest
     for (int i = threadIdx.x; i < n; i += blockDim.x) part[(long)blockIdx.x * n + i] = st[i];
 }
 
+// ---- image-width front-end
+constexpr int EDDIW_MAX_K = 32;
+constexpr int EDDIW_MAX_D = 1024;
+constexpr int EDDIW_KT = 4;  // table rows (k) per workgroup
+
+// LDS image of one k-tile: [2][KT][64 T] with the columns d .. 64 T - 1 zero, so that no read needs a bound check
+template <int T>
+__device__ __forceinline__ void eddiw_stage(float* lds, const float* __restrict__ AC, int d, int K, int k0, int kn) {
+    constexpr int DP = 64 * T;
+    for (int i = threadIdx.x; i < 2 * EDDIW_KT * DP; i += blockDim.x) {
+        const int half = i / (EDDIW_KT * DP), kk = (i / DP) % EDDIW_KT, j = i % DP;
+        lds[i] = (kk < kn && j < d) ? AC[(long)(half * K + k0 + kk) * d + j] : 0.f;
+    }
+    __syncthreads();
+}
+
+// one row of x (T features per lane) and its mask as one bit per feature
+template <int T>
+__device__ __forceinline__ void eddiw_row(const float* __restrict__ x, const uint8_t* __restrict__ m, long b, int d, int lane,
+                                          float (&xv)[T], unsigned& mbits) {
+    mbits = 0u;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int j = lane + 64 * t;
+        const bool ok = j < d;
+        xv[t] = ok ? x[b * d + j] : 0.f;
+        if (ok && m[b * d + j]) mbits |= 1u << t;
+    }
+}
+
+// rows r = pass * B + b: the passes of one step (mask, mask_p) are stacked, x is shared
+template <int T>
+__global__ __launch_bounds__(256) void eddiw_front_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m0,
+                                                              const uint8_t* __restrict__ m1,
+                                                              const float* __restrict__ AC, float* __restrict__ agg,
+                                                              int B, int npass, int d, int K) {
+    constexpr int DP = 64 * T;
+    __shared__ float lds[2 * EDDIW_KT * DP];
+    const int k0 = blockIdx.y * EDDIW_KT;
+    const int kn = K - k0 < EDDIW_KT ? K - k0 : EDDIW_KT;
+    eddiw_stage<T>(lds, AC, d, K, k0, kn);
+    const float* sA = lds;
+    const float* sC = lds + EDDIW_KT * DP;
+    const int lane = threadIdx.x & 63;
+    const int gwave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    for (int r = gwave; r < npass * B; r += nwaves) {
+        const int b = r < B ? r : r - B;
+        float xv[T];
+        unsigned mbits;
+        eddiw_row<T>(x, r < B ? m0 : m1, b, d, lane, xv, mbits);
+        float out = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < EDDIW_KT; ++kk) {
+            float v = 0.f;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const float h = fmaxf(xv[t] * sA[kk * DP + lane + 64 * t] + sC[kk * DP + lane + 64 * t], 0.f);
+                v += ((mbits >> t) & 1u) ? h : 0.f;
+            }
+            const float s = wave_sum_dpp(v);
+            if (lane == kk) out = s;
+        }
+        if (lane < kn) agg[(long)r * K + k0 + lane] = out;
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void eddiw_front_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m0,
+                                                              const uint8_t* __restrict__ m1,
+                                                              const float* __restrict__ AC,
+                                                              const float* __restrict__ dagg, float* __restrict__ part,
+                                                              int B, int npass, int d, int K) {
+    constexpr int DP = 64 * T;
+    __shared__ float lds[2 * EDDIW_KT * DP];  // the k-tile's table; after the row loop the cross-wave combine stage
+    const int k0 = blockIdx.y * EDDIW_KT;
+    const int kn = K - k0 < EDDIW_KT ? K - k0 : EDDIW_KT;
+    eddiw_stage<T>(lds, AC, d, K, k0, kn);
+    const float* sA = lds;
+    const float* sC = lds + EDDIW_KT * DP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gwave = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
+    float dA[EDDIW_KT][T], dC[EDDIW_KT][T];
+#pragma unroll
+    for (int kk = 0; kk < EDDIW_KT; ++kk)
+#pragma unroll
+        for (int t = 0; t < T; ++t) dA[kk][t] = dC[kk][t] = 0.f;
+    for (int r = gwave; r < npass * B; r += nwaves) {
+        const int b = r < B ? r : r - B;
+        float xv[T];
+        unsigned mbits;
+        eddiw_row<T>(x, r < B ? m0 : m1, b, d, lane, xv, mbits);
+        const float dgl = lane < kn ? dagg[(long)r * K + k0 + lane] : 0.f;  // lanes >= kn: 0, so a tile's unused k add nothing
+#pragma unroll
+        for (int kk = 0; kk < EDDIW_KT; ++kk) {
+            const float dg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dgl), kk));
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const float pre = xv[t] * sA[kk * DP + lane + 64 * t] + sC[kk * DP + lane + 64 * t];
+                const float g = (((mbits >> t) & 1u) && pre > 0.f) ? dg : 0.f;
+                dA[kk][t] += g * xv[t];
+                dC[kk][t] += g;
+            }
+        }
+    }
+    // ---- combine the 4 waves through the (now free) LDS, wave after wave: a fixed order, hence deterministic
+    for (int ww = 0; ww < 4; ++ww) {
+        __syncthreads();
+        if (wave == ww) {
+#pragma unroll
+            for (int kk = 0; kk < EDDIW_KT; ++kk) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    float* pa = lds + kk * DP + lane + 64 * t;
+                    float* pc = lds + (EDDIW_KT + kk) * DP + lane + 64 * t;
+                    *pa = (ww == 0 ? 0.f : *pa) + dA[kk][t];
+                    *pc = (ww == 0 ? 0.f : *pc) + dC[kk][t];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float* out = part + (long)blockIdx.x * 2 * K * d;  // this workgroup's block [2][K][d]: rows k0 .. k0 + kn of both halves
+    for (int i = threadIdx.x; i < 2 * EDDIW_KT * DP; i += blockDim.x) {
+        const int half = i / (EDDIW_KT * DP), kk = (i / DP) % EDDIW_KT, j = i % DP;
+        if (kk < kn && j < d) out[(long)(half * K + k0 + kk) * d + j] = lds[i];
+    }
+}
+
 // dAC[i] = sum over the workgroup partials (sum_partials_16x16: fixed order)
 __global__ __launch_bounds__(256) void eddi_reduce_kernel(const float* __restrict__ part, int G, int n, float* __restrict__ dAC) {
     __shared__ float sh[16][16];
@@ -205,12 +346,42 @@ __global__ __launch_bounds__(256) void eddi_param_bwd_kernel(const float* __rest
     }
 }
 
-
 static int eddi_blocks(long B) {
     long blocks = (B + 3) / 4;
     const long cap = 3L * num_cus();  // the backward kernel fits 3 workgroups per CU (registers)
     if (blocks > cap) blocks = cap;
     return (int)(blocks < 1 ? 1 : blocks);
+}
+
+static int eddiw_ktiles(int K) { return (K + EDDIW_KT - 1) / EDDIW_KT; }
+
+// forward: one row per wave until the device is full (about 4 workgroups per CU over all k-tiles)
+static int eddiw_fwd_blocks(long R, int K) {
+    long blocks = (R + 3) / 4;
+    long cap = 4L * num_cus() / eddiw_ktiles(K);
+    if (cap < 1) cap = 1;
+    if (blocks > cap) blocks = cap;
+    return (int)(blocks < 1 ? 1 : blocks);
+}
+
+// backward: every workgroup (blockIdx.x) writes one partial block [2][K][d]; at most 128 of them (16 MB at d = 784, K = 20)
+static int eddiw_bwd_blocks(long R) {
+    long blocks = (R + 7) / 8;
+    if (blocks > 128) blocks = 128;
+    return (int)(blocks < 1 ? 1 : blocks);
+}
+
+static bool eddiw_shape_ok(int d, int K) { return d > 0 && d <= EDDIW_MAX_D && K > 0 && K <= EDDIW_MAX_K; }
+
+// the tail of both backward launches: partial blocks -> (dA | dC) in a fixed order, then the chain rule to the parameters
+static int eddi_bwd_tail(const float* part, int G, float* dAC, const float* E, const float* tb, const float* Wp, float* gE,
+                         float* gtb, float* gWp, float* gcp, int accumulate, int d, int K, hipStream_t st) {
+    const int n = 2 * K * d;
+    hipLaunchKernelGGL(eddi_reduce_kernel, dim3((n + 15) / 16), dim3(256), 0, st, part, G, n, dAC);
+    const int gA = (d * K + d + 255) / 256, gB = (K * (2 + K) + K + 3) / 4;
+    hipLaunchKernelGGL(eddi_param_bwd_kernel, dim3(gA + gB), dim3(256), 0, st, dAC, E, tb, Wp, gE, gtb, gWp, gcp, d, K,
+                       accumulate, gA);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
 }  // namespace vpc
@@ -219,6 +390,7 @@ using namespace vpc;
 
 extern "C" {
 
+// ---- narrow entry points (obs_dim <= 128)
 int vpc_eddi_fold(const float* E, const float* tb, const float* Wp, const float* cp, float* AC, int d, int K,
                   void* stream) {
     if (!E || !tb || !Wp || !cp || !AC) return VPC_ERR_ARG;
@@ -276,11 +448,65 @@ int vpc_eddi_front_bwd(const float* x, const uint8_t* mask, const uint8_t* mask2
     }
 #undef VPC_EDDI_BWD
     if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
-    hipLaunchKernelGGL(eddi_reduce_kernel, dim3((n + 15) / 16), dim3(256), 0, st, part, G, n, dAC);
-    const int gA = (d * K + d + 255) / 256, gB = (K * (2 + K) + K + 3) / 4;
-    hipLaunchKernelGGL(eddi_param_bwd_kernel, dim3(gA + gB), dim3(256), 0, st, dAC, E, tb, Wp, gE, gtb, gWp, gcp, d, K,
-                       accumulate, gA);
+    return eddi_bwd_tail(part, G, dAC, E, tb, Wp, gE, gtb, gWp, gcp, accumulate, d, K, st);
+}
+
+// ---- image-width entry points (obs_dim <= 1024)
+// features per lane: the smallest compiled T with 64 T >= d (13: d = 784)
+#define VPC_EDDIW_DISPATCH(d, CALL)                                                                                    \
+    do {                                                                                                               \
+        if ((d) <= 64) CALL(1); else if ((d) <= 128) CALL(2); else if ((d) <= 256) CALL(4);                            \
+        else if ((d) <= 512) CALL(8); else if ((d) <= 832) CALL(13); else CALL(16);                                    \
+    } while (0)
+
+int vpc_eddiw_fold(const float* E, const float* tb, const float* Wp, const float* cp, float* AC, int d, int K,
+                   void* stream) {
+    if (!E || !tb || !Wp || !cp || !AC) return VPC_ERR_ARG;
+    if (!eddiw_shape_ok(d, K)) return VPC_ERR_SHAPE;
+    hipLaunchKernelGGL(eddi_fold_kernel, dim3((d * K + 255) / 256), dim3(256), 0, (hipStream_t)stream, E, tb, Wp, cp, AC,
+                       d, K);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_eddiw_front_fwd(const float* x, const uint8_t* mask, const uint8_t* mask2, const float* AC, float* agg, long B,
+                        int d, int K, void* stream) {
+    if (!x || !mask || !AC || !agg || B <= 0 || 2 * B * (long)d > 0x7fffff00L) return VPC_ERR_ARG;
+    if (!eddiw_shape_ok(d, K)) return VPC_ERR_SHAPE;
+    const int npass = mask2 ? 2 : 1;
+    const dim3 grid(eddiw_fwd_blocks(npass * B, K), eddiw_ktiles(K));
+    hipStream_t st = (hipStream_t)stream;
+#define VPC_EDDIW_FWD(T) \
+    hipLaunchKernelGGL((eddiw_front_fwd_kernel<T>), grid, dim3(256), 0, st, x, mask, mask2, AC, agg, (int)B, npass, d, K)
+    VPC_EDDIW_DISPATCH(d, VPC_EDDIW_FWD);
+#undef VPC_EDDIW_FWD
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+long vpc_eddiw_front_scratch(long rows, int d, int K) {  // floats: per-workgroup partial blocks + the reduced (dA | dC)
+    if (rows <= 0 || d <= 0 || K <= 0) return 0;
+    return (long)(eddiw_bwd_blocks(rows) + 1) * 2 * K * d;
+}
+
+int vpc_eddiw_front_bwd(const float* x, const uint8_t* mask, const uint8_t* mask2, const float* AC, const float* dagg,
+                        const float* E, const float* tb, const float* Wp, float* scratch, long scratch_floats, float* gE,
+                        float* gtb, float* gWp, float* gcp, int accumulate, long B, int d, int K, void* stream) {
+    if (!x || !mask || !AC || !dagg || !E || !tb || !Wp || !scratch || !gE || !gtb || !gWp || !gcp || B <= 0 ||
+        2 * B * (long)d > 0x7fffff00L)
+        return VPC_ERR_ARG;
+    if (!eddiw_shape_ok(d, K)) return VPC_ERR_SHAPE;
+    const int npass = mask2 ? 2 : 1;
+    if (scratch_floats < vpc_eddiw_front_scratch(npass * B, d, K)) return VPC_ERR_ARG;
+    const int G = eddiw_bwd_blocks(npass * B), n = 2 * K * d;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = scratch;
+    float* dAC = scratch + (long)G * n;
+    const dim3 grid(G, eddiw_ktiles(K));
+#define VPC_EDDIW_BWD(T) \
+    hipLaunchKernelGGL((eddiw_front_bwd_kernel<T>), grid, dim3(256), 0, st, x, mask, mask2, AC, dagg, part, (int)B, npass, d, K)
+    VPC_EDDIW_DISPATCH(d, VPC_EDDIW_BWD);
+#undef VPC_EDDIW_BWD
+    if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
+    return eddi_bwd_tail(part, G, dAC, E, tb, Wp, gE, gtb, gWp, gcp, accumulate, d, K, st);
 }
 
 }  // extern "C"

@@ -9,17 +9,6 @@
 
 namespace vpc {
 
-#ifdef VPC_ABLATE
-#define VPC_STAMP(i)                                        \
-    do {                                                    \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-        T[i] += t_ - tlast;                                 \
-        tlast = t_;                                         \
-    } while (0)
-#else
-#define VPC_STAMP(i) do {} while (0)
-#endif
-
 // layer-1 input tile t of one row in C layout.  AUG = mask-augmented encoder input [x*mask | mask] of width 2d
 // (Reg_VAE_mask / vanilla_VAE_mask, src/models/VAE.py:545-548): element f < d is x_f * m_f, d <= f < 2d is m_{f-d}.
 template <bool VEC, bool AUG>

@@ -41,6 +41,8 @@ constexpr int NK1 = (H1 + 1 + 3) / 4, NK2 = (H2 + 1 + 3) / 4;  // 26 of 28, 13 o
 // 48, 52, 56 for H2 (j = 1, 2, 3 of tile 3).  Only vpc_build_indices knows this; the kernels see opaque positions.
 VPC_HD constexpr int pos1(int u) { return u < 96 ? u : (u < 100 ? 96 + 4 * (u - 96) : 97); }
 VPC_HD constexpr int pos2(int u) { return u < 48 ? u : 48 + 4 * (u - 48); }
+// packed row of encoder layer 3: mean rows -> tile 0, logvar rows -> tile 1
+VPC_HD constexpr int row3(int o, int L) { return o < L ? o : 16 + (o - L); }
 // bijection of 0..111 that extends pos1: indices past the constant unit go to the padding positions
 VPC_HD inline int pos1_full(int f) {
     const int pad[H1P - H1 - 1] = {98, 99, 101, 102, 103, 105, 106, 107, 109, 110, 111};

@@ -73,9 +73,6 @@ bool lds_attr_done(const void* kern, size_t lds) {
     return true;
 }
 
-// packed row of encoder layer 3: mean rows -> tile 0, logvar rows -> tile 1
-static inline int row3(int o, int L) { return o < L ? o : 16 + (o - L); }
-
 // ------------------------------------------------------------------------------------------------
 // weight pack:  img[pack_idx[i]] = flat[i]
 __global__ void pack_kernel(const float* __restrict__ flat, const int* __restrict__ idx, float* __restrict__ img,

@@ -11,7 +11,7 @@
 // Workgroup: 4 waves (one per SIMD, 512 registers each), one 16-row slice of the 64-row tile per wave.  A tile holds the K replicas
 // of nb = 64 / K data rows (rows r = bl * K + k; the last 64 - nb K rows are padding: K = 20 -> 60 of 64 rows carry work); the
 // stacked passes (q rows, then p rows) are tiled separately, so a tile's pass is uniform.
-// LDS (162 976 of 163 840 bytes): one bf16 image of the three layers in the compact layout of vpc_step.hip (c_elem<KP>: W1 128 x 32,
+// LDS (162 976 of 163 840 bytes): one bf16 image of the three layers in the compact layout of vpc_bf16c.h (c_elem<KP>: W1 128 x 32,
 // W2 128 x 128, Wx 256 x 128) + fp32 biases + W, b of the missingness model and their softplus / sigmoid (111 KB), 25 staging
 // slots of [64 rows x 16 features] bf16 for the wgrad operands (50 KB, bf_stage layout of vpc_bf16.h), 128 floats for the K-coupling.
 // Registers: 204 gradient accumulators per lane (dWx 128, dW2 64, dW1 8 and ONE tile for every column sum: the three bias gradients
@@ -24,7 +24,7 @@
 // and dz (summed over K by one lane per (data row, latent), which also adds the analytic KL gradients).
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
-#include "vpc_bf16.h"
+#include "vpc_bf16c.h"
 #include "vpc_adam.h"
 #include "vpc_dec_args.h"
 #include <climits>
@@ -33,17 +33,6 @@
 #include <type_traits>
 
 namespace vpc {
-
-// compact image helpers (same layout as vpc_step.hip; kept local: that file's are tied to its layer constants)
-template <int KP>
-VPC_HD constexpr int nd_key(int row) {
-    return KP == 128 ? ((((row >> 1) & 3) << 2) | (((row >> 3) & 1) << 1) | (row & 1))
-                     : ((row / (128 / KP)) & (KP / 8 - 1));
-}
-template <int KP>
-VPC_HD constexpr int nd_elem(int row, int f) {  // u16 index of (row, input feature f) inside a layer image
-    return row * KP + (((4 * (f >> 5) + ((f >> 2) & 3)) ^ nd_key<KP>(row)) << 3) + 4 * ((f >> 4) & 1) + (f & 3);
-}
 
 constexpr int ND_WAVES = 4, ND_THREADS = 256, ND_ROWS = 64, ND_HID = 128, ND_HT = 8;
 constexpr int ND_FT = 25;                                  // staging slots per row
@@ -76,8 +65,6 @@ constexpr int R_X = 0, R_2 = 128, R_1 = 192, R_B = 200;
 constexpr int NB_BX = 0, NB_B2 = 4, NB_B1 = 6;
 constexpr int R_WB = 204;  // 4 more registers of wave 0's threads: dW | db of the missingness model, summed over the waves
 
-typedef bf16x8 Op;
-
 struct NmdArgs {
     const float* img;
     const float* x; const float* m; const float* mp;   // [B][d]
@@ -92,25 +79,6 @@ struct NmdArgs {
     int dbg;
 };
 
-__device__ __forceinline__ Op nd_pack2(f32x4 t0, f32x4 t1) {
-    const u32x4 h = {pk_bf16(t0[0], t0[1]), pk_bf16(t0[2], t0[3]), pk_bf16(t1[0], t1[1]), pk_bf16(t1[2], t1[3])};
-    return __builtin_bit_cast(Op, h);
-}
-template <int KP>
-__device__ __forceinline__ Op nd_wfrag(const float* W, int mt, int kb, int m, int q) {
-    return __builtin_bit_cast(Op, *reinterpret_cast<const f32x4*>(W + (16 * mt + m) * (KP / 2) + 4 * ((4 * kb + q) ^ nd_key<KP>(m))));
-}
-template <int KP>
-__device__ __forceinline__ Op nd_wfrag_T(const float* W, int mt, int kb, int lane) {
-    const int q = lane >> 4, rr = (lane >> 2) & 3, pp = lane & 3;
-    const int r0 = 32 * kb + 4 * q + rr, r1 = r0 + 16;
-    const int pi = 4 * (mt >> 1) + pp, e = 2 * (mt & 1);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x4 h0 = ds_tr16(W + r0 * (KP / 2) + 4 * (pi ^ nd_key<KP>(r0)) + e);
-    const s16x4 h1 = ds_tr16(W + r1 * (KP / 2) + 4 * (pi ^ nd_key<KP>(r1)) + e);
-    const s16x8 h = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    return __builtin_bit_cast(Op, h);
-}
 // forward layer, TWO out tiles per step (two independent MFMA chains: one wave per SIMD has nothing else to cover the dependent
 // latency with); the fragments of the next pair are requested behind the MFMAs of this one
 // (bias: the lane's part of the layer's fp32 bias, bias + 4 q - the accumulators START from it, so the sink has no add to do; nullptr:
@@ -120,7 +88,7 @@ __device__ __forceinline__ void nd_layer_fwd(const float* W, const Op (&in)[KB],
     static_assert(NT % 2 == 0, "");
     Op c0[KB], c1[KB];
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) { c0[kb] = nd_wfrag<KP>(W, 0, kb, m, q); c1[kb] = nd_wfrag<KP>(W, 1, kb, m, q); }
+    for (int kb = 0; kb < KB; ++kb) { c0[kb] = c_wfrag<KP>(W, 0, kb, m, q); c1[kb] = c_wfrag<KP>(W, 1, kb, m, q); }
 #pragma unroll
     for (int mt = 0; mt < NT; mt += 2) {
         f32x4 a0 = bias ? *reinterpret_cast<const f32x4*>(bias + 16 * mt) : zero4();
@@ -129,7 +97,7 @@ __device__ __forceinline__ void nd_layer_fwd(const float* W, const Op (&in)[KB],
         for (int kb = 0; kb < KB; ++kb) { a0 = VPC_MFMA_BF(c0[kb], in[kb], a0); a1 = VPC_MFMA_BF(c1[kb], in[kb], a1); }
         if (mt + 2 < NT) {
 #pragma unroll
-            for (int kb = 0; kb < KB; ++kb) { c0[kb] = nd_wfrag<KP>(W, mt + 2, kb, m, q); c1[kb] = nd_wfrag<KP>(W, mt + 3, kb, m, q); }
+            for (int kb = 0; kb < KB; ++kb) { c0[kb] = c_wfrag<KP>(W, mt + 2, kb, m, q); c1[kb] = c_wfrag<KP>(W, mt + 3, kb, m, q); }
         }
         asm volatile("" : "+v"(a0), "+v"(a1));
         __builtin_amdgcn_sched_barrier(0);
@@ -143,7 +111,7 @@ __device__ __forceinline__ void nd_layer_T(const float* W, const Op (&in)[KB], i
     if constexpr (NT == 1) {
         f32x4 a0 = zero4();
 #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) a0 = VPC_MFMA_BF(nd_wfrag_T<KP>(W, 0, kb, lane), in[kb], a0);
+        for (int kb = 0; kb < KB; ++kb) a0 = VPC_MFMA_BF(c_wfrag_T<KP>(W, 0, kb, lane), in[kb], a0);
         sink(0, a0, a0);
     } else if constexpr (KB > 4) {
         // two accumulator chains over the k-blocks of ONE tile pair, fragments fetched in two halves of KB / 2 blocks
@@ -156,8 +124,8 @@ __device__ __forceinline__ void nd_layer_T(const float* W, const Op (&in)[KB], i
                 Op c0[HB], c1[HB];
 #pragma unroll
                 for (int kb = 0; kb < HB; ++kb) {
-                    c0[kb] = nd_wfrag_T<KP>(W, mt, h * HB + kb, lane);
-                    c1[kb] = nd_wfrag_T<KP>(W, mt + 1, h * HB + kb, lane);
+                    c0[kb] = c_wfrag_T<KP>(W, mt, h * HB + kb, lane);
+                    c1[kb] = c_wfrag_T<KP>(W, mt + 1, h * HB + kb, lane);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -172,7 +140,7 @@ __device__ __forceinline__ void nd_layer_T(const float* W, const Op (&in)[KB], i
     } else {
         Op c0[KB], c1[KB];
 #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) { c0[kb] = nd_wfrag_T<KP>(W, 0, kb, lane); c1[kb] = nd_wfrag_T<KP>(W, 1, kb, lane); }
+        for (int kb = 0; kb < KB; ++kb) { c0[kb] = c_wfrag_T<KP>(W, 0, kb, lane); c1[kb] = c_wfrag_T<KP>(W, 1, kb, lane); }
 #pragma unroll
         for (int mt = 0; mt < NT; mt += 2) {
             f32x4 a0 = zero4(), a1 = zero4();
@@ -180,7 +148,7 @@ __device__ __forceinline__ void nd_layer_T(const float* W, const Op (&in)[KB], i
             for (int kb = 0; kb < KB; ++kb) { a0 = VPC_MFMA_BF(c0[kb], in[kb], a0); a1 = VPC_MFMA_BF(c1[kb], in[kb], a1); }
             if (mt + 2 < NT) {
 #pragma unroll
-                for (int kb = 0; kb < KB; ++kb) { c0[kb] = nd_wfrag_T<KP>(W, mt + 2, kb, lane); c1[kb] = nd_wfrag_T<KP>(W, mt + 3, kb, lane); }
+                for (int kb = 0; kb < KB; ++kb) { c0[kb] = c_wfrag_T<KP>(W, mt + 2, kb, lane); c1[kb] = c_wfrag_T<KP>(W, mt + 3, kb, lane); }
             }
             __builtin_amdgcn_sched_barrier(0);
             sink(mt, a0, a1);
@@ -196,7 +164,7 @@ __device__ __forceinline__ void nd_heads(const float* W, const Op (&in)[4], int 
                                          const float* bl) {
     Op c0[4], c1[4];
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) { c0[kb] = nd_wfrag<128>(W, 0, kb, m, q); c1[kb] = nd_wfrag<128>(W, DT, kb, m, q); }
+    for (int kb = 0; kb < 4; ++kb) { c0[kb] = c_wfrag<128>(W, 0, kb, m, q); c1[kb] = c_wfrag<128>(W, DT, kb, m, q); }
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
         pre(t);
@@ -205,30 +173,13 @@ __device__ __forceinline__ void nd_heads(const float* W, const Op (&in)[4], int 
         for (int kb = 0; kb < 4; ++kb) { a0 = VPC_MFMA_BF(c0[kb], in[kb], a0); a1 = VPC_MFMA_BF(c1[kb], in[kb], a1); }
         if (t + 1 < DT) {
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) { c0[kb] = nd_wfrag<128>(W, t + 1, kb, m, q); c1[kb] = nd_wfrag<128>(W, DT + t + 1, kb, m, q); }
+            for (int kb = 0; kb < 4; ++kb) { c0[kb] = c_wfrag<128>(W, t + 1, kb, m, q); c1[kb] = c_wfrag<128>(W, DT + t + 1, kb, m, q); }
         }
         asm volatile("" : "+v"(a0), "+v"(a1));
         __builtin_amdgcn_sched_barrier(0);
         sink(t, a0, a1);
         __builtin_amdgcn_sched_barrier(0);
     }
-}
-// staging: a packed operand (tiles 2 kb, 2 kb + 1 of the lane's row) into slots slot0 + 2 kb (+ 1)
-template <bool BOTH = true, int FT = ND_FT>
-__device__ __forceinline__ void nd_st_op(float* st, int row, int slot0, int kb, int q, Op op) {
-    const u32x4 h = __builtin_bit_cast(u32x4, op);
-    const int o0 = bf_stage_off<FT>(row, slot0 + 2 * kb, q);
-    *reinterpret_cast<u32x2*>(st + o0) = u32x2{h[0], h[1]};
-    if (BOTH) *reinterpret_cast<u32x2*>(st + o0 + 64) = u32x2{h[2], h[3]};
-}
-template <int FT = ND_FT>
-__device__ __forceinline__ Op nd_st_frag(const float* st, int slot, int kb, int lane) {
-    const int g = lane >> 4, rr = (lane >> 2) & 3, pp = lane & 3;
-    const int off = bf_stage_off<FT>(32 * kb + 4 * g + rr, slot, pp);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x4 h0 = ds_tr16(st + off), h1 = ds_tr16(st + off + 128 * FT);
-    const s16x8 h = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    return __builtin_bit_cast(Op, h);
 }
 __device__ __forceinline__ f32x4 elu4(f32x4 v) {  // ELU(alpha = 1), hardware exp as the GEMM epilogue (vpc_gemm.hip)
     return f32x4{v[0] > 0.f ? v[0] : __expf(v[0]) - 1.f, v[1] > 0.f ? v[1] : __expf(v[1]) - 1.f,
@@ -291,14 +242,6 @@ __device__ __forceinline__ void row_sum_dpp4(float (&v)[4]) {
         : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
     v[0] = t0; v[1] = t1; v[2] = t2; v[3] = t3;
 }
-
-#ifdef VPC_ABLATE
-#define ND_BARRIER() do { if (!(a.dbg & 2)) lds_barrier(); } while (0)
-#define NSTP(i) VPC_STAMP(i)
-#else
-#define ND_BARRIER() lds_barrier()
-#define NSTP(i) do {} while (0)
-#endif
 
 template <int DT, bool REG>
 __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
@@ -443,7 +386,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
     }
     __syncthreads();
 
-    NSTP(0);
+    VPC_STAMP(0);
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         int cc = c, qq = q;
         launder(cc, qq);
@@ -461,7 +404,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         // ---------------- the tile's inputs -> LDS, once per tile (every replica of a data row reads the same x / masks / statistics);
         // they were requested from global memory while the previous tile's staging rounds ran (request_inputs below)
         store_inputs(qpass);
-        ND_BARRIER();  // B0
+        VPC_LDS_BARRIER();  // B0
         // ---------------- reparameterisation (VAE.py:2385-2389): z = mean + eps * exp(logvar / 2)   (columns >= L are staged as 0)
         f32x4 z, ehs;  // ehs = eps * exp(logvar / 2) / 2: d z / d logvar
         f32x4 zk = zero4(), hk = zero4();  // un-regularised class: z' of the KL draw and eps_kl sd / 2
@@ -485,15 +428,15 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
             }
         }
         if (!REG) { klmc += __shfl_xor(klmc, 16, 64); klmc += __shfl_xor(klmc, 32, 64); }
-        const Op zb = nd_pack2(z, zero4());
-        NSTP(1);
+        const Op zb = pack2(z, zero4());
+        VPC_STAMP(1);
         // ---------------- decoder forward
         // g1 = ELU(W1 z + b1) is formed here for the forward and AGAIN in front of R2 (8 MFMAs + the ELUs instead of 16 registers
         // held across the loss passes and R1, the phases with the most live state)
         const Op zin[1] = {zb};
         auto make_g1 = [&](Op (&g1b)[4]) {
             nd_layer_fwd<32, 1, ND_HT>(W1, zin, cc, qq, [&](int mt, f32x4 a0, f32x4 a1) {
-                g1b[mt >> 1] = nd_pack2(elu4(a0), elu4(a1));
+                g1b[mt >> 1] = pack2(elu4(a0), elu4(a1));
             }, b1 + 4 * qq);
         };
         Op g2b[4];
@@ -502,12 +445,12 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
             make_g1(g1b);
             launder(cc, qq);
             nd_layer_fwd<128, 4, ND_HT>(W2, g1b, cc, qq, [&](int mt, f32x4 a0, f32x4 a1) {
-                g2b[mt >> 1] = nd_pack2(elu4(a0), elu4(a1));
+                g2b[mt >> 1] = pack2(elu4(a0), elu4(a1));
             }, b2 + 4 * qq);
         }
         launder(cc, qq);
         VPC_CUT();
-        NSTP(2);
+        VPC_STAMP(2);
         // ---------------- heads + bound terms of the lane's row, pass 1: sums over the features (VAE.py:2393-2396, 2405-2440).
         // The head outputs are NOT kept for pass 2 (64 registers across the exchange, beside its 64 registers of results): each
         // pass forms them tile by tile on the matrix pipe - 64 bf16 MFMAs again instead of scratch traffic.
@@ -555,7 +498,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         }
         launder(cc, qq);
         VPC_CUT();
-        NSTP(3);
+        VPC_STAMP(3);
         // (pass 2 must not be merged with pass 1 by common-subexpression elimination - everything it would carry across the
         // exchange ends up in scratch: the asm makes its operand a new value)
 #pragma unroll
@@ -571,8 +514,8 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         // Monte-Carlo KL of the other class differs per replica)
         const float lw = RE + sN + klmc;
         if (qq == 0 && rvalid) lwbuf[bl * KP4 + k] = lw;
-        NSTP(4);
-        ND_BARRIER();  // B1
+        VPC_STAMP(4);
+        VPC_LDS_BARRIER();  // B1
         float wgt;     // softmax weight of the replica x the gradient weight of its pass
         {
             const float* lwp = lwbuf + blc * KP4;
@@ -603,7 +546,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
                 if (qpass) { if (REG) S[2] += sE + a.cd; S[4] += RE; }
             }
         }
-        NSTP(5);
+        VPC_STAMP(5);
         // ---------------- pass 2: gradients w.r.t. the head PRE-activations (through Sigmoid / Hardtanh), packed as they are made
         // (each tile's results are packed at once - 2 registers per tile and array; carried as fp32 until the partner tile of a
         // 32-feature operand is done they are 16 more live registers in the phase that has the fewest to spare)
@@ -660,27 +603,27 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         }
         launder(cc, qq);
         VPC_CUT();
-        NSTP(6);
+        VPC_STAMP(6);
         // ---------------- R1a: dWx rows of the mean head, their bias, db of the missingness model
         const int fl = 16 * qq + cc;
-        ND_BARRIER();  // B1': every wave is past its reads of the tile inputs, which the staged operands overwrite
+        VPC_LDS_BARRIER();  // B1': every wave is past its reads of the tile inputs, which the staged operands overwrite
         if (tile + (int)gridDim.x < a.ntiles) request_inputs(tile + gridDim.x);  // (arrive under the staging rounds)
 #pragma unroll
-        for (int kb = 0; kb < DT / 2; ++kb) nd_st_op(st, r, 0, kb, qq, Gb[kb]);
+        for (int kb = 0; kb < DT / 2; ++kb) st_op<true, ND_FT>(st, r, 0, kb, qq, Gb[kb]);
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) nd_st_op(st, r, 8, kb, qq, g2b[kb]);
-        ND_BARRIER();  // B2
+        for (int kb = 0; kb < 4; ++kb) st_op<true, ND_FT>(st, r, 8, kb, qq, g2b[kb]);
+        VPC_LDS_BARRIER();  // B2
         auto round_x = [&](auto half_c) {
             constexpr int half = decltype(half_c)::value;  // owner: wave w -> head tiles w and w + 4 of this half (DT = 8: both exist)
 #pragma unroll
             for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
                 Op fb[8];
 #pragma unroll
-                for (int nt = 0; nt < 8; ++nt) fb[nt] = nd_st_frag(st, 8 + nt, kb, fl);
+                for (int nt = 0; nt < 8; ++nt) fb[nt] = st_frag<ND_FT>(st, 8 + nt, kb, fl);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     if (DT < 8 && w + 4 * i >= DT) continue;
-                    const Op fa = nd_st_frag(st, w + 4 * i, kb, fl);
+                    const Op fa = st_frag<ND_FT>(st, w + 4 * i, kb, fl);
                     const int ai = 2 * half + i;
 #pragma unroll
                     for (int nt = 0; nt < 8; ++nt) accx[ai][nt] = VPC_MFMA_BF(fa, fb[nt], accx[ai][nt]);
@@ -689,40 +632,40 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
             }
         };
         round_x(std::integral_constant<int, 0>{});
-        ND_BARRIER();  // B3
+        VPC_LDS_BARRIER();  // B3
         // ---------------- R1b: the log-variance head (g2 stays in slots 8-15)
 #pragma unroll
-        for (int kb = 0; kb < DT / 2; ++kb) nd_st_op(st, r, 0, kb, qq, Gb[DT / 2 + kb]);
-        ND_BARRIER();  // B4
+        for (int kb = 0; kb < DT / 2; ++kb) st_op<true, ND_FT>(st, r, 0, kb, qq, Gb[DT / 2 + kb]);
+        VPC_LDS_BARRIER();  // B4
         round_x(std::integral_constant<int, 1>{});
         launder(cc, qq);
         VPC_CUT();
-        NSTP(7);
+        VPC_STAMP(7);
         // ---------------- dg2 = ELU'(g2) * (Wx^T G)
         Op dg2b[4];
         nd_layer_T<128, DT, ND_HT>(Wx, Gb, fl, [&](int mt, f32x4 a0, f32x4 a1) {
-            dg2b[mt >> 1] = nd_pack2(elu_gate(a0, g2b[mt >> 1], 0), elu_gate(a1, g2b[mt >> 1], 1));
+            dg2b[mt >> 1] = pack2(elu_gate(a0, g2b[mt >> 1], 0), elu_gate(a1, g2b[mt >> 1], 1));
         });
         launder(cc, qq);
         VPC_CUT();
-        NSTP(8);
+        VPC_STAMP(8);
         Op g1b[4];
         make_g1(g1b);
         launder(cc, qq);
-        ND_BARRIER();  // B5: every wave is past the reads of R1b
+        VPC_LDS_BARRIER();  // B5: every wave is past the reads of R1b
         // ---------------- R2: dW2 = dg2^T g1, db2   (owner: wave w -> out tiles 2 w, 2 w + 1)
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) { nd_st_op(st, r, 0, kb, qq, dg2b[kb]); nd_st_op(st, r, 8, kb, qq, g1b[kb]); }
-        nd_st_op<false>(st, r, 24, 0, qq, zb);  // (R3's second operand: slot 24 is read by nobody until then)
-        ND_BARRIER();  // B6
+        for (int kb = 0; kb < 4; ++kb) { st_op<true, ND_FT>(st, r, 0, kb, qq, dg2b[kb]); st_op<true, ND_FT>(st, r, 8, kb, qq, g1b[kb]); }
+        st_op<false, ND_FT>(st, r, 24, 0, qq, zb);  // (R3's second operand: slot 24 is read by nobody until then)
+        VPC_LDS_BARRIER();  // B6
 #pragma unroll
         for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
             Op fb[8];
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) fb[nt] = nd_st_frag(st, 8 + nt, kb, fl);
+            for (int nt = 0; nt < 8; ++nt) fb[nt] = st_frag<ND_FT>(st, 8 + nt, kb, fl);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const Op fa = nd_st_frag(st, 2 * w + i, kb, fl);
+                const Op fa = st_frag<ND_FT>(st, 2 * w + i, kb, fl);
 #pragma unroll
                 for (int nt = 0; nt < 8; ++nt) acc2[i][nt] = VPC_MFMA_BF(fa, fb[nt], acc2[i][nt]);
                 accb = VPC_MFMA_BF(fa, sel_col(NB_B2 + i, cc), accb);
@@ -730,31 +673,31 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         }
         launder(cc, qq);
         VPC_CUT();
-        NSTP(9);
+        VPC_STAMP(9);
         // ---------------- dg1 = ELU'(g1) * (W2^T dg2);  dz = W1^T dg1
         Op dg1b[4];
         nd_layer_T<128, 4, ND_HT>(W2, dg2b, fl, [&](int mt, f32x4 a0, f32x4 a1) {
-            dg1b[mt >> 1] = nd_pack2(elu_gate(a0, g1b[mt >> 1], 0), elu_gate(a1, g1b[mt >> 1], 1));
+            dg1b[mt >> 1] = pack2(elu_gate(a0, g1b[mt >> 1], 0), elu_gate(a1, g1b[mt >> 1], 1));
         });
         f32x4 dz = zero4();
         nd_layer_T<32, 4, 1>(W1, dg1b, fl, [&](int, f32x4 a0, f32x4) { dz = a0; });
         launder(cc, qq);
-        NSTP(10);
+        VPC_STAMP(10);
         // ---------------- R3: dW1 = dg1^T z, db1.  dg1 goes to slots 16-23, which R2 does not read: no barrier in front of the writes
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) nd_st_op(st, r, 16, kb, qq, dg1b[kb]);
-        ND_BARRIER();  // B8
+        for (int kb = 0; kb < 4; ++kb) st_op<true, ND_FT>(st, r, 16, kb, qq, dg1b[kb]);
+        VPC_LDS_BARRIER();  // B8
 #pragma unroll
         for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
-            const Op fb = nd_st_frag(st, 24, kb, fl);
+            const Op fb = st_frag<ND_FT>(st, 24, kb, fl);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const Op fa = nd_st_frag(st, 16 + 2 * w + i, kb, fl);
+                const Op fa = st_frag<ND_FT>(st, 16 + 2 * w + i, kb, fl);
                 acc1[i] = VPC_MFMA_BF(fa, fb, acc1[i]);
                 accb = VPC_MFMA_BF(fa, sel_col(NB_B1 + i, cc), accb);
             }
         }
-        NSTP(11);
+        VPC_STAMP(11);
         // the dz exchange lives in the dwords of slots 0-15 (all reads of R2 are behind B8): no barrier in front of the writes either
         {
             float* dzx = st + nd_dzx(r);
@@ -770,7 +713,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
             *reinterpret_cast<f32x4*>(dzx + 4 * qq) = dm;
             *reinterpret_cast<f32x4*>(dzx + 16 + 4 * qq) = dl;
         }
-        ND_BARRIER();  // B10
+        VPC_LDS_BARRIER();  // B10
         // ---------------- sum over the K replicas (nm_sample_bwd) + the analytic KL terms and their gradients (VAE.py:2441-2452):
         // wave w takes the data rows w, w + 4, ...; lane = (half of the replicas, mean | logvar, latent)
         for (int ebl = w; ebl < a.nb; ebl += ND_WAVES) {
@@ -805,7 +748,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
             }
         }
         // (no barrier: the next tile's inputs land behind the exchange area, and whoever stores them is past B10)
-        NSTP(12);
+        VPC_STAMP(12);
     }
 
     // ---------------- partial block of the workgroup (register-major, coalesced) and its statistics
@@ -860,7 +803,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmdec_kernel(NmdArgs a) {
         a.stat_part[(long)blockIdx.x * ND_NSTAT + threadIdx.x] =
             (red[threadIdx.x] + red[ND_NSTAT + threadIdx.x]) + (red[2 * ND_NSTAT + threadIdx.x] + red[3 * ND_NSTAT + threadIdx.x]);
 #ifdef VPC_ABLATE
-    NSTP(13);
+    VPC_STAMP(13);
     if ((a.dbg & 64) && blockIdx.x == 7 && lane == 0 && (w == 0 || w == 3))
         printf("nmdec blk %d wave %d: prologue %llu | load+z %llu g1g2 %llu Y %llu pass1 %llu (lw write) B1+lse %llu pass2 %llu R1a+R1b %llu dg2 %llu "
                "B5+R2 %llu dg1+dz %llu B7+R3 %llu B9..epi %llu | partials %llu\n",
@@ -906,7 +849,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_fwd_kernel(NmeArgs a) {
         for (int kb = 0; kb < 4; ++kb) {
             const f32x4 t0 = *reinterpret_cast<const f32x4*>(a.xin + rc * 128 + 32 * kb + 4 * q);
             const f32x4 t1 = *reinterpret_cast<const f32x4*>(a.xin + rc * 128 + 32 * kb + 16 + 4 * q);
-            xb[kb] = nd_pack2(t0, t1);
+            xb[kb] = pack2(t0, t1);
         }
         Op h1b[4], h2b[4];
         nd_layer_fwd<128, 4, ND_HT>(W1, xb, c, q, [&](int mt, f32x4 a0, f32x4 a1) {
@@ -916,7 +859,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_fwd_kernel(NmeArgs a) {
                 *reinterpret_cast<f32x4*>(a.h1 + row * 128 + 16 * mt + 4 * q) = v0;
                 *reinterpret_cast<f32x4*>(a.h1 + row * 128 + 16 * mt + 16 + 4 * q) = v1;
             }
-            h1b[mt >> 1] = nd_pack2(v0, v1);
+            h1b[mt >> 1] = pack2(v0, v1);
         });
         nd_layer_fwd<128, 4, ND_HT>(W2, h1b, c, q, [&](int mt, f32x4 a0, f32x4 a1) {
             const f32x4 v0 = elu4(a0 + *reinterpret_cast<const f32x4*>(b2 + 16 * mt + 4 * q));
@@ -925,7 +868,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_fwd_kernel(NmeArgs a) {
                 *reinterpret_cast<f32x4*>(a.h2 + row * 128 + 16 * mt + 4 * q) = v0;
                 *reinterpret_cast<f32x4*>(a.h2 + row * 128 + 16 * mt + 16 + 4 * q) = v1;
             }
-            h2b[mt >> 1] = nd_pack2(v0, v1);
+            h2b[mt >> 1] = pack2(v0, v1);
         });
         nd_layer_fwd<128, 4, 2>(Wh, h2b, c, q, [&](int, f32x4 a0, f32x4 a1) {  // out rows 0 .. 2 L - 1 (two 16-row tiles; the rest is 0)
 #pragma unroll
@@ -1014,19 +957,19 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         launder(cc, qq);
         const int r = 16 * w + cc, fl = 16 * qq + cc;
         const long nxt = tile + gridDim.x;
-        const Op dhb[1] = {nd_pack2(d0, d1)};
+        const Op dhb[1] = {pack2(d0, d1)};
         lds_barrier();  // (the previous tile's last round is read)
         // ---- Rh: dWh = dht^T h2, dbh   [dht 0-1 | h2 8-15]
-        nd_st_op<true, NE_FT>(st, r, 0, 0, qq, dhb[0]);
+        st_op<true, NE_FT>(st, r, 0, 0, qq, dhb[0]);
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) nd_st_op<true, NE_FT>(st, r, 8, kb, qq, nd_pack2(hf2[2 * kb], hf2[2 * kb + 1]));
+        for (int kb = 0; kb < 4; ++kb) st_op<true, NE_FT>(st, r, 8, kb, qq, pack2(hf2[2 * kb], hf2[2 * kb + 1]));
         lds_barrier();
 #pragma unroll
         for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
-            const Op fa0 = nd_st_frag<NE_FT>(st, 0, kb, fl), fa1 = nd_st_frag<NE_FT>(st, 1, kb, fl);
+            const Op fa0 = st_frag<NE_FT>(st, 0, kb, fl), fa1 = st_frag<NE_FT>(st, 1, kb, fl);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const Op fb = nd_st_frag<NE_FT>(st, 8 + 2 * w + i, kb, fl);
+                const Op fb = st_frag<NE_FT>(st, 8 + 2 * w + i, kb, fl);
                 acch[i][0] = VPC_MFMA_BF(fa0, fb, acch[i][0]);
                 acch[i][1] = VPC_MFMA_BF(fa1, fb, acch[i][1]);
             }
@@ -1035,7 +978,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         // ---- dh2 = ELU'(h2) (Wh^T dht)
         Op dh2b[4];
         nd_layer_T<128, 1, ND_HT>(Wh, dhb, fl, [&](int mt, f32x4 a0, f32x4 a1) {
-            dh2b[mt >> 1] = nd_pack2(elu_gate_f32(a0, hf2[mt]), elu_gate_f32(a1, hf2[mt + 1]));
+            dh2b[mt >> 1] = pack2(elu_gate_f32(a0, hf2[mt]), elu_gate_f32(a1, hf2[mt + 1]));
         });
         launder(cc, qq);
         if (nxt < ntiles) { req_d(nxt); req(hf2, a.h2, nxt); }
@@ -1043,18 +986,18 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         // ---- R2: dW2 = dh2^T h1, db2   [dh2 0-7 | h1 8-15]
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-            nd_st_op<true, NE_FT>(st, r, 0, kb, qq, dh2b[kb]);
-            nd_st_op<true, NE_FT>(st, r, 8, kb, qq, nd_pack2(hf1[2 * kb], hf1[2 * kb + 1]));
+            st_op<true, NE_FT>(st, r, 0, kb, qq, dh2b[kb]);
+            st_op<true, NE_FT>(st, r, 8, kb, qq, pack2(hf1[2 * kb], hf1[2 * kb + 1]));
         }
         lds_barrier();
 #pragma unroll
         for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
             Op fb[8];
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) fb[nt] = nd_st_frag<NE_FT>(st, 8 + nt, kb, fl);
+            for (int nt = 0; nt < 8; ++nt) fb[nt] = st_frag<NE_FT>(st, 8 + nt, kb, fl);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const Op fa = nd_st_frag<NE_FT>(st, 2 * w + i, kb, fl);
+                const Op fa = st_frag<NE_FT>(st, 2 * w + i, kb, fl);
 #pragma unroll
                 for (int nt = 0; nt < 8; ++nt) acc2[i][nt] = VPC_MFMA_BF(fa, fb[nt], acc2[i][nt]);
                 accb = VPC_MFMA_BF(fa, sel_col(NBE_B2 + i, cc), accb);
@@ -1063,7 +1006,7 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         // ---- dh1 = ELU'(h1) (W2^T dh2)
         Op dh1b[4];
         nd_layer_T<128, 4, ND_HT>(W2, dh2b, fl, [&](int mt, f32x4 a0, f32x4 a1) {
-            dh1b[mt >> 1] = nd_pack2(elu_gate_f32(a0, hf1[mt]), elu_gate_f32(a1, hf1[mt + 1]));
+            dh1b[mt >> 1] = pack2(elu_gate_f32(a0, hf1[mt]), elu_gate_f32(a1, hf1[mt + 1]));
         });
         launder(cc, qq);
         if (nxt < ntiles) req(hf1, a.h1, nxt);
@@ -1071,8 +1014,8 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         // ---- R1: dW1 = dh1^T x, db1   [dh1 0-7 | x * mask 8-15]
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-            nd_st_op<true, NE_FT>(st, r, 0, kb, qq, dh1b[kb]);
-            nd_st_op<true, NE_FT>(st, r, 8, kb, qq, nd_pack2(hfx[2 * kb], hfx[2 * kb + 1]));
+            st_op<true, NE_FT>(st, r, 0, kb, qq, dh1b[kb]);
+            st_op<true, NE_FT>(st, r, 8, kb, qq, pack2(hfx[2 * kb], hfx[2 * kb + 1]));
         }
         if (nxt < ntiles) req(hfx, a.xin, nxt);
         lds_barrier();
@@ -1080,10 +1023,10 @@ __global__ __launch_bounds__(ND_THREADS) void nmenc_bwd_kernel(NmebArgs a) {
         for (int kb = 0; kb < ND_ROWS / 32; ++kb) {
             Op fb[8];
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) fb[nt] = nd_st_frag<NE_FT>(st, 8 + nt, kb, fl);
+            for (int nt = 0; nt < 8; ++nt) fb[nt] = st_frag<NE_FT>(st, 8 + nt, kb, fl);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const Op fa = nd_st_frag<NE_FT>(st, 2 * w + i, kb, fl);
+                const Op fa = st_frag<NE_FT>(st, 2 * w + i, kb, fl);
 #pragma unroll
                 for (int nt = 0; nt < 8; ++nt) acc1[i][nt] = VPC_MFMA_BF(fa, fb[nt], acc1[i][nt]);
                 accb = VPC_MFMA_BF(fa, sel_col(NBE_B1 + i, cc), accb);
@@ -1272,13 +1215,13 @@ int vpc_nmdec_build_indices(int d, int L, int hid, int* pack_idx, int* grad_idx,
         const int e0 = 2 * d, oWe1 = e0, obe1 = oWe1 + hid * d, oWe2 = obe1 + hid, obe2 = oWe2 + hid * hid, oWh = obe2 + hid,
                   obh = oWh + 2 * L * hid, I0 = NdImg::total;
         for (int r = 0; r < hid; ++r) {
-            for (int f = 0; f < d; ++f) pack_idx[oWe1 + r * d + f] = 2 * (I0 + NeImg::oW1) + nd_elem<128>(r, f);
+            for (int f = 0; f < d; ++f) pack_idx[oWe1 + r * d + f] = 2 * (I0 + NeImg::oW1) + c_elem<128>(r, f);
             pack_idx[obe1 + r] = -(I0 + NeImg::ob1 + r + 1);
-            for (int f = 0; f < hid; ++f) pack_idx[oWe2 + r * hid + f] = 2 * (I0 + NeImg::oW2) + nd_elem<128>(r, f);
+            for (int f = 0; f < hid; ++f) pack_idx[oWe2 + r * hid + f] = 2 * (I0 + NeImg::oW2) + c_elem<128>(r, f);
             pack_idx[obe2 + r] = -(I0 + NeImg::ob2 + r + 1);
         }
         for (int r = 0; r < 2 * L; ++r) {
-            for (int f = 0; f < hid; ++f) pack_idx[oWh + r * hid + f] = 2 * (I0 + NeImg::oWh) + nd_elem<128>(r, f);
+            for (int f = 0; f < hid; ++f) pack_idx[oWh + r * hid + f] = 2 * (I0 + NeImg::oWh) + c_elem<128>(r, f);
             pack_idx[obh + r] = -(I0 + NeImg::obh + r + 1);
         }
     }
@@ -1288,13 +1231,13 @@ int vpc_nmdec_build_indices(int d, int L, int hid, int* pack_idx, int* grad_idx,
     for (int r = 0; r < hid; ++r) {  // out feature r of the two hidden layers: tile mt = r >> 4 owned by wave mt >> 1
         const int mt = r >> 4, w = mt >> 1, i = mt & 1, q = (r >> 2) & 3, j = r & 3;
         for (int f = 0; f < L; ++f) {
-            pack_idx[oWd1 + r * L + f] = 2 * NdImg::oW1 + nd_elem<32>(r, f);
+            pack_idx[oWd1 + r * L + f] = 2 * NdImg::oW1 + c_elem<32>(r, f);
             grad_idx[oWd1 + r * L + f] = pos(R_1 + 4 * i + j, w, q, f);
         }
         pack_idx[obd1 + r] = -(NdImg::ob1 + r + 1);
         grad_idx[obd1 + r] = pos(R_B + j, w, q, NB_B1 + i);
         for (int f = 0; f < hid; ++f) {
-            pack_idx[oWd2 + r * hid + f] = 2 * NdImg::oW2 + nd_elem<128>(r, f);
+            pack_idx[oWd2 + r * hid + f] = 2 * NdImg::oW2 + c_elem<128>(r, f);
             grad_idx[oWd2 + r * hid + f] = pos(R_2 + (8 * i + (f >> 4)) * 4 + j, w, q, f & 15);
         }
         pack_idx[obd2 + r] = -(NdImg::ob2 + r + 1);
@@ -1303,7 +1246,7 @@ int vpc_nmdec_build_indices(int d, int L, int hid, int* pack_idx, int* grad_idx,
     for (int r = 0; r < 2 * d; ++r) {  // head rows: tile t = r >> 4; half = t / 8, owner wave (t & 7) & 3, slot i = (t & 7) >> 2
         const int t = r >> 4, half = t >> 3, tt = t & 7, w = tt & 3, i = tt >> 2, ai = 2 * half + i, q = (r >> 2) & 3, j = r & 3;
         for (int f = 0; f < hid; ++f) {
-            pack_idx[oWx + r * hid + f] = 2 * NdImg::oWx + nd_elem<128>(r, f);
+            pack_idx[oWx + r * hid + f] = 2 * NdImg::oWx + c_elem<128>(r, f);
             grad_idx[oWx + r * hid + f] = pos(R_X + (8 * ai + (f >> 4)) * 4 + j, w, q, f & 15);
         }
         pack_idx[obx + r] = -(NdImg::obx + r + 1);

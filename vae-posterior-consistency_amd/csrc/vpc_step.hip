@@ -23,7 +23,7 @@
 // (dz and the KL seeds need no barrier - dgrads read only the weight image - so dml is known before R3 is staged.)
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
-#include "vpc_bf16.h"
+#include "vpc_bf16c.h"
 #include "vpc_dec_args.h"
 #include <climits>
 #include <cstring>
@@ -31,22 +31,7 @@
 
 namespace vpc {
 
-// ------------------------------------------------------------------------------------------------ compact bf16 image
-// Layer image: `rows` rows of KP bf16 (KP = inputs padded to 32); the 16-byte slot pi = 4 kb + q of a row holds the k-slots
-// (kb, q, 0..7) = input features 32 kb + 16 (j >> 2) + 4 q + (j & 3) (vpc_bf16.h), pi XOR-swizzled with a key of the row.
-// The key makes the forward fragment read (ds_read_b128: 16 rows x one slot per lane group) conflict-free for every row
-// pitch - rows of 128 / 64 bytes share a 256-byte bank row in pairs / fours, so the key is taken from the row bits above
-// that - and, for 256-byte rows, spreads the 8 consecutive rows of a transposed read (ds_read_b64_tr_b16) over four slot
-// groups (2-way instead of 4-way conflicts).
-template <int KP>
-VPC_HD constexpr int c_key(int row) {
-    return KP == 128 ? ((((row >> 1) & 3) << 2) | (((row >> 3) & 1) << 1) | (row & 1))
-                     : ((row / (128 / KP)) & (KP / 8 - 1));
-}
-template <int KP>
-VPC_HD constexpr int c_elem(int row, int f) {  // u16 index of (row, input feature f) inside the layer image
-    return row * KP + (((4 * (f >> 5) + ((f >> 2) & 3)) ^ c_key<KP>(row)) << 3) + 4 * ((f >> 4) & 1) + (f & 3);
-}
+// (compact bf16 image, its fragments and the operand staging: vpc_bf16c.h)
 // dword offsets of the layers inside the image: [W1 112 x 128][b1 128 fp32][W2 64 x 128][W3 32 x 64][W4 64 x 32][W5 112 x 64]
 // [W6 128 x 128]
 struct StepImg {
@@ -61,8 +46,6 @@ constexpr int ST2_FT = 6;
 static_assert((TILE_ROWS / 8) * ST2_FT * 64 <= StepImg::total - StepImg::oW4, "second staging area");
 static_assert(STEP_LDS <= 163840, "LDS budget");
 
-typedef bf16x8 Op;  // one MFMA operand: 8 k-slots per lane
-
 #ifndef VPC_STEP_PREFETCH
 #define VPC_STEP_PREFETCH 0  // 1: request a tile's inputs one tile ahead (see request_tile); measured, see profiles/r03_notes.md
 #endif
@@ -74,28 +57,6 @@ constexpr bool AHEAD = VPC_STEP_AHEAD != 0;
 
 // (lds_barrier(), vpc_device.h: s_waitcnt lgkmcnt(0); s_barrier - no vmcnt(0) as __syncthreads() carries)
 
-__device__ __forceinline__ Op pack2(f32x4 t0, f32x4 t1) {
-    const u32x4 h = {pk_bf16(t0[0], t0[1]), pk_bf16(t0[2], t0[3]), pk_bf16(t1[0], t1[1]), pk_bf16(t1[2], t1[3])};
-    return __builtin_bit_cast(Op, h);
-}
-// forward A fragment: weight rows 16 mt + m, k-block kb
-template <int KP>
-__device__ __forceinline__ Op c_wfrag(const float* W, int mt, int kb, int m, int q) {
-    return __builtin_bit_cast(Op, *reinterpret_cast<const f32x4*>(W + (16 * mt + m) * (KP / 2) + 4 * ((4 * kb + q) ^ c_key<KP>(m))));
-}
-// transposed A fragment (dgrad): in-feature tile mt, k-block kb of the layer's OUT features (rows of the image)
-template <int KP, bool SECOND>
-__device__ __forceinline__ Op c_wfrag_T(const float* W, int mt, int kb, int lane) {
-    const int q = lane >> 4, rr = (lane >> 2) & 3, pp = lane & 3;
-    const int r0 = 32 * kb + 4 * q + rr, r1 = r0 + 16;
-    const int pi = 4 * (mt >> 1) + pp, e = 2 * (mt & 1);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x4 zz = {0, 0, 0, 0};
-    const s16x4 h0 = ds_tr16(W + r0 * (KP / 2) + 4 * (pi ^ c_key<KP>(r0)) + e);
-    const s16x4 h1 = SECOND ? ds_tr16(W + r1 * (KP / 2) + 4 * (pi ^ c_key<KP>(r1)) + e) : zz;
-    const s16x8 h = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    return __builtin_bit_cast(Op, h);
-}
 // forward layer: NT out tiles, KB k-blocks.  ONE set of fragment registers: the fragments of tile mt + 1 are requested right
 // behind the MFMAs of tile mt (which have read theirs at issue) and arrive under the sink's VALU and the partner wave's work.
 // (A second set - next tile requested before the MFMAs - costs 4 KB registers per layer call, which this kernel does not have.)
@@ -168,24 +129,6 @@ __device__ __forceinline__ void c_layer_T(const float* W, const Op (&in)[KB], in
         sink(mt, acc);
     }
 }
-// ---- staging (bf_stage layout of vpc_bf16.h, FT = 15): operand of NT tiles whose first tile sits in slot `slot0`
-template <int NT, int FT = ST_FT>
-__device__ __forceinline__ void st_op(float* st, int row, int slot0, int kb, int q, Op op) {
-    const u32x4 h = __builtin_bit_cast(u32x4, op);
-    const int o0 = bf_stage_off<FT>(row, slot0 + 2 * kb, q);
-    *reinterpret_cast<u32x2*>(st + o0) = u32x2{h[0], h[1]};
-    if (2 * kb + 1 < NT) *reinterpret_cast<u32x2*>(st + o0 + 64) = u32x2{h[2], h[3]};
-}
-template <int FT = ST_FT>
-__device__ __forceinline__ Op st_frag(const float* st, int slot, int kb, int lane) {
-    const int g = lane >> 4, rr = (lane >> 2) & 3, pp = lane & 3;
-    const int off = bf_stage_off<FT>(32 * kb + 4 * g + rr, slot, pp);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x4 h0 = ds_tr16(st + off), h1 = ds_tr16(st + off + 128 * FT);
-    const s16x8 h = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    return __builtin_bit_cast(Op, h);
-}
-
 struct StepArgs {
     const float* x;
     const float* img;
@@ -204,14 +147,6 @@ struct StepArgs {
     int stagger;  // start delay of workgroup group (blockIdx.x / 8) % 8, in units of 64 clocks per group (0 = none)
     int dbg;  // diagnostic build only (-DVPC_ABLATE): 64 = print the phase stamps of workgroup 100
 };
-
-#ifdef VPC_ABLATE
-#define STP(i) VPC_STAMP(i)
-#define LDS_BARRIER() do { if (!(a.dbg & 2)) lds_barrier(); } while (0)   // VPC_DEBUG & 2: timing without barriers (wrong results)
-#else
-#define STP(i) do {} while (0)
-#define LDS_BARRIER() lds_barrier()
-#endif
 
 // Two sweeps over the workgroup's tiles, so that only HALF of the gradient accumulators is live at any time (all 100 of them
 // beside the working set of the decoder phase do not fit 256 registers: hipcc then parks the accumulators in scratch and
@@ -392,7 +327,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
         if (!AHEAD) stage_issue(tile, 0, with_eps);
 #pragma unroll
         for (int hc = 0; hc < 2; ++hc) {
-            LDS_BARRIER();  // the staging area is free: every wave is past its reads of the previous round / half
+            VPC_LDS_BARRIER();  // the staging area is free: every wave is past its reads of the previous round / half
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int gi = (4 * w + k) * 64 + lane, row = gi >> 4, gc = gi & 15;
@@ -406,10 +341,10 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                 if (with_eps && hc == 0) *reinterpret_cast<f32x4*>(st + SE0 + 4 * gi) = ge;
             }
 #ifdef VPC_ABLATE
-            if (hc == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); STP(15); }
+            if (hc == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); VPC_STAMP(15); }
 #endif
             if (hc == 0) stage_issue(tile, 1, with_eps);  // the second half's loads fly while the first half is read
-            LDS_BARRIER();
+            VPC_LDS_BARRIER();
             const int lr = 16 * w + c;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -466,7 +401,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
         for (int t = 0; t < DT; ++t) mw1[t] = 0u;
     }
     lds_barrier();
-    STP(0);
+    VPC_STAMP(0);
 
     // ============================================================================================================ sweep 1
     {
@@ -505,7 +440,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                 make_xb(xr, mw0, xb, qq);
 #ifdef VPC_ABLATE
                 asm volatile("" ::"v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]));
-                STP(14);
+                VPC_STAMP(14);
 #endif
                 if (two) {
                     Op xbp[KB1];
@@ -521,7 +456,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
             if (!(a.dbg & 8))
 #endif
             if (!PREFETCH && !(staged_in && AHEAD) && tile + (int)gridDim.x < a.ntiles) tv = touch(tile + (int)gridDim.x);
-            STP(1);
+            VPC_STAMP(1);
             for (int p = 0; p < a.npass; ++p) {
                 asm volatile("" ::: "memory");
                 launder(cc, qq);
@@ -565,13 +500,13 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                         });
                     }
                     launder(cc, qq);
-                    STP(2);
+                    VPC_STAMP(2);
                     VPC_CUT();
                     // ---------------- output tiles: forward, loss terms, d / d pre-activation.  dpre goes straight into its R1
                     // staging slots (tile mt -> slot mt, 8 bytes per lane and tile) instead of growing to 16 registers across
                     // the loop; the dgrad below reads the lane's own chunks back.  The barrier: every wave is past the reads of
                     // the previous staging round.
-                    LDS_BARRIER();
+                    VPC_LDS_BARRIER();
                     {
                         typedef float f32x2 __attribute__((ext_vector_type(2)));
                         constexpr float NLOG2E = -1.4426950408889634f;
@@ -622,7 +557,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                         const float sa = sa2[0] + sa2[1], se = se2[0] + se2[1];
                         if (p == 0) { S_A0 += sa; S_E0 += se; } else { S_A1 += sa; }
                     }
-                    STP(3);
+                    VPC_STAMP(3);
                     VPC_CUT();
                     launder(cc, qq);
                     // x and the mask words are dead after the last pass's output tiles: the next tile's are requested now
@@ -630,29 +565,29 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                     if (staged_in && AHEAD && p + 1 == a.npass && tile + (int)gridDim.x < a.ntiles) stage_issue(tile + (int)gridDim.x, 0, true);
                     // ---------------- R1: dW6~ += dpre^T g2   (owner: wave w -> out tile w, all 7 in tiles)
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) st_op<H1T>(st, lrow, 8, kb, qq, g2b[kb]);
-                    LDS_BARRIER();
+                    for (int kb = 0; kb < 4; ++kb) st_op<false, ST_FT, H1T>(st, lrow, 8, kb, qq, g2b[kb]);
+                    VPC_LDS_BARRIER();
                     // (all fragment reads of a k-block are in flight before its first MFMA: issued one by one in front of their
                     // MFMA every product waits a full LDS round trip - the rounds were 4-6 k cycles of that)
                     if (own6) {
 #pragma unroll
                         for (int kb = 0; kb < TILE_ROWS / 32; ++kb) {
                             __builtin_amdgcn_sched_barrier(0);
-                            const Op fa = st_frag(st, w, kb, 16 * qq + cc);
+                            const Op fa = st_frag<ST_FT>(st, w, kb, 16 * qq + cc);
                             Op fb[4];  // in tiles 0-3, then 4-6: two batches of reads (registers)
 #pragma unroll
-                            for (int nt = 0; nt < 4; ++nt) fb[nt] = st_frag(st, 8 + nt, kb, 16 * qq + cc);
+                            for (int nt = 0; nt < 4; ++nt) fb[nt] = st_frag<ST_FT>(st, 8 + nt, kb, 16 * qq + cc);
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int nt = 0; nt < 4; ++nt) acc6[nt] = VPC_MFMA_BF(fa, fb[nt], acc6[nt]);
 #pragma unroll
-                            for (int nt = 4; nt < H1T; ++nt) fb[nt - 4] = st_frag(st, 8 + nt, kb, 16 * qq + cc);
+                            for (int nt = 4; nt < H1T; ++nt) fb[nt - 4] = st_frag<ST_FT>(st, 8 + nt, kb, 16 * qq + cc);
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int nt = 4; nt < H1T; ++nt) acc6[nt] = VPC_MFMA_BF(fa, fb[nt - 4], acc6[nt]);
                         }
                     }
-                    STP(4);
+                    VPC_STAMP(4);
                     VPC_CUT();
                     launder(cc, qq);
                     // ---------------- dg2 = relu'(g2) * (W6~^T dpre): B operands = the lane's own dpre chunks, back from their
@@ -684,34 +619,34 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                             hprev = h;
                         });
                     }
-                    STP(5);
+                    VPC_STAMP(5);
                     VPC_CUT();
                     launder(cc, qq);
                     // ---------------- R2: dW5~ += dg2^T g1   (owner: wave w -> in tile w & 3 of out tiles 4 (w >> 2) .. + 3)
                     Op g1b[2];  // (also the ReLU gate of dg1 below: a packed relu output is non-zero where the unit is active)
                     make_g1(g1b);
-                    LDS_BARRIER();
+                    VPC_LDS_BARRIER();
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) st_op<H1T>(st, lrow, 0, kb, qq, dg2b[kb]);
+                    for (int kb = 0; kb < 4; ++kb) st_op<false, ST_FT, H1T>(st, lrow, 0, kb, qq, dg2b[kb]);
 #pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) st_op<H2T>(st, lrow, 8, kb, qq, g1b[kb]);
-                    LDS_BARRIER();
+                    for (int kb = 0; kb < 2; ++kb) st_op<true, ST_FT>(st, lrow, 8, kb, qq, g1b[kb]);
+                    VPC_LDS_BARRIER();
                     {
                         const int nt5 = w & 3, mt5 = 4 * (w >> 2);
 #pragma unroll
                         for (int kb = 0; kb < TILE_ROWS / 32; ++kb) {
                             __builtin_amdgcn_sched_barrier(0);
-                            const Op fb = st_frag(st, 8 + nt5, kb, 16 * qq + cc);
+                            const Op fb = st_frag<ST_FT>(st, 8 + nt5, kb, 16 * qq + cc);
                             Op fa[4];
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) fa[i] = st_frag(st, (i < 3 || w < 4) ? mt5 + i : mt5, kb, 16 * qq + cc);
+                            for (int i = 0; i < 4; ++i) fa[i] = st_frag<ST_FT>(st, (i < 3 || w < 4) ? mt5 + i : mt5, kb, 16 * qq + cc);
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
                                 if (i < 3 || w < 4) acc5[i] = VPC_MFMA_BF(fa[i], fb, acc5[i]);
                         }
                     }
-                    STP(6);
+                    VPC_STAMP(6);
                     VPC_CUT();
                     launder(cc, qq);
                     // ---------------- dg1 = relu'(g1) * (W5~^T dg2);  dz = W4~^T dg1
@@ -727,12 +662,12 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                         c_layer_T<32, 2, 1, H2T>(W4, dg1b, 16 * qq + cc, [&](int, f32x4 acc) { dz = acc; });
                     }
                     // R3's decoder operands (the seeds and h2 follow below)
-                    LDS_BARRIER();
+                    VPC_LDS_BARRIER();
 #pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) st_op<H2T>(st, lrow, 0, kb, qq, dg1b[kb]);
-                    st_op<1>(st, lrow, 8, 0, qq, zb);
+                    for (int kb = 0; kb < 2; ++kb) st_op<true, ST_FT>(st, lrow, 0, kb, qq, dg1b[kb]);
+                    st_op<false, ST_FT>(st, lrow, 8, 0, qq, zb);
                 }
-                STP(7);
+                VPC_STAMP(7);
                 // ---------------- KL terms, their seeds, total seeds on (mean | logvar)
                 {
                     f32x4 dmu, dlv;
@@ -793,13 +728,13 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                 // the next pass's (or the next tile's first pass's) eps arrives under this round
                 if (two && p == 0) e = ld_lat(a.eps[1], row0);  // (a 4-line read per wave; the staged copy is gone by now)
                 else if (PREFETCH && tile + (int)gridDim.x < a.ntiles) e = ld_lat(a.eps[0], row0 + (long)gridDim.x * TILE_ROWS);
-                LDS_BARRIER();
+                VPC_LDS_BARRIER();
                 if (own4) {
                     Op fa4[TILE_ROWS / 32], fb4[TILE_ROWS / 32];
 #pragma unroll
                     for (int kb = 0; kb < TILE_ROWS / 32; ++kb) {
-                        fa4[kb] = st_frag(st, w, kb, 16 * qq + cc);
-                        fb4[kb] = st_frag(st, 8, kb, 16 * qq + cc);
+                        fa4[kb] = st_frag<ST_FT>(st, w, kb, 16 * qq + cc);
+                        fb4[kb] = st_frag<ST_FT>(st, 8, kb, 16 * qq + cc);
                     }
 #pragma unroll
                     for (int kb = 0; kb < TILE_ROWS / 32; ++kb) acc4 = VPC_MFMA_BF(fa4[kb], fb4[kb], acc4);
@@ -812,7 +747,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
 #pragma unroll
                     for (int t = 0; t < DT; ++t) { const uint32_t u = mw0[t]; mw0[t] = mw1[t]; mw1[t] = u; }
                 }
-                STP(8);
+                VPC_STAMP(8);
             }
         }
         // sweep 2's first tile is requested before this sweep's partial-block stores
@@ -843,14 +778,14 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
             const float v = wave_sum_dpp(s[i]);
             if (lane == 0) red[w * LOSS_TERMS + i] = v;
         }
-        LDS_BARRIER();
+        VPC_LDS_BARRIER();
         if (threadIdx.x < LOSS_TERMS) {
             double t = 0.0;
             for (int k = 0; k < WAVES; ++k) t += (double)red[k * LOSS_TERMS + threadIdx.x];
             a.loss_part[(long)blockIdx.x * LOSS_TERMS + threadIdx.x] = t;
         }
     }
-    STP(9);
+    VPC_STAMP(9);
     // ============================================================================================================ sweep 2
     {
         f32x4 acc1[H1T], acc2[H2T], accb = zero4(), acc3 = zero4();
@@ -905,7 +840,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                     request_tile(nt, two);
                     if (two) { s0 = *ws_ptr(nt, 1); s1 = *ws_ptr(nt, 0); } else { s0 = *ws_ptr(nt, 0); }
                 }
-                STP(10);
+                VPC_STAMP(10);
                 launder(cc, qq);
                 // ---------------- dh2 = relu'(h2) * (W3~^T dml)
                 Op dh2b[2];
@@ -921,15 +856,15 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                 }
                 // ---------------- R4: dW2~ += dh2^T h1   (owner: wave w < 7 -> in tile w, all 4 out tiles);  dW3~ += dml^T h2 (wave w ->
                 // out tile w >> 2, in tile w & 3) from the second staging area
-                LDS_BARRIER();
+                VPC_LDS_BARRIER();
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb) st_op<H2T>(st, lrow, 0, kb, qq, dh2b[kb]);
+                for (int kb = 0; kb < 2; ++kb) st_op<true, ST_FT>(st, lrow, 0, kb, qq, dh2b[kb]);
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) st_op<H1T>(st, lrow, 8, kb, qq, h1b[kb]);
-                st_op<2, ST2_FT>(st2, lrow, 0, 0, qq, dmlb);
+                for (int kb = 0; kb < 4; ++kb) st_op<false, ST_FT, H1T>(st, lrow, 8, kb, qq, h1b[kb]);
+                st_op<true, ST2_FT>(st2, lrow, 0, 0, qq, dmlb);
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb) st_op<H2T, ST2_FT>(st2, lrow, 2, kb, qq, h2b[kb]);
-                LDS_BARRIER();
+                for (int kb = 0; kb < 2; ++kb) st_op<true, ST2_FT>(st2, lrow, 2, kb, qq, h2b[kb]);
+                VPC_LDS_BARRIER();
                 {
                     Op fa3[TILE_ROWS / 32], fb3[TILE_ROWS / 32];
 #pragma unroll
@@ -944,16 +879,16 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
 #pragma unroll
                     for (int kb = 0; kb < TILE_ROWS / 32; ++kb) {
                         __builtin_amdgcn_sched_barrier(0);
-                        const Op fb = st_frag(st, 8 + w, kb, 16 * qq + cc);
+                        const Op fb = st_frag<ST_FT>(st, 8 + w, kb, 16 * qq + cc);
                         Op fa[H2T];
 #pragma unroll
-                        for (int mt = 0; mt < H2T; ++mt) fa[mt] = st_frag(st, mt, kb, 16 * qq + cc);
+                        for (int mt = 0; mt < H2T; ++mt) fa[mt] = st_frag<ST_FT>(st, mt, kb, 16 * qq + cc);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int mt = 0; mt < H2T; ++mt) acc2[mt] = VPC_MFMA_BF(fa[mt], fb, acc2[mt]);
                     }
                 }
-                STP(11);
+                VPC_STAMP(11);
                 VPC_CUT();
                 launder(cc, qq);
                 // ---------------- dh1 = relu'(h1) * (W2~^T dh2)
@@ -970,20 +905,20 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
                 }
                 // ---------------- R5: dW1 += dh1^T (x * mask)  (owner: wave w -> in tile w, all 7 out tiles);  db1 += dh1^T 1
                 // (wave w < 7 -> out tile w)
-                LDS_BARRIER();
+                VPC_LDS_BARRIER();
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) st_op<H1T>(st, lrow, 0, kb, qq, dh1b[kb]);
+                for (int kb = 0; kb < 4; ++kb) st_op<false, ST_FT, H1T>(st, lrow, 0, kb, qq, dh1b[kb]);
 #pragma unroll
-                for (int kb = 0; kb < KB1; ++kb) st_op<DT>(st, lrow, 7, kb, qq, xb[kb]);
-                LDS_BARRIER();
+                for (int kb = 0; kb < KB1; ++kb) st_op<false, ST_FT, DT>(st, lrow, 7, kb, qq, xb[kb]);
+                VPC_LDS_BARRIER();
 #pragma unroll
                 for (int kb = 0; kb < TILE_ROWS / 32; ++kb) {
                     __builtin_amdgcn_sched_barrier(0);
-                    const Op fb = st_frag(st, 7 + w, kb, 16 * qq + cc);
-                    const Op fw = st_frag(st, own2 ? w : 0, kb, 16 * qq + cc);  // dh1 tile w once more, for db1
+                    const Op fb = st_frag<ST_FT>(st, 7 + w, kb, 16 * qq + cc);
+                    const Op fw = st_frag<ST_FT>(st, own2 ? w : 0, kb, 16 * qq + cc);  // dh1 tile w once more, for db1
                     Op fa[H1T];
 #pragma unroll
-                    for (int mt = 0; mt < H1T; ++mt) fa[mt] = st_frag(st, mt, kb, 16 * qq + cc);
+                    for (int mt = 0; mt < H1T; ++mt) fa[mt] = st_frag<ST_FT>(st, mt, kb, 16 * qq + cc);
                     __builtin_amdgcn_sched_barrier(0);
                     if (own2) accb = VPC_MFMA_BF(fw, ones, accb);
 #pragma unroll
@@ -994,7 +929,7 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
 #pragma unroll
                     for (int t = 0; t < DT; ++t) { const uint32_t u = mw0[t]; mw0[t] = mw1[t]; mw1[t] = u; }
                 }
-                STP(12);
+                VPC_STAMP(12);
             }
         }
         float* part = a.partE + (long)blockIdx.x * ENC_PART + (long)w * GREGS * 64 + lane;
@@ -1016,25 +951,26 @@ __global__ __launch_bounds__(THREADS) void step_bf16_kernel(StepArgs a) {
         if (w == 7 && lane < 16) a.partE[(long)blockIdx.x * ENC_PART + WAVES * GREGS * 64 + 112 + lane] = 0.f;
     }
 #ifdef VPC_ABLATE
-    STP(13);
+    VPC_STAMP(13);
     if ((a.dbg & 64) && blockIdx.x == 100 && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) % 3 == 0)
         printf("step blk %d wave %d: half0 arrived %llu xwait(rest) %llu | prologue %llu E1 %llu g1g2 %llu out %llu R1 %llu dg2 %llu R2 %llu dg1+dz %llu KL+R3 %llu epi1 %llu | E2 %llu dh2+R4 %llu dh1+R5 %llu epi2 %llu\n",
                blockIdx.x, (int)(threadIdx.x >> 6), T[15], T[14], T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11], T[12], T[13]);
 #endif
 }
 
-static inline int row3c(int o, int L) { return o < L ? o : 16 + (o - L); }
-
 }  // namespace vpc
 
 using namespace vpc;
+
+// shapes of the fused step: obs_dim in (64, 128], a multiple of 4 (16-byte row loads)
+static bool step_shape_ok(int d, int L) { return d > 64 && d <= MAX_D && d % 4 == 0 && L >= 1 && L <= MAX_L; }
 
 // 1 when vpc_step_fused_bf16 is the form the library runs for this shape: obs_dim in (64, 128], obs_dim % 4 == 0, any batch (the
 // caller routes the smallest batches to vpc_step_small_f32 first).  Mid-size batches too: one 128-row tile per workgroup in ONE launch
 // beats the three small-shape launches (B = 8 192: 55 us against 69, B = 16 384: 58 against 97; profiles/r03_notes.md).
 // VPC_TILE=64 or VPC_STEP_FUSED=0 in the environment keep the three-kernel form (A/B runs, tests of those kernels).
 extern "C" int vpc_step_fused_applicable(long B, int d, int L, int npass) {
-    if (d <= 64 || d > MAX_D || d % 4 || L < 1 || L > MAX_L || npass < 1 || npass > 2 || B <= 0) return 0;
+    if (!step_shape_ok(d, L) || npass < 1 || npass > 2 || B <= 0) return 0;
     if (const char* e = getenv("VPC_STEP_FUSED")) {
         if (atoi(e) == 0) return 0;
     }
@@ -1050,7 +986,7 @@ extern "C" long vpc_step_workspace_floats(long B) {
 }
 
 extern "C" int vpc_step_layout_bf16(int d, int L, int* img_floats, int* lds_bytes) {
-    if (d <= 64 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (!step_shape_ok(d, L)) return VPC_ERR_SHAPE;
     if (img_floats) *img_floats = StepImg::total;
     if (lds_bytes) *lds_bytes = STEP_LDS;
     return VPC_OK;
@@ -1059,7 +995,7 @@ extern "C" int vpc_step_layout_bf16(int d, int L, int* img_floats, int* lds_byte
 // pack_idx_c[i] >= 0: u16 index of flat parameter i inside the compact image; < 0: dword index -(idx + 1) of a value that stays
 // fp32 (the layer-1 bias).  img_template_c: zeros + the constant ones of the bias chain.
 extern "C" int vpc_step_build_indices_bf16(int d, int L, int* pack_idx_c, float* img_template_c) {
-    if (d <= 64 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (!step_shape_ok(d, L)) return VPC_ERR_SHAPE;
     if (!pack_idx_c || !img_template_c) return VPC_ERR_ARG;
     const ParamOffsets po(d, L, d);
     std::memset(img_template_c, 0, sizeof(float) * (size_t)StepImg::total);
@@ -1078,7 +1014,7 @@ extern "C" int vpc_step_build_indices_bf16(int d, int L, int* pack_idx_c, float*
     }
     u[2 * StepImg::oW2 + c_elem<128>(pos2(H2), pos1(H1))] = ONE;
     for (int o = 0; o < 2 * L; ++o) {
-        const int pr = row3c(o, L);
+        const int pr = row3(o, L);
         for (int i = 0; i <= H2; ++i)
             pack_idx_c[(i < H2) ? po.w3 + o * H2 + i : po.b3 + o] = 2 * StepImg::oW3 + c_elem<64>(pr, pos2(i));
     }
@@ -1126,7 +1062,7 @@ extern "C" int vpc_step_fused_bf16(const float* x, const float* img_c, int npass
     if (!x || !img_c || !mask || !cA || !cE || !eps || !partE || !partD || !loss_partials || !workspace) return VPC_ERR_ARG;
     if (!aligned16(workspace)) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0) return VPC_ERR_ARG;
-    if (d <= 64 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (!step_shape_ok(d, L)) return VPC_ERR_SHAPE;
     if (!aligned16(x) || !aligned16(img_c)) return VPC_ERR_ARG;
     if (wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     StepArgs a{};

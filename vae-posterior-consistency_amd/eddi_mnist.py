@@ -9,7 +9,7 @@ constructor arguments, attributes, module construction order (same seed -> same 
 
     type_pars1, type_bias1, prior_mean, prior_std, pnp_encoder1.0.*, pnp_encoder2.{0,2,4,6}.*, seq_decoder.{0,2,4,6}.*
 
-The encoder is the point-net front-end at image width (csrc/vpc_eddiw.hip: folded per-feature affine + ReLU + mask-weighted
+The encoder is the point-net front-end at image width (vpc_eddiw_* of csrc/vpc_eddi.hip: folded per-feature affine + ReLU + mask-weighted
 sum over the d features, nothing of size B*d*(2+K) materialised) followed by the trunk K -> 500 -> 500 -> 200 -> 2L; the
 decoder is L -> 200 -> 500 -> 500 -> d with a Sigmoid.  The seven wide layers and the two narrow ones run on the generic fp32
 MFMA GEMMs (csrc/vpc_gemm.hip); the loss is the width-independent fused loss kernel K4 (vpc_loss_fwd_bwd), which has the
