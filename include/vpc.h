@@ -614,6 +614,29 @@ int vpc_ais_run(const float* x, const float* dec_img, const float* schedule, int
  * v [T-1][B][L] ~ N(0, 1) (:185), u [T-1][B] ~ U(0, 1) (:289). */
 int vpc_ais_draws(float* z0, float* v, float* u, long B, int L, int T, unsigned long long seed, void* stream);
 
+/* ---- the GEMM-backed AIS engine (csrc/vpc_aisg.hip) ------------------------------------------------------------------
+ * The same chain (AIS.py:155-217, 237-304) for every decoder the reference's ais_trajectory can run, which needs only
+ * model.decoder(z) -> (mean, logvar) (:125-140): the decoder is an MLP chain of vpc_linear_fwd / vpc_linear_dgrad layers,
+ * HOST arrays of n_layers (<= 8) entries: w[i] [N[i]][K[i]], b[i] [N[i]], act[i] (the activation codes above), K[0] = L,
+ * K[i+1] = N[i].  The last layer is either N = d (mean; the log-variance is the scalar x_logvar) or N = 2 d with
+ * act = 2, last_split = d ([mean | logvar] with Sigmoid | Hardtanh(-10, 0): VAE.py:2359-2363, 2392-2396).
+ * NLL = sum over the columns of -log N(x; mean, exp(logvar)) (utils.py:149-151), each term times mask[row][column] when
+ * mask [nb][d] (float 0/1) is given.  grad U = z - t * sign * dNLL/dz clamped to +-grad_clip (:196); leapfrog :252-260;
+ * accept / reject and the 1.02 / 0.98 adaptation with its clamp :285-297.
+ * Same j0 / nsteps / init / draws contract as vpc_ais_run; draws come from the same counters (vpc_ais_draws returns
+ * them; latent groups past 16 components use bits 24.. of the counter's high word, so T < 2^24).  Every launch of the
+ * block of temperatures is enqueued on `stream`: (leapfrog_steps + 1) * (2 n_layers + 2) + 1 per temperature, + 1 per
+ * call; nothing is allocated and nothing synchronises; fp32 GEMMs.  Results are bit-equal however the schedule is split.
+ * workspace: vpc_aisg_workspace_floats(B, L, n_layers, N) floats, 16-byte aligned.  With r4(n) = n rounded up to a
+ * multiple of 4 it starts with z [B][L] (r4(B L) floats) | epsilon | accept_hist | logw | nll_current (r4(B) each).
+ * Returns 2 for obs_dim > 1024, a hidden width > 512, latent_dim > 64 or B >= 2^30. */
+long vpc_aisg_workspace_floats(long B, int L, int n_layers, const int* N);
+int vpc_aisg_run(const float* x, const float* mask, const float* const* w, const float* const* b, const int* K,
+                 const int* N, const int* act, int n_layers, int last_split, float x_logvar, const float* schedule, int T,
+                 int j0, int nsteps, int init, float* workspace, long workspace_floats, const float* z0, const float* v,
+                 const float* u, unsigned long long seed, float sign, int leapfrog_steps, float init_step_size,
+                 float grad_clip, long B, long nb, int d, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VPC_LIB") or os.path.join(_HERE, "csrc", "libvpc_hip.so")  # VPC_LIB: diagnostic builds only
 
-_ERR = {1: "bad argument (null / misaligned pointer or bad count)", 2: "unsupported shape (d > 128 or L > 15)",
+_ERR = {1: "bad argument (null / misaligned pointer or bad count)", 2: "unsupported shape (beyond the limits of this entry point, include/vpc.h)",
         3: "HIP runtime error"}
 
 
@@ -124,6 +124,9 @@ _PROTOS = {
     "vpc_ais_state_floats": [L_],
     "vpc_ais_run": [P, P, P, I, I, I, I, P, P, P, P, ULL, F, I, F, F, F, L_, L_, I, I, P],
     "vpc_ais_draws": [P, P, P, L_, I, I, ULL, P],
+    # the GEMM-backed AIS engine (csrc/vpc_aisg.hip)
+    "vpc_aisg_workspace_floats": [L_, I, I, IP],
+    "vpc_aisg_run": [P, P, PP, PP, IP, IP, IP, I, I, F, P, I, I, I, I, P, L_, P, P, P, ULL, F, I, F, F, L_, L_, I, I, P],
     # PNP / EDDI encoder front-end
     "vpc_eddi_fold": [P, P, P, P, P, I, I, P],
     "vpc_eddi_front_fwd": [P, P, P, P, P, L_, I, I, P],
@@ -135,7 +138,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
 
 _lib = None
 

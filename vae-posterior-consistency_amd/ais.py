@@ -1,5 +1,6 @@
 """Annealed importance sampling with adaptive-step HMC: the reference's src/utils/AIS.py on the persistent kernel of
-csrc/vpc_ais.hip.
+csrc/vpc_ais.hip (engine="persistent") or, for every other Gaussian decoder, on the generic GEMM layer ops with the HMC
+kernels of csrc/vpc_aisg.hip around them (engine="gemm").
 
     linear_schedule, sigmoidial_schedule, log_mean_exp    AIS.py:19-25, 65-77 (host side)
     ais_chains       one batch: the temperature loop of AIS.py:155-217 -> per-chain logw, z, epsilon, accept_hist
@@ -17,11 +18,21 @@ Quirks of the reference, kept and named:
   * ais_trajectory's model_loader call (AIS.py:120-121) has the wrong arity in the reference; here the keywords
     harness.model_loader needs are keyword arguments, and `model=` skips loading.
 
-There is no CPU fallback: CPU tensors raise, and so does every model whose decoder is not the latent -> 50 -> 100 -> d
-sigmoid chain with the constant x_logvar (obs_dim <= 128, or <= 64 for the mask-augmented classes; latent_dim <= 15).
+There is no CPU fallback: CPU tensors raise.  engine="persistent" (the default) covers the latent -> 50 -> 100 -> d sigmoid
+chain with the constant x_logvar (obs_dim <= 128, or <= 64 for the mask-augmented classes; latent_dim <= 15) and raises for
+every other model.  engine="gemm" covers every family whose decoder returns (mean, logvar) - what the reference's
+ais_trajectory needs (AIS.py:125-140) - at obs_dim <= 1024, hidden width <= 512, latent_dim <= 64:
+    REG_notMIWAE_v2 / notMIWAE_myversion   2 ELU layers, merged [x_mean | x_logvar] head, Sigmoid / Hardtanh(-10, 0)
+    VAEFlow / REG_VAEFlow                  4 ELU layers, sigmoid mean head, logvar = -8
+    Reg_EDDI_mnist / vanilla_EDDI_mnist    3 ReLU layers, sigmoid head, the scalar x_logvar
+    Reg_VAE / vanilla_VAE (+ _mask), Reg_EDDI / vanilla_EDDI at any width: the 50-100 ReLU chain, the scalar x_logvar
+and takes mask= [nb, d] (0/1): the likelihood of the observed columns only.  engine="auto": the persistent kernel where it
+applies and no mask is given, else gemm.  MIWAE / Reg_MIWAE raise under every engine: their decoder returns three tensors
+(a Student-t) and the reference's AIS cannot run on it.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -29,6 +40,9 @@ import torch
 
 from . import _lib as L
 from ._lib import VpcError, check, lib, ptr, stream_ptr
+from .linear import ACT_RELU, ACT_SIGMOID_HARDTANH, chain
+
+ENGINES = ("persistent", "gemm", "auto")
 
 # Temperatures per launch when the caller does not say.  It has to come from a measurement of one launch at the largest
 # benchmarked shape (tools/bench_ais.py "launch" records -> profiles/ais.jsonl); none has been taken yet,
@@ -72,6 +86,69 @@ def _decoder_image(model):
     return model._dec_img(), d, Ld, model._x_logvar_value
 
 
+def _decoder_chain(model):
+    """(layers of linear.chain, d, L, x_logvar) of a model's decoder for the GEMM engine; x_logvar None = the chain's last
+    layer is the merged [mean | logvar] head.  The layers are the model's own parameters (the views its API path runs
+    on), not a packed copy: nothing here can go stale."""
+    from .eddi_mnist import _EDDIMnistBase
+    from .flow import _FlowBase
+    from .models import _VAEBase
+    from .notmiwae import _NMBase
+    d, Ld = getattr(model, "obs_dim", None), getattr(model, "latent_dim", None)
+    if isinstance(model, _NMBase):
+        return model._chains()[1], d, Ld, None
+    if isinstance(model, _FlowBase):
+        return model._chains()[1], d, Ld, float(model.obs_logvar)
+    if isinstance(model, _EDDIMnistBase):
+        return model._chains()[1], d, Ld, model._x_logvar_value
+    if isinstance(model, _VAEBase):
+        w = model.trainable()[6:12]
+        return chain(w, (ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), d), d, Ld, model._x_logvar_value
+    raise VpcError("AIS needs a decoder that returns a Gaussian (mean, logvar) (AIS.py:125-140): "
+                   f"{type(model).__name__} has none (MIWAE / Reg_MIWAE return the three tensors of a Student-t)")
+
+
+def _pick_engine(model, engine, mask):
+    if engine not in ENGINES:
+        raise ValueError(f"engine must be one of {ENGINES}")
+    if engine == "persistent" and mask is not None:
+        raise VpcError("mask= needs engine='gemm' (or 'auto'): the persistent kernel sums over all d columns")
+    if engine != "auto":
+        return engine
+    if mask is None:
+        try:
+            _decoder_image(model)
+            return "persistent"
+        except VpcError:
+            pass
+    return "gemm"
+
+
+def _run_gemm(model, x, mask, sched, T, B, nb, z0, v, u, seed, sign, leapfrog_steps, init_step_size, grad_clip, tpl):
+    layers, d, Ld, xlv = _decoder_chain(model)
+    n = len(layers)
+    for w, b, _, _, _, _ in layers:
+        L.require_cuda(w, b)
+    Ks, Ns = (C.c_int * n)(*[int(l[2]) for l in layers]), (C.c_int * n)(*[int(l[3]) for l in layers])
+    acts = (C.c_int * n)(*[int(l[4]) for l in layers])
+    ws_, bs_ = L.ptr_array([l[0] for l in layers]), L.ptr_array([l[1] for l in layers])
+    floats = int(lib().vpc_aisg_workspace_floats(B, Ld, n, Ns))
+    work = torch.empty(max(floats, 4), device=x.device)
+    j = 1
+    while j < T:
+        k = min(int(tpl), T - j)
+        check(lib().vpc_aisg_run(ptr(x), ptr(mask), ws_, bs_, Ks, Ns, acts, n, int(layers[-1][5]),
+                                 0.0 if xlv is None else float(xlv), ptr(sched), T, j, k, int(j == 1), ptr(work), floats,
+                                 ptr(z0), ptr(v), ptr(u), int(seed), sign, int(leapfrog_steps), float(init_step_size),
+                                 float(grad_clip), B, nb, d, Ld, stream_ptr()), "vpc_aisg_run")
+        j += k
+    r4 = lambda m: (m + 3) & ~3
+    z = work[:B * Ld].view(B, Ld).clone()
+    o = r4(B * Ld)
+    eps, hist, logw = (work[o + i * r4(B):o + i * r4(B) + B].clone() for i in range(3))  # (not views: `work` is large)
+    return logw, z, eps, hist
+
+
 def ais_draws(B, latent_dim, T, seed, device="cuda"):
     """(z0 [B, L], v [T-1, B, L], u [T-1, B]): the draws ais_chains(seed=seed) generates inside the kernel."""
     dev = torch.device(device)
@@ -85,8 +162,10 @@ def ais_draws(B, latent_dim, T, seed, device="cuda"):
 
 
 def ais_chains(model, x, schedule, n_sample, mode="forward", post_z=None, likelihood="reference", seed=None, draws=None,
-               init_step_size=0.01, leapfrog_steps=10, grad_clip=1e4, temps_per_launch=None):
+               init_step_size=0.01, leapfrog_steps=10, grad_clip=1e4, temps_per_launch=None, engine="persistent", mask=None):
     """One batch of AIS chains (AIS.py:155-217).  x [nb, d] on the GPU; B = nb * n_sample chains in safe_repeat order.
+    engine: "persistent" | "gemm" | "auto" (module docstring); mask [nb, d] (0/1, gemm engine): the likelihood sums over
+    the observed columns of each row only.
     draws: optional (z0 [B, L] or None, v [T-1, B, L] or None, u [T-1, B] or None) injected instead of the kernel's
     own Philox draws (seed; None = a fresh one from torch's generator).  mode="backward" starts from the repeated post_z
     [nb, L] (AIS.py:173).  Returns per-chain (logw [B], z [B, L], epsilon [B], accept_hist [B])."""
@@ -96,15 +175,23 @@ def ais_chains(model, x, schedule, n_sample, mode="forward", post_z=None, likeli
         raise ValueError("likelihood must be 'reference' or 'corrected'")
     if not isinstance(x, torch.Tensor):
         raise VpcError("x must be a torch tensor on the GPU")
-    L.require_cuda(x, post_z)
-    img, d, Ld, xlv = _decoder_image(model)
-    L.require_cuda(img)
+    L.require_cuda(x, post_z, mask)
+    engine = _pick_engine(model, engine, mask)
+    if engine == "persistent":
+        img, d, Ld, xlv = _decoder_image(model)
+        L.require_cuda(img)
+    else:
+        _, d, Ld, _ = _decoder_chain(model)
     if x.dim() != 2 or x.shape[1] != d:
         raise VpcError(f"x must be [nb, {d}]")
     dev = x.device
     x = x.float().contiguous()
     nb = x.shape[0]
     B = nb * int(n_sample)
+    if mask is not None:
+        if tuple(mask.shape) != (nb, d):
+            raise VpcError(f"mask must be [{nb}, {d}]")
+        mask = mask.to(dev).float().contiguous()
     sched = torch.as_tensor(np.asarray(schedule, dtype=np.float64), dtype=torch.float32).to(dev)
     T = sched.numel()
     if T < 2 or B < 1:
@@ -124,9 +211,12 @@ def ais_chains(model, x, schedule, n_sample, mode="forward", post_z=None, likeli
     z0, v, u = [None if t is None else t.float().contiguous() for t in (z0, v, u)]
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    state = torch.empty(int(lib().vpc_ais_state_floats(B)), device=dev)
     tpl = temps_per_launch or DEFAULT_TEMPS_PER_LAUNCH or T - 1
     sign = 1.0 if likelihood == "reference" else -1.0
+    if engine == "gemm":
+        return _run_gemm(model, x, mask, sched, T, B, nb, z0, v, u, seed, sign, leapfrog_steps, init_step_size, grad_clip,
+                         tpl)
+    state = torch.empty(int(lib().vpc_ais_state_floats(B)), device=dev)
     j = 1
     while j < T:
         n = min(int(tpl), T - j)
@@ -150,11 +240,11 @@ def ais_trajectory(loader, obs_dim, hid_dim, K, latent_dim, missing_rate, data_t
                    vae_type, stage, num_samples, num_estimates, mode="forward", schedule=np.linspace(0., 1., 500),
                    n_sample=100, device=torch.device("cuda"), *, model=None, experiment_type="exp", reg_type="kl_reg",
                    alpha=1.0, p_missingness=30, likelihood="reference", seed=None, draws=None, init_step_size=0.01,
-                   leapfrog_steps=10, grad_clip=1e4, temps_per_launch=None):
+                   leapfrog_steps=10, grad_clip=1e4, temps_per_launch=None, engine="persistent", masks=None):
     """AIS.py:94-234.  loader yields (batch [nb, d], post_z); returns the reference's list of per-batch means and writes
     `<stage>_ais.pt` (their mean) and `<stage>_ais_true_latents.pt` ([sum nb, n_sample, L], the reference's reshape of
-    the chain-major z - see the module docstring).  draws: one tuple per batch (a list), or None; seed: batch i uses
-    seed + i."""
+    the chain-major z - see the module docstring).  draws: one tuple per batch (a list), or None; masks: one [nb, d]
+    mask per batch (a list), or None; seed: batch i uses seed + i."""
     device = torch.device(device)
     if device.type != "cuda":
         raise VpcError("this path runs only on the GPU (HIP kernels, no CPU fallback)")
@@ -174,7 +264,8 @@ def ais_trajectory(loader, obs_dim, hid_dim, K, latent_dim, missing_rate, data_t
                                    post_z=post_z.to(device) if mode == "backward" else None, likelihood=likelihood,
                                    seed=None if seed is None else int(seed) + i, draws=None if draws is None else draws[i],
                                    init_step_size=init_step_size, leapfrog_steps=leapfrog_steps, grad_clip=grad_clip,
-                                   temps_per_launch=temps_per_launch)
+                                   temps_per_launch=temps_per_launch, engine=engine,
+                                   mask=None if masks is None else masks[i])
         lw = log_mean_exp(logw.view(n_sample, -1).transpose(0, 1))  # AIS.py:220
         if mode == "backward":
             lw = -lw

@@ -25,25 +25,8 @@ namespace vpc {
 constexpr int AIS_WAVES = 8, AIS_THREADS = AIS_WAVES * 64;
 constexpr int AIS_ZP = 16;                 // row pitch of z inside the state
 constexpr int AIS_STATE = AIS_ZP + 4;      // floats per chain: z[16], epsilon, accept_hist, logw, nll_current
-constexpr uint32_t AIS_KIND_Z0 = 2u, AIS_KIND_V = 3u, AIS_KIND_U = 4u;  // Philox streams (0 / 1: the training-step draws)
-
-// Draw counters: (global chain index, latent 4-group) in the low word, the 1-based temperature index j (0 for z0) in the
-// high word, the kind as the Philox stream - independent of tile mapping, workgroup count and launch splitting.
-__device__ __forceinline__ uint64_t ais_ctr(long chain, int group, int j) {
-    return ((uint64_t)(uint32_t)j << 32) | (uint64_t)(uint32_t)(chain * 4 + group);
-}
-// four standard normals (latent components 4 group .. 4 group + 3): the Box-Muller form of fill_normal_body (vpc_rng.h)
-__device__ __forceinline__ f32x4 ais_normal4(long chain, int group, int j, uint32_t kind, uint64_t seed) {
-    const U4 r = philox(ais_ctr(chain, group, j), kind, seed);
-    const float r0 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.x)));
-    const float r1 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.z)));
-    const float t0 = u01(r.y), t1 = u01(r.w);
-    return f32x4{r0 * __builtin_amdgcn_cosf(t0), r0 * __builtin_amdgcn_sinf(t0), r1 * __builtin_amdgcn_cosf(t1),
-                 r1 * __builtin_amdgcn_sinf(t1)};
-}
-__device__ __forceinline__ float ais_uniform(long chain, int j, uint64_t seed) {
-    return u01(philox(ais_ctr(chain, 0, j), AIS_KIND_U, seed).x);
-}
+// the draw counters and the Box-Muller draws (ais_ctr, ais_normal4, ais_uniform, AIS_KIND_*): vpc_rng.h, shared with
+// the GEMM-backed engine of vpc_aisg.hip
 
 struct AisArgs {
     const float* x;         // [nb][d]
@@ -238,11 +221,12 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_kernel(AisArgs a) {
 
 // the draws of ais_kernel as dense arrays (any of them may be NULL): z0 [B][L], v [T-1][B][L], u [T-1][B]
 __global__ __launch_bounds__(256) void ais_draws_kernel(float* z0, float* v, float* u, long B, int L, int T, uint64_t seed) {
-    const long total = (long)T * B * 4;  // (j, chain, group); j = 0: z0
+    const int G = (L + 3) / 4;
+    const long total = (long)T * B * G;  // (j, chain, group); j = 0: z0
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int group = (int)(e & 3);
-        const long chain = (e >> 2) % B;
-        const int j = (int)((e >> 2) / B);
+        const int group = (int)(e % G);
+        const long chain = (e / G) % B;
+        const int j = (int)((e / G) / B);
         float* out = j == 0 ? z0 : v;
         if (out) {
             const f32x4 n = ais_normal4(chain, group, j, j == 0 ? AIS_KIND_Z0 : AIS_KIND_V, seed);
@@ -302,8 +286,8 @@ int vpc_ais_run(const float* x, const float* dec_img, const float* schedule, int
 
 int vpc_ais_draws(float* z0, float* v, float* u, long B, int L, int T, unsigned long long seed, void* stream) {
     if (B < 1 || T < 1 || (!z0 && !v && !u)) return VPC_ERR_ARG;
-    if (B >= (1L << 30) || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
-    const long total = (long)T * B * 4;
+    if (B >= (1L << 30) || L < 1 || L > AIS_DRAW_MAX_L || T >= (1 << 24)) return VPC_ERR_SHAPE;
+    const long total = (long)T * B * ((L + 3) / 4);
     const long blocks = (total + 255) / 256;
     hipLaunchKernelGGL(ais_draws_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                        (hipStream_t)stream, z0, v, u, B, L, T, (uint64_t)seed);

@@ -84,4 +84,26 @@ __device__ __forceinline__ void fill_normal_body(float* __restrict__ out, long n
     for (int j = 0; j < 4 && i0 + j < n; ++j) out[i0 + j] = v[j];
 }
 
+// ---- the draws of the AIS engines (vpc_ais.hip: the persistent kernel; vpc_aisg.hip: the GEMM-backed one; ais_draws_kernel)
+constexpr uint32_t AIS_KIND_Z0 = 2u, AIS_KIND_V = 3u, AIS_KIND_U = 4u;  // Philox streams (0 / 1: the training-step draws)
+constexpr int AIS_DRAW_MAX_L = 64;
+// Draw counters: (global chain index, latent 4-group) in the low word, the 1-based temperature index j (0 for z0) in the
+// high word, the kind as the Philox stream - independent of tile mapping, workgroup count and launch splitting.  Groups
+// past the fourth (latent_dim > 16: the GEMM-backed engine only) go to bits 24.. of the high word, so j < 2^24.
+__device__ __forceinline__ uint64_t ais_ctr(long chain, int group, int j) {
+    return ((uint64_t)((uint32_t)j | ((uint32_t)(group >> 2) << 24)) << 32) | (uint64_t)(uint32_t)(chain * 4 + (group & 3));
+}
+// four standard normals (latent components 4 group .. 4 group + 3): the Box-Muller form of fill_normal_body
+__device__ __forceinline__ f32x4 ais_normal4(long chain, int group, int j, uint32_t kind, uint64_t seed) {
+    const U4 r = philox(ais_ctr(chain, group, j), kind, seed);
+    const float r0 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.x)));
+    const float r1 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.z)));
+    const float t0 = u01(r.y), t1 = u01(r.w);
+    return f32x4{r0 * __builtin_amdgcn_cosf(t0), r0 * __builtin_amdgcn_sinf(t0), r1 * __builtin_amdgcn_cosf(t1),
+                 r1 * __builtin_amdgcn_sinf(t1)};
+}
+__device__ __forceinline__ float ais_uniform(long chain, int j, uint64_t seed) {
+    return u01(philox(ais_ctr(chain, 0, j), AIS_KIND_U, seed).x);
+}
+
 }  // namespace vpc
