@@ -58,12 +58,17 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
     __syncthreads();
     VPC_STAMP(0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int round_w = w >> 2;                 // staging round in which this wave writes
+    // the wave index as a scalar: threadIdx.x >> 6 is divergent to hipcc, and every ownership / round test on it would
+    // become an exec-masked region (with accumulator copies in front of the wgrad loops); lane-level uses keep w
+    // (not in the split-bf16 instantiation: it sits at 256 registers with scratch in use, and either change grows that)
+    constexpr bool SW = PREC != PREC_BF16X3;
+    const int ws = SW ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
+    const int round_w = ws >> 2;                // staging round in which this wave writes
     int sb[4];
     stage_bases<CH>(sb, 16 * (w & 3), c, q);
     const float inv_s2 = expf(-a.x_logvar), half_lv = 0.5f * a.x_logvar;
     constexpr float HL2PI = 0.91893853320467274f;
-    const bool own6 = w < DT, own5 = w < H1T, own4 = w < H2T;
+    const bool own6 = (SW && DT == DEC8_WAVES) || ws < DT, own4 = ws < H2T;
 
     // latent-width ([B][16]) arrays go through range-checked buffer descriptors over the rows [row0, B): a row past B
     // reads 0 / is not written, and an absent optional array (NULL) gets an empty descriptor and reads 0 - no address
@@ -387,7 +392,7 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                                 const BfOp fb = bf_stage_frag<PREC, 7>(sBh, sBl, nt5, kb, 16 * qq + cc);
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) {
-                                    if (i < 3 || w < 4) {
+                                    if (i < 3 || ws < 4) {
                                         const BfOp fa = bf_stage_frag<PREC, 8>(sAh, sAl, mt5 + i, kb, 16 * qq + cc);
                                         acc5[i] = bf_mma<PREC>(fa, fb, acc5[i]);
                                     }
@@ -409,7 +414,7 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                                 for (int j = 0; j < 4; ++j) acc5[i] = VPC_MFMA(fa_cur[j], fb[j], acc5[i]);
                                 fa_cur = fa_nxt;
                             }
-                            if (w < 4) {
+                            if (ws < 4) {
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) acc5[3] = VPC_MFMA(fa_cur[j], fb[j], acc5[3]);
                             }

@@ -273,6 +273,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
     float* sBh = stB;
     float* sBl = stB + 56 * CH;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+    // the wave index as a scalar for the ownership tests (threadIdx.x >> 6 is divergent to hipcc: exec-masked regions
+    // around the wgrad loops); addresses keep the vector value
+    const int ws = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p_lo = a.psplit ? (int)blockIdx.y : 0, p_hi = a.psplit ? p_lo + 1 : a.npass;
     // row-layout operands of one (tile, pass) through range-checked buffer descriptors: rows past B read 0 - zero seeds make
     // dh2, dh1 and every wgrad contribution of such a row exactly zero.  (hipcc turns `ok ? load : 0` into an exec-masked
@@ -375,6 +378,28 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                     mb |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rm, off, 0, 0) << (8 * j);
                 }
             };
+            // fp32 engine: the four mask bytes stay in their own registers until the fragment is formed.  Packing them into
+            // one word where they are requested (ld_xb) is VALU on the loaded values in front of the MFMAs the loads are
+            // meant to run under (hipcc waits for every slice's mask bytes right behind their request), and five
+            // instructions per slice where the unpacked form needs four.
+            auto ld_xr = [&](int o, int sl, f32x4& xv, uint32_t (&mr)[4]) {
+                const int vo0 = 4 * qq * a.d + colB[o];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int off = vo0 + (16 * sl + j) * a.d;
+                    xv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, 4 * off, 0, 0));
+                    mr[j] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rm, off, 0, 0);
+                }
+            };
+            auto mk_fr = [&](int o, const f32x4& xv, const uint32_t (&mr)[4]) -> f32x4 {
+                const uint32_t k = (AUG || fx[o]) ? 0xffu : 0u;  // columns past the input width: mask 0
+                const f32x4 m = {(float)(mr[0] & k), (float)(mr[1] & k), (float)(mr[2] & k), (float)(mr[3] & k)};
+                if (!AUG) return xv * m;
+                f32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = fx[o] ? xv[j] * m[j] : (fm[o] ? m[j] : 0.f);
+                return v;
+            };
             auto mk_fb = [&](int o, const f32x4& xv, uint32_t mb) -> f32x4 {
                 if (!AUG) return xv * mask_to_f32(mb & (fx[o] ? 0xffffffffu : 0u));  // columns past the input width: mask 0
                 const f32x4 m = mask_to_f32(mb);
@@ -431,7 +456,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
 #pragma unroll
             for (int o = 0; o < OWN; ++o) {
                 if (PREC != PREC_F32) {
-                    if (w + NW * o < H1T && !ABLE(4)) {
+                    if (ws + NW * o < H1T && !ABLE(4)) {
 #pragma unroll
                         for (int kb = 0; kb < SKB; ++kb) {
                             asm volatile("" ::: "memory");
@@ -443,7 +468,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                             }
                         }
                     }
-                } else if (w + NW * o < H1T && !ABLE(4)) {
+                } else if (ws + NW * o < H1T && !ABLE(4)) {
 #pragma unroll
                     for (int s = 0; s < CH / 16; ++s) {
                         asm volatile("" ::: "memory");
@@ -467,12 +492,18 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
             constexpr int NS = CH / 16;
             f32x4 xb[OWN][3];  // rotating: slices s, s + 1, s + 2
             uint32_t mbb[OWN][3];
+            uint32_t mrr[OWN][3][4];  // fp32 engine: unpacked
 #pragma unroll
             for (int o = 0; o < OWN; ++o)
-                if (w + NW * o < DT) {
-                    ld_xb(o, 0, xb[o][0], mbb[o][0]);
-                    ld_xb(o, 1, xb[o][1], mbb[o][1]);
-                    if (PREC != PREC_F32) ld_xb(o, 2, xb[o][2], mbb[o][2]);  // bf16: slices are consumed in pairs
+                if (NW * (o + 1) <= DT || ws + NW * o < DT) {
+                    if (PREC == PREC_F32) {
+                        ld_xr(o, 0, xb[o][0], mrr[o][0]);
+                        ld_xr(o, 1, xb[o][1], mrr[o][1]);
+                    } else {
+                        ld_xb(o, 0, xb[o][0], mbb[o][0]);
+                        ld_xb(o, 1, xb[o][1], mbb[o][1]);
+                        ld_xb(o, 2, xb[o][2], mbb[o][2]);  // bf16: slices are consumed in pairs
+                    }
                 }
             // ---- dh1 = relu'(h1) * (W2~^T dh2);  db1 += dh1
             launder(cc, qq);
@@ -540,7 +571,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
 #pragma unroll
             for (int o = 0; o < OWN; ++o) {
                 if (PREC != PREC_F32) {
-                    if (w + NW * o < DT) {
+                    if (NW * (o + 1) <= DT || ws + NW * o < DT) {
                         // slices in pairs (one 32-row k-block per MFMA); ring of 4 slices: block sb2 + 1 in flight
                         f32x4 xq[4] = {xb[o][0], xb[o][1], xb[o][2], zero4()};
                         uint32_t mq[4] = {mbb[o][0], mbb[o][1], mbb[o][2], 0u};
@@ -559,12 +590,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                             }
                         }
                     }
-                } else if (w + NW * o < DT && !ABLE(4)) {
+                } else if ((NW * (o + 1) <= DT || ws + NW * o < DT) && !ABLE(4)) {
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
                         asm volatile("" ::: "memory");  // keep each slice's loads in its slice (hipcc hoists all 8 otherwise)
-                        if (s + 2 < NS) ld_xb(o, s + 2, xb[o][(s + 2) % 3], mbb[o][(s + 2) % 3]);
-                        const f32x4 fb = mk_fb(o, xb[o][s % 3], mbb[o][s % 3]);
+                        if (s + 2 < NS) ld_xr(o, s + 2, xb[o][(s + 2) % 3], mrr[o][(s + 2) % 3]);
+                        const f32x4 fb = mk_fr(o, xb[o][s % 3], mrr[o][s % 3]);
                         f32x4 fa = stage_frag<CH>(stA, 0, s, cc, qq);
 #pragma unroll
                         for (int mt = 0; mt < H1T; ++mt) {
