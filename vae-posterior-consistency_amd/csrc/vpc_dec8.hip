@@ -19,6 +19,12 @@ namespace vpc {
 
 constexpr int DEC8_WAVES = 8, DEC8_THREADS = 512;
 
+// fp32 engine: LDS fragment addresses as lane bases + immediates (vpc_device.h, frag_bases / fragT_bases); 0 builds the
+// form that computes every address at its read (for A/B measurements)
+#ifndef VPC_LANE_BASES
+#define VPC_LANE_BASES 1
+#endif
+
 #ifdef VPC_ABLATE
 #define ABL(bit) VPC_DBG(bit)   // timing experiments (diagnostic build): 1 no staging writes, 2 no barriers, 4 no wgrad MFMAs
 #else
@@ -37,6 +43,10 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
     constexpr int NA = (16 * DT > H1P ? 16 * DT : H1P);
     constexpr bool BF = PREC != PREC_F32;
     constexpr int S4K = BF ? 32 : S4;  // row pitch of the W4 image
+    constexpr bool LB = !BF && VPC_LANE_BASES;
+    constexpr int OFF_B = NA * CH * 4;  // stB behind stA, bytes: the staging bases serve both buffers
+    static_assert(OFF_B + frag_imm(CH, H1T - 1, CH / 16 - 1) < 65536 && frag_imm(128, DT - 1, H1T - 1) < 65536 &&
+                      fragT_imm(128, H1T - 1, DT - 1) < 65536, "ds_read immediates are 16 bits");
     const DecImg im(DT, S4K);
     load_image<13>(lds, a.img, im.total);  // one round of loads for 512 threads
     const float* W4 = lds + im.oW4;
@@ -150,6 +160,14 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 if (BF) {
                     bf_layer_fwd<PREC, 2, 64, H1T, 2>(W5, g1b, cc, qq,
                                                                          [&](int mt, f32x4 acc) { g2[0][mt] = relu4(acc); });
+                } else if (LB) {
+                    uint32_t f5[4];
+                    frag_bases<64>(f5, W5, cc, qq);
+#pragma unroll
+                    for (int mt = 0; mt < H1T; ++mt) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        g2[0][mt] = relu4(tile_fwd_p2_b<H2T, 64, NK2>(f5, mt, g1[0]));
+                    }
                 } else {
 #pragma unroll
                     for (int mt = 0; mt < H1T; ++mt) {
@@ -208,6 +226,8 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 // plain bf16: the W6 fragments of tile mt + 1 are requested before tile mt's MFMAs and loss math (4 MFMAs of 16
                 // cycles do not cover an LDS round trip; in the split form the 12-MFMA chain nearly does, and registers are short)
                 constexpr bool WPF = PREC == PREC_BF16;
+                uint32_t f6[4];
+                if (LB) frag_bases<128>(f6, W6, cc, qq);
                 BfOp w6n[4];
                 if (WPF) {
 #pragma unroll
@@ -233,6 +253,7 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
 #pragma unroll
                         for (int kb = 0; kb < 4; ++kb) pre[0] = bf_mma<PREC>(w6c[kb], g2b[kb], pre[0]);
                     } else if (BF) pre[0] = bf_tile_fwd<PREC, 4, 128>(W6, mt, g2b, zero4(), cc, qq);
+                    else if (LB) pre[0] = tile_fwd_p2_b<H1T, 128, NK1>(f6, mt, g2[0]);
                     else pre[0] = tile_fwd_p2<H1T, 128, NK1>(W6, mt, g2[0], cc, qq);
                     if (VEC && mt >= DT / 2) {
                         const uint32_t vm = opaque_mask(16 * mt + 4 * q + 3 < a.d);
@@ -276,6 +297,16 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 // ---------------- dW6~ += dpre * g2^T   (owner: wave w -> out tile w; all 7 in tiles)
                 VPC_CUT();
                 launder(cc, qq);
+                // staging fragments: bases of tile 0 (the B buffer sits OFF_B behind) and of this wave's own A tile
+                uint32_t sf[4], sfw[4];
+                if (LB) {
+                    frag_bases<CH>(sf, stA, cc, qq);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        sfw[v] = sf[v] + (uint32_t)(ws * frag_imm(CH, 1, 0));
+                        asm volatile("" : "+v"(sfw[v]));
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < (BF ? ROUNDS : 2); ++r) {
                     if (!ABL(2)) lds_barrier();
@@ -313,11 +344,12 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
 #pragma unroll
                         for (int s = 0; s < CH / 16; ++s) {
                             __builtin_amdgcn_sched_barrier(0);
-                            const f32x4 fa = stage_frag<CH>(stA, w, s, cc, qq);
-                            f32x4 fb_cur = stage_frag<CH>(stB, 0, s, cc, qq);
+                            const f32x4 fa = LB ? frag_ld<CH>(sfw, 0, s) : stage_frag<CH>(stA, w, s, cc, qq);
+                            f32x4 fb_cur = LB ? frag_ld<CH, OFF_B>(sf, 0, s) : stage_frag<CH>(stB, 0, s, cc, qq);
 #pragma unroll
                             for (int nt = 0; nt < H1T; ++nt) {
-                                const f32x4 fb_nxt = stage_frag<CH>(stB, nt + 1 < H1T ? nt + 1 : nt, s, cc, qq);
+                                const f32x4 fb_nxt = LB ? frag_ld<CH, OFF_B>(sf, nt + 1 < H1T ? nt + 1 : nt, s)
+                                                        : stage_frag<CH>(stB, nt + 1 < H1T ? nt + 1 : nt, s, cc, qq);
                                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) acc6[nt] = VPC_MFMA(fa[j], fb_cur[j], acc6[nt]);
@@ -334,6 +366,15 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 if (BF) {
                     bf_layer_T<PREC, (DT + 1) / 2, 128, H1T, DT, PREC == PREC_BF16 ? (DT + 1) / 2 : 2>(
                         W6, dpreb, 16 * qq + cc, [&](int mt, f32x4 acc) { dg2[0][mt] = gate_bits(acc, gm2, mt); });
+                } else if (LB) {
+                    uint32_t tj[4], tv[4];
+                    fragT_bases<128>(tj, tv, W6, cc, qq);
+#pragma unroll
+                    for (int mt = 0; mt < H1T; ++mt) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        VPC_CUT();
+                        dg2[0][mt] = gate_bits(tile_T_p2_b<DT, 128>(tj, tv, mt, dpre[0]), gm2, mt);
+                    }
                 } else {
 #pragma unroll
                     for (int mt = 0; mt < H1T; ++mt) {
@@ -360,6 +401,17 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 }
                 const uint32_t gm1 = relu_bits<H2T>(g1r[0]);
                 const int nt5 = w & 3, mt5 = 4 * (w >> 2);
+                // bases of this wave's first A tile (mt5) and of its B tile (nt5), from the scalar wave index
+                uint32_t s5a[4], s5b[4];
+                if (LB) {
+                    frag_bases<CH>(s5a, stA, cc, qq);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        s5b[v] = s5a[v] + (uint32_t)((ws & 3) * frag_imm(CH, 1, 0));
+                        s5a[v] += (uint32_t)((ws >> 2) * frag_imm(CH, 4, 0));
+                        asm volatile("" : "+v"(s5a[v]), "+v"(s5b[v]));
+                    }
+                }
                 BfOp dg2b[4], g1rb[2];
                 if (BF) {
                     bf_acts<PREC, H1T>(dg2[0], dg2b);
@@ -404,11 +456,12 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
 #pragma unroll
                         for (int s = 0; s < CH / 16; ++s) {
                             __builtin_amdgcn_sched_barrier(0);
-                            const f32x4 fb = stage_frag<CH>(stB, nt5, s, cc, qq);
-                            f32x4 fa_cur = stage_frag<CH>(stA, mt5, s, cc, qq);
+                            const f32x4 fb = LB ? frag_ld<CH, OFF_B>(s5b, 0, s) : stage_frag<CH>(stB, nt5, s, cc, qq);
+                            f32x4 fa_cur = LB ? frag_ld<CH>(s5a, 0, s) : stage_frag<CH>(stA, mt5, s, cc, qq);
 #pragma unroll
                             for (int i = 0; i < 3; ++i) {
-                                const f32x4 fa_nxt = stage_frag<CH>(stA, mt5 + i + 1, s, cc, qq);  // mt5 + 3 = 7: unused rows of stA
+                                // mt5 + 3 = 7: unused rows of stA
+                                const f32x4 fa_nxt = LB ? frag_ld<CH>(s5a, i + 1, s) : stage_frag<CH>(stA, mt5 + i + 1, s, cc, qq);
                                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) acc5[i] = VPC_MFMA(fa_cur[j], fb[j], acc5[i]);
@@ -429,6 +482,15 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 if (BF) {
                     bf_layer_T<PREC, 4, 64, H2T, H1T, PREC == PREC_BF16 ? 4 : 2>(
                         W5, dg2b, 16 * qq + cc, [&](int mt, f32x4 acc) { dg1[0][mt] = gate_bits(acc, gm1, mt); });
+                } else if (LB) {
+                    uint32_t tj[4], tv[4];
+                    fragT_bases<64>(tj, tv, W5, cc, qq);
+#pragma unroll
+                    for (int mt = 0; mt < H2T; ++mt) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        VPC_CUT();
+                        dg1[0][mt] = gate_bits(tile_T_p2_b<H1T, 64, NK1>(tj, tv, mt, dg2[0]), gm1, mt);
+                    }
                 } else {
 #pragma unroll
                     for (int mt = 0; mt < H2T; ++mt) {
@@ -442,6 +504,15 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                 VPC_CUT();
                 launder(cc, qq);
                 fetch_stats();  // the pass-end operands come in under this phase's MFMAs
+                uint32_t s4a[4], s4b[4];
+                if (LB) {
+                    frag_bases<CH>(s4b, stA, cc, qq);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        s4a[v] = s4b[v] + (uint32_t)(ws * frag_imm(CH, 1, 0));
+                        asm volatile("" : "+v"(s4a[v]));
+                    }
+                }
                 BfOp dg1b[2];
                 if (BF) bf_acts<PREC, H2T>(dg1[0], dg1b);
 #pragma unroll
@@ -471,8 +542,8 @@ __global__ __launch_bounds__(DEC8_THREADS) void dec8_kernel(DecArgs a) {
                     } else if (own4 && !ABL(4)) {
 #pragma unroll
                         for (int s = 0; s < CH / 16; ++s) {
-                            const f32x4 fa = stage_frag<CH>(stA, w, s, cc, qq);
-                            const f32x4 fb = stage_frag<CH>(stB, 0, s, cc, qq);
+                            const f32x4 fa = LB ? frag_ld<CH>(s4a, 0, s) : stage_frag<CH>(stA, w, s, cc, qq);
+                            const f32x4 fb = LB ? frag_ld<CH, OFF_B>(s4b, 0, s) : stage_frag<CH>(stB, 0, s, cc, qq);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) acc4 = VPC_MFMA(fa[j], fb[j], acc4);
                         }

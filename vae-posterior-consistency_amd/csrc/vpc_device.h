@@ -230,6 +230,111 @@ __device__ __forceinline__ f32x4 stage_frag(const float* st, int t, int s, int m
     return *reinterpret_cast<const f32x4*>(st + f * CH + 4 * ((4 * s + q) ^ (f & stage_swz_mask<CH>())));
 }
 
+// ---- the same LDS reads as  lane base + immediate  (vpc_layout.h: frag_base / fragT_base_*).  tile_fwd_p2, tile_T_p2 and
+// stage_frag form every address from the lane id where it is used: after launder() hipcc cannot see through the lane id,
+// so each ds_read gets its own add / xor / shift-add in front of it - VALU that issues in MFMA time.  Here a phase computes
+// its few bases once (byte addresses in LDS, made opaque so that hipcc neither re-expands them at every use nor hoists
+// one per tile out of the loops), and the tile indices only pick a base and an immediate that folds into `offset:`.
+typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_cptr;
+typedef const __attribute__((address_space(3))) float* lds_f32_cptr;
+__device__ __forceinline__ uint32_t lds_addr(const float* p) {
+    return (uint32_t)(uintptr_t)(lds_f32_cptr)p;
+}
+__device__ __forceinline__ f32x4 lds_ld128(uint32_t addr) { return *(lds_f32x4_cptr)(uintptr_t)addr; }
+__device__ __forceinline__ float lds_ld32(uint32_t addr) { return *(lds_f32_cptr)(uintptr_t)addr; }
+// bases of the forward / staging fragments of the image (or staging buffer) at W with S-dword rows
+template <int S>
+__device__ __forceinline__ void frag_bases(uint32_t (&fb)[frag_nvar(S)], const float* W, int m, int q) {
+    const uint32_t w0 = lds_addr(W);
+#pragma unroll
+    for (int v = 0; v < frag_nvar(S); ++v) {
+        fb[v] = w0 + (uint32_t)frag_base(S, v, m, q);
+        asm volatile("" : "+v"(fb[v]));
+    }
+}
+// the fragment (tile t, k-tile s) behind the bases; OFF: a compile-time byte offset (a second buffer behind the first)
+template <int S, int OFF = 0>
+__device__ __forceinline__ f32x4 frag_ld(const uint32_t (&fb)[frag_nvar(S)], int t, int s) {
+    return lds_ld128(fb[frag_var(S, s)] + (uint32_t)(frag_imm(S, t, s) + OFF));
+}
+// tile_fwd_p2 on bases: the same reads and the same MFMA order
+template <int KT, int S, int NK = 4 * KT>
+__device__ __forceinline__ f32x4 tile_fwd_p2_b(const uint32_t (&fb)[frag_nvar(S)], int mt, const f32x4 (&in)[KT]) {
+    f32x4 acc = zero4();
+    f32x4 fa = frag_ld<S>(fb, mt, 0);
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+        const f32x4 fn = kt + 1 < KT ? frag_ld<S>(fb, mt, kt + 1) : fa;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
+        fa = fn;
+    }
+    return acc;
+}
+// bases of the transposed fragments: one per register j (it holds the image's address) plus one per mt & 3
+template <int S>
+__device__ __forceinline__ void fragT_bases(uint32_t (&tj)[4], uint32_t (&tv)[fragT_nvar(S)], const float* W, int m, int q) {
+    const uint32_t w0 = lds_addr(W);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        tj[j] = w0 + (uint32_t)fragT_base_j(S, j, m, q);
+        asm volatile("" : "+v"(tj[j]));
+    }
+#pragma unroll
+    for (int v = 0; v < fragT_nvar(S); ++v) {
+        tv[v] = (uint32_t)fragT_base_v(S, v, q);
+        asm volatile("" : "+v"(tv[v]));
+    }
+}
+// tile_T_p2 on bases: four adds per tile, none per read
+template <int KT, int S, int NK = 4 * KT>
+__device__ __forceinline__ f32x4 tile_T_p2_b(const uint32_t (&tj)[4], const uint32_t (&tv)[fragT_nvar(S)], int mt,
+                                             const f32x4 (&in)[KT]) {
+    uint32_t p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = tj[j] + tv[fragT_var(S, mt)];
+    auto rd = [&](int kt) {
+        f32x4 f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f[j] = (4 * kt + j < NK) ? lds_ld32(p[j] + (uint32_t)fragT_imm(S, mt, kt)) : 0.f;
+        return f;
+    };
+    f32x4 acc = zero4();
+    f32x4 fa = rd(0);
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+        const f32x4 fn = kt + 1 < KT ? rd(kt + 1) : fa;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) acc = VPC_MFMA(fa[j], in[kt][j], acc);
+        fa = fn;
+    }
+    return acc;
+}
+// tile_T on bases (every fragment requested before the first MFMA, as there)
+template <int KT, int S, int NK = 4 * KT>
+__device__ __forceinline__ f32x4 tile_T_b(const uint32_t (&tj)[4], const uint32_t (&tv)[fragT_nvar(S)], int mt,
+                                          const f32x4 (&in)[KT], f32x4 acc) {
+    uint32_t p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = tj[j] + tv[fragT_var(S, mt)];
+    float a[KT][4];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) a[kt][j] = lds_ld32(p[j] + (uint32_t)fragT_imm(S, mt, kt));
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * kt + j < NK) acc = VPC_MFMA(a[kt][j], in[kt][j], acc);
+    return acc;
+}
+
 // ---- row-major [rows][ld] global <-> C-layout tile.  Loads are branch-free: an out-of-range element reads
 // element 0 of the array (always valid) and is then replaced by 0, so the kernels stay straight-line code.
 template <bool VEC>

@@ -233,6 +233,12 @@ struct EncBwdArgs {
     int psplit;  // as EncFwdArgs
 };
 
+// 8-wave fp32 backward kernel: LDS fragment addresses as lane bases + immediates (vpc_device.h, frag_bases / fragT_bases);
+// 0 builds the form that computes every address at its read (for A/B measurements)
+#ifndef VPC_LANE_BASES
+#define VPC_LANE_BASES 1
+#endif
+
 #ifdef VPC_ABLATE
 #define ABLE(bit) ((a.dbg & (bit)) != 0)  // timing experiments (diagnostic build): 1 no staging writes, 2 no barriers, 4 no wgrad 1/2 MFMAs
 #else
@@ -268,6 +274,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
     // (vpc_bf16.h, bf_stage_*): written once by the owner of the row, read back with the transposing LDS read
     constexpr bool BF = PREC != PREC_F32;
     constexpr int SKB = CH / 32;
+    constexpr bool LB = !BF && NW == 8 && VPC_LANE_BASES;
+    constexpr int OFF_B = H1P * CH * 4;  // stB behind stA, bytes (too far for an immediate: the B buffer has bases of its own)
+    static_assert(frag_imm(128, H1T - 1, 7) < 65536, "ds_read immediates are 16 bits");
     float* sAh = stA;
     float* sAl = stA + 56 * CH;
     float* sBh = stB;
@@ -426,15 +435,28 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
             f32x4 dh2[H2T];
             BfOp dmlb[1], dh2b[2];  // bf16 engine: packed once, used by the dgrad MFMAs AND the wgrad staging writes
             if (BF) dmlb[0] = bf_pack<PREC>(dml[0], dml[1]);
+            uint32_t tj[4], tv[4];
+            if (LB) fragT_bases<64>(tj, tv, W3, cc, qq);
 #pragma unroll
             for (int mt = 0; mt < H2T; ++mt) {
-                if (PREC == PREC_F32) dh2[mt] = gate4(tile_T<2, 64>(W3, mt, dml, zero4(), cc, qq), h2[mt]);
+                if (LB) dh2[mt] = gate4(tile_T_b<2, 64>(tj, tv, mt, dml, zero4()), h2[mt]);
+                else if (PREC == PREC_F32) dh2[mt] = gate4(tile_T<2, 64>(W3, mt, dml, zero4(), cc, qq), h2[mt]);
                 else dh2[mt] = gate_h2(mt, bf_tile_T<PREC, 1, 64>(W3, mt, dmlb, zero4(), 16 * qq + cc));
             }
             if (BF) bf_acts<PREC, H2T>(dh2, dh2b);
             VPC_STAMP(2);
             // ---- dW2~ += dh2 * h1^T   (owner: wave w -> in tiles w + NW o < 7, all 4 out tiles)
             launder(cc, qq);
+            // staging fragments: bases of tile 0 of the A buffer and of this wave's own tile of the B buffer
+            uint32_t sf[4], sfw[4];
+            if (LB) {
+                frag_bases<CH>(sf, stA, cc, qq);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    sfw[v] = sf[v] + (uint32_t)(OFF_B + ws * frag_imm(CH, 1, 0));
+                    asm volatile("" : "+v"(sfw[v]));
+                }
+            }
             if (!ABLE(2)) lds_barrier();
             if (BF && !ABLE(1)) {
 #pragma unroll
@@ -472,13 +494,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
 #pragma unroll
                     for (int s = 0; s < CH / 16; ++s) {
                         asm volatile("" ::: "memory");
-                        const f32x4 fb = stage_frag<CH>(stB, w + NW * o, s, cc, qq);
+                        const f32x4 fb = LB ? frag_ld<CH>(sfw, 0, s) : stage_frag<CH>(stB, w + NW * o, s, cc, qq);
                         // A fragments double-buffered by hand (hipcc sinks each LDS read to its first use: one exposed
                         // LDS latency per 4 MFMAs); the sched_barrier pins the read of mt+1 above the MFMAs of mt
-                        f32x4 fa = stage_frag<CH>(stA, 0, s, cc, qq);
+                        f32x4 fa = LB ? frag_ld<CH>(sf, 0, s) : stage_frag<CH>(stA, 0, s, cc, qq);
 #pragma unroll
                         for (int mt = 0; mt < H2T; ++mt) {
-                            const f32x4 fn = stage_frag<CH>(stA, mt + 1 < H2T ? mt + 1 : mt, s, cc, qq);
+                            const f32x4 fn = LB ? frag_ld<CH>(sf, mt + 1 < H2T ? mt + 1 : mt, s)
+                                                : stage_frag<CH>(stA, mt + 1 < H2T ? mt + 1 : mt, s, cc, qq);
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) acc2[o][mt] = VPC_MFMA(fa[j], fb[j], acc2[o][mt]);
@@ -517,6 +540,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                     dbacc[mt] += dh1[mt];
                 });
             } else {
+                // (not on lane bases: this phase is the kernel's register peak, and the 4 + 4 bases spill 116 B / lane)
 #pragma unroll
                 for (int mt = 0; mt < H1T; ++mt) {
                     dh1[mt] = gate4(tile_T<H2T, 128, NK2>(W2, mt, dh2, zero4(), cc, qq), h1[mt]);
@@ -526,6 +550,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
             VPC_STAMP(4);
             // ---- dW1 += dh1 * (x*mask)^T   (owner: wave w -> in tiles w + NW o < DT, all 7 out tiles; B straight from global)
             launder(cc, qq);
+            // bases of tile 0 of the A buffer (dW1) and of this wave's two operand tiles of dW3 in the B buffer
+            uint32_t s1[4], s3a[4], s3b[4];
+            if (LB) {
+                frag_bases<CH>(s1, stA, cc, qq);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    s3a[v] = s1[v] + (uint32_t)(OFF_B + (H2T + (ws >> 2)) * frag_imm(CH, 1, 0));
+                    s3b[v] = s1[v] + (uint32_t)(OFF_B + (ws & 3) * frag_imm(CH, 1, 0));
+                    asm volatile("" : "+v"(s3a[v]), "+v"(s3b[v]));
+                }
+            }
             if (!ABLE(2)) lds_barrier();
             if (BF && !ABLE(1)) {
 #pragma unroll
@@ -554,8 +589,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                 if (PREC == PREC_F32) {
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        const f32x4 fa = stage_frag<CH>(stB, H2T + (t8 >> 2), s, cc, qq);
-                        const f32x4 fb = stage_frag<CH>(stB, t8 & 3, s, cc, qq);
+                        const f32x4 fa = LB ? frag_ld<CH>(s3a, 0, s) : stage_frag<CH>(stB, H2T + (t8 >> 2), s, cc, qq);
+                        const f32x4 fb = LB ? frag_ld<CH>(s3b, 0, s) : stage_frag<CH>(stB, t8 & 3, s, cc, qq);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) acc3[o] = VPC_MFMA(fa[j], fb[j], acc3[o]);
                     }
@@ -596,10 +631,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
                         asm volatile("" ::: "memory");  // keep each slice's loads in its slice (hipcc hoists all 8 otherwise)
                         if (s + 2 < NS) ld_xr(o, s + 2, xb[o][(s + 2) % 3], mrr[o][(s + 2) % 3]);
                         const f32x4 fb = mk_fr(o, xb[o][s % 3], mrr[o][s % 3]);
-                        f32x4 fa = stage_frag<CH>(stA, 0, s, cc, qq);
+                        f32x4 fa = LB ? frag_ld<CH>(s1, 0, s) : stage_frag<CH>(stA, 0, s, cc, qq);
 #pragma unroll
                         for (int mt = 0; mt < H1T; ++mt) {
-                            const f32x4 fn = stage_frag<CH>(stA, mt + 1 < H1T ? mt + 1 : mt, s, cc, qq);
+                            const f32x4 fn = LB ? frag_ld<CH>(s1, mt + 1 < H1T ? mt + 1 : mt, s)
+                                                : stage_frag<CH>(stA, mt + 1 < H1T ? mt + 1 : mt, s, cc, qq);
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) acc1[o][mt] = VPC_MFMA(fa[j], fb[j], acc1[o][mt]);

@@ -59,6 +59,37 @@ VPC_HD inline int swz(int col, int row, int S = 64) {
     return ((((col >> 2) ^ (row & 15 & (S / 4 - 1))) << 2) | (col & 3));
 }
 
+// ---- The swizzled LDS reads as  lane base + compile-time immediate  (byte addresses inside one image / staging buffer of
+// S-dword rows).  Lane (m, q) = (lane & 15, lane >> 4).  The 16-byte slot index is XORed with the low bits of the row; the
+// XOR never carries, so the tile indices split into bits that only add a constant (the `offset:` field of the ds_read) and
+// at most two bits that pick one of a few per-lane bases ("variants"), held in registers across a phase.
+VPC_HD constexpr int swz_mask(int S) { return (S / 4 - 1) & 15; }
+// forward A fragment (tile_fwd*, 16 bytes) and wgrad staging fragment (stage_frag, S = CH): row 16 mt + m, slot
+// (4 kt + q) ^ (m & mask).  S >= 64: with m = 4 mh + ml and kt = 4 a + b the slot is 16 a + 4 (b ^ mh) + (q ^ ml):
+// variant b = kt & 3, immediate 64 S mt + 256 (kt >> 2).  S = 16 (one k-tile): one variant.
+VPC_HD constexpr int frag_addr(int S, int mt, int kt, int m, int q) {
+    return 4 * ((16 * mt + m) * S + 4 * ((4 * kt + q) ^ (m & swz_mask(S))));
+}
+VPC_HD constexpr int frag_nvar(int S) { return S >= 64 ? 4 : 1; }
+VPC_HD constexpr int frag_var(int S, int kt) { return S >= 64 ? kt & 3 : 0; }
+VPC_HD constexpr int frag_base(int S, int var, int m, int q) {
+    return S >= 64 ? 4 * S * m + 64 * (var ^ (m >> 2)) + 16 * (q ^ (m & 3)) : 4 * S * m + 16 * (q ^ (m & swz_mask(S)));
+}
+VPC_HD constexpr int frag_imm(int S, int mt, int kt) { return 64 * S * mt + (S >= 64 ? 256 * (kt >> 2) : 0); }
+// transposed A fragment (tile_T*, 4 bytes, register j): row 16 kt + 4 q + j, column 16 mt + m, slot (4 mt + (m >> 2)) ^ (4 q + j)
+// = 16 (mt >> 2) + 4 ((mt & 3) ^ q) + ((m >> 2) ^ j).  The base is the sum of a part per register j and a part per
+// mt & 3 (S = 16: one 16-column tile, no second part): 4 + 4 lane values, immediate 64 S kt + 256 (mt >> 2).
+VPC_HD constexpr int fragT_addr(int S, int mt, int kt, int j, int m, int q) {
+    return 4 * ((16 * kt + 4 * q + j) * S + (((((16 * mt + m) >> 2) ^ ((4 * q + j) & swz_mask(S))) << 2) | (m & 3)));
+}
+VPC_HD constexpr int fragT_nvar(int S) { return S >= 64 ? 4 : 1; }
+VPC_HD constexpr int fragT_var(int S, int mt) { return S >= 64 ? mt & 3 : 0; }
+VPC_HD constexpr int fragT_base_j(int S, int j, int m, int q) {
+    return 4 * S * (4 * q + j) + 16 * ((m >> 2) ^ j) + 4 * (m & 3);
+}
+VPC_HD constexpr int fragT_base_v(int S, int var, int q) { return S >= 64 ? 64 * (var ^ q) : 0; }
+VPC_HD constexpr int fragT_imm(int S, int mt, int kt) { return 64 * S * kt + (S >= 64 ? 256 * (mt >> 2) : 0); }
+
 // ---- encoder image: [W1: 112 x S1][b1: 128][W2: 64 x 128][W3: 32 x 64]
 struct EncImg {
     int DT, S1, oW1, ob1, oW2, oW3, total;
