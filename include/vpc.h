@@ -482,6 +482,61 @@ int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* d
                             long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
                             void* stream);
 
+/* ---- ensemble step: G independent models of ONE architecture in one pair of launches (csrc/vpc_small.hip, csrc/vpc_misc.hip).
+ * The reference trains lists of tiny runs: src/experiment_main/imputation.py:21-39 wraps the step loop of
+ * src/experiment_main/train.py:28-117 in `for missing in [...]: for alpha in [...]:` per split, every run at batch 64, where the
+ * single-model step occupies 4 workgroups.  Here workgroup (tile t, member g) runs the tile body of vpc_step_small(_draw)_f32 on
+ * member g's buffers, and the reduction + Adam launch runs per member on blockIdx.y: every member gets, bit for bit, the partial
+ * blocks, gradient, loss terms, Adam state and re-packed images its stand-alone vpc_step_small(_draw)_f32 + vpc_reduce_step_adam
+ * would give it.
+ *
+ * Member table: G device-resident VpcMember records (64 bytes each, read with ordinary loads), everything that may differ
+ * between members beside their buffers.  Shared, by value: npass, the Philox offsets, inv_B, x_logvar, B, d, L (one class, shape and
+ * reg_type, so every member consumes the same counters; member g draws with ITS seed in its own element space, as the unsharded
+ * vpc_step_small_draw_f32 does: eps_rows_local = eps_rows_global = B, mask_elem_lo = 0).
+ *
+ * Buffers: the pointers are member 0's; member g's slice starts g * strides[k] ELEMENTS further (host array of VPC_MS_COUNT longs):
+ *   VPC_MS_X, VPC_MS_MASK     x [B][d] fp32, mask [B][d] bytes; stride 0 = one batch shared by every member
+ *   VPC_MS_MASK_P             mask_p [B][d] bytes (npass 2; written when draw != 0; 0 = shared, injected only)
+ *   VPC_MS_EPS                eps planes [nplanes][B][16] fp32: eps_q, eps_p (npass 2), eps_ml (nplanes 3)
+ *   VPC_MS_IMG                the fp32 weight images: enc_img and dec_img of member g are both g * stride floats further
+ *   VPC_MS_PARTE, _PARTD      partial blocks: member g's tiles-per-member blocks [tiles][enc / dec_part_floats]
+ *   VPC_MS_LOSS               loss partials [tiles][8] doubles
+ *   VPC_MS_PARAM              rows of params / exp_avg / exp_avg_sq / grad_out (vpc_reduce_step_adam_multi only)
+ * Strides of fp32 arrays are multiples of 4, of byte masks multiples of 4; a non-zero stride holds the member's slice.
+ *
+ * Limits (VPC_ERR_SHAPE / VPC_ERR_ARG outside them, never a fault): fp32, plain encoder, d % 4 == 0, d <= 128, L <= 15, tiles per
+ * member = ceil(B / 16) <= 2 x CUs as vpc_step_small_f32, and G x tiles <= VPC_MULTI_MAX_BLOCKS workgroups; the caller's partial-block
+ * strides must hold `tiles` blocks per member (8192 workgroups admit G = 2048 at B = 64; a block is ~193 KB of partials).
+ * order: 0 = workgroup id g * tiles + t; 1 = members partitioned over (id % 8), all tiles of a member on ids of one residue (the
+ * workgroups that share an XCD's L2 - a speed choice, the results are the same). */
+#define VPC_MULTI_MAX_BLOCKS 8192
+typedef struct VpcMember {
+    float cA[2], cE[2], bq, bp, cr, wml; /* loss coefficients (cA[1] = cE[1] = 0 for npass 1) */
+    float keep_prob;                     /* mask_p keep probability */
+    float lr;                            /* Adam learning rate */
+    unsigned long long seed;             /* Philox seed of the member's draws */
+    int use_maskB;                       /* != 0: the E terms of pass 0 use mask & ~mask_p (maskB = {mask_p, NULL}) */
+    int reserved[3];
+} VpcMember;
+enum { VPC_MS_X = 0, VPC_MS_MASK, VPC_MS_MASK_P, VPC_MS_EPS, VPC_MS_IMG, VPC_MS_PARTE, VPC_MS_PARTD, VPC_MS_LOSS, VPC_MS_PARAM,
+       VPC_MS_COUNT };
+/* draw == 0: mask_p and the eps planes are given; draw != 0: drawn in the launch (mask_p = mask & keep, then the normals). */
+int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                             const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                             unsigned long long offset_mask, unsigned long long offset_eps, float inv_B, float x_logvar,
+                             float* partE, float* partD, double* loss_partials, const long* strides, long B, int d, int L,
+                             int order, void* stream);
+/* vpc_reduce_step_adam with blockIdx.y = member (train.py:114-117 per member): member g's `blocks` partial blocks -> row g of
+ * grad_out (same summation order), its loss terms -> out9[g][9] and accum[g] +=, Adam with the member's lr on row g of params /
+ * exp_avg / exp_avg_sq (rows VPC_MS_PARAM floats apart) and the re-pack of ITS image (pack_idx shared, img rows VPC_MS_IMG apart).
+ * The step count (bias corrections) is shared.  inv_maps (vpc_build_inverse_maps) is required. */
+int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials, int blocks,
+                               long enc_stride, long dec_stride, const long* strides, const int* inv_maps,
+                               const VpcMember* members, int G, float* grad_out, long B, int d, float* out9, float* accum,
+                               float* params, float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, long step,
+                               const int* pack_idx, float* img, void* stream);
+
 /* ---- MIWAE path: MIWAE / Reg_MIWAE (csrc/vpc_miw.hip) ------------------------------------------------------------
  * Reference: src/models/VAE.py:3011-3134 and :3137-3301.  Encoder d->128->128 ReLU -> [mean L | raw L] and decoder
  * L->128->128 ReLU -> [mean d | scale d | df d] run on vpc_linear_fwd / dgrad / wgrad (ACT_RELU, last layer ACT_NONE);

@@ -267,6 +267,41 @@ __global__ __launch_bounds__(256) void reduce_step_v2_kernel(const float* __rest
         }
     }
 }
+// the same launch for G members (ensemble step, include/vpc.h): blockIdx.y = member.  Member g's pointers are member 0's plus
+// g x the member strides, its loss coefficients and learning rate come from record g of the member table; the bodies, and so the
+// summation order and Adam's rounding sequence, are those of the single-model launch.
+struct ReduceMultiArgs {
+    const float* partE; const float* partD; const double* lp;
+    const int* invE; const int* invD;
+    float* grad; float* out9; float* accum;
+    const VpcMember* members;
+    AdamFuse adam;  // member 0's rows; lr from the table
+    long strideE, strideD;           // floats per partial block
+    long sE, sD, sL, sP, sI;         // member strides (elements)
+    double nll_const, inv_B;
+    int nb;
+};
+__global__ __launch_bounds__(256) void reduce_step_multi_kernel(ReduceMultiArgs a) {
+    __shared__ f32x4 shf[32][8];
+    __shared__ double shd[32][LOSS_TERMS];
+    __shared__ double s[LOSS_TERMS];
+    const long g = blockIdx.y;
+    const VpcMember* r = a.members + g;
+    const int nE4 = (int)(a.strideE >> 2), nD4 = (int)(a.strideD >> 2);
+    const int gE = (nE4 + 7) / 8, gD = (nD4 + 7) / 8;
+    const int b = blockIdx.x;
+    if (b < gE + gD) {
+        AdamFuse adam = a.adam;
+        adam.param += g * a.sP; adam.m += g * a.sP; adam.v += g * a.sP; adam.img += g * a.sI;
+        adam.lr = r->lr;
+        float* grad = a.grad + g * a.sP;
+        if (b < gE) reduce_body_v2(a.partE + g * a.sE, a.nb, a.strideE, a.invE, grad, nE4, b, shf, &adam);
+        else reduce_body_v2(a.partD + g * a.sD, a.nb, a.strideD, a.invD, grad, nD4, b - gE, shf, &adam);
+    } else {
+        const LossCoef k{r->cA[0], r->cE[0], r->cA[1], r->bq, r->bp, r->cr, r->wml, a.nll_const, a.inv_B};
+        finalize_body(a.lp + g * a.sL, a.nb, k, a.out9 + g * 9, a.accum + g, shd, s);
+    }
+}
 // inverse maps (block position -> flat parameter index, -1 for padding): built by the explicit entry point
 // vpc_build_inverse_maps into a caller-owned buffer [enc_stride | dec_stride] ints (the library keeps no state)
 __global__ void inv_fill_kernel(int* __restrict__ inv, long n) {
@@ -752,6 +787,39 @@ extern "C" int vpc_reduce_step_adam_bf16c(const float* enc_partials, int enc_blo
     hipLaunchKernelGGL(reduce_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
                        enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, grad_out, n_enc, n, loss_partials,
                        loss_blocks, k, out9, accum, (long long*)nullptr, 0LL, A);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials,
+                                          int blocks, long enc_stride, long dec_stride, const long* strides, const int* inv_maps,
+                                          const VpcMember* members, int G, float* grad_out, long B, int d, float* out9,
+                                          float* accum, float* params, float* exp_avg, float* exp_avg_sq, float beta1,
+                                          float beta2, float eps, long step, const int* pack_idx, float* img, void* stream) {
+    if (!enc_partials || !dec_partials || !loss_partials || !strides || !inv_maps || !members || !grad_out || !out9 || !accum)
+        return VPC_ERR_ARG;
+    if (!params || !exp_avg || !exp_avg_sq || !pack_idx || !img || step < 1) return VPC_ERR_ARG;
+    if (G < 1 || G > 65535 || blocks <= 0 || (long)G * blocks > VPC_MULTI_MAX_BLOCKS || enc_stride <= 0 || dec_stride <= 0 ||
+        B <= 0 || d <= 0)
+        return VPC_ERR_ARG;
+    const long sE = strides[VPC_MS_PARTE], sD = strides[VPC_MS_PARTD], sL = strides[VPC_MS_LOSS], sP = strides[VPC_MS_PARAM],
+               sI = strides[VPC_MS_IMG];
+    if (!inv_usable(inv_maps, enc_partials, enc_stride, dec_partials, dec_stride) || sE % 4 || sD % 4) return VPC_ERR_ARG;
+    if (sE < blocks * enc_stride || sD < blocks * dec_stride || sL < (long)blocks * LOSS_TERMS || sP <= 0 || sI <= 0)
+        return VPC_ERR_ARG;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    ReduceMultiArgs a{};
+    a.partE = enc_partials; a.partD = dec_partials; a.lp = loss_partials;
+    a.invE = inv_maps; a.invD = inv_maps + enc_stride;
+    a.grad = grad_out; a.out9 = out9; a.accum = accum; a.members = members;
+    a.adam = AdamFuse{params, exp_avg, exp_avg_sq, pack_idx, img, 0.f, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 0};
+    a.strideE = enc_stride; a.strideD = dec_stride;
+    a.sE = sE; a.sD = sD; a.sL = sL; a.sP = sP; a.sI = sI;
+    a.nll_const = 0.91893853320467274178 * (double)B * (double)d;
+    a.inv_B = 1.0 / (double)B;
+    a.nb = blocks;
+    const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8 + 1);
+    hipLaunchKernelGGL(reduce_step_multi_kernel, dim3(grid2, G), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

@@ -107,385 +107,8 @@ __device__ __forceinline__ f32x4 mmW(const f32x4 (&a)[KT], const f32x4 (&in)[KT]
 
 template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_kernel(SmallArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    auto buf = [&](int b) { return lds + b * SBUF; };
-    float* red = lds + B_COUNT * SBUF;
-    constexpr int S1 = s_for_tiles(DT);
-    const EncImg ei(DT);
-    const DecImg di(DT);
-    // (re-derived from opaque base pointers in every tile / pass: the weights never change during the launch, and hipcc
-    // otherwise hoists the global fragment loads of ALL layers out of the loops - 900 bytes of scratch per lane)
-    const float *W1, *b1, *W2, *W3, *W4, *W5, *W6;
-    auto weights = [&]() {
-        const float* e_ = a.enc_img;
-        const float* d_ = a.dec_img;
-        asm volatile("" : "+s"(e_), "+s"(d_)::"memory");
-        W1 = e_ + ei.oW1; b1 = e_ + ei.ob1; W2 = e_ + ei.oW2; W3 = e_ + ei.oW3;
-        W4 = d_ + di.oW4; W5 = d_ + di.oW5; W6 = d_ + di.oW6;
-    };
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const bool two = a.npass == 2;
-    const float inv_s2 = expf(-a.x_logvar), half_lv = 0.5f * a.x_logvar;
-    constexpr float HL2PI = 0.91893853320467274f;
-
-    // ONE 16-row tile per workgroup (the host launches one workgroup per tile): the decoder-side gradient accumulators live
-    // through the decoder phases of both passes, are written out, and only then the encoder-side ones come to life for the
-    // encoder backward of both passes - everything those need (x * mask, h1, h2 and the seeds of both passes) is still in LDS.
-    // (All 100 accumulators beside two stages' worth of weight fragments do not fit 256 registers.)
-    f32x4 acc6[H1T], acc5[H2T], acc4 = zero4();
-#pragma unroll
-    for (int t = 0; t < H1T; ++t) acc6[t] = zero4();
-#pragma unroll
-    for (int t = 0; t < H2T; ++t) acc5[t] = zero4();
-    float S_A0 = 0.f, S_E0 = 0.f, S_A1 = 0.f, S_kl0q = 0.f, S_kl0p = 0.f, S_klr = 0.f, S_zll = 0.f;
-
-    if (a.draw) {
-        // ---- the step's draws for this tile's rows (same Philox counters and values as vpc_draw_step: vpc_rng.h)
-        const long row0 = (long)blockIdx.x * 16;
-        const long nrow = a.B - row0 < 16 ? a.B - row0 : 16;
-        uint64_t off_m = a.off_mask, off_e = a.off_eps;
-        if (a.state) { off_m += (uint64_t)a.state[1]; off_e += (uint64_t)a.state[1]; }
-        if (a.mask_in) {  // mask_p bytes [row0 d, (row0 + nrow) d): every 8-byte Philox group that touches them (a group on a
-                          // tile boundary is written by both neighbours - the same bytes)
-            const long lo = row0 * a.d + (a.mask_elem_lo & 7), hi = (row0 + nrow) * a.d + (a.mask_elem_lo & 7);
-            const long g0 = lo / MASK_PER_CALL, g1 = (hi + MASK_PER_CALL - 1) / MASK_PER_CALL;
-            for (long g = g0 + threadIdx.x; g < g1; g += THREADS)
-                draw_mask_body(a.mask_in, const_cast<uint8_t*>(a.m[1]), a.B * (long)a.d, a.keep_prob, a.seed, off_m, g, a.mask_elem_lo);
-        }
-        const long plane = a.B * 16, nplanes = a.n_eps / plane;
-        for (long i = threadIdx.x; i < nplanes * nrow * 4; i += THREADS) {  // 4 groups of 4 normals per row and plane
-            const long pl = i / (nrow * 4), rem = i - pl * nrow * 4;
-            fill_normal_body(a.eps_out, a.n_eps, a.seed, off_e, (pl * plane + row0 * 16) / 4 + rem, a.shard);
-        }
-        __syncthreads();  // (a fence: the stores above are visible to the loads below)
-    }
-    {
-        const int tile = blockIdx.x;
-        const long row0 = (long)tile * 16;
-        const bool ok = row0 + c < a.B;
-        // ---- this wave's column tile of x and of the mask words of both passes (range-checked: rows past B read 0; the last
-        // tile's columns past d read column 0 and have their mask words cleared)
-        const bool colok = 16 * w + 4 * q + 3 < a.d;
-        f32x4 xv = zero4();
-        uint32_t mwq = 0, mwp = 0;
-        if (w < DT) {
-            const int vo = c * a.d + (colok ? 16 * w + 4 * q : 0);
-            xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rows_rsrc(a.x, row0, a.B, a.d), 4 * vo, 0, 0));
-            const long rem = (a.B - row0) * (long)a.d;
-            const uint32_t rec = rem > 0xffffffffL ? 0xffffffffu : (uint32_t)rem;
-            mwq = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.m[0]) + row0 * a.d, 0, rec, 0x00020000), vo, 0, 0);
-            if (two)
-                mwp = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.m[1]) + row0 * a.d, 0, rec, 0x00020000), vo, 0, 0);
-            if (!colok) { mwq = 0; mwp = 0; }
-        }
-        auto ld_lat = [&](const float* base) -> f32x4 {  // [B][16] padded latent-width array; NULL reads 0
-            return ld_rows(rows_rsrc(base ? base : a.x, row0, base ? a.B : row0, 16), c, 16, 4 * q);
-        };
-        int cc = c, qq = q;
-        launder(cc, qq);
-        // ================================================================ E: encoder forward of both passes
-        // (every stage requests the weight fragments of the NEXT stage before it computes: a stage is ~30 MFMAs, an L2 round
-        // trip as long as that; lds_barrier() leaves those loads in flight)
-        for (int p = 0; p < a.npass; ++p) {
-            weights();
-            float* X = buf(p == 0 ? B_XQ : B_XP);
-            float* H1b = buf(p == 0 ? B_H1Q : B_H1P);
-            float* H2b = buf(p == 0 ? B_H2Q : B_H2P);
-            f32x4 fW1[DT], fW2[H1T], fW3[H2T], bias1 = zero4();
-            if (w < H1T) {
-                ldW<DT, S1>(W1, w, cc, qq, fW1);
-                bias1 = *reinterpret_cast<const f32x4*>(b1 + 16 * w + 4 * qq);
-            }
-            if (w < DT) st_act(X, w, cc, qq, xv * mask_to_f32(p == 0 ? mwq : mwp));  // x.float() * mask  (VAE.py:388)
-            if (w < H2T) ldW<H1T, 128>(W2, w, cc, qq, fW2);
-            lds_barrier();
-            launder(cc, qq);
-            if (w < H1T) {
-                f32x4 in[DT];
-#pragma unroll
-                for (int t = 0; t < DT; ++t) in[t] = ld_act(X, t, cc, qq);
-                st_act(H1b, w, cc, qq, relu4(mmW<DT>(fW1, in, bias1)));
-            }
-            if (w < 2) ldW<H2T, 64>(W3, w, cc, qq, fW3);
-            lds_barrier();
-            launder(cc, qq);
-            if (w < H2T) {
-                f32x4 in[H1T];
-#pragma unroll
-                for (int t = 0; t < H1T; ++t) in[t] = ld_act(H1b, t, cc, qq);
-                st_act(H2b, w, cc, qq, relu4(mmW<H1T, NK1>(fW2, in, zero4())));
-            }
-            lds_barrier();
-            launder(cc, qq);
-            if (w < 2) {  // wave 0: mean tile, wave 1: logvar tile -> ML tiles 2 p, 2 p + 1
-                f32x4 in[H2T];
-#pragma unroll
-                for (int t = 0; t < H2T; ++t) in[t] = ld_act(H2b, t, cc, qq);
-                f32x4 o = mmW<H2T, NK2>(fW3, in, zero4());
-                if (!ok) o = zero4();  // rows past B: statistics 0
-                st_act(buf(B_ML), 2 * p + w, cc, qq, o);
-            }
-        }
-        lds_barrier();
-        launder(cc, qq);
-        // ================================================================ per pass: decoder, loss, all backward
-        for (int p = 0; p < a.npass; ++p) {
-            weights();
-            const float* X = buf(p == 0 ? B_XQ : B_XP);
-            const float* H1b = buf(p == 0 ? B_H1Q : B_H1P);
-            const float* H2b = buf(p == 0 ? B_H2Q : B_H2P);
-            f32x4 fW4[1], fW5[H2T], fW6[H1T], fT6[DT], fT5[H1T], fT4[H2T];
-            float* DML = buf(p == 0 ? B_DMLQ : B_DMLP);
-            if (w < H2T) ldW<1, S4>(W4, w, cc, qq, fW4);
-            if (w < H1T) ldW<H2T, 64>(W5, w, cc, qq, fW5);
-            const f32x4 mu = ld_act(buf(B_ML), 2 * p, cc, qq), lv = ld_act(buf(B_ML), 2 * p + 1, cc, qq);
-            const f32x4 e = ld_lat(a.eps[p]);
-            if (w == 0) {  // z = mean + eps * exp(logvar / 2); z[L] = 1 drives the bias chain
-                f32x4 z;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    z[j] = mu[j] + ((4 * qq + j < a.L) ? e[j] : 0.f) * __expf(0.5f * lv[j]);
-                    if (4 * qq + j == a.L) z[j] = 1.f;
-                }
-                st_act(buf(B_Z), 0, cc, qq, z);
-            }
-            lds_barrier();
-            launder(cc, qq);
-            if (w < H2T) {
-                const f32x4 in[1] = {ld_act(buf(B_Z), 0, cc, qq)};
-                st_act(buf(B_G1), w, cc, qq, relu4(mmW<1>(fW4, in, zero4())));
-            }
-            if (w < DT) ldW<H1T, 128>(W6, w, cc, qq, fW6);
-            lds_barrier();
-            launder(cc, qq);
-            if (w < H1T) {
-                f32x4 in[H2T];
-#pragma unroll
-                for (int t = 0; t < H2T; ++t) in[t] = ld_act(buf(B_G1), t, cc, qq);
-                st_act(buf(B_G2), w, cc, qq, relu4(mmW<H2T, NK2>(fW5, in, zero4())));
-            }
-            lds_barrier();
-            launder(cc, qq);
-            if (w < DT) {  // output tile w: forward, loss terms, d / d pre-activation
-                f32x4 in[H1T];
-#pragma unroll
-                for (int t = 0; t < H1T; ++t) in[t] = ld_act(buf(B_G2), t, cc, qq);
-                const f32x4 pre = mmW<H1T, NK1>(fW6, in, zero4());
-                const uint32_t ua = p == 0 ? mwq : mwp;
-                const uint32_t ub = a.mB[p] ? (p == 0 ? mwp : mwq) : ua;  // (host: the second mask is the other pass's)
-                const f32x4 mA = mask_to_f32(ua), mE = mask_to_f32(ua & ~ub);
-                const float kA = a.cA[p] * inv_s2 * a.inv_B, kE = a.cE[p] * inv_s2 * a.inv_B, hinv_s2 = 0.5f * inv_s2;
-                f32x4 dp;
-                float sa = 0.f, se = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float xh = fast_sigmoid(pre[j]);
-                    const float diff = xh - xv[j];
-                    const float t = diff * diff * hinv_s2 + half_lv;
-                    sa += mA[j] * t;
-                    se += mE[j] * t;
-                    dp[j] = (kA * mA[j] + kE * mE[j]) * diff * (xh - xh * xh);
-                }
-                if (p == 0) { S_A0 += sa; S_E0 += se; } else { S_A1 += sa; }
-                st_act(buf(B_DP), w, cc, qq, dp);
-            }
-            if (w < H1T) ldWT<DT, 128>(W6, w, cc, qq, fT6);  // dg2's fragments
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dW6~ (wave w: out tile w, 7 in tiles)  |  dg2 = relu'(g2) * (W6~^T dpre) (waves 0-6: tile w)
-            if (w < DT) {
-#pragma unroll
-                for (int nt = 0; nt < H1T; ++nt) acc6[nt] = wgrad16(buf(B_DP), w, buf(B_G2), nt, acc6[nt], cc, qq);
-            }
-            if (w < H1T) {
-                f32x4 in[DT];
-#pragma unroll
-                for (int t = 0; t < DT; ++t) in[t] = ld_act(buf(B_DP), t, cc, qq);
-                st_act(buf(B_DG2), w, cc, qq, gate4(mmW<DT>(fT6, in, zero4()), ld_act(buf(B_G2), w, cc, qq)));
-            }
-            if (w < H2T) ldWT<H1T, 64, NK1>(W5, w, cc, qq, fT5);  // dg1's fragments
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dW5~ (wave w: in tile w & 3 of out tiles 4 (w >> 2) .. + 3)  |  dg1 (waves 0-3)
-            {
-                const int nt5 = w & 3, mt5 = 4 * (w >> 2);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < 3 || w < 4) acc5[i] = wgrad16(buf(B_DG2), mt5 + i, buf(B_G1), nt5, acc5[i], cc, qq);
-            }
-            if (w < H2T) {
-                f32x4 in[H1T];
-#pragma unroll
-                for (int t = 0; t < H1T; ++t) in[t] = ld_act(buf(B_DG2), t, cc, qq);
-                st_act(buf(B_DG1), w, cc, qq, gate4(mmW<H1T, NK1>(fT5, in, zero4()), ld_act(buf(B_G1), w, cc, qq)));
-            }
-            if (w == 4) ldWT<H2T, S4, NK2>(W4, 0, cc, qq, fT4);  // dz's fragments
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dW4~ (waves 0-3: out tile w)  |  wave 4: dz, KL terms, seeds on (mean | logvar) -> DML
-            if (w < H2T) acc4 = wgrad16(buf(B_DG1), w, buf(B_Z), 0, acc4, cc, qq);
-            if (w == 4) {
-                f32x4 in[H2T];
-#pragma unroll
-                for (int t = 0; t < H2T; ++t) in[t] = ld_act(buf(B_DG1), t, cc, qq);
-                const f32x4 dz = mmW<H2T, NK2>(fT4, in, zero4());
-                const f32x4 mo = two ? ld_act(buf(B_ML), 2 * (1 - p), cc, qq) : zero4();
-                const f32x4 lo = two ? ld_act(buf(B_ML), 2 * (1 - p) + 1, cc, qq) : zero4();
-                f32x4 dmu, dlv;
-                const float b0 = (p == 0) ? a.bq : a.bp;
-                const float sgn = (p == 0) ? 1.f : -1.f;
-                const float crr = two ? a.cr : 0.f;
-                float kl0 = 0.f, klr = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float elv = __expf(lv[j]);
-                    kl0 += 0.5f * (elv + mu[j] * mu[j] - 1.f - lv[j]);
-                    const float mq = (p == 0) ? mu[j] : mo[j], lq = (p == 0) ? lv[j] : lo[j];
-                    const float mp = (p == 0) ? mo[j] : mu[j], lp = (p == 0) ? lo[j] : lv[j];
-                    const float diff = mq - mp, eip = __expf(-lp), r = __expf(lq - lp);
-                    klr += 0.5f * (r + diff * diff * eip - 1.f - (lq - lp));
-                    const float dm = b0 * mu[j] + sgn * crr * diff * eip;
-                    const float dl = b0 * 0.5f * (elv - 1.f) + crr * 0.5f * ((p == 0) ? (r - 1.f) : (1.f - r - diff * diff * eip));
-                    dmu[j] = dm * a.inv_B;
-                    dlv[j] = dl * a.inv_B;
-                }
-                if (p == 0) { S_kl0q += kl0; if (two) S_klr += klr; } else { S_kl0p += kl0; }
-                if (two && a.wml != 0.f) {  // ml_reg: extra rsample z' of q scored under p (VAE.py:435-440)
-                    const f32x4 e3 = ld_lat(a.eps_ml);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const bool live = ok && 4 * qq + j < a.L;
-                        const float e3j = (4 * qq + j < a.L) ? e3[j] : 0.f;
-                        const float mq = (p == 0) ? mu[j] : mo[j], lq = (p == 0) ? lv[j] : lo[j];
-                        const float mp = (p == 0) ? mo[j] : mu[j], lp = (p == 0) ? lo[j] : lv[j];
-                        const float sq = __expf(0.5f * lq), eip = __expf(-lp);
-                        const float dlt = mq + e3j * sq - mp;
-                        const float g = a.wml * dlt * eip * a.inv_B;
-                        if (p == 0) {
-                            if (live) S_zll += -HL2PI - 0.5f * lp - 0.5f * dlt * dlt * eip;
-                            dmu[j] += g;
-                            dlv[j] += g * e3j * 0.5f * sq;
-                        } else {
-                            dmu[j] -= g;
-                            dlv[j] += live ? a.wml * (0.5f - 0.5f * dlt * dlt * eip) * a.inv_B : 0.f;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float ef = (4 * qq + j < a.L) ? e[j] * 0.5f * __expf(0.5f * lv[j]) : 0.f;
-                    dmu[j] = (4 * qq + j < a.L) ? dmu[j] + dz[j] : 0.f;  // columns >= L carry no gradient (dz's column L is db4)
-                    dlv[j] = (4 * qq + j < a.L) ? dlv[j] + dz[j] * ef : 0.f;
-                }
-                st_act(DML, 0, cc, qq, dmu);
-                st_act(DML, 1, cc, qq, dlv);
-            }
-            lds_barrier();
-            launder(cc, qq);
-        }
-        // ================================================================ decoder partial block and the loss terms
-        {
-            float* part = a.partD + (long)blockIdx.x * DEC_PART + (long)(w & 3) * DEC_GREGS * 64 + lane;
-            const int hi = w >> 2;
-#pragma unroll
-            for (int nt = 0; nt < H1T; ++nt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[(28 * hi + 4 * nt + j) * 64] = (w < DT) ? acc6[nt][j] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float* p5 = a.partD + (long)blockIdx.x * DEC_PART + (long)i * DEC_GREGS * 64 + lane;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) p5[(56 + 16 * hi + 4 * (w & 3) + j) * 64] = (i < 3 || w < 4) ? acc5[i][j] : 0.f;
-            }
-            if (w < H2T) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[(88 + j) * 64] = acc4[j];
-            }
-            const float s[LOSS_TERMS] = {S_A0, S_E0, S_A1, S_kl0q, S_kl0p, S_klr, S_zll, 0.f};
-#pragma unroll
-            for (int i = 0; i < LOSS_TERMS; ++i) {
-                const float v = wave_sum_dpp(s[i]);
-                if (lane == 0) red[w * LOSS_TERMS + i] = v;
-            }
-            lds_barrier();
-            if (threadIdx.x < LOSS_TERMS) {
-                double t = 0.0;
-                for (int k = 0; k < WAVES; ++k) t += (double)red[k * LOSS_TERMS + threadIdx.x];
-                a.loss_part[(long)blockIdx.x * LOSS_TERMS + threadIdx.x] = t;
-            }
-        }
-        // ================================================================ encoder backward of both passes
-        f32x4 acc1[H1T], acc2[H2T], acc3 = zero4(), dbacc = zero4();
-#pragma unroll
-        for (int t = 0; t < H1T; ++t) acc1[t] = zero4();
-#pragma unroll
-        for (int t = 0; t < H2T; ++t) acc2[t] = zero4();
-        for (int p = 0; p < a.npass; ++p) {
-            weights();
-            const float* X = buf(p == 0 ? B_XQ : B_XP);
-            const float* H1b = buf(p == 0 ? B_H1Q : B_H1P);
-            const float* H2b = buf(p == 0 ? B_H2Q : B_H2P);
-            const float* DML = buf(p == 0 ? B_DMLQ : B_DMLP);
-            f32x4 fT3[2], fT2[H2T];
-            if (w < H2T) ldWT<2, 64>(W3, w, cc, qq, fT3);    // dh2's fragments
-            if (w < H1T) ldWT<H2T, 128, NK2>(W2, w, cc, qq, fT2);  // dh1's fragments
-            // ---- dW3~ (wave w: out tile w >> 2, in tile w & 3)  |  dh2 (waves 0-3)
-            acc3 = wgrad16(DML, w >> 2, H2b, w & 3, acc3, cc, qq);
-            if (w < H2T) {
-                const f32x4 in[2] = {ld_act(DML, 0, cc, qq), ld_act(DML, 1, cc, qq)};
-                st_act(buf(B_DH2), w, cc, qq, gate4(mmW<2>(fT3, in, zero4()), ld_act(H2b, w, cc, qq)));
-            }
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dW2~ (waves 0-6: in tile w, 4 out tiles)  |  dh1 (waves 0-6), db1 += column sums of dh1
-            if (w < H1T) {
-#pragma unroll
-                for (int mt = 0; mt < H2T; ++mt) acc2[mt] = wgrad16(buf(B_DH2), mt, H1b, w, acc2[mt], cc, qq);
-                f32x4 in[H2T];
-#pragma unroll
-                for (int t = 0; t < H2T; ++t) in[t] = ld_act(buf(B_DH2), t, cc, qq);
-                const f32x4 dh1 = gate4(mmW<H2T, NK2>(fT2, in, zero4()), ld_act(H1b, w, cc, qq));
-                st_act(buf(B_DH1), w, cc, qq, dh1);
-                dbacc += dh1;  // per-lane (row c) running sums; the sum over the rows happens once, at the end
-            }
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dW1 (wave w < DT: in tile w, 7 out tiles)
-            if (w < DT) {
-#pragma unroll
-                for (int mt = 0; mt < H1T; ++mt) acc1[mt] = wgrad16(buf(B_DH1), mt, X, w, acc1[mt], cc, qq);
-            }
-            lds_barrier();
-            launder(cc, qq);
-        }
-        // ================================================================ encoder partial block
-        {
-            float* part = a.partE + (long)blockIdx.x * ENC_PART + (long)w * GREGS * 64 + lane;
-#pragma unroll
-            for (int mt = 0; mt < H1T; ++mt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[(4 * mt + j) * 64] = (w < DT) ? acc1[mt][j] : 0.f;
-#pragma unroll
-            for (int mt = 0; mt < H2T; ++mt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) part[(28 + 4 * mt + j) * 64] = (w < H1T) ? acc2[mt][j] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) part[(44 + j) * 64] = acc3[j];
-            // db1[16 w + 4 q + j] = sum over the 16 rows (lanes c) of dbacc: DPP butterfly inside each 16-lane row
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v = dbacc[j];
-                v += dpp_mov<0xB1>(v);
-                v += dpp_mov<0x4E>(v);
-                v += dpp_mov<0x141>(v);
-                v += dpp_mov<0x140>(v);
-                if (c == 0 && w < H1T) a.partE[(long)blockIdx.x * ENC_PART + WAVES * GREGS * 64 + 16 * w + 4 * q + j] = v;
-            }
-            if (w == 7 && lane < 16) a.partE[(long)blockIdx.x * ENC_PART + WAVES * GREGS * 64 + 112 + lane] = 0.f;
-        }
-    }
+    const unsigned tile_id = blockIdx.x;
+#include "vpc_small_body.h"
 }
 
 }  // namespace vpc
@@ -590,4 +213,151 @@ extern "C" int vpc_step_small_draw_f32(const float* x, const float* enc_img, con
                  EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch}};
     return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE,
                              partD, loss_partials, nblocks_out, B, d, L, dr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ensemble: G independent models of one architecture in ONE launch (imputation.py:21-39 wraps train.py:28-117 in loops over
+// missing rate, alpha and split: many runs of the same tiny model).  Workgroup (t, g) builds member g's SmallArgs - member 0's
+// pointers plus g x the member strides, the coefficients / keep probability / seed of record g of the device-resident member
+// table - and runs the tile body (vpc_small_body.h) on tile t: the single-model kernel's body, so member g's partial blocks, loss terms and draws
+// are bit for bit those of its stand-alone step.
+namespace vpc {
+struct SmallMultiArgs {
+    SmallArgs base;             // member 0's buffers, and everything the members share
+    const VpcMember* members;   // [G] records
+    long sx, sm, smp, seps, simg, sE, sD, sL;  // member strides in elements (sx / sm 0: one batch shared by all members)
+    unsigned G, tiles;
+    int order;
+};
+// The arguments of one member, as the tile body names them (the fields of SmallArgs), built in registers at kernel entry.  The
+// per-pass arrays are pairs picked by a select: a struct that lives in registers cannot be indexed with the pass counter (it
+// would be demoted to scratch).
+template <class T>
+struct PassPair {
+    T v0, v1;
+    __device__ __forceinline__ T operator[](int p) const { return p == 0 ? v0 : v1; }
+};
+struct MemberArgs {
+    const float* x;
+    const float* enc_img;
+    const float* dec_img;
+    PassPair<const uint8_t*> m, mB;
+    PassPair<float> cA, cE;
+    PassPair<const float*> eps;
+    const float* eps_ml;
+    float* partE;
+    float* partD;
+    double* loss_part;
+    float bq, bp, cr, wml, inv_B, x_logvar;
+    long B;
+    int d, L, npass;
+    int draw;
+    const uint8_t* mask_in;
+    float keep_prob;
+    float* eps_out; long n_eps;
+    unsigned long long seed, off_mask, off_eps;
+    const long long* state;
+    long mask_elem_lo;
+    EpsShard shard;
+};
+
+template <int DT>
+__global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArgs ma) {
+    // (tile, member) of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs by their linear id (x fastest).
+    //   order 0: grid (tiles, G), id = g * tiles + t - the tiles of a member land on different XCDs, every L2 sees every
+    //            member's images;
+    //   order 1: grid (8 x tiles, ceil(G / 8)), t = x / 8, g = 8 y + x % 8 - all tiles of a member sit on ids of one residue
+    //            mod 8, so a member's images are read through ONE L2 (the surplus workgroups of the last member group return).
+    unsigned mem, tile_;
+    if (ma.order == 0) {
+        mem = blockIdx.y;
+        tile_ = blockIdx.x;
+    } else {
+        tile_ = blockIdx.x >> 3;
+        mem = 8 * blockIdx.y + (blockIdx.x & 7);
+        if (mem >= ma.G) return;
+    }
+    const VpcMember* r = ma.members + mem;  // (uniform address: scalar loads)
+    const SmallArgs& b = ma.base;
+    MemberArgs a;
+    a.x = b.x + mem * ma.sx;
+    a.enc_img = b.enc_img + mem * ma.simg;
+    a.dec_img = b.dec_img + mem * ma.simg;
+    a.m.v0 = b.m[0] + mem * ma.sm;
+    a.m.v1 = b.m[1] ? b.m[1] + mem * ma.smp : nullptr;
+    a.mB.v0 = r->use_maskB ? a.m.v1 : nullptr;  // (the E terms' second mask is the other pass's: cE[0] != 0)
+    a.mB.v1 = nullptr;
+    a.cA.v0 = r->cA[0]; a.cA.v1 = r->cA[1]; a.cE.v0 = r->cE[0]; a.cE.v1 = r->cE[1];
+    // (the planes of a member follow each other and the draws are those of an unsharded stand-alone step - no device-side state,
+    // element offset 0, all B rows local: derived from eps[0], mask, B and constants instead of carried in registers)
+    a.eps.v0 = b.eps[0] + mem * ma.seps;
+    a.eps.v1 = b.eps[1] ? a.eps.v0 + b.B * 16 : nullptr;
+    a.eps_ml = b.eps_ml ? a.eps.v0 + 2 * b.B * 16 : nullptr;
+    a.partE = b.partE + mem * ma.sE;
+    a.partD = b.partD + mem * ma.sD;
+    a.loss_part = b.loss_part + mem * ma.sL;
+    a.bq = r->bq; a.bp = r->bp; a.cr = r->cr; a.wml = r->wml; a.inv_B = b.inv_B; a.x_logvar = b.x_logvar;
+    a.B = b.B; a.d = b.d; a.L = b.L; a.npass = b.npass;
+    a.draw = b.draw;
+    a.mask_in = b.mask_in ? a.m.v0 : nullptr;
+    a.keep_prob = r->keep_prob;
+    a.eps_out = const_cast<float*>(a.eps.v0);
+    a.n_eps = b.n_eps;
+    a.seed = r->seed; a.off_mask = b.off_mask; a.off_eps = b.off_eps;
+    a.state = nullptr; a.mask_elem_lo = 0; a.shard = EpsShard{b.B, b.B, 0, 16};
+    const unsigned tile_id = tile_;
+#include "vpc_small_body.h"
+}
+}  // namespace vpc
+
+extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                        const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                        unsigned long long offset_mask, unsigned long long offset_eps, float inv_B,
+                                        float x_logvar, float* partE, float* partD, double* loss_partials, const long* strides,
+                                        long B, int d, int L, int order, void* stream) {
+    if (!x || !mask || !eps || !enc_img || !dec_img || !members || !partE || !partD || !loss_partials || !strides) return VPC_ERR_ARG;
+    if (G < 1 || npass < 1 || npass > 2 || B <= 0 || order < 0 || order > 1) return VPC_ERR_ARG;
+    if (npass == 2 ? (!mask_p || nplanes < 2 || nplanes > 3) : nplanes != 1) return VPC_ERR_ARG;
+    if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img) || !aligned16(eps)) return VPC_ERR_ARG;
+    if ((uintptr_t)mask % 4 || (uintptr_t)mask_p % 4) return VPC_ERR_ARG;
+    const long tiles = (B + 15) / 16;
+    if (tiles > 2L * num_cus() || (long)G * tiles > VPC_MULTI_MAX_BLOCKS) return VPC_ERR_SHAPE;
+    const long sx = strides[VPC_MS_X], sm = strides[VPC_MS_MASK], smp = strides[VPC_MS_MASK_P], seps = strides[VPC_MS_EPS],
+               simg = strides[VPC_MS_IMG], sE = strides[VPC_MS_PARTE], sD = strides[VPC_MS_PARTD], sL = strides[VPC_MS_LOSS];
+    const long nx = B * (long)d, ne = (long)nplanes * B * 16;
+    // every member's slice inside its stride, 16-byte (masks: 4-byte) aligned; only read-only inputs may be shared (stride 0)
+    if ((sx != 0 && sx < nx) || sx % 4 || (sm != 0 && sm < nx) || sm % 4) return VPC_ERR_ARG;
+    if (npass == 2 && ((smp != 0 && smp < nx) || smp % 4 || (draw && smp == 0 && G > 1))) return VPC_ERR_ARG;
+    if ((seps != 0 && seps < ne) || seps % 4 || (draw && seps == 0 && G > 1)) return VPC_ERR_ARG;
+    if (simg <= 0 || simg % 4) return VPC_ERR_ARG;
+    if (sE < tiles * ENC_PART || sE % 4 || sD < tiles * DEC_PART || sD % 4 || sL < tiles * LOSS_TERMS) return VPC_ERR_ARG;
+    SmallMultiArgs ma{};
+    SmallArgs& a = ma.base;
+    a.x = x; a.enc_img = enc_img; a.dec_img = dec_img; a.partE = partE; a.partD = partD; a.loss_part = loss_partials;
+    a.inv_B = inv_B; a.x_logvar = x_logvar; a.B = B; a.d = d; a.L = L; a.npass = npass; a.ntiles = (int)tiles;
+    a.m[0] = mask;
+    a.eps[0] = eps;
+    if (npass == 2) { a.m[1] = mask_p; a.eps[1] = eps + B * 16; }
+    if (nplanes == 3) a.eps_ml = eps + 2 * B * 16;
+    if (draw) {  // the draws of vpc_step_small_draw_f32 on an unsharded batch: member g with ITS seed, in its own element space
+        a.draw = 1; a.mask_in = npass == 2 ? mask : nullptr; a.eps_out = eps; a.n_eps = ne;
+        a.off_mask = offset_mask; a.off_eps = offset_eps; a.state = nullptr; a.mask_elem_lo = 0;
+        a.shard = EpsShard{B, B, 0, 16};
+    }
+    ma.members = members;
+    ma.sx = sx; ma.sm = sm; ma.smp = smp; ma.seps = seps; ma.simg = simg; ma.sE = sE; ma.sD = sD; ma.sL = sL;
+    ma.G = (unsigned)G; ma.tiles = (unsigned)tiles; ma.order = order;
+    const dim3 grid = order == 0 ? dim3((unsigned)tiles, (unsigned)G) : dim3((unsigned)(8 * tiles), (unsigned)((G + 7) / 8));
+    hipStream_t s = (hipStream_t)stream;
+#define VPC_CASE(T)                                                                                        \
+    case T: {                                                                                              \
+        auto kern = step_small_multi_kernel<T>;                                                            \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), SMALL_LDS, s, ma);                             \
+        return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
+    }
+    switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
+#undef VPC_CASE
+    return VPC_ERR_SHAPE;
 }

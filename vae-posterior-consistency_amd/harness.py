@@ -4,6 +4,8 @@
   model_loader         src/utils/loaders.py:13-246   vae_type substring dispatch + checkpoint naming
   checkpoint_path      src/experiment_main/train.py:120-131
   train                src/experiment_main/train.py:13-133   epoch / batch loop, Adam(lr=1e-3), save at end
+  train_sweep          src/experiment_main/imputation.py:21-39  the drivers' loops over alpha / p_missingness / split around
+                                                             train(), as ensembles stepped by one pair of launches (ensemble.py)
   eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL
   eval_vae_mnar        src/experiment_main/evaluate.py:13-69    importance-weighted imputation RMSE (MNAR path)
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
@@ -221,6 +223,90 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
         torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
     print("Training is over!")
     return model
+
+
+def _save_checkpoint(model, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
+    path = checkpoint_path(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
+    os.makedirs(os.path.dirname(path), exist_ok=True)  # the reference never creates it
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
+
+
+def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
+                experiment_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), stage="train",
+                reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, save=True, verbose=True,
+                models=None, loaders=None):
+    """train() for a LIST of runs that differ in vae_type (the data split), alpha, p_missingness and seed - the drivers' loops
+    `for missing in [...]: for alpha in [...]:` around train() (src/experiment_main/imputation.py:21-39) as one call.
+    configs: one dict per member with the keys vae_type, alpha (1.0), p_missingness (30), seed (0).  data_loader_train: what
+    train() takes, shared by every member; or loaders = one such object per member (different splits), which must yield
+    equal batch shapes at every step.  models (optional): one pre-built model per member, as train(model=).
+    Plain Reg_VAE / vanilla_VAE members of one class and reg_type step together, one ensemble.EnsembleTrainer.step per batch
+    (a mixed list is split into such groups); every other family, and batches beyond the small-batch step, go through train()
+    one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints the
+    reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
+    from .ensemble import EnsembleTrainer
+
+    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
+    G = len(cfgs)
+    if models is not None and len(models) != G:
+        raise L.VpcError(f"{len(models)} models for {G} configurations")
+    if loaders is not None and len(loaders) != G:
+        raise L.VpcError(f"{len(loaders)} loaders for {G} configurations")
+    member_loader = (lambda g: loaders[g]) if loaders is not None else (lambda g: data_loader_train)
+    out = [None] * G
+    groups = {}
+    for g, c in enumerate(cfgs):
+        vt = c["vae_type"]
+        m = models[g] if models is not None else model_loader(
+            "train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters, max_epochs, train_k,
+            num_estimates, experiment_type, reg_type, vt, alpha=c["alpha"], p_missingness=c["p_missingness"])
+        m.to(device)
+        out[g] = m
+        small = type(m) in (Reg_VAE, vanilla_VAE) and not getattr(m, "_wide", False) and "with_drop" not in vt
+        if small:  # the batch must fit the small-batch step (larger ones fill the chip on their own)
+            first = next(iter(member_loader(g)[0]), None)
+            small = first is not None and first[0].reshape(-1, obs_dim).shape[0] <= ops.step_small_max_rows()
+        if not small:
+            train(member_loader(g), missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
+                  experiment_type, vt, train_k, num_estimates, max_epochs, device, c["alpha"], stage, c["p_missingness"],
+                  reg_type, beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
+            continue
+        rt = getattr(m, "reg_type", None)
+        ml_on = rt == "ml_reg" and c["alpha"] != 0.0  # (members of one step agree on whether the third eps plane is drawn)
+        groups.setdefault((type(m), rt, ml_on), []).append(g)
+    for idx in groups.values():
+        ms = [out[g] for g in idx]
+        ens = EnsembleTrainer(ms, lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
+        alphas = [cfgs[g]["alpha"] for g in idx]
+        pms = [cfgs[g]["p_missingness"] for g in idx]
+        for i in range(max_epochs):
+            if loaders is None:
+                for data_sample, mask in data_loader_train[0]:
+                    ens.step(data_sample.to(device).reshape(-1, obs_dim), mask.to(device).reshape(-1, obs_dim), epoch=i + 1,
+                             alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
+            else:
+                its = [iter(loaders[g][0]) for g in idx]
+                while True:
+                    batches = [next(it, None) for it in its]
+                    if all(b is None for b in batches):
+                        break
+                    if any(b is None for b in batches):
+                        raise L.VpcError("per-member loaders must have the same number of batches")
+                    if any(b[0].shape != batches[0][0].shape or b[1].shape != batches[0][1].shape for b in batches):
+                        raise L.VpcError("per-member loaders must yield equal batch shapes at every step")
+                    x = torch.stack([b[0].to(device).reshape(-1, obs_dim) for b in batches])
+                    mk = torch.stack([b[1].to(device).reshape(-1, obs_dim) for b in batches])
+                    ens.step(x, mk, epoch=i + 1, alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
+            totals = ens.epoch_total()
+            if verbose:
+                for g, total_loss in zip(idx, totals):
+                    print("Epoch: [{}/{}], Total Loss: {}".format(i, max_epochs, total_loss))
+        for g in idx:
+            if save:
+                _save_checkpoint(out[g], experiment_type, data_type, cfgs[g]["vae_type"], missing_rate, cfgs[g]["alpha"],
+                                 cfgs[g]["p_missingness"], reg_type)
+            print("Training is over!")
+    return out
 
 
 def result_paths(experiment_type, data_type, vae_type, loader_stage, missing_rate, alpha=0.5, p_missingness=30,

@@ -150,6 +150,29 @@ def step_small_draw_f32(x, enc_img, dec_img, masks, maskB, cA, cE, eps, eps_ml, 
     return nb.value
 
 
+def _member_strides(strides):
+    return (C.c_long * len(strides))(*[int(v) for v in strides])
+
+
+def step_small_multi_f32(x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask, offset_eps,
+                         inv_B, x_logvar, partE, partD, loss_part, strides, B, d, Ld, order=0):
+    """The small-batch step of G members in one launch (include/vpc.h: ensemble step).  Pointers are member 0's, `strides`
+    the VPC_MS_* member strides in elements, `members` the device-resident VpcMember table."""
+    check(lib().vpc_step_small_multi_f32(ptr(x), ptr(mask), ptr(mask_p), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members),
+                                         G, npass, nplanes, int(bool(draw)), int(offset_mask), int(offset_eps), inv_B, x_logvar,
+                                         ptr(partE), ptr(partD), ptr(loss_part), _member_strides(strides), B, d, Ld, int(order),
+                                         stream_ptr()), "vpc_step_small_multi_f32")
+
+
+def reduce_step_adam_multi(partE, partD, loss_part, blocks, strideE, strideD, strides, inv_maps, members, G, grad, B, d, out9,
+                           accum, params, m, v, beta1, beta2, eps, step, pack_idx, img):
+    """reduce_step_adam of G members in one launch (blockIdx.y = member; lr and loss coefficients from the member table)."""
+    check(lib().vpc_reduce_step_adam_multi(ptr(partE), ptr(partD), ptr(loss_part), blocks, strideE, strideD,
+                                           _member_strides(strides), ptr(inv_maps), ptr(members), G, ptr(grad), B, d, ptr(out9),
+                                           ptr(accum), ptr(params), ptr(m), ptr(v), beta1, beta2, eps, int(step), ptr(pack_idx),
+                                           ptr(img), stream_ptr()), "vpc_reduce_step_adam_multi")
+
+
 def step_fused_applicable(B, d, Ld, npass):
     return bool(lib().vpc_step_fused_applicable(int(B), d, Ld, npass))
 
