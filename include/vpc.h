@@ -115,22 +115,28 @@ int vpc_decoder_bwd(const float* z, const float* dxhat, const float* dec_img, fl
                     int* nblocks_out, long B, int d, int L, void* stream);
 
 /* ---- loss ---------------------------------------------------------------------------------------- */
-/* Both loss entry points evaluate (VAE.py:403-467, 469-494, 1171-1208)
+/* Every entry point that computes or finalises the loss evaluates ONE generic form (VAE.py:403-467, 469-494, 1171-1208;
+ * SURVEY.md Appendix A)
  *   loss * B = sum_p [ cA[p] * NLL(A_p, xhat_p) + cE[p] * NLL(A_p & ~B_p, xhat_p) ]
  *              + bq * KL(q || N(0,1)) + bp * KL(p || N(0,1)) + cr * KL(q || p) - wml * log N(z'; mu_p, var_p)
- * with NLL(m, xhat) = sum_ij [ 0.5 log 2pi + m_ij (0.5 x_logvar + (x_ij - xhat_ij)^2 / (2 exp(x_logvar))) ]
+ * whose coefficients travel as one record, VpcLossCoef `co` (host memory, read before the call returns; NULL is
+ * VPC_ERR_ARG; one pass: cA[1] = cE[1] = 0).  inv_B, x_logvar and npass stay arguments of their own.  It is also the head
+ * of a VpcMember record (ensemble step).
+ * Here NLL(m, xhat) = sum_ij [ 0.5 log 2pi + m_ij (0.5 x_logvar + (x_ij - xhat_ij)^2 / (2 exp(x_logvar))) ]
  * and z' = mean_q + eps_ml * exp(logvar_q / 2).  maskA/maskB are per-pass byte masks (maskB[p] may be
  * NULL).  Per-workgroup partial sums are written as doubles, loss_partials[nblocks][8]:
  *   0 S_A(pass 0)  1 S_E(pass 0)  2 S_A(pass 1)  3 KL0(q)  4 KL0(p)  5 KL(q||p)  6 loglik  7 S_notA(pass 0)
  * where S_* are the NLL sums WITHOUT the 0.5 log 2pi constants.  Seeds are d(loss)/d(.) times inv_B. */
+typedef struct VpcLossCoef {
+    float cA[2], cE[2], bq, bp, cr, wml;
+} VpcLossCoef; /* 32 bytes */
 
 /* K4: loss on materialised tensors (the model.loss(...) API).  dxhat/dmean/dlogvar NULL -> no seeds. */
 int vpc_loss_fwd_bwd(const float* x, int npass, const float* const* xhat, const uint8_t* const* maskA,
-                     const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* mean,
-                     const float* const* logvar, const float* eps_ml, float bq, float bp, float cr, float wml,
-                     float inv_B, float x_logvar, float* const* dxhat, float* const* dmean,
-                     float* const* dlogvar, double* loss_partials, int max_blocks, int* nblocks_out, long B, int d,
-                     int L, void* stream);
+                     const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                     const float* const* logvar, const float* eps_ml, float inv_B, float x_logvar,
+                     float* const* dxhat, float* const* dmean, float* const* dlogvar, double* loss_partials,
+                     int max_blocks, int* nblocks_out, long B, int d, int L, void* stream);
 
 /* Fused training path: reparameterise + decoder forward + loss + backward seeds + decoder backward in one
  * pass (nothing of size B x d is written).  Outputs the TOTAL seeds on the encoder outputs
@@ -138,18 +144,16 @@ int vpc_loss_fwd_bwd(const float* x, int npass, const float* const* xhat, const 
  * (term 7 unused).  mean / logvar / eps / eps_ml / dmean / dlogvar are padded [B][16] workspaces (lat_pitch must
  * be 16; pad entries of mean / logvar must be 0 as vpc_encoder_fwd writes them, pad entries of eps are ignored).  Replaces VAE.py:389-392 (rsample), 397-401, 403-467 and their autograd. */
 int vpc_decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
-                      const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* mean,
-                      const float* const* logvar, const float* const* eps, const float* eps_ml, float bq, float bp,
-                      float cr, float wml, float inv_B, float x_logvar, float* const* dmean,
-                      float* const* dlogvar, int lat_pitch, int precision, float* partials, double* loss_partials,
-                      int* nblocks_out, long B, int d, int L, void* stream);
+                      const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                      const float* const* logvar, const float* const* eps, const float* eps_ml, float inv_B,
+                      float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch, int precision,
+                      float* partials, double* loss_partials, int* nblocks_out, long B, int d, int L, void* stream);
 
 /* out9[0] = loss / B_global with the NLL constants of the B_local rows this rank processed (so that the
  * sum over data-parallel ranks is the loss of the concatenated batch), out9[1..8] = the 8 raw sums;
  * if accum != NULL, accum[0] += out9[0] (device-side epoch total, train.py:117 without a host sync). */
-int vpc_loss_finalize(const double* loss_partials, int nblocks, float cA0, float cE0, float cA1, float bq, float bp,
-                      float cr, float wml, long B_local, long B_global, int d, float* out9, float* accum,
-                      void* stream);
+int vpc_loss_finalize(const double* loss_partials, int nblocks, const VpcLossCoef* co, long B_local, long B_global,
+                      int d, float* out9, float* accum, void* stream);
 
 /* vpc_reduce_partials (encoder) + vpc_reduce_partials (decoder) + vpc_loss_finalize in ONE launch: the whole
  * post-backward reduction of the fused step.  grad_out[0, n_enc) from the encoder blocks, [n_enc, n) from the
@@ -165,30 +169,26 @@ int vpc_build_inverse_maps(const int* grad_idx, int n_enc, int n, long enc_strid
                            void* stream); /* inv_out: enc_stride + dec_stride ints (device) */
 int vpc_reduce_step(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
                     int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps, float* grad_out,
-                    int n_enc, int n,
-                    const double* loss_partials, int loss_blocks, float cA0, float cE0, float cA1, float bq, float bp,
-                    float cr, float wml, long B_local, long B_global, int d, float* out9, float* accum,
-                    long long* state, long long rng_inc, void* stream);
+                    int n_enc, int n, const double* loss_partials, int loss_blocks, const VpcLossCoef* co, long B_local,
+                    long B_global, int d, float* out9, float* accum, long long* state, long long rng_inc, void* stream);
 
 /* vpc_reduce_step + vpc_adam_step in ONE launch (single process, eager): Adam is elementwise, so the thread that
  * finishes gradient i updates parameter i (and its packed-image entry) on the spot.  Same result as the two
  * calls in sequence; `step` >= 1 is the optimiser step count of THIS update. */
 int vpc_reduce_step_adam(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
                          int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps, float* grad_out,
-                         int n_enc, int n,
-                         const double* loss_partials, int loss_blocks, float cA0, float cE0, float cA1, float bq,
-                         float bp, float cr, float wml, long B_local, long B_global, int d, float* out9, float* accum,
-                         float* params, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
-                         float eps, long step, const int* pack_idx, float* img, void* stream);
+                         int n_enc, int n, const double* loss_partials, int loss_blocks, const VpcLossCoef* co,
+                         long B_local, long B_global, int d, float* out9, float* accum, float* params, float* exp_avg,
+                         float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
+                         const int* pack_idx, float* img, void* stream);
 /* the same, re-packing the compact bf16 image of the whole-step kernel instead of the fp32 images: pack_idx_c / img_c of
  * vpc_step_build_indices_bf16 (a plain-bf16 step then needs no vpc_step_pack_weights_bf16 launch) */
 int vpc_reduce_step_adam_bf16c(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
                          int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps, float* grad_out,
-                         int n_enc, int n,
-                         const double* loss_partials, int loss_blocks, float cA0, float cE0, float cA1, float bq,
-                         float bp, float cr, float wml, long B_local, long B_global, int d, float* out9, float* accum,
-                         float* params, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
-                         float eps, long step, const int* pack_idx_c, float* img_c, void* stream);
+                         int n_enc, int n, const double* loss_partials, int loss_blocks, const VpcLossCoef* co,
+                         long B_local, long B_global, int d, float* out9, float* accum, float* params, float* exp_avg,
+                         float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
+                         const int* pack_idx_c, float* img_c, void* stream);
 
 /* ---- random draws (Philox4x32-10, counter = GLOBAL element-group index + offset) -------------------
  * Data parallel: a rank that holds rows [row_lo, row_lo + B_local) of a global batch passes
@@ -450,8 +450,8 @@ int vpc_step_layout_bf16(int d, int L, int* img_floats, int* lds_bytes);
 int vpc_step_build_indices_bf16(int d, int L, int* pack_idx_c, float* img_template_c);
 int vpc_step_pack_weights_bf16(const float* flat_params, const int* pack_idx_c, float* img_c, int n, void* stream);
 int vpc_step_fused_bf16(const float* x, const float* img_c, int npass, const uint8_t* const* mask,
-                        const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* eps,
-                        const float* eps_ml, float bq, float bp, float cr, float wml, float inv_B, float x_logvar,
+                        const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                        const float* eps_ml, float inv_B, float x_logvar,
                         float* partE, float* partD, double* loss_partials, float* workspace, int* nblocks_out, long B,
                         int d, int L, void* stream);
 
@@ -465,8 +465,8 @@ int vpc_step_fused_bf16(const float* x, const float* img_c, int npass, const uin
  * vpc_step_small_max_rows: batches up to this many rows take this path inside FusedTrainer (0 = off; env VPC_STEP_SMALL). */
 long vpc_step_small_max_rows(void);
 int vpc_step_small_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
-                       const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* eps,
-                       const float* eps_ml, float bq, float bp, float cr, float wml, float inv_B, float x_logvar, float* partE,
+                       const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                       const float* eps_ml, float inv_B, float x_logvar, float* partE,
                        float* partD, double* loss_partials, int* nblocks_out, long B, int d, int L, void* stream);
 /* vpc_draw_step + vpc_step_small_f32 in ONE launch: every workgroup draws the mask_p bytes (mask[1] = mask_in & keep; mask_in NULL:
  * none - vanilla_VAE) and the normals of ITS 16 rows (eps_out = eps[0], planes [B][16]: eps[1] and eps_ml follow it, n_eps floats
@@ -474,8 +474,8 @@ int vpc_step_small_f32(const float* x, const float* enc_img, const float* dec_im
  * (eps_pitch 16, eps_rows_local = B) as there -, stores them where the step reads them, and runs the step: the same draws
  * (train.py:53-55, VAE.py:389-392), one launch less at the batch sizes where a launch is a fifth of the step. */
 int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
-                            const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* eps,
-                            const float* eps_ml, float bq, float bp, float cr, float wml, float inv_B, float x_logvar,
+                            const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                            const float* eps_ml, float inv_B, float x_logvar,
                             float* partE, float* partD, double* loss_partials, int* nblocks_out, long B, int d, int L,
                             const uint8_t* mask_in, float keep_prob, float* eps_out, long n_eps, unsigned long long seed,
                             unsigned long long offset_mask, unsigned long long offset_eps, const long long* state,
@@ -512,7 +512,7 @@ int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* d
  * workgroups that share an XCD's L2 - a speed choice, the results are the same). */
 #define VPC_MULTI_MAX_BLOCKS 8192
 typedef struct VpcMember {
-    float cA[2], cE[2], bq, bp, cr, wml; /* loss coefficients (cA[1] = cE[1] = 0 for npass 1) */
+    VpcLossCoef co;                      /* loss coefficients (cA[1] = cE[1] = 0 for npass 1) */
     float keep_prob;                     /* mask_p keep probability */
     float lr;                            /* Adam learning rate */
     unsigned long long seed;             /* Philox seed of the member's draws */

@@ -481,8 +481,7 @@ def test_gradient_reduction_forms_agree():
     lay, (nbE, nb) = tr.lay, tr.last_blocks
     assert nbE == nb
     co = tr.coefficients(1, 0.7, 0.9, False)
-    args = (lay.n_enc, tr.loss_part, nb, co["cA"][0], co["cE"][0], co["cA"][1], co["bq"], co["bp"], co["cr"], co["wml"],
-            B, B, d)
+    args = (lay.n_enc, tr.loss_part, nb, co, B, B, d)
     res = []
     for shift in (0, 1, 2):  # 1: views that start 4 bytes into a buffer -> not 16-byte aligned -> gather form; 2: no map
         sh = shift & 1

@@ -59,8 +59,7 @@ def test_ctypes_prototypes_match_the_header():
         got = vpc._lib._PROTOS[name]
         assert len(got) == len(want), (name, len(got), len(want))
         for i, (g, w) in enumerate(zip(got, want)):
-            ok = g is w or (w is ctypes.c_void_p and g in (ctypes.c_void_p,)) or \
-                (g is ctypes.POINTER(ctypes.c_float) and w is ctypes.c_void_p)  # host float arrays (cA / cE)
+            ok = g is w  # (a struct pointer, VpcLossCoef / VpcMember, is a c_void_p on both sides)
             if w in (ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_long)) and g is ctypes.c_void_p:
                 ok = True  # int / long arrays passed as raw pointers
             assert ok, (name, i, g, w)
@@ -104,6 +103,20 @@ def test_bad_arguments_are_rejected_without_gpu():
     assert l.vpc_linear_wgrad_reduce(9, ptrs, Ms, Ns, Ks, ptrs, ptrs, acc, None) == 1
     assert l.vpc_nm_sample(None, 20, None, None, 10, 4, 2, 10, None) == 1
     assert l.vpc_linear_wgrad_scratch(0, 4, 4) == 0 and l.vpc_nm_loss_scratch(0, 4) == 0
+    # a NULL loss-coefficient record is refused by each of the nine entry points that take one, every other argument given
+    nb = ctypes.byref(ctypes.c_int())
+    step = (p, p, p, 1, ptrs, ptrs, None, ptrs, p, 1.0, 0.0, p, p, p, nb, 16, 16, 10)
+    assert l.vpc_step_small_f32(*step, None) == 1
+    assert l.vpc_step_small_draw_f32(*step, p, 0.7, p, 256, 0, 0, 0, None, 0, 16, 16, 0, 16, None) == 1
+    assert l.vpc_step_fused_bf16(p, p, 1, ptrs, ptrs, None, ptrs, p, 1.0, 0.0, p, p, p, p, nb, 128, 128, 10, None) == 1
+    assert l.vpc_loss_fwd_bwd(p, 1, ptrs, ptrs, ptrs, None, ptrs, ptrs, p, 1.0, 0.0, ptrs, ptrs, ptrs, p, 8, nb, 16, 16, 10, None) == 1
+    assert l.vpc_decoder_fused(p, p, 1, ptrs, ptrs, None, ptrs, ptrs, ptrs, p, 1.0, 0.0, ptrs, ptrs, 16, 0, p, p, nb, 16, 16, 10,
+                               None) == 1
+    assert l.vpc_loss_finalize(p, 1, None, 16, 16, 16, p, p, None) == 1
+    red = (p, 1, 4, p, 1, 4, p, p, p, 1, 2, p, 1, None, 16, 16, 16, p, p)
+    assert l.vpc_reduce_step(*red, None, 0, None) == 1
+    for fn in (l.vpc_reduce_step_adam, l.vpc_reduce_step_adam_bf16c):
+        assert fn(*red, p, p, p, 1e-3, 0.9, 0.999, 1e-8, 1, p, p, None) == 1
 
 
 def swz(col, row, S=64):

@@ -30,6 +30,20 @@ F = C.c_float
 IP = C.POINTER(C.c_int)
 ULL = C.c_ulonglong
 
+
+class VpcLossCoef(C.Structure):
+    """VpcLossCoef of include/vpc.h: the coefficients of the generic loss form as ONE 32-byte record, passed by address to
+    every entry point that computes or finalises the loss and copied as it is into the head of a VpcMember row.  One pass:
+    cA[1] = cE[1] = 0.  Built once per distinct set of hyperparameters and shared (models.loss_coefficients): read-only."""
+    _fields_ = [("cA", F * 2), ("cE", F * 2), ("bq", F), ("bp", F), ("cr", F), ("wml", F)]
+
+    def __init__(self, cA, cE, bq, bp=0.0, cr=0.0, wml=0.0):
+        super().__init__((F * 2)(*cA), (F * 2)(*cE), bq, bp, cr, wml)
+        self._as_parameter_ = P(C.addressof(self))  # what a c_void_p argument takes: no per-call conversion object
+
+    ml_on = property(lambda self: self.wml != 0.0)  # the ml_reg term: the step consumes a third eps plane
+    maskB_on = property(lambda self: self.cE[0] != 0.0)  # the E terms of pass 0: they take mask & ~mask_p (maskB = [mask_p, None])
+
 # name -> argtypes, in the order of include/vpc.h
 _PROTOS = {
     "vpc_layout_sizes": [I, I, I, IP, IP, IP, IP, IP, IP, IP, IP],
@@ -43,9 +57,9 @@ _PROTOS = {
     "vpc_build_indices_bf16": [I, I, I, P, P],
     "vpc_pack_weights_bf16": [P, P, P, I, P],
     "vpc_step_small_max_rows": [],
-    "vpc_step_small_f32": [P, P, P, I, PP, PP, C.POINTER(F), C.POINTER(F), PP, P, F, F, F, F, F, F, P, P, P, IP, L_, I, I, P],
-    "vpc_step_small_draw_f32": [P, P, P, I, PP, PP, C.POINTER(F), C.POINTER(F), PP, P, F, F, F, F, F, F, P, P, P, IP, L_, I, I,
-                                P, F, P, L_, ULL, ULL, ULL, P, L_, L_, L_, L_, I, P],
+    "vpc_step_small_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, P],
+    "vpc_step_small_draw_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, P, F, P, L_, ULL, ULL, ULL, P, L_, L_,
+                                L_, L_, I, P],
     "vpc_step_small_multi_f32": [P, P, P, P, P, P, P, I, I, I, I, ULL, ULL, F, F, P, P, P, C.POINTER(L_), L_, I, I, I, P],
     "vpc_reduce_step_adam_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P],
     "vpc_step_fused_applicable": [L_, I, I, I],
@@ -53,23 +67,18 @@ _PROTOS = {
     "vpc_step_build_indices_bf16": [I, I, P, P],
     "vpc_step_pack_weights_bf16": [P, P, P, I, P],
     "vpc_step_workspace_floats": [L_],
-    "vpc_step_fused_bf16": [P, P, I, PP, PP, C.POINTER(F), C.POINTER(F), PP, P, F, F, F, F, F, F, P, P, P, P, IP, L_, I, I, P],
+    "vpc_step_fused_bf16": [P, P, I, PP, PP, P, PP, P, F, F, P, P, P, P, IP, L_, I, I, P],
     "vpc_encoder_fwd": [P, P, I, PP, PP, PP, PP, PP, PP, PP, I, I, I, L_, I, I, P],
     "vpc_encoder_bwd": [P, P, I, PP, PP, PP, PP, PP, I, I, I, P, IP, L_, I, I, P],
     "vpc_decoder_fwd": [P, P, P, L_, I, I, P],
     "vpc_decoder_bwd": [P, P, P, P, P, IP, L_, I, I, P],
-    "vpc_loss_fwd_bwd": [P, I, PP, PP, PP, C.POINTER(F), C.POINTER(F), PP, PP, P, F, F, F, F, F, F, PP, PP, PP, P, I,
-                         IP, L_, I, I, P],
-    "vpc_decoder_fused": [P, P, I, PP, PP, C.POINTER(F), C.POINTER(F), PP, PP, PP, P, F, F, F, F, F, F, PP, PP, I, I,
-                          P, P, IP, L_, I, I, P],
-    "vpc_loss_finalize": [P, I, F, F, F, F, F, F, F, L_, L_, I, P, P, P],
+    "vpc_loss_fwd_bwd": [P, I, PP, PP, PP, P, PP, PP, P, F, F, PP, PP, PP, P, I, IP, L_, I, I, P],
+    "vpc_decoder_fused": [P, P, I, PP, PP, P, PP, PP, PP, P, F, F, PP, PP, I, I, P, P, IP, L_, I, I, P],
+    "vpc_loss_finalize": [P, I, P, L_, L_, I, P, P, P],
     "vpc_build_inverse_maps": [P, I, I, L_, L_, P, P],
-    "vpc_reduce_step": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, F, F, F, F, F, F, F, L_, L_, I, P, P, P, C.c_longlong,
-                        P],
-    "vpc_reduce_step_adam": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, F, F, F, F, F, F, F, L_, L_, I, P, P, P, P, P, F, F,
-                             F, F, L_, P, P, P],
-    "vpc_reduce_step_adam_bf16c": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, F, F, F, F, F, F, F, L_, L_, I, P, P, P, P, P, F, F,
-                             F, F, L_, P, P, P],
+    "vpc_reduce_step": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, P, L_, L_, I, P, P, P, C.c_longlong, P],
+    "vpc_reduce_step_adam": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, P, L_, L_, I, P, P, P, P, P, F, F, F, F, L_, P, P, P],
+    "vpc_reduce_step_adam_bf16c": [P, I, L_, P, I, L_, P, P, P, I, I, P, I, P, L_, L_, I, P, P, P, P, P, F, F, F, F, L_, P, P, P],
     "vpc_draw_mask": [P, P, L_, F, ULL, ULL, L_, P],
     "vpc_draw_step": [P, P, L_, F, P, L_, ULL, ULL, ULL, P, L_, L_, L_, L_, I, P],
     "vpc_fill_normal": [P, L_, ULL, ULL, P, L_, L_, L_, I, P],
@@ -184,10 +193,6 @@ def ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = None if t is None else t.data_ptr()
     return arr
-
-
-def farray(vals):
-    return (C.c_float * len(vals))(*[float(v) for v in vals])
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

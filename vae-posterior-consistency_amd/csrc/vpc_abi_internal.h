@@ -26,4 +26,11 @@ struct TileShape { int small, ntiles, grid_x, grid_y, nblocks; };
 TileShape tile_shape(long B, int npass, bool force_big = false);  // force_big: kernels that exist in the throughput shape only
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, size); false on a HIP error
 bool lds_attr_done(const void* kern, size_t lds);
+// The loss coefficients of a kernel-argument struct (DecArgs, StepArgs, SmallArgs, LossArgs: cA[2], cE[2], bq, bp, cr, wml)
+// from the ABI's record.  Per-pass entries past npass keep the zeros of a value-initialised struct.
+template <class Args>
+inline void set_loss_coef(Args& a, const VpcLossCoef& co, int npass) {
+    for (int p = 0; p < npass; ++p) { a.cA[p] = co.cA[p]; a.cE[p] = co.cE[p]; }
+    a.bq = co.bq; a.bp = co.bp; a.cr = co.cr; a.wml = co.wml;
+}
 }  // namespace vpc

@@ -717,20 +717,19 @@ extern "C" int vpc_decoder_bwd(const float* z, const float* dxhat, const float* 
 }
 
 extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
-                                 const uint8_t* const* maskB, const float* cA, const float* cE,
+                                 const uint8_t* const* maskB, const VpcLossCoef* co,
                                  const float* const* mean, const float* const* logvar, const float* const* eps,
-                                 const float* eps_ml, float bq, float bp, float cr, float wml, float inv_B,
-                                 float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
+                                 const float* eps_ml, float inv_B, float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
                                  int precision, float* partials, double* loss_partials, int* nblocks_out, long B, int d,
                                  int L, void* stream) {
-    if (!x || !dec_img || !maskA || !cA || !cE || !mean || !logvar || !dmean || !dlogvar || !partials ||
+    if (!x || !dec_img || !maskA || !co || !mean || !logvar || !dmean || !dlogvar || !partials ||
         !loss_partials)
         return VPC_ERR_ARG;
     if (int e = check_common(B, d, L, npass)) return e;
     if (precision < 0 || precision > 2) return VPC_ERR_ARG;
     DecArgs a{};
     a.x = x; a.img = dec_img; a.part = partials; a.loss_part = loss_partials; a.eps_ml = eps_ml;
-    a.bq = bq; a.bp = bp; a.cr = cr; a.wml = wml; a.inv_B = inv_B; a.x_logvar = x_logvar;
+    a.inv_B = inv_B; a.x_logvar = x_logvar;
     if (lat_pitch != 16) return VPC_ERR_ARG;  // the fused kernel works on padded [B][16] latent workspaces only
     a.B = B; a.d = d; a.L = L; a.npass = npass; a.lp = lat_pitch;
     const TileShape ts = tile_shape(B, npass);
@@ -741,12 +740,13 @@ extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass
     bool vec = (d % 4 == 0) && aligned16(x);
     for (int p = 0; p < npass; ++p) {
         if (!maskA[p] || !mean[p] || !logvar[p] || !dmean[p] || !dlogvar[p]) return VPC_ERR_ARG;
-        a.mA[p] = maskA[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.cA[p] = cA[p]; a.cE[p] = cE[p];
+        a.mA[p] = maskA[p]; a.mB[p] = maskB ? maskB[p] : nullptr;
         a.mean[p] = mean[p]; a.logvar[p] = logvar[p]; a.eps[p] = eps ? eps[p] : nullptr;
         a.dmean[p] = dmean[p]; a.dlogvar[p] = dlogvar[p];
         vec = vec && ((uintptr_t)a.mA[p] % 4 == 0) && (!a.mB[p] || (uintptr_t)a.mB[p] % 4 == 0);
     }
-    if (wml != 0.f && !eps_ml) return VPC_ERR_ARG;
+    set_loss_coef(a, *co, npass);
+    if (a.wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     if (nblocks_out) *nblocks_out = ts.nblocks;
     // throughput shape, d in (64, 128]: the 8-wave / one-tile-per-wave kernel (vpc_dec8.hip); VPC_DEC8=0 selects the
     // 4-wave / two-tiles-per-wave kernel of this file instead (same arguments, same partial-block layout; kept for A/B

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void reduce_step_multi_kernel(ReduceMultiArgs 
         if (b < gE) reduce_body_v2(a.partE + g * a.sE, a.nb, a.strideE, a.invE, grad, nE4, b, shf, &adam);
         else reduce_body_v2(a.partD + g * a.sD, a.nb, a.strideD, a.invD, grad, nD4, b - gE, shf, &adam);
     } else {
-        const LossCoef k{r->cA[0], r->cE[0], r->cA[1], r->bq, r->bp, r->cr, r->wml, a.nll_const, a.inv_B};
+        const LossCoef k{r->co.cA[0], r->co.cE[0], r->co.cA[1], r->co.bq, r->co.bp, r->co.cr, r->co.wml, a.nll_const, a.inv_B};
         finalize_body(a.lp + g * a.sL, a.nb, k, a.out9 + g * 9, a.accum + g, shd, s);
     }
 }
@@ -677,15 +677,17 @@ extern "C" int vpc_adam_step(float* params, const float* grads, float* exp_avg, 
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
-extern "C" int vpc_loss_finalize(const double* loss_partials, int nblocks, float cA0, float cE0, float cA1, float bq,
-                                 float bp, float cr, float wml, long B_local, long B_global, int d, float* out9,
-                                 float* accum,
-                                 void* stream) {
-    if (!loss_partials || !out9 || nblocks <= 0 || B_local <= 0 || B_global <= 0) return VPC_ERR_ARG;
-    const LossCoef k{cA0, cE0, cA1, bq, bp, cr, wml, 0.91893853320467274178 * (double)B_local * (double)d,
-                     1.0 / (double)B_global};
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_partials, nblocks, k,
-                       out9, accum);
+// the coefficients of the finalising kernels (LossCoef) from the ABI's record and the batch sizes
+static LossCoef finalize_coef(const VpcLossCoef& co, long B_local, long B_global, int d) {
+    return LossCoef{co.cA[0], co.cE[0], co.cA[1], co.bq, co.bp, co.cr, co.wml,
+                    0.91893853320467274178 * (double)B_local * (double)d, 1.0 / (double)B_global};
+}
+
+extern "C" int vpc_loss_finalize(const double* loss_partials, int nblocks, const VpcLossCoef* co, long B_local,
+                                 long B_global, int d, float* out9, float* accum, void* stream) {
+    if (!loss_partials || !co || !out9 || nblocks <= 0 || B_local <= 0 || B_global <= 0) return VPC_ERR_ARG;
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_partials, nblocks,
+                       finalize_coef(*co, B_local, B_global, d), out9, accum);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
@@ -699,95 +701,80 @@ extern "C" int vpc_build_inverse_maps(const int* grad_idx, int n_enc, int n, lon
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
-extern "C" int vpc_reduce_step(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
-                               int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps,
-                               float* grad_out, int n_enc, int n,
-                               const double* loss_partials, int loss_blocks, float cA0, float cE0, float cA1, float bq,
-                               float bp, float cr, float wml, long B_local, long B_global, int d, float* out9,
-                               float* accum, long long* state, long long rng_inc, void* stream) {
-    if (!enc_partials || !dec_partials || !grad_idx || !grad_out || !loss_partials || !out9) return VPC_ERR_ARG;
-    if (enc_blocks <= 0 || dec_blocks <= 0 || loss_blocks <= 0 || n_enc <= 0 || n <= n_enc || B_local <= 0 ||
-        B_global <= 0)
-        return VPC_ERR_ARG;
-    const LossCoef k{cA0, cE0, cA1, bq, bp, cr, wml, 0.91893853320467274178 * (double)B_local * (double)d,
-                     1.0 / (double)B_global};
+// The body of vpc_reduce_step (A = AdamFuse{}: gradient and loss terms only) and of its two Adam forms.
+static int reduce_step_launch(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
+                              int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps, float* grad_out,
+                              int n_enc, int n, const double* loss_partials, int loss_blocks, const VpcLossCoef* co,
+                              long B_local, long B_global, int d, float* out9, float* accum, long long* state,
+                              long long rng_inc, const AdamFuse& A, void* stream) {
+    if (!enc_partials || !dec_partials || !grad_idx || !grad_out || !loss_partials || !co || !out9) return VPC_ERR_ARG;
+    if (enc_blocks <= 0 || dec_blocks <= 0 || loss_blocks <= 0 || n_enc <= 0 || n <= n_enc) return VPC_ERR_ARG;
+    const LossCoef k = finalize_coef(*co, B_local, B_global, d);
     if (inv_usable(inv_maps, enc_partials, enc_stride, dec_partials, dec_stride)) {
         const int *invE = inv_maps, *invD = inv_maps + enc_stride;
         const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8 + 1);
         hipLaunchKernelGGL(reduce_step_v2_kernel, dim3(grid2), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
                            enc_stride, dec_partials, dec_blocks, dec_stride, invE, invD, grad_out, loss_partials,
-                           loss_blocks, k, out9, accum, state, rng_inc, AdamFuse{});
+                           loss_blocks, k, out9, accum, state, rng_inc, A);
         return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
     }
     const int grid = (n_enc + 31) / 32 + (n - n_enc + 31) / 32 + 1;
     hipLaunchKernelGGL(reduce_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
                        enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, grad_out, n_enc, n, loss_partials,
-                       loss_blocks, k, out9, accum, state, rng_inc, AdamFuse{});
+                       loss_blocks, k, out9, accum, state, rng_inc, A);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+extern "C" int vpc_reduce_step(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
+                               int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps,
+                               float* grad_out, int n_enc, int n, const double* loss_partials, int loss_blocks,
+                               const VpcLossCoef* co, long B_local, long B_global, int d, float* out9, float* accum,
+                               long long* state, long long rng_inc, void* stream) {
+    if (B_local <= 0 || B_global <= 0) return VPC_ERR_ARG;
+    return reduce_step_launch(enc_partials, enc_blocks, enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, inv_maps,
+                              grad_out, n_enc, n, loss_partials, loss_blocks, co, B_local, B_global, d, out9, accum, state,
+                              rng_inc, AdamFuse{}, stream);
+}
+
+// bf16c = 1: the re-pack target is the compact bf16 image of the whole-step kernel (pack_idx_c / img_c of
+// vpc_step_build_indices_bf16; a bf16 step then needs no separate pack launch), 0: the fp32 images
+static int reduce_step_adam_launch(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
+                                   int dec_blocks, long dec_stride, const int* grad_idx, const int* inv_maps,
+                                   float* grad_out, int n_enc, int n, const double* loss_partials, int loss_blocks,
+                                   const VpcLossCoef* co, long B_local, long B_global, int d, float* out9, float* accum,
+                                   float* params, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                   float eps, long step, const int* pack_idx, float* img, int bf16c, void* stream) {
+    if (!params || !exp_avg || !exp_avg_sq || step < 1 || (pack_idx == nullptr) != (img == nullptr)) return VPC_ERR_ARG;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    const AdamFuse A{params, exp_avg, exp_avg_sq, pack_idx, img, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), bf16c};
+    return reduce_step_launch(enc_partials, enc_blocks, enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, inv_maps,
+                              grad_out, n_enc, n, loss_partials, loss_blocks, co, B_local, B_global, d, out9, accum, nullptr, 0LL,
+                              A, stream);
 }
 
 extern "C" int vpc_reduce_step_adam(const float* enc_partials, int enc_blocks, long enc_stride,
                                     const float* dec_partials, int dec_blocks, long dec_stride, const int* grad_idx,
                                     const int* inv_maps, float* grad_out, int n_enc, int n,
-                                    const double* loss_partials, int loss_blocks,
-                                    float cA0, float cE0, float cA1, float bq, float bp, float cr, float wml,
-                                    long B_local, long B_global, int d, float* out9, float* accum, float* params,
-                                    float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                                    long step, const int* pack_idx, float* img, void* stream) {
-    if (!enc_partials || !dec_partials || !grad_idx || !grad_out || !loss_partials || !out9) return VPC_ERR_ARG;
-    if (enc_blocks <= 0 || dec_blocks <= 0 || loss_blocks <= 0 || n_enc <= 0 || n <= n_enc) return VPC_ERR_ARG;
-    if (!params || !exp_avg || !exp_avg_sq || step < 1 || (pack_idx == nullptr) != (img == nullptr)) return VPC_ERR_ARG;
-    const LossCoef k{cA0, cE0, cA1, bq, bp, cr, wml, 0.91893853320467274178 * (double)B_local * (double)d,
-                     1.0 / (double)B_global};
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    const AdamFuse A{params, exp_avg, exp_avg_sq, pack_idx, img, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 0};
-    if (inv_usable(inv_maps, enc_partials, enc_stride, dec_partials, dec_stride)) {
-        const int *invE = inv_maps, *invD = inv_maps + enc_stride;
-        const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8 + 1);
-        hipLaunchKernelGGL(reduce_step_v2_kernel, dim3(grid2), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
-                           enc_stride, dec_partials, dec_blocks, dec_stride, invE, invD, grad_out, loss_partials,
-                           loss_blocks, k, out9, accum, (long long*)nullptr, 0LL, A);
-        return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
-    }
-    const int grid = (n_enc + 31) / 32 + (n - n_enc + 31) / 32 + 1;
-    hipLaunchKernelGGL(reduce_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
-                       enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, grad_out, n_enc, n, loss_partials,
-                       loss_blocks, k, out9, accum, (long long*)nullptr, 0LL, A);
-    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+                                    const double* loss_partials, int loss_blocks, const VpcLossCoef* co, long B_local,
+                                    long B_global, int d, float* out9, float* accum, float* params, float* exp_avg,
+                                    float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
+                                    const int* pack_idx, float* img, void* stream) {
+    return reduce_step_adam_launch(enc_partials, enc_blocks, enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx,
+                                   inv_maps, grad_out, n_enc, n, loss_partials, loss_blocks, co, B_local, B_global, d, out9,
+                                   accum, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, pack_idx, img, 0, stream);
 }
 
-// The same with the compact bf16 image of the whole-step kernel as the re-pack target (pack_idx_c / img_c of
-// vpc_step_build_indices_bf16): a bf16 step then needs no separate pack launch.
 extern "C" int vpc_reduce_step_adam_bf16c(const float* enc_partials, int enc_blocks, long enc_stride,
-                                    const float* dec_partials, int dec_blocks, long dec_stride, const int* grad_idx,
-                                    const int* inv_maps, float* grad_out, int n_enc, int n,
-                                    const double* loss_partials, int loss_blocks,
-                                    float cA0, float cE0, float cA1, float bq, float bp, float cr, float wml,
-                                    long B_local, long B_global, int d, float* out9, float* accum, float* params,
-                                          float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                                    long step, const int* pack_idx, float* img, void* stream) {
-    if (!enc_partials || !dec_partials || !grad_idx || !grad_out || !loss_partials || !out9) return VPC_ERR_ARG;
-    if (enc_blocks <= 0 || dec_blocks <= 0 || loss_blocks <= 0 || n_enc <= 0 || n <= n_enc) return VPC_ERR_ARG;
-    if (!params || !exp_avg || !exp_avg_sq || step < 1 || (pack_idx == nullptr) != (img == nullptr)) return VPC_ERR_ARG;
-    const LossCoef k{cA0, cE0, cA1, bq, bp, cr, wml, 0.91893853320467274178 * (double)B_local * (double)d,
-                     1.0 / (double)B_global};
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    const AdamFuse A{params, exp_avg, exp_avg_sq, pack_idx, img, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 1};
-    if (inv_usable(inv_maps, enc_partials, enc_stride, dec_partials, dec_stride)) {
-        const int *invE = inv_maps, *invD = inv_maps + enc_stride;
-        const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8 + 1);
-        hipLaunchKernelGGL(reduce_step_v2_kernel, dim3(grid2), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
-                           enc_stride, dec_partials, dec_blocks, dec_stride, invE, invD, grad_out, loss_partials,
-                           loss_blocks, k, out9, accum, (long long*)nullptr, 0LL, A);
-        return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
-    }
-    const int grid = (n_enc + 31) / 32 + (n - n_enc + 31) / 32 + 1;
-    hipLaunchKernelGGL(reduce_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
-                       enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx, grad_out, n_enc, n, loss_partials,
-                       loss_blocks, k, out9, accum, (long long*)nullptr, 0LL, A);
-    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+                                          const float* dec_partials, int dec_blocks, long dec_stride, const int* grad_idx,
+                                          const int* inv_maps, float* grad_out, int n_enc, int n,
+                                          const double* loss_partials, int loss_blocks, const VpcLossCoef* co, long B_local,
+                                          long B_global, int d, float* out9, float* accum, float* params, float* exp_avg,
+                                          float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
+                                          const int* pack_idx_c, float* img_c, void* stream) {
+    return reduce_step_adam_launch(enc_partials, enc_blocks, enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx,
+                                   inv_maps, grad_out, n_enc, n, loss_partials, loss_blocks, co, B_local, B_global, d, out9,
+                                   accum, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, pack_idx_c, img_c, 1, stream);
 }
 
 extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials,
@@ -824,23 +811,23 @@ extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float
 }
 
 extern "C" int vpc_loss_fwd_bwd(const float* x, int npass, const float* const* xhat, const uint8_t* const* maskA,
-                                const uint8_t* const* maskB, const float* cA, const float* cE,
-                                const float* const* mean, const float* const* logvar, const float* eps_ml, float bq,
-                                float bp, float cr, float wml, float inv_B, float x_logvar, float* const* dxhat,
-                                float* const* dmean, float* const* dlogvar, double* loss_partials, int max_blocks,
-                                int* nblocks_out, long B, int d, int L, void* stream) {
-    if (!x || !xhat || !maskA || !cA || !cE || !mean || !logvar || !loss_partials || !nblocks_out) return VPC_ERR_ARG;
+                                const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                                const float* const* logvar, const float* eps_ml, float inv_B, float x_logvar,
+                                float* const* dxhat, float* const* dmean, float* const* dlogvar, double* loss_partials,
+                                int max_blocks, int* nblocks_out, long B, int d, int L, void* stream) {
+    if (!x || !xhat || !maskA || !co || !mean || !logvar || !loss_partials || !nblocks_out) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0 || d < 1 || L < 1 || max_blocks < 1) return VPC_ERR_ARG;
-    if (wml != 0.f && !eps_ml) return VPC_ERR_ARG;
+    if (co->wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     LossArgs a{};
     a.x = x; a.eps_ml = eps_ml; a.loss_part = loss_partials;
-    a.bq = bq; a.bp = bp; a.cr = cr; a.wml = wml; a.inv_B = inv_B; a.x_logvar = x_logvar;
+    set_loss_coef(a, *co, npass);
+    a.inv_B = inv_B; a.x_logvar = x_logvar;
     a.n_el = B * (long)d; a.n_lat = B * (long)L; a.npass = npass;
     a.want_grad = (dxhat && dmean && dlogvar) ? 1 : 0;
     bool al = aligned16(x);
     for (int p = 0; p < npass; ++p) {
         if (!xhat[p] || !maskA[p] || !mean[p] || !logvar[p]) return VPC_ERR_ARG;
-        a.xh[p] = xhat[p]; a.mA[p] = maskA[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.cA[p] = cA[p]; a.cE[p] = cE[p];
+        a.xh[p] = xhat[p]; a.mA[p] = maskA[p]; a.mB[p] = maskB ? maskB[p] : nullptr;
         a.mean[p] = mean[p]; a.logvar[p] = logvar[p];
         if (a.want_grad) {
             if (!dmean[p] || !dlogvar[p]) return VPC_ERR_ARG;

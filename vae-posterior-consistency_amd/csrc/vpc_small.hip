@@ -135,23 +135,23 @@ struct SmallDraw {
     const long long* state; long mask_elem_lo; EpsShard shard;
 };
 static int step_small_launch(const float* x, const float* enc_img, const float* dec_img, int npass,
-                             const uint8_t* const* mask, const uint8_t* const* maskB, const float* cA, const float* cE,
-                             const float* const* eps, const float* eps_ml, float bq, float bp, float cr, float wml,
-                             float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                             const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                             const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
                              int* nblocks_out, long B, int d, int L, const SmallDraw& dr, void* stream) {
-    if (!x || !enc_img || !dec_img || !mask || !cA || !cE || !eps || !partE || !partD || !loss_partials) return VPC_ERR_ARG;
+    if (!x || !enc_img || !dec_img || !mask || !co || !eps || !partE || !partD || !loss_partials) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0) return VPC_ERR_ARG;
     if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
     if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img)) return VPC_ERR_ARG;
-    if (wml != 0.f && !eps_ml) return VPC_ERR_ARG;
+    if (co->wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     SmallArgs a{};
     a.x = x; a.enc_img = enc_img; a.dec_img = dec_img; a.eps_ml = eps_ml; a.partE = partE; a.partD = partD;
     a.loss_part = loss_partials;
-    a.bq = bq; a.bp = bp; a.cr = cr; a.wml = wml; a.inv_B = inv_B; a.x_logvar = x_logvar;
+    set_loss_coef(a, *co, npass);
+    a.inv_B = inv_B; a.x_logvar = x_logvar;
     a.B = B; a.d = d; a.L = L; a.npass = npass;
     for (int p = 0; p < npass; ++p) {
         if (!mask[p] || !eps[p]) return VPC_ERR_ARG;
-        a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.cA[p] = cA[p]; a.cE[p] = cE[p]; a.eps[p] = eps[p];
+        a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.eps[p] = eps[p];
         if ((uintptr_t)a.m[p] % 4 || !aligned16(a.eps[p])) return VPC_ERR_ARG;
     }
     for (int p = 0; p < npass; ++p)  // the second loss mask of a pass must be the other pass's mask (as vpc_step_fused_bf16)
@@ -186,11 +186,10 @@ static int step_small_launch(const float* x, const float* enc_img, const float* 
 }  // namespace vpc
 
 extern "C" int vpc_step_small_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
-                                  const uint8_t* const* mask, const uint8_t* const* maskB, const float* cA, const float* cE,
-                                  const float* const* eps, const float* eps_ml, float bq, float bp, float cr, float wml,
-                                  float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                  const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                  const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
                                   int* nblocks_out, long B, int d, int L, void* stream) {
-    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE,
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
                              partD, loss_partials, nblocks_out, B, d, L, SmallDraw{}, stream);
 }
 
@@ -199,9 +198,8 @@ extern "C" int vpc_step_small_f32(const float* x, const float* enc_img, const fl
 // Philox counters vpc_draw_step would use (seed, offsets, state, mask_elem_lo and the eps_* shard description as there), stores them
 // where the step reads them, and runs the step.  Same draws, one launch less at the batch sizes where a launch is a fifth of the step.
 extern "C" int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
-                                       const uint8_t* const* mask, const uint8_t* const* maskB, const float* cA, const float* cE,
-                                       const float* const* eps, const float* eps_ml, float bq, float bp, float cr, float wml,
-                                       float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                       const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                       const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
                                        int* nblocks_out, long B, int d, int L, const uint8_t* mask_in, float keep_prob,
                                        float* eps_out, long n_eps, unsigned long long seed, unsigned long long offset_mask,
                                        unsigned long long offset_eps, const long long* state, long mask_elem_lo,
@@ -211,7 +209,7 @@ extern "C" int vpc_step_small_draw_f32(const float* x, const float* enc_img, con
         return VPC_ERR_ARG;
     SmallDraw dr{1, mask_in, keep_prob, eps_out, n_eps, seed, offset_mask, offset_eps, state, mask_elem_lo,
                  EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch}};
-    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE,
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
                              partD, loss_partials, nblocks_out, B, d, L, dr, stream);
 }
 
@@ -287,7 +285,7 @@ __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArg
     a.m.v1 = b.m[1] ? b.m[1] + mem * ma.smp : nullptr;
     a.mB.v0 = r->use_maskB ? a.m.v1 : nullptr;  // (the E terms' second mask is the other pass's: cE[0] != 0)
     a.mB.v1 = nullptr;
-    a.cA.v0 = r->cA[0]; a.cA.v1 = r->cA[1]; a.cE.v0 = r->cE[0]; a.cE.v1 = r->cE[1];
+    a.cA.v0 = r->co.cA[0]; a.cA.v1 = r->co.cA[1]; a.cE.v0 = r->co.cE[0]; a.cE.v1 = r->co.cE[1];
     // (the planes of a member follow each other and the draws are those of an unsharded stand-alone step - no device-side state,
     // element offset 0, all B rows local: derived from eps[0], mask, B and constants instead of carried in registers)
     a.eps.v0 = b.eps[0] + mem * ma.seps;
@@ -296,7 +294,7 @@ __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArg
     a.partE = b.partE + mem * ma.sE;
     a.partD = b.partD + mem * ma.sD;
     a.loss_part = b.loss_part + mem * ma.sL;
-    a.bq = r->bq; a.bp = r->bp; a.cr = r->cr; a.wml = r->wml; a.inv_B = b.inv_B; a.x_logvar = b.x_logvar;
+    a.bq = r->co.bq; a.bp = r->co.bp; a.cr = r->co.cr; a.wml = r->co.wml; a.inv_B = b.inv_B; a.x_logvar = b.x_logvar;
     a.B = b.B; a.d = b.d; a.L = b.L; a.npass = b.npass;
     a.draw = b.draw;
     a.mask_in = b.mask_in ? a.m.v0 : nullptr;

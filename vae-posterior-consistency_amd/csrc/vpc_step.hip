@@ -1055,23 +1055,24 @@ extern "C" int vpc_step_pack_weights_bf16(const float* flat_params, const int* p
 }
 
 extern "C" int vpc_step_fused_bf16(const float* x, const float* img_c, int npass, const uint8_t* const* mask,
-                                   const uint8_t* const* maskB, const float* cA, const float* cE, const float* const* eps,
-                                   const float* eps_ml, float bq, float bp, float cr, float wml, float inv_B, float x_logvar,
+                                   const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                                   const float* eps_ml, float inv_B, float x_logvar,
                                    float* partE, float* partD, double* loss_partials, float* workspace, int* nblocks_out,
                                    long B, int d, int L, void* stream) {
-    if (!x || !img_c || !mask || !cA || !cE || !eps || !partE || !partD || !loss_partials || !workspace) return VPC_ERR_ARG;
+    if (!x || !img_c || !mask || !co || !eps || !partE || !partD || !loss_partials || !workspace) return VPC_ERR_ARG;
     if (!aligned16(workspace)) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0) return VPC_ERR_ARG;
     if (!step_shape_ok(d, L)) return VPC_ERR_SHAPE;
     if (!aligned16(x) || !aligned16(img_c)) return VPC_ERR_ARG;
-    if (wml != 0.f && !eps_ml) return VPC_ERR_ARG;
+    if (co->wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     StepArgs a{};
     a.x = x; a.img = img_c; a.eps_ml = eps_ml; a.partE = partE; a.partD = partD; a.loss_part = loss_partials; a.ws = workspace;
-    a.bq = bq; a.bp = bp; a.cr = cr; a.wml = wml; a.inv_B = inv_B; a.x_logvar = x_logvar;
+    set_loss_coef(a, *co, npass);
+    a.inv_B = inv_B; a.x_logvar = x_logvar;
     a.B = B; a.d = d; a.L = L; a.npass = npass;
     for (int p = 0; p < npass; ++p) {
         if (!mask[p] || !eps[p]) return VPC_ERR_ARG;
-        a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.cA[p] = cA[p]; a.cE[p] = cE[p]; a.eps[p] = eps[p];
+        a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.eps[p] = eps[p];
         if ((uintptr_t)a.m[p] % 4 || !aligned16(a.eps[p])) return VPC_ERR_ARG;
     }
     // the second loss mask of a pass (mE = mA (1 - mB)) must be the OTHER pass's mask - what the consistency term

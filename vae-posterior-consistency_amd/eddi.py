@@ -18,13 +18,12 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .fused import loss_coefficients
 from .images import PackedImage, mlp_spec
 from .models import _W6, MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .linear import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad
 from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
-from .trainer import _FlatAdamTrainer
+from .trainer import _FlatAdamTrainer, draw_counters
 
 H1, H2 = 100, 50  # VAE.py:694-698 hard-codes 100 / 50
 
@@ -228,9 +227,6 @@ class EDDITrainer(_FlatAdamTrainer):
         self.n_dec = self.lay.n_params - self.lay.n_enc
         self._B = None
 
-    def coefficients(self, epoch, alpha, beta, beta_annealing):
-        return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
-
     def _ws(self, B):
         if self._B == B:
             return
@@ -267,7 +263,7 @@ class EDDITrainer(_FlatAdamTrainer):
         mask = as_mask_u8(mask.reshape(-1, d))
         B = x.shape[0]
         self._ws(B)
-        Bg = global_batch if global_batch is not None else B * self.world_size
+        Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
         two = not self.vanilla
         P = 2 if two else 1
@@ -276,27 +272,22 @@ class EDDITrainer(_FlatAdamTrainer):
         E, tb, Wp, cp = t[12:]
         dec_img = m._images(m._param_key(t))[lay.enc_img:]  # re-packed after the previous step's Adam
         # ---- draws
-        need_ml = two and co["wml"] != 0.0
+        need_ml = two and co.ml_on
         eps_view = self.eps_buf[: (3 if need_ml else 2 if two else 1)]
-        inject = eps_q is not None
-        if row_lo is None:
-            row_lo = self.rank * B if self.world_size > 1 else 0
-        # Philox counters of the GLOBAL row: draws do not depend on the world size
-        eps_shard = (B, Bg, row_lo, LP)
-        n_eps_groups = eps_view.shape[0] * Bg * (LP // 4)
-        if two and mask_p is None:
-            off_m = self.rng_offset
-            self.rng_offset += (Bg * d + 7) // 8 + 1  # counters advance by what the GLOBAL batch consumes
-            ops.draw_step(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, eps_view, self.seed, off_m,
-                          self.rng_offset, None, row_lo * d, eps_shard)
-            self.rng_offset += n_eps_groups
+        # eps is drawn together with mask_p whenever mask_p is absent (injected planes are copied over it), else unless injected
+        draw_mask = two and mask_p is None
+        dr = draw_counters(self.rng_offset, draw_mask, eps_view.shape[0] if (draw_mask or eps_q is None) else 0, B, Bg,
+                           row_lo, LP, d)
+        self.rng_offset = dr.next_offset
+        if draw_mask:
+            ops.draw_step(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, eps_view, self.seed, dr.offset_mask,
+                          dr.offset_eps, None, dr.elem_lo, dr.eps_shard)
             mask_p = self.mask_p_buf
         else:
             if two:
                 mask_p = as_mask_u8(mask_p.reshape(-1, d))
-            if not inject:
-                ops.fill_normal(eps_view, self.seed, self.rng_offset, None, eps_shard)
-                self.rng_offset += n_eps_groups
+            if eps_q is None:
+                ops.fill_normal(eps_view, self.seed, dr.offset_eps, None, dr.eps_shard)
         if eps_q is not None:
             self.eps_buf[0, :, :Ld].copy_(eps_q)
         if two and eps_p is not None:
@@ -317,14 +308,11 @@ class EDDITrainer(_FlatAdamTrainer):
         epss = sl["eps"][:P]
         eml = sl["eps"][2] if need_ml else None
         # ---- fused decoder + loss + decoder backward (the VAE step's kernel)
-        maskB = [mask_p, None] if (two and co["cE"][0] != 0.0) else [None] * P
-        nbD = ops.decoder_fused(x, dec_img, masks, maskB, co["cA"], co["cE"], mean, logvar, epss, eml, co["bq"],
-                                co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value, dmean, dlogvar, self.partD,
-                                self.loss_part, d, Ld, LP)
+        maskB = [mask_p, None] if (two and co.maskB_on) else [None] * P
+        nbD = ops.decoder_fused(x, dec_img, masks, maskB, co, mean, logvar, epss, eml, 1.0 / Bg, m._x_logvar_value, dmean,
+                                dlogvar, self.partD, self.loss_part, d, Ld, LP)
         ops.reduce_partials(self.partD, nbD, lay.dec_part, sl["gidx_dec"], sl["gdec"])
-        cA1 = co["cA"][1] if two else 0.0
-        ops.loss_finalize(self.loss_part, nbD, co["cA"][0], co["cE"][0], cA1, co["bq"], co["bp"], co["cr"], co["wml"], B,
-                          Bg, d, self.out9, self.accum if self.world_size == 1 else None)
+        ops.loss_finalize(self.loss_part, nbD, co, B, Bg, d, self.out9, self.accum if self.world_size == 1 else None)
         # ---- encoder backward
         sl["dheads_dst"].copy_(sl["dlat_src"])
         g = self.g

@@ -41,13 +41,12 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .fused import loss_coefficients
 from .images import mlp_spec
 from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now
 from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
-from .trainer import _FlatAdamTrainer
+from .trainer import _FlatAdamTrainer, draw_counters
 
 H1, H2, H3 = 500, 500, 200  # VAE.py:32-44 hard-codes the widths: trunk K-500-500-200-2L, decoder L-200-500-500-d
 MAX_D, MAX_K, MAX_L = 1024, 32, 15
@@ -357,7 +356,7 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         L.require_cuda(mask)
         B = x.shape[0]
         self._ws(B)
-        co = loss_coefficients(m, epoch, alpha, beta, beta_annealing)
+        co = self.coefficients(epoch, alpha, beta, beta_annealing)
         two = not self.vanilla
         P = 2 if two else 1
         R = P * B
@@ -365,17 +364,18 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         t = self._plist
         E, tb, Wp, cp = t[:4]
         # ---- draws
-        need_ml = two and co["wml"] != 0.0
-        if two:
-            if mask_p is None:
-                ops.draw_mask(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, self.seed, self.rng_offset, 0)
-                self.rng_offset += (B * d + 7) // 8 + 1
-                mask_p = self.mask_p_buf
-            else:
-                mask_p = as_mask_u8(mask_p.reshape(-1, d))
-        if eps is None or (need_ml and eps_ml is None):
-            ops.fill_normal(self.eps_pad, self.seed, self.rng_offset, None, (B, B, 0, self.LP))
-            self.rng_offset += 3 * B * (self.LP // 4)
+        need_ml = two and co.ml_on
+        # (always all three planes of eps_pad, whatever the step consumes)
+        draw_mask, draw_eps = two and mask_p is None, eps is None or (need_ml and eps_ml is None)
+        dr = draw_counters(self.rng_offset, draw_mask, 3 if draw_eps else 0, B, B, 0, self.LP, d)
+        self.rng_offset = dr.next_offset
+        if draw_mask:
+            ops.draw_mask(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, self.seed, dr.offset_mask, dr.elem_lo)
+            mask_p = self.mask_p_buf
+        elif two:
+            mask_p = as_mask_u8(mask_p.reshape(-1, d))
+        if draw_eps:
+            ops.fill_normal(self.eps_pad, self.seed, dr.offset_eps, None, dr.eps_shard)
         if eps is None:
             sl["eps_dst"].copy_(sl["eps_src"])
         else:
@@ -393,12 +393,10 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         chain_fwd(self.dec_layers, self.dec, R)
         # ---- loss + seeds (K4 on the materialised xhat; the statistics as [pass][mean | logvar][B][L])
         self.lat.copy_(sl["heads_src"])
-        maskB = [mask_p, None] if (two and co["cE"][0] != 0.0) else [None] * P
-        nb = ops.loss_fwd_bwd(x, sl["xhat"], masks, maskB, co["cA"], co["cE"], sl["mean"], sl["logvar"],
-                              self.eps_ml if need_ml else None, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / B,
-                              m._x_logvar_value, sl["dxhat"], sl["dmean"], sl["dlogvar"], self.loss_part, d, Ld)
-        ops.loss_finalize(self.loss_part, nb, co["cA"][0], co["cE"][0], co["cA"][1] if two else 0.0, co["bq"], co["bp"],
-                          co["cr"], co["wml"], B, B, d, self.out9, self.accum)
+        maskB = [mask_p, None] if (two and co.maskB_on) else [None] * P
+        nb = ops.loss_fwd_bwd(x, sl["xhat"], masks, maskB, co, sl["mean"], sl["logvar"], self.eps_ml if need_ml else None,
+                              1.0 / B, m._x_logvar_value, sl["dxhat"], sl["dmean"], sl["dlogvar"], self.loss_part, d, Ld)
+        ops.loss_finalize(self.loss_part, nb, co, B, B, d, self.out9, self.accum)
         # ---- decoder backward (weight gradients stay partials until the one reduce launch)
         chain_bwd(self.dec_layers, self.dec, self.ddec, R, self._wgrad, _DEC_WKEYS, y_gate=self.dec[4],
                   gate=ACT_SIGMOID_HARDTANH, gate_split=d)

@@ -18,17 +18,20 @@ computes on its data: same tile body, same summation order, same Philox counters
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops
-from .fused import LP, loss_coefficients
+from .fused import LP
 from .images import PackedImage, flat_written
-from .models import Reg_VAE, vanilla_VAE
+from .models import Reg_VAE, loss_coefficients, vanilla_VAE
 from .ops import as_mask_u8
+from .trainer import draw_counters, pad_cols
 
-# VpcMember of include/vpc.h (64 bytes)
+# VpcMember of include/vpc.h (64 bytes): the first 32 are its VpcLossCoef, spelled flat
 MEMBER_DTYPE = np.dtype([("cA", "<f4", 2), ("cE", "<f4", 2), ("bq", "<f4"), ("bp", "<f4"), ("cr", "<f4"), ("wml", "<f4"),
                          ("keep_prob", "<f4"), ("lr", "<f4"), ("seed", "<u8"), ("use_maskB", "<i4"), ("reserved", "<i4", 3)])
 assert MEMBER_DTYPE.itemsize == 64
@@ -122,9 +125,6 @@ class MemberTable:
         self.version = 0  # bumped whenever a row's bytes changed
         self._inputs = None
 
-    def coefficients(self, g, epoch, alpha, beta, beta_annealing):
-        return loss_coefficients(self.models[g], epoch, alpha, beta, beta_annealing)
-
     def update(self, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False, p_missingness=30):
         G = len(self.models)
         inputs = (epoch, _per_member(alpha, G, "alpha"), _per_member(beta, G, "beta"), bool(beta_annealing),
@@ -133,14 +133,12 @@ class MemberTable:
             return False
         _, alphas, betas_, _, pms = inputs
         rows = self.rows.copy()
+        heads = rows.view(np.uint8).reshape(G, MEMBER_DTYPE.itemsize)[:, :C.sizeof(L.VpcLossCoef)]
         for g in range(G):
-            co = self.coefficients(g, epoch, alphas[g], betas_[g], beta_annealing)
-            r = rows[g]
-            r["cA"] = (co["cA"] + [0.0])[:2]
-            r["cE"] = (co["cE"] + [0.0])[:2]
-            r["bq"], r["bp"], r["cr"], r["wml"] = co["bq"], co["bp"], co["cr"], co["wml"]
-            r["keep_prob"] = 1.0 - pms[g] / 100.0
-            r["use_maskB"] = int(self.two and co["cE"][0] != 0.0)
+            co = loss_coefficients(self.models[g], epoch, alphas[g], betas_[g], beta_annealing)
+            heads[g] = np.frombuffer(co, np.uint8)  # the record is the head of the row
+            rows[g]["keep_prob"] = 1.0 - pms[g] / 100.0
+            rows[g]["use_maskB"] = int(self.two and co.maskB_on)
         ml = rows["wml"] != 0.0
         if self.two and ml.any() != ml.all():
             # a member with wml == 0 draws two eps planes, one with wml != 0 three: they would not consume the same counters
@@ -232,15 +230,6 @@ class EnsembleTrainer:
         self._ws = (B, dk)
         return tiles
 
-    def _pad_cols(self, t, dk, slot):
-        """[.., B, d] -> zero-padded [.., B, dk] (a persistent buffer per input slot)."""
-        key = (slot, tuple(t.shape[:-1]), dk, t.dtype)
-        buf = self._pads.get(key)
-        if buf is None:
-            buf = self._pads[key] = torch.zeros(*t.shape[:-1], dk, dtype=t.dtype, device=self.dev)
-        buf[..., :t.shape[-1]].copy_(t)
-        return buf
-
     def _upload_table(self):
         if self._table_version != self.table.version:
             self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
@@ -279,7 +268,7 @@ class EnsembleTrainer:
         mask = as_mask_u8(mask)
         dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # (the padding rule of FusedTrainer.step)
         if dk != d:
-            x, mask = self._pad_cols(x, dk, 0), self._pad_cols(mask, dk, 1)
+            x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
         self._workspaces(B, dk)
         if changed or self._table_version != self.table.version:
             self._upload_table()
@@ -294,12 +283,8 @@ class EnsembleTrainer:
             keys.append(key)
         nplanes = 3 if need_ml else 2 if two else 1
         off_m = off_e = 0
-        if draw:  # the counters of FusedTrainer.step: mask_p first, then the eps planes
-            off_m = self.rng_offset
-            if two:
-                self.rng_offset += (B * dk + 7) // 8 + 1
-            off_e = self.rng_offset
-            self.rng_offset += nplanes * B * (LP // 4)
+        if draw:  # every member is an unsharded batch of B rows
+            off_m, off_e, self.rng_offset, _, _ = draw_counters(self.rng_offset, two, nplanes, B, B, 0, LP, dk)
         else:
             if two:
                 self.mask_p_buf[:, :, :d].copy_(as_mask_u8(mask_p))

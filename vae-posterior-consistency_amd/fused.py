@@ -28,25 +28,11 @@ from . import _lib as L
 from . import dist as dp_mod
 from . import ops
 from .images import PackedImage
-from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
+from .models import Reg_VAE, loss_coefficients, vanilla_VAE  # noqa: F401  (also reached as fused.loss_coefficients)
 from .ops import H1P, H2P, as_mask_u8
-from .trainer import _FlatAdamTrainer
+from .trainer import _FlatAdamTrainer, draw_counters, pad_cols
 
 LP = 16  # row pitch of the padded latent workspaces
-
-
-def loss_coefficients(model, epoch, alpha, beta, beta_annealing):
-    """Loss coefficients of the generic form in csrc/vpc_dec.hip (VAE.py:425-446 / 1183-1195)."""
-    bw = (epoch / MAX_EPOCH) * beta if beta_annealing else beta
-    if isinstance(model, vanilla_VAE):
-        return dict(cA=[1.0], cE=[0.0], bq=bw, bp=0.0, cr=0.0, wml=0.0)
-    rt = model.reg_type
-    if rt == "kl_reg":
-        return dict(cA=[1.0 - alpha, alpha], cE=[alpha, 0.0], bq=(1.0 - alpha) * bw, bp=alpha * bw, cr=alpha, wml=0.0)
-    if rt == "ml_reg":
-        return dict(cA=[1.0, 0.0], cE=[0.0, 0.0], bq=bw, bp=0.0, cr=0.0, wml=(epoch / MAX_EPOCH) * alpha)
-    print("Not implemented!")  # VAE.py:447-449
-    raise NotImplementedError(f"reg_type {rt!r}")
 
 
 class FusedTrainer(_FlatAdamTrainer):
@@ -107,15 +93,6 @@ class FusedTrainer(_FlatAdamTrainer):
         self.model.invalidate_images()
 
     # ------------------------------------------------------------------
-    def _pad_cols(self, t, dk, slot):
-        """[B, d] -> zero-padded [B, dk] (a persistent buffer per input slot)."""
-        key = (slot, t.shape[0], dk, t.dtype)
-        buf = self._pads.get(key)
-        if buf is None:
-            buf = self._pads[key] = torch.zeros(t.shape[0], dk, dtype=t.dtype, device=self.dev)
-        buf[:, :t.shape[1]].copy_(t)
-        return buf
-
     def _workspaces(self, B, d):
         if self._ws_B == (B, d):
             return
@@ -145,9 +122,6 @@ class FusedTrainer(_FlatAdamTrainer):
             return "step_small"
         return "step_fused" if getattr(self, "_used_step_fused", False) else "decoder_fused"
 
-    def coefficients(self, epoch, alpha, beta, beta_annealing):
-        return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
-
     # ------------------------------------------------------------------
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=1.0, beta=1.0,
              beta_annealing=False, p_missingness=30, global_batch=None, row_lo=None, update=True, _state=None):
@@ -162,6 +136,7 @@ class FusedTrainer(_FlatAdamTrainer):
         self._timer_tick += 1
         lay, m = self.lay, self.model
         B, d, Ld = x.shape[0], lay.d, lay.L
+        # ---- inputs and padding
         x = ops._f32c(x)
         mask = as_mask_u8(mask)
         # Row pitch of the kernels' x / mask arrays.  obs_dim % 4 != 0 would take the scalar-load kernel variants (the ones
@@ -170,15 +145,11 @@ class FusedTrainer(_FlatAdamTrainer):
         # images already hold zeros for the columns / rows past obs_dim - and the 16-byte-vector variants run on those.
         dk = d if (d % 4 == 0 or lay.mask_augm) else 4 * ((d + 3) // 4)
         if dk != d:
-            x, mask = self._pad_cols(x, dk, 0), self._pad_cols(mask, dk, 1)
+            x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
             if mask_p is not None:
-                mask_p = self._pad_cols(as_mask_u8(mask_p), dk, 2)
+                mask_p = pad_cols(self._pads, as_mask_u8(mask_p), dk, 2, self.dev)
         self._workspaces(B, dk)
-        Bg = global_batch if global_batch is not None else B * self.world_size
-        if row_lo is None:
-            row_lo = self.rank * B if self.world_size > 1 else 0
-        if row_lo < 0 or row_lo + B > Bg:
-            raise ValueError(f"rows [{row_lo}, {row_lo + B}) are not inside the global batch of {Bg}")
+        Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
         two = not self.vanilla
         # Small batches run the fp32 N-split kernel (csrc/vpc_small.hip) in EVERY precision: `precision` bounds the rounding a step may
@@ -192,107 +163,104 @@ class FusedTrainer(_FlatAdamTrainer):
         # kernels read and the Adam launches re-pack; the whole-step bf16 kernel has its own image and leaves them stale
         key = m._param_key(self._plist)
         img = None if use_step else m._images(key)
-        enc_img, dec_img = (None, None) if use_step else (img[:lay.enc_img], img[lay.enc_img:])
         if use_step:
-            img_c = self._whole.get(key, m._flat)
+            imgs = (self._whole.get(key, m._flat),)
         elif self.prec and not use_small:
             img_bf = self._pair.get(key, m._flat)
-            enc_img, dec_img = img_bf[:self.enc_img_bf], img_bf[self.enc_img_bf:]
+            imgs = (img_bf[:self.enc_img_bf], img_bf[self.enc_img_bf:])
+        else:
+            imgs = (img[:lay.enc_img], img[lay.enc_img:])
         rng0 = self.rng_offset
-        # ---- random draws (mask_p and eps in ONE launch when both are drawn on the device)
-        need_ml = two and co["wml"] != 0.0
-        draw_eps = eps_q is None or (two and eps_p is None) or (need_ml and eps_ml is None)
-        eps_view = self.eps_buf[: (3 if need_ml else 2 if two else 1)]  # only the draws this step consumes
-        # counters advance by what the GLOBAL batch consumes, so that all ranks stay on one stream of counters
-        n_eps_groups = eps_view.shape[0] * Bg * (LP // 4)
-        eps_shard = (B, Bg, row_lo, LP)
-        # small batches: the N-split kernel makes the step's draws itself (same counters, one launch less) when ALL of them are
-        # drawn on the device
-        all_dev = eps_q is None and (not two or eps_p is None) and (not need_ml or eps_ml is None)
-        fuse_draw = use_small and all_dev and (not two or mask_p is None) and LP == 16
-        draw_args = None
-        if fuse_draw:
-            off_m = self.rng_offset
-            if two:
-                self.rng_offset += (Bg * dk + 7) // 8 + 1
-                mask_p = self.mask_p_buf
-            draw_args = (mask if two else None, 1.0 - p_missingness / 100.0, eps_view, self.seed, off_m, self.rng_offset, _state,
-                         row_lo * dk, eps_shard)
-            self.rng_offset += n_eps_groups
-            draw_eps = False
-        elif two and mask_p is None:
-            off_m = self.rng_offset
-            self.rng_offset += (Bg * dk + 7) // 8 + 1
-            if draw_eps:
-                self._timed("draw_step", ops.draw_step, mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, eps_view,
-                            self.seed, off_m, self.rng_offset, _state, row_lo * dk, eps_shard)
-                self.rng_offset += n_eps_groups
-                draw_eps = False
-            else:
-                ops.draw_mask(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, self.seed, off_m, row_lo * dk)
+        # ---- random draws
+        mask_p, in_kernel = self._draws(co, mask, mask_p, (eps_q, eps_p, eps_ml), B, Bg, row_lo, dk, use_small,
+                                        1.0 - p_missingness / 100.0, _state)
+        # ---- forward, loss and backward: the launches of this batch size and precision
+        nbE, nbD = self.last_blocks = self._launches(co, x, mask, mask_p, in_kernel, imgs, B, Bg, dk, use_small, use_step)
+        # ---- flat gradient + loss terms, Adam
+        self._tail(co, key, img, imgs[0] if use_step else None, nbE, nbD, B, Bg, update, _state, self.rng_offset - rng0)
+
+    def _draws(self, co, mask, mask_p, eps_in, B, Bg, row_lo, dk, use_small, keep_prob, _state):
+        """The step's draws - mask_p into mask_p_buf, eps into eps_buf - on the device unless injected, at the counters of
+        trainer.draw_counters (mask_p and eps in ONE launch when both are drawn).  All planes are drawn if any consumed
+        plane is missing; injected ones are copied over them.  Returns (mask_p, the arguments of the in-kernel draw or None)."""
+        two = not self.vanilla
+        planes = 3 if (two and co.ml_on) else 2 if two else 1  # only the draws this step consumes
+        eps_view, eps_in = self.eps_buf[:planes], eps_in[:planes]
+        draw_mask = two and mask_p is None
+        draw_eps = any(e is None for e in eps_in)
+        dr = draw_counters(self.rng_offset, draw_mask, planes if draw_eps else 0, B, Bg, row_lo, LP, dk)
+        self.rng_offset = dr.next_offset
+        # (`_state`: under graph replay the offset lives on the device - a frozen host offset would replay one eps)
+        in_kernel = None
+        if use_small and draw_mask == two and all(e is None for e in eps_in) and LP == 16:
+            # small batches: the N-split kernel makes the step's draws itself (same counters, one launch less) when ALL of
+            # them are drawn on the device
+            in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, _state,
+                         dr.elem_lo, dr.eps_shard)
+        elif draw_mask and draw_eps:
+            self._timed("draw_step", ops.draw_step, mask, self.mask_p_buf, keep_prob, eps_view, self.seed, dr.offset_mask,
+                        dr.offset_eps, _state, dr.elem_lo, dr.eps_shard)
+        elif draw_mask:
+            ops.draw_mask(mask, self.mask_p_buf, keep_prob, self.seed, dr.offset_mask, dr.elem_lo)
+        elif draw_eps:
+            ops.fill_normal(eps_view, self.seed, dr.offset_eps, _state, dr.eps_shard)
+        if draw_mask:
             mask_p = self.mask_p_buf
         elif two:
             mask_p = as_mask_u8(mask_p)
-        if draw_eps:
-            # `_state`: under graph replay the offset lives on the device (a frozen host offset would replay one eps)
-            ops.fill_normal(eps_view, self.seed, self.rng_offset, _state, eps_shard)
-            self.rng_offset += n_eps_groups
-        if eps_q is not None:  # injected draws (parity tests) arrive dense [B][L]; pad entries are ignored
-            self.eps_buf[0, :, :Ld].copy_(eps_q)
-        if two and eps_p is not None:
-            self.eps_buf[1, :, :Ld].copy_(eps_p)
-        if need_ml and eps_ml is not None:
-            self.eps_buf[2, :, :Ld].copy_(eps_ml)
-        eq = self.eps_buf[0]
-        ep = self.eps_buf[1] if two else None
-        eml = self.eps_buf[2] if need_ml else None
+        for plane, e in enumerate(eps_in):  # injected draws (parity tests) arrive dense [B][L]; pad entries are ignored
+            if e is not None:
+                self.eps_buf[plane, :, :self.lay.L].copy_(e)
+        return mask_p, in_kernel
+
+    def _launches(self, co, x, mask, mask_p, in_kernel, imgs, B, Bg, dk, use_small, use_step):
+        """Forward, loss and backward into the partial blocks; returns how many (encoder, decoder) blocks were written."""
+        lay, two = self.lay, not self.vanilla
+        Ld, inv_B, xlv = lay.L, 1.0 / Bg, self.model._x_logvar_value
         masks = [mask, mask_p] if two else [mask]
-        epss = [eq, ep] if two else [eq]
-        maskB = [mask_p, None] if (two and co["cE"][0] != 0.0) else [None] * len(masks)
+        epss = [self.eps_buf[0], self.eps_buf[1]] if two else [self.eps_buf[0]]
+        eml = self.eps_buf[2] if (two and co.ml_on) else None
+        maskB = [mask_p, None] if (two and co.maskB_on) else [None] * len(masks)
         if use_small:
-            # ---- small batch (fp32 arithmetic in every precision): the whole step in ONE launch, 16-row tiles with the feature tiles split over the waves
-            if draw_args is not None:
-                nbE = nbD = self._timed("step_small", ops.step_small_draw_f32, x, enc_img, dec_img, masks, maskB, co["cA"],
-                                        co["cE"], epss, eml, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value,
-                                        self.partE, self.partD, self.loss_part, dk, Ld, *draw_args)
+            # small batch (fp32 arithmetic in every precision): the whole step in ONE launch, 16-row tiles with the feature
+            # tiles split over the waves
+            args = (x, *imgs, masks, maskB, co, epss, eml, inv_B, xlv, self.partE, self.partD, self.loss_part, dk, Ld)
+            if in_kernel is not None:
+                nb = self._timed("step_small", ops.step_small_draw_f32, *args, *in_kernel)
             else:
-                nbE = nbD = self._timed("step_small", ops.step_small_f32, x, enc_img, dec_img, masks, maskB, co["cA"], co["cE"],
-                                        epss, eml, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value,
-                                        self.partE, self.partD, self.loss_part, dk, Ld)
-        elif use_step:
-            # ---- plain bf16, throughput shape: encoder forward + decoder + loss + all backward in ONE launch
-            nbE = nbD = self._timed("step_fused", ops.step_fused_bf16, x, img_c, masks, maskB, co["cA"], co["cE"], epss,
-                                    eml, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value, self.partE,
-                                    self.partD, self.loss_part, self._step_ws(B), dk, Ld)
-        else:
-            # ---- forward (encoder), fused decoder + loss + decoder backward, encoder backward
-            self._timed("encoder_fwd", ops.encoder_fwd, x, enc_img, masks, None, self.h1, self.h2, self.mean, self.logvar,
-                        None, dk, Ld, LP, lay.mask_augm, self.prec)
-            nbD = self._timed("decoder_fused", ops.decoder_fused, x, dec_img, masks, maskB, co["cA"], co["cE"], self.mean,
-                              self.logvar, epss, eml, co["bq"], co["bp"], co["cr"], co["wml"], 1.0 / Bg, m._x_logvar_value,
-                              self.dmean, self.dlogvar, self.partD, self.loss_part, dk, Ld, LP, self.prec)
-            nbE = self._timed("encoder_bwd", ops.encoder_bwd, x, enc_img, masks, self.h1, self.h2, self.dmean,
-                              self.dlogvar, self.partE, dk, Ld, LP, lay.mask_augm, self.prec)
-        # ---- flat gradient + loss terms (+ Adam when nothing has to happen between them): one launch
-        cA1 = co["cA"][1] if two else 0.0
-        self.last_blocks = (nbE, nbD)
+                nb = self._timed("step_small", ops.step_small_f32, *args)
+            return nb, nb
+        if use_step:
+            # plain bf16, throughput shape: encoder forward + decoder + loss + all backward in ONE launch
+            nb = self._timed("step_fused", ops.step_fused_bf16, x, imgs[0], masks, maskB, co, epss, eml, inv_B, xlv,
+                             self.partE, self.partD, self.loss_part, self._step_ws(B), dk, Ld)
+            return nb, nb
+        # forward (encoder), fused decoder + loss + decoder backward, encoder backward
+        enc_img, dec_img = imgs
+        self._timed("encoder_fwd", ops.encoder_fwd, x, enc_img, masks, None, self.h1, self.h2, self.mean, self.logvar,
+                    None, dk, Ld, LP, lay.mask_augm, self.prec)
+        nbD = self._timed("decoder_fused", ops.decoder_fused, x, dec_img, masks, maskB, co, self.mean, self.logvar, epss,
+                          eml, inv_B, xlv, self.dmean, self.dlogvar, self.partD, self.loss_part, dk, Ld, LP, self.prec)
+        nbE = self._timed("encoder_bwd", ops.encoder_bwd, x, enc_img, masks, self.h1, self.h2, self.dmean,
+                          self.dlogvar, self.partE, dk, Ld, LP, lay.mask_augm, self.prec)
+        return nbE, nbD
+
+    def _tail(self, co, key, img, img_c, nbE, nbD, B, Bg, update, _state, rng_inc):
+        """Partial blocks -> flat gradient + loss terms (+ Adam when nothing has to happen between them: one launch).
+        img_c: the compact bf16 image when the whole-step kernel ran (else None), img: the model's fp32 images."""
+        lay, m, use_step = self.lay, self.model, img_c is not None
+        blocks = (self.partE, nbE, lay.enc_part, self.partD, nbD, lay.dec_part, self.gidx, self.grad, lay.n_enc,
+                  self.loss_part, nbD, co, B, Bg, lay.d, self.out9)
         if update and not self.dp and _state is None:
             self.step_count += 1
             # the fused Adam re-packs the image the step read: the whole-step kernel's compact bf16 image, else the model's
             # fp32 images (the pair-slot bf16 image goes stale and is re-packed by whoever needs it next)
-            self._timed("reduce_step", ops.reduce_step_adam, self.partE, nbE, lay.enc_part, self.partD, nbD,
-                        lay.dec_part, self.gidx, self.grad, lay.n_enc, self.loss_part, nbD, co["cA"][0], co["cE"][0],
-                        cA1, co["bq"], co["bp"], co["cr"], co["wml"], B, Bg, d, self.out9, self.accum, m._flat,
-                        self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.adam_eps,
-                        self.step_count, self.pidx_c if use_step else self.pidx, img_c if use_step else img, self.inv,
-                        use_step)
+            self._timed("reduce_step", ops.reduce_step_adam, *blocks, self.accum, m._flat, self.exp_avg, self.exp_avg_sq,
+                        self.lr, self.betas[0], self.betas[1], self.adam_eps, self.step_count,
+                        self.pidx_c if use_step else self.pidx, img_c if use_step else img, self.inv, use_step)
             self._flat_written(key, self._whole if use_step else m._img)
             return
-        ops.reduce_step(self.partE, nbE, lay.enc_part, self.partD, nbD, lay.dec_part,
-                    self.gidx, self.grad, lay.n_enc, self.loss_part, nbD, co["cA"][0], co["cE"][0], cA1, co["bq"],
-                    co["bp"], co["cr"], co["wml"], B, Bg, d, self.out9,
-                    None if self.dp else self.accum, _state,
-                    self.rng_offset - rng0 if _state is not None else 0, self.inv)
+        ops.reduce_step(*blocks, None if self.dp else self.accum, _state, rng_inc if _state is not None else 0, self.inv)
         if self.dp:
             self._allreduce()
         if update:
@@ -330,6 +298,6 @@ class FusedTrainer(_FlatAdamTrainer):
         x = ops._f32c(x)
         mask = as_mask_u8(mask)
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
-        key = (tuple(x.shape), p_missingness, tuple(co["cA"]), tuple(co["cE"]), co["bq"], co["bp"], co["cr"], co["wml"])
+        key = (tuple(x.shape), p_missingness, bytes(co))
         kw = dict(epoch=epoch, alpha=alpha, beta=beta, beta_annealing=beta_annealing, p_missingness=p_missingness)
         self._graph_step(key, (x, mask), lambda *a, **k: self.step(*a, **kw, **k))

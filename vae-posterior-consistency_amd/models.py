@@ -17,6 +17,8 @@ There is no CPU fallback: calling forward / loss with CPU tensors raises.
 """
 from __future__ import annotations
 
+from functools import lru_cache
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -27,6 +29,27 @@ from .images import FlatParams, PackedImage, mlp_spec
 from .ops import DecoderFn, EncoderFn, LossFn, as_mask_u8
 
 MAX_EPOCH = 2800  # VAE.py:384
+
+
+@lru_cache(maxsize=256)
+def loss_coef(kind, epoch, alpha, beta, beta_annealing):
+    """The coefficients of the generic loss form (include/vpc.h) as one record: kind "vanilla" is the one-pass ELBO
+    (VAE.py:1183-1195), else a reg_type of the two-pass losses (VAE.py:425-446).  One record per distinct set of arguments,
+    shared by its callers: read-only."""
+    bw = (epoch / MAX_EPOCH) * beta if beta_annealing else beta
+    if kind == "vanilla":
+        return L.VpcLossCoef([1.0], [0.0], bw)
+    if kind == "kl_reg":  # VAE.py:441-446
+        return L.VpcLossCoef([1.0 - alpha, alpha], [alpha, 0.0], (1.0 - alpha) * bw, alpha * bw, alpha)
+    if kind == "ml_reg":  # VAE.py:435-440 (draws one more eps)
+        return L.VpcLossCoef([1.0, 0.0], [0.0, 0.0], bw, wml=(epoch / MAX_EPOCH) * alpha)
+    print("Not implemented!")  # VAE.py:447-449
+    raise NotImplementedError(f"reg_type {kind!r}")
+
+
+def loss_coefficients(model, epoch, alpha, beta, beta_annealing):
+    """loss_coef of a model's training loss."""
+    return loss_coef("vanilla" if isinstance(model, vanilla_VAE) else model.reg_type, epoch, alpha, beta, bool(beta_annealing))
 
 _W6 = ("W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4", "W5", "b5", "W6", "b6")
 

@@ -531,14 +531,12 @@ class NMTrainer(_FlatAdamTrainer):
         xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
         L.require_cuda(xf, mf)
         B = xf.shape[0]
-        Bg = global_batch or B * self.world_size  # every rank normalises by the GLOBAL batch: SUM over ranks = result
+        Bg, row_lo = self._batch_rows(B, global_batch or None, row_lo)  # every rank normalises by the GLOBAL batch: SUM over ranks = result
         self._ws(B, v)
         reg = self.reg
         P = 2 if reg else 1
         R, M, BK = P * B, P * B * K, B * K
         t = self._timed
-        if row_lo is None:
-            row_lo = self.rank * B if self.world_size > 1 else 0
         rng_inc = (2 * Bg * K * Ld + 3) // 4 + (Bg * d + 3) // 4 + 1  # what the GLOBAL batch consumes
         sharded = (row_lo * d) % 4 == 0 and (K * Ld) % 4 == 0
         # shapes whose shards do not start on a Philox group: per-rank counter streams instead of global-row counters

@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib as L
-from ._lib import check, farray, lib, ptr, ptr_array, require_cuda, stream_ptr
+from ._lib import check, lib, ptr, ptr_array, require_cuda, stream_ptr
 from .linear import _f32c  # noqa: F401  (also reached as ops._f32c)
 
 H1P, H2P = 112, 64  # padded hidden widths of the h1 / h2 workspaces (csrc/vpc_layout.h)
@@ -93,26 +93,25 @@ def decoder_bwd(z, dxhat, dec_img, dz, partials, d, Ld):
     return nb.value
 
 
-def loss_fwd_bwd(x, xhat, maskA, maskB, cA, cE, mean, logvar, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, dxhat, dmean,
-                 dlogvar, loss_part, d, Ld):
+def loss_fwd_bwd(x, xhat, maskA, maskB, co, mean, logvar, eps_ml, inv_B, x_logvar, dxhat, dmean, dlogvar, loss_part, d, Ld):
+    """co: the loss coefficients, a _lib.VpcLossCoef (here and in every wrapper below that takes `co`)."""
     n = len(xhat)
     nb = C.c_int(0)
     want = dxhat is not None
-    check(lib().vpc_loss_fwd_bwd(ptr(x), n, ptr_array(xhat), ptr_array(maskA), ptr_array(maskB), farray(cA), farray(cE),
-                                 ptr_array(mean), ptr_array(logvar), ptr(eps_ml), bq, bp, cr, wml, inv_B, x_logvar,
+    check(lib().vpc_loss_fwd_bwd(ptr(x), n, ptr_array(xhat), ptr_array(maskA), ptr_array(maskB), co,
+                                 ptr_array(mean), ptr_array(logvar), ptr(eps_ml), inv_B, x_logvar,
                                  ptr_array(dxhat) if want else None, ptr_array(dmean) if want else None,
                                  ptr_array(dlogvar) if want else None, ptr(loss_part), loss_part.shape[0],
                                  C.byref(nb), x.shape[0], d, Ld, stream_ptr()), "vpc_loss_fwd_bwd")
     return nb.value
 
 
-def decoder_fused(x, dec_img, maskA, maskB, cA, cE, mean, logvar, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, dmean,
-                  dlogvar, partials, loss_part, d, Ld, lat_pitch=None, precision=0):
+def decoder_fused(x, dec_img, maskA, maskB, co, mean, logvar, eps, eps_ml, inv_B, x_logvar, dmean, dlogvar, partials,
+                  loss_part, d, Ld, lat_pitch=None, precision=0):
     n = len(maskA)
     nb = C.c_int(0)
-    check(lib().vpc_decoder_fused(ptr(x), ptr(dec_img), n, ptr_array(maskA), ptr_array(maskB), farray(cA), farray(cE),
-                                  ptr_array(mean), ptr_array(logvar), ptr_array(eps), ptr(eps_ml), bq, bp, cr, wml,
-                                  inv_B, x_logvar, ptr_array(dmean), ptr_array(dlogvar), lat_pitch or Ld, int(precision),
+    check(lib().vpc_decoder_fused(ptr(x), ptr(dec_img), n, ptr_array(maskA), ptr_array(maskB), co,
+                                  ptr_array(mean), ptr_array(logvar), ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr_array(dmean), ptr_array(dlogvar), lat_pitch or Ld, int(precision),
                                   ptr(partials), ptr(loss_part), C.byref(nb), x.shape[0], d, Ld, stream_ptr()),
           "vpc_decoder_fused")
     return nb.value
@@ -122,27 +121,25 @@ def step_small_max_rows():
     return int(lib().vpc_step_small_max_rows())
 
 
-def step_small_f32(x, enc_img, dec_img, masks, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE, partD,
-                   loss_part, d, Ld):
+def step_small_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d, Ld):
     """Whole fp32 step of a small batch in one launch (16-row tiles, feature tiles split over the waves); returns the
     number of partial blocks."""
     n = len(masks)
     nb = C.c_int(0)
-    check(lib().vpc_step_small_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), farray(cA),
-                                   farray(cE), ptr_array(eps), ptr(eps_ml), bq, bp, cr, wml, inv_B, x_logvar, ptr(partE),
+    check(lib().vpc_step_small_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                   ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE),
                                    ptr(partD), ptr(loss_part), C.byref(nb), x.shape[0], d, Ld, stream_ptr()), "vpc_step_small_f32")
     return nb.value
 
 
-def step_small_draw_f32(x, enc_img, dec_img, masks, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE, partD,
-                        loss_part, d, Ld, mask_in, keep_prob, eps_out, seed, offset_mask, offset_eps, state=None, elem_lo=0,
+def step_small_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d, Ld, mask_in, keep_prob, eps_out, seed, offset_mask, offset_eps, state=None, elem_lo=0,
                         eps_shard=None):
     """step_small_f32 that also makes the step's draws (mask_p = mask_in & keep into masks[1], eps into eps_out = eps[0]...)
     inside the same launch, with vpc_draw_step's counters."""
     n = len(masks)
     nb = C.c_int(0)
-    check(lib().vpc_step_small_draw_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), farray(cA),
-                                        farray(cE), ptr_array(eps), ptr(eps_ml), bq, bp, cr, wml, inv_B, x_logvar, ptr(partE),
+    check(lib().vpc_step_small_draw_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                        ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE),
                                         ptr(partD), ptr(loss_part), C.byref(nb), x.shape[0], d, Ld, ptr(mask_in),
                                         float(keep_prob), ptr(eps_out), eps_out.numel(), int(seed), int(offset_mask),
                                         int(offset_eps), ptr(state), int(elem_lo), *_shard4(eps_shard), stream_ptr()),
@@ -186,39 +183,35 @@ def step_workspace_floats(B):
     return int(lib().vpc_step_workspace_floats(int(B)))
 
 
-def step_fused_bf16(x, img_c, masks, maskB, cA, cE, eps, eps_ml, bq, bp, cr, wml, inv_B, x_logvar, partE, partD, loss_part,
-                    ws, d, Ld):
+def step_fused_bf16(x, img_c, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, ws, d, Ld):
     """Whole step (encoder fwd + decoder + loss + all backward) in one launch; returns the number of partial blocks."""
     n = len(masks)
     nb = C.c_int(0)
-    check(lib().vpc_step_fused_bf16(ptr(x), ptr(img_c), n, ptr_array(masks), ptr_array(maskB), farray(cA), farray(cE),
-                                    ptr_array(eps), ptr(eps_ml), bq, bp, cr, wml, inv_B, x_logvar, ptr(partE), ptr(partD),
+    check(lib().vpc_step_fused_bf16(ptr(x), ptr(img_c), n, ptr_array(masks), ptr_array(maskB), co,
+                                    ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE), ptr(partD),
                                     ptr(loss_part), ptr(ws), C.byref(nb), x.shape[0], d, Ld, stream_ptr()), "vpc_step_fused_bf16")
     return nb.value
 
 
-def loss_finalize(loss_part, nblocks, cA0, cE0, cA1, bq, bp, cr, wml, B_local, B_global, d, out9, accum=None):
-    check(lib().vpc_loss_finalize(ptr(loss_part), nblocks, cA0, cE0, cA1, bq, bp, cr, wml, B_local, B_global, d,
-                                  ptr(out9), ptr(accum), stream_ptr()), "vpc_loss_finalize")
+def loss_finalize(loss_part, nblocks, co, B_local, B_global, d, out9, accum=None):
+    check(lib().vpc_loss_finalize(ptr(loss_part), nblocks, co, B_local, B_global, d, ptr(out9), ptr(accum), stream_ptr()),
+          "vpc_loss_finalize")
 
 
-def reduce_step(partE, nbE, strideE, partD, nbD, strideD, grad_idx, grad, n_enc, loss_part, nbL, cA0, cE0, cA1, bq, bp,
-                cr, wml, B_local, B_global, d, out9, accum=None, state=None, rng_inc=0, inv_maps=None):
+def reduce_step(partE, nbE, strideE, partD, nbD, strideD, grad_idx, grad, n_enc, loss_part, nbL, co, B_local, B_global, d,
+                out9, accum=None, state=None, rng_inc=0, inv_maps=None):
     check(lib().vpc_reduce_step(ptr(partE), nbE, strideE, ptr(partD), nbD, strideD, ptr(grad_idx), ptr(inv_maps),
-                                ptr(grad), n_enc,
-                                grad.numel(), ptr(loss_part), nbL, cA0, cE0, cA1, bq, bp, cr, wml, B_local, B_global, d,
+                                ptr(grad), n_enc, grad.numel(), ptr(loss_part), nbL, co, B_local, B_global, d,
                                 ptr(out9), ptr(accum), ptr(state), int(rng_inc), stream_ptr()), "vpc_reduce_step")
 
 
-def reduce_step_adam(partE, nbE, strideE, partD, nbD, strideD, grad_idx, grad, n_enc, loss_part, nbL, cA0, cE0, cA1, bq,
-                     bp, cr, wml, B_local, B_global, d, out9, accum, params, m, v, lr, beta1, beta2, eps, step, pack_idx,
-                     img, inv_maps=None, bf16c=False):
+def reduce_step_adam(partE, nbE, strideE, partD, nbD, strideD, grad_idx, grad, n_enc, loss_part, nbL, co, B_local, B_global,
+                     d, out9, accum, params, m, v, lr, beta1, beta2, eps, step, pack_idx, img, inv_maps=None, bf16c=False):
     """bf16c: (pack_idx, img) are the compact bf16 image tables of the whole-step kernel (re-packed instead of the fp32 images)."""
     fn = lib().vpc_reduce_step_adam_bf16c if bf16c else lib().vpc_reduce_step_adam
-    check(fn(ptr(partE), nbE, strideE, ptr(partD), nbD, strideD, ptr(grad_idx), ptr(inv_maps),
-                                     ptr(grad), n_enc, grad.numel(), ptr(loss_part), nbL, cA0, cE0, cA1, bq, bp, cr, wml, B_local,
-                                     B_global, d, ptr(out9), ptr(accum), ptr(params), ptr(m), ptr(v), lr, beta1, beta2,
-                                     eps, int(step), ptr(pack_idx), ptr(img), stream_ptr()), "vpc_reduce_step_adam")
+    check(fn(ptr(partE), nbE, strideE, ptr(partD), nbD, strideD, ptr(grad_idx), ptr(inv_maps), ptr(grad), n_enc, grad.numel(),
+             ptr(loss_part), nbL, co, B_local, B_global, d, ptr(out9), ptr(accum), ptr(params), ptr(m), ptr(v), lr, beta1,
+             beta2, eps, int(step), ptr(pack_idx), ptr(img), stream_ptr()), "vpc_reduce_step_adam")
 
 
 def draw_mask(mask_in, mask_out, keep_prob, seed, offset, elem_lo=0):
@@ -398,15 +391,15 @@ class LossFn(torch.autograd.Function):
         dl = [torch.empty_like(t) for t in ls] if need_grad else None
         max_blocks = L.num_cus() * 8
         lp_buf = torch.empty(max_blocks, 8, dtype=torch.float64, device=dev)
-        nb = loss_fwd_bwd(x, xs, cfg["maskA"], cfg["maskB"], cfg["cA"], cfg["cE"], ms, ls, eps_ml, cfg["bq"], cfg["bp"],
-                          cfg["cr"], cfg["wml"], 1.0 / B, cfg["x_logvar"], dx, dm, dl, lp_buf, d, Ld)
+        n = len(xs)  # (the entries of the passes that run)
+        co = L.VpcLossCoef(cfg["cA"][:n], cfg["cE"][:n], cfg["bq"], cfg["bp"], cfg["cr"], cfg["wml"])
+        nb = loss_fwd_bwd(x, xs, cfg["maskA"], cfg["maskB"], co, ms, ls, eps_ml, 1.0 / B, cfg["x_logvar"], dx, dm, dl, lp_buf,
+                          d, Ld)
         # block partials -> [loss | 8 raw sums] in ONE launch (vpc_loss_finalize: doubles inside, fixed order): the torch
         # expression it replaces was ~15 tiny launches per loss() call - the API path is launch-bound at the reference's
         # batch sizes
-        cA, cE = cfg["cA"], cfg["cE"]
         out9 = torch.empty(9, device=dev)
-        loss_finalize(lp_buf, nb, cA[0], cE[0], cA[1] if two else 0.0, cfg["bq"], cfg["bp"] if two else 0.0,
-                      cfg["cr"] if two else 0.0, cfg["wml"] if two else 0.0, B, B, d, out9)
+        loss_finalize(lp_buf, nb, co, B, B, d, out9)
         loss, sums = out9[0], out9[1:]
         ctx.two = two
         if need_grad:

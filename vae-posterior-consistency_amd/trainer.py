@@ -4,13 +4,46 @@ that data parallelism all-reduces in ONE collective, the deferred weight gradien
 one reduction launch), timers, the loss readers and the capture / replay of a step as a HIP graph."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import _lib as L
 from . import dist as dp_mod
 from .images import flat_written
 from .linear import linear_wgrad, wgrad_reduce
+from .models import loss_coefficients
 from .ops import adam_step
+
+
+class Draws(NamedTuple):
+    """Philox counters of one step's draws (draw_counters)."""
+    offset_mask: int  # of the mask_p draw
+    offset_eps: int  # of the eps planes
+    next_offset: int  # the trainer's rng_offset after the step
+    elem_lo: int  # index of this rank's first mask element inside the global [rows_global, row_width] array
+    eps_shard: tuple  # (rows_local, rows_global, row_lo, pitch) as ops.draw_step / fill_normal / step_small_draw_f32 take it
+
+
+def draw_counters(rng_offset, draw_mask, planes, rows_local, rows_global, row_lo, pitch, row_width):
+    """THE counter rule of the dense-VAE step's draws, for every trainer that makes them.  mask_p
+    comes first: one Philox call serves 8 bytes of the GLOBAL [rows_global, row_width] array, and the draw consumes one
+    counter per 8 elements of that array, rounded up, and one more.  Then `planes` eps planes of `pitch` floats per row,
+    one call per 4 floats.  Counters advance by what the GLOBAL batch consumes, so all ranks stay on one stream and a row's
+    draws do not depend on the world size.  No mask draw: offset_mask == offset_eps == rng_offset; planes may be 0."""
+    offset_eps = rng_offset + ((rows_global * row_width + 7) // 8 + 1 if draw_mask else 0)
+    return Draws(rng_offset, offset_eps, offset_eps + planes * rows_global * (pitch // 4), row_lo * row_width,
+                 (rows_local, rows_global, row_lo, pitch))
+
+
+def pad_cols(pads, t, dk, slot, dev):
+    """[..., B, d] -> zero-padded [..., B, dk]: a persistent buffer per input slot, kept in the dict `pads`."""
+    key = (slot, tuple(t.shape[:-1]), dk, t.dtype)
+    buf = pads.get(key)
+    if buf is None:
+        buf = pads[key] = torch.zeros(*t.shape[:-1], dk, dtype=t.dtype, device=dev)
+    buf[..., :t.shape[-1]].copy_(t)
+    return buf
 
 
 class _FlatAdamTrainer:
@@ -46,6 +79,19 @@ class _FlatAdamTrainer:
         for p in self._plist:
             p.grad = self.grad[off:off + p.numel()].view_as(p)
             off += p.numel()
+
+    def coefficients(self, epoch, alpha, beta, beta_annealing):
+        return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
+
+    def _batch_rows(self, B, global_batch=None, row_lo=None):
+        """(rows of the global batch, global index of this rank's first row): by default B * world_size rows of which this
+        rank holds [rank * B, (rank + 1) * B)."""
+        Bg = global_batch if global_batch is not None else B * self.world_size
+        if row_lo is None:
+            row_lo = self.rank * B if self.world_size > 1 else 0
+        if row_lo < 0 or row_lo + B > Bg:
+            raise ValueError(f"rows [{row_lo}, {row_lo + B}) are not inside the global batch of {Bg}")
+        return Bg, row_lo
 
     def _timed(self, name, fn, *args, **kw):
         """Run one launch; with timers enabled bracket it with events on the launch stream."""

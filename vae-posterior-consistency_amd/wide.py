@@ -19,7 +19,7 @@ from . import ops
 from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, _f32c, linear_dgrad, linear_fwd, linear_wgrad
 from .notmiwae import nm_mul, nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
-from .trainer import _FlatAdamTrainer
+from .trainer import _FlatAdamTrainer, draw_counters
 
 H1, H2 = 100, 50
 
@@ -128,20 +128,20 @@ class WideTrainer(_FlatAdamTrainer):
         m = self.model
         x = _f32c(x)
         B, d, Ld = x.shape[0], m.obs_dim, m.latent_dim
-        Bg = global_batch if global_batch is not None else B * self.world_size
-        if row_lo is None:
-            row_lo = self.rank * B if self.world_size > 1 else 0
+        Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         mu8 = as_mask_u8(mask)
         two = not self.vanilla
-        if two and mask_p is None:  # Philox counters of the GLOBAL row
-            mask_p = torch.empty(B, d, dtype=torch.uint8, device=self.dev)
-            ops.draw_mask(mu8, mask_p, 1.0 - p_missingness / 100.0, self.seed, self.rng_offset, row_lo * d)
-            self.rng_offset += (Bg * d + 7) // 8 + 1
         n_eps = 2 if two else 1
-        if eps_q is None or (two and eps_p is None):
-            e = torch.empty(n_eps, B, 4 * ((Ld + 3) // 4), device=self.dev)
-            ops.fill_normal(e, self.seed, self.rng_offset, None, (B, Bg, row_lo, e.shape[2]))
-            self.rng_offset += n_eps * Bg * (e.shape[2] // 4)
+        draw_mask, draw_eps = two and mask_p is None, eps_q is None or (two and eps_p is None)
+        # Philox counters of the GLOBAL row
+        dr = draw_counters(self.rng_offset, draw_mask, n_eps if draw_eps else 0, B, Bg, row_lo, 4 * ((Ld + 3) // 4), d)
+        self.rng_offset = dr.next_offset
+        if draw_mask:
+            mask_p = torch.empty(B, d, dtype=torch.uint8, device=self.dev)
+            ops.draw_mask(mu8, mask_p, 1.0 - p_missingness / 100.0, self.seed, dr.offset_mask, dr.elem_lo)
+        if draw_eps:
+            e = torch.empty(n_eps, B, dr.eps_shard[3], device=self.dev)
+            ops.fill_normal(e, self.seed, dr.offset_eps, None, dr.eps_shard)
             eps_q = e[0, :, :Ld].contiguous() if eps_q is None else eps_q
             eps_p = (e[1, :, :Ld].contiguous() if eps_p is None else eps_p) if two else None
         for p in m.trainable():
