@@ -45,13 +45,8 @@ def main():
         if tr is not None:
             tr.step(x, m, epoch=1, alpha=0.5, p_missingness=30)
             return tr.out9[0]
-        if a.vanilla:
-            o = model.forward(x, m)
-            _, tl = model.loss(x, o[2], o[3], o[0], o[1], 1, m)
-        else:
-            mp = vpc_amd.create_missing_uci(x.shape, 30) * m
-            o = model.forward(x, m, mp, "train")
-            _, tl = model.loss(x, o[2], o[3], o[0], o[1], o[6], o[7], o[4], o[5], m, mp, 1, alpha=0.5)
+        mp = None if a.vanilla else vpc_amd.create_missing_uci(x.shape, 30) * m
+        _, (_, tl) = model.forward_loss(x, m, mp, epoch=1, alpha=0.5)
         opt.zero_grad()
         tl.backward()
         opt.step()

@@ -117,13 +117,8 @@ def bench_step(kind, B, d, steps, warmup, emit, cpu_reps, cpu_B=None):
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
 
     def api():
-        if reg:
-            mp = vpc_amd.create_missing_uci(xd.shape, 30, device="cuda") * md
-            o = model.forward(xd, md, mp)
-            _, tl = model.loss(xd, o[6], o[7], o[4], o[5], o[2], o[3], o[0], o[1], md, mp, 0.5)
-        else:
-            o = model.forward(xd, md)
-            _, tl = model.loss(xd, o[2], o[3], o[0], o[1], md)
+        mp = vpc_amd.create_missing_uci(xd.shape, 30, device="cuda") * md if reg else None
+        _, (_, tl) = model.forward_loss(xd, md, mp, alpha=0.5)
         opt.zero_grad()
         tl.backward()
         opt.step()

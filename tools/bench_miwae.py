@@ -115,13 +115,8 @@ def bench_step(kind, B, d, S, L, steps, warmup, emit, cpu_reps, cpu_B=None):
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
 
     def api():
-        if kind == "reg":
-            mp = vpc_amd.create_missing_uci(xd.shape, 30, device="cuda") * md
-            o = model.forward(xd, md, mp)
-            _, tl = model.loss(xd, o[2], o[3], o[4], o[0], o[1], o[7], o[8], o[9], o[5], o[6], md, mp, 1, alpha=0.5)
-        else:
-            o = model.forward(xd, md)
-            _, tl = model.loss(xd, o[2], o[3], o[4], o[0], o[1], md, 1)
+        mp = vpc_amd.create_missing_uci(xd.shape, 30, device="cuda") * md if kind == "reg" else None
+        _, (_, tl) = model.forward_loss(xd, md, mp, epoch=1, alpha=0.5)
         opt.zero_grad()
         tl.backward()
         opt.step()

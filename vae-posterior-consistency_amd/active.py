@@ -265,11 +265,8 @@ def mc_forward(model, x, mask, mask_p, M, stage="evaluate"):
     Normal.rsample are i.i.d. per row, so M calls of model.forward on n rows == one call on M n rows): [M, n, d]."""
     n, d = x.shape
     xr, mr = x.repeat(M, 1), mask.repeat(M, 1)
-    if hasattr(model, "reg_type"):  # Reg_VAE family: forward(data, mask, mask_p, stage) -> (..p.., mean_q, logvar_q, x_mean_q, ..)
-        x_mean = model.forward(xr, mr, mask_p.repeat(M, 1), stage)[6]
-    else:
-        x_mean = model.forward(xr, mr)[2]
-    return x_mean.reshape(M, n, d)
+    o = model.forward(xr, mr, mask_p.repeat(M, 1), stage) if model.regularised else model.forward(xr, mr)
+    return o[model.X_MEAN_Q].reshape(M, n, d)
 
 
 def active_learning_func(data_loader_train, test_data, test_mask, missing_rate, obs_dim, hid_dim, K, M, latent_dim,
@@ -312,7 +309,7 @@ def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, R
     """The loop body of evaluate.py:340-455 shared by active_learning_func and active_learning_flow.
     load() -> a model for a repeat without one; passes(mdl, x, mask, mask_p) -> x_mean [M, n, d];
     reward(mdl, x, mask, im, step) -> R [n, d-1]."""
-    from .harness import create_missing_uci
+    from .harness import draw_mask_p
     dev = torch.device(device) if device is not None else torch.device("cuda")
     n_test, d = test_data.shape[0], obs_dim
     info = torch.zeros(Repeat, n_test, d)
@@ -325,7 +322,7 @@ def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, R
     with torch.no_grad():
         for r in range(Repeat):
             mdl = (load() if model is None or r > 0 else model).to(dev)
-            mask_p = tmask * create_missing_uci(tuple(test_data.shape), p_missingness, device=dev)  # evaluate.py:349-350
+            mask_p = draw_mask_p(mdl, tuple(test_data.shape), tmask, p_missingness, dev)  # evaluate.py:349-350
             mask = torch.zeros(n_test, d, device=dev)
 
             def target_mse(xm):  # mean over the M passes of F.mse_loss on the target column (evaluate.py:390-392)
@@ -347,11 +344,11 @@ def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, R
 
 
 def _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
+    from .harness import _save
     if save:
         paths = active_result_paths(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
         for k, pth in paths.items():
-            os.makedirs(os.path.dirname(pth), exist_ok=True)
-            torch.save(out[k], pth)
+            _save(out[k], pth)
     return out
 
 
@@ -373,9 +370,8 @@ def active_learning_flow(data_loader_train, test_data, test_mask, missing_rate, 
     def passes(mdl, x, cur_mask, mask_p):
         if _forward is not None:
             return torch.stack([_forward(cur_mask).to(x.device) for _ in range(M)], 0)
-        if mdl.regularised:  # evaluate.py:396-399
-            return torch.stack([mdl.forward(x, cur_mask, mask_p)[6] for _ in range(M)], 0)
-        return torch.stack([mdl.forward(x, cur_mask)[2] for _ in range(M)], 0)
+        args = (x, cur_mask, mask_p) if mdl.regularised else (x, cur_mask)  # evaluate.py:396-399
+        return torch.stack([mdl.forward(*args)[mdl.X_MEAN_Q] for _ in range(M)], 0)
 
     def reward(mdl, x, mask, im, t):
         steps[0] += 1

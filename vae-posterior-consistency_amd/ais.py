@@ -33,7 +33,6 @@ applies and no mask is given, else gemm.  MIWAE / Reg_MIWAE raise under every en
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -248,12 +247,9 @@ def ais_trajectory(loader, obs_dim, hid_dim, K, latent_dim, missing_rate, data_t
     device = torch.device(device)
     if device.type != "cuda":
         raise VpcError("this path runs only on the GPU (HIP kernels, no CPU fallback)")
-    if model is None:
-        from .harness import model_loader
-        model = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                             max_epochs, num_samples, num_estimates, experiment_type, reg_type, vae_type, alpha,
-                             p_missingness)
-    model.to(device)
+    from .harness import _model_for_eval, _save
+    model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                            max_epochs, num_samples, num_estimates, experiment_type, reg_type, vae_type, alpha, p_missingness)
     assert mode == "forward" or mode == "backward", "Should have forward/backward mode"
     model.eval()
     print("In %s mode" % mode)
@@ -273,10 +269,8 @@ def ais_trajectory(loader, obs_dim, hid_dim, K, latent_dim, missing_rate, data_t
         latents.append(z.reshape(nb, n_sample, model.latent_dim))  # AIS.py:225
         print("last batch stats %.4f" % lw.mean().item())
     f_ais, f_lat = _paths(vae_type, data_type, missing_rate, max_epochs, stage)
-    for f in (f_ais, f_lat):
-        os.makedirs(os.path.dirname(f), exist_ok=True)  # (the reference expects the folders to exist)
-    torch.save(torch.stack(logws).mean(), f_ais)
-    torch.save(torch.cat(latents, 0), f_lat)
+    _save(torch.stack(logws).mean(), f_ais)
+    _save(torch.cat(latents, 0), f_lat)
     return logws
 
 

@@ -53,20 +53,28 @@ def _pitch(n):
     return (n + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
 
 
+def stackable(model):
+    """Can `model` be one row of a stack?  THE predicate of stack_models, EnsembleTrainer and harness.train_sweep: exactly
+    Reg_VAE or vanilla_VAE (no subclass: not mask-augmented, not EDDI) on the small layouts (not wide)."""
+    return type(model) in (Reg_VAE, vanilla_VAE) and not model._wide
+
+
+def _require_stackable(m):
+    if not stackable(m):
+        if getattr(m, "mask_augm", False) or getattr(m, "_wide", False):
+            raise L.VpcError("ensemble members are plain (not mask-augmented) models with obs_dim <= 128 and latent_dim <= 15")
+        raise TypeError(f"EnsembleTrainer supports Reg_VAE and vanilla_VAE members, got {type(m).__name__}")
+
+
 def validate_members(models, world_size=1):
-    """What one ensemble can hold: plain, not wide Reg_VAE or vanilla_VAE members of ONE class, shape and reg_type, on one
-    process.  Raises before anything touches the device."""
+    """What one ensemble can hold: stackable members of ONE class, shape and reg_type, on one process.  Raises before
+    anything touches the device."""
     if world_size > 1:
         raise L.VpcError("EnsembleTrainer is single-process: data parallelism is not part of the ensemble step")
     if len(models) == 0:
         raise L.VpcError("an ensemble needs at least one member")
     for m in models:
-        if not isinstance(m, (Reg_VAE, vanilla_VAE)):
-            raise TypeError(f"EnsembleTrainer supports Reg_VAE and vanilla_VAE members, got {type(m).__name__}")
-        if m.mask_augm or getattr(m, "_wide", False):
-            raise L.VpcError("ensemble members are plain (not mask-augmented) models with obs_dim <= 128 and latent_dim <= 15")
-        if type(m) not in (Reg_VAE, vanilla_VAE):
-            raise TypeError(f"EnsembleTrainer supports Reg_VAE and vanilla_VAE members, got {type(m).__name__}")
+        _require_stackable(m)
     m0 = models[0]
     for m in models[1:]:
         if type(m) is not type(m0):
@@ -85,6 +93,8 @@ def stack_models(models):
     models = list(models)
     if len(models) == 0:
         raise L.VpcError("an ensemble needs at least one member")
+    for m in models:
+        _require_stackable(m)
     first = models[0].__dict__.get("_stack")
     if first is not None and len(first[1]) == len(models) and all(a is b for a, b in zip(first[1], models)) and \
             all(m.flatten_parameters().data_ptr() == first[0][g].data_ptr() for g, m in enumerate(models)):

@@ -195,7 +195,7 @@ class _Flow(nn.Module):
 
 
 class _FlowBase(FlatParams, nn.Module):
-    regularised = False
+    regularised, X_MEAN_Q = False, 2  # forward takes mask_p; index of the q pass's reconstruction mean in forward's tuple
     _ENC_NAMES, _DEC_NAMES = _ENC_NAMES, _DEC_NAMES
     # flat parameter buffer: [We1 be1 We2 be2 We3 be3 | Wd1 bd1 .. Wd4 bd4 Wm bm] = state_dict order of the 16 tensors that get
     # a gradient; the other 9 stay ordinary parameters outside it
@@ -274,6 +274,17 @@ class _FlowBase(FlatParams, nn.Module):
         xm_p, z_p, zlp_p = (None, None, None) if p is None else p
         return FlowLossFn.apply(cfg, xf, mf, mpf, c(q[0]), c(q[1]), c(q[2]), c(xm_p), c(z_p), c(zlp_p))
 
+    def forward_loss(self, x, mask, mask_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False, alpha_annealing=True,
+                     stage="train", llh_eval=False):
+        """forward, then loss, wired as the reference's drivers wire them: the flows take neither
+        epoch nor beta from the schedule."""
+        if self.regularised:  # train.py:53-55, 77-81; evaluate.py:172-173, 189-195
+            o = self.forward(x, mask, mask_p)
+            return o, self.loss(x, o[6], o[7], o[4], o[5], o[2], o[3], o[0], o[1], mask, mask_p, alpha, llh_eval=llh_eval,
+                                stage=stage)
+        o = self.forward(x, mask)  # train.py:82-85; evaluate.py:196-200
+        return o, self.loss(x, o[2], o[3], o[0], o[1], mask, llh_eval=llh_eval)
+
     @staticmethod
     def neg_gaussian_log_likelihood(targets, mean, log_var):  # VAE.py:1987-1989 (elementwise; not on the hot path)
         return -torch.distributions.Normal(mean, torch.exp(log_var / 2.)).log_prob(targets)
@@ -299,7 +310,7 @@ class VAEFlow(_FlowBase):
 
 class REG_VAEFlow(_FlowBase):
     """Posterior-consistency regularised VAEFlow.  Reference: src/models/VAE.py:1999-2124."""
-    regularised = True
+    regularised, X_MEAN_Q = True, 6
 
     def forward(self, data, mask, mask_p):
         # VAE.py:2118-2124: both encoders first (RNG order q, p), p outputs returned first
@@ -384,6 +395,9 @@ class FlowTrainer(_FlatAdamTrainer):
         self._sl = dict(xm=pq(self.Y), z=pq(self.z), zlp=pq(self.zlp),
                         g=(*pq(self.G), *pq(self.gz), *pq(self.gzlp)))
         self._B, self._v = B, v
+
+    def train_step(self, x, mask, *, alpha, p_missingness, stage, **schedule):
+        return self.step(x, mask, alpha=alpha, p_missingness=p_missingness, stage=stage)
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, beta=1.0, p_missingness=30, stage="train"):
         """One optimiser step.  mask_p [B,d] (REG_VAEFlow) and eps [P,B,10] (the q pass, then the p pass) may be

@@ -11,9 +11,14 @@
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
 The families model_loader builds are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI (and, for
-data_type == 'mnist', Reg_EDDI_mnist / vanilla_EDDI_mnist), REG_notMIWAE_v2, notMIWAE_myversion and MIWAE / Reg_MIWAE.  The flow models (VAEFlow / REG_VAEFlow, flow.py) are reached
-through their classes and the `model=` keyword of train() and eval_vae() (which then take the reference's flow branches,
-train.py:77-86 and evaluate.py:189-200); model_loader itself still raises NotImplementedError for flow vae_types.
+data_type == 'mnist', Reg_EDDI_mnist / vanilla_EDDI_mnist), REG_notMIWAE_v2, notMIWAE_myversion and MIWAE / Reg_MIWAE.  The flow
+models (VAEFlow / REG_VAEFlow, flow.py) are reached through their classes and the `model=` keyword of train() and eval_vae();
+model_loader itself still raises NotImplementedError for flow vae_types.
+
+The loops ask the model, not vae_type: trainer_class_for(model) picks the step trainer by class,
+model.regularised says whether a mask_p is drawn (draw_mask_p), model.forward_loss is the reference's forward -> loss call
+for that family and model.X_MEAN_Q the reconstruction mean in forward's tuple.  vae_type decides file names, the 'with_drop'
+data treatment and whether the loader comes alone (MNAR) or as a pair.
 """
 from __future__ import annotations
 
@@ -23,13 +28,15 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .ensemble import EnsembleTrainer, stackable
 from .fused import FusedTrainer
-from .models import Reg_VAE, Reg_VAE_mask, vanilla_VAE, vanilla_VAE_mask
-from .notmiwae import NMTrainer, REG_notMIWAE_v2, notMIWAE_myversion
-from .eddi import EDDITrainer, Reg_EDDI, vanilla_EDDI
+from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
+from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
+from .eddi import EDDITrainer, Reg_EDDI, _EDDIBase, vanilla_EDDI
 from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _EDDIMnistBase
-from .miwae import MIWAE, MIWTrainer, Reg_MIWAE
+from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase
 from .flow import FlowTrainer, _FlowBase
+from .wide import WideTrainer
 
 _seed_counter = [0]
 
@@ -112,6 +119,49 @@ def model_loader(stage, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type
     return model
 
 
+def trainer_class_for(model):
+    """The step trainer of a model, decided on its class (and, for the dense classes, on `_wide`): image-width EDDI first
+    (train.py:31-47), then the generic-GEMM step of an encoder input > 128 columns (wide.py), then the families."""
+    if isinstance(model, _EDDIMnistBase):
+        return EDDIMnistTrainer
+    if getattr(model, "_wide", False):
+        return WideTrainer
+    for base, cls in ((_FlowBase, FlowTrainer), (_MIWBase, MIWTrainer), (_NMBase, NMTrainer), (_EDDIBase, EDDITrainer),
+                      (_VAEBase, FusedTrainer)):
+        if isinstance(model, base):
+            return cls
+    raise TypeError(f"no step trainer for {type(model).__name__}")
+
+
+def draw_mask_p(model, shape, mask, p_missingness, device):
+    """mask_p = create_missing_uci(shape, p) * mask (train.py:53-56; evaluate.py:172-173), as float for the MNAR classes."""
+    mask_p = create_missing_uci(shape, p_missingness, device=device) * mask
+    return mask_p.float() if isinstance(model, _NMBase) else mask_p
+
+
+def _rmse_unobserved(x_mean, x, mask):
+    """RMSE of x_mean against x over the entries with mask == 0 (bool or float 0 / 1 mask)."""
+    inv = ~mask if mask.dtype == torch.bool else (mask == 0)
+    return torch.sqrt(torch.sum(torch.square(x_mean * inv - x * inv)) / torch.sum(inv))
+
+
+def _save(obj, path):
+    os.makedirs(os.path.dirname(path), exist_ok=True)  # the reference never creates it (SURVEY App. B 13)
+    torch.save(obj, path)
+
+
+def _save_checkpoint(model, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
+    _save({k: v.detach().cpu() for k, v in model.state_dict().items()},
+          checkpoint_path(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type))
+
+
+def _model_for_eval(model, device, *loader_args, **loader_kw):
+    """`model` if given, else the checkpoint that model_loader('test', ...) reloads; on `device`."""
+    if model is None:
+        model = model_loader("test", *loader_args, **loader_kw)
+    return model.to(device)
+
+
 def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
           experiment_type, vae_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), alpha=1.0,
           stage="train", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True,
@@ -120,95 +170,37 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
     passed as `model` (train.py:77-86; model_loader does not build flows).  With fused=True every batch is one trainer
     step (no per-step host sync: the epoch total is read once per epoch, as the reference only prints it per epoch);
     with fused=False it is the reference's own sequence model.forward -> model.loss -> backward -> optim.Adam
-    on the API path.  `model` (optional): train this model instead of a fresh one from model_loader.  Returns the
-    trained model."""
+    on the API path (model.forward_loss).  `model` (optional): train this model instead of a fresh one from model_loader;
+    its class, not vae_type, picks the trainer and the forward -> loss wiring.  Returns the trained model."""
     if model is None:
         model = model_loader("train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
                              max_epochs, train_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
                              p_missingness=p_missingness)
     model.to(device)
-    nm = "notMIWAE" in vae_type
-    loader = data_loader_train if nm else data_loader_train[0]  # train.py:22-25
-    is_reg = "reg" in vae_type
-    eddi = "EDDI" in vae_type
-    miw = isinstance(model, (MIWAE, Reg_MIWAE))
-    flow = isinstance(model, _FlowBase)
+    loader = data_loader_train if "notMIWAE" in vae_type else data_loader_train[0]  # train.py:22-25
     # 'with_drop' variants (train.py:32-37, 50-51; vanilla classes only - the reference's regularised branch never draws mask_p
     # beside it): the model sees mask * mask_drop, the keep-mask of create_missing_uci_drop_eddi (utils.py:42-45)
-    drop = "with_drop" in vae_type and not is_reg
+    drop = "with_drop" in vae_type and not model.regularised
     if fused:
-        if isinstance(model, _EDDIMnistBase):  # data_type == 'mnist' (train.py:31-47): the image-width point-net step
-            trainer = EDDIMnistTrainer(model, lr=0.001, seed=seed)
-        elif getattr(model, "_wide", False):  # encoder input > 128 columns: the generic-GEMM step (wide.py)
-            from .wide import WideTrainer
-            trainer = WideTrainer(model, lr=0.001, seed=seed)
-        else:
-            trainer = (FlowTrainer if flow else MIWTrainer if miw else NMTrainer if nm else EDDITrainer if eddi else
-                       FusedTrainer)(model, lr=0.001, seed=seed)
+        trainer = trainer_class_for(model)(model, lr=0.001, seed=seed)
+        train_step = trainer.train_step  # (bound once: the loop is host-paced at the reference's batch)
     else:
         model.flatten_parameters()
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001)  # train.py:21
     for i in range(max_epochs):
-        total_loss = 0.0
+        total_loss, epoch = 0.0, i + 1
         for data_sample, mask in loader:
-            data_sample = data_sample.to(device)
-            mask = mask.to(device)
-            if fused and drop:  # the fused vanilla step on the thinned mask (one more elementwise launch, no host sync)
+            data_sample, mask = data_sample.to(device), mask.to(device)
+            if drop:  # the step on the thinned mask (one more elementwise launch, no host sync)
                 mask = mask.to(torch.float32) * create_missing_uci_drop_eddi(data_sample.shape, device=device)
-            if fused and flow:
-                trainer.step(data_sample, mask, alpha=alpha, p_missingness=p_missingness, stage=stage)
-                continue
-            if fused and (nm or miw):
-                trainer.step(data_sample, mask, alpha=alpha, p_missingness=p_missingness)
-                continue
-            if flow:
-                if model.regularised:  # train.py:53-55, 77-81
-                    mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
-                    o = model.forward(data_sample, mask, mask_p)
-                    _, train_loss = model.loss(data_sample, o[6], o[7], o[4], o[5], o[2], o[3], o[0], o[1], mask,
-                                               mask_p, alpha, stage=stage)
-                else:  # train.py:82-85
-                    o = model.forward(data_sample, mask)
-                    _, train_loss = model.loss(data_sample, o[2], o[3], o[0], o[1], mask)
-                optimizer.zero_grad()
-                train_loss.backward()
-                optimizer.step()
-                total_loss += train_loss.item()
-                continue
-            if miw:
-                if is_reg:  # train.py:53-55, 102-108
-                    mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
-                    o = model.forward(data_sample, mask, mask_p)
-                    _, train_loss = model.loss(data_sample, o[2], o[3], o[4], o[0], o[1], o[7], o[8], o[9], o[5], o[6],
-                                               mask, mask_p, i + 1, beta_annealing=beta_annealing, beta=beta, alpha=alpha)
-                else:  # train.py:109-113
-                    o = model.forward(data_sample, mask)
-                    _, train_loss = model.loss(data_sample, o[2], o[3], o[4], o[0], o[1], mask, i + 1)
-                optimizer.zero_grad()
-                train_loss.backward()
-                optimizer.step()
-                total_loss += train_loss.item()
-                continue
             if fused:
-                trainer.step(data_sample, mask, epoch=i + 1, alpha=alpha, beta=beta, beta_annealing=beta_annealing,
-                             p_missingness=p_missingness)
+                train_step(data_sample, mask, epoch=epoch, alpha=alpha, beta=beta, beta_annealing=beta_annealing,
+                           p_missingness=p_missingness, stage=stage)
                 continue
-            if is_reg:  # train.py:53-56, 87-94
-                mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
-                if nm:
-                    mask_p = mask_p.float()
-                o = model.forward(data_sample, mask, mask_p, stage=stage)
-                _, train_loss = model.loss(data_sample, o[2], o[3], o[0], o[1], o[6], o[7], o[4], o[5], mask, mask_p,
-                                           i + 1, beta_annealing=beta_annealing, beta=beta, alpha=alpha,
-                                           alpha_annealing=alpha_annealing, stage=stage)
-            else:  # train.py:50-51, 58, 95-101
-                if drop:
-                    mask_drop = create_missing_uci_drop_eddi(data_sample.shape, device=device)
-                else:
-                    mask_drop = torch.ones(data_sample.shape, device=device)
-                o = model.forward(data_sample, mask * mask_drop)
-                _, train_loss = model.loss(data_sample, o[2], o[3], o[0], o[1], i + 1, mask * mask_drop,
-                                           beta_annealing=beta_annealing, beta=beta, stage=stage)
+            mask_p = draw_mask_p(model, data_sample.shape, mask, p_missingness, device) if model.regularised else None
+            _, (_, train_loss) = model.forward_loss(data_sample, mask, mask_p, epoch=epoch, alpha=alpha, beta=beta,
+                                                    beta_annealing=beta_annealing, alpha_annealing=alpha_annealing,
+                                                    stage=stage)
             optimizer.zero_grad()
             train_loss.backward()
             optimizer.step()
@@ -218,17 +210,9 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
         if verbose:
             print("Epoch: [{}/{}], Total Loss: {}".format(i, max_epochs, total_loss))
     if save:
-        path = checkpoint_path(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
-        os.makedirs(os.path.dirname(path), exist_ok=True)  # the reference never creates it
-        torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
+        _save_checkpoint(model, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
     print("Training is over!")
     return model
-
-
-def _save_checkpoint(model, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
-    path = checkpoint_path(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
-    os.makedirs(os.path.dirname(path), exist_ok=True)  # the reference never creates it
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
 
 
 def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
@@ -244,8 +228,6 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
     (a mixed list is split into such groups); every other family, and batches beyond the small-batch step, go through train()
     one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints the
     reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
-    from .ensemble import EnsembleTrainer
-
     cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
     G = len(cfgs)
     if models is not None and len(models) != G:
@@ -262,7 +244,7 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
             num_estimates, experiment_type, reg_type, vt, alpha=c["alpha"], p_missingness=c["p_missingness"])
         m.to(device)
         out[g] = m
-        small = type(m) in (Reg_VAE, vanilla_VAE) and not getattr(m, "_wide", False) and "with_drop" not in vt
+        small = stackable(m) and "with_drop" not in vt
         if small:  # the batch must fit the small-batch step (larger ones fill the chip on their own)
             first = next(iter(member_loader(g)[0]), None)
             small = first is not None and first[0].reshape(-1, obs_dim).shape[0] <= ops.step_small_max_rows()
@@ -338,50 +320,21 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
     {loader_stage: dict(rmse, elbo, negll, negll_imp)} and (save=True) writes the reference's four files."""
     out = {}
     with torch.no_grad():
-        if model is None:
-            model = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
-                                 p_missingness=p_missingness)
-        model.to(device)
-        opt_epoch = max_epochs
-        is_reg = "reg_vae" in vae_type or "reg_EDDI" in vae_type
+        model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                                max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                                p_missingness=p_missingness)
         for loader, loader_stage in list_loaders:
             recon, res, res_negll, res_negll_imp = [], [], [], []
             for _ in range(M):
                 elbos, negls, negls_imp, temp_recon = [], [], [], []
                 for data_sample, mask in loader:
                     data_sample, mask = data_sample.to(device), mask.to(device)
-                    if isinstance(model, _FlowBase):  # evaluate.py:172-173, 189-200
-                        if model.regularised:
-                            mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
-                            o = model.forward(data_sample, mask, mask_p)
-                            _, train_loss, negl, negl_imp = model.loss(data_sample, o[6], o[7], o[4], o[5], o[2], o[3],
-                                                                       o[0], o[1], mask, mask_p, alpha, llh_eval=True,
-                                                                       stage=stage)
-                            x_mean = o[6]
-                        else:
-                            o = model.forward(data_sample, mask)
-                            _, train_loss, negl, negl_imp = model.loss(data_sample, o[2], o[3], o[0], o[1], mask,
-                                                                       llh_eval=True)
-                            x_mean = o[2]
-                    elif is_reg:  # evaluate.py:172-173, 210-216
-                        mask_p = create_missing_uci(data_sample.shape, p_missingness, device=device) * mask
-                        o = model.forward(data_sample, mask, mask_p, stage=stage)
-                        _, train_loss, negl, negl_imp = model.loss(
-                            data_sample, o[2], o[3], o[0], o[1], o[6], o[7], o[4], o[5], mask, mask_p, opt_epoch,
-                            llh_eval=True, beta_annealing=beta_annealing, beta=beta, alpha=alpha,
-                            alpha_annealing=alpha_annealing, stage=stage)
-                        x_mean = o[6]
-                    else:  # evaluate.py:219-227
-                        o = model.forward(data_sample, mask)
-                        _, train_loss, negl, negl_imp = model.loss(data_sample, o[2], o[3], o[0], o[1], opt_epoch, mask,
-                                                                   llh_eval=True, beta_annealing=beta_annealing,
-                                                                   beta=beta, stage=stage)
-                        x_mean = o[2]
-                    mask = mask.reshape(-1, obs_dim)
-                    inv = ~mask if mask.dtype == torch.bool else (mask == 0)
-                    temp_recon.append(torch.sqrt(torch.sum(torch.square(
-                        torch.squeeze(x_mean) * inv - data_sample.view(-1, obs_dim) * inv)) / torch.sum(inv)))
+                    mask_p = draw_mask_p(model, data_sample.shape, mask, p_missingness, device) if model.regularised else None
+                    o, (_, train_loss, negl, negl_imp) = model.forward_loss(
+                        data_sample, mask, mask_p, epoch=max_epochs, alpha=alpha, beta=beta, beta_annealing=beta_annealing,
+                        alpha_annealing=alpha_annealing, stage=stage, llh_eval=True)
+                    temp_recon.append(_rmse_unobserved(torch.squeeze(o[model.X_MEAN_Q]), data_sample.view(-1, obs_dim),
+                                                       mask.reshape(-1, obs_dim)))
                     elbos.append(train_loss)
                     negls.append(torch.as_tensor(negl, device=device, dtype=torch.float32))
                     negls_imp.append(torch.as_tensor(negl_imp, device=device, dtype=torch.float32))
@@ -396,8 +349,7 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
                 paths = result_paths(experiment_type, data_type, vae_type, loader_stage, missing_rate, alpha,
                                      p_missingness, reg_type)
                 for k, pth in paths.items():
-                    os.makedirs(os.path.dirname(pth), exist_ok=True)
-                    torch.save(out[loader_stage][k], pth)
+                    _save(out[loader_stage][k], pth)
     return out
 
 
@@ -421,12 +373,9 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
     sequence, one mask_p draw per repetition - the same estimator, row-independent, so the result has the same
     distribution.  Returns the RMSE (0-dim CPU tensor) and, with save=True, writes the reference's result file."""
     with torch.no_grad():
-        if model is None:
-            model = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
-                                 p_missingness=p_missingness, not_miwae_type=not_miwae_type)
-        model.to(device)
-        is_reg = "reg_notMIWAE" in vae_type
+        model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                                max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                                p_missingness=p_missingness, not_miwae_type=not_miwae_type)
         data_test = data_test.to(device).float().reshape(-1, obs_dim)
         mask_test = mask_test.to(device).float().reshape(-1, obs_dim)
         N = data_test.shape[0]
@@ -434,26 +383,17 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
         temp_recon = []
         for _ in range(M):
             XM = torch.zeros_like(data_test)
-            mask_p = create_missing_uci(data_test.shape, p_missingness, device=device).float() * mask_test
+            mask_p = draw_mask_p(model, data_test.shape, mask_test, p_missingness, device)  # (for both classes: evaluate.py:30-31)
             for lo in range(0, N, rows):
-                x, m, mp = data_test[lo:lo + rows], mask_test[lo:lo + rows], mask_p[lo:lo + rows]
-                if is_reg:
-                    o = model.forward(x, m, mp, stage=stage)
-                    xm, _, _ = model.loss(x, o[2], o[3], o[0], o[1], o[6], o[7], o[4], o[5], m, mp, max_epochs,
-                                          llh_eval=True, beta_annealing=beta_annealing, beta=beta, alpha=alpha,
-                                          alpha_annealing=alpha_annealing, stage=stage)
-                else:
-                    o = model.forward(x, m)
-                    xm, _, _ = model.loss(x, o[2], o[3], o[0], o[1], max_epochs, m, llh_eval=True,
-                                          beta_annealing=beta_annealing, beta=beta, stage=stage)
+                _, (xm, _, _) = model.forward_loss(
+                    data_test[lo:lo + rows], mask_test[lo:lo + rows], mask_p[lo:lo + rows] if model.regularised else None,
+                    epoch=max_epochs, alpha=alpha, beta=beta, beta_annealing=beta_annealing, alpha_annealing=alpha_annealing,
+                    stage=stage, llh_eval=True)
                 XM[lo:lo + rows] = xm
-            inv = 1 - mask_test
-            temp_recon.append(torch.sqrt(torch.sum(torch.square(XM * inv - data_test * inv)) / torch.sum(inv)))
+            temp_recon.append(_rmse_unobserved(XM, data_test, mask_test))
         recon = torch.stack(temp_recon).mean().cpu()
         if save:
-            pth = mnar_result_path(experiment_type, data_type, vae_type, alpha, p_missingness, reg_type, not_miwae_type)
-            os.makedirs(os.path.dirname(pth), exist_ok=True)
-            torch.save(recon, pth)
+            _save(recon, mnar_result_path(experiment_type, data_type, vae_type, alpha, p_missingness, reg_type, not_miwae_type))
     return recon
 
 
@@ -477,12 +417,9 @@ def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
     CPU tensors) and, with save=True, writes the reference's result files (miwae_result_path)."""
     out = {}
     with torch.no_grad():
-        if model is None:
-            model = model_loader("test", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
-                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
-                                 p_missingness=p_missingness)
-        model.to(device)
-        is_reg = "reg_MIWAE" in vae_type
+        model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                                max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
+                                p_missingness=p_missingness)
         rows = max(1, max_decoder_rows // max(1, valid_k))
         for loader, loader_stage in list_loaders:
             recon = []
@@ -491,18 +428,15 @@ def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
                 for data_sample, mask in loader:
                     x = data_sample.to(device).float().reshape(-1, obs_dim)
                     mask = mask.to(device).reshape(-1, obs_dim)
-                    mp = create_missing_uci(x.shape, p_missingness, device=device) * mask if is_reg else None
+                    mp = draw_mask_p(model, x.shape, mask, p_missingness, device) if model.regularised else None
                     xm = torch.empty_like(x)
                     for lo in range(0, x.shape[0], rows):
                         xm[lo:lo + rows] = model.impute(x[lo:lo + rows], mask[lo:lo + rows],
                                                         None if mp is None else mp[lo:lo + rows], num_samples=valid_k)
-                    inv = ~mask if mask.dtype == torch.bool else (mask == 0)
-                    XM.append(torch.sqrt(torch.sum(torch.square(xm * inv - x * inv)) / torch.sum(inv)))
+                    XM.append(_rmse_unobserved(xm, x, mask))
                 recon.append(torch.stack(XM).mean())
             out[loader_stage] = torch.stack(recon).mean().cpu()
             if save:
-                pth = miwae_result_path(experiment_type, data_type, vae_type, loader_stage, alpha, p_missingness,
-                                        reg_type)
-                os.makedirs(os.path.dirname(pth), exist_ok=True)
-                torch.save(out[loader_stage], pth)
+                _save(out[loader_stage], miwae_result_path(experiment_type, data_type, vae_type, loader_stage, alpha,
+                                                           p_missingness, reg_type))
     return out

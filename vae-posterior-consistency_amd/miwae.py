@@ -293,6 +293,17 @@ class _MIWBase(FlatParams, nn.Module):
             ep = _f32c(eps[1])
         return MIWLossFn.apply(cfg, xf, mf, mpf, Yq, hq, _f32c(eps[0]), Yp, hp, ep)
 
+    def forward_loss(self, x, mask, mask_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False, alpha_annealing=True,
+                     stage="train", llh_eval=False):
+        """forward, then loss, wired as the reference's drivers wire them.  With llh_eval the
+        imputation is loss's first return (evaluate.py:97-112): no X_MEAN_Q here."""
+        if self.regularised:  # train.py:53-55, 102-108
+            o = self.forward(x, mask, mask_p)
+            return o, self.loss(x, o[2], o[3], o[4], o[0], o[1], o[7], o[8], o[9], o[5], o[6], mask, mask_p, epoch,
+                                llh_eval=llh_eval, beta_annealing=beta_annealing, beta=beta, alpha=alpha)
+        o = self.forward(x, mask)  # train.py:109-113 (evaluate.py:108-112 adds beta_annealing / beta, which MIWAE.loss ignores)
+        return o, self.loss(x, o[2], o[3], o[4], o[0], o[1], mask, epoch, llh_eval=llh_eval)
+
     @torch.no_grad()
     def impute(self, x, mask, mask_p=None, num_samples=None, pairing=PAIR_PER_ROW):
         """llh_eval imputation of every row of x with num_samples draws, rows independent (per-row pairing): what
@@ -413,6 +424,9 @@ class MIWTrainer(_FlatAdamTrainer):
                         hp=self.hact[B:] if self.reg else None, ghp=self.gh[B:] if self.reg else None,
                         eq=self.eps[P], ep=self.eps[P + 1] if self.reg else None, es=self.eps[:P])
         self._B, self._v = B, v
+
+    def train_step(self, x, mask, *, alpha, p_missingness, **schedule):
+        return self.step(x, mask, alpha=alpha, p_missingness=p_missingness)
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30):
         """One optimiser step.  mask_p [B,d] and eps ([4,B,S,L] = forward q, forward p, loss q, loss p for Reg_MIWAE;

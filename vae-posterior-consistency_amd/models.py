@@ -185,6 +185,7 @@ class _VAEBase(FlatParams, nn.Module):
 
 class Reg_VAE(_VAEBase):
     """Reg VAE (posterior-consistency regulariser).  Reference: src/models/VAE.py:350-507."""
+    regularised, X_MEAN_Q = True, 6  # forward takes mask_p; index of the q pass's reconstruction mean in forward's tuple
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, reg_type, num_samples=1,
                  num_estimates=1):
@@ -246,9 +247,20 @@ class Reg_VAE(_VAEBase):
                                       logvar_q.contiguous(), mean_p.contiguous(), logvar_p.contiguous(), eps_ml)
         return self._finish(loss, sums, B, d, llh_eval, MI, stage, mean_q, logvar_q)
 
+    def forward_loss(self, x, mask, mask_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False, alpha_annealing=True,
+                     stage="train", llh_eval=False):
+        """forward, then loss, wired as the reference's drivers wire them for this family (train.py:53-56, 87-94;
+        evaluate.py:172-173, 210-216) -> (forward's tuple, loss's return).  Every family has one (DESIGN.md section 2.21);
+        the keyword defaults are train()'s."""
+        o = self.forward(x, mask, mask_p, stage=stage)
+        return o, self.loss(x, o[2], o[3], o[0], o[1], o[6], o[7], o[4], o[5], mask, mask_p, epoch, llh_eval=llh_eval,
+                            beta_annealing=beta_annealing, beta=beta, alpha=alpha, alpha_annealing=alpha_annealing,
+                            stage=stage)
+
 
 class vanilla_VAE(_VAEBase):
     """vanilla_VAE.  Reference: src/models/VAE.py:1119-1240."""
+    regularised, X_MEAN_Q = False, 2
 
     def forward(self, data, mask):
         z_q, mean_q, logvar_q = self.encoder(data, mask)
@@ -267,6 +279,13 @@ class vanilla_VAE(_VAEBase):
         loss, sums = LossFn.apply(cfg, ops._f32c(x), x_recon_q.contiguous(), None, mean_q.contiguous(),
                                   logvar_q.contiguous(), None, None, None)
         return self._finish(loss, sums, B, d, llh_eval, MI, stage, mean_q, logvar_q)
+
+    def forward_loss(self, x, mask, mask_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False, alpha_annealing=True,
+                     stage="train", llh_eval=False):
+        """Reg_VAE.forward_loss for the one-pass classes (train.py:95-101; evaluate.py:219-227): no mask_p, no alpha."""
+        o = self.forward(x, mask)
+        return o, self.loss(x, o[2], o[3], o[0], o[1], epoch, mask, llh_eval=llh_eval, beta_annealing=beta_annealing,
+                            beta=beta, stage=stage)
 
 
 class Reg_VAE_mask(Reg_VAE):

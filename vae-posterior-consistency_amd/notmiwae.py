@@ -24,6 +24,7 @@ from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chai
                      wgrad_now_keys)
 from .linear import ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad, wgrad_reduce  # noqa: F401  (the GEMM ops were first
 # reached as vpc_amd.notmiwae.linear_*: the names stay importable from here; they are defined in linear.py only)
+from .models import Reg_VAE, vanilla_VAE
 from .ops import PRECISIONS, fill_normal, step_pack_weights_bf16
 from .trainer import _FlatAdamTrainer
 
@@ -379,6 +380,12 @@ class _NMBase(FlatParams, nn.Module):
             return imp, loss, out8[5].float()
         return loss, loss  # (print_loss, train_loss)
 
+    def forward_loss(self, x, mask, mask_p=None, **schedule):
+        """forward, then loss, in the order and with the keywords of the dense classes: the reference's drivers call the MNAR
+        pair through the same branches (train.py:87-101; evaluate.py:33-50).  With llh_eval the imputation is loss's first
+        return, so there is no X_MEAN_Q here."""
+        return (Reg_VAE if self.regularised else vanilla_VAE).forward_loss(self, x, mask, mask_p, **schedule)
+
 
 class REG_notMIWAE_v2(_NMBase):
     """Posterior-consistency regularised not-MIWAE.  Reference: src/models/VAE.py:2327-2505."""
@@ -518,6 +525,9 @@ class NMTrainer(_FlatAdamTrainer):
             self.ne_part = e(nblk.value * int(self._nd_tables[3].numel()))  # the encoder-backward kernel's blocks (fused tail)
             self.nd_stat = torch.empty(nblk.value * 5, dtype=torch.float64, device=dev)
         self._B, self._v = B, v
+
+    def train_step(self, x, mask, *, alpha, p_missingness, **schedule):
+        return self.step(x, mask, alpha=alpha, p_missingness=p_missingness)
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30, global_batch=None, row_lo=None,
              _state=None):

@@ -83,6 +83,12 @@ class _FlatAdamTrainer:
     def coefficients(self, epoch, alpha, beta, beta_annealing):
         return loss_coefficients(self.model, epoch, alpha, beta, beta_annealing)
 
+    def train_step(self, x, mask, *, epoch, alpha, beta, beta_annealing, p_missingness, stage):
+        """One batch of harness.train's fused loop: step() with what this trainer's step takes from the schedule (here all
+        but stage; NMTrainer, MIWTrainer and FlowTrainer take less)."""
+        return self.step(x, mask, epoch=epoch, alpha=alpha, beta=beta, beta_annealing=beta_annealing,
+                         p_missingness=p_missingness)
+
     def _batch_rows(self, B, global_batch=None, row_lo=None):
         """(rows of the global batch, global index of this rank's first row): by default B * world_size rows of which this
         rank holds [rank * B, (rank + 1) * B)."""

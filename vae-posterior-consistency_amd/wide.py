@@ -121,7 +121,7 @@ class WideTrainer(_FlatAdamTrainer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
         super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
         self.loss = self.tail
-        self.vanilla = not hasattr(model, "reg_type")
+        self.vanilla = not model.regularised
 
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, *, epoch=1, alpha=1.0, beta=1.0, beta_annealing=False,
              p_missingness=30, global_batch=None, row_lo=None):
