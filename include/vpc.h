@@ -537,6 +537,45 @@ int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_parti
                                float* params, float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, long step,
                                const int* pack_idx, float* img, void* stream);
 
+/* ---- ensemble evaluation: the evaluate stage of G members over a list of batches and M Monte-Carlo passes in one pair of launches
+ * (csrc/vpc_evalsmall.hip).  Replaces the loop body of eval_vae, src/experiment_main/evaluate.py:136-297, for Reg_VAE / vanilla_VAE:
+ * model.forward (src/models/VAE.py:496-507, :1153-1169), model.loss(llh_eval=True, stage='evaluate') (VAE.py:410-420: the q pass
+ * only - mask_p, alpha and the p pass reach no output) and the RMSE on ~mask (evaluate.py:229-234).
+ *
+ * Tables (device-resident, long long):
+ *   tiles   [n_tiles][4]    data row of the tile's first row | valid rows 1..16 | draw row of its first row | batch index.  A tile
+ *                           lies inside ONE batch.  Data row and draw row are separate: M passes over an unshuffled data set read
+ *                           the same x rows with M different eps, without an M-fold copy.  0 <= data row, data row + valid <= N;
+ *                           0 <= draw row, draw row + valid <= R (an entry outside these reads nothing and counts as zero).
+ *   batches [n_batches][4]  rows in the batch | MC pass index | first tile | tiles (a batch's tiles are consecutive)
+ *   passes  [M][2]          first batch | batches (a pass's batches are consecutive)
+ * eps: draw == 0: planes [G or 1][R][16] of normals (row r = draw row r, columns >= L ignored); draw != 0: drawn in registers,
+ * no buffer: the eps of draw row r, columns 4 q .. 4 q + 3, under member g is what vpc_fill_normal writes at float index 16 r + 4 q
+ * of a flat [R x 16] array with seed members[g].seed and this call's `offset` (one Philox counter per group: the call consumes 4 R).
+ * Members: the VpcMember table of the ensemble step (seed; co.bq = the member's KL weight); pointers are member 0's, member g's slice
+ * g * strides[k] ELEMENTS further (VPC_MS_X, VPC_MS_MASK, VPC_MS_EPS: 0 = shared by all members; VPC_MS_IMG; VPC_MS_LOSS = the
+ * records, in doubles).  d = row pitch of x and mask (multiple of 4: the host pads), d_real <= d the model's obs_dim: columns
+ * [d_real, d) are padding and enter neither the sums on mask (zero mask bytes) nor the sums on its complement.
+ *
+ * vpc_eval_small_multi_f32: one record of VPC_EVAL_TERMS doubles per (member, tile), with t = (x_hat - x)^2 / (2 sigma^2) +
+ * x_logvar / 2:  sum mask t | sum (1 - mask) t | sum (1 - mask)(x_hat - x)^2 | sum (1 - mask) | sum over rows of KL(q || N(0, I)).
+ * A pure function of its inputs (no atomics).  One launch holds at most max_blocks workgroups (0: VPC_EVAL_MAX_BLOCKS); the entry
+ * walks the tile table in chunks (a lower max_blocks gives the same records: it lets a small case walk the chunk loop).  Limits as the ensemble step: fp32, plain encoder, d % 4 == 0, d <= 128, L <= 15, G <= 65535;
+ * VPC_ERR_ARG / VPC_ERR_SHAPE outside them (d_real > d and misaligned pointers included), never a fault. */
+#define VPC_EVAL_TERMS 5
+#define VPC_EVAL_MAX_BLOCKS 65536
+int vpc_eval_small_multi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                             const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                             unsigned long long offset, float x_logvar, double* part, const long* strides, int d, int d_real,
+                             int L, int max_blocks, void* stream);
+/* The records -> out[G][4] = (rmse, elbo, negll, negll_imp), blockIdx.y = member, fp64, fixed summation order.  Per batch of n_b
+ * rows: negll = (S_A + n_b d_real log(2 pi) / 2) / n_b and negll_imp likewise from S_I (masked entries contribute the constant,
+ * as _finish / VAE.py:414-419), elbo = negll + co.bq KL / n_b, rmse = sqrt(SQ / CNT) - 0 / 0 = NaN for a batch without an
+ * unobserved entry, as evaluate.py:232-234.  Then the mean over the batches of a pass and the mean over the passes
+ * (evaluate.py:238-245). */
+int vpc_eval_reduce_multi(const double* part, const long long* batches, long n_batches, const long long* passes, int M,
+                          const VpcMember* members, int G, long part_stride, long n_tiles, int d_real, float* out, void* stream);
+
 /* ---- MIWAE path: MIWAE / Reg_MIWAE (csrc/vpc_miw.hip) ------------------------------------------------------------
  * Reference: src/models/VAE.py:3011-3134 and :3137-3301.  Encoder d->128->128 ReLU -> [mean L | raw L] and decoder
  * L->128->128 ReLU -> [mean d | scale d | df d] run on vpc_linear_fwd / dgrad / wgrad (ACT_RELU, last layer ACT_NONE);

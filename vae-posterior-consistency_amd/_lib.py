@@ -62,6 +62,8 @@ _PROTOS = {
                                 L_, L_, I, P],
     "vpc_step_small_multi_f32": [P, P, P, P, P, P, P, I, I, I, I, ULL, ULL, F, F, P, P, P, C.POINTER(L_), L_, I, I, I, P],
     "vpc_reduce_step_adam_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P],
+    "vpc_eval_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],
+    "vpc_eval_reduce_multi": [P, P, L_, P, I, P, I, L_, L_, I, P, P],
     "vpc_step_fused_applicable": [L_, I, I, I],
     "vpc_step_layout_bf16": [I, I, IP, IP],
     "vpc_step_build_indices_bf16": [I, I, P, P],

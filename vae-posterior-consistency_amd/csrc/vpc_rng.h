@@ -84,6 +84,19 @@ __device__ __forceinline__ void fill_normal_body(float* __restrict__ out, long n
     for (int j = 0; j < 4 && i0 + j < n; ++j) out[i0 + j] = v[j];
 }
 
+// The four normals of ONE group of the eps stream, in registers: exactly the values fill_normal_body stores for the group whose
+// counter (eps_counter + offset) is `ctr` - same Philox call, same Box-Muller form.  (vpc_evalsmall.hip: the lane that forms
+// z[row][4 q .. 4 q + 3] draws its own eps; nothing is written to memory.)
+__device__ __forceinline__ f32x4 eps_normal4(uint64_t ctr, uint64_t seed) {
+    const U4 r = philox(ctr, 1u, seed);
+    const float r0 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.x)));
+    const float r1 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(r.z)));
+    const float t0 = u01(r.y), t1 = u01(r.w);
+    const float s0 = __builtin_amdgcn_sinf(t0), c0 = __builtin_amdgcn_cosf(t0);
+    const float s1 = __builtin_amdgcn_sinf(t1), c1 = __builtin_amdgcn_cosf(t1);
+    return f32x4{r0 * c0, r0 * s0, r1 * c1, r1 * s1};
+}
+
 // ---- the draws of the AIS engines (vpc_ais.hip: the persistent kernel; vpc_aisg.hip: the GEMM-backed one; ais_draws_kernel)
 constexpr uint32_t AIS_KIND_Z0 = 2u, AIS_KIND_V = 3u, AIS_KIND_U = 4u;  // Philox streams (0 / 1: the training-step draws)
 constexpr int AIS_DRAW_MAX_L = 64;

@@ -20,13 +20,12 @@
 // partial blocks are what vpc_reduce_step(_adam) expects).
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
+#include "vpc_small_device.h"
 #include "vpc_rng.h"
 #include "vpc_dec_args.h"
 
 namespace vpc {
 
-constexpr int SP = 144;             // row pitch of the LDS activation buffers (dwords)
-constexpr int SBUF = 16 * SP;       // one buffer: 16 rows
 enum { B_XQ = 0, B_XP, B_H1Q, B_H1P, B_H2Q, B_H2P, B_ML, B_Z, B_G1, B_G2, B_DP, B_DG2, B_DG1, B_DMLQ, B_DMLP, B_DH2, B_DH1, B_COUNT };
 constexpr int SMALL_LDS = (B_COUNT * SBUF + WAVES * LOSS_TERMS) * 4;
 static_assert(SMALL_LDS <= 163840, "LDS budget");
@@ -58,50 +57,10 @@ struct SmallArgs {
     EpsShard shard;
 };
 
-// C-layout tile <-> [row][feature] buffer
-__device__ __forceinline__ f32x4 ld_act(const float* buf, int t, int c, int q) {
-    return *reinterpret_cast<const f32x4*>(buf + c * SP + 16 * t + 4 * q);
-}
-__device__ __forceinline__ void st_act(float* buf, int t, int c, int q, f32x4 v) {
-    *reinterpret_cast<f32x4*>(buf + c * SP + 16 * t + 4 * q) = v;
-}
 // gradient tile (out tile of A-buffer `da`, in tile of B-buffer `xb`) over the 16 rows: acc[m][n] += sum_row da[row][16 ta + m] * xb[row][16 tb + n]
 __device__ __forceinline__ f32x4 wgrad16(const float* da, int ta, const float* xb, int tb, f32x4 acc, int m, int kq) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) acc = VPC_MFMA(da[(4 * s + kq) * SP + 16 * ta + m], xb[(4 * s + kq) * SP + 16 * tb + m], acc);
-    return acc;
-}
-
-// Weight fragments straight from the fp32 image in global memory (the layout of vpc_layout.h: row pitch S dwords, 16-byte slot
-// XOR-swizzled with the row) - REQUESTED one stage ahead of their use (ldW / ldWT), consumed by mmW.  Forward: rows 16 mt + m,
-// one 16-byte load per k-tile; transposed (dgrad): column 16 mt + m, four dword loads per k-tile (tile_fwd / tile_T of
-// vpc_device.h, split into request and use).
-template <int KT, int S>
-__device__ __forceinline__ void ldW(const float* W, int mt, int m, int q, f32x4 (&a)[KT]) {
-    constexpr int MASK = (S / 4 - 1) & 15;
-    const float* rowp = W + (16 * mt + m) * S;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) a[kt] = *reinterpret_cast<const f32x4*>(rowp + 4 * ((4 * kt + q) ^ (m & MASK)));
-}
-template <int KT, int S, int NK = 4 * KT>
-__device__ __forceinline__ void ldWT(const float* W, int mt, int m, int q, f32x4 (&a)[KT]) {
-    constexpr int MASK = (S / 4 - 1) & 15;
-    const int col = 16 * mt + m, cs = col >> 2, cl = col & 3;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = 4 * q + j;
-            a[kt][j] = (4 * kt + j < NK) ? W[(16 * kt + r) * S + (((cs ^ (r & MASK)) << 2) | cl)] : 0.f;
-        }
-}
-template <int KT, int NK = 4 * KT>
-__device__ __forceinline__ f32x4 mmW(const f32x4 (&a)[KT], const f32x4 (&in)[KT], f32x4 acc) {
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (4 * kt + j < NK) acc = VPC_MFMA(a[kt][j], in[kt][j], acc);
     return acc;
 }
 

@@ -15,10 +15,21 @@ computes on its data: same tile body, same summation order, same Philox counters
     stack_models(models)         one [G, n] buffer under the members' parameters; every model stays an ordinary module
     MemberTable                  the per-member records (loss coefficients, keep probability, lr, seed) on the host
     EnsembleTrainer              the step, the read-outs and per-member views of the stacked state
+
+The sweep's evaluation shares a launch the same way (every train() of the drivers is followed by eval_vae, imputation.py:51-59
+around evaluate.py:136-297: M Monte-Carlo passes over the loaders, forward + loss(llh_eval=True, stage='evaluate') per batch):
+
+    vpc_eval_small_multi_f32     grid = tiles x G; workgroup (t, g) runs the evaluate-stage forward of member g on one 16-row
+                                 tile of one batch of one MC pass and leaves five sums (csrc/vpc_evalsmall.hip)
+    vpc_eval_reduce_multi        tiles -> batches -> passes -> (rmse, elbo, negll, negll_imp) per member, blockIdx.y = member
+
+    build_eval_tables            the tile / batch / pass tables of one (N, batch layout, M)
+    EnsembleEvaluator            the call, the table cache, image freshness and the Philox offset of its draws
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -29,13 +40,14 @@ from .fused import LP
 from .images import PackedImage, flat_written
 from .models import Reg_VAE, loss_coefficients, vanilla_VAE
 from .ops import as_mask_u8
-from .trainer import draw_counters, pad_cols
+from .trainer import draw_counters, eval_draw_counters, pad_cols
 
 # VpcMember of include/vpc.h (64 bytes): the first 32 are its VpcLossCoef, spelled flat
 MEMBER_DTYPE = np.dtype([("cA", "<f4", 2), ("cE", "<f4", 2), ("bq", "<f4"), ("bp", "<f4"), ("cr", "<f4"), ("wml", "<f4"),
                          ("keep_prob", "<f4"), ("lr", "<f4"), ("seed", "<u8"), ("use_maskB", "<i4"), ("reserved", "<i4", 3)])
 assert MEMBER_DTYPE.itemsize == 64
 MAX_BLOCKS = 8192  # VPC_MULTI_MAX_BLOCKS of include/vpc.h: workgroups (G x tiles per member) of one ensemble launch
+EVAL_MAX_BLOCKS = 65536  # VPC_EVAL_MAX_BLOCKS: workgroups of one evaluation launch (the entry walks the tile table in chunks)
 ROW_ALIGN = 64  # floats: every row of a stack starts on a 256-byte boundary, as a stand-alone flat buffer does
 
 
@@ -119,6 +131,30 @@ def stack_models(models):
     return stack
 
 
+def install_image_stack(models, lay, dev):
+    """The members' fp32 weight images [enc | dec] as rows of ONE new stack: row g becomes model g's own image (images.py), so
+    the API path, the ensemble step's re-pack and the ensemble evaluation read and stamp the same buffer.  Returns the stack."""
+    if (lay.enc_img + lay.dec_img) % 4:
+        raise L.VpcError("weight image rows must be 16-byte multiples")
+    img = torch.from_numpy(lay.img_template).to(dev).repeat(len(models), 1)
+    pidx = lay.device_tables(dev)[0]
+    for g, m in enumerate(models):
+        m._img = PackedImage(img[g], lambda flat, buf: ops.pack_weights(flat, pidx, buf))
+    return img
+
+
+def image_stack_of(models, n_img, dev):
+    """(member 0's image, row stride in floats) when the members' images are rows of one stack on `dev`, else None."""
+    bufs = [getattr(m._img, "buf", None) for m in models]
+    if any(b is None or b.device != dev or b.numel() != n_img or b.dtype != torch.float32 for b in bufs):
+        return None
+    p0 = bufs[0].data_ptr()
+    step = bufs[1].data_ptr() - p0 if len(bufs) > 1 else 4 * n_img
+    if step < 4 * n_img or step % 16 or any(b.data_ptr() != p0 + g * step for g, b in enumerate(bufs)):
+        return None
+    return bufs[0], step // 4
+
+
 class MemberTable:
     """Host side of the device-resident member table: one VpcMember record per member.  `update` rebuilds the rows only when
     one of its inputs changed, and reports whether any row did (then, and only then, the trainer uploads it)."""
@@ -199,14 +235,9 @@ class EnsembleTrainer:
         self.inv = lay.inverse_maps(self.dev)
         # the members' fp32 weight images are rows of one stack: each stays the model's own image (images.py), so the API
         # path reads what the ensemble step re-packs
-        n_img = lay.enc_img + lay.dec_img
-        self.img = torch.from_numpy(lay.img_template).to(self.dev).repeat(G, 1)
-        if n_img % 4:
-            raise L.VpcError("weight image rows must be 16-byte multiples")
-        pidx = self.pidx
+        self.img = install_image_stack(models, lay, self.dev)
         self._plists, self._row_ptr = [], []
         for g, m in enumerate(models):
-            m._img = PackedImage(self.img[g], lambda flat, buf: ops.pack_weights(flat, pidx, buf))
             pl = m.trainable()
             self._plists.append(pl)
             self._row_ptr.append(self.params[g].data_ptr())
@@ -330,3 +361,163 @@ class EnsembleTrainer:
         if reset:
             self.accum.zero_()
         return v
+
+    def evaluator(self):
+        """An EnsembleEvaluator on this trainer's members, with their seeds: it reads the image stack the step re-packs."""
+        return EnsembleEvaluator(self.models, seeds=self.table.rows["seed"].tolist())
+
+
+# ------------------------------------------------------------------------------------------------ evaluation
+class EvalTables(NamedTuple):
+    """Host form of the tables of include/vpc.h (ensemble evaluation), int64."""
+    tiles: np.ndarray  # [T, 4]: data row of the first row, valid rows 1..16, draw row of the first row, batch index
+    batches: np.ndarray  # [NB, 4]: rows, MC pass, first tile, tiles
+    passes: np.ndarray  # [M, 2]: first batch, batches
+    R: int  # draw rows: every row of every batch of every pass
+
+
+def eval_layout_key(N, batch_size=None, M=1, batches=None):
+    """What the tables depend on, hashable: (N, batch layout, M)."""
+    if (batch_size is None) == (batches is None):
+        raise L.VpcError("give either batch_size or batches (one list of (row_lo, row_hi) ranges per MC pass)")
+    if batches is None:
+        return int(N), ("batch_size", int(batch_size)), int(M)
+    return int(N), tuple(tuple((int(lo), int(hi)) for lo, hi in p) for p in batches), int(M)
+
+
+def build_eval_tables(N, batch_size=None, M=1, batches=None):
+    """The tile, batch and pass tables of one evaluation over N data rows.  batch_size: every pass walks the rows in
+    consecutive ranges of batch_size (the last one short); batches: M lists of (row_lo, row_hi) ranges, one list per pass.
+    A batch is cut into tiles of 16 rows (the last one ragged), so no tile straddles two batches.  Draw rows count on from pass
+    to pass, batch to batch, row to row: under batch_size, row n of pass p draws as row p * N + n."""
+    N, layout, M = eval_layout_key(N, batch_size, M, batches)
+    if N < 1 or M < 1:
+        raise L.VpcError("evaluation needs at least one data row and one MC pass")
+    if batches is None:
+        if batch_size < 1:
+            raise L.VpcError(f"batch_size {batch_size}")
+        batches = [[(lo, min(lo + batch_size, N)) for lo in range(0, N, batch_size)]] * M
+    else:
+        batches = layout
+        if len(batches) != M:
+            raise L.VpcError(f"{len(batches)} batch lists for {M} MC passes")
+    tiles, brows, prows, r = [], [], [], 0
+    for p, ranges in enumerate(batches):
+        if len(ranges) == 0:
+            raise L.VpcError(f"MC pass {p} has no batch")
+        prows.append((len(brows), len(ranges)))
+        for lo, hi in ranges:
+            if not 0 <= lo < hi <= N:
+                raise L.VpcError(f"batch rows [{lo}, {hi}) outside the {N} data rows (or empty)")
+            t0 = len(tiles)
+            for s in range(lo, hi, 16):
+                tiles.append((s, min(16, hi - s), r + s - lo, len(brows)))
+            r += hi - lo
+            brows.append((hi - lo, p, t0, len(tiles) - t0))
+    return EvalTables(np.array(tiles, np.int64), np.array(brows, np.int64), np.array(prows, np.int64), r)
+
+
+class EnsembleEvaluator:
+    """eval_vae's numbers (evaluate.py:136-297) for G stackable members over all batches and MC passes in one pair of launches:
+    vpc_eval_small_multi_f32 (forward of every member x pass x batch x 16-row tile -> five sums per tile) and
+    vpc_eval_reduce_multi (tiles -> batches -> passes -> [G, 4]).  Only the q pass is computed: VAE.py:410-420 reads nothing else."""
+    TABLE_CACHE = 8  # distinct (N, batch layout, M) kept on the device
+
+    def __init__(self, models, seeds=None, world_size=1):
+        """models: as EnsembleTrainer (validate_members), on the GPU.  seeds: one Philox seed per member (None: member g draws
+        with seed g).  The evaluator owns a Philox offset: a call advances it by the groups it consumed (eval_draw_counters)."""
+        models = list(models)
+        validate_members(models, world_size)
+        self.table = MemberTable(models, 0.0, seeds)
+        self.models = models
+        self.rng_offset = 0
+        # ---- device state from here on
+        self.params = stack_models(models)
+        L.require_cuda(self.params)
+        self.G, self.dev = len(models), self.params.device
+        self.lay = lay = models[0]._lay()
+        self.n_img = lay.enc_img + lay.dec_img
+        # the members' images are rows of one stack: the one they already sit in (an EnsembleTrainer's), else a new one
+        if image_stack_of(models, self.n_img, self.dev) is None:
+            install_image_stack(models, lay, self.dev)
+        self._plists = [m.trainable() for m in models]
+        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self._table_version = -1
+        self._tables, self._pads, self._part = {}, {}, None
+        self.launches = 0  # kernel launches of the last call (the forward entry walks the tile table in chunks)
+
+    def tables(self, N, batch_size=None, M=1, batches=None):
+        """(EvalTables, device tiles, device batches, device passes) of a layout: built and uploaded once, then cached."""
+        key = eval_layout_key(N, batch_size, M, batches)
+        hit = self._tables.get(key)
+        if hit is None:
+            tb = build_eval_tables(N, batch_size, M, batches)
+            if len(self._tables) >= self.TABLE_CACHE:
+                self._tables.pop(next(iter(self._tables)))
+            hit = self._tables[key] = (tb,) + tuple(torch.from_numpy(a).to(self.dev) for a in (tb.tiles, tb.batches, tb.passes))
+        return hit
+
+    def _images(self):
+        """(member 0's image, row stride): every member's image is checked against its parameter key (images.py) and a stale one
+        re-packed from its parameters, so a call after load_state_dict or after training steps reads the current weights."""
+        if image_stack_of(self.models, self.n_img, self.dev) is None:  # (a model's image was replaced: .to(), a stand-alone trainer)
+            install_image_stack(self.models, self.lay, self.dev)
+        for g, m in enumerate(self.models):
+            key = m._param_key(self._plists[g])
+            if m._img.key != key:
+                m._images(key)
+        return image_stack_of(self.models, self.n_img, self.dev)
+
+    def evaluate(self, x, mask, batch_size=None, M=1, *, batches=None, epoch, beta=1.0, beta_annealing=False, eps=None,
+                 max_blocks=0):
+        """x, mask: [N, d] (one data set shared by all members) or [G, N, d].  Batches: consecutive ranges of batch_size rows in
+        every one of the M passes, or `batches` = M lists of (row_lo, row_hi).  beta: scalar or one per member; epoch and
+        beta_annealing as model.loss takes them.  eps: [R, L] or [G, R, L] normals, R = the rows of all batches of all passes in
+        order (M * N under batch_size), or None: drawn on the device from member g's Philox stream (eval_draw_counters).
+        Returns [G, 4] on the device = (rmse on ~mask, elbo, negll, negll_imp) as eval_vae averages them; no host sync.
+        max_blocks: workgroups per launch (0: the library's limit)."""
+        L.require_cuda(x)
+        G, lay = self.G, self.lay
+        d, Ld = lay.d, lay.L
+        for t, name in ((x, "x"), (mask, "mask")):
+            if t.dim() not in (2, 3) or t.shape[-1] != d or (t.dim() == 3 and t.shape[0] != G):
+                raise L.VpcError(f"{name}: expected [N, {d}] or [{G}, N, {d}], got {tuple(t.shape)}")
+        N = x.shape[-2]
+        if mask.shape[-2] != N:
+            raise L.VpcError("x and mask differ in their row count")
+        tb, tiles_dev, batches_dev, passes_dev = self.tables(N, batch_size, M, batches)
+        T, R = tb.tiles.shape[0], tb.R
+        if eps is not None and (eps.dim() not in (2, 3) or tuple(eps.shape[-2:]) != (R, Ld) or (eps.dim() == 3 and eps.shape[0] != G)):
+            raise L.VpcError(f"eps: expected [{R}, {Ld}] or [{G}, {R}, {Ld}], got {tuple(eps.shape)}")
+        # the evaluate stage is the q pass's ELBO (VAE.py:410-420): at alpha = 0 every loss record's bq is its KL weight
+        self.table.update(epoch, 0.0, beta, beta_annealing, 0)
+        if self._table_version != self.table.version:
+            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
+            self._table_version = self.table.version
+        x = ops._f32c(x)
+        mask = as_mask_u8(mask)
+        dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # (the padding rule of FusedTrainer.step)
+        if dk != d:
+            x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
+        img0, simg = self._images()
+        offset, eps_buf = 0, None
+        if eps is None:
+            offset, self.rng_offset = eval_draw_counters(self.rng_offset, R, LP)
+        else:
+            eps_buf = torch.zeros(*eps.shape[:-1], LP, device=self.dev)
+            eps_buf[..., :Ld].copy_(eps)
+        if self._part is None or self._part.shape[1] < T * 5:
+            self._part = torch.empty(G, T * 5, dtype=torch.float64, device=self.dev)
+        out = torch.empty(G, 4, device=self.dev)
+        strides = [0] * 9  # VPC_MS_* of include/vpc.h
+        strides[0] = x.stride(0) if x.dim() == 3 else 0
+        strides[1] = mask.stride(0) if mask.dim() == 3 else 0
+        strides[3] = eps_buf.stride(0) if eps_buf is not None and eps_buf.dim() == 3 else 0
+        strides[4], strides[7] = simg, self._part.stride(0)
+        ops.eval_small_multi_f32(x, mask, eps_buf, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, G, tiles_dev, T, N, R,
+                                 eps is None, offset, self.models[0]._x_logvar_value, self._part, strides, dk, d, Ld, max_blocks)
+        ops.eval_reduce_multi(self._part, batches_dev, tb.batches.shape[0], passes_dev, M, self.table_dev, G,
+                              self._part.stride(0), T, d, out)
+        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
+        self.launches = (T + per - 1) // per + 1
+        return out

@@ -7,7 +7,9 @@
   train_sweep          src/experiment_main/imputation.py:21-39  the drivers' loops over alpha / p_missingness / split around
                                                              train(), as ensembles stepped by one pair of launches (ensemble.py)
   eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL
-  eval_vae_mnar        src/experiment_main/evaluate.py:13-69    importance-weighted imputation RMSE (MNAR path)
+  eval_sweep           src/experiment_main/imputation.py:51-59  eval_vae() of a list of runs, stackable members in one pair of
+                                                             launches per loader (ensemble.EnsembleEvaluator)
+  eval_vae_mnar        src/experiment_main/evaluate.py:13-69   importance-weighted imputation RMSE (MNAR path)
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
 The families model_loader builds are Reg_VAE, vanilla_VAE and their *_mask variants, Reg_EDDI / vanilla_EDDI (and, for
@@ -28,7 +30,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .ensemble import EnsembleTrainer, stackable
+from .ensemble import EnsembleEvaluator, EnsembleTrainer, stackable
 from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
@@ -350,6 +352,114 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
                                      p_missingness, reg_type)
                 for k, pth in paths.items():
                     _save(out[loader_stage][k], pth)
+    return out
+
+
+def eval_groups(models):
+    """How eval_sweep splits its members: ({(class, reg_type): [member indices]}, [indices evaluated one by one]).  Stackable
+    members (ensemble.stackable) of one class and reg_type share an EnsembleEvaluator; every other family goes alone."""
+    groups, alone = {}, []
+    for g, m in enumerate(models):
+        if stackable(m):
+            groups.setdefault((type(m), getattr(m, "reg_type", None)), []).append(g)
+        else:
+            alone.append(g)
+    return groups, alone
+
+
+def _gather_passes(sources, M, obs_dim, device):
+    """Iterate every loader of `sources` (one shared loader, or one per member) once per MC pass, as eval_vae does, and put
+    the batches of all passes behind each other on the device.  -> (x, mask, batches): x / mask [R, d] for one source, else
+    [G, R, d]; batches = M lists of (row_lo, row_hi) into them.  None when the members' loaders do not yield the same batch
+    sizes at every step (one evaluate call needs one layout)."""
+    xs, ms, ranges, r = [[] for _ in sources], [[] for _ in sources], [], 0
+    for _ in range(M):
+        its, pr = [iter(s) for s in sources], []
+        while True:
+            bs = [next(it, None) for it in its]
+            if all(b is None for b in bs):
+                break
+            if any(b is None for b in bs):
+                return None
+            rows = {b[0].reshape(-1, obs_dim).shape[0] for b in bs}
+            if len(rows) != 1:
+                return None
+            for k, b in enumerate(bs):
+                xs[k].append(b[0].to(device).reshape(-1, obs_dim))
+                ms[k].append(b[1].to(device).reshape(-1, obs_dim))
+            n = rows.pop()
+            pr.append((r, r + n))
+            r += n
+        if not pr:
+            return None
+        ranges.append(pr)
+    x, mk = [torch.cat(v) for v in xs], [torch.cat(v) for v in ms]
+    return (x[0], mk[0], ranges) if len(sources) == 1 else (torch.stack(x), torch.stack(mk), ranges)
+
+
+def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
+               experiment_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), stage="evaluate",
+               reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, models=None, loaders=None, save=True):
+    """eval_vae() for a LIST of runs - the evaluation that follows every train() of the drivers' loops
+    (src/experiment_main/imputation.py:51-59 around evaluate.py:136-297) as one call; the twin of train_sweep, with its
+    conventions.  configs: one dict per member with the keys vae_type, alpha (1.0), p_missingness (30), seed (0).
+    list_loaders: what eval_vae takes, shared by every member; or loaders = one such list per member.  models (optional): one
+    model per member, else each member's checkpoint through model_loader('test', ...).
+    Plain Reg_VAE / vanilla_VAE members of one class and reg_type are evaluated together: per (loader, loader_stage) the
+    loader is iterated once per MC pass (a shuffling loader gives every pass its own partition into batches), the batches
+    are gathered on the device and ONE ensemble.EnsembleEvaluator.evaluate call computes every member x pass x batch.  Every
+    other family (mask-augmented, wide, EDDI, MNAR, MIWAE, flow), and per-member loaders whose batch sizes differ, go
+    through eval_vae one by one.  Returns, per member in the order of configs, what eval_vae returns, and (save=True) writes
+    the reference's four files under result_paths(...) with that member's alpha / p_missingness.
+    What differs from eval_vae for the members evaluated together: no p pass and no mask_p draw (VAE.py:410-420 never reads
+    them, and under Philox there is no stream position to preserve); eps comes from the member's Philox stream (seed =
+    the config's seed), not from torch.randn; a shared loader is iterated once per pass for the whole group, not once per
+    member.  The estimator and its distribution are the same."""
+    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
+    G = len(cfgs)
+    if models is not None and len(models) != G:
+        raise L.VpcError(f"{len(models)} models for {G} configurations")
+    if loaders is not None and len(loaders) != G:
+        raise L.VpcError(f"{len(loaders)} loaders for {G} configurations")
+    member_loaders = (lambda g: loaders[g]) if loaders is not None else (lambda g: list_loaders)
+    ms = [_model_for_eval(models[g] if models is not None else None, device, obs_dim, hid_dim, K, latent_dim, missing_rate,
+                          data_type, training_parameters, max_epochs, valid_k, num_estimates, experiment_type, reg_type,
+                          c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"]) for g, c in enumerate(cfgs)]
+    out = [None] * G
+
+    def alone(g):
+        c = cfgs[g]
+        out[g] = eval_vae(member_loaders(g), missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
+                          experiment_type, c["vae_type"], max_epochs, valid_k, num_estimates, device, c["alpha"], stage,
+                          c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, model=ms[g], save=save)
+
+    groups, single = eval_groups(ms)
+    for g in single:
+        alone(g)
+    for idx in groups.values():
+        stages = [s for _, s in member_loaders(idx[0])]
+        gathered = []
+        for li in range(len(stages)):
+            sources = [list_loaders[li][0]] if loaders is None else [loaders[g][li][0] for g in idx]
+            gathered.append(_gather_passes(sources, M, obs_dim, device))
+        if any(t is None for t in gathered) or any([s for _, s in member_loaders(g)] != stages for g in idx):
+            for g in idx:
+                alone(g)
+            continue
+        with torch.no_grad():
+            ev = EnsembleEvaluator([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
+            for g in idx:
+                out[g] = {}
+            for loader_stage, (x, mk, ranges) in zip(stages, gathered):
+                r = ev.evaluate(x, mk, M=M, batches=ranges, epoch=max_epochs, beta=beta, beta_annealing=beta_annealing).cpu()
+                for k, g in enumerate(idx):
+                    res = out[g][loader_stage] = dict(rmse=r[k, 0].clone(), elbo=r[k, 1].clone(), negll=r[k, 2].clone(),
+                                                      negll_imp=r[k, 3].clone())
+                    if save:
+                        paths = result_paths(experiment_type, data_type, cfgs[g]["vae_type"], loader_stage, missing_rate,
+                                             cfgs[g]["alpha"], cfgs[g]["p_missingness"], reg_type)
+                        for name, pth in paths.items():
+                            _save(res[name], pth)
     return out
 
 

@@ -170,6 +170,22 @@ def reduce_step_adam_multi(partE, partD, loss_part, blocks, strideE, strideD, st
                                            ptr(img), stream_ptr()), "vpc_reduce_step_adam_multi")
 
 
+def eval_small_multi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, part,
+                         strides, d, d_real, Ld, max_blocks=0):
+    """The evaluate-stage forward of G members over the tiles of a tile table (include/vpc.h: ensemble evaluation): one record of
+    5 doubles per (member, tile) into `part`.  Pointers are member 0's, `strides` the VPC_MS_* member strides in elements."""
+    check(lib().vpc_eval_small_multi_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G, ptr(tiles),
+                                         int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar, ptr(part),
+                                         _member_strides(strides), d, d_real, Ld, int(max_blocks), stream_ptr()),
+          "vpc_eval_small_multi_f32")
+
+
+def eval_reduce_multi(part, batches, n_batches, passes, M, members, G, part_stride, n_tiles, d_real, out):
+    """The tile records -> out[G][4] = (rmse, elbo, negll, negll_imp): per batch, mean over a pass's batches, mean over passes."""
+    check(lib().vpc_eval_reduce_multi(ptr(part), ptr(batches), int(n_batches), ptr(passes), int(M), ptr(members), G,
+                                      int(part_stride), int(n_tiles), d_real, ptr(out), stream_ptr()), "vpc_eval_reduce_multi")
+
+
 def step_fused_applicable(B, d, Ld, npass):
     return bool(lib().vpc_step_fused_applicable(int(B), d, Ld, npass))
 

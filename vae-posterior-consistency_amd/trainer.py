@@ -36,6 +36,15 @@ def draw_counters(rng_offset, draw_mask, planes, rows_local, rows_global, row_lo
                  (rows_local, rows_global, row_lo, pitch))
 
 
+def eval_draw_counters(rng_offset, draw_rows, pitch=16):
+    """THE counter rule of the ensemble evaluation's draws: one call draws eps for `draw_rows` rows
+    (every row of every batch of every MC pass, in tile-table order) of `pitch` floats, one Philox call per 4 floats, on the
+    eps stream with the member's seed.  The group of draw row r, columns 4 q .. 4 q + 3, has counter offset + r * (pitch / 4) + q:
+    what ops.fill_normal(flat [draw_rows * pitch], seed, offset) writes at float index r * pitch + 4 q.
+    Returns (offset of this call, the evaluator's rng_offset after it)."""
+    return rng_offset, rng_offset + draw_rows * (pitch // 4)
+
+
 def pad_cols(pads, t, dk, slot, dev):
     """[..., B, d] -> zero-padded [..., B, dk]: a persistent buffer per input slot, kept in the dict `pads`."""
     key = (slot, tuple(t.shape[:-1]), dk, t.dtype)
