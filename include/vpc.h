@@ -576,6 +576,47 @@ int vpc_eval_small_multi_f32(const float* x, const uint8_t* mask, const float* e
 int vpc_eval_reduce_multi(const double* part, const long long* batches, long n_batches, const long long* passes, int M,
                           const VpcMember* members, int G, long part_stride, long n_tiles, int d_real, float* out, void* stream);
 
+/* ---- ensemble acquisition: the loop of active_learning_func (src/experiment_main/evaluate.py:300-511) for G members of one
+ * ensemble, a fixed number of launches per acquisition step and no host round trip (csrc/vpc_evalsmall.hip, csrc/vpc_reward.hip).
+ *
+ * vpc_impute_small_multi_f32: the M Monte-Carlo forwards of evaluate.py:396-414 (and of :380-392): the forward of
+ * vpc_eval_small_multi_f32 - same arguments, tile table, fences, draw rule and max_blocks chunking, same arithmetic up to x_hat -
+ * that WRITES instead of summing.  mode 0: out[g][draw row][0..d_real) = x_hat, a dense [R][d_real] array per member (real rows
+ * and real columns only); under the table of (n, batch_size = n, M) draw row m n + i is row i of pass m, so out is im [M][n][d].
+ * mode 1: out[g][draw row] = (x_hat[T] - x[T])^2 of the target column T = d_real - 1.  out_stride: floats between members
+ * (>= R d_real / >= R).  Limits and errors as vpc_eval_small_multi_f32; mode outside {0, 1}: VPC_ERR_ARG. */
+int vpc_impute_small_multi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                               const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                               unsigned long long offset, float x_logvar, int mode, float* out, long out_stride,
+                               const long* strides, int d, int d_real, int L, int max_blocks, void* stream);
+/* target_mse of evaluate.py:390-392 per member: out[g * out_stride] = mean of sq[g * sq_stride + 0..R) (the mode-1 squared errors
+ * of the R = M n draw rows), accumulated in fp64 in a fixed order (no atomics), stored as float. */
+int vpc_target_mse_multi(const float* sq, long sq_stride, long R, int G, float* out, long out_stride, void* stream);
+/* vpc_reward_matrix (evaluate.py:424-433 around :514-634) with a member dimension: the same three launches with blockIdx.y =
+ * member, for the plain model at d <= 128.  Pointers are member 0's; member g's slice starts g * strides[k] ELEMENTS further
+ * (host array of VPC_RM_COUNT longs):
+ *   VPC_RM_X      x [n][d] (0 = shared)            VPC_RM_MASK   mask [n][d] bytes          VPC_RM_IM     im [M][n][d]
+ *   VPC_RM_PARAM  W1 [100][d] and b1 [100]: both g * stride floats further (rows of a parameter stack)
+ *   VPC_RM_IMG    enc_img (rows of an image stack; multiple of 4)
+ *   VPC_RM_PRE, VPC_RM_STAT, VPC_RM_W1T   the workspaces, vpc_reward_scratch_multi's sizes per member (multiples of 4)
+ *   VPC_RM_R      R [n][d-1]
+ * R[g] is bit for bit what vpc_reward_matrix gives on member g's operands (same per-item arithmetic and in-wave summation order;
+ * only the order in which items are handed out differs).  chunk: the workspaces hold `chunk` members; members go through them in
+ * ceil(G / chunk) rounds of three launches (the inputs and R are indexed by the member, the workspaces by the member's place in its
+ * round).  Limits as vpc_reward_matrix. */
+enum { VPC_RM_X = 0, VPC_RM_MASK, VPC_RM_IM, VPC_RM_PARAM, VPC_RM_IMG, VPC_RM_PRE, VPC_RM_STAT, VPC_RM_W1T, VPC_RM_R, VPC_RM_COUNT };
+int vpc_reward_scratch_multi(int n, int d, int M, long* pre_floats, long* stat_floats, long* w1t_floats);
+int vpc_reward_matrix_multi(const float* x, const uint8_t* mask, const float* im, const float* W1, const float* b1,
+                            const float* enc_img, float* pre, float* stat, float* w1t, float* R, int G, int chunk,
+                            const long* strides, int n, int d, int L, int M, void* stream);
+/* The acquisition of evaluate.py:435-440 per (member, row): i_opt = the lowest index among the maxima of R[g][row][0..d-1)
+ * (torch.argmax on finite input), mask[g][row][i_opt] = 1 (bytes, rows mask_pitch apart; mask2, if not NULL, is the same mask kept at
+ * a second row pitch - the forward reads rows padded to a multiple of 4 columns, the reward rows of d), action[g][row] = i_opt with
+ * rows action_pitch ints apart (the step's column of an action history [n][d-1]). */
+int vpc_acquire_multi(const float* R, long R_stride, uint8_t* mask, long mask_stride, int mask_pitch, uint8_t* mask2,
+                      long mask2_stride, int mask2_pitch, int* action, long action_stride, int action_pitch, int G, int n, int d,
+                      void* stream);
+
 /* ---- MIWAE path: MIWAE / Reg_MIWAE (csrc/vpc_miw.hip) ------------------------------------------------------------
  * Reference: src/models/VAE.py:3011-3134 and :3137-3301.  Encoder d->128->128 ReLU -> [mean L | raw L] and decoder
  * L->128->128 ReLU -> [mean d | scale d | df d] run on vpc_linear_fwd / dgrad / wgrad (ACT_RELU, last layer ACT_NONE);

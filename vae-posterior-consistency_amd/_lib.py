@@ -64,6 +64,11 @@ _PROTOS = {
     "vpc_reduce_step_adam_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P],
     "vpc_eval_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],
     "vpc_eval_reduce_multi": [P, P, L_, P, I, P, I, L_, L_, I, P, P],
+    "vpc_impute_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, I, P, L_, C.POINTER(L_), I, I, I, I, P],
+    "vpc_target_mse_multi": [P, L_, L_, I, P, L_, P],
+    "vpc_reward_scratch_multi": [I, I, I, C.POINTER(L_), C.POINTER(L_), C.POINTER(L_)],
+    "vpc_reward_matrix_multi": [P, P, P, P, P, P, P, P, P, P, I, I, C.POINTER(L_), I, I, I, I, P],
+    "vpc_acquire_multi": [P, L_, P, L_, I, P, L_, I, P, L_, I, I, I, I, P],
     "vpc_step_fused_applicable": [L_, I, I, I],
     "vpc_step_layout_bf16": [I, I, IP, IP],
     "vpc_step_build_indices_bf16": [I, I, P, P],

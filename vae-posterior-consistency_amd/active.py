@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib, ptr, stream_ptr
+from .ensemble import EnsembleAcquirer
 from .images import PackedImage
 from .ops import _f32c, as_mask_u8, pack_weights
 
@@ -381,3 +382,55 @@ def active_learning_flow(data_loader_train, test_data, test_mask, missing_rate, 
     out = _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, Repeat, model, lambda: model, passes,
                             reward, verbose, max_steps)
     return _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
+
+
+def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type,
+                 training_parameters, experiment_type, max_epochs, valid_k, num_estimates, device=None, stage="evaluate",
+                 reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, Repeat=5, models=None, save=True,
+                 max_steps=None):
+    """active_learning_func() for a LIST of runs - the loop body of src/experiment_main/active_learning.py (train, then
+    active_learning_func, inside `for data_file: for missing: for alpha:`) after train_sweep, as one call; the twin of
+    harness.eval_sweep, with its conventions.  configs: one dict per member with the keys vae_type, alpha (1.0), p_missingness
+    (30), seed (0).  models (optional): one model per member, else each member's checkpoint through model_loader('test', ...).
+    Members are grouped with harness.eval_groups: plain Reg_VAE / vanilla_VAE members of one class and reg_type run the whole
+    loop through ONE ensemble.EnsembleAcquirer - a fixed number of launches per acquisition step whatever their number, nothing
+    read back before the end; every other family (mask-augmented, wide, EDDI) goes alone through active_learning_func, and the
+    flow models through active_learning_flow.  Returns, per member in the order of configs, the dict active_learning_func returns
+    (information_curve_CHAI [Repeat, n, d] - the scalar curve broadcast over the rows, as the reference stores it -, action_CHAI
+    [Repeat, n, d-1] float, R_hist_CHAI [Repeat, d-1, n, d-1], im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the
+    reference's four files under active_result_paths(...) with that member's alpha / p_missingness.
+    What differs from active_learning_func for the members run together: no p pass and no mask_p draw (VAE.py:496-507: neither
+    reaches an output of the loop); eps comes from the member's Philox stream (seed = the config's seed), not from torch.randn;
+    the M passes of a forward call are one launch; a given (or loaded) model serves every repeat - the reference reloads the
+    same checkpoint per repeat.  The estimator and its distribution are the same."""
+    from .harness import _model_for_eval, eval_groups
+    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
+    G = len(cfgs)
+    if models is not None and len(models) != G:
+        raise L.VpcError(f"{len(models)} models for {G} configurations")
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    ms = [_model_for_eval(models[g] if models is not None else None, dev, obs_dim, hid_dim, K, latent_dim, missing_rate,
+                          data_type, training_parameters, max_epochs, valid_k, num_estimates, experiment_type, reg_type,
+                          c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"], alpha_annealing=alpha_annealing)
+          for g, c in enumerate(cfgs)]
+    out = [None] * G
+    groups, single = eval_groups(ms)
+    for g in single:
+        c = cfgs[g]
+        fn = active_learning_flow if _is_flow(ms[g]) else active_learning_func
+        out[g] = fn(data_loader_train, test_data, test_mask, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type,
+                    training_parameters, experiment_type, c["vae_type"], max_epochs, valid_k, num_estimates, dev, c["alpha"],
+                    stage, c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, Repeat, model=ms[g], save=save,
+                    max_steps=max_steps)
+    x = test_data.reshape(-1, obs_dim).float().to(dev)
+    for idx in groups.values():
+        with torch.no_grad():
+            acq = EnsembleAcquirer([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
+            info, action, R_hist, im_hist = [t.cpu() for t in acq.run(x, M, repeats=Repeat, max_steps=max_steps)]
+        n = x.shape[0]
+        for k, g in enumerate(idx):
+            res = dict(information_curve_CHAI=info[k, :, None, :].expand(Repeat, n, obs_dim).clone(),
+                       action_CHAI=action[k].float(), R_hist_CHAI=R_hist[k].clone(), im_CHAI=im_hist[k].clone())
+            out[g] = _save_active(res, save, experiment_type, data_type, cfgs[g]["vae_type"], missing_rate, cfgs[g]["alpha"],
+                                  cfgs[g]["p_missingness"], reg_type)
+    return out

@@ -13,6 +13,9 @@
 // per-batch quantities are non-linear); the host's tile table says where its rows are.  Five sums per tile, one record of doubles
 // per (member, tile), no atomics.
 // eval_reduce_multi_kernel: blockIdx.y = member; tiles -> batches -> passes -> out[g][4] in fp64, in a fixed order.
+// impute_small_kernel: the same forward (ONE body text, vpc_evalsmall_body.h) keeping x_hat instead of the sums - the M Monte-Carlo
+// forwards of active_learning_func (evaluate.py:380-414) for G members: x_hat per draw row, or the target column's squared error;
+// target_mse_multi_kernel: the mean of those errors per member (evaluate.py:390-392), fp64 in a fixed order.
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
 #include "vpc_small_device.h"
@@ -42,174 +45,32 @@ struct EvalArgs {
     int d, d_real, L, draw;
 };
 
+// What becomes of x_hat: OUT_SUMS the five sums of the tile's record, OUT_XHAT / OUT_SQERR what impute_small_kernel writes.
+enum { OUT_SUMS = 0, OUT_XHAT, OUT_SQERR };
 template <int DT>
 __global__ __launch_bounds__(THREADS) void eval_small_kernel(EvalArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    auto buf = [&](int b) { return lds + b * SBUF; };
-    float* red = lds + E_COUNT * SBUF;
-    constexpr int S1 = s_for_tiles(DT);
-    const EncImg ei(DT);
-    const DecImg di(DT);
-    const unsigned mem = blockIdx.y;
-    const long tile_id = a.tile0 + blockIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    double* rec = a.part + mem * a.spart + tile_id * EVAL_TERMS;
-    // (uniform addresses: scalar loads)
-    const long long* te = a.tiles + 4 * tile_id;
-    const long xrow0 = te[0], nvl = te[1], erow0 = te[2];
-    // a tile entry that points outside the arrays reads nothing: its record is zero (the host builds the table; this is the fence)
-    if (xrow0 < 0 || nvl < 1 || nvl > 16 || xrow0 + nvl > a.N || erow0 < 0 || erow0 + nvl > a.R) {
-        if (threadIdx.x < EVAL_TERMS) rec[threadIdx.x] = 0.0;
-        return;
-    }
-    const int nv = (int)nvl;
-    const float* xg = a.x + mem * a.sx;
-    const uint8_t* mg = a.mask + mem * a.sm;
-    const float* enc_img = a.enc_img + mem * a.simg;
-    const float* dec_img = a.dec_img + mem * a.simg;
-    // (re-derived from opaque base pointers per phase, as the tile body does: keeps the fragment loads of all layers from being
-    // hoisted to the top of the kernel)
-    const float *W1, *b1, *W2, *W3, *W4, *W5, *W6;
-    auto weights = [&]() {
-        const float* e_ = enc_img;
-        const float* d_ = dec_img;
-        asm volatile("" : "+s"(e_), "+s"(d_)::"memory");
-        W1 = e_ + ei.oW1; b1 = e_ + ei.ob1; W2 = e_ + ei.oW2; W3 = e_ + ei.oW3;
-        W4 = d_ + di.oW4; W5 = d_ + di.oW5; W6 = d_ + di.oW6;
-    };
-    const float inv_s2 = expf(-a.x_logvar), half_lv = 0.5f * a.x_logvar;
-    const bool ok = c < nv;
-    // ---- this wave's column tile of x and of the mask words (range-checked: rows past the tile's valid rows read 0; the last
-    // tile's columns past d read column 0 and are cleared)
-    const bool colok = 16 * w + 4 * q + 3 < a.d;
-    f32x4 xv = zero4();
-    uint32_t mw = 0;
-    if (w < DT) {
-        const int vo = c * a.d + (colok ? 16 * w + 4 * q : 0);
-        xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rows_rsrc(xg, xrow0, xrow0 + nv, a.d), 4 * vo, 0, 0));
-        mw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(mg) + xrow0 * a.d, 0, (uint32_t)(nv * a.d), 0x00020000), vo, 0, 0);
-        if (!colok) { mw = 0; xv = zero4(); }
-    }
-    int cc = c, qq = q;
-    launder(cc, qq);
-    // ================================================================ encoder forward (phase E of the tile body, pass 0)
-    {
-        weights();
-        f32x4 fW1[DT], fW2[H1T], fW3[H2T], bias1 = zero4();
-        if (w < H1T) {
-            ldW<DT, S1>(W1, w, cc, qq, fW1);
-            bias1 = *reinterpret_cast<const f32x4*>(b1 + 16 * w + 4 * qq);
-        }
-        if (w < DT) st_act(buf(E_X), w, cc, qq, xv * mask_to_f32(mw));  // x.float() * mask  (VAE.py:388)
-        if (w < H2T) ldW<H1T, 128>(W2, w, cc, qq, fW2);
-        lds_barrier();
-        launder(cc, qq);
-        if (w < H1T) {
-            f32x4 in[DT];
-#pragma unroll
-            for (int t = 0; t < DT; ++t) in[t] = ld_act(buf(E_X), t, cc, qq);
-            st_act(buf(E_H1), w, cc, qq, relu4(mmW<DT>(fW1, in, bias1)));
-        }
-        if (w < 2) ldW<H2T, 64>(W3, w, cc, qq, fW3);
-        lds_barrier();
-        launder(cc, qq);
-        if (w < H2T) {
-            f32x4 in[H1T];
-#pragma unroll
-            for (int t = 0; t < H1T; ++t) in[t] = ld_act(buf(E_H1), t, cc, qq);
-            st_act(buf(E_H2), w, cc, qq, relu4(mmW<H1T, NK1>(fW2, in, zero4())));
-        }
-        lds_barrier();
-        launder(cc, qq);
-        if (w < 2) {  // wave 0: mean tile, wave 1: logvar tile
-            f32x4 in[H2T];
-#pragma unroll
-            for (int t = 0; t < H2T; ++t) in[t] = ld_act(buf(E_H2), t, cc, qq);
-            f32x4 o = mmW<H2T, NK2>(fW3, in, zero4());
-            if (!ok) o = zero4();  // rows past the valid ones: statistics 0
-            st_act(buf(E_ML), w, cc, qq, o);
-        }
-    }
-    lds_barrier();
-    launder(cc, qq);
-    // ================================================================ decoder forward and the five sums
-    float S_A = 0.f, S_I = 0.f, SQ = 0.f, CNT = 0.f, KL = 0.f;
-    {
-        weights();
-        f32x4 fW4[1], fW5[H2T], fW6[H1T];
-        if (w < H2T) ldW<1, S4>(W4, w, cc, qq, fW4);
-        if (w < H1T) ldW<H2T, 64>(W5, w, cc, qq, fW5);
-        if (w == 0) {  // z = mean + eps * exp(logvar / 2); z[L] = 1 drives the bias chain; the row's KL to the standard normal
-            const f32x4 mu = ld_act(buf(E_ML), 0, cc, qq), lv = ld_act(buf(E_ML), 1, cc, qq);
-            f32x4 e;
-            if (a.draw) {
-                // group q of draw row r has the counter vpc_fill_normal gives float index 16 r + 4 q of a flat [R x 16] array
-                e = eps_normal4((uint64_t)((erow0 + cc) * 4 + qq) + a.offset, a.members[mem].seed);
-            } else {
-                e = ld_rows(rows_rsrc(a.eps + mem * a.seps, erow0, erow0 + nv, 16), cc, 16, 4 * qq);
-            }
-            f32x4 z;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool lat = 4 * qq + j < a.L;
-                z[j] = mu[j] + ((lat && ok) ? e[j] : 0.f) * __expf(0.5f * lv[j]);
-                if (4 * qq + j == a.L) z[j] = 1.f;
-                if (lat) KL += 0.5f * (__expf(lv[j]) + mu[j] * mu[j] - 1.f - lv[j]);  // (rows past the valid ones: 0)
-            }
-            st_act(buf(E_Z), 0, cc, qq, z);
-        }
-        lds_barrier();
-        launder(cc, qq);
-        if (w < H2T) {
-            const f32x4 in[1] = {ld_act(buf(E_Z), 0, cc, qq)};
-            st_act(buf(E_G1), w, cc, qq, relu4(mmW<1>(fW4, in, zero4())));
-        }
-        if (w < DT) ldW<H1T, 128>(W6, w, cc, qq, fW6);
-        lds_barrier();
-        launder(cc, qq);
-        if (w < H1T) {
-            f32x4 in[H2T];
-#pragma unroll
-            for (int t = 0; t < H2T; ++t) in[t] = ld_act(buf(E_G1), t, cc, qq);
-            st_act(buf(E_G2), w, cc, qq, relu4(mmW<H2T, NK2>(fW5, in, zero4())));
-        }
-        lds_barrier();
-        launder(cc, qq);
-        if (w < DT) {  // output tile w: x_hat = sigmoid(.), the terms on mask and on its complement
-            f32x4 in[H1T];
-#pragma unroll
-            for (int t = 0; t < H1T; ++t) in[t] = ld_act(buf(E_G2), t, cc, qq);
-            const f32x4 pre = mmW<H1T, NK1>(fW6, in, zero4());
-            const f32x4 mA = mask_to_f32(mw);
-            const float hinv_s2 = 0.5f * inv_s2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = fast_sigmoid(pre[j]);
-                const float diff = xh - xv[j];
-                const float t = diff * diff * hinv_s2 + half_lv;
-                // the complement counts real rows and REAL columns only: a padding column has a zero mask byte too
-                const float mI = (ok && 16 * w + 4 * qq + j < a.d_real) ? 1.f - mA[j] : 0.f;
-                S_A += mA[j] * t;
-                S_I += mI * t;
-                SQ += mI * diff * diff;
-                CNT += mI;
-            }
-        }
-    }
-    // ================================================================ the tile's record
-    const float s[EVAL_TERMS] = {S_A, S_I, SQ, CNT, KL};
-#pragma unroll
-    for (int i = 0; i < EVAL_TERMS; ++i) {
-        const float v = wave_sum_dpp(s[i]);
-        if (lane == 0) red[w * EVAL_TERMS + i] = v;
-    }
-    lds_barrier();
-    if (threadIdx.x < EVAL_TERMS) {
-        double t = 0.0;
-        for (int k = 0; k < WAVES; ++k) t += (double)red[k * EVAL_TERMS + threadIdx.x];
-        rec[threadIdx.x] = t;
-    }
+    constexpr int OUT = OUT_SUMS;
+    float* const out = nullptr;
+    const long sout = 0;
+#include "vpc_evalsmall_body.h"
+}
+
+// The same forward, x_hat kept: MODE 0 writes x_hat[g][draw row][0..d_real), MODE 1 (x_hat[T] - x[T])^2 of the target column
+// T = d_real - 1 per draw row (the M passes of active_learning_func's imputation and of its target MSE, evaluate.py:390-414).
+constexpr int IMPUTE_LDS = E_COUNT * SBUF * 4;
+static_assert(2 * IMPUTE_LDS <= 163840, "two workgroups per CU");
+struct ImputeArgs {
+    EvalArgs e;   // (part unused)
+    float* out;   // member 0's [R][d_real] (MODE 0) or [R] (MODE 1)
+    long sout;    // member stride in floats
+};
+template <int DT, int MODE>
+__global__ __launch_bounds__(THREADS) void impute_small_kernel(ImputeArgs ia) {
+    constexpr int OUT = MODE == 0 ? OUT_XHAT : OUT_SQERR;
+    const EvalArgs& a = ia.e;
+    float* const out = ia.out;
+    const long sout = ia.sout;
+#include "vpc_evalsmall_body.h"
 }
 
 // ---- tiles -> batches -> passes -> out[g][4]
@@ -272,54 +133,137 @@ __global__ __launch_bounds__(RED_WAVES * 64) void eval_reduce_multi_kernel(EvalR
     }
 }
 
+// ---- out[g * out_stride] = mean of sq[g][0..R), blockIdx.y = member: fp64 in a fixed order (thread t sums rows t, t + 512, ..; a
+// butterfly per wave; the waves in order)
+__global__ __launch_bounds__(RED_WAVES * 64) void target_mse_multi_kernel(const float* __restrict__ sq, long ssq, long R,
+                                                                          float* __restrict__ out, long out_stride) {
+    __shared__ double tot[RED_WAVES];
+    const unsigned mem = blockIdx.y;
+    const float* s = sq + mem * ssq;
+    double v = 0.0;
+    for (long r = threadIdx.x; r < R; r += RED_WAVES * 64) v += (double)s[r];
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) tot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < RED_WAVES; ++k) t += tot[k];
+        out[mem * out_stride] = (float)(t / (double)R);
+    }
+}
+
 }  // namespace vpc
 
 using namespace vpc;
+
+namespace {
+// the checks and the argument record the two forward entries share (everything but where the result goes)
+int eval_forward_args(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                      const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                      unsigned long long offset, float x_logvar, const long* strides, int d, int d_real, int L, int max_blocks,
+                      EvalArgs& a) {
+    if (!x || !mask || !enc_img || !dec_img || !members || !tiles || !strides) return VPC_ERR_ARG;
+    if (G < 1 || G > 65535 || n_tiles < 1 || N < 1 || R < 1 || max_blocks < 0) return VPC_ERR_ARG;
+    if (!draw && !eps) return VPC_ERR_ARG;
+    if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (d_real < 1 || d_real > d || dt_for(d_real) != dt_for(d)) return VPC_ERR_ARG;
+    if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img) || !aligned16(eps)) return VPC_ERR_ARG;
+    if ((uintptr_t)mask % 4 || (uintptr_t)tiles % 8) return VPC_ERR_ARG;
+    const long sx = strides[VPC_MS_X], sm = strides[VPC_MS_MASK], seps = strides[VPC_MS_EPS], simg = strides[VPC_MS_IMG];
+    // every member's slice inside its stride, 16-byte (masks: 4-byte) aligned; the read-only inputs may be shared (stride 0)
+    if ((sx != 0 && sx < N * (long)d) || sx % 4 || (sm != 0 && sm < N * (long)d) || sm % 4) return VPC_ERR_ARG;
+    if (!draw && ((seps != 0 && seps < R * 16) || seps % 4)) return VPC_ERR_ARG;
+    if (simg <= 0 || simg % 4) return VPC_ERR_ARG;
+    a = EvalArgs{};
+    a.x = x; a.mask = mask; a.eps = draw ? nullptr : eps; a.enc_img = enc_img; a.dec_img = dec_img; a.members = members;
+    a.tiles = tiles;
+    a.sx = sx; a.sm = sm; a.seps = draw ? 0 : seps; a.simg = simg;
+    a.N = N; a.R = R; a.offset = offset; a.x_logvar = x_logvar; a.d = d; a.d_real = d_real; a.L = L; a.draw = draw ? 1 : 0;
+    return VPC_OK;
+}
+
+// The grid is (tiles of the chunk, G): consecutive workgroups are tiles of one member, so the workgroups in flight read one or two
+// members' images.  A launch holds at most max_blocks workgroups (0: VPC_EVAL_MAX_BLOCKS); the tile table is walked in chunks:
+// launch(first tile, grid) starts one of them.
+template <class Launch>
+int eval_chunks(long n_tiles, int G, int max_blocks, Launch launch) {
+    const long cap = max_blocks ? max_blocks : VPC_EVAL_MAX_BLOCKS;
+    const long per = cap / G > 0 ? cap / G : 1;
+    for (long t0 = 0; t0 < n_tiles; t0 += per) {
+        const long nt = n_tiles - t0 < per ? n_tiles - t0 : per;
+        if (!launch(t0, dim3((unsigned)nt, (unsigned)G))) return VPC_ERR_HIP;
+        if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
+    }
+    return VPC_OK;
+}
+}  // namespace
 
 extern "C" int vpc_eval_small_multi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
                                         const float* dec_img, const VpcMember* members, int G, const long long* tiles,
                                         long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
                                         double* part, const long* strides, int d, int d_real, int L, int max_blocks,
                                         void* stream) {
-    if (!x || !mask || !enc_img || !dec_img || !members || !tiles || !part || !strides) return VPC_ERR_ARG;
-    if (G < 1 || G > 65535 || n_tiles < 1 || N < 1 || R < 1 || max_blocks < 0) return VPC_ERR_ARG;
-    if (!draw && !eps) return VPC_ERR_ARG;
-    if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
-    if (d_real < 1 || d_real > d || dt_for(d_real) != dt_for(d)) return VPC_ERR_ARG;
-    if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img) || !aligned16(eps)) return VPC_ERR_ARG;
-    if ((uintptr_t)mask % 4 || (uintptr_t)tiles % 8 || (uintptr_t)part % 8) return VPC_ERR_ARG;
-    const long sx = strides[VPC_MS_X], sm = strides[VPC_MS_MASK], seps = strides[VPC_MS_EPS], simg = strides[VPC_MS_IMG],
-               sp = strides[VPC_MS_LOSS];
-    // every member's slice inside its stride, 16-byte (masks: 4-byte) aligned; the read-only inputs may be shared (stride 0)
-    if ((sx != 0 && sx < N * (long)d) || sx % 4 || (sm != 0 && sm < N * (long)d) || sm % 4) return VPC_ERR_ARG;
-    if (!draw && ((seps != 0 && seps < R * 16) || seps % 4)) return VPC_ERR_ARG;
-    if (simg <= 0 || simg % 4 || sp < n_tiles * EVAL_TERMS) return VPC_ERR_ARG;
-    EvalArgs a{};
-    a.x = x; a.mask = mask; a.eps = draw ? nullptr : eps; a.enc_img = enc_img; a.dec_img = dec_img; a.members = members;
-    a.tiles = tiles; a.part = part;
-    a.sx = sx; a.sm = sm; a.seps = draw ? 0 : seps; a.simg = simg; a.spart = sp;
-    a.N = N; a.R = R; a.offset = offset; a.x_logvar = x_logvar; a.d = d; a.d_real = d_real; a.L = L; a.draw = draw ? 1 : 0;
-    // the grid is (tiles of the chunk, G): consecutive workgroups are tiles of one member, so the workgroups in flight read one or
-    // two members' images.  A launch holds at most max_blocks workgroups (0: VPC_EVAL_MAX_BLOCKS); the tile table is walked in chunks.
-    const long cap = max_blocks ? max_blocks : VPC_EVAL_MAX_BLOCKS;
-    const long per = cap / G > 0 ? cap / G : 1;
+    if (!part || (uintptr_t)part % 8) return VPC_ERR_ARG;
+    EvalArgs a;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, a);
+    if (rc != VPC_OK) return rc;
+    if (strides[VPC_MS_LOSS] < n_tiles * EVAL_TERMS) return VPC_ERR_ARG;
+    a.part = part;
+    a.spart = strides[VPC_MS_LOSS];
     hipStream_t s = (hipStream_t)stream;
-    for (long t0 = 0; t0 < n_tiles; t0 += per) {
-        const long nt = n_tiles - t0 < per ? n_tiles - t0 : per;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
         a.tile0 = t0;
-        const dim3 grid((unsigned)nt, (unsigned)G);
 #define VPC_CASE(T)                                                                                        \
     case T: {                                                                                              \
         auto kern = eval_small_kernel<T>;                                                                  \
-        if (!lds_attr_done(reinterpret_cast<const void*>(kern), EVAL_LDS)) return VPC_ERR_HIP;             \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), EVAL_LDS)) return false;                   \
         hipLaunchKernelGGL(kern, grid, dim3(THREADS), EVAL_LDS, s, a);                                     \
-        break;                                                                                             \
+        return true;                                                                                       \
     }
-        switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) default: return VPC_ERR_SHAPE; }
+        switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
 #undef VPC_CASE
-        if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
+        return false;
+    });
+}
+
+extern "C" int vpc_impute_small_multi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                          const float* dec_img, const VpcMember* members, int G, const long long* tiles,
+                                          long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
+                                          int mode, float* out, long out_stride, const long* strides, int d, int d_real, int L,
+                                          int max_blocks, void* stream) {
+    if (!out || (uintptr_t)out % 4 || mode < 0 || mode > 1) return VPC_ERR_ARG;
+    ImputeArgs ia;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, ia.e);
+    if (rc != VPC_OK) return rc;
+    if (out_stride < (mode == 0 ? R * (long)d_real : R)) return VPC_ERR_ARG;  // a draw row < R is the only row written
+    ia.out = out;
+    ia.sout = out_stride;
+    hipStream_t s = (hipStream_t)stream;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
+        ia.e.tile0 = t0;
+#define VPC_CASE(T, MODE)                                                                                  \
+    case 2 * T + MODE: {                                                                                   \
+        auto kern = impute_small_kernel<T, MODE>;                                                          \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), IMPUTE_LDS)) return false;                 \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), IMPUTE_LDS, s, ia);                                  \
+        return true;                                                                                       \
     }
-    return VPC_OK;
+        switch (2 * dt_for(d) + mode) {
+            VPC_CASE(1, 0) VPC_CASE(2, 0) VPC_CASE(4, 0) VPC_CASE(8, 0) VPC_CASE(1, 1) VPC_CASE(2, 1) VPC_CASE(4, 1) VPC_CASE(8, 1)
+        }
+#undef VPC_CASE
+        return false;
+    });
+}
+
+extern "C" int vpc_target_mse_multi(const float* sq, long sq_stride, long R, int G, float* out, long out_stride, void* stream) {
+    if (!sq || !out || (uintptr_t)sq % 4 || (uintptr_t)out % 4) return VPC_ERR_ARG;
+    if (G < 1 || G > 65535 || R < 1 || sq_stride < R || out_stride < 1) return VPC_ERR_ARG;
+    hipLaunchKernelGGL(target_mse_multi_kernel, dim3(1, (unsigned)G), dim3(RED_WAVES * 64), 0, (hipStream_t)stream, sq, sq_stride,
+                       R, out, out_stride);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
 extern "C" int vpc_eval_reduce_multi(const double* part, const long long* batches, long n_batches, const long long* passes,

@@ -25,6 +25,10 @@
 //               relu(im_u A_u + C_u) to agg, so the update is W1 relu(im_u A_u + C_u): ceil(K/4) MFMA k-steps per h1
 //               tile, each lane building its B value with one FMA and one max.  Prep evaluates the base agg per
 //               (n, m, chain), target adjustments included, and W1 agg + b1.
+//
+// The plain model at d <= 128 also runs with a member dimension (vpc_reward_matrix_multi: blockIdx.y = member, the kernel bodies of
+// vpc_reward_prep_body.h / vpc_reward_chain_body.h on the member's operands), followed by the acquisition itself
+// (acquire_multi_kernel: argmax per row, mask byte, action; evaluate.py:435-440): the loop of G models without a host round trip.
 #include "vpc_device.h"
 #include "vpc_abi_internal.h"
 
@@ -54,177 +58,7 @@ __global__ __launch_bounds__(128) void reward_prep_kernel(const float* __restric
                                                           float* __restrict__ pre, float* __restrict__ W1T,
                                                           int* __restrict__ cand, float* __restrict__ R, int n, int d,
                                                           int M, int Mp, int K) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) cand[(long)n * d] = 0;  // work counter of reward_chain_kernel<1>
-    const int f = threadIdx.x;  // 0..127: hidden unit (100 = constant, 101..111 = padding), >= 112 idle
-    const int pf = f < H1P ? pos1_full(f) : 0;
-    const int din = KIND == RK_DENSE_MASK ? 2 * d : d;  // row pitch of a dense W1
-    if (blockIdx.x >= (unsigned)n) {
-        if constexpr (KIND == RK_POINTNET) {
-            // one block: the A fragments of W1 [100][K] for the update MFMAs of reward_chain_kernel,
-            //   W1T[((g * 7 + t) * 64 + lane) * 4 + j] = W1[unit at position 16 t + (lane & 15)][16 g + 4 j + (lane >> 4)]
-            // (zero for padding units, the constant unit and k >= K)
-            if (f < H1P) {
-                const int t = pf >> 4, mr = pf & 15;
-                for (int k = 0; k < PN_MAX_K; ++k) {
-                    const int s = k >> 2, g = s >> 2, j = s & 3, ln = mr + 16 * (k & 3);
-                    W1T[((g * H1T + t) * 64 + ln) * 4 + j] = (f < H1 && k < K) ? W1[f * K + k] : 0.f;
-                }
-            }
-        } else {  // trailing blocks: W1T[u][f] = W1[f][u] (and W1T[d + u][f] = W1[f][d + u]), 8 input columns per block
-            const int u0 = 8 * ((int)blockIdx.x - n);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int u = u0 + k;
-                if (u < d && f < H1P) {
-                    W1T[u * H1P + pf] = f < H1 ? W1[f * din + u] : 0.f;
-                    if (KIND == RK_DENSE_MASK) W1T[(d + u) * H1P + pf] = f < H1 ? W1[f * din + d + u] : 0.f;
-                }
-            }
-        }
-        return;
-    }
-    const int r = blockIdx.x, T = d - 1;
-    // the row's candidates: cand[r][0] = their number, cand[r][1 + k] = the k-th feature u < d - 1 that is not observed yet, in
-    // ascending order; observed features get the reference's R = -1e4 here (evaluate.py:424-433)
-    if constexpr (!WIDE) {
-        __shared__ int cnt0;
-        const int u = threadIdx.x;
-        const bool isc = u < T && !mask[(long)r * d + u];
-        const unsigned long long bal = __ballot(isc);
-        if (threadIdx.x == 0) cnt0 = __popcll(bal);
-        __syncthreads();
-        const int before = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull)) + (threadIdx.x >= 64 ? cnt0 : 0);
-        int* cr = cand + (long)r * d;
-        if (isc) cr[1 + before] = u;
-        if (u < T && !isc) R[(long)r * T + u] = -1e4f;
-        if (threadIdx.x == 127) cr[0] = before + (isc ? 1 : 0);
-        __syncthreads();
-    } else {  // the same ballot over 128-feature chunks, `run` candidates before the chunk
-        __shared__ int cnt0, tot;
-        int* cr = cand + (long)r * d;
-        int run = 0;
-        for (int c0 = 0; c0 < T; c0 += 128) {
-            const int u = c0 + threadIdx.x;
-            const bool isc = u < T && !mask[(long)r * d + u];
-            const unsigned long long bal = __ballot(isc);
-            if (threadIdx.x == 0) cnt0 = __popcll(bal);
-            __syncthreads();
-            const int before = run + __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull)) + (threadIdx.x >= 64 ? cnt0 : 0);
-            if (isc) cr[1 + before] = u;
-            if (u < T && !isc) R[(long)r * T + u] = -1e4f;
-            if (threadIdx.x == 127) tot = before + (isc ? 1 : 0);
-            __syncthreads();
-            run = tot;
-        }
-        if (threadIdx.x == 0) cr[0] = run;
-    }
-    if constexpr (KIND == RK_POINTNET) {
-        // agg_X[k] = sum_{j < T} mask_j relu(x_j A[k][j] + C[k][j]): each wave takes every second k, lanes over j
-        __shared__ float aggx[PN_MAX_K], aT[PN_MAX_K], cT[PN_MAX_K], agg[2][PN_MAX_K];
-        {
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-            for (int k = wv; k < K; k += 2) {
-                const float* A = AC + (long)k * d;
-                const float* Cc = AC + (long)(K + k) * d;
-                float s = 0.f;
-                for (int j = lane; j < T; j += 64)
-                    if (mask[(long)r * d + j]) s += fmaxf(fmaf(x[(long)r * d + j], A[j], Cc[j]), 0.f);
-                s = wave_sum_dpp(s);
-                if (lane == 0) {
-                    aggx[k] = s;
-                    aT[k] = A[T];
-                    cT[k] = Cc[T];
-                }
-            }
-        }
-        float w[PN_MAX_K];
-#pragma unroll
-        for (int k = 0; k < PN_MAX_K; ++k) w[k] = (f < H1 && k < K) ? W1[f * K + k] : 0.f;
-        const float bias = f < H1 ? b1[f] : 0.f;
-        const float xT = x[(long)r * d + T], mT = mask[(long)r * d + T] ? 1.f : 0.f;
-        __syncthreads();
-        for (int m = 0; m < Mp; ++m) {
-            if (m < M) {  // (uniform)
-                if (f < K) {
-                    const float carry = m == 0 ? xT : im[((long)(m - 1) * n + r) * d + T];
-                    const float imT = im[((long)m * n + r) * d + T];
-                    agg[0][f] = aggx[f] + mT * fmaxf(fmaf(carry, aT[f], cT[f]), 0.f);
-                    agg[1][f] = aggx[f] + fmaxf(fmaf(imT, aT[f], cT[f]), 0.f);
-                }
-                __syncthreads();
-            }
-            float p1 = 0.f, p2 = 0.f;
-            if (m < M && f < H1) {
-                p1 = p2 = bias;
-#pragma unroll
-                for (int k = 0; k < PN_MAX_K; ++k)
-                    if (k < K) {
-                        p1 = fmaf(w[k], agg[0][k], p1);
-                        p2 = fmaf(w[k], agg[1][k], p2);
-                    }
-            }
-            if (f == H1) p1 = p2 = 1.f;
-            if (f < H1P) {
-                float* o = pre + (((long)r * Mp + m) * 2) * H1P;
-                o[pf] = p1;
-                o[H1P + pf] = p2;
-            }
-            if (m < M) __syncthreads();  // agg is rewritten by the next sample
-        }
-        return;
-    } else {
-        // base[f] = b1[f] + sum_i W1[f][i] in[r][i], in = x * mask (| mask): each wave takes every second unit, lanes over i (the
-        // rows of W1 are read coalesced; one thread per unit walked its row with a stride of d floats: 128 dependent loads,
-        // 35 us for this launch)
-        __shared__ float base_sh[H1P];
-        {
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-            for (int i0 = 0; i0 < (WIDE ? din : 1); i0 += 128) {
-                float xm[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int i = i0 + lane + 64 * k;
-                    if (KIND == RK_DENSE_MASK && i >= d)
-                        xm[k] = i < din ? (mask[(long)r * d + i - d] ? 1.f : 0.f) : 0.f;
-                    else
-                        xm[k] = i < d ? x[(long)r * d + i] * (mask[(long)r * d + i] ? 1.f : 0.f) : 0.f;
-                }
-                for (int u = wv; u < H1; u += 2) {
-                    float sacc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int i = i0 + lane + 64 * k;
-                        if (i < din) sacc += W1[u * din + i] * xm[k];
-                    }
-                    sacc = wave_sum_dpp(sacc);
-                    if (lane == 0) base_sh[u] = (i0 == 0 ? b1[u] : base_sh[u]) + sacc;
-                }
-            }
-        }
-        __syncthreads();
-        if (f >= H1P) return;
-        float base = 0.f, wT = 0.f, wTm = 0.f;
-        if (f < H1) {
-            base = base_sh[f];
-            wT = W1[f * din + T];
-            if (KIND == RK_DENSE_MASK) wTm = W1[f * din + d + T];
-        }
-        const float xT = x[(long)r * d + T], mT = mask[(long)r * d + T] ? 1.f : 0.f;
-        for (int m = 0; m < Mp; ++m) {
-            float p1 = 0.f, p2 = 0.f;
-            if (m < M) {
-                const float carry = m == 0 ? xT : im[((long)(m - 1) * n + r) * d + T];
-                p1 = base + wT * mT * (carry - xT);
-                p2 = base + wT * (im[((long)m * n + r) * d + T] - xT * mT);
-                if (KIND == RK_DENSE_MASK) p2 += wTm * (1.f - mT);
-            }
-            if (f == H1) p1 = p2 = 1.f;
-            if (f > H1) p1 = p2 = 0.f;
-            float* o = pre + (((long)r * Mp + m) * 2) * H1P;
-            o[pf] = p1;
-            o[H1P + pf] = p2;
-        }
-    }
+#include "vpc_reward_prep_body.h"
 }
 
 struct RewardArgs {
@@ -250,141 +84,85 @@ struct RewardArgs {
 constexpr int RW_CH = 4;
 template <int KIND, int MODE>
 __global__ __launch_bounds__(RW_THREADS) void reward_chain_kernel(RewardArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    load_image(lds, a.w23, W23_FLOATS);
-    const float* W2 = lds;
-    const float* W3 = lds + H2P * 128;
-    const float* W1F = lds + W23_FLOATS;  // POINTNET: the W1 fragments of the groups g < ceil(K / 16)
-    if (KIND == RK_POINTNET) load_image(lds + W23_FLOATS, a.W1T, (a.K + 15) / 16 * PN_FRAG);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int nch = (a.d - 1 + RW_CH - 1) / RW_CH;  // chunks per row (upper bound)
-    const long nitems = MODE == 0 ? a.n : (long)a.n * nch;
-    const float invM = 1.f / (float)a.M;
+#include "vpc_reward_chain_body.h"
+}
 
-    long item = (long)blockIdx.x * RW_WAVES + w;
-    auto next = [&]() {
-        if (MODE == 0) { item += (long)gridDim.x * RW_WAVES; return; }
-        int v = 0;
-        if (lane == 0) v = atomicAdd(a.next_item, 1);
-        item = (long)gridDim.x * RW_WAVES + __builtin_amdgcn_readfirstlane(v);  // (the first round is the launch's own grid)
-    };
-    for (; item < nitems; next()) {
-        const int r = MODE == 0 ? (int)item : (int)(item / nch);
-        const int ch = MODE == 0 ? 0 : (int)(item % nch);
-        int ncand = 0;
-        const int* cl = a.cand + (long)r * a.d + 1 + RW_CH * ch;
-        if (MODE == 1) {
-            ncand = a.cand[(long)r * a.d] - RW_CH * ch;
-            if (ncand <= 0) continue;
-            if (ncand > RW_CH) ncand = RW_CH;
-        }
-        const int total = MODE == 0 ? a.Mp : ncand * a.M;  // columns of this item
-        float acc[RW_CH];
+// ---- the member dimension (plain model, d <= 128): blockIdx.y = member, every operand of member g `g * stride` elements after
+// member 0's (stride 0: shared).  A workgroup serves ONE member - its LDS holds that member's [W2 | W3] - and runs the bodies above
+// on the member's operands with its own candidate lists and work counter, so R[g] is what vpc_reward_matrix gives on them.
+struct RewardMultiArgs {
+    const float *x, *im, *W1, *b1, *w23;
+    const uint8_t* mask;
+    float *pre, *stat, *w1t, *R;
+    long sx, sm, sim, sparam, simg, spre, sstat, sw1t, sR;
+    int n, d, L, M, Mp;
+};
+
+__device__ __forceinline__ RewardArgs reward_member_args(const RewardMultiArgs& m, unsigned g) {
+    float* w1t = m.w1t + g * m.sw1t;
+    int* cand = reinterpret_cast<int*>(w1t + (long)m.d * H1P);
+    return RewardArgs{m.w23 + g * m.simg, m.pre + g * m.spre, w1t, nullptr, m.im + g * m.sim, m.mask + g * m.sm, cand,
+                      cand + (long)m.n * m.d, m.stat + g * m.sstat, m.R + g * m.sR, m.n, m.d, m.L, m.M, m.Mp, 0};
+}
+
+__global__ __launch_bounds__(128) void reward_prep_multi_kernel(RewardMultiArgs m) {
+    constexpr int KIND = RK_DENSE;
+    constexpr bool WIDE = false;
+    const unsigned g = blockIdx.y;
+    const float* __restrict__ x = m.x + g * m.sx;
+    const uint8_t* __restrict__ mask = m.mask + g * m.sm;
+    const float* __restrict__ im = m.im + g * m.sim;
+    const float* __restrict__ W1 = m.W1 + g * m.sparam;
+    const float* __restrict__ b1 = m.b1 + g * m.sparam;
+    const float* __restrict__ AC = nullptr;
+    float* __restrict__ pre = m.pre + g * m.spre;
+    float* __restrict__ W1T = m.w1t + g * m.sw1t;
+    int* __restrict__ cand = reinterpret_cast<int*>(W1T + (long)m.d * H1P);
+    float* __restrict__ R = m.R + g * m.sR;
+    const int n = m.n, d = m.d, M = m.M, Mp = m.Mp, K = 0;
+#include "vpc_reward_prep_body.h"
+}
+
+template <int MODE>
+__global__ __launch_bounds__(RW_THREADS) void reward_chain_multi_kernel(RewardMultiArgs m) {
+    constexpr int KIND = RK_DENSE;
+    const RewardArgs a = reward_member_args(m, blockIdx.y);
+#include "vpc_reward_chain_body.h"
+}
+
+// ---- acquire: per (member, row) the lowest index among the maxima of R[g][row][0..d-1) (torch.argmax on finite input; evaluate.py:
+// 435-440), revealed in the member's mask(s) and written to the step's slot of the action history.  One wave per row.
+struct AcquireArgs {
+    const float* R;
+    uint8_t *mask, *mask2;  // [n][pitch] bytes; mask2 (may be NULL): the same mask at a second row pitch
+    int* action;            // member 0's slot of row 0; rows a_pitch ints apart
+    long sR, sm, sm2, sa;
+    int n, d, pitch, pitch2, a_pitch;
+};
+
+__global__ __launch_bounds__(RW_THREADS) void acquire_multi_kernel(AcquireArgs a) {
+    const unsigned g = blockIdx.y;
+    const int lane = threadIdx.x & 63, row = blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
+    if (row >= a.n) return;
+    const int T = a.d - 1;
+    const float* r = a.R + g * a.sR + (long)row * T;
+    float best = -INFINITY;
+    int bi = T;
+    for (int u = lane; u < T; u += 64) {  // (ascending: the first of equal values stays)
+        const float v = r[u];
+        if (v > best) { best = v; bi = u; }
+    }
 #pragma unroll
-        for (int k = 0; k < RW_CH; ++k) acc[k] = 0.f;
-        for (int t0 = 0; t0 < total; t0 += 16) {
-            asm volatile("" ::: "memory");
-            int cc = c, qq = q;
-            launder(cc, qq);
-            const int f = t0 + c;
-            const bool live = MODE == 0 ? f < a.M : f < total;
-            int kk = 0, m = f;
-            if (MODE == 1) {
-                kk = live ? f / a.M : 0;
-                m = live ? f - kk * a.M : 0;
-            }
-            const int u = MODE == 1 ? cl[kk] : 0;
-            const float imu = (MODE == 1 && live) ? a.im[((long)m * a.n + r) * a.d + u] : 0.f;
-            const float* pp = a.pre + (((long)r * a.Mp + m) * 2) * H1P + 4 * q;
-            f32x4 h1[2][H1T];
-            if constexpr (KIND == RK_POINTNET && MODE == 1) {
-                // upd = W1 relu(im_u A_u + C_u), shared by both chains: A = W1 fragments (LDS), B = lane (c, q)'s value of
-                // k = 16 g + 4 j + q for its column's candidate
-                f32x4 upd[H1T];
-#pragma unroll
-                for (int t = 0; t < H1T; ++t) upd[t] = zero4();
-                const float* Au = a.AC + u;
-                const float* Cu = a.AC + (long)a.K * a.d + u;
-#pragma unroll
-                for (int g = 0; g < PN_MAX_K / 16; ++g) {
-                    if (16 * g >= a.K) break;  // (uniform)
-                    float bv[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int k = 16 * g + 4 * j + q;
-                        bv[j] = k < a.K ? fmaxf(fmaf(imu, Au[(long)k * a.d], Cu[(long)k * a.d]), 0.f) : 0.f;
-                    }
-                    f32x4 af[H1T];
-#pragma unroll
-                    for (int t = 0; t < H1T; ++t) af[t] = *reinterpret_cast<const f32x4*>(W1F + ((g * H1T + t) * 64 + lane) * 4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (16 * g + 4 * j < a.K)  // (uniform) k-steps past K multiply zeros
-#pragma unroll
-                            for (int t = 0; t < H1T; ++t) upd[t] = VPC_MFMA(af[t][j], bv[j], upd[t]);
-                }
-#pragma unroll
-                for (int chn = 0; chn < 2; ++chn)
-#pragma unroll
-                    for (int t = 0; t < H1T; ++t)
-                        h1[chn][t] = relu4(*reinterpret_cast<const f32x4*>(pp + chn * H1P + 16 * t) + upd[t]);
-            } else {
-#pragma unroll
-                for (int chn = 0; chn < 2; ++chn)
-#pragma unroll
-                    for (int t = 0; t < H1T; ++t) {
-                        f32x4 v = *reinterpret_cast<const f32x4*>(pp + chn * H1P + 16 * t);
-                        if (MODE == 1) v += *reinterpret_cast<const f32x4*>(a.W1T + (long)u * H1P + 16 * t + 4 * q) * imu;
-                        if (MODE == 1 && KIND == RK_DENSE_MASK)  // revealing u also sets its mask input to 1
-                            v += *reinterpret_cast<const f32x4*>(a.W1T + ((long)a.d + u) * H1P + 16 * t + 4 * q);
-                        h1[chn][t] = relu4(v);
-                    }
-            }
-            f32x4 h2[2][H2T];
-#pragma unroll
-            for (int t = 0; t < H2T; ++t) {
-                f32x4 o[2] = {zero4(), zero4()};
-                tile_fwd_nb<H1T, 128, 2, NK1>(W2, t, h1, o, cc, qq);
-                h2[0][t] = relu4(o[0]);
-                h2[1][t] = relu4(o[1]);
-            }
-            f32x4 mu[2] = {zero4(), zero4()}, lv[2] = {zero4(), zero4()};
-            tile_fwd_nb<H2T, 64, 2, NK2>(W3, 0, h2, mu, cc, qq);
-            tile_fwd_nb<H2T, 64, 2, NK2>(W3, 1, h2, lv, cc, qq);
-            float* st = a.stat + ((long)r * a.Mp + m) * STAT + 4 * q;
-            if (MODE == 0) {
-                *reinterpret_cast<f32x4*>(st) = mu[0];
-                *reinterpret_cast<f32x4*>(st + 16) = lv[0];
-                *reinterpret_cast<f32x4*>(st + 32) = mu[1];
-                *reinterpret_cast<f32x4*>(st + 48) = lv[1];
-            } else {
-                float val = 0.f;
-#pragma unroll
-                for (int chn = 0; chn < 2; ++chn) {
-                    const f32x4 ma = *reinterpret_cast<const f32x4*>(st + 32 * chn);
-                    const f32x4 la = *reinterpret_cast<const f32x4*>(st + 32 * chn + 16);
-                    float kl = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float dm = mu[chn][j] - ma[j];
-                        const float t = dm * dm * expf(-0.5f * la[j]) + expf(lv[chn][j] - la[j]) - 1.f - lv[chn][j] + la[j];
-                        kl += (4 * q + j < a.L) ? t : 0.f;
-                    }
-                    kl = live ? 0.5f * kl : 0.f;
-                    val += chn == 0 ? kl : -kl;
-                }
-#pragma unroll
-                for (int k = 0; k < RW_CH; ++k) acc[k] += kk == k ? val : 0.f;
-            }
-        }
-        if (MODE == 1) {
-#pragma unroll
-            for (int k = 0; k < RW_CH; ++k) {
-                const float sacc = wave_sum(acc[k]);
-                if (lane == 0 && k < ncand) a.R[(long)r * (a.d - 1) + cl[k]] = sacc * invM;
-            }
-        }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (bi >= T) bi = 0;  // (no value above -inf: argmax's answer, and never an index outside the row)
+    if (lane == 0) {
+        a.mask[g * a.sm + (long)row * a.pitch + bi] = 1;
+        if (a.mask2) a.mask2[g * a.sm2 + (long)row * a.pitch2 + bi] = 1;
+        a.action[g * a.sa + (long)row * a.a_pitch] = bi;
     }
 }
 
@@ -471,4 +249,72 @@ extern "C" int vpc_reward_matrix_ex(int kind, const float* x, const uint8_t* mas
     if (d <= MAX_D)  // the plain path's own instantiation
         return reward_launch<RK_DENSE, false>(x, mask, im, W1, b1, nullptr, 0, w23_img, pre, stat, w1t, R, n, d, L, M, s);
     return reward_launch<RK_DENSE, true>(x, mask, im, W1, b1, nullptr, 0, w23_img, pre, stat, w1t, R, n, d, L, M, s);
+}
+
+// ---- member dimension ------------------------------------------------------------------------------------------------------------
+// Workspace floats PER MEMBER (each a multiple of 4, so that member slices stay 16-byte aligned).
+extern "C" int vpc_reward_scratch_multi(int n, int d, int M, long* pre_floats, long* stat_floats, long* w1t_floats) {
+    long w1t = 0;
+    const int rc = vpc_reward_scratch(n, d, M, pre_floats, stat_floats, &w1t);
+    if (rc != VPC_OK) return rc;
+    if (w1t_floats) *w1t_floats = (w1t + 3) / 4 * 4;
+    return VPC_OK;
+}
+
+extern "C" int vpc_reward_matrix_multi(const float* x, const uint8_t* mask, const float* im, const float* W1, const float* b1,
+                                       const float* enc_img, float* pre, float* stat, float* w1t, float* R, int G, int chunk,
+                                       const long* strides, int n, int d, int L, int M, void* stream) {
+    if (!x || !mask || !im || !W1 || !b1 || !enc_img || !pre || !stat || !w1t || !R || !strides) return VPC_ERR_ARG;
+    if (n <= 0 || M <= 0 || G < 1 || chunk < 1 || chunk > 65535) return VPC_ERR_ARG;
+    if (d < 2 || d > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (!aligned16(pre) || !aligned16(stat) || !aligned16(w1t) || !aligned16(enc_img)) return VPC_ERR_ARG;
+    const long Mp = (M + 15) / 16 * 16, nd = (long)n * d;
+    const long sx = strides[VPC_RM_X], sm = strides[VPC_RM_MASK], sim = strides[VPC_RM_IM], sparam = strides[VPC_RM_PARAM],
+               simg = strides[VPC_RM_IMG], spre = strides[VPC_RM_PRE], sstat = strides[VPC_RM_STAT], sw1t = strides[VPC_RM_W1T],
+               sR = strides[VPC_RM_R];
+    // every member's slice inside its stride; x may be shared (stride 0); the image and workspace slices stay 16-byte aligned
+    if ((sx != 0 && sx < nd) || sm < nd || sim < (long)M * nd || sparam < (long)H1 * d + H1 || sR < (long)n * (d - 1))
+        return VPC_ERR_ARG;
+    if (simg <= 0 || simg % 4 || spre < (long)n * Mp * 2 * H1P || spre % 4 || sstat < (long)n * Mp * STAT || sstat % 4 ||
+        sw1t < (long)d * H1P + nd + 4 || sw1t % 4)
+        return VPC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = sizeof(float) * W23_FLOATS;
+    if (!lds_attr_done(reinterpret_cast<const void*>(reward_chain_multi_kernel<0>), lds)) return VPC_ERR_HIP;
+    if (!lds_attr_done(reinterpret_cast<const void*>(reward_chain_multi_kernel<1>), lds)) return VPC_ERR_HIP;
+    const long itemsB = (long)n * ((d - 1 + RW_CH - 1) / RW_CH);
+    // members [g0, g0 + gc) go through the workspaces (held for `chunk` members) one chunk after the other on the stream
+    for (int g0 = 0; g0 < G; g0 += chunk) {
+        const int gc = G - g0 < chunk ? G - g0 : chunk;
+        RewardMultiArgs m{x + g0 * sx, im + g0 * sim, W1 + g0 * sparam, b1 + g0 * sparam, enc_img + EncImg(dt_for(d)).oW2 + g0 * simg,
+                          mask + g0 * sm, pre, stat, w1t, R + g0 * sR, sx, sm, sim, sparam, simg, spre, sstat, sw1t, sR,
+                          n, d, L, M, (int)Mp};
+        // per member the grid of vpc_reward_matrix, the chunk's total held to the same 3 workgroups per CU (the hand-out order of
+        // the items is all that depends on it)
+        const long cap = ((long)num_cus() * 3 + gc - 1) / gc;
+        long gA = (n + RW_WAVES - 1) / RW_WAVES, gB = (itemsB + RW_WAVES - 1) / RW_WAVES;
+        if (gA > cap) gA = cap;
+        if (gB > cap) gB = cap;
+        hipLaunchKernelGGL(reward_prep_multi_kernel, dim3(n + (d + 7) / 8, gc), dim3(128), 0, s, m);
+        hipLaunchKernelGGL(reward_chain_multi_kernel<0>, dim3((unsigned)gA, gc), dim3(RW_THREADS), lds, s, m);
+        hipLaunchKernelGGL(reward_chain_multi_kernel<1>, dim3((unsigned)gB, gc), dim3(RW_THREADS), lds, s, m);
+        if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
+    }
+    return VPC_OK;
+}
+
+extern "C" int vpc_acquire_multi(const float* R, long R_stride, uint8_t* mask, long mask_stride, int mask_pitch, uint8_t* mask2,
+                                 long mask2_stride, int mask2_pitch, int* action, long action_stride, int action_pitch, int G,
+                                 int n, int d, void* stream) {
+    if (!R || !mask || !action || (uintptr_t)R % 4 || (uintptr_t)action % 4) return VPC_ERR_ARG;
+    if (G < 1 || G > 65535 || n < 1) return VPC_ERR_ARG;
+    if (d < 2 || d > MAX_D) return VPC_ERR_SHAPE;
+    if (R_stride < (long)n * (d - 1) || mask_pitch < d || mask_stride < (long)n * mask_pitch || action_pitch < 1 ||
+        action_stride < (long)(n - 1) * action_pitch + 1)
+        return VPC_ERR_ARG;
+    if (mask2 && (mask2_pitch < d || mask2_stride < (long)n * mask2_pitch)) return VPC_ERR_ARG;
+    AcquireArgs a{R, mask, mask2, action, R_stride, mask_stride, mask2_stride, action_stride, n, d, mask_pitch, mask2_pitch,
+                  action_pitch};
+    hipLaunchKernelGGL(acquire_multi_kernel, dim3((n + RW_WAVES - 1) / RW_WAVES, G), dim3(RW_THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }

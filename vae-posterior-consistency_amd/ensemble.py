@@ -25,6 +25,18 @@ around evaluate.py:136-297: M Monte-Carlo passes over the loaders, forward + los
 
     build_eval_tables            the tile / batch / pass tables of one (N, batch layout, M)
     EnsembleEvaluator            the call, the table cache, image freshness and the Philox offset of its draws
+
+and so does its active variable selection (active_learning.py follows every train() with active_learning_func,
+evaluate.py:300-511: per acquisition step M imputation forwards, the reward of every candidate, an argmax per row, M forwards for
+the target MSE), a fixed number of launches per step whatever G, with the loop's state on the device:
+
+    vpc_impute_small_multi_f32   the forward of vpc_eval_small_multi_f32, written instead of summed: x_hat, or the target's squared error
+    vpc_reward_matrix_multi      the three launches of vpc_reward_matrix with blockIdx.y = member (csrc/vpc_reward.hip)
+    vpc_acquire_multi            argmax per (member, row) -> mask byte, action
+    vpc_target_mse_multi         the information curve's next point per member
+
+    acquire_plan / acquire_draw_offsets   the shapes and the Philox offsets of a run, on the host alone
+    EnsembleAcquirer             the loop (run), one forward call (impute), one reward (reward)
 """
 from __future__ import annotations
 
@@ -521,3 +533,210 @@ class EnsembleEvaluator:
         per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
         self.launches = (T + per - 1) // per + 1
         return out
+
+
+# ------------------------------------------------------------------------------------------------ acquisition
+REWARD_WS_FLOATS = 64 << 20  # default bound of the reward workspaces of one member chunk (256 MB), as active.FLOW_REWARD_WS_FLOATS
+
+
+def acquire_plan(G, d, Ld, x_shape, M, repeats=1, max_steps=None, eps_shape=None):
+    """Shapes of one EnsembleAcquirer.run, checked on the host alone: -> (n, steps, forward calls of the run, draw rows per
+    call).  A repeat is 1 + 2 * steps forward calls: the curve's start, then per acquisition step the imputation and the
+    curve's next point."""
+    x_shape = tuple(x_shape)
+    if len(x_shape) not in (2, 3) or x_shape[-1] != d or (len(x_shape) == 3 and x_shape[0] != G):
+        raise L.VpcError(f"x: expected [n, {d}] or [{G}, n, {d}], got {x_shape}")
+    n = x_shape[-2]
+    if n < 1 or M < 1 or repeats < 1 or d < 2:
+        raise L.VpcError(f"run: n = {n}, M = {M}, repeats = {repeats}, obs_dim = {d}: each at least 1 (obs_dim 2)")
+    if max_steps is not None and max_steps < 0:
+        raise L.VpcError(f"max_steps {max_steps}")
+    steps = d - 1 if max_steps is None else min(int(max_steps), d - 1)
+    calls, R = repeats * (1 + 2 * steps), M * n
+    if eps_shape is not None:
+        eps_shape = tuple(eps_shape)
+        if eps_shape not in ((calls, R, Ld), (G, calls, R, Ld)):
+            raise L.VpcError(f"eps: expected [{calls}, {R}, {Ld}] or [{G}, {calls}, {R}, {Ld}] ({calls} forward calls = "
+                             f"{repeats} repeats x (1 + 2 x {steps} steps)), got {eps_shape}")
+    return n, steps, calls, R
+
+
+def acquire_draw_offsets(rng_offset, draw_rows, steps, repeats=1):
+    """The Philox offsets of a run's forward calls in issue order - successive eval_draw_counters(., draw_rows, LP), no rule of
+    its own - and the acquirer's rng_offset after the run."""
+    offs = []
+    for _ in range(repeats * (1 + 2 * steps)):
+        off, rng_offset = eval_draw_counters(rng_offset, draw_rows, LP)
+        offs.append(off)
+    return offs, rng_offset
+
+
+def reward_member_chunk(G, n, d, M, budget_floats=REWARD_WS_FLOATS, sizes=None):
+    """Members per pass through the reward workspaces so that they stay within `budget_floats` (at least one member)."""
+    per = sum(sizes if sizes is not None else ops.reward_scratch_multi(n, d, M))
+    return max(1, min(G, int(budget_floats) // per))
+
+
+class EnsembleAcquirer(EnsembleEvaluator):
+    """The acquisition loop of active_learning_func (evaluate.py:300-511) for G stackable members at once.  Per acquisition step,
+    whatever G:  vpc_impute_small_multi_f32 (mode 0: the M imputations `im` of every member) -> vpc_reward_matrix_multi (three
+    launches per member chunk: R) -> vpc_acquire_multi (argmax, mask, action) -> vpc_impute_small_multi_f32 (mode 1) +
+    vpc_target_mse_multi (the information curve's next point).  Masks, actions, rewards and the curve stay on the device: no host
+    sync inside a repeat.  Members, stacking, image freshness and the Philox offset are EnsembleEvaluator's.  Only the q pass is
+    computed (mask_p and the p pass reach no output of the loop, VAE.py:496-507)."""
+
+    def _setup(self, x, n, M):
+        """What every forward call of a run shares: member table on the device, tables, x at both row pitches, fresh images."""
+        lay, dev = self.lay, self.dev
+        d = lay.d
+        self.params = stack_models(self.models)  # (idempotent; a member moved since is stacked again)
+        tb, tiles_dev, _, _ = self.tables(n, n, M)
+        self.table.update(1, 0.0, 1.0, False, 0)  # (the loop reads the seeds only)
+        if self._table_version != self.table.version:
+            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
+            self._table_version = self.table.version
+        x = ops._f32c(x)
+        dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # the forward reads rows padded to 4 columns, the reward rows of d
+        xk = x if dk == d else pad_cols(self._pads, x, dk, 0, dev)
+        img0, simg = self._images()
+        return x, xk, dk, tiles_dev, tb.tiles.shape[0], img0, simg
+
+    def _forward(self, xk, maskk, dk, tiles_dev, T, img0, simg, n, R, eps_plane, seps, offset, mode, out, out_stride, max_blocks):
+        lay = self.lay
+        strides = [0] * 9  # VPC_MS_* of include/vpc.h
+        strides[0] = xk.stride(0) if xk.dim() == 3 else 0
+        strides[1], strides[3], strides[4] = maskk.stride(0), seps, simg
+        ops.impute_small_multi_f32(xk, maskk, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, self.G,
+                                   tiles_dev, T, n, R, eps_plane is None, offset, self.models[0]._x_logvar_value, mode, out,
+                                   out_stride, strides, dk, lay.d, lay.L, max_blocks)
+
+    def impute(self, x, mask, M, mode=0, *, eps=None, max_blocks=0):
+        """ONE forward call of the loop under a given mask [G, n, d] (or [n, d], shared): mode 0 -> x_hat of the M passes
+        [G, M, n, d] (`im`), mode 1 -> the target column's squared error per draw row [G, M n].  eps: [M n, L] or [G, M n, L],
+        or None: drawn at the next eval_draw_counters offset."""
+        G, lay = self.G, self.lay
+        d, Ld = lay.d, lay.L
+        n, _, _, R = acquire_plan(G, d, Ld, x.shape, M)
+        if eps is not None and tuple(eps.shape) not in ((R, Ld), (G, R, Ld)):
+            raise L.VpcError(f"eps: expected [{R}, {Ld}] or [{G}, {R}, {Ld}], got {tuple(eps.shape)}")
+        if tuple(mask.shape) not in ((n, d), (G, n, d)) or mode not in (0, 1):
+            raise L.VpcError(f"mask: expected [{n}, {d}] or [{G}, {n}, {d}], got {tuple(mask.shape)}; mode 0 or 1, got {mode}")
+        L.require_cuda(x, mask, eps)
+        x, xk, dk, tiles_dev, T, img0, simg = self._setup(x, n, M)
+        maskk = torch.zeros(G, n, dk, dtype=torch.uint8, device=self.dev)
+        maskk[:, :, :d].copy_(as_mask_u8(mask))
+        offset, plane, seps = 0, None, 0
+        if eps is None:
+            offset, self.rng_offset = eval_draw_counters(self.rng_offset, R, LP)
+        else:
+            plane = torch.zeros(*eps.shape[:-1], LP, device=self.dev)
+            plane[..., :Ld].copy_(eps)
+            seps = plane.stride(0) if plane.dim() == 3 else 0
+        out = torch.empty((G, M, n, d) if mode == 0 else (G, R), device=self.dev)
+        self._forward(xk, maskk, dk, tiles_dev, T, img0, simg, n, R, plane, seps, offset, mode, out, out.stride(0), max_blocks)
+        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
+        self.launches = (T + per - 1) // per
+        return out
+
+    def _reward_workspaces(self, n, M, ws_floats):
+        """(floats per member of pre / stat / w1t, members per chunk); the buffers are kept between calls."""
+        sizes = ops.reward_scratch_multi(n, self.lay.d, M)
+        chunk = reward_member_chunk(self.G, n, self.lay.d, M, ws_floats, sizes)
+        key = (n, M, chunk)
+        if getattr(self, "_reward_ws_key", None) != key:
+            self._reward_ws = tuple(torch.empty(chunk * s, device=self.dev) for s in sizes)
+            self._reward_ws_key = key
+        return sizes, chunk
+
+    def _reward(self, x, mask, im, R, img0, simg, sizes, chunk, n, M):
+        """x [n, d] or [G, n, d] fp32, mask [G, n, d] bytes, im / R: [G, ...] views whose member slices are dense."""
+        lay = self.lay
+        w1 = self.params[0]  # seq_encoder.0.weight [100][d] opens a member's row of the parameter stack, its bias follows
+        pre, stat, w1t = self._reward_ws
+        strides = (x.stride(0) if x.dim() == 3 else 0, mask.stride(0), im.stride(0), self.params.stride(0), simg, sizes[0],
+                   sizes[1], sizes[2], R.stride(0))  # VPC_RM_* of include/vpc.h
+        ops.reward_matrix_multi(x, mask, im[0], w1, w1[100 * lay.d:], img0[:lay.enc_img], pre, stat, w1t, R[0], self.G, chunk,
+                                strides, n, lay.d, lay.L, M)
+
+    def reward(self, x, mask, im, *, ws_floats=REWARD_WS_FLOATS):
+        """R [G, n, d-1] of ONE acquisition step: member g's reward_matrix on x (shared [n, d] or [G, n, d]), its mask [G, n, d]
+        and its imputations im [G, M, n, d].  ws_floats bounds the workspaces: members go through them in chunks."""
+        G, d = self.G, self.lay.d
+        n = acquire_plan(G, d, self.lay.L, x.shape, im.shape[1] if im.dim() == 4 else 0)[0]
+        M = im.shape[1]
+        if tuple(mask.shape) != (G, n, d) or tuple(im.shape) != (G, M, n, d):
+            raise L.VpcError(f"mask: expected [{G}, {n}, {d}], got {tuple(mask.shape)}; im: expected [{G}, M, {n}, {d}], got "
+                             f"{tuple(im.shape)}")
+        L.require_cuda(x, mask, im)
+        self.params = stack_models(self.models)
+        img0, simg = self._images()
+        sizes, chunk = self._reward_workspaces(n, M, ws_floats)
+        R = torch.empty(G, n, d - 1, device=self.dev)
+        self._reward(ops._f32c(x), as_mask_u8(mask), ops._f32c(im), R, img0, simg, sizes, chunk, n, M)
+        self.launches = 3 * ((G + chunk - 1) // chunk)
+        return R
+
+    def run(self, x, M, *, repeats=1, max_steps=None, eps=None, keep_im=True, max_blocks=0, ws_floats=REWARD_WS_FLOATS):
+        """x: [n, d] (shared) or [G, n, d]; the target is the last column and is never revealed.  Every member starts every
+        repeat with nothing observed and reveals, per row, the best candidate of each step.  eps: [calls, M n, L] or
+        [G, calls, M n, L] normals for ALL forward calls of the run in issue order (acquire_plan), draw row m n + i = row i of
+        pass m; None: member g draws from its Philox stream, every call at the next eval_draw_counters offset.
+        Returns device tensors (info [G, repeats, d], action [G, repeats, n, d-1] int32, R_hist [G, repeats, d-1, n, d-1],
+        im_hist [G, repeats, d-1, M, n, d] or None when keep_im is false); slots past max_steps stay zero.
+        max_blocks: workgroups per forward launch (0: the library's limit); ws_floats: bound of the reward workspaces (members
+        go through them in chunks).  `launches`: the library's kernel launches of the call, `launches_per_step` of one step."""
+        G, lay = self.G, self.lay
+        d, Ld = lay.d, lay.L
+        n, steps, calls, R = acquire_plan(G, d, Ld, x.shape, M, repeats, max_steps, None if eps is None else eps.shape)
+        L.require_cuda(x, eps)
+        dev = self.dev
+        x, xk, dk, tiles_dev, T, img0, simg = self._setup(x, n, M)
+        draw = eps is None
+        if draw:
+            offs, self.rng_offset = acquire_draw_offsets(self.rng_offset, R, steps, repeats)
+            eps_buf, seps = None, 0
+        else:
+            offs = [0] * calls
+            eps_buf = torch.zeros(*eps.shape[:-1], LP, device=dev)
+            eps_buf[..., :Ld].copy_(eps)
+            seps = eps_buf.stride(0) if eps_buf.dim() == 4 else 0
+        info = torch.zeros(G, repeats, d, device=dev)
+        action = torch.zeros(G, repeats, n, d - 1, dtype=torch.int32, device=dev)
+        R_hist = torch.zeros(G, repeats, d - 1, n, d - 1, device=dev)
+        im_hist = torch.zeros(G, repeats, d - 1, M, n, d, device=dev) if keep_im else None
+        im_buf = None if keep_im else torch.empty(G, M, n, d, device=dev)
+        sq = torch.empty(G, R, device=dev)
+        mask = torch.zeros(G, n, d, dtype=torch.uint8, device=dev)
+        maskk = mask if dk == d else torch.zeros(G, n, dk, dtype=torch.uint8, device=dev)
+        sizes, chunk = self._reward_workspaces(n, M, ws_floats)
+        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
+        f_launches, r_launches = (T + per - 1) // per, 3 * ((G + chunk - 1) // chunk)
+        call = [0]
+
+        def forward(mode, out, out_stride):
+            c = call[0]
+            call[0] += 1
+            e = None if draw else (eps_buf[0, c] if eps_buf.dim() == 4 else eps_buf[c])
+            self._forward(xk, maskk, dk, tiles_dev, T, img0, simg, n, R, e, seps, offs[c], mode, out, out_stride, max_blocks)
+
+        def curve_point(r, t):
+            forward(1, sq, sq.stride(0))
+            ops.target_mse_multi(sq, sq.stride(0), R, G, info[0, r, t:], info.stride(0))
+
+        for r in range(repeats):
+            if r > 0:
+                mask.zero_()
+                if maskk is not mask:
+                    maskk.zero_()
+            curve_point(r, 0)
+            for t in range(steps):
+                im = im_hist[:, r, t] if keep_im else im_buf
+                forward(0, im[0], im.stride(0))
+                Rt = R_hist[:, r, t]
+                self._reward(x, mask, im, Rt, img0, simg, sizes, chunk, n, M)
+                ops.acquire_multi(Rt[0], Rt.stride(0), mask, mask.stride(0), d, None if maskk is mask else maskk,
+                                  maskk.stride(0), dk, action[0, r, :, t:], action.stride(0), d - 1, G, n, d)
+                curve_point(r, t + 1)
+        self.launches_per_step = 2 * f_launches + r_launches + 2
+        self.launches = repeats * (f_launches + 1 + steps * self.launches_per_step)
+        return info, action, R_hist, im_hist

@@ -186,6 +186,44 @@ def eval_reduce_multi(part, batches, n_batches, passes, M, members, G, part_stri
                                       int(part_stride), int(n_tiles), d_real, ptr(out), stream_ptr()), "vpc_eval_reduce_multi")
 
 
+def impute_small_multi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, mode, out,
+                           out_stride, strides, d, d_real, Ld, max_blocks=0):
+    """The forward of eval_small_multi_f32, written instead of summed (include/vpc.h: ensemble acquisition): mode 0 x_hat
+    [R][d_real] per member, mode 1 the target column's squared error [R] per member; members out_stride floats apart."""
+    check(lib().vpc_impute_small_multi_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G, ptr(tiles),
+                                           int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar, int(mode),
+                                           ptr(out), int(out_stride), _member_strides(strides), d, d_real, Ld, int(max_blocks),
+                                           stream_ptr()), "vpc_impute_small_multi_f32")
+
+
+def target_mse_multi(sq, sq_stride, R, G, out, out_stride):
+    """out[g * out_stride] = mean of sq[g * sq_stride + 0..R) in fp64, fixed order."""
+    check(lib().vpc_target_mse_multi(ptr(sq), int(sq_stride), int(R), G, ptr(out), int(out_stride), stream_ptr()),
+          "vpc_target_mse_multi")
+
+
+def reward_scratch_multi(n, d, M):
+    """(pre, stat, w1t) workspace floats PER MEMBER of reward_matrix_multi."""
+    sizes = [C.c_long() for _ in range(3)]
+    check(lib().vpc_reward_scratch_multi(n, d, M, *[C.byref(s) for s in sizes]), "vpc_reward_scratch_multi")
+    return tuple(s.value for s in sizes)
+
+
+def reward_matrix_multi(x, mask, im, W1, b1, enc_img, pre, stat, w1t, R, G, chunk, strides, n, d, Ld, M):
+    """vpc_reward_matrix with blockIdx.y = member; `strides` the VPC_RM_* member strides, the workspaces hold `chunk` members."""
+    check(lib().vpc_reward_matrix_multi(ptr(x), ptr(mask), ptr(im), ptr(W1), ptr(b1), ptr(enc_img), ptr(pre), ptr(stat), ptr(w1t),
+                                        ptr(R), G, int(chunk), _member_strides(strides), n, d, Ld, M, stream_ptr()),
+          "vpc_reward_matrix_multi")
+
+
+def acquire_multi(R, R_stride, mask, mask_stride, mask_pitch, mask2, mask2_stride, mask2_pitch, action, action_stride,
+                  action_pitch, G, n, d):
+    """Per (member, row): argmax of R (lowest index among the maxima) -> mask byte(s) set, action written."""
+    check(lib().vpc_acquire_multi(ptr(R), int(R_stride), ptr(mask), int(mask_stride), mask_pitch, ptr(mask2), int(mask2_stride),
+                                  mask2_pitch, ptr(action), int(action_stride), action_pitch, G, n, d, stream_ptr()),
+          "vpc_acquire_multi")
+
+
 def step_fused_applicable(B, d, Ld, npass):
     return bool(lib().vpc_step_fused_applicable(int(B), d, Ld, npass))
 
