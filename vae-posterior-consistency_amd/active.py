@@ -20,6 +20,7 @@ import torch
 from . import _lib as L
 from ._lib import check, lib, ptr, stream_ptr
 from .ensemble import EnsembleAcquirer
+from .harness import _save_results, _sweep_configs, _sweep_models, draw_mask_p, eval_groups, model_loader
 from .images import PackedImage
 from .ops import _f32c, as_mask_u8, pack_weights
 
@@ -285,7 +286,6 @@ def active_learning_func(data_loader_train, test_data, test_mask, missing_rate, 
     pass (tests replay the outputs recorded from the reference, whose eps come from the global RNG).
     Returns dict(information_curve_CHAI [Repeat, n, d], action_CHAI [Repeat, n, d-1], R_hist_CHAI [Repeat, d-1, n, d-1],
     im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the reference's four files."""
-    from .harness import model_loader
     if _is_flow(model):
         raise NotImplementedError("active_learning_func: the flow models' reward (R_lindley_chain_ratio_version, "
                                   "evaluate.py) is not on the accelerated path")
@@ -310,7 +310,6 @@ def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, R
     """The loop body of evaluate.py:340-455 shared by active_learning_func and active_learning_flow.
     load() -> a model for a repeat without one; passes(mdl, x, mask, mask_p) -> x_mean [M, n, d];
     reward(mdl, x, mask, im, step) -> R [n, d-1]."""
-    from .harness import draw_mask_p
     dev = torch.device(device) if device is not None else torch.device("cuda")
     n_test, d = test_data.shape[0], obs_dim
     info = torch.zeros(Repeat, n_test, d)
@@ -345,11 +344,9 @@ def _acquisition_loop(test_data, test_mask, obs_dim, M, device, p_missingness, R
 
 
 def _save_active(out, save, experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type):
-    from .harness import _save
     if save:
-        paths = active_result_paths(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness, reg_type)
-        for k, pth in paths.items():
-            _save(out[k], pth)
+        _save_results(out, active_result_paths(experiment_type, data_type, vae_type, missing_rate, alpha, p_missingness,
+                                               reg_type))
     return out
 
 
@@ -390,8 +387,7 @@ def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate,
                  max_steps=None):
     """active_learning_func() for a LIST of runs - the loop body of src/experiment_main/active_learning.py (train, then
     active_learning_func, inside `for data_file: for missing: for alpha:`) after train_sweep, as one call; the twin of
-    harness.eval_sweep, with its conventions.  configs: one dict per member with the keys vae_type, alpha (1.0), p_missingness
-    (30), seed (0).  models (optional): one model per member, else each member's checkpoint through model_loader('test', ...).
+    harness.eval_sweep, with its conventions for configs and models.
     Members are grouped with harness.eval_groups: plain Reg_VAE / vanilla_VAE members of one class and reg_type run the whole
     loop through ONE ensemble.EnsembleAcquirer - a fixed number of launches per acquisition step whatever their number, nothing
     read back before the end; every other family (mask-augmented, wide, EDDI) goes alone through active_learning_func, and the
@@ -399,21 +395,14 @@ def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate,
     (information_curve_CHAI [Repeat, n, d] - the scalar curve broadcast over the rows, as the reference stores it -, action_CHAI
     [Repeat, n, d-1] float, R_hist_CHAI [Repeat, d-1, n, d-1], im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the
     reference's four files under active_result_paths(...) with that member's alpha / p_missingness.
-    What differs from active_learning_func for the members run together: no p pass and no mask_p draw (VAE.py:496-507: neither
-    reaches an output of the loop); eps comes from the member's Philox stream (seed = the config's seed), not from torch.randn;
-    the M passes of a forward call are one launch; a given (or loaded) model serves every repeat - the reference reloads the
-    same checkpoint per repeat.  The estimator and its distribution are the same."""
-    from .harness import _model_for_eval, eval_groups
-    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
-    G = len(cfgs)
-    if models is not None and len(models) != G:
-        raise L.VpcError(f"{len(models)} models for {G} configurations")
+    What differs from active_learning_func for the members run together: what eval_sweep states for its members (no p pass,
+    eps from the member's Philox stream), and a given (or loaded) model serves every repeat - the reference reloads the same
+    checkpoint per repeat.  The estimator and its distribution are the same."""
+    cfgs = _sweep_configs(configs, models)
     dev = torch.device(device) if device is not None else torch.device("cuda")
-    ms = [_model_for_eval(models[g] if models is not None else None, dev, obs_dim, hid_dim, K, latent_dim, missing_rate,
-                          data_type, training_parameters, max_epochs, valid_k, num_estimates, experiment_type, reg_type,
-                          c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"], alpha_annealing=alpha_annealing)
-          for g, c in enumerate(cfgs)]
-    out = [None] * G
+    ms = _sweep_models(cfgs, models, dev, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                       max_epochs, valid_k, num_estimates, experiment_type, reg_type, alpha_annealing=alpha_annealing)
+    out = [None] * len(cfgs)
     groups, single = eval_groups(ms)
     for g in single:
         c = cfgs[g]

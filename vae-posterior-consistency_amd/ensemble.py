@@ -14,33 +14,17 @@ computes on its data: same tile body, same summation order, same Philox counters
 
     stack_models(models)         one [G, n] buffer under the members' parameters; every model stays an ordinary module
     MemberTable                  the per-member records (loss coefficients, keep probability, lr, seed) on the host
+    _MemberSet                   what the three classes hold of their members: stacks, device member table, fresh images, inputs
     EnsembleTrainer              the step, the read-outs and per-member views of the stacked state
 
-The sweep's evaluation shares a launch the same way (every train() of the drivers is followed by eval_vae, imputation.py:51-59
-around evaluate.py:136-297: M Monte-Carlo passes over the loaders, forward + loss(llh_eval=True, stage='evaluate') per batch):
-
-    vpc_eval_small_multi_f32     grid = tiles x G; workgroup (t, g) runs the evaluate-stage forward of member g on one 16-row
-                                 tile of one batch of one MC pass and leaves five sums (csrc/vpc_evalsmall.hip)
-    vpc_eval_reduce_multi        tiles -> batches -> passes -> (rmse, elbo, negll, negll_imp) per member, blockIdx.y = member
-
-    build_eval_tables            the tile / batch / pass tables of one (N, batch layout, M)
-    EnsembleEvaluator            the call, the table cache, image freshness and the Philox offset of its draws
-
-and so does its active variable selection (active_learning.py follows every train() with active_learning_func,
-evaluate.py:300-511: per acquisition step M imputation forwards, the reward of every candidate, an argmax per row, M forwards for
-the target MSE), a fixed number of launches per step whatever G, with the loop's state on the device:
-
-    vpc_impute_small_multi_f32   the forward of vpc_eval_small_multi_f32, written instead of summed: x_hat, or the target's squared error
-    vpc_reward_matrix_multi      the three launches of vpc_reward_matrix with blockIdx.y = member (csrc/vpc_reward.hip)
-    vpc_acquire_multi            argmax per (member, row) -> mask byte, action
-    vpc_target_mse_multi         the information curve's next point per member
-
-    acquire_plan / acquire_draw_offsets   the shapes and the Philox offsets of a run, on the host alone
-    EnsembleAcquirer             the loop (run), one forward call (impute), one reward (reward)
+The sweep's evaluation (eval_vae, evaluate.py:136-297) and its active variable selection (active_learning_func,
+evaluate.py:300-511) share their launches the same way: EnsembleEvaluator over build_eval_tables, EnsembleAcquirer over
+acquire_plan / acquire_draw_offsets (the shapes and Philox offsets of a run, on the host alone).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple
 
 import numpy as np
@@ -51,8 +35,8 @@ from . import ops
 from .fused import LP
 from .images import PackedImage, flat_written
 from .models import Reg_VAE, loss_coefficients, vanilla_VAE
-from .ops import as_mask_u8
-from .trainer import draw_counters, eval_draw_counters, pad_cols
+from .ops import as_mask_u8, stride_vector
+from .trainer import draw_counters, eval_draw_counters, pad_cols, padded_width
 
 # VpcMember of include/vpc.h (64 bytes): the first 32 are its VpcLossCoef, spelled flat
 MEMBER_DTYPE = np.dtype([("cA", "<f4", 2), ("cE", "<f4", 2), ("bq", "<f4"), ("bp", "<f4"), ("cr", "<f4"), ("wml", "<f4"),
@@ -81,6 +65,30 @@ def stackable(model):
     """Can `model` be one row of a stack?  THE predicate of stack_models, EnsembleTrainer and harness.train_sweep: exactly
     Reg_VAE or vanilla_VAE (no subclass: not mask-augmented, not EDDI) on the small layouts (not wide)."""
     return type(model) in (Reg_VAE, vanilla_VAE) and not model._wide
+
+
+def steps_in_ensemble(model, vae_type, loader, obs_dim):
+    """Does train_sweep step `model` in an ensemble?  Stackable, no 'with_drop' run, a first batch within the small-batch step."""
+    first = next(iter(loader), None) if stackable(model) and "with_drop" not in vae_type else None
+    return first is not None and first[0].reshape(-1, obs_dim).shape[0] <= ops.step_small_max_rows()
+
+
+def _shared_or_per_member(t, name, G, tail, note=""):
+    """Check that `t` (a tensor, or a shape alone) is [*tail], one array shared by all members, or [G, *tail]; tail[0] = None
+    admits any number of rows.  -> the member stride in elements of a DENSE array of that shape, 0 when shared: the shape alone
+    decides (an expanded view still has its member axis), and a caller takes the stride of the array it hands to a kernel."""
+    shape = tuple(getattr(t, "shape", t))
+    k = len(shape) - len(tail)
+    if (k == 0 or k == 1 and shape[0] == G) and shape[k + 1:] == tail[1:] and tail[0] in (None, shape[k]):
+        return math.prod(shape[1:]) if k else 0
+    want = ", ".join("rows" if a is None else str(a) for a in tail)
+    raise L.VpcError(f"{name}: expected [{want}] or [{G}, {want}]{note}, got {shape}")
+
+
+def forward_launches(T, G, max_blocks=0):
+    """Launches of one forward call over T tiles x G members at max_blocks workgroups per launch (0: the library's limit)."""
+    per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
+    return (T + per - 1) // per
 
 
 def _require_stackable(m):
@@ -220,59 +228,100 @@ class MemberView:
         self.out9, self.accum = ens.out9[g], ens.accum[g:g + 1]
 
 
-class EnsembleTrainer:
-    def __init__(self, models, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seeds=None, world_size=1):
-        """models: G plain Reg_VAE or G plain vanilla_VAE of one (obs_dim, latent_dim, reg_type), on the GPU.  lr and seeds:
-        scalars or one value per member (seeds=None: member g draws with seed g).  The step count (Adam's bias corrections)
-        and the Philox offsets are shared: every member steps in every call."""
+class _MemberSet:
+    """What EnsembleTrainer, EnsembleEvaluator and EnsembleAcquirer hold of their members, stated once: validation (raised
+    before anything touches the device), member table, parameter and image stack, image freshness, inputs at the row pitch."""
+
+    def __init__(self, models, lr, seeds, world_size):
         models = list(models)
         validate_members(models, world_size)
         self.table = MemberTable(models, lr, seeds)
         self.models = models
-        self.betas, self.adam_eps = betas, eps
-        self.rng_offset, self.step_count = 0, 0
+        self.rng_offset = 0
         # ---- device state from here on
         self.params = stack_models(models)
         L.require_cuda(self.params)
-        G, n = self.params.shape
-        self.G, self.dev = G, self.params.device
-        self.vanilla = isinstance(models[0], vanilla_VAE)
+        self.G, self.dev = len(models), self.params.device
         self.lay = lay = models[0]._lay()
+        self.n_img, self.dk = lay.enc_img + lay.dec_img, padded_width(lay.d)  # (dk: row pitch of x / mask in the kernels)
+        self._plists = [m.trainable() for m in models]
+        self._pads = {}  # pad_cols buffers of this object: slot 0 = x, slot 1 = mask
+
+    def _image_stack_and_table(self, new_image_stack):
+        """The members' images as rows of ONE stack (a trainer installs a new one, an evaluator only when they sit in none) and
+        the device member table; the trainer allocates them after its own state."""
+        adopt = not new_image_stack and image_stack_of(self.models, self.n_img, self.dev) is not None
+        self.img = None if adopt else install_image_stack(self.models, self.lay, self.dev)
+        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self._table_version = -1
+
+    def _sync_table(self):  # THE upload of the member table: whenever the host rows changed since the last one
+        if self._table_version != self.table.version:
+            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
+            self._table_version = self.table.version
+
+    def _fresh_images(self, row_ptr=None):
+        """Re-pack every image whose parameter key is stale (images.py) -> the keys.  row_ptr: the trainer's rows of the stack."""
+        keys = []
+        for g, m in enumerate(self.models):
+            key = m._param_key(self._plists[g])
+            if row_ptr is not None and key[1] != row_ptr[g]:
+                raise L.VpcError(f"member {g} no longer sits in the ensemble's parameter stack (moved or re-flattened)")
+            if m._img.key != key:
+                m._images(key)
+            keys.append(key)
+        return keys
+
+    def _check_inputs(self, x, mask):
+        """x, mask: each [rows, d] (shared by all members) or [G, rows, d] -> (rows, whether x has the member axis, whether mask)."""
+        per_x = _shared_or_per_member(x, "x", self.G, (None, self.lay.d))
+        rows = x.shape[-2]
+        return rows, per_x, _shared_or_per_member(mask, "mask", self.G, (rows, self.lay.d), " (x and mask agree in their rows)")
+
+    def _padded_inputs(self, x, mask, per_x, per_mask):
+        """-> (x fp32, mask 0 / 1 bytes, both dense in rows of dk columns, and the member strides of these two arrays)."""
+        x, mask = ops._f32c(x), as_mask_u8(mask)
+        if self.dk != self.lay.d:
+            x, mask = pad_cols(self._pads, x, self.dk, 0, self.dev), pad_cols(self._pads, mask, self.dk, 1, self.dev)
+        return x, mask, x.stride(0) if per_x else 0, mask.stride(0) if per_mask else 0
+
+
+class EnsembleTrainer(_MemberSet):
+    def __init__(self, models, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seeds=None, world_size=1):
+        """models: G plain Reg_VAE or G plain vanilla_VAE of one (obs_dim, latent_dim, reg_type), on the GPU.  lr and seeds:
+        scalars or one value per member (seeds=None: member g draws with seed g).  The step count (Adam's bias corrections)
+        and the Philox offsets are shared: every member steps in every call."""
+        super().__init__(models, lr, seeds, world_size)
+        self.betas, self.adam_eps = betas, eps
+        self.step_count = 0
+        G, n = self.params.shape
+        self.vanilla = isinstance(self.models[0], vanilla_VAE)
         zeros = lambda w: torch.zeros(G, _pitch(w), device=self.dev)[:, :w]
         self.grad, self.exp_avg, self.exp_avg_sq = zeros(n), zeros(n), zeros(n)
         self.row_pitch = self.params.stride(0)
         self.out9 = torch.zeros(G, 9, device=self.dev)
         self.accum = torch.zeros(G, device=self.dev)
-        self.pidx, self.gidx = lay.device_tables(self.dev)
-        self.inv = lay.inverse_maps(self.dev)
-        # the members' fp32 weight images are rows of one stack: each stays the model's own image (images.py), so the API
-        # path reads what the ensemble step re-packs
-        self.img = install_image_stack(models, lay, self.dev)
-        self._plists, self._row_ptr = [], []
-        for g, m in enumerate(models):
-            pl = m.trainable()
-            self._plists.append(pl)
-            self._row_ptr.append(self.params[g].data_ptr())
+        self.pidx, self.gidx = self.lay.device_tables(self.dev)
+        self.inv = self.lay.inverse_maps(self.dev)
+        self._image_stack_and_table(new_image_stack=True)
+        self._row_ptr = [self.params[g].data_ptr() for g in range(G)]
+        for g, pl in enumerate(self._plists):
             off = 0
             for p in pl:  # .grad are views of the stacked gradient, as under a stand-alone trainer
                 p.grad = self.grad[g, off:off + p.numel()].view_as(p)
                 off += p.numel()
-        self.table_dev = torch.zeros(G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
-        self._table_version = -1
         self.trainers = [MemberView(self, g) for g in range(G)]
         # workgroup order of the step launch (include/vpc.h): 1 = all tiles of a member on one XCD, 0 = member-major.  Same bits;
         # 1 is 3-5 % faster where the GPU is the limit and never slower from 8 members on; below 8 members its grid has
         # surplus workgroups that cost 0.3-0.8 us (profiles/ensemble_notes.md)
         self.order = 1 if G >= 8 else 0
         self._ws = None
-        self._pads = {}
 
     # ------------------------------------------------------------------
     def _workspaces(self, B, dk):
-        tiles = (B + 15) // 16
         if self._ws == (B, dk):
-            return tiles
-        G, lay, dev = self.G, self.lay, self.dev
+            return
+        G, lay, dev, tiles = self.G, self.lay, self.dev, (B + 15) // 16
         self.eps_buf = torch.empty(G, 3, B, LP, device=dev)
         self.mask_p_buf = torch.zeros(G, B, dk, dtype=torch.uint8, device=dev)
         if getattr(self, "_tiles_cap", 0) < tiles:
@@ -280,15 +329,12 @@ class EnsembleTrainer:
             self.partD = torch.empty(G, tiles * lay.dec_part, device=dev)
             self.loss_part = torch.empty(G, tiles * 8, dtype=torch.float64, device=dev)
             self._tiles_cap = tiles
+        self._strides = stride_vector(ops.MS_COUNT, {  # of what the trainer owns; a step fills in those of its x and mask
+            ops.MS_MASK_P: self.mask_p_buf.stride(0), ops.MS_EPS: self.eps_buf.stride(0), ops.MS_IMG: self.img.stride(0),
+            ops.MS_PARTE: self.partE.stride(0), ops.MS_PARTD: self.partD.stride(0), ops.MS_LOSS: self.loss_part.stride(0),
+            ops.MS_PARAM: self.row_pitch})
         self._ws = (B, dk)
-        return tiles
 
-    def _upload_table(self):
-        if self._table_version != self.table.version:
-            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
-            self._table_version = self.table.version
-
-    # ------------------------------------------------------------------
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=1.0, beta=1.0,
              beta_annealing=False, p_missingness=30):
         """One training step of every member.  x, mask: [B, d] (one batch shared by all members) or [G, B, d]; alpha, beta,
@@ -296,44 +342,25 @@ class EnsembleTrainer:
         in its own element space, exactly as its stand-alone trainer would - unless ALL the step's draws are injected
         ([G, ...] or shared).  No host sync: losses are in `out9[:, 0]`, the running totals in `accum`."""
         L.require_cuda(x)
-        G, lay = self.G, self.lay
-        d, Ld = lay.d, lay.L
-        for t, name in ((x, "x"), (mask, "mask")):
-            if t.dim() not in (2, 3) or t.shape[-1] != d or (t.dim() == 3 and t.shape[0] != G):
-                raise L.VpcError(f"{name}: expected [B, {d}] or [{G}, B, {d}], got {tuple(t.shape)}")
-        B = x.shape[-2]
-        if mask.shape[-2] != B:
-            raise L.VpcError("x and mask differ in their batch size")
+        G, lay, d, Ld, dk = self.G, self.lay, self.lay.d, self.lay.L, self.dk
+        B, per_x, per_mask = self._check_inputs(x, mask)
+        tiles = (B + 15) // 16
         if B > ops.step_small_max_rows():
             raise L.VpcError(f"batch {B}: the ensemble step covers batches up to {ops.step_small_max_rows()} rows "
                              "(larger ones fill the chip on their own: FusedTrainer)")
-        tiles = (B + 15) // 16
         if G * tiles > MAX_BLOCKS:
             raise L.VpcError(f"{G} members x {tiles} tiles = {G * tiles} workgroups: one ensemble launch holds {MAX_BLOCKS}")
         two = not self.vanilla
-        changed = self.table.update(epoch, alpha, beta, beta_annealing, p_missingness)
+        self.table.update(epoch, alpha, beta, beta_annealing, p_missingness)
         need_ml = self.table.need_ml
         given = [mask_p is not None] * two + [eps_q is not None] + [eps_p is not None] * two + [eps_ml is not None] * need_ml
         if any(given) != all(given):
             raise L.VpcError("inject all of the step's draws (mask_p, eps_q, eps_p, eps_ml as the model uses them) or none")
         draw = not any(given)
-        x = ops._f32c(x)
-        mask = as_mask_u8(mask)
-        dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # (the padding rule of FusedTrainer.step)
-        if dk != d:
-            x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
+        x, mask, sx, smask = self._padded_inputs(x, mask, per_x, per_mask)
         self._workspaces(B, dk)
-        if changed or self._table_version != self.table.version:
-            self._upload_table()
-        # every member's image is checked against its parameter key (images.py); a stale one is re-packed from its row
-        keys = []
-        for g, m in enumerate(self.models):
-            key = m._param_key(self._plists[g])
-            if key[1] != self._row_ptr[g]:
-                raise L.VpcError(f"member {g} no longer sits in the ensemble's parameter stack (moved or re-flattened)")
-            if m._img.key != key:
-                m._images(key)
-            keys.append(key)
+        self._sync_table()
+        keys = self._fresh_images(self._row_ptr)
         nplanes = 3 if need_ml else 2 if two else 1
         off_m = off_e = 0
         if draw:  # every member is an unsharded batch of B rows
@@ -341,19 +368,14 @@ class EnsembleTrainer:
         else:
             if two:
                 self.mask_p_buf[:, :, :d].copy_(as_mask_u8(mask_p))
-            self.eps_buf[:, 0, :, :Ld].copy_(eps_q)
-            if two:
-                self.eps_buf[:, 1, :, :Ld].copy_(eps_p)
-            if need_ml:
-                self.eps_buf[:, 2, :, :Ld].copy_(eps_ml)
-        m0 = self.models[0]
-        strides = (x.stride(0) if x.dim() == 3 else 0, mask.stride(0) if mask.dim() == 3 else 0, self.mask_p_buf.stride(0),
-                   self.eps_buf.stride(0), self.img.stride(0), self.partE.stride(0), self.partD.stride(0),
-                   self.loss_part.stride(0), self.row_pitch)
+            for k, e in enumerate((eps_q, eps_p, eps_ml)[:nplanes]):
+                self.eps_buf[:, k, :, :Ld].copy_(e)
+        strides = self._strides
+        strides[ops.MS_X], strides[ops.MS_MASK] = sx, smask
         ops.step_small_multi_f32(x, mask, self.mask_p_buf if two else None, self.eps_buf, self.img[0, :lay.enc_img],
                                  self.img[0, lay.enc_img:], self.table_dev, G, 2 if two else 1, nplanes, draw, off_m, off_e,
-                                 1.0 / B, m0._x_logvar_value, self.partE, self.partD, self.loss_part, strides, B, dk, Ld,
-                                 self.order)
+                                 1.0 / B, self.models[0]._x_logvar_value, self.partE, self.partD, self.loss_part, strides, B, dk,
+                                 Ld, self.order)
         self.step_count += 1
         ops.reduce_step_adam_multi(self.partE, self.partD, self.loss_part, tiles, lay.enc_part, lay.dec_part, strides,
                                    self.inv, self.table_dev, G, self.grad, B, d, self.out9, self.accum, self.params,
@@ -429,7 +451,7 @@ def build_eval_tables(N, batch_size=None, M=1, batches=None):
     return EvalTables(np.array(tiles, np.int64), np.array(brows, np.int64), np.array(prows, np.int64), r)
 
 
-class EnsembleEvaluator:
+class EnsembleEvaluator(_MemberSet):
     """eval_vae's numbers (evaluate.py:136-297) for G stackable members over all batches and MC passes in one pair of launches:
     vpc_eval_small_multi_f32 (forward of every member x pass x batch x 16-row tile -> five sums per tile) and
     vpc_eval_reduce_multi (tiles -> batches -> passes -> [G, 4]).  Only the q pass is computed: VAE.py:410-420 reads nothing else."""
@@ -438,24 +460,9 @@ class EnsembleEvaluator:
     def __init__(self, models, seeds=None, world_size=1):
         """models: as EnsembleTrainer (validate_members), on the GPU.  seeds: one Philox seed per member (None: member g draws
         with seed g).  The evaluator owns a Philox offset: a call advances it by the groups it consumed (eval_draw_counters)."""
-        models = list(models)
-        validate_members(models, world_size)
-        self.table = MemberTable(models, 0.0, seeds)
-        self.models = models
-        self.rng_offset = 0
-        # ---- device state from here on
-        self.params = stack_models(models)
-        L.require_cuda(self.params)
-        self.G, self.dev = len(models), self.params.device
-        self.lay = lay = models[0]._lay()
-        self.n_img = lay.enc_img + lay.dec_img
-        # the members' images are rows of one stack: the one they already sit in (an EnsembleTrainer's), else a new one
-        if image_stack_of(models, self.n_img, self.dev) is None:
-            install_image_stack(models, lay, self.dev)
-        self._plists = [m.trainable() for m in models]
-        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
-        self._table_version = -1
-        self._tables, self._pads, self._part = {}, {}, None
+        super().__init__(models, 0.0, seeds, world_size)
+        self._image_stack_and_table(new_image_stack=False)
+        self._tables, self._part = {}, None
         self.launches = 0  # kernel launches of the last call (the forward entry walks the tile table in chunks)
 
     def tables(self, N, batch_size=None, M=1, batches=None):
@@ -470,14 +477,10 @@ class EnsembleEvaluator:
         return hit
 
     def _images(self):
-        """(member 0's image, row stride): every member's image is checked against its parameter key (images.py) and a stale one
-        re-packed from its parameters, so a call after load_state_dict or after training steps reads the current weights."""
+        """(member 0's image, row stride) of the stack the members' images sit in NOW, every image fresh (_fresh_images)."""
         if image_stack_of(self.models, self.n_img, self.dev) is None:  # (a model's image was replaced: .to(), a stand-alone trainer)
-            install_image_stack(self.models, self.lay, self.dev)
-        for g, m in enumerate(self.models):
-            key = m._param_key(self._plists[g])
-            if m._img.key != key:
-                m._images(key)
+            self.img = install_image_stack(self.models, self.lay, self.dev)
+        self._fresh_images()
         return image_stack_of(self.models, self.n_img, self.dev)
 
     def evaluate(self, x, mask, batch_size=None, M=1, *, batches=None, epoch, beta=1.0, beta_annealing=False, eps=None,
@@ -489,50 +492,44 @@ class EnsembleEvaluator:
         Returns [G, 4] on the device = (rmse on ~mask, elbo, negll, negll_imp) as eval_vae averages them; no host sync.
         max_blocks: workgroups per launch (0: the library's limit)."""
         L.require_cuda(x)
-        G, lay = self.G, self.lay
-        d, Ld = lay.d, lay.L
-        for t, name in ((x, "x"), (mask, "mask")):
-            if t.dim() not in (2, 3) or t.shape[-1] != d or (t.dim() == 3 and t.shape[0] != G):
-                raise L.VpcError(f"{name}: expected [N, {d}] or [{G}, N, {d}], got {tuple(t.shape)}")
-        N = x.shape[-2]
-        if mask.shape[-2] != N:
-            raise L.VpcError("x and mask differ in their row count")
+        G, lay, d, Ld, dk = self.G, self.lay, self.lay.d, self.lay.L, self.dk
+        N, per_x, per_mask = self._check_inputs(x, mask)
+        x, mask, sx, smask = self._padded_inputs(x, mask, per_x, per_mask)
         tb, tiles_dev, batches_dev, passes_dev = self.tables(N, batch_size, M, batches)
         T, R = tb.tiles.shape[0], tb.R
-        if eps is not None and (eps.dim() not in (2, 3) or tuple(eps.shape[-2:]) != (R, Ld) or (eps.dim() == 3 and eps.shape[0] != G)):
-            raise L.VpcError(f"eps: expected [{R}, {Ld}] or [{G}, {R}, {Ld}], got {tuple(eps.shape)}")
+        if eps is not None:
+            _shared_or_per_member(eps, "eps", G, (R, Ld))
         # the evaluate stage is the q pass's ELBO (VAE.py:410-420): at alpha = 0 every loss record's bq is its KL weight
         self.table.update(epoch, 0.0, beta, beta_annealing, 0)
-        if self._table_version != self.table.version:
-            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
-            self._table_version = self.table.version
-        x = ops._f32c(x)
-        mask = as_mask_u8(mask)
-        dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # (the padding rule of FusedTrainer.step)
-        if dk != d:
-            x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
+        self._sync_table()
         img0, simg = self._images()
-        offset, eps_buf = 0, None
-        if eps is None:
-            offset, self.rng_offset = eval_draw_counters(self.rng_offset, R, LP)
-        else:
-            eps_buf = torch.zeros(*eps.shape[:-1], LP, device=self.dev)
-            eps_buf[..., :Ld].copy_(eps)
+        [(offset, eps_plane)], seps = self._draws(None if eps is None else eps.unsqueeze(-3), R)
         if self._part is None or self._part.shape[1] < T * 5:
             self._part = torch.empty(G, T * 5, dtype=torch.float64, device=self.dev)
         out = torch.empty(G, 4, device=self.dev)
-        strides = [0] * 9  # VPC_MS_* of include/vpc.h
-        strides[0] = x.stride(0) if x.dim() == 3 else 0
-        strides[1] = mask.stride(0) if mask.dim() == 3 else 0
-        strides[3] = eps_buf.stride(0) if eps_buf is not None and eps_buf.dim() == 3 else 0
-        strides[4], strides[7] = simg, self._part.stride(0)
-        ops.eval_small_multi_f32(x, mask, eps_buf, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, G, tiles_dev, T, N, R,
-                                 eps is None, offset, self.models[0]._x_logvar_value, self._part, strides, dk, d, Ld, max_blocks)
+        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: sx, ops.MS_MASK: smask, ops.MS_EPS: seps, ops.MS_IMG: simg,
+                                               ops.MS_PART: self._part.stride(0)})
+        ops.eval_small_multi_f32(x, mask, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, G, tiles_dev, T, N,
+                                 R, eps is None, offset, self.models[0]._x_logvar_value, self._part, strides, dk, d, Ld,
+                                 max_blocks)
         ops.eval_reduce_multi(self._part, batches_dev, tb.batches.shape[0], passes_dev, M, self.table_dev, G,
                               self._part.stride(0), T, d, out)
-        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
-        self.launches = (T + per - 1) // per + 1
+        self.launches = forward_launches(T, G, max_blocks) + 1
         return out
+
+    def _draws(self, eps, R, calls=1):
+        """-> ([(Philox offset, member 0's eps plane) of `calls` forward calls in issue order], the planes' member stride).
+        eps None: drawn on the device at successive eval_draw_counters offsets; else [calls, R, L] (shared by the members) or
+        [G, calls, R, L], checked by the caller, which uses no counter."""
+        if eps is None:
+            offs, self.rng_offset = forward_draw_offsets(self.rng_offset, R, calls)
+            return [(off, None) for off in offs], 0
+        buf = torch.zeros(*eps.shape[:-1], LP, device=self.dev)  # THE padding of injected normals: rows of LP floats
+        Ld = self.lay.L
+        buf[..., :Ld].copy_(eps)
+        if eps.dim() == 3:
+            return [(0, buf[c]) for c in range(calls)], 0
+        return [(0, buf[0, c]) for c in range(calls)], buf.stride(0)  # (the stride of the copy: eps may be an expanded view)
 
 
 # ------------------------------------------------------------------------------------------------ acquisition
@@ -543,9 +540,7 @@ def acquire_plan(G, d, Ld, x_shape, M, repeats=1, max_steps=None, eps_shape=None
     """Shapes of one EnsembleAcquirer.run, checked on the host alone: -> (n, steps, forward calls of the run, draw rows per
     call).  A repeat is 1 + 2 * steps forward calls: the curve's start, then per acquisition step the imputation and the
     curve's next point."""
-    x_shape = tuple(x_shape)
-    if len(x_shape) not in (2, 3) or x_shape[-1] != d or (len(x_shape) == 3 and x_shape[0] != G):
-        raise L.VpcError(f"x: expected [n, {d}] or [{G}, n, {d}], got {x_shape}")
+    _shared_or_per_member(x_shape, "x", G, (None, d))
     n = x_shape[-2]
     if n < 1 or M < 1 or repeats < 1 or d < 2:
         raise L.VpcError(f"run: n = {n}, M = {M}, repeats = {repeats}, obs_dim = {d}: each at least 1 (obs_dim 2)")
@@ -554,27 +549,44 @@ def acquire_plan(G, d, Ld, x_shape, M, repeats=1, max_steps=None, eps_shape=None
     steps = d - 1 if max_steps is None else min(int(max_steps), d - 1)
     calls, R = repeats * (1 + 2 * steps), M * n
     if eps_shape is not None:
-        eps_shape = tuple(eps_shape)
-        if eps_shape not in ((calls, R, Ld), (G, calls, R, Ld)):
-            raise L.VpcError(f"eps: expected [{calls}, {R}, {Ld}] or [{G}, {calls}, {R}, {Ld}] ({calls} forward calls = "
-                             f"{repeats} repeats x (1 + 2 x {steps} steps)), got {eps_shape}")
+        _shared_or_per_member(eps_shape, "eps", G, (calls, R, Ld),
+                              f" ({calls} forward calls = {repeats} repeats x (1 + 2 x {steps} steps))")
     return n, steps, calls, R
 
 
-def acquire_draw_offsets(rng_offset, draw_rows, steps, repeats=1):
-    """The Philox offsets of a run's forward calls in issue order - successive eval_draw_counters(., draw_rows, LP), no rule of
-    its own - and the acquirer's rng_offset after the run."""
+def forward_draw_offsets(rng_offset, draw_rows, calls):
+    """The Philox offsets of `calls` forward calls in issue order - successive eval_draw_counters(., draw_rows, LP), no rule of
+    its own - and the rng_offset after them."""
     offs = []
-    for _ in range(repeats * (1 + 2 * steps)):
+    for _ in range(calls):
         off, rng_offset = eval_draw_counters(rng_offset, draw_rows, LP)
         offs.append(off)
     return offs, rng_offset
+
+
+def acquire_draw_offsets(rng_offset, draw_rows, steps, repeats=1):
+    """forward_draw_offsets of a run: a repeat is 1 + 2 * steps forward calls (acquire_plan)."""
+    return forward_draw_offsets(rng_offset, draw_rows, repeats * (1 + 2 * steps))
 
 
 def reward_member_chunk(G, n, d, M, budget_floats=REWARD_WS_FLOATS, sizes=None):
     """Members per pass through the reward workspaces so that they stay within `budget_floats` (at least one member)."""
     per = sum(sizes if sizes is not None else ops.reward_scratch_multi(n, d, M))
     return max(1, min(G, int(budget_floats) // per))
+
+
+class _AcquireCall(NamedTuple):
+    """The constants of one EnsembleAcquirer call for its forward and reward launches (EnsembleAcquirer._setup)."""
+    n: int
+    M: int
+    x: torch.Tensor  # fp32 [n, d] or [G, n, d]: the reward reads rows of d columns
+    sx: int  # member stride of x (0: shared)
+    img0: torch.Tensor  # member 0's weight image [enc | dec]
+    simg: int  # row stride of the image stack
+    xk: torch.Tensor = None  # x in rows of dk columns (x itself when dk == d)
+    sxk: int = 0
+    tiles_dev: torch.Tensor = None  # the tile table [T, 4] of (n, one batch of n rows, M passes)
+    max_blocks: int = 0
 
 
 class EnsembleAcquirer(EnsembleEvaluator):
@@ -585,57 +597,49 @@ class EnsembleAcquirer(EnsembleEvaluator):
     sync inside a repeat.  Members, stacking, image freshness and the Philox offset are EnsembleEvaluator's.  Only the q pass is
     computed (mask_p and the p pass reach no output of the loop, VAE.py:496-507)."""
 
-    def _setup(self, x, n, M):
-        """What every forward call of a run shares: member table on the device, tables, x at both row pitches, fresh images."""
-        lay, dev = self.lay, self.dev
-        d = lay.d
+    def _setup(self, x, n, M, forward=True, max_blocks=0):
+        """What the launches of one call share; forward: also the device member table, the tile table, x at the row pitch."""
+        d = self.lay.d
         self.params = stack_models(self.models)  # (idempotent; a member moved since is stacked again)
-        tb, tiles_dev, _, _ = self.tables(n, n, M)
-        self.table.update(1, 0.0, 1.0, False, 0)  # (the loop reads the seeds only)
-        if self._table_version != self.table.version:
-            self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
-            self._table_version = self.table.version
+        per_x = _shared_or_per_member(x, "x", self.G, (n, d))
         x = ops._f32c(x)
-        dk = d if d % 4 == 0 else 4 * ((d + 3) // 4)  # the forward reads rows padded to 4 columns, the reward rows of d
-        xk = x if dk == d else pad_cols(self._pads, x, dk, 0, dev)
         img0, simg = self._images()
-        return x, xk, dk, tiles_dev, tb.tiles.shape[0], img0, simg
+        sx = x.stride(0) if per_x else 0
+        if not forward:
+            return _AcquireCall(n, M, x, sx, img0, simg)
+        tiles_dev = self.tables(n, n, M)[1]
+        self.table.update(1, 0.0, 1.0, False, 0)  # (the loop reads the seeds only)
+        self._sync_table()
+        xk = x if self.dk == d else pad_cols(self._pads, x, self.dk, 0, self.dev)  # (the reward reads rows of d columns)
+        return _AcquireCall(n, M, x, sx, img0, simg, xk, xk.stride(0) if per_x else 0, tiles_dev, max_blocks)
 
-    def _forward(self, xk, maskk, dk, tiles_dev, T, img0, simg, n, R, eps_plane, seps, offset, mode, out, out_stride, max_blocks):
+    def _forward(self, c, strides, maskk, eps_plane, offset, mode, out, out_stride):
         lay = self.lay
-        strides = [0] * 9  # VPC_MS_* of include/vpc.h
-        strides[0] = xk.stride(0) if xk.dim() == 3 else 0
-        strides[1], strides[3], strides[4] = maskk.stride(0), seps, simg
-        ops.impute_small_multi_f32(xk, maskk, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, self.G,
-                                   tiles_dev, T, n, R, eps_plane is None, offset, self.models[0]._x_logvar_value, mode, out,
-                                   out_stride, strides, dk, lay.d, lay.L, max_blocks)
+        ops.impute_small_multi_f32(c.xk, maskk, eps_plane, c.img0[:lay.enc_img], c.img0[lay.enc_img:], self.table_dev, self.G,
+                                   c.tiles_dev, c.tiles_dev.shape[0], c.n, c.M * c.n, eps_plane is None, offset,
+                                   self.models[0]._x_logvar_value, mode, out, out_stride, strides, c.xk.shape[-1], lay.d, lay.L,
+                                   c.max_blocks)
 
     def impute(self, x, mask, M, mode=0, *, eps=None, max_blocks=0):
         """ONE forward call of the loop under a given mask [G, n, d] (or [n, d], shared): mode 0 -> x_hat of the M passes
         [G, M, n, d] (`im`), mode 1 -> the target column's squared error per draw row [G, M n].  eps: [M n, L] or [G, M n, L],
         or None: drawn at the next eval_draw_counters offset."""
-        G, lay = self.G, self.lay
-        d, Ld = lay.d, lay.L
+        G, lay, d, Ld = self.G, self.lay, self.lay.d, self.lay.L
         n, _, _, R = acquire_plan(G, d, Ld, x.shape, M)
-        if eps is not None and tuple(eps.shape) not in ((R, Ld), (G, R, Ld)):
-            raise L.VpcError(f"eps: expected [{R}, {Ld}] or [{G}, {R}, {Ld}], got {tuple(eps.shape)}")
-        if tuple(mask.shape) not in ((n, d), (G, n, d)) or mode not in (0, 1):
-            raise L.VpcError(f"mask: expected [{n}, {d}] or [{G}, {n}, {d}], got {tuple(mask.shape)}; mode 0 or 1, got {mode}")
+        if eps is not None:
+            _shared_or_per_member(eps, "eps", G, (R, Ld))
+        _shared_or_per_member(mask, "mask", G, (n, d))
+        if mode not in (0, 1):
+            raise L.VpcError(f"mode 0 or 1, got {mode}")
         L.require_cuda(x, mask, eps)
-        x, xk, dk, tiles_dev, T, img0, simg = self._setup(x, n, M)
-        maskk = torch.zeros(G, n, dk, dtype=torch.uint8, device=self.dev)
+        c = self._setup(x, n, M, max_blocks=max_blocks)
+        maskk = torch.zeros(G, n, c.xk.shape[-1], dtype=torch.uint8, device=self.dev)
         maskk[:, :, :d].copy_(as_mask_u8(mask))
-        offset, plane, seps = 0, None, 0
-        if eps is None:
-            offset, self.rng_offset = eval_draw_counters(self.rng_offset, R, LP)
-        else:
-            plane = torch.zeros(*eps.shape[:-1], LP, device=self.dev)
-            plane[..., :Ld].copy_(eps)
-            seps = plane.stride(0) if plane.dim() == 3 else 0
+        [(offset, plane)], seps = self._draws(None if eps is None else eps.unsqueeze(-3), R)
         out = torch.empty((G, M, n, d) if mode == 0 else (G, R), device=self.dev)
-        self._forward(xk, maskk, dk, tiles_dev, T, img0, simg, n, R, plane, seps, offset, mode, out, out.stride(0), max_blocks)
-        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
-        self.launches = (T + per - 1) // per
+        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg})
+        self._forward(c, strides, maskk, plane, offset, mode, out, out.stride(0))
+        self.launches = forward_launches(c.tiles_dev.shape[0], G, max_blocks)
         return out
 
     def _reward_workspaces(self, n, M, ws_floats):
@@ -648,15 +652,18 @@ class EnsembleAcquirer(EnsembleEvaluator):
             self._reward_ws_key = key
         return sizes, chunk
 
-    def _reward(self, x, mask, im, R, img0, simg, sizes, chunk, n, M):
-        """x [n, d] or [G, n, d] fp32, mask [G, n, d] bytes, im / R: [G, ...] views whose member slices are dense."""
+    def _reward_strides(self, c, mask, im, R, sizes):
+        return stride_vector(ops.RM_COUNT, {
+            ops.RM_X: c.sx, ops.RM_MASK: mask.stride(0), ops.RM_IM: im.stride(0), ops.RM_PARAM: self.params.stride(0),
+            ops.RM_IMG: c.simg, ops.RM_PRE: sizes[0], ops.RM_STAT: sizes[1], ops.RM_W1T: sizes[2], ops.RM_R: R.stride(0)})
+
+    def _reward(self, c, strides, mask, im, R, chunk):
+        """mask [G, n, d] bytes, im / R: [G, ...] views whose member slices are dense; strides: _reward_strides of such views."""
         lay = self.lay
         w1 = self.params[0]  # seq_encoder.0.weight [100][d] opens a member's row of the parameter stack, its bias follows
         pre, stat, w1t = self._reward_ws
-        strides = (x.stride(0) if x.dim() == 3 else 0, mask.stride(0), im.stride(0), self.params.stride(0), simg, sizes[0],
-                   sizes[1], sizes[2], R.stride(0))  # VPC_RM_* of include/vpc.h
-        ops.reward_matrix_multi(x, mask, im[0], w1, w1[100 * lay.d:], img0[:lay.enc_img], pre, stat, w1t, R[0], self.G, chunk,
-                                strides, n, lay.d, lay.L, M)
+        ops.reward_matrix_multi(c.x, mask, im[0], w1, w1[100 * lay.d:], c.img0[:lay.enc_img], pre, stat, w1t, R[0], self.G, chunk,
+                                strides, c.n, lay.d, lay.L, c.M)
 
     def reward(self, x, mask, im, *, ws_floats=REWARD_WS_FLOATS):
         """R [G, n, d-1] of ONE acquisition step: member g's reward_matrix on x (shared [n, d] or [G, n, d]), its mask [G, n, d]
@@ -668,11 +675,11 @@ class EnsembleAcquirer(EnsembleEvaluator):
             raise L.VpcError(f"mask: expected [{G}, {n}, {d}], got {tuple(mask.shape)}; im: expected [{G}, M, {n}, {d}], got "
                              f"{tuple(im.shape)}")
         L.require_cuda(x, mask, im)
-        self.params = stack_models(self.models)
-        img0, simg = self._images()
+        c = self._setup(x, n, M, forward=False)
         sizes, chunk = self._reward_workspaces(n, M, ws_floats)
         R = torch.empty(G, n, d - 1, device=self.dev)
-        self._reward(ops._f32c(x), as_mask_u8(mask), ops._f32c(im), R, img0, simg, sizes, chunk, n, M)
+        mask, im = as_mask_u8(mask), ops._f32c(im)
+        self._reward(c, self._reward_strides(c, mask, im, R, sizes), mask, im, R, chunk)
         self.launches = 3 * ((G + chunk - 1) // chunk)
         return R
 
@@ -685,21 +692,14 @@ class EnsembleAcquirer(EnsembleEvaluator):
         im_hist [G, repeats, d-1, M, n, d] or None when keep_im is false); slots past max_steps stay zero.
         max_blocks: workgroups per forward launch (0: the library's limit); ws_floats: bound of the reward workspaces (members
         go through them in chunks).  `launches`: the library's kernel launches of the call, `launches_per_step` of one step."""
-        G, lay = self.G, self.lay
-        d, Ld = lay.d, lay.L
+        G, lay, d, Ld = self.G, self.lay, self.lay.d, self.lay.L
         n, steps, calls, R = acquire_plan(G, d, Ld, x.shape, M, repeats, max_steps, None if eps is None else eps.shape)
         L.require_cuda(x, eps)
         dev = self.dev
-        x, xk, dk, tiles_dev, T, img0, simg = self._setup(x, n, M)
-        draw = eps is None
-        if draw:
-            offs, self.rng_offset = acquire_draw_offsets(self.rng_offset, R, steps, repeats)
-            eps_buf, seps = None, 0
-        else:
-            offs = [0] * calls
-            eps_buf = torch.zeros(*eps.shape[:-1], LP, device=dev)
-            eps_buf[..., :Ld].copy_(eps)
-            seps = eps_buf.stride(0) if eps_buf.dim() == 4 else 0
+        c = self._setup(x, n, M, max_blocks=max_blocks)
+        dk = c.xk.shape[-1]
+        draws, seps = self._draws(eps, R, calls)
+        draws = iter(draws)  # (offset, eps plane) of the forward calls in issue order
         info = torch.zeros(G, repeats, d, device=dev)
         action = torch.zeros(G, repeats, n, d - 1, dtype=torch.int32, device=dev)
         R_hist = torch.zeros(G, repeats, d - 1, n, d - 1, device=dev)
@@ -709,15 +709,14 @@ class EnsembleAcquirer(EnsembleEvaluator):
         mask = torch.zeros(G, n, d, dtype=torch.uint8, device=dev)
         maskk = mask if dk == d else torch.zeros(G, n, dk, dtype=torch.uint8, device=dev)
         sizes, chunk = self._reward_workspaces(n, M, ws_floats)
-        per = max(1, (max_blocks or EVAL_MAX_BLOCKS) // G)
-        f_launches, r_launches = (T + per - 1) // per, 3 * ((G + chunk - 1) // chunk)
-        call = [0]
+        f_launches, r_launches = forward_launches(c.tiles_dev.shape[0], G, max_blocks), 3 * ((G + chunk - 1) // chunk)
+        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg})
+
+        r_strides = self._reward_strides(c, mask, im_hist[:, 0, 0] if keep_im else im_buf, R_hist[:, 0, 0], sizes)
 
         def forward(mode, out, out_stride):
-            c = call[0]
-            call[0] += 1
-            e = None if draw else (eps_buf[0, c] if eps_buf.dim() == 4 else eps_buf[c])
-            self._forward(xk, maskk, dk, tiles_dev, T, img0, simg, n, R, e, seps, offs[c], mode, out, out_stride, max_blocks)
+            offset, plane = next(draws)
+            self._forward(c, strides, maskk, plane, offset, mode, out, out_stride)
 
         def curve_point(r, t):
             forward(1, sq, sq.stride(0))
@@ -733,7 +732,7 @@ class EnsembleAcquirer(EnsembleEvaluator):
                 im = im_hist[:, r, t] if keep_im else im_buf
                 forward(0, im[0], im.stride(0))
                 Rt = R_hist[:, r, t]
-                self._reward(x, mask, im, Rt, img0, simg, sizes, chunk, n, M)
+                self._reward(c, r_strides, mask, im, Rt, chunk)
                 ops.acquire_multi(Rt[0], Rt.stride(0), mask, mask.stride(0), d, None if maskk is mask else maskk,
                                   maskk.stride(0), dk, action[0, r, :, t:], action.stride(0), d - 1, G, n, d)
                 curve_point(r, t + 1)

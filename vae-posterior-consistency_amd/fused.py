@@ -30,7 +30,7 @@ from . import ops
 from .images import PackedImage
 from .models import Reg_VAE, loss_coefficients, vanilla_VAE  # noqa: F401  (also reached as fused.loss_coefficients)
 from .ops import H1P, H2P, as_mask_u8
-from .trainer import _FlatAdamTrainer, draw_counters, pad_cols
+from .trainer import _FlatAdamTrainer, draw_counters, pad_cols, padded_width
 
 LP = 16  # row pitch of the padded latent workspaces
 
@@ -143,7 +143,7 @@ class FusedTrainer(_FlatAdamTrainer):
         # that spill, profiles/r01_kernel_resources.txt): instead the inputs are copied into arrays padded to a multiple of
         # 4 columns with mask 0 in the padding - never observed, so it adds nothing to any sum or gradient, and the weight
         # images already hold zeros for the columns / rows past obs_dim - and the 16-byte-vector variants run on those.
-        dk = d if (d % 4 == 0 or lay.mask_augm) else 4 * ((d + 3) // 4)
+        dk = padded_width(d, lay.mask_augm)
         if dk != d:
             x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
             if mask_p is not None:

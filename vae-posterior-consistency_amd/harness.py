@@ -24,13 +24,14 @@ data treatment and whether the loader comes alone (MNAR) or as a pair.
 """
 from __future__ import annotations
 
+import itertools
 import os
 
 import torch
 
 from . import _lib as L
 from . import ops
-from .ensemble import EnsembleEvaluator, EnsembleTrainer, stackable
+from .ensemble import EnsembleEvaluator, EnsembleTrainer, stackable, steps_in_ensemble
 from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
@@ -164,6 +165,56 @@ def _model_for_eval(model, device, *loader_args, **loader_kw):
     return model.to(device)
 
 
+# ------------------------------------------------------------------------------------------------ the frame of the sweeps
+def _sweep_configs(configs, models=None, loaders=None):
+    """A sweep's configs with their defaults filled in; `models` and `loaders`, where given, hold one entry per config."""
+    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
+    for given, what in ((models, "models"), (loaders, "loaders")):
+        if given is not None and len(given) != len(cfgs):
+            raise L.VpcError(f"{len(given)} {what} for {len(cfgs)} configurations")
+    return cfgs
+
+
+def _sweep_models(cfgs, models, device, *loader_args, **loader_kw):
+    """One model per member on `device`: models[g], else its checkpoint (model_loader('test', *loader_args, vae_type, ...))."""
+    return [_model_for_eval(None if models is None else models[g], device, *loader_args, c["vae_type"], alpha=c["alpha"],
+                            p_missingness=c["p_missingness"], **loader_kw) for g, c in enumerate(cfgs)]
+
+
+def _stack_key(model):
+    """(class, reg_type), what the members of one ensemble share (ensemble.validate_members); None: not stackable."""
+    return (type(model), getattr(model, "reg_type", None)) if stackable(model) else None
+
+
+def _group(keys):
+    """THE split of a sweep, from one key per member: ({key: [member indices]}, [indices whose key is None: they go alone])."""
+    groups, alone = {}, []
+    for g, k in enumerate(keys):
+        (alone if k is None else groups.setdefault(k, [])).append(g)
+    return groups, alone
+
+
+def eval_groups(models):
+    """How eval_sweep splits its members: ({(class, reg_type): [member indices]}, [indices evaluated one by one]).  Stackable
+    members (ensemble.stackable) of one class and reg_type share an EnsembleEvaluator; every other family goes alone."""
+    return _group([_stack_key(m) for m in models])
+
+
+class _LoadersDiffer(L.VpcError):
+    """_lock_step: the loaders ran out at different steps, or the batches of one step differ."""
+
+
+def _lock_step(loaders, batch_key):
+    """Iterate several loaders together: one tuple of batches (one per loader) per step.  All must end at the same step, and
+    the batches of a step must agree in batch_key(batch): else _LoadersDiffer."""
+    for batches in itertools.zip_longest(*loaders):
+        if any(b is None for b in batches):
+            raise _LoadersDiffer("per-member loaders must have the same number of batches")
+        if len({batch_key(b) for b in batches}) != 1:
+            raise _LoadersDiffer("per-member loaders must yield equal batch shapes at every step")
+        yield batches
+
+
 def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
           experiment_type, vae_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), alpha=1.0,
           stage="train", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True,
@@ -230,57 +281,33 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
     (a mixed list is split into such groups); every other family, and batches beyond the small-batch step, go through train()
     one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints the
     reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
-    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
-    G = len(cfgs)
-    if models is not None and len(models) != G:
-        raise L.VpcError(f"{len(models)} models for {G} configurations")
-    if loaders is not None and len(loaders) != G:
-        raise L.VpcError(f"{len(loaders)} loaders for {G} configurations")
-    member_loader = (lambda g: loaders[g]) if loaders is not None else (lambda g: data_loader_train)
-    out = [None] * G
-    groups = {}
+    cfgs = _sweep_configs(configs, models, loaders)
+    out, keys = [], []
     for g, c in enumerate(cfgs):
-        vt = c["vae_type"]
+        loader = data_loader_train if loaders is None else loaders[g]
         m = models[g] if models is not None else model_loader(
             "train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters, max_epochs, train_k,
-            num_estimates, experiment_type, reg_type, vt, alpha=c["alpha"], p_missingness=c["p_missingness"])
-        m.to(device)
-        out[g] = m
-        small = stackable(m) and "with_drop" not in vt
-        if small:  # the batch must fit the small-batch step (larger ones fill the chip on their own)
-            first = next(iter(member_loader(g)[0]), None)
-            small = first is not None and first[0].reshape(-1, obs_dim).shape[0] <= ops.step_small_max_rows()
-        if not small:
-            train(member_loader(g), missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
-                  experiment_type, vt, train_k, num_estimates, max_epochs, device, c["alpha"], stage, c["p_missingness"],
-                  reg_type, beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
-            continue
-        rt = getattr(m, "reg_type", None)
-        ml_on = rt == "ml_reg" and c["alpha"] != 0.0  # (members of one step agree on whether the third eps plane is drawn)
-        groups.setdefault((type(m), rt, ml_on), []).append(g)
-    for idx in groups.values():
-        ms = [out[g] for g in idx]
-        ens = EnsembleTrainer(ms, lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
-        alphas = [cfgs[g]["alpha"] for g in idx]
-        pms = [cfgs[g]["p_missingness"] for g in idx]
+            num_estimates, experiment_type, reg_type, c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"])
+        out.append(m.to(device))
+        # eval_groups' key and whether the third eps plane is drawn (the members of one step agree on it), or None: alone
+        keys.append(_stack_key(m) + (getattr(m, "reg_type", None) == "ml_reg" and c["alpha"] != 0.0,)
+                    if steps_in_ensemble(m, c["vae_type"], loader[0], obs_dim) else None)
+        if keys[g] is None:  # at once: before the next member is built
+            train(loader, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters, experiment_type,
+                  c["vae_type"], train_k, num_estimates, max_epochs, device, c["alpha"], stage, c["p_missingness"], reg_type,
+                  beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
+    rows = lambda t: t.to(device).reshape(-1, obs_dim)
+    for idx in _group(keys)[0].values():
+        ens = EnsembleTrainer([out[g] for g in idx], lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
+        alphas, pms = [cfgs[g]["alpha"] for g in idx], [cfgs[g]["p_missingness"] for g in idx]
+        sources = [data_loader_train[0]] if loaders is None else [loaders[g][0] for g in idx]
         for i in range(max_epochs):
-            if loaders is None:
-                for data_sample, mask in data_loader_train[0]:
-                    ens.step(data_sample.to(device).reshape(-1, obs_dim), mask.to(device).reshape(-1, obs_dim), epoch=i + 1,
-                             alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
-            else:
-                its = [iter(loaders[g][0]) for g in idx]
-                while True:
-                    batches = [next(it, None) for it in its]
-                    if all(b is None for b in batches):
-                        break
-                    if any(b is None for b in batches):
-                        raise L.VpcError("per-member loaders must have the same number of batches")
-                    if any(b[0].shape != batches[0][0].shape or b[1].shape != batches[0][1].shape for b in batches):
-                        raise L.VpcError("per-member loaders must yield equal batch shapes at every step")
-                    x = torch.stack([b[0].to(device).reshape(-1, obs_dim) for b in batches])
-                    mk = torch.stack([b[1].to(device).reshape(-1, obs_dim) for b in batches])
-                    ens.step(x, mk, epoch=i + 1, alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
+            for batches in _lock_step(sources, lambda b: (b[0].shape, b[1].shape)):  # (raises when the loaders differ)
+                if loaders is None:  # one batch shared by the members
+                    x, mk = rows(batches[0][0]), rows(batches[0][1])
+                else:
+                    x, mk = torch.stack([rows(b[0]) for b in batches]), torch.stack([rows(b[1]) for b in batches])
+                ens.step(x, mk, epoch=i + 1, alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
             totals = ens.epoch_total()
             if verbose:
                 for g, total_loss in zip(idx, totals):
@@ -309,6 +336,11 @@ def result_paths(experiment_type, data_type, vae_type, loader_stage, missing_rat
     return dict(rmse=os.path.join(rest, pre + "_rmse" + suf), elbo=os.path.join(elbo, pre + "_vae_elbo" + suf),
                 negll=os.path.join(rest, pre + "_negative_llh_q" + suf),
                 negll_imp=os.path.join(rest, pre + "_negative_llh_q_imputed" + suf))
+
+
+def _save_results(res, paths):  # the files of one result dict: res[k] under paths[k]
+    for k, pth in paths.items():
+        _save(res[k], pth)
 
 
 def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
@@ -348,23 +380,9 @@ def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, dat
                      negll_imp=torch.stack(res_negll_imp).mean())
             out[loader_stage] = {k: v.cpu() for k, v in r.items()}
             if save:
-                paths = result_paths(experiment_type, data_type, vae_type, loader_stage, missing_rate, alpha,
-                                     p_missingness, reg_type)
-                for k, pth in paths.items():
-                    _save(out[loader_stage][k], pth)
+                _save_results(out[loader_stage], result_paths(experiment_type, data_type, vae_type, loader_stage, missing_rate,
+                                                              alpha, p_missingness, reg_type))
     return out
-
-
-def eval_groups(models):
-    """How eval_sweep splits its members: ({(class, reg_type): [member indices]}, [indices evaluated one by one]).  Stackable
-    members (ensemble.stackable) of one class and reg_type share an EnsembleEvaluator; every other family goes alone."""
-    groups, alone = {}, []
-    for g, m in enumerate(models):
-        if stackable(m):
-            groups.setdefault((type(m), getattr(m, "reg_type", None)), []).append(g)
-        else:
-            alone.append(g)
-    return groups, alone
 
 
 def _gather_passes(sources, M, obs_dim, device):
@@ -373,26 +391,21 @@ def _gather_passes(sources, M, obs_dim, device):
     [G, R, d]; batches = M lists of (row_lo, row_hi) into them.  None when the members' loaders do not yield the same batch
     sizes at every step (one evaluate call needs one layout)."""
     xs, ms, ranges, r = [[] for _ in sources], [[] for _ in sources], [], 0
-    for _ in range(M):
-        its, pr = [iter(s) for s in sources], []
-        while True:
-            bs = [next(it, None) for it in its]
-            if all(b is None for b in bs):
-                break
-            if any(b is None for b in bs):
+    try:
+        for _ in range(M):
+            pr = []
+            for bs in _lock_step(sources, lambda b: b[0].reshape(-1, obs_dim).shape[0]):
+                for k, b in enumerate(bs):
+                    xs[k].append(b[0].to(device).reshape(-1, obs_dim))
+                    ms[k].append(b[1].to(device).reshape(-1, obs_dim))
+                n = xs[0][-1].shape[0]
+                pr.append((r, r + n))
+                r += n
+            if not pr:
                 return None
-            rows = {b[0].reshape(-1, obs_dim).shape[0] for b in bs}
-            if len(rows) != 1:
-                return None
-            for k, b in enumerate(bs):
-                xs[k].append(b[0].to(device).reshape(-1, obs_dim))
-                ms[k].append(b[1].to(device).reshape(-1, obs_dim))
-            n = rows.pop()
-            pr.append((r, r + n))
-            r += n
-        if not pr:
-            return None
-        ranges.append(pr)
+            ranges.append(pr)
+    except _LoadersDiffer:
+        return None
     x, mk = [torch.cat(v) for v in xs], [torch.cat(v) for v in ms]
     return (x[0], mk[0], ranges) if len(sources) == 1 else (torch.stack(x), torch.stack(mk), ranges)
 
@@ -402,9 +415,8 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
                reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, models=None, loaders=None, save=True):
     """eval_vae() for a LIST of runs - the evaluation that follows every train() of the drivers' loops
     (src/experiment_main/imputation.py:51-59 around evaluate.py:136-297) as one call; the twin of train_sweep, with its
-    conventions.  configs: one dict per member with the keys vae_type, alpha (1.0), p_missingness (30), seed (0).
-    list_loaders: what eval_vae takes, shared by every member; or loaders = one such list per member.  models (optional): one
-    model per member, else each member's checkpoint through model_loader('test', ...).
+    conventions for configs.  list_loaders: what eval_vae takes, shared by every member; or loaders = one such list per
+    member.  models (optional): one model per member, else each member's checkpoint through model_loader('test', ...).
     Plain Reg_VAE / vanilla_VAE members of one class and reg_type are evaluated together: per (loader, loader_stage) the
     loader is iterated once per MC pass (a shuffling loader gives every pass its own partition into batches), the batches
     are gathered on the device and ONE ensemble.EnsembleEvaluator.evaluate call computes every member x pass x batch.  Every
@@ -415,17 +427,11 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
     them, and under Philox there is no stream position to preserve); eps comes from the member's Philox stream (seed =
     the config's seed), not from torch.randn; a shared loader is iterated once per pass for the whole group, not once per
     member.  The estimator and its distribution are the same."""
-    cfgs = [{"alpha": 1.0, "p_missingness": 30, "seed": 0, **c} for c in configs]
-    G = len(cfgs)
-    if models is not None and len(models) != G:
-        raise L.VpcError(f"{len(models)} models for {G} configurations")
-    if loaders is not None and len(loaders) != G:
-        raise L.VpcError(f"{len(loaders)} loaders for {G} configurations")
+    cfgs = _sweep_configs(configs, models, loaders)
     member_loaders = (lambda g: loaders[g]) if loaders is not None else (lambda g: list_loaders)
-    ms = [_model_for_eval(models[g] if models is not None else None, device, obs_dim, hid_dim, K, latent_dim, missing_rate,
-                          data_type, training_parameters, max_epochs, valid_k, num_estimates, experiment_type, reg_type,
-                          c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"]) for g, c in enumerate(cfgs)]
-    out = [None] * G
+    ms = _sweep_models(cfgs, models, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                       max_epochs, valid_k, num_estimates, experiment_type, reg_type)
+    out = [None] * len(cfgs)
 
     def alone(g):
         c = cfgs[g]
@@ -438,10 +444,8 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
         alone(g)
     for idx in groups.values():
         stages = [s for _, s in member_loaders(idx[0])]
-        gathered = []
-        for li in range(len(stages)):
-            sources = [list_loaders[li][0]] if loaders is None else [loaders[g][li][0] for g in idx]
-            gathered.append(_gather_passes(sources, M, obs_dim, device))
+        gathered = [_gather_passes([list_loaders[li][0]] if loaders is None else [loaders[g][li][0] for g in idx], M, obs_dim,
+                                   device) for li in range(len(stages))]
         if any(t is None for t in gathered) or any([s for _, s in member_loaders(g)] != stages for g in idx):
             for g in idx:
                 alone(g)
@@ -456,10 +460,8 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
                     res = out[g][loader_stage] = dict(rmse=r[k, 0].clone(), elbo=r[k, 1].clone(), negll=r[k, 2].clone(),
                                                       negll_imp=r[k, 3].clone())
                     if save:
-                        paths = result_paths(experiment_type, data_type, cfgs[g]["vae_type"], loader_stage, missing_rate,
-                                             cfgs[g]["alpha"], cfgs[g]["p_missingness"], reg_type)
-                        for name, pth in paths.items():
-                            _save(res[name], pth)
+                        _save_results(res, result_paths(experiment_type, data_type, cfgs[g]["vae_type"], loader_stage,
+                                                        missing_rate, cfgs[g]["alpha"], cfgs[g]["p_missingness"], reg_type))
     return out
 
 

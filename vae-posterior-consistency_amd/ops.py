@@ -147,6 +147,20 @@ def step_small_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_
     return nb.value
 
 
+# Slots of the member-stride vectors of include/vpc.h: VPC_MS_* (ensemble step, evaluation, imputation), VPC_RM_* (reward)
+MS_X, MS_MASK, MS_MASK_P, MS_EPS, MS_IMG, MS_PARTE, MS_PARTD, MS_LOSS, MS_PARAM, MS_COUNT = range(10)
+MS_PART = MS_LOSS  # the evaluation's per-tile sums [tiles][5] doubles travel in the loss slot
+RM_X, RM_MASK, RM_IM, RM_PARAM, RM_IMG, RM_PRE, RM_STAT, RM_W1T, RM_R, RM_COUNT = range(10)
+
+
+def stride_vector(count, slots):
+    """A member-stride vector of `count` slots: `slots` = {slot: stride in elements}, every slot not named is 0."""
+    v = [0] * count
+    for k, s in slots.items():
+        v[k] = s
+    return v
+
+
 def _member_strides(strides):
     return (C.c_long * len(strides))(*[int(v) for v in strides])
 

@@ -45,6 +45,12 @@ def eval_draw_counters(rng_offset, draw_rows, pitch=16):
     return rng_offset, rng_offset + draw_rows * (pitch // 4)
 
 
+def padded_width(d, mask_augm=False):
+    """Row pitch of the kernels' x / mask arrays: d rounded up to a multiple of 4 columns, so that the 16-byte-vector kernel
+    variants run (FusedTrainer.step says why); the mask-augmented layouts take their rows unpadded."""
+    return d if (d % 4 == 0 or mask_augm) else 4 * ((d + 3) // 4)
+
+
 def pad_cols(pads, t, dk, slot, dev):
     """[..., B, d] -> zero-padded [..., B, dk]: a persistent buffer per input slot, kept in the dict `pads`."""
     key = (slot, tuple(t.shape[:-1]), dk, t.dtype)
