@@ -481,6 +481,25 @@ int vpc_step_small_draw_f32(const float* x, const float* enc_img, const float* d
                             unsigned long long offset_mask, unsigned long long offset_eps, const long long* state,
                             long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
                             void* stream);
+/* vpc_step_small_f32 / vpc_step_small_draw_f32 for the mask-augmented classes Reg_VAE_mask / vanilla_VAE_mask
+ * (src/models/VAE.py:545-555, 1031-1041: encoder input cat([x * mask, mask]); src/experiment_main/train.py:87-115): the images are
+ * those of the mask-augmented layout (vpc_layout_sizes / vpc_build_indices with mask_augm = 1), and the kernel's input stage builds
+ * the 2 d_real wide input - x_f m_f, then m_f, then zeros up to the tile edge - per pass, with mask[p].  d_real is obs_dim; d is
+ * the ROW PITCH of x and the masks, 4 ceil(d_real / 4), whose padding columns carry mask 0 (draws are made at that pitch).
+ * VPC_ERR_SHAPE when d_real < 1, d_real > d, d - d_real > 3, d % 4 != 0 or 2 d_real > 128; VPC_ERR_ARG on the pointer and
+ * alignment conditions of the plain entries; nothing is launched in either case.  All other arguments as there. */
+int vpc_step_small_aug_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
+                           const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                           const float* eps_ml, float inv_B, float x_logvar, float* partE,
+                           float* partD, double* loss_partials, int* nblocks_out, long B, int d, int d_real, int L, void* stream);
+int vpc_step_small_aug_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
+                                const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                                const float* eps_ml, float inv_B, float x_logvar,
+                                float* partE, float* partD, double* loss_partials, int* nblocks_out, long B, int d, int d_real, int L,
+                                const uint8_t* mask_in, float keep_prob, float* eps_out, long n_eps, unsigned long long seed,
+                                unsigned long long offset_mask, unsigned long long offset_eps, const long long* state,
+                                long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
+                                void* stream);
 
 /* ---- ensemble step: G independent models of ONE architecture in one pair of launches (csrc/vpc_small.hip, csrc/vpc_misc.hip).
  * The reference trains lists of tiny runs: src/experiment_main/imputation.py:21-39 wraps the step loop of

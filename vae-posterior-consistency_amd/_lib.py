@@ -60,6 +60,9 @@ _PROTOS = {
     "vpc_step_small_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, P],
     "vpc_step_small_draw_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, P, F, P, L_, ULL, ULL, ULL, P, L_, L_,
                                 L_, L_, I, P],
+    "vpc_step_small_aug_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, P],
+    "vpc_step_small_aug_draw_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, P, F, P, L_, ULL, ULL, ULL, P, L_,
+                                    L_, L_, L_, I, P],
     "vpc_step_small_multi_f32": [P, P, P, P, P, P, P, I, I, I, I, ULL, ULL, F, F, P, P, P, C.POINTER(L_), L_, I, I, I, P],
     "vpc_reduce_step_adam_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P],
     "vpc_eval_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],

@@ -48,6 +48,8 @@ struct SmallArgs {
     // optional in-kernel draws of the step (vpc_step_small_draw_f32): the workgroup draws the mask_p bytes and the eps values of ITS
     // 16 rows with the counters vpc_draw_step would use, stores them where the step reads them (m[1], eps[...]) and goes on
     int draw;                    // 0: inputs are given; 1: draw eps (and mask_p when mask_in != NULL)
+    int d_real;                  // mask-augmented kernels: obs_dim (d is the row pitch); in the padding in front of mask_in, so
+                                 // the argument offsets of the plain kernels stay what they were
     const uint8_t* mask_in;      // mask that mask_p thins (NULL: no mask draw - vanilla_VAE)
     float keep_prob;
     float* eps_out; long n_eps;  // [planes][B][16] planes of normals, n_eps floats in all
@@ -66,6 +68,17 @@ __device__ __forceinline__ f32x4 wgrad16(const float* da, int ta, const float* x
 
 template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_kernel(SmallArgs a) {
+    constexpr int DTI = DT;
+    constexpr bool AUG = false;
+    const unsigned tile_id = blockIdx.x;
+#include "vpc_small_body.h"
+}
+
+// Reg_VAE_mask / vanilla_VAE_mask (src/models/VAE.py:510-667, 995-1116): encoder input [x*mask | mask] of DTI = dt_for(2 d) tiles,
+// decoder output of DT = dt_for(d) tiles.
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void step_small_aug_kernel(SmallArgs a) {
+    constexpr bool AUG = true;
     const unsigned tile_id = blockIdx.x;
 #include "vpc_small_body.h"
 }
@@ -96,10 +109,13 @@ struct SmallDraw {
 static int step_small_launch(const float* x, const float* enc_img, const float* dec_img, int npass,
                              const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
                              const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
-                             int* nblocks_out, long B, int d, int L, const SmallDraw& dr, void* stream) {
+                             int* nblocks_out, long B, int d, int L, const SmallDraw& dr, void* stream, int d_real = 0) {
+    // d_real != 0: the mask-augmented kernels - obs_dim d_real in rows of pitch d = 4 ceil(d_real / 4), encoder input 2 d_real wide
+    const bool aug = d_real != 0;
     if (!x || !enc_img || !dec_img || !mask || !co || !eps || !partE || !partD || !loss_partials) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0) return VPC_ERR_ARG;
     if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (aug && (d_real < 1 || d_real > d || d - d_real > 3 || 2 * d_real > MAX_D)) return VPC_ERR_SHAPE;
     if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img)) return VPC_ERR_ARG;
     if (co->wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     SmallArgs a{};
@@ -107,7 +123,7 @@ static int step_small_launch(const float* x, const float* enc_img, const float* 
     a.loss_part = loss_partials;
     set_loss_coef(a, *co, npass);
     a.inv_B = inv_B; a.x_logvar = x_logvar;
-    a.B = B; a.d = d; a.L = L; a.npass = npass;
+    a.B = B; a.d = d; a.d_real = d_real; a.L = L; a.npass = npass;
     for (int p = 0; p < npass; ++p) {
         if (!mask[p] || !eps[p]) return VPC_ERR_ARG;
         a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.eps[p] = eps[p];
@@ -138,7 +154,19 @@ static int step_small_launch(const float* x, const float* enc_img, const float* 
         hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, a);                              \
         return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
     }
+#define VPC_CASE_AUG(TI, T)                                                                                \
+    case TI: {                                                                                             \
+        auto kern = step_small_aug_kernel<TI, T>;                                                          \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, a);                              \
+        return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
+    }
+    if (aug) {  // (input tiles, output tiles) = (dt_for(2 d_real), dt_for(d_real)): d_real <= 8, 16, 32, 64
+        switch (dt_for(2 * d_real)) { VPC_CASE_AUG(1, 1) VPC_CASE_AUG(2, 1) VPC_CASE_AUG(4, 2) VPC_CASE_AUG(8, 4) }
+        return VPC_ERR_SHAPE;
+    }
     switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
+#undef VPC_CASE_AUG
 #undef VPC_CASE
     return VPC_ERR_SHAPE;
 }
@@ -209,6 +237,7 @@ struct MemberArgs {
     long B;
     int d, L, npass;
     int draw;
+    int d_real;  // (read by the mask-augmented input stage only, which the ensemble kernels do not have)
     const uint8_t* mask_in;
     float keep_prob;
     float* eps_out; long n_eps;
@@ -220,6 +249,8 @@ struct MemberArgs {
 
 template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArgs ma) {
+    constexpr int DTI = DT;
+    constexpr bool AUG = false;
     // (tile, member) of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs by their linear id (x fastest).
     //   order 0: grid (tiles, G), id = g * tiles + t - the tiles of a member land on different XCDs, every L2 sees every
     //            member's images;
@@ -256,6 +287,7 @@ __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArg
     a.bq = r->co.bq; a.bp = r->co.bp; a.cr = r->co.cr; a.wml = r->co.wml; a.inv_B = b.inv_B; a.x_logvar = b.x_logvar;
     a.B = b.B; a.d = b.d; a.L = b.L; a.npass = b.npass;
     a.draw = b.draw;
+    a.d_real = b.d;
     a.mask_in = b.mask_in ? a.m.v0 : nullptr;
     a.keep_prob = r->keep_prob;
     a.eps_out = const_cast<float*>(a.eps.v0);
@@ -317,4 +349,33 @@ extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uin
     switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
 #undef VPC_CASE
     return VPC_ERR_SHAPE;
+}
+
+// The same step for Reg_VAE_mask / vanilla_VAE_mask (src/models/VAE.py:545-555, 1031-1041; src/experiment_main/train.py:87-115):
+// encoder input [x*mask | mask] of width 2 d_real built in the kernel's input stage, images of the mask-augmented layout.  d is the
+// row pitch of x and the masks, 4 ceil(d_real / 4), with mask 0 in the padding.
+extern "C" int vpc_step_small_aug_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
+                                      const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                      const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                      int* nblocks_out, long B, int d, int d_real, int L, void* stream) {
+    if (d_real < 1) return VPC_ERR_SHAPE;
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
+                             partD, loss_partials, nblocks_out, B, d, L, SmallDraw{}, stream, d_real);
+}
+
+extern "C" int vpc_step_small_aug_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
+                                           const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                           const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                           int* nblocks_out, long B, int d, int d_real, int L, const uint8_t* mask_in, float keep_prob,
+                                           float* eps_out, long n_eps, unsigned long long seed, unsigned long long offset_mask,
+                                           unsigned long long offset_eps, const long long* state, long mask_elem_lo,
+                                           long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch, void* stream) {
+    if (d_real < 1) return VPC_ERR_SHAPE;
+    if (eps_rows_local < 0 || (eps_rows_local > 0 && (eps_pitch != 16 || eps_rows_local != B || eps_row_lo < 0 ||
+                                                      eps_row_lo + eps_rows_local > eps_rows_global)))
+        return VPC_ERR_ARG;
+    SmallDraw dr{1, mask_in, keep_prob, eps_out, n_eps, seed, offset_mask, offset_eps, state, mask_elem_lo,
+                 EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch}};
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
+                             partD, loss_partials, nblocks_out, B, d, L, dr, stream, d_real);
 }

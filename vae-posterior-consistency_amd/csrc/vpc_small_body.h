@@ -1,18 +1,22 @@
 // The step of ONE 16-row tile: the BODY of the small-batch whole-step kernels of vpc_small.hip, included as text into
-//   step_small_kernel        (a = the SmallArgs kernel argument, tile_id = blockIdx.x) and
+//   step_small_kernel        (a = the SmallArgs kernel argument, tile_id = blockIdx.x),
+//   step_small_aug_kernel    (the same for the mask-augmented classes) and
 //   step_small_multi_kernel  (a = member g's arguments built in registers, MemberArgs - the same fields -, tile_id = the
 //                             member's tile),
 // so that both run ONE piece of code - a member of an ensemble computes bit for bit what its stand-alone step computes - and
 // the single-model kernel compiles to the instructions it had as a self-contained kernel (a shared inline function is
 // simplified before it is inlined, without knowing that `a` is the kernel-argument segment, and schedules differently).
-// In scope at the point of inclusion: template parameter DT, `a`, `const unsigned tile_id`; everything vpc_small.hip
-// declares before its kernels.  Partial blocks and loss terms go to slot tile_id of a.partE / a.partD / a.loss_part.
+// In scope at the point of inclusion: the compile-time tile counts DT (tiles of d: x / mask words of the loss, W6, the output
+// tiles, dW6) and DTI (tiles of the encoder INPUT: W1's k-tiles, the X buffers, dW1) and the flag AUG, `a`, `const unsigned
+// tile_id`; everything vpc_small.hip declares before its kernels.  Plain models: DTI == DT, AUG false.  AUG (Reg_VAE_mask /
+// vanilla_VAE_mask, src/models/VAE.py:545-548, 1031-1033): the encoder input is [x*mask | mask] of width 2 a.d_real, a.d is
+// the row pitch of x and the masks.  Partial blocks and loss terms go to slot tile_id of a.partE / a.partD / a.loss_part.
 // (No include guard: this is a code fragment, included once per kernel.)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     auto buf = [&](int b) { return lds + b * SBUF; };
     float* red = lds + B_COUNT * SBUF;
-    constexpr int S1 = s_for_tiles(DT);
-    const EncImg ei(DT);
+    constexpr int S1 = s_for_tiles(DTI);
+    const EncImg ei(DTI);
     const DecImg di(DT);
     // (re-derived from opaque base pointers in every tile / pass: the weights never change during the launch, and hipcc
     // otherwise hoists the global fragment loads of ALL layers out of the loops - 900 bytes of scratch per lane)
@@ -94,20 +98,37 @@
             float* X = buf(p == 0 ? B_XQ : B_XP);
             float* H1b = buf(p == 0 ? B_H1Q : B_H1P);
             float* H2b = buf(p == 0 ? B_H2Q : B_H2P);
-            f32x4 fW1[DT], fW2[H1T], fW3[H2T], bias1 = zero4();
+            f32x4 fW1[DTI], fW2[H1T], fW3[H2T], bias1 = zero4();
             if (w < H1T) {
-                ldW<DT, S1>(W1, w, cc, qq, fW1);
+                ldW<DTI, S1>(W1, w, cc, qq, fW1);
                 bias1 = *reinterpret_cast<const f32x4*>(b1 + 16 * w + 4 * qq);
             }
-            if (w < DT) st_act(X, w, cc, qq, xv * mask_to_f32(p == 0 ? mwq : mwp));  // x.float() * mask  (VAE.py:388)
+            if constexpr (!AUG) {
+                if (w < DT) st_act(X, w, cc, qq, xv * mask_to_f32(p == 0 ? mwq : mwp));  // x.float() * mask  (VAE.py:388)
+            } else {
+                // [x*mask | mask | 0] (ld_input<.., true> of vpc_enc.hip; VAE.py:545-548): element f < d is x_f m_f, d <= f < 2 d
+                // is m_{f-d}, 2 d <= f < 16 DTI is 0.  Column d is in general not 4-aligned, so every element is a dword store of
+                // its own; each column of the buffer has exactly one writer.  Rows past B: xv and the mask words are 0.
+                const f32x4 mk = mask_to_f32(p == 0 ? mwq : mwp), xm = xv * mk;
+                float* xrow = X + cc * SP;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int f = 16 * w + 4 * qq + j;
+                    if (w < DT && f < a.d_real) {
+                        xrow[f] = xm[j];
+                        xrow[a.d_real + f] = mk[j];
+                    }
+                    if (w < DTI && f >= 2 * a.d_real) xrow[f] = 0.f;
+                }
+            }
             if (w < H2T) ldW<H1T, 128>(W2, w, cc, qq, fW2);
             lds_barrier();
             launder(cc, qq);
             if (w < H1T) {
-                f32x4 in[DT];
+                f32x4 in[DTI];
 #pragma unroll
-                for (int t = 0; t < DT; ++t) in[t] = ld_act(X, t, cc, qq);
-                st_act(H1b, w, cc, qq, relu4(mmW<DT>(fW1, in, bias1)));
+                for (int t = 0; t < DTI; ++t) in[t] = ld_act(X, t, cc, qq);
+                st_act(H1b, w, cc, qq, relu4(mmW<DTI>(fW1, in, bias1)));
             }
             if (w < 2) ldW<H2T, 64>(W3, w, cc, qq, fW3);
             lds_barrier();
@@ -353,8 +374,8 @@
             }
             lds_barrier();
             launder(cc, qq);
-            // ---- dW1 (wave w < DT: in tile w, 7 out tiles)
-            if (w < DT) {
+            // ---- dW1 (wave w < DTI: in tile w, 7 out tiles)
+            if (w < DTI) {
 #pragma unroll
                 for (int mt = 0; mt < H1T; ++mt) acc1[mt] = wgrad16(buf(B_DH1), mt, X, w, acc1[mt], cc, qq);
             }
@@ -367,7 +388,7 @@
 #pragma unroll
             for (int mt = 0; mt < H1T; ++mt)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) part[(4 * mt + j) * 64] = (w < DT) ? acc1[mt][j] : 0.f;
+                for (int j = 0; j < 4; ++j) part[(4 * mt + j) * 64] = (w < DTI) ? acc1[mt][j] : 0.f;
 #pragma unroll
             for (int mt = 0; mt < H2T; ++mt)
 #pragma unroll

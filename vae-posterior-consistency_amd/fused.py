@@ -45,6 +45,11 @@ class FusedTrainer(_FlatAdamTrainer):
         the bf16 forms exist for Reg_VAE / vanilla_VAE with obs_dim % 4 == 0, both workgroup shapes (csrc/vpc_bf16.h).
         `precision` bounds the rounding a step may use; it does not choose the kernel: small batches run the fp32
         N-split kernel in every precision.
+        Mask-augmented models (Reg_VAE_mask / vanilla_VAE_mask) take the N-split kernel too at small batches.  There
+        x, mask and mask_p are padded to 4 * ceil(obs_dim / 4) columns (mask 0 in the padding) and the draw counters are
+        trainer.draw_counters at THAT pitch: for obs_dim % 4 == 0 the draws are bit for bit those of the row-tiled path
+        (VPC_STEP_SMALL=0, or a larger batch); for obs_dim % 4 != 0 the mask_p stream of a seed is the plain models'
+        stream at the padded pitch, not the unpadded one the row-tiled path draws.
         collective: carrier of the per-step bucket under data parallelism (dist.FlatAllReduce = ncclAllReduce on the
         compute stream); None = chosen on the first multi-rank step by dist.make_collective (RCCL when the process group
         is NCCL, torch.distributed.all_reduce otherwise)."""
@@ -136,6 +141,10 @@ class FusedTrainer(_FlatAdamTrainer):
         self._timer_tick += 1
         lay, m = self.lay, self.model
         B, d, Ld = x.shape[0], lay.d, lay.L
+        # Small batches run the fp32 N-split kernel (csrc/vpc_small.hip) in EVERY precision: `precision` bounds the rounding a step may
+        # use, and at these sizes the fp32 kernel is both the most accurate and the fastest form (B = 64: 41 us against 62 us for the
+        # bf16 engine's small-shape kernels).  VPC_STEP_SMALL=0 in the environment keeps the requested engine (tests of its kernels).
+        use_small = B <= ops.step_small_max_rows()  # (<= 16 x CUs rows)
         # ---- inputs and padding
         x = ops._f32c(x)
         mask = as_mask_u8(mask)
@@ -143,7 +152,8 @@ class FusedTrainer(_FlatAdamTrainer):
         # that spill, profiles/r01_kernel_resources.txt): instead the inputs are copied into arrays padded to a multiple of
         # 4 columns with mask 0 in the padding - never observed, so it adds nothing to any sum or gradient, and the weight
         # images already hold zeros for the columns / rows past obs_dim - and the 16-byte-vector variants run on those.
-        dk = padded_width(d, lay.mask_augm)
+        # The mask-augmented classes: unpadded rows for the row-tiled kernels, that padding rule for the N-split kernel.
+        dk = ops.small_aug_pitch(d) if (use_small and lay.mask_augm) else padded_width(d, lay.mask_augm)
         if dk != d:
             x, mask = pad_cols(self._pads, x, dk, 0, self.dev), pad_cols(self._pads, mask, dk, 1, self.dev)
             if mask_p is not None:
@@ -152,10 +162,6 @@ class FusedTrainer(_FlatAdamTrainer):
         Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
         two = not self.vanilla
-        # Small batches run the fp32 N-split kernel (csrc/vpc_small.hip) in EVERY precision: `precision` bounds the rounding a step may
-        # use, and at these sizes the fp32 kernel is both the most accurate and the fastest form (B = 64: 41 us against 62 us for the
-        # bf16 engine's small-shape kernels).  VPC_STEP_SMALL=0 in the environment keeps the requested engine (tests of its kernels).
-        use_small = not lay.mask_augm and B <= ops.step_small_max_rows()  # (<= 16 x CUs rows)
         self._used_step_small = use_small
         use_step = (not use_small) and bool(self.prec) and self._step_ok and ops.step_fused_applicable(B, dk, Ld, 2 if two else 1)
         self._used_step_fused = use_step
@@ -223,12 +229,15 @@ class FusedTrainer(_FlatAdamTrainer):
         maskB = [mask_p, None] if (two and co.maskB_on) else [None] * len(masks)
         if use_small:
             # small batch (fp32 arithmetic in every precision): the whole step in ONE launch, 16-row tiles with the feature
-            # tiles split over the waves
-            args = (x, *imgs, masks, maskB, co, epss, eml, inv_B, xlv, self.partE, self.partD, self.loss_part, dk, Ld)
+            # tiles split over the waves; the mask-augmented classes through the entries whose input stage builds [x*mask | mask]
+            args = (x, *imgs, masks, maskB, co, epss, eml, inv_B, xlv, self.partE, self.partD, self.loss_part, dk)
+            args += (lay.d, Ld) if lay.mask_augm else (Ld,)
+            fn, fn_draw = ((ops.step_small_aug_f32, ops.step_small_aug_draw_f32) if lay.mask_augm else
+                           (ops.step_small_f32, ops.step_small_draw_f32))
             if in_kernel is not None:
-                nb = self._timed("step_small", ops.step_small_draw_f32, *args, *in_kernel)
+                nb = self._timed("step_small", fn_draw, *args, *in_kernel)
             else:
-                nb = self._timed("step_small", ops.step_small_f32, *args)
+                nb = self._timed("step_small", fn, *args)
             return nb, nb
         if use_step:
             # plain bf16, throughput shape: encoder forward + decoder + loss + all backward in ONE launch

@@ -147,6 +147,47 @@ def step_small_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_
     return nb.value
 
 
+def small_aug_pitch(d):
+    """Row pitch of x / mask / mask_p on the small-batch path of the mask-augmented classes: 4 * ceil(d / 4), the plain
+    models' rule (mask 0 in the padding)."""
+    return 4 * ((d + 3) // 4)
+
+
+def small_aug_tiles(d):
+    """(DTI, DT) of the step_small_aug_kernel instantiation that serves obs_dim d: 16-wide tiles of the encoder input
+    [x*mask | mask] (2 d wide) and of the decoder output (d wide); None past the kernels' reach (2 d > 128)."""
+    dt_for = lambda n: 1 if n <= 16 else 2 if n <= 32 else 4 if n <= 64 else 8
+    return (dt_for(2 * d), dt_for(d)) if 1 <= d and 2 * d <= 128 else None
+
+
+def step_small_aug_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d, d_real,
+                       Ld):
+    """step_small_f32 of Reg_VAE_mask / vanilla_VAE_mask: `d` is the row pitch small_aug_pitch(d_real) of x and the masks,
+    the images are those of the mask-augmented layout; the kernel builds [x*mask | mask] itself."""
+    n = len(masks)
+    nb = C.c_int(0)
+    check(lib().vpc_step_small_aug_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                       ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE),
+                                       ptr(partD), ptr(loss_part), C.byref(nb), x.shape[0], d, d_real, Ld, stream_ptr()),
+          "vpc_step_small_aug_f32")
+    return nb.value
+
+
+def step_small_aug_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d,
+                            d_real, Ld, mask_in, keep_prob, eps_out, seed, offset_mask, offset_eps, state=None, elem_lo=0,
+                            eps_shard=None):
+    """step_small_aug_f32 that also makes the step's draws inside the launch (as step_small_draw_f32, at the pitch `d`)."""
+    n = len(masks)
+    nb = C.c_int(0)
+    check(lib().vpc_step_small_aug_draw_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                            ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE),
+                                            ptr(partD), ptr(loss_part), C.byref(nb), x.shape[0], d, d_real, Ld, ptr(mask_in),
+                                            float(keep_prob), ptr(eps_out), eps_out.numel(), int(seed), int(offset_mask),
+                                            int(offset_eps), ptr(state), int(elem_lo), *_shard4(eps_shard), stream_ptr()),
+          "vpc_step_small_aug_draw_f32")
+    return nb.value
+
+
 # Slots of the member-stride vectors of include/vpc.h: VPC_MS_* (ensemble step, evaluation, imputation), VPC_RM_* (reward)
 MS_X, MS_MASK, MS_MASK_P, MS_EPS, MS_IMG, MS_PARTE, MS_PARTD, MS_LOSS, MS_PARAM, MS_COUNT = range(10)
 MS_PART = MS_LOSS  # the evaluation's per-tile sums [tiles][5] doubles travel in the loss slot

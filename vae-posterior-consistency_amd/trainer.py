@@ -47,7 +47,8 @@ def eval_draw_counters(rng_offset, draw_rows, pitch=16):
 
 def padded_width(d, mask_augm=False):
     """Row pitch of the kernels' x / mask arrays: d rounded up to a multiple of 4 columns, so that the 16-byte-vector kernel
-    variants run (FusedTrainer.step says why); the mask-augmented layouts take their rows unpadded."""
+    variants run (FusedTrainer.step says why); the mask-augmented layouts take their rows unpadded (on the row-tiled path:
+    their small-batch step pads by ops.small_aug_pitch)."""
     return d if (d % 4 == 0 or mask_augm) else 4 * ((d + 3) // 4)
 
 
