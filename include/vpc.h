@@ -46,6 +46,15 @@ int vpc_layout_sizes(int d, int L, int mask_augm, int* enc_img_floats, int* dec_
  * img_template[enc_img_floats + dec_img_floats] (zeros plus the constant ones of the bias chain). */
 int vpc_build_indices(int d, int L, int mask_augm, int* pack_idx, int* grad_idx, float* img_template);
 
+/* The same pair for the point-net classes Reg_EDDI / vanilla_EDDI (src/models/VAE.py:694-700): the tiled part of the model is
+ * the trunk pnp_encoder2 K -> 100 -> 50 -> 2L as the encoder (input width K <= 32) and seq_decoder L -> 50 -> 100 -> d.
+ * n_params counts those twelve tensors in state_dict order (pack_idx / grad_idx cover them), n_front_params the four front-end
+ * tensors that follow them in the flat parameter vector of vpc_reduce_step_adam_eddi: type_pars1 [d][K], type_bias1 [d],
+ * pnp_encoder1.0.weight [K][2+K], pnp_encoder1.0.bias [K]. */
+int vpc_layout_sizes_pointnet(int d, int K, int L, int* enc_img_floats, int* dec_img_floats, int* n_enc_params, int* n_params,
+                              int* n_front_params, int* enc_part_floats, int* dec_part_floats, int* loss_terms, int* tile_rows);
+int vpc_build_indices_pointnet(int d, int K, int L, int* pack_idx, int* grad_idx, float* img_template);
+
 /* Compute units of the current device. */
 int vpc_num_cus(void);
 /* Upper bound of *nblocks_out of any kernel below (= 2 * CUs: the small-batch shape spreads the two passes over
@@ -500,6 +509,48 @@ int vpc_step_small_aug_draw_f32(const float* x, const float* enc_img, const floa
                                 unsigned long long offset_mask, unsigned long long offset_eps, const long long* state,
                                 long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
                                 void* stream);
+/* vpc_step_small_f32 / vpc_step_small_draw_f32 for the point-net classes Reg_EDDI / vanilla_EDDI: replaces the launch chain
+ * fold -> front-end -> three trunk GEMMs -> fused decoder -> trunk wgrads / dgrads -> front-end backward of the step
+ * (src/models/VAE.py:713-741, 897-925 encoder with the point-net front-end :719-733, 903-917; :743-747 decoder; :749-813, 933-964
+ * loss; src/experiment_main/train.py:87-115).  The images are those of vpc_build_indices_pointnet.  `front` holds the front-end
+ * parameters in flat order (type_pars1 [d_real][K] | type_bias1 [d_real] | pnp_encoder1.0.weight [K][2+K] | .bias [K]); every
+ * workgroup folds them (A_j = w_x + W_E E_j, C_j = w_t t_j + c) into LDS, builds agg[r][k] = sum_j m[r][j] relu(x[r][j] A_j[k] +
+ * C_j[k]) as the trunk's input, and in the backward pass goes on from dh1 to dagg = dh1 . W1 and the front-end's gradient block of
+ * its 16 rows: front_partials [tiles][2][K][d] = (dA | dC), both passes summed, no atomics.  Tile 0 copies `front` to
+ * front_snapshot [d_real K + d_real + K (2 + K) + K] for the chain rule of vpc_reduce_step_adam_eddi.  d_real is obs_dim; d is the
+ * ROW PITCH of x and the masks, 4 ceil(d_real / 4), mask 0 in the padding (draws are made at that pitch).
+ * VPC_ERR_SHAPE when K < 1, K > 32, d > 64, d % 4 != 0, d_real < 1, d_real > d or d - d_real > 3 (no instantiation: K <= 16 / 32
+ * against obs_dim <= 16 / 32 / 64); VPC_ERR_ARG on null pointers, x / images not 16-byte or front / front_partials /
+ * front_snapshot not 4-byte aligned, and the conditions of the plain entries; nothing is launched in either case. */
+int vpc_step_small_eddi_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
+                            const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                            const float* eps_ml, float inv_B, float x_logvar, float* partE,
+                            float* partD, double* loss_partials, int* nblocks_out, long B, int d, int d_real, int L, int K,
+                            const float* front, float* front_partials, float* front_snapshot, void* stream);
+int vpc_step_small_eddi_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass, const uint8_t* const* mask,
+                                 const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* eps,
+                                 const float* eps_ml, float inv_B, float x_logvar,
+                                 float* partE, float* partD, double* loss_partials, int* nblocks_out, long B, int d, int d_real, int L,
+                                 int K, const float* front, float* front_partials, float* front_snapshot,
+                                 const uint8_t* mask_in, float keep_prob, float* eps_out, long n_eps, unsigned long long seed,
+                                 unsigned long long offset_mask, unsigned long long offset_eps, const long long* state,
+                                 long mask_elem_lo, long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch,
+                                 void* stream);
+/* The tail behind them, ONE launch (train.py:114-117; replaces the reductions, vpc_eddi_front_bwd's tail and vpc_adam_step of the
+ * chain): vpc_reduce_step_adam over the trunk and decoder blocks and the loss terms (layout-order reduction: inv_maps of
+ * vpc_build_inverse_maps is required), and for the front-end the fixed-order sum of front_partials over the tiles, the chain rule
+ * from (dA, dC) to (type_pars1, type_bias1, pnp_encoder1.0.weight, .bias) - dE[j][e] = sum_k W_E[k][e] dA[k][j], dt[j] = sum_k
+ * w_t[k] dC[k][j], dW[k] = [sum_j dA | sum_j dA E[j][.] | sum_j dC t[j]], dc[k] = sum_j dC[k][j], with E, t, W read from
+ * front_snapshot - and Adam.  grad_out, params, exp_avg, exp_avg_sq: the model's flat vectors [trunk | decoder | front-end];
+ * n = trunk + decoder parameters (pack_idx [n], img: the point-net images, re-packed).  d = obs_dim, d_pitch the row pitch of the
+ * front-end blocks (<= 64). */
+int vpc_reduce_step_adam_eddi(const float* enc_partials, int enc_blocks, long enc_stride, const float* dec_partials,
+                              int dec_blocks, long dec_stride, const int* inv_maps, float* grad_out, int n,
+                              const double* loss_partials, int loss_blocks, const VpcLossCoef* co, long B_local, long B_global,
+                              int d, float* out9, float* accum, float* params, float* exp_avg, float* exp_avg_sq, float lr,
+                              float beta1, float beta2, float eps, long step, const int* pack_idx, float* img,
+                              const float* front_partials, int front_blocks, const float* front_snapshot, int K, int d_pitch,
+                              void* stream);
 
 /* ---- ensemble step: G independent models of ONE architecture in one pair of launches (csrc/vpc_small.hip, csrc/vpc_misc.hip).
  * The reference trains lists of tiny runs: src/experiment_main/imputation.py:21-39 wraps the step loop of

@@ -48,6 +48,8 @@ class VpcLossCoef(C.Structure):
 _PROTOS = {
     "vpc_layout_sizes": [I, I, I, IP, IP, IP, IP, IP, IP, IP, IP],
     "vpc_build_indices": [I, I, I, P, P, P],
+    "vpc_layout_sizes_pointnet": [I, I, I, IP, IP, IP, IP, IP, IP, IP, IP, IP],
+    "vpc_build_indices_pointnet": [I, I, I, P, P, P],
     "vpc_num_cus": [],
     "vpc_max_partial_blocks": [],
     "vpc_pack_weights": [P, P, P, I, P],
@@ -63,6 +65,11 @@ _PROTOS = {
     "vpc_step_small_aug_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, P],
     "vpc_step_small_aug_draw_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, P, F, P, L_, ULL, ULL, ULL, P, L_,
                                     L_, L_, L_, I, P],
+    "vpc_step_small_eddi_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, I, P, P, P, P],
+    "vpc_step_small_eddi_draw_f32": [P, P, P, I, PP, PP, P, PP, P, F, F, P, P, P, IP, L_, I, I, I, I, P, P, P, P, F, P, L_, ULL, ULL,
+                                     ULL, P, L_, L_, L_, L_, I, P],
+    "vpc_reduce_step_adam_eddi": [P, I, L_, P, I, L_, P, P, I, P, I, P, L_, L_, I, P, P, P, P, P, F, F, F, F, L_, P, P, P, I, P, I,
+                                  I, P],
     "vpc_step_small_multi_f32": [P, P, P, P, P, P, P, I, I, I, I, ULL, ULL, F, F, P, P, P, C.POINTER(L_), L_, I, I, I, P],
     "vpc_reduce_step_adam_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P],
     "vpc_eval_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],
@@ -224,21 +231,33 @@ def require_cuda(*tensors):
 
 
 class Layout:
-    """Sizes and index tables of the packed layouts for one (d, L)."""
+    """Sizes and index tables of the packed layouts for one (d, L).  pointnet_K > 0: the point-net kind (Reg_EDDI /
+    vanilla_EDDI on the small-batch step) - the encoder is the trunk with an input of pointnet_K columns, n_params counts trunk
+    and decoder, n_front the four front-end tensors behind them in the flat vector."""
 
-    def __init__(self, d: int, L: int, mask_augm: bool = False):
+    def __init__(self, d: int, L: int, mask_augm: bool = False, pointnet_K: int = 0):
         l = lib()
         self.mask_augm = int(bool(mask_augm))
+        self.K, self.n_front = pointnet_K, 0
         vals = [C.c_int() for _ in range(8)]
-        check(l.vpc_layout_sizes(d, L, self.mask_augm, *[C.byref(v) for v in vals]), "vpc_layout_sizes")
+        if pointnet_K:
+            nf = C.c_int()
+            refs = [C.byref(v) for v in vals]
+            check(l.vpc_layout_sizes_pointnet(d, pointnet_K, L, *refs[:4], C.byref(nf), *refs[4:]), "vpc_layout_sizes_pointnet")
+            self.n_front = nf.value
+        else:
+            check(l.vpc_layout_sizes(d, L, self.mask_augm, *[C.byref(v) for v in vals]), "vpc_layout_sizes")
         (self.enc_img, self.dec_img, self.n_enc, self.n_params, self.enc_part, self.dec_part, self.loss_terms,
          self.tile_rows) = [v.value for v in vals]
         self.d, self.L = d, L
         self.pack_idx = np.empty(self.n_params, np.int32)
         self.grad_idx = np.empty(self.n_params, np.int32)
         self.img_template = np.empty(self.enc_img + self.dec_img, np.float32)
-        check(l.vpc_build_indices(d, L, self.mask_augm, self.pack_idx.ctypes.data_as(P), self.grad_idx.ctypes.data_as(P),
-                                  self.img_template.ctypes.data_as(P)), "vpc_build_indices")
+        tables = (self.pack_idx.ctypes.data_as(P), self.grad_idx.ctypes.data_as(P), self.img_template.ctypes.data_as(P))
+        if pointnet_K:
+            check(l.vpc_build_indices_pointnet(d, pointnet_K, L, *tables), "vpc_build_indices_pointnet")
+        else:
+            check(l.vpc_build_indices(d, L, self.mask_augm, *tables), "vpc_build_indices")
         self._dev = {}
 
     def device_tables(self, device):
@@ -297,6 +316,11 @@ class Layout:
 @lru_cache(maxsize=None)
 def layout(d: int, L: int, mask_augm: bool = False) -> Layout:
     return Layout(d, L, mask_augm)
+
+
+@lru_cache(maxsize=None)
+def pointnet_layout(d: int, K: int, L: int) -> Layout:
+    return Layout(d, L, pointnet_K=K)
 
 
 _NCU = None

@@ -267,6 +267,101 @@ __global__ __launch_bounds__(256) void reduce_step_v2_kernel(const float* __rest
         }
     }
 }
+// ---- the same launch for Reg_EDDI / vanilla_EDDI after step_small_eddi_kernel: flat parameters [trunk | decoder | front-end].
+// The trunk and decoder blocks and the loss are reduce_step_v2_kernel's.  Behind them: the front-end's per-tile blocks
+// [dA | dC], each [K][dp] (dp = row pitch), summed over the tiles in a fixed order, then the chain rule of eddi_param_bwd_kernel
+// (csrc/vpc_eddi.hip) to (E, t, W, c) and Adam on those - one workgroup per feature j (dE[j][.], dt[j], from column j of dA, dC)
+// and one per k (dW[k][.], dc[k], from row k).  The chain rule reads E, t, W from `snap`, the copy of the step's front-end
+// parameters that tile 0 of the step kernel left: the Adam workgroups of this launch overwrite the parameters in place.
+struct FrontTail {
+    const float* part;  // [nb][2][K][dp]
+    const float* snap;  // [E | t | W | c] as the step read them
+    int nb, K, d, dp;   // d = obs_dim
+    int base;           // flat index of E: the front-end follows the trunk and the decoder
+};
+constexpr int FRONT_SNAP = 64 * 32 + 64;  // floats of the snapshot one workgroup stages: E and t (d <= 64, K <= 32), or W (<= 32 x 34)
+__device__ __forceinline__ void front_tail_body(const FrontTail& f, int blk, float* __restrict__ grad, const AdamFuse& adam,
+                                                float (*sh)[128], float* red, float* sn) {
+    const int K = f.K, d = f.d, dp = f.dp;
+    const long n = 2L * K * dp;
+    // the part of the snapshot this workgroup's dot products read, staged in LDS by independent loads first: read from global
+    // memory inside the K- and d-term loops they were up to 64 dependent L2 latencies in a row (a 24 us tail at d = 64 against
+    // 6 us at d = 12: profiles/eddi_small_notes.md)
+    const bool feat = blk < d;
+    const float* src = feat ? f.snap + d * K + d : f.snap;  // W | (E, t)
+    const int ns = feat ? K * (2 + K) : d * K + d;
+    for (int i = threadIdx.x; i < ns; i += 256) sn[i] = src[i];
+    const float *E = sn, *tb = sn + d * K, *Wp = sn;
+    const int iE = f.base, it = iE + d * K, iW = it + d, ic = iW + K * (2 + K);
+    AdamFuse A = adam;
+    A.pack_idx = nullptr;  // (the front-end has no packed image: the step kernel folds it from the flat parameters)
+    auto put = [&](int i, float v) {
+        grad[i] = v;
+        if (A.param) adam_apply(A, i, v);
+    };
+    if (blk < d) {  // feature j: values v < K are dA[v][j], K <= v < 2 K are dC[v - K][j] - both at v dp + j of a block
+        const int j = blk, v = threadIdx.x & 63, g = threadIdx.x >> 6;
+        float s = 0.f;
+        if (v < 2 * K)
+            for (int b = g; b < f.nb; b += 4) s += f.part[b * n + (long)v * dp + j];
+        sh[g][v] = s;
+        __syncthreads();
+        if (threadIdx.x < 2 * K) red[v] = ((sh[0][v] + sh[1][v]) + sh[2][v]) + sh[3][v];
+        __syncthreads();
+        const int e = threadIdx.x;
+        if (e < K) {  // dE[j][e] = sum_k W_E[k][e] dA[k][j]
+            float t = 0.f;
+            for (int k = 0; k < K; ++k) t += Wp[k * (2 + K) + 1 + e] * red[k];
+            put(iE + j * K + e, t);
+        } else if (e == K) {  // dt[j] = sum_k w_t[k] dC[k][j]
+            float t = 0.f;
+            for (int k = 0; k < K; ++k) t += Wp[k * (2 + K) + 1 + K] * red[K + k];
+            put(it + j, t);
+        }
+        return;
+    }
+    // row k: values v < dp are dA[k][v], dp <= v < 2 dp are dC[k][v - dp]
+    const int k = blk - d, v = threadIdx.x & 127, g = threadIdx.x >> 7;
+    float s = 0.f;
+    if (v < 2 * dp) {
+        const long off = v < dp ? (long)k * dp + v : (long)(K + k) * dp + (v - dp);
+        for (int b = g; b < f.nb; b += 2) s += f.part[b * n + off];
+    }
+    sh[g][v] = s;
+    __syncthreads();
+    if (threadIdx.x < 2 * dp) red[v] = sh[0][v] + sh[1][v];
+    __syncthreads();
+    const int c = threadIdx.x;
+    if (c < 2 + K) {  // dW[k][0] = sum_j dA; dW[k][1+e] = sum_j dA E[j][e]; dW[k][1+K] = sum_j dC t[j]
+        float t = 0.f;
+        for (int j = 0; j < d; ++j) t += c == 0 ? red[j] : c == 1 + K ? red[dp + j] * tb[j] : red[j] * E[j * K + (c - 1)];
+        put(iW + k * (2 + K) + c, t);
+    } else if (c == 2 + K) {  // dc[k] = sum_j dC[k][j]
+        float t = 0.f;
+        for (int j = 0; j < d; ++j) t += red[dp + j];
+        put(ic + k, t);
+    }
+}
+__global__ __launch_bounds__(256) void reduce_step_eddi_kernel(const float* __restrict__ partE, int nbE, long strideE,
+                                                               const float* __restrict__ partD, int nbD, long strideD,
+                                                               const int* __restrict__ invE, const int* __restrict__ invD,
+                                                               float* __restrict__ grad, const double* __restrict__ lp,
+                                                               int nbL, LossCoef k, float* __restrict__ out9,
+                                                               float* __restrict__ accum, AdamFuse adam, FrontTail f) {
+    __shared__ f32x4 shf[32][8];
+    __shared__ float shp[4][128];
+    __shared__ float redp[128];
+    __shared__ float snp[FRONT_SNAP];
+    __shared__ double shd[32][LOSS_TERMS];
+    __shared__ double s[LOSS_TERMS];
+    const int nE4 = (int)(strideE >> 2), nD4 = (int)(strideD >> 2);
+    const int gE = (nE4 + 7) / 8, gD = (nD4 + 7) / 8, gF = f.d + f.K;
+    const int b = blockIdx.x;
+    if (b < gE) reduce_body_v2(partE, nbE, strideE, invE, grad, nE4, b, shf, &adam);
+    else if (b < gE + gD) reduce_body_v2(partD, nbD, strideD, invD, grad, nD4, b - gE, shf, &adam);
+    else if (b < gE + gD + gF) front_tail_body(f, b - gE - gD, grad, adam, shp, redp, snp);
+    else finalize_body(lp, nbL, k, out9, accum, shd, s);
+}
 // the same launch for G members (ensemble step, include/vpc.h): blockIdx.y = member.  Member g's pointers are member 0's plus
 // g x the member strides, its loss coefficients and learning rate come from record g of the member table; the bodies, and so the
 // summation order and Adam's rounding sequence, are those of the single-model launch.
@@ -486,11 +581,11 @@ using namespace vpc;
 
 // ================================================================================================
 // host-side layout queries / index builders (no GPU needed)
-extern "C" int vpc_layout_sizes(int d, int L, int mask_augm, int* enc_img_floats, int* dec_img_floats,
-                                int* n_enc_params, int* n_params, int* enc_part_floats, int* dec_part_floats,
-                                int* loss_terms, int* tile_rows) {
-    const int din = mask_augm ? 2 * d : d;
-    if (d < 1 || din > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+// (din: width of the encoder input - d, 2 d for the mask-augmented classes, K for the point-net trunk)
+static int layout_sizes(int d, int din, int L, int* enc_img_floats, int* dec_img_floats,
+                        int* n_enc_params, int* n_params, int* enc_part_floats, int* dec_part_floats,
+                        int* loss_terms, int* tile_rows) {
+    if (d < 1 || d > MAX_D || din < 1 || din > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
     const int DT = dt_for(d);
     const ParamOffsets po(d, L, din);
     if (enc_img_floats) *enc_img_floats = EncImg(dt_for(din)).total;
@@ -503,13 +598,31 @@ extern "C" int vpc_layout_sizes(int d, int L, int mask_augm, int* enc_img_floats
     if (tile_rows) *tile_rows = TILE_ROWS;
     return VPC_OK;
 }
+extern "C" int vpc_layout_sizes(int d, int L, int mask_augm, int* enc_img_floats, int* dec_img_floats,
+                                int* n_enc_params, int* n_params, int* enc_part_floats, int* dec_part_floats,
+                                int* loss_terms, int* tile_rows) {
+    return layout_sizes(d, mask_augm ? 2 * d : d, L, enc_img_floats, dec_img_floats, n_enc_params, n_params, enc_part_floats,
+                        dec_part_floats, loss_terms, tile_rows);
+}
+// Point-net layout (Reg_EDDI / vanilla_EDDI, src/models/VAE.py:694-700): the tiled part of the model is the trunk pnp_encoder2
+// K -> 100 -> 50 -> 2L as the encoder and seq_decoder L -> 50 -> 100 -> d; n_params counts those twelve tensors, n_front_params
+// the four of the front-end behind them in the flat vector (type_pars1 [d][K], type_bias1 [d], pnp_encoder1.0.weight [K][2+K],
+// .bias [K]), which have no image and no tiled partial block.
+extern "C" int vpc_layout_sizes_pointnet(int d, int K, int L, int* enc_img_floats, int* dec_img_floats, int* n_enc_params,
+                                         int* n_params, int* n_front_params, int* enc_part_floats, int* dec_part_floats,
+                                         int* loss_terms, int* tile_rows) {
+    if (K < 1 || K > 32) return VPC_ERR_SHAPE;
+    const int r = layout_sizes(d, K, L, enc_img_floats, dec_img_floats, n_enc_params, n_params, enc_part_floats,
+                               dec_part_floats, loss_terms, tile_rows);
+    if (r == VPC_OK && n_front_params) *n_front_params = d * K + d + K * (2 + K) + K;
+    return r;
+}
 
 // pack_idx[i]: offset of flat parameter i inside the combined image buffer [enc image | dec image].
 // grad_idx[i]: offset of d loss / d param_i inside the encoder (i < n_enc) or decoder partial block.
 // img_template: combined image with zeros and the constant ones of the bias chain.
-extern "C" int vpc_build_indices(int d, int L, int mask_augm, int* pack_idx, int* grad_idx, float* img_template) {
-    const int din = mask_augm ? 2 * d : d;
-    if (d < 1 || din > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+static int build_indices(int d, int din, int L, int* pack_idx, int* grad_idx, float* img_template) {
+    if (d < 1 || d > MAX_D || din < 1 || din > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
     if (!pack_idx || !grad_idx || !img_template) return VPC_ERR_ARG;
     const int DT = dt_for(d);
     const EncImg ei(dt_for(din));
@@ -582,6 +695,13 @@ extern "C" int vpc_build_indices(int d, int L, int mask_augm, int* pack_idx, int
         }
     }
     return VPC_OK;
+}
+extern "C" int vpc_build_indices(int d, int L, int mask_augm, int* pack_idx, int* grad_idx, float* img_template) {
+    return build_indices(d, mask_augm ? 2 * d : d, L, pack_idx, grad_idx, img_template);
+}
+extern "C" int vpc_build_indices_pointnet(int d, int K, int L, int* pack_idx, int* grad_idx, float* img_template) {
+    if (K < 1 || K > 32) return VPC_ERR_SHAPE;
+    return build_indices(d, K, L, pack_idx, grad_idx, img_template);
 }
 
 // ---- bf16 images (PREC_BF16X3 / PREC_BF16): same row geometry as the fp32 images (W4 rows 32 dwords instead of 16),
@@ -763,6 +883,30 @@ extern "C" int vpc_reduce_step_adam(const float* enc_partials, int enc_blocks, l
     return reduce_step_adam_launch(enc_partials, enc_blocks, enc_stride, dec_partials, dec_blocks, dec_stride, grad_idx,
                                    inv_maps, grad_out, n_enc, n, loss_partials, loss_blocks, co, B_local, B_global, d, out9,
                                    accum, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, pack_idx, img, 0, stream);
+}
+
+extern "C" int vpc_reduce_step_adam_eddi(const float* enc_partials, int enc_blocks, long enc_stride,
+                                         const float* dec_partials, int dec_blocks, long dec_stride, const int* inv_maps,
+                                         float* grad_out, int n, const double* loss_partials, int loss_blocks,
+                                         const VpcLossCoef* co, long B_local, long B_global, int d, float* out9, float* accum,
+                                         float* params, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                         float eps, long step, const int* pack_idx, float* img, const float* front_partials,
+                                         int front_blocks, const float* front_snapshot, int K, int d_pitch, void* stream) {
+    if (!enc_partials || !dec_partials || !inv_maps || !grad_out || !loss_partials || !co || !out9) return VPC_ERR_ARG;
+    if (!params || !exp_avg || !exp_avg_sq || !pack_idx || !img || !front_partials || !front_snapshot || step < 1) return VPC_ERR_ARG;
+    if (enc_blocks <= 0 || dec_blocks <= 0 || loss_blocks <= 0 || front_blocks <= 0 || n <= 0 || B_local <= 0 || B_global <= 0)
+        return VPC_ERR_ARG;
+    if (K < 1 || K > 32 || d < 1 || d_pitch < d || d_pitch > 64) return VPC_ERR_SHAPE;
+    if (!inv_usable(inv_maps, enc_partials, enc_stride, dec_partials, dec_stride)) return VPC_ERR_ARG;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    const AdamFuse A{params, exp_avg, exp_avg_sq, pack_idx, img, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 0};
+    const FrontTail f{front_partials, front_snapshot, front_blocks, K, d, d_pitch, n};
+    const int grid = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8) + d + K + 1;
+    hipLaunchKernelGGL(reduce_step_eddi_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc_partials, enc_blocks,
+                       enc_stride, dec_partials, dec_blocks, dec_stride, inv_maps, inv_maps + enc_stride, grad_out,
+                       loss_partials, loss_blocks, finalize_coef(*co, B_local, B_global, d), out9, accum, A, f);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
 extern "C" int vpc_reduce_step_adam_bf16c(const float* enc_partials, int enc_blocks, long enc_stride,

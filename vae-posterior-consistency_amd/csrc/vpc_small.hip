@@ -58,6 +58,14 @@ struct SmallArgs {
     long mask_elem_lo;
     EpsShard shard;
 };
+// what the point-net kernel (step_small_eddi_kernel) takes besides: the tile body names it pnx
+struct SmallPointNet {
+    int K;                       // emb_dim: width of the trunk's input agg
+    const float* front;          // the front-end parameters in flat order: E [d_real][K] | t [d_real] | W [K][2+K] | c [K]
+    float* partF;                // [tiles][2][K][d]: the tile's (dA | dC) block
+    float* snap;                 // [n_front]: tile 0 leaves the parameters of this step here for the tail's chain rule
+};
+struct SmallPnArgs : SmallArgs { SmallPointNet pn; };
 
 // gradient tile (out tile of A-buffer `da`, in tile of B-buffer `xb`) over the 16 rows: acc[m][n] += sum_row da[row][16 ta + m] * xb[row][16 tb + n]
 __device__ __forceinline__ f32x4 wgrad16(const float* da, int ta, const float* xb, int tb, f32x4 acc, int m, int kq) {
@@ -70,6 +78,8 @@ template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_kernel(SmallArgs a) {
     constexpr int DTI = DT;
     constexpr bool AUG = false;
+    constexpr bool PN = false;
+    constexpr SmallPointNet pnx{};
     const unsigned tile_id = blockIdx.x;
 #include "vpc_small_body.h"
 }
@@ -79,6 +89,20 @@ __global__ __launch_bounds__(THREADS) void step_small_kernel(SmallArgs a) {
 template <int DTI, int DT>
 __global__ __launch_bounds__(THREADS) void step_small_aug_kernel(SmallArgs a) {
     constexpr bool AUG = true;
+    constexpr bool PN = false;
+    constexpr SmallPointNet pnx{};
+    const unsigned tile_id = blockIdx.x;
+#include "vpc_small_body.h"
+}
+
+// Reg_EDDI / vanilla_EDDI (src/models/VAE.py:670-853, 856-992): the point-net front-end (:719-733, 903-917) as the input stage -
+// folded per workgroup into LDS -, the trunk K -> 100 -> 50 -> 2L as the body's encoder with DTI = dt_for(K) input tiles, decoder
+// output of DT = dt_for(d) tiles; the encoder backward goes on to dagg = dh1 . W1 and the front-end's (dA | dC) block of the tile.
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void step_small_eddi_kernel(SmallPnArgs a) {
+    constexpr bool AUG = false;
+    constexpr bool PN = true;
+    const SmallPointNet& pnx = a.pn;
     const unsigned tile_id = blockIdx.x;
 #include "vpc_small_body.h"
 }
@@ -109,21 +133,28 @@ struct SmallDraw {
 static int step_small_launch(const float* x, const float* enc_img, const float* dec_img, int npass,
                              const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
                              const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
-                             int* nblocks_out, long B, int d, int L, const SmallDraw& dr, void* stream, int d_real = 0) {
-    // d_real != 0: the mask-augmented kernels - obs_dim d_real in rows of pitch d = 4 ceil(d_real / 4), encoder input 2 d_real wide
-    const bool aug = d_real != 0;
+                             int* nblocks_out, long B, int d, int L, const SmallDraw& dr, void* stream, int d_real = 0,
+                             const SmallPointNet* pn = nullptr) {
+    // d_real != 0: the mask-augmented kernels - obs_dim d_real in rows of pitch d = 4 ceil(d_real / 4), encoder input 2 d_real wide;
+    // with pn: the point-net kernels - the same rows, encoder input pn->K wide
+    const bool aug = d_real != 0 && !pn;
     if (!x || !enc_img || !dec_img || !mask || !co || !eps || !partE || !partD || !loss_partials) return VPC_ERR_ARG;
     if (npass < 1 || npass > 2 || B <= 0) return VPC_ERR_ARG;
     if (d < 4 || d > MAX_D || d % 4 || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
     if (aug && (d_real < 1 || d_real > d || d - d_real > 3 || 2 * d_real > MAX_D)) return VPC_ERR_SHAPE;
+    // (d <= 64, K <= 32: the instantiations, and what the front-end's LDS workspace of the tile body is laid out for)
+    if (pn && (d_real < 1 || d_real > d || d - d_real > 3 || d > 64 || pn->K < 1 || pn->K > 32)) return VPC_ERR_SHAPE;
+    if (pn && (!pn->front || !pn->partF || !pn->snap || (uintptr_t)pn->front % 4 || (uintptr_t)pn->partF % 4 || (uintptr_t)pn->snap % 4))
+        return VPC_ERR_ARG;
     if (!aligned16(x) || !aligned16(enc_img) || !aligned16(dec_img)) return VPC_ERR_ARG;
     if (co->wml != 0.f && !eps_ml) return VPC_ERR_ARG;
-    SmallArgs a{};
+    SmallPnArgs a{};
     a.x = x; a.enc_img = enc_img; a.dec_img = dec_img; a.eps_ml = eps_ml; a.partE = partE; a.partD = partD;
     a.loss_part = loss_partials;
     set_loss_coef(a, *co, npass);
     a.inv_B = inv_B; a.x_logvar = x_logvar;
     a.B = B; a.d = d; a.d_real = d_real; a.L = L; a.npass = npass;
+    if (pn) a.pn = *pn;
     for (int p = 0; p < npass; ++p) {
         if (!mask[p] || !eps[p]) return VPC_ERR_ARG;
         a.m[p] = mask[p]; a.mB[p] = maskB ? maskB[p] : nullptr; a.eps[p] = eps[p];
@@ -151,21 +182,35 @@ static int step_small_launch(const float* x, const float* enc_img, const float* 
     case T: {                                                                                              \
         auto kern = step_small_kernel<T>;                                                                  \
         if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, a);                              \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, static_cast<const SmallArgs&>(a));   \
         return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
     }
 #define VPC_CASE_AUG(TI, T)                                                                                \
     case TI: {                                                                                             \
         auto kern = step_small_aug_kernel<TI, T>;                                                          \
         if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, static_cast<const SmallArgs&>(a));   \
+        return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
+    }
+#define VPC_CASE_PN(TI, T)                                                                                 \
+    case 4 * TI + T: {                                                                                     \
+        auto kern = step_small_eddi_kernel<TI, T>;                                                         \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), SMALL_LDS, s, a);                              \
         return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
+    }
+    if (pn) {  // (input tiles, output tiles) = (dt_for(K), dt_for(d_real)): K <= 16, 32; d_real <= 16, 32, 64
+        switch (4 * dt_for(pn->K) + dt_for(d_real)) {
+            VPC_CASE_PN(1, 1) VPC_CASE_PN(1, 2) VPC_CASE_PN(1, 4) VPC_CASE_PN(2, 1) VPC_CASE_PN(2, 2) VPC_CASE_PN(2, 4)
+        }
+        return VPC_ERR_SHAPE;
     }
     if (aug) {  // (input tiles, output tiles) = (dt_for(2 d_real), dt_for(d_real)): d_real <= 8, 16, 32, 64
         switch (dt_for(2 * d_real)) { VPC_CASE_AUG(1, 1) VPC_CASE_AUG(2, 1) VPC_CASE_AUG(4, 2) VPC_CASE_AUG(8, 4) }
         return VPC_ERR_SHAPE;
     }
     switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
+#undef VPC_CASE_PN
 #undef VPC_CASE_AUG
 #undef VPC_CASE
     return VPC_ERR_SHAPE;
@@ -251,6 +296,8 @@ template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArgs ma) {
     constexpr int DTI = DT;
     constexpr bool AUG = false;
+    constexpr bool PN = false;
+    constexpr SmallPointNet pnx{};
     // (tile, member) of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs by their linear id (x fastest).
     //   order 0: grid (tiles, G), id = g * tiles + t - the tiles of a member land on different XCDs, every L2 sees every
     //            member's images;
@@ -378,4 +425,39 @@ extern "C" int vpc_step_small_aug_draw_f32(const float* x, const float* enc_img,
                  EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch}};
     return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
                              partD, loss_partials, nblocks_out, B, d, L, dr, stream, d_real);
+}
+
+// The same step for Reg_EDDI / vanilla_EDDI (src/models/VAE.py:713-741, 897-925 encoder; src/experiment_main/train.py:87-115): the
+// images are those of the point-net layout (vpc_build_indices_pointnet: trunk K -> 100 -> 50 -> 2L, decoder L -> 50 -> 100 -> d_real),
+// `front` the front-end parameters in flat order (type_pars1 | type_bias1 | pnp_encoder1.0.weight | .bias), read and folded by every
+// workgroup.  Besides partE / partD the tiles write their (dA | dC) blocks [2][K][d] to front_partials and tile 0 a copy of `front`
+// to front_snapshot (what vpc_reduce_step_adam_eddi's chain rule reads).  d is the row pitch 4 ceil(d_real / 4) of x and the masks.
+extern "C" int vpc_step_small_eddi_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
+                                       const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                       const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                       int* nblocks_out, long B, int d, int d_real, int L, int K, const float* front,
+                                       float* front_partials, float* front_snapshot, void* stream) {
+    if (d_real < 1) return VPC_ERR_SHAPE;
+    const SmallPointNet pn{K, front, front_partials, front_snapshot};
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
+                             partD, loss_partials, nblocks_out, B, d, L, SmallDraw{}, stream, d_real, &pn);
+}
+
+extern "C" int vpc_step_small_eddi_draw_f32(const float* x, const float* enc_img, const float* dec_img, int npass,
+                                            const uint8_t* const* mask, const uint8_t* const* maskB, const VpcLossCoef* co,
+                                            const float* const* eps, const float* eps_ml, float inv_B, float x_logvar, float* partE, float* partD, double* loss_partials,
+                                            int* nblocks_out, long B, int d, int d_real, int L, int K, const float* front,
+                                            float* front_partials, float* front_snapshot, const uint8_t* mask_in, float keep_prob,
+                                            float* eps_out, long n_eps, unsigned long long seed, unsigned long long offset_mask,
+                                            unsigned long long offset_eps, const long long* state, long mask_elem_lo,
+                                            long eps_rows_local, long eps_rows_global, long eps_row_lo, int eps_pitch, void* stream) {
+    if (d_real < 1) return VPC_ERR_SHAPE;
+    if (eps_rows_local < 0 || (eps_rows_local > 0 && (eps_pitch != 16 || eps_rows_local != B || eps_row_lo < 0 ||
+                                                      eps_row_lo + eps_rows_local > eps_rows_global)))
+        return VPC_ERR_ARG;
+    const SmallPointNet pn{K, front, front_partials, front_snapshot};
+    SmallDraw dr{1, mask_in, keep_prob, eps_out, n_eps, seed, offset_mask, offset_eps, state, mask_elem_lo,
+                 EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch}};
+    return step_small_launch(x, enc_img, dec_img, npass, mask, maskB, co, eps, eps_ml, inv_B, x_logvar, partE,
+                             partD, loss_partials, nblocks_out, B, d, L, dr, stream, d_real, &pn);
 }

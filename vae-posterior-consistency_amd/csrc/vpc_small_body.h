@@ -7,8 +7,12 @@
 // the single-model kernel compiles to the instructions it had as a self-contained kernel (a shared inline function is
 // simplified before it is inlined, without knowing that `a` is the kernel-argument segment, and schedules differently).
 // In scope at the point of inclusion: the compile-time tile counts DT (tiles of d: x / mask words of the loss, W6, the output
-// tiles, dW6) and DTI (tiles of the encoder INPUT: W1's k-tiles, the X buffers, dW1) and the flag AUG, `a`, `const unsigned
-// tile_id`; everything vpc_small.hip declares before its kernels.  Plain models: DTI == DT, AUG false.  AUG (Reg_VAE_mask /
+// tiles, dW6) and DTI (tiles of the encoder INPUT: W1's k-tiles, the X buffers, dW1) and the flags AUG and PN, `a`, `pnx` (a
+// SmallPointNet: the point-net kernel's own arguments, an empty record elsewhere), `const unsigned tile_id`; everything
+// vpc_small.hip declares before its kernels.  Plain models: DTI == DT, AUG and PN false.  PN (Reg_EDDI / vanilla_EDDI,
+// src/models/VAE.py:719-733, 903-917): the encoder input is the point-net aggregate agg [16][pnx.K] of the folded front-end
+// (DTI = dt_for(K)), the encoder backward goes on to dagg and the front-end's (dA | dC) block of the tile in pnx.partF; a.d is
+// the row pitch of x and the masks, a.d_real obs_dim.  AUG (Reg_VAE_mask /
 // vanilla_VAE_mask, src/models/VAE.py:545-548, 1031-1033): the encoder input is [x*mask | mask] of width 2 a.d_real, a.d is
 // the row pitch of x and the masks.  Partial blocks and loss terms go to slot tile_id of a.partE / a.partD / a.loss_part.
 // (No include guard: this is a code fragment, included once per kernel.)
@@ -90,6 +94,70 @@
         };
         int cc = c, qq = q;
         launder(cc, qq);
+        // ---- PN: the point-net front-end's workspace.  Buffers B_Z .. B_DG1 (6 x SBUF = 13 824 floats, contiguous) are idle
+        // before the encoder forward and again after the encoder backward; both front-end phases stage into them:
+        //   PT  [a.d][64]   folded table: PT[64 j + k] = A_j[k], PT[64 j + 32 + k] = C_j[k], zero for k >= K and j >= d_real
+        //   PPR [n_front]   the front-end parameters in flat order (E [d_real][K] | t [d_real] | W [K][2+K] | c [K])
+        //   PXS, PMQ, PMP [16][a.d]   x and the masks of both passes as floats; rows past B and columns past d_real are 0
+        // 4 096 + 3 328 + 3 x 1 024 = 10 496 floats at the limits d = 64, K = 32.
+        float* const PT = buf(B_Z);
+        float* const PPR = PT + 4096;
+        float* const PXS = PPR + 3328;
+        float* const PMQ = PXS + 1024;
+        float* const PMP = PMQ + 1024;
+        auto pn_stage = [&]() {
+            const int K = pnx.K, dr = a.d_real, dp = a.d;
+            const int nfront = dr * K + dr + K * (2 + K) + K;
+            // (opaque thread id: the stage runs twice, and what the two copies share would otherwise be kept in registers
+            // across the whole step - launder() in vpc_device.h)
+            int tid = threadIdx.x, tid2 = 0;
+            launder(tid, tid2);
+            for (int i = tid; i < nfront; i += THREADS) PPR[i] = pnx.front[i];
+            for (int i = tid; i < 16 * dp; i += THREADS) {
+                const int r = i / dp, j = i - r * dp;
+                const bool in = row0 + r < a.B && j < dr;
+                const long g = (row0 + r) * dp + j;
+                PXS[i] = in ? a.x[g] : 0.f;
+                PMQ[i] = (in && a.m[0][g]) ? 1.f : 0.f;
+                PMP[i] = (two && in && a.m[1][g]) ? 1.f : 0.f;
+            }
+            __syncthreads();
+            // the fold of eddi_fold_kernel: A_j = w_x + W_E E_j, C_j = w_t t_j + c  (W = [w_x | W_E | w_t], VAE.py:719-727)
+            const float *pE = PPR, *ptb = pE + dr * K, *pW = ptb + dr, *pc = pW + K * (2 + K);
+            for (int i = tid; i < 32 * dp; i += THREADS) {
+                const int k = i & 31, j = i >> 5;
+                float A = 0.f, C = 0.f;
+                if (k < K && j < dr) {
+                    const float* wr = pW + k * (2 + K);
+                    A = wr[0];
+#pragma unroll 4
+                    for (int e = 0; e < K; ++e) A += wr[1 + e] * pE[j * K + e];
+                    C = wr[1 + K] * ptb[j] + pc[k];
+                }
+                PT[64 * j + k] = A;
+                PT[64 * j + 32 + k] = C;
+            }
+            __syncthreads();
+        };
+        if constexpr (PN) {
+            // ---- input stage of both passes (eddi_front_fwd_kernel; VAE.py:719-733, 903-917): thread (row r, k) sums
+            // m[r][j] relu(x[r][j] A_j[k] + C_j[k]) over the features in a fixed order; columns K .. 16 DTI - 1 are written as 0
+            pn_stage();
+            int tid = threadIdx.x, tid2 = 0;
+            launder(tid, tid2);
+            const int r = tid >> 5, k = tid & 31, dp = a.d;
+            float sq = 0.f, sp = 0.f;
+#pragma unroll 4
+            for (int j = 0; j < a.d_real; ++j) {
+                const float h = fmaxf(PXS[r * dp + j] * PT[64 * j + k] + PT[64 * j + 32 + k], 0.f);
+                sq += PMQ[r * dp + j] * h;
+                sp += PMP[r * dp + j] * h;
+            }
+            if (k < 16 * DTI) {
+                buf(B_XQ)[r * SP + k] = k < pnx.K ? sq : 0.f;
+                if (two) buf(B_XP)[r * SP + k] = k < pnx.K ? sp : 0.f;
+            }
+        }
         // ================================================================ E: encoder forward of both passes
         // (every stage requests the weight fragments of the NEXT stage before it computes: a stage is ~30 MFMAs, an L2 round
         // trip as long as that; lds_barrier() leaves those loads in flight)
@@ -103,7 +171,9 @@
                 ldW<DTI, S1>(W1, w, cc, qq, fW1);
                 bias1 = *reinterpret_cast<const f32x4*>(b1 + 16 * w + 4 * qq);
             }
-            if constexpr (!AUG) {
+            if constexpr (PN) {
+                // (the X buffers of both passes hold agg already: the input stage above)
+            } else if constexpr (!AUG) {
                 if (w < DT) st_act(X, w, cc, qq, xv * mask_to_f32(p == 0 ? mwq : mwp));  // x.float() * mask  (VAE.py:388)
             } else {
                 // [x*mask | mask | 0] (ld_input<.., true> of vpc_enc.hip; VAE.py:545-548): element f < d is x_f m_f, d <= f < 2 d
@@ -353,6 +423,10 @@
             f32x4 fT3[2], fT2[H2T];
             if (w < H2T) ldWT<2, 64>(W3, w, cc, qq, fT3);    // dh2's fragments
             if (w < H1T) ldWT<H2T, 128, NK2>(W2, w, cc, qq, fT2);  // dh1's fragments
+            f32x4 fT1[H1T];  // (PN only; never written or read otherwise)
+            if constexpr (PN) {
+                if (w < DTI) ldWT<H1T, S1, NK1>(W1, w, cc, qq, fT1);  // dagg's fragments
+            }
             // ---- dW3~ (wave w: out tile w >> 2, in tile w & 3)  |  dh2 (waves 0-3)
             acc3 = wgrad16(DML, w >> 2, H2b, w & 3, acc3, cc, qq);
             if (w < H2T) {
@@ -378,6 +452,14 @@
             if (w < DTI) {
 #pragma unroll
                 for (int mt = 0; mt < H1T; ++mt) acc1[mt] = wgrad16(buf(B_DH1), mt, X, w, acc1[mt], cc, qq);
+                if constexpr (PN) {
+                    // dagg = dh1 . W1 (the layer-0 dgrad the dense body has no use for: x carries no gradient), tile w of the
+                    // pass, into the pass's H2 buffer - dead since the dW3 / dh2 stage
+                    f32x4 in[H1T];
+#pragma unroll
+                    for (int t = 0; t < H1T; ++t) in[t] = ld_act(buf(B_DH1), t, cc, qq);
+                    st_act(buf(p == 0 ? B_H2Q : B_H2P), w, cc, qq, mmW<H1T, NK1>(fT1, in, zero4()));
+                }
             }
             lds_barrier();
             launder(cc, qq);
@@ -406,5 +488,41 @@
                 if (c == 0 && w < H1T) a.partE[(long)tile_id * ENC_PART + WAVES * GREGS * 64 + 16 * w + 4 * q + j] = v;
             }
             if (w == 7 && lane < 16) a.partE[(long)tile_id * ENC_PART + WAVES * GREGS * 64 + 112 + lane] = 0.f;
+        }
+        if constexpr (PN) {
+            // ================================================================ front-end backward (eddi_front_bwd_kernel)
+            // dA[k][j] = sum over passes and rows of g x, dC[k][j] = sum of g, g = m 1[x A + C > 0] dagg: gates recomputed from
+            // the re-staged table; thread (k, j) walks pass 0's rows, then pass 1's - a fixed order, no atomics.  The tile's
+            // block is [dA | dC], each [K][a.d], columns past d_real zero.
+            pn_stage();  // (its first barrier is behind the encoder backward's last stage: B_Z .. B_DG1 are idle again)
+            const int K = pnx.K, dp = a.d;
+            const float *DQ = buf(B_H2Q), *DPp = buf(B_H2P);
+            float* pf = pnx.partF + (long)tile_id * 2 * K * dp;
+            int tid = threadIdx.x, tid2 = 0;
+            launder(tid, tid2);
+            for (int i = tid; i < 32 * dp; i += THREADS) {
+                const int k = i & 31, j = i >> 5;
+                if (k >= K) continue;
+                const float A = PT[64 * j + k], C = PT[64 * j + 32 + k];
+                float dA = 0.f, dC = 0.f;
+                for (int pp = 0; pp < a.npass; ++pp) {
+                    const float* M = pp == 0 ? PMQ : PMP;
+                    const float* D = pp == 0 ? DQ : DPp;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float xr = PXS[r * dp + j];
+                        const float g = (xr * A + C > 0.f) ? M[r * dp + j] * D[r * SP + k] : 0.f;
+                        dA += g * xr;
+                        dC += g;
+                    }
+                }
+                pf[k * dp + j] = dA;
+                pf[(K + k) * dp + j] = dC;
+            }
+            // the parameters this step's gradients were taken at, for the tail's chain rule: its Adam blocks overwrite them in place
+            if (tile_id == 0) {
+                const int nfront = a.d_real * K + a.d_real + K * (2 + K) + K;
+                for (int i = tid; i < nfront; i += THREADS) pnx.snap[i] = PPR[i];
+            }
         }
     }

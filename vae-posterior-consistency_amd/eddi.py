@@ -23,7 +23,7 @@ from .models import _W6, MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .linear import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad
 from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
-from .trainer import _FlatAdamTrainer, draw_counters
+from .trainer import _FlatAdamTrainer, draw_counters, pad_cols
 
 H1, H2 = 100, 50  # VAE.py:694-698 hard-codes 100 / 50
 
@@ -204,12 +204,52 @@ class vanilla_EDDI(_EDDIBase, vanilla_VAE):
 LP = 16  # row pitch of the padded latent workspaces of the fused decoder kernel
 
 
+def small_step_route(d, K, B, world_size, max_rows):
+    """Whether EDDITrainer.step takes the small-batch one-kernel step (csrc/vpc_small.hip: step_small_eddi_kernel): a single
+    rank, 0 < B <= max_rows (ops.step_small_max_rows(): 16 x CUs by default, 0 with VPC_STEP_SMALL=0) and a shape with an
+    instantiation (K <= 32, obs_dim <= 64).  Data-parallel steps, larger batches and wider tables keep the launch chain."""
+    return world_size == 1 and 0 < B <= max_rows and ops.small_eddi_tiles(d, K) is not None
+
+
+class _SmallStep:
+    """What the small-batch step of one EDDITrainer owns: the point-net layout's tables, the packed images of trunk and decoder
+    and the per-tile buffers the chain has no use for."""
+
+    def __init__(self, tr):
+        m, dev = tr.model, tr.dev
+        d, Ld, K = m.obs_dim, m.latent_dim, m.emb_dim
+        lay = self.lay = L.pointnet_layout(d, K, Ld)
+        n = lay.n_params
+        self.pidx, _ = lay.device_tables(dev)
+        self.inv = lay.inverse_maps(dev)
+        pidx = self.pidx
+        self.img = PackedImage(torch.from_numpy(lay.img_template).to(dev), lambda flat, buf: ops.pack_weights(flat[:n], pidx, buf))
+        self.enc_img, self.dec_img = self.img.buf[:lay.enc_img], self.img.buf[lay.enc_img:]
+        self.dk = ops.small_aug_pitch(d)
+        nb = L.max_blocks()
+        self.partE = torch.empty(nb * lay.enc_part, device=dev)
+        self.partF = torch.empty(nb * 2 * K * self.dk, device=dev)
+        self.snap = torch.empty(lay.n_front, device=dev)
+        self.pads = {}
+        self.B = None
+
+
 class EDDITrainer(_FlatAdamTrainer):
     """The EDDI training step (train.py:28-117 for 'reg_EDDI*' / 'vanilla_EDDI*') as a fixed launch sequence without
     host synchronisation: [decoder image re-pack] -> mask_p + eps draws -> fold -> front-end (both passes) ->
     pnp_encoder2 GEMMs on the stacked passes -> the SAME fused decoder + loss + decoder-backward kernel as the VAE step
     (nothing of size B x d is materialised) -> trunk backward GEMMs -> front-end backward -> [one all-reduce of
-    [grads | loss terms]] -> flat Adam."""
+    [grads | loss terms]] -> flat Adam.
+
+    Small batches on one rank (small_step_route: B <= ops.step_small_max_rows(), K <= 32, obs_dim <= 64) run the whole step as
+    TWO launches instead: step_small_eddi_kernel (draws, front-end, trunk, decoder, loss and every backward pass of a 16-row
+    tile per workgroup) and one tail (fixed-order reductions, the front-end's chain rule, Adam, image re-pack).  The kernel
+    takes x, mask and mask_p at 4 * ceil(obs_dim / 4) columns (mask 0 in the padding).  The draws keep the chain's counters,
+    trainer.draw_counters at the pitch obs_dim, so the device-drawn mask_p and eps of a seed are bit for bit the chain's at
+    every width: for obs_dim % 4 == 0 the kernel makes them itself; for obs_dim % 4 != 0 the chain's draw launch makes them on
+    the unpadded rows and mask_p is padded afterwards (one launch and one copy more) - NOT the padded-pitch stream of the dense
+    small-batch step, because tests/test_draw_rule_gpu.py pins this trainer's stream at obs_dim 14 to the unpadded pitch.
+    VPC_STEP_SMALL=0 in the environment keeps the chain.  `last_path` names what the last step ran: "small" or "chain"."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
         if not isinstance(model, _EDDIBase):
@@ -226,6 +266,10 @@ class EDDITrainer(_FlatAdamTrainer):
         self.n_trunk = sum(p.numel() for p in self._plist[:6])
         self.n_dec = self.lay.n_params - self.lay.n_enc
         self._B = None
+        self._small = None  # the small-batch step's tables and buffers: made on its first use
+        # (what of small_step_route is fixed per trainer: the row limit is asked for only where it can matter)
+        self._small_shape = world_size == 1 and ops.small_eddi_tiles(model.obs_dim, model.emb_dim) is not None
+        self.last_path = None
 
     def _ws(self, B):
         if self._B == B:
@@ -253,6 +297,8 @@ class EDDITrainer(_FlatAdamTrainer):
                         dlat_src=self.dlat[..., :Ld].permute(0, 2, 1, 3),
                         gdec=self.grad[self.n_trunk:self.n_trunk + self.n_dec], gidx_dec=self.gidx[self.lay.n_enc:])
         self._B = B
+        if self._small is not None:
+            self._small.B = None  # (eps_buf and mask_p_buf are the chain's now)
 
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=0.5, beta=1.0,
              beta_annealing=False, p_missingness=30, global_batch=None, row_lo=None):
@@ -262,6 +308,10 @@ class EDDITrainer(_FlatAdamTrainer):
         L.require_cuda(x)
         mask = as_mask_u8(mask.reshape(-1, d))
         B = x.shape[0]
+        if self._small_shape and small_step_route(d, K, B, self.world_size, ops.step_small_max_rows()):
+            return self._step_small(x, mask, mask_p, (eps_q, eps_p, eps_ml), self.coefficients(epoch, alpha, beta, beta_annealing),
+                                    1.0 - p_missingness / 100.0, global_batch, row_lo)
+        self.last_path = "chain"
         self._ws(B)
         Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         co = self.coefficients(epoch, alpha, beta, beta_annealing)
@@ -330,3 +380,66 @@ class EDDITrainer(_FlatAdamTrainer):
             self._allreduce()
         dp = self.world_size > 1  # the Adam launch also adds the all-reduced loss to the epoch accumulator
         self._adam(None, self.out9 if dp else None, self.accum if dp else None)
+
+    def _step_small(self, x, mask, mask_p, eps_in, co, keep_prob, global_batch, row_lo):
+        """The step as step_small_eddi_kernel + one tail launch (class docstring).  x [B][d] fp32, mask [B][d] uint8."""
+        m, dev = self.model, self.dev
+        d, Ld, K = m.obs_dim, m.latent_dim, m.emb_dim
+        s = self._small
+        if s is None:
+            s = self._small = _SmallStep(self)
+        lay, dk, B = s.lay, s.dk, x.shape[0]
+        two = not self.vanilla
+        if s.B != B:
+            self.eps_buf = torch.empty(3, B, LP, device=dev)
+            self.mask_p_buf = torch.empty(B, d, dtype=torch.uint8, device=dev)
+            s.eps = [self.eps_buf[p_] for p_ in range(3)]
+            s.B, self._B = B, None  # (the chain makes its own workspaces again)
+        Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
+        key = m._param_key(self._plist)
+        img = s.img.get(key, m._flat)
+        # ---- draws: the chain's counters and its rule for which planes are drawn (step), at the chain's pitch d.  obs_dim % 4 == 0
+        # and every draw made on the device: the kernel makes them; else the chain's launches, on the unpadded rows
+        need_ml = two and co.ml_on
+        planes = 3 if need_ml else 2 if two else 1
+        eps_view, eps_in = self.eps_buf[:planes], eps_in[:planes]
+        draw_mask = two and mask_p is None
+        draw_eps = draw_mask or eps_in[0] is None
+        dr = draw_counters(self.rng_offset, draw_mask, planes if draw_eps else 0, B, Bg, row_lo, LP, d)
+        self.rng_offset = dr.next_offset
+        in_kernel = None
+        if dk == d and draw_mask == two and all(e is None for e in eps_in):
+            in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
+                         dr.eps_shard)
+        elif draw_mask:
+            ops.draw_step(mask, self.mask_p_buf, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
+                          dr.eps_shard)
+        elif draw_eps:
+            ops.fill_normal(eps_view, self.seed, dr.offset_eps, None, dr.eps_shard)
+        if draw_mask:
+            mask_p = self.mask_p_buf
+        elif two:
+            mask_p = as_mask_u8(mask_p.reshape(-1, d))
+        for plane, e in enumerate(eps_in):
+            if e is not None:
+                self.eps_buf[plane, :, :Ld].copy_(e)
+        if dk != d:  # the kernel's rows: 4 * ceil(d / 4) columns, mask 0 in the padding
+            x, mask = pad_cols(s.pads, x, dk, 0, dev), pad_cols(s.pads, mask, dk, 1, dev)
+            if two:
+                mask_p = pad_cols(s.pads, mask_p, dk, 2, dev)
+        # ---- the step, then the tail
+        masks = [mask, mask_p] if two else [mask]
+        maskB = [mask_p, None] if (two and co.maskB_on) else [None] * len(masks)
+        args = (x, s.enc_img, s.dec_img, masks, maskB, co, s.eps[:len(masks)], s.eps[2] if need_ml else None, 1.0 / Bg,
+                m._x_logvar_value, s.partE, self.partD, self.loss_part, dk, d, Ld, K, m._flat[lay.n_params:], s.partF, s.snap)
+        if in_kernel is not None:
+            nb = self._timed("step_small", ops.step_small_eddi_draw_f32, *args, *in_kernel)
+        else:
+            nb = self._timed("step_small", ops.step_small_eddi_f32, *args)
+        self.step_count += 1
+        self._timed("reduce_step", ops.reduce_step_adam_eddi, s.partE, self.partD, nb, lay.enc_part, lay.dec_part, s.inv,
+                    self.grad, lay.n_params, self.loss_part, co, B, Bg, d, self.out9, self.accum, m._flat, self.exp_avg,
+                    self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.adam_eps, self.step_count, s.pidx, img, s.partF,
+                    s.snap, K, dk)
+        self._flat_written(key, s.img)
+        self.last_path = "small"

@@ -188,6 +188,53 @@ def step_small_aug_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, 
     return nb.value
 
 
+def small_eddi_tiles(d, K):
+    """(DTI, DT) of the step_small_eddi_kernel instantiation that serves obs_dim d and emb_dim K: 16-wide tiles of the trunk's
+    input agg (K wide) and of the decoder output (d wide); None where there is none (K > 32 or d > 64)."""
+    if not (1 <= K <= 32 and 1 <= d <= 64):
+        return None
+    return (1 if K <= 16 else 2), (1 if d <= 16 else 2 if d <= 32 else 4)
+
+
+def step_small_eddi_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d, d_real,
+                        Ld, K, front, partF, snap):
+    """step_small_f32 of Reg_EDDI / vanilla_EDDI: `d` is the row pitch small_aug_pitch(d_real) of x and the masks, the images
+    are those of the point-net layout, `front` the front-end parameters in flat order; the tiles' (dA | dC) blocks go to partF,
+    a copy of `front` to snap (include/vpc.h)."""
+    n = len(masks)
+    nb = C.c_int(0)
+    check(lib().vpc_step_small_eddi_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                        ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE), ptr(partD), ptr(loss_part),
+                                        C.byref(nb), x.shape[0], d, d_real, Ld, K, ptr(front), ptr(partF), ptr(snap),
+                                        stream_ptr()), "vpc_step_small_eddi_f32")
+    return nb.value
+
+
+def step_small_eddi_draw_f32(x, enc_img, dec_img, masks, maskB, co, eps, eps_ml, inv_B, x_logvar, partE, partD, loss_part, d,
+                             d_real, Ld, K, front, partF, snap, mask_in, keep_prob, eps_out, seed, offset_mask, offset_eps,
+                             state=None, elem_lo=0, eps_shard=None):
+    """step_small_eddi_f32 that also makes the step's draws inside the launch (as step_small_draw_f32, at the pitch `d`)."""
+    n = len(masks)
+    nb = C.c_int(0)
+    check(lib().vpc_step_small_eddi_draw_f32(ptr(x), ptr(enc_img), ptr(dec_img), n, ptr_array(masks), ptr_array(maskB), co,
+                                             ptr_array(eps), ptr(eps_ml), inv_B, x_logvar, ptr(partE), ptr(partD),
+                                             ptr(loss_part), C.byref(nb), x.shape[0], d, d_real, Ld, K, ptr(front), ptr(partF),
+                                             ptr(snap), ptr(mask_in), float(keep_prob), ptr(eps_out), eps_out.numel(), int(seed),
+                                             int(offset_mask), int(offset_eps), ptr(state), int(elem_lo), *_shard4(eps_shard),
+                                             stream_ptr()), "vpc_step_small_eddi_draw_f32")
+    return nb.value
+
+
+def reduce_step_adam_eddi(partE, partD, nb, strideE, strideD, inv_maps, grad, n, loss_part, co, B_local, B_global, d, out9, accum,
+                          params, m, v, lr, beta1, beta2, eps, step, pack_idx, img, partF, snap, K, d_pitch):
+    """The tail of the small-batch EDDI step in one launch: trunk / decoder blocks and loss as reduce_step_adam, the front-end
+    blocks partF summed, chained back to the four front-end tensors and stepped (include/vpc.h).  `nb` blocks of each kind."""
+    check(lib().vpc_reduce_step_adam_eddi(ptr(partE), nb, strideE, ptr(partD), nb, strideD, ptr(inv_maps), ptr(grad), n,
+                                          ptr(loss_part), nb, co, B_local, B_global, d, ptr(out9), ptr(accum), ptr(params),
+                                          ptr(m), ptr(v), lr, beta1, beta2, eps, int(step), ptr(pack_idx), ptr(img), ptr(partF),
+                                          nb, ptr(snap), K, d_pitch, stream_ptr()), "vpc_reduce_step_adam_eddi")
+
+
 # Slots of the member-stride vectors of include/vpc.h: VPC_MS_* (ensemble step, evaluation, imputation), VPC_RM_* (reward)
 MS_X, MS_MASK, MS_MASK_P, MS_EPS, MS_IMG, MS_PARTE, MS_PARTD, MS_LOSS, MS_PARAM, MS_COUNT = range(10)
 MS_PART = MS_LOSS  # the evaluation's per-tile sums [tiles][5] doubles travel in the loss slot
