@@ -607,6 +607,51 @@ int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_parti
                                float* params, float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, long step,
                                const int* pack_idx, float* img, void* stream);
 
+/* ---- the ensemble step for the mask-augmented and the point-net families: the same pair of launches with the tile bodies of
+ * vpc_step_small_aug(_draw)_f32 (Reg_VAE_mask / vanilla_VAE_mask, src/models/VAE.py:510-667, 995-1116) and of
+ * vpc_step_small_eddi(_draw)_f32 (Reg_EDDI / vanilla_EDDI, VAE.py:670-853, 856-992) per (tile, member) workgroup, around the step
+ * loop of src/experiment_main/train.py:87-117 under the drivers' loops of src/experiment_main/imputation.py:21-39.  Member g gets,
+ * bit for bit, what its stand-alone small-batch step and tail give it.  Arguments as vpc_step_small_multi_f32 /
+ * vpc_reduce_step_adam_multi, and besides:
+ *   d_real    the members' obs_dim; d is the ROW PITCH 4 ceil(d_real / 4) of x and the masks (mask 0 in the padding), and the pitch
+ *             the draws of draw != 0 are made at (point-net members keep their stand-alone stream, which is drawn at the pitch
+ *             obs_dim: the caller asks for draws only where d == d_real)
+ *   K, front, front_partials, front_snapshot (point-net)   as vpc_step_small_eddi_f32; the pointers are member 0's.  `front` lies
+ *             inside the member's row [trunk | decoder | front-end] of the parameter stack: member g's is strides[VPC_MS_PARAM]
+ *             floats further.  Every member's tile 0 leaves that member's snapshot.
+ * The stride vector of these three entries has VPC_MS_COUNT_FAMILIES slots: the nine of the entries above, then
+ *   VPC_MS_PARTF   front_partials [tiles][2][K][d] floats of a member (point-net)
+ *   VPC_MS_SNAP    front_snapshot [d_real K + d_real + K (2 + K) + K] floats of a member (point-net)
+ * (vpc_step_small_multi_aug_f32 reads the first eight only).  The images are those of the mask-augmented layout (vpc_build_indices
+ * with mask_augm = 1), resp. the point-net layout (vpc_build_indices_pointnet), rows VPC_MS_IMG apart.
+ * Limits: those of the single-model entries - 2 d_real <= 128 (mask-augmented); K <= 32 and d <= 64 (point-net); d % 4 == 0,
+ * d - d_real <= 3, L <= 15 - and those of the ensemble entries - tiles <= 2 x CUs, G x tiles <= VPC_MULTI_MAX_BLOCKS, every member's
+ * slice inside its stride, read-only inputs may be shared (stride 0), written ones (mask_p and eps under draw != 0, the partial
+ * blocks, front_partials, front_snapshot) not.  VPC_ERR_SHAPE / VPC_ERR_ARG outside them; nothing is launched then. */
+enum { VPC_MS_PARTF = VPC_MS_COUNT, VPC_MS_SNAP, VPC_MS_COUNT_FAMILIES };
+int vpc_step_small_multi_aug_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                 const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                 unsigned long long offset_mask, unsigned long long offset_eps, float inv_B, float x_logvar,
+                                 float* partE, float* partD, double* loss_partials, const long* strides, long B, int d, int d_real,
+                                 int L, int order, void* stream);
+int vpc_step_small_multi_eddi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                  const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                  unsigned long long offset_mask, unsigned long long offset_eps, float inv_B, float x_logvar,
+                                  float* partE, float* partD, double* loss_partials, const long* strides, long B, int d, int d_real,
+                                  int L, int K, const float* front, float* front_partials, float* front_snapshot, int order,
+                                  void* stream);
+/* vpc_reduce_step_adam_eddi with blockIdx.y = member (the tail of vpc_step_small_multi_eddi_f32; the mask-augmented members take
+ * vpc_reduce_step_adam_multi with the mask-augmented layout's maps): per member the trunk and decoder blocks, the loss terms with
+ * the coefficients of record g, the fixed-order sum of ITS front_partials, the chain rule from ITS front_snapshot and Adam with
+ * the member's lr on row g of params / exp_avg / exp_avg_sq [trunk | decoder | front-end] - the front-end in place.  n = trunk +
+ * decoder parameters (pack_idx [n]); d = obs_dim, d_pitch the row pitch of the front-end blocks (<= 64). */
+int vpc_reduce_step_adam_eddi_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials, int blocks,
+                                    long enc_stride, long dec_stride, const long* strides, const int* inv_maps,
+                                    const VpcMember* members, int G, float* grad_out, int n, long B, int d, float* out9,
+                                    float* accum, float* params, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
+                                    float eps, long step, const int* pack_idx, float* img, const float* front_partials,
+                                    const float* front_snapshot, int K, int d_pitch, void* stream);
+
 /* ---- ensemble evaluation: the evaluate stage of G members over a list of batches and M Monte-Carlo passes in one pair of launches
  * (csrc/vpc_evalsmall.hip).  Replaces the loop body of eval_vae, src/experiment_main/evaluate.py:136-297, for Reg_VAE / vanilla_VAE:
  * model.forward (src/models/VAE.py:496-507, :1153-1169), model.loss(llh_eval=True, stage='evaluate') (VAE.py:410-420: the q pass

@@ -397,6 +397,46 @@ __global__ __launch_bounds__(256) void reduce_step_multi_kernel(ReduceMultiArgs 
         finalize_body(a.lp + g * a.sL, a.nb, k, a.out9 + g * 9, a.accum + g, shd, s);
     }
 }
+// reduce_step_eddi_kernel for G members (Reg_EDDI / vanilla_EDDI ensembles): blockIdx.y = member, the block ranges of the
+// single-model launch on blockIdx.x.  Member g's front-end blocks and snapshot are member 0's plus g x their strides; the
+// front-end Adam writes into member g's parameter row in place.  Same bodies, so the summation order and Adam's rounding
+// sequence are those of reduce_step_eddi_kernel.
+struct ReduceMultiPnArgs {
+    ReduceMultiArgs r;
+    FrontTail f;      // member 0's blocks and snapshot
+    long sF, sS;      // member strides of those two (floats)
+};
+__global__ __launch_bounds__(256) void reduce_step_eddi_multi_kernel(ReduceMultiPnArgs pa) {
+    __shared__ f32x4 shf[32][8];
+    __shared__ float shp[4][128];
+    __shared__ float redp[128];
+    __shared__ float snp[FRONT_SNAP];
+    __shared__ double shd[32][LOSS_TERMS];
+    __shared__ double s[LOSS_TERMS];
+    const ReduceMultiArgs& a = pa.r;
+    const long g = blockIdx.y;
+    const VpcMember* r = a.members + g;
+    const int nE4 = (int)(a.strideE >> 2), nD4 = (int)(a.strideD >> 2);
+    const int gE = (nE4 + 7) / 8, gD = (nD4 + 7) / 8, gF = pa.f.d + pa.f.K;
+    const int b = blockIdx.x;
+    if (b < gE + gD + gF) {
+        AdamFuse adam = a.adam;
+        adam.param += g * a.sP; adam.m += g * a.sP; adam.v += g * a.sP; adam.img += g * a.sI;
+        adam.lr = r->lr;
+        float* grad = a.grad + g * a.sP;
+        if (b < gE) reduce_body_v2(a.partE + g * a.sE, a.nb, a.strideE, a.invE, grad, nE4, b, shf, &adam);
+        else if (b < gE + gD) reduce_body_v2(a.partD + g * a.sD, a.nb, a.strideD, a.invD, grad, nD4, b - gE, shf, &adam);
+        else {
+            FrontTail f = pa.f;
+            f.part += g * pa.sF;
+            f.snap += g * pa.sS;
+            front_tail_body(f, b - gE - gD, grad, adam, shp, redp, snp);
+        }
+    } else {
+        const LossCoef k{r->co.cA[0], r->co.cE[0], r->co.cA[1], r->co.bq, r->co.bp, r->co.cr, r->co.wml, a.nll_const, a.inv_B};
+        finalize_body(a.lp + g * a.sL, a.nb, k, a.out9 + g * 9, a.accum + g, shd, s);
+    }
+}
 // inverse maps (block position -> flat parameter index, -1 for padding): built by the explicit entry point
 // vpc_build_inverse_maps into a caller-owned buffer [enc_stride | dec_stride] ints (the library keeps no state)
 __global__ void inv_fill_kernel(int* __restrict__ inv, long n) {
@@ -921,11 +961,12 @@ extern "C" int vpc_reduce_step_adam_bf16c(const float* enc_partials, int enc_blo
                                    accum, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, pack_idx_c, img_c, 1, stream);
 }
 
-extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials,
-                                          int blocks, long enc_stride, long dec_stride, const long* strides, const int* inv_maps,
-                                          const VpcMember* members, int G, float* grad_out, long B, int d, float* out9,
-                                          float* accum, float* params, float* exp_avg, float* exp_avg_sq, float beta1,
-                                          float beta2, float eps, long step, const int* pack_idx, float* img, void* stream) {
+// the argument checks and the ReduceMultiArgs of the two ensemble tails
+static int reduce_multi_prepare(ReduceMultiArgs& a, const float* enc_partials, const float* dec_partials,
+                                const double* loss_partials, int blocks, long enc_stride, long dec_stride, const long* strides,
+                                const int* inv_maps, const VpcMember* members, int G, float* grad_out, long B, int d, float* out9,
+                                float* accum, float* params, float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps,
+                                long step, const int* pack_idx, float* img) {
     if (!enc_partials || !dec_partials || !loss_partials || !strides || !inv_maps || !members || !grad_out || !out9 || !accum)
         return VPC_ERR_ARG;
     if (!params || !exp_avg || !exp_avg_sq || !pack_idx || !img || step < 1) return VPC_ERR_ARG;
@@ -939,7 +980,6 @@ extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float
         return VPC_ERR_ARG;
     const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
     const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    ReduceMultiArgs a{};
     a.partE = enc_partials; a.partD = dec_partials; a.lp = loss_partials;
     a.invE = inv_maps; a.invD = inv_maps + enc_stride;
     a.grad = grad_out; a.out9 = out9; a.accum = accum; a.members = members;
@@ -949,8 +989,46 @@ extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float
     a.nll_const = 0.91893853320467274178 * (double)B * (double)d;
     a.inv_B = 1.0 / (double)B;
     a.nb = blocks;
+    return VPC_OK;
+}
+
+extern "C" int vpc_reduce_step_adam_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials,
+                                          int blocks, long enc_stride, long dec_stride, const long* strides, const int* inv_maps,
+                                          const VpcMember* members, int G, float* grad_out, long B, int d, float* out9,
+                                          float* accum, float* params, float* exp_avg, float* exp_avg_sq, float beta1,
+                                          float beta2, float eps, long step, const int* pack_idx, float* img, void* stream) {
+    ReduceMultiArgs a{};
+    if (const int rc = reduce_multi_prepare(a, enc_partials, dec_partials, loss_partials, blocks, enc_stride, dec_stride, strides,
+                                            inv_maps, members, G, grad_out, B, d, out9, accum, params, exp_avg, exp_avg_sq, beta1,
+                                            beta2, eps, step, pack_idx, img))
+        return rc;
     const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8 + 1);
     hipLaunchKernelGGL(reduce_step_multi_kernel, dim3(grid2, G), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+// vpc_reduce_step_adam_eddi with blockIdx.y = member: n = trunk + decoder parameters of a member's row [trunk | decoder |
+// front-end]; front_partials / front_snapshot are member 0's, strides[VPC_MS_PARTF] / [VPC_MS_SNAP] floats apart.
+extern "C" int vpc_reduce_step_adam_eddi_multi(const float* enc_partials, const float* dec_partials, const double* loss_partials,
+                                               int blocks, long enc_stride, long dec_stride, const long* strides,
+                                               const int* inv_maps, const VpcMember* members, int G, float* grad_out, int n, long B,
+                                               int d, float* out9, float* accum, float* params, float* exp_avg, float* exp_avg_sq,
+                                               float beta1, float beta2, float eps, long step, const int* pack_idx, float* img,
+                                               const float* front_partials, const float* front_snapshot, int K, int d_pitch,
+                                               void* stream) {
+    if (K < 1 || K > 32 || d < 1 || d_pitch < d || d_pitch > 64) return VPC_ERR_SHAPE;
+    if (!front_partials || !front_snapshot || n <= 0) return VPC_ERR_ARG;
+    ReduceMultiPnArgs pa{};
+    if (const int rc = reduce_multi_prepare(pa.r, enc_partials, dec_partials, loss_partials, blocks, enc_stride, dec_stride, strides,
+                                            inv_maps, members, G, grad_out, B, d, out9, accum, params, exp_avg, exp_avg_sq, beta1,
+                                            beta2, eps, step, pack_idx, img))
+        return rc;
+    const long nfront = (long)d * K + d + (long)K * (2 + K) + K;
+    pa.sF = strides[VPC_MS_PARTF]; pa.sS = strides[VPC_MS_SNAP];
+    if (pa.r.sP < n + nfront || pa.sF < (long)blocks * 2 * K * d_pitch || pa.sS < nfront) return VPC_ERR_ARG;
+    pa.f = FrontTail{front_partials, front_snapshot, blocks, K, d, d_pitch, n};
+    const int grid2 = (int)((enc_stride / 4 + 7) / 8 + (dec_stride / 4 + 7) / 8) + d + K + 1;
+    hipLaunchKernelGGL(reduce_step_eddi_multi_kernel, dim3(grid2, G), dim3(256), 0, (hipStream_t)stream, pa);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

@@ -267,22 +267,25 @@ struct PassPair {
     T v0, v1;
     __device__ __forceinline__ T operator[](int p) const { return p == 0 ? v0 : v1; }
 };
-struct MemberArgs {
+// `How` says how the fields that are read late in the step come about (MemberEarly / MemberLate below).
+template <class How>
+struct MemberArgsOf {
     const float* x;
     const float* enc_img;
     const float* dec_img;
-    PassPair<const uint8_t*> m, mB;
+    PassPair<const uint8_t*> m;
+    typename How::MaskB mB;
     PassPair<float> cA, cE;
-    PassPair<const float*> eps;
-    const float* eps_ml;
-    float* partE;
-    float* partD;
-    double* loss_part;
+    typename How::Eps eps;
+    typename How::EpsMl eps_ml;
+    typename How::PartE partE;
+    typename How::PartD partD;
+    typename How::LossPart loss_part;
     float bq, bp, cr, wml, inv_B, x_logvar;
     long B;
     int d, L, npass;
     int draw;
-    int d_real;  // (read by the mask-augmented input stage only, which the ensemble kernels do not have)
+    int d_real;  // (read by the mask-augmented and point-net stages only)
     const uint8_t* mask_in;
     float keep_prob;
     float* eps_out; long n_eps;
@@ -291,6 +294,86 @@ struct MemberArgs {
     long mask_elem_lo;
     EpsShard shard;
 };
+// MemberEarly: every field is a value made at kernel entry.
+struct MemberEarly {
+    using MaskB = PassPair<const uint8_t*>;
+    using Eps = PassPair<const float*>;
+    using EpsMl = const float*;
+    using PartE = float*;
+    using PartD = float*;
+    using LossPart = double*;
+    template <class A>
+    static __device__ __forceinline__ void second_mask(A& a, unsigned, const VpcMember* r) {
+        a.mB.v0 = r->use_maskB ? a.m.v1 : nullptr;  // (the E terms' second mask is the other pass's: cE[0] != 0)
+        a.mB.v1 = nullptr;
+    }
+    template <class A>
+    static __device__ __forceinline__ void planes_and_blocks(A& a, const SmallMultiArgs& ma, unsigned mem) {
+        const SmallArgs& b = ma.base;
+        // (the planes of a member follow each other)
+        a.eps.v0 = b.eps[0] + mem * ma.seps;
+        a.eps.v1 = b.eps[1] ? a.eps.v0 + b.B * 16 : nullptr;
+        a.eps_ml = b.eps_ml ? a.eps.v0 + 2 * b.B * 16 : nullptr;
+        a.partE = b.partE + mem * ma.sE;
+        a.partD = b.partD + mem * ma.sD;
+        a.loss_part = b.loss_part + mem * ma.sL;
+    }
+    template <class A>
+    static __device__ __forceinline__ const float* plane0(const A& a, const SmallMultiArgs&, unsigned) { return a.eps.v0; }
+};
+using MemberArgs = MemberArgsOf<MemberEarly>;
+// MemberLate: the fields the tile body reads from the decoder phases on - the eps planes, whether the E terms take the second
+// mask, where the partial blocks and the loss terms go - are made WHERE they are read, from the kernel-argument segment and the
+// member index.  Made at entry they sit in scalar registers through the encoder forward, the kernels are at the scalar limit
+// there, and the compiler parks them in lanes of a vector register it then holds for the whole step: the one register the
+// DT = 4 instantiations lack (8 bytes of scratch in step_small_multi_kernel<4>).  A read is made opaque, or it joins the loads
+// of the kernel's entry again.  The kernel argument is ONE record at offset 0 of the segment.
+template <class T>
+__device__ __forceinline__ T kernarg_at(unsigned off) {
+    asm volatile("" : "+s"(off));
+    typedef const char __attribute__((address_space(4))) SegByte;
+    typedef const T __attribute__((address_space(4))) SegT;
+    return *(SegT*)((SegByte*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+template <class T, unsigned BASE, unsigned STRIDE>
+struct LatePtr {  // member 0's pointer at BASE of the segment, the member stride (elements) at STRIDE
+    unsigned mem;
+    __device__ __forceinline__ operator T*() const { return kernarg_at<T*>(BASE) + mem * kernarg_at<long>(STRIDE); }
+};
+struct MemberLate {
+    struct MaskB {  // (the tile body asks only whether there is a second mask: it takes the other pass's)
+        unsigned mem;
+        __device__ __forceinline__ bool operator[](int p) const {
+            typedef const VpcMember __attribute__((address_space(4))) ConstMember;  // (the table is not written during the launch)
+            const ConstMember* r = (const ConstMember*)kernarg_at<const VpcMember*>(offsetof(SmallMultiArgs, members));
+            return p == 0 && r[mem].use_maskB != 0;
+        }
+    };
+    struct Eps {  // plane p of the member: eps[0] + g x stride + p B 16 (the body reads plane p < npass only)
+        unsigned mem;
+        __device__ __forceinline__ const float* operator[](int p) const {
+            return kernarg_at<const float*>(offsetof(SmallMultiArgs, base.eps)) + mem * kernarg_at<long>(offsetof(SmallMultiArgs, seps)) +
+                   p * kernarg_at<long>(offsetof(SmallMultiArgs, base.B)) * 16;
+        }
+    };
+    struct EpsMl {  // the third plane (read only where wml != 0: the host then gave three planes)
+        unsigned mem;
+        __device__ __forceinline__ operator const float*() const { return Eps{mem}[2]; }
+    };
+    using PartE = LatePtr<float, offsetof(SmallMultiArgs, base.partE), offsetof(SmallMultiArgs, sE)>;
+    using PartD = LatePtr<float, offsetof(SmallMultiArgs, base.partD), offsetof(SmallMultiArgs, sD)>;
+    using LossPart = LatePtr<double, offsetof(SmallMultiArgs, base.loss_part), offsetof(SmallMultiArgs, sL)>;
+    template <class A>
+    static __device__ __forceinline__ void second_mask(A& a, unsigned mem, const VpcMember*) { a.mB.mem = mem; }
+    template <class A>
+    static __device__ __forceinline__ void planes_and_blocks(A& a, const SmallMultiArgs&, unsigned mem) {
+        a.eps.mem = a.eps_ml.mem = a.partE.mem = a.partD.mem = a.loss_part.mem = mem;
+    }
+    template <class A>
+    static __device__ __forceinline__ const float* plane0(const A&, const SmallMultiArgs& ma, unsigned mem) {
+        return ma.base.eps[0] + mem * ma.seps;  // (for the draws at kernel entry)
+    }
+};
 
 template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArgs ma) {
@@ -298,59 +381,50 @@ __global__ __launch_bounds__(THREADS) void step_small_multi_kernel(SmallMultiArg
     constexpr bool AUG = false;
     constexpr bool PN = false;
     constexpr SmallPointNet pnx{};
-    // (tile, member) of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs by their linear id (x fastest).
-    //   order 0: grid (tiles, G), id = g * tiles + t - the tiles of a member land on different XCDs, every L2 sees every
-    //            member's images;
-    //   order 1: grid (8 x tiles, ceil(G / 8)), t = x / 8, g = 8 y + x % 8 - all tiles of a member sit on ids of one residue
-    //            mod 8, so a member's images are read through ONE L2 (the surplus workgroups of the last member group return).
-    unsigned mem, tile_;
-    if (ma.order == 0) {
-        mem = blockIdx.y;
-        tile_ = blockIdx.x;
-    } else {
-        tile_ = blockIdx.x >> 3;
-        mem = 8 * blockIdx.y + (blockIdx.x & 7);
-        if (mem >= ma.G) return;
-    }
-    const VpcMember* r = ma.members + mem;  // (uniform address: scalar loads)
-    const SmallArgs& b = ma.base;
-    MemberArgs a;
-    a.x = b.x + mem * ma.sx;
-    a.enc_img = b.enc_img + mem * ma.simg;
-    a.dec_img = b.dec_img + mem * ma.simg;
-    a.m.v0 = b.m[0] + mem * ma.sm;
-    a.m.v1 = b.m[1] ? b.m[1] + mem * ma.smp : nullptr;
-    a.mB.v0 = r->use_maskB ? a.m.v1 : nullptr;  // (the E terms' second mask is the other pass's: cE[0] != 0)
-    a.mB.v1 = nullptr;
-    a.cA.v0 = r->co.cA[0]; a.cA.v1 = r->co.cA[1]; a.cE.v0 = r->co.cE[0]; a.cE.v1 = r->co.cE[1];
-    // (the planes of a member follow each other and the draws are those of an unsharded stand-alone step - no device-side state,
-    // element offset 0, all B rows local: derived from eps[0], mask, B and constants instead of carried in registers)
-    a.eps.v0 = b.eps[0] + mem * ma.seps;
-    a.eps.v1 = b.eps[1] ? a.eps.v0 + b.B * 16 : nullptr;
-    a.eps_ml = b.eps_ml ? a.eps.v0 + 2 * b.B * 16 : nullptr;
-    a.partE = b.partE + mem * ma.sE;
-    a.partD = b.partD + mem * ma.sD;
-    a.loss_part = b.loss_part + mem * ma.sL;
-    a.bq = r->co.bq; a.bp = r->co.bp; a.cr = r->co.cr; a.wml = r->co.wml; a.inv_B = b.inv_B; a.x_logvar = b.x_logvar;
-    a.B = b.B; a.d = b.d; a.L = b.L; a.npass = b.npass;
-    a.draw = b.draw;
-    a.d_real = b.d;
-    a.mask_in = b.mask_in ? a.m.v0 : nullptr;
-    a.keep_prob = r->keep_prob;
-    a.eps_out = const_cast<float*>(a.eps.v0);
-    a.n_eps = b.n_eps;
-    a.seed = r->seed; a.off_mask = b.off_mask; a.off_eps = b.off_eps;
-    a.state = nullptr; a.mask_elem_lo = 0; a.shard = EpsShard{b.B, b.B, 0, 16};
-    const unsigned tile_id = tile_;
+    using MemberHow = MemberEarly;
+#include "vpc_small_member.h"
 #include "vpc_small_body.h"
 }
-}  // namespace vpc
+// Reg_VAE_mask / vanilla_VAE_mask members: the frame of step_small_multi_kernel around the mask-augmented tile body
+// (step_small_aug_kernel's).  ma.base.d_real is the members' obs_dim, ma.base.d the row pitch; the images have the mask-augmented layout.
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void step_small_multi_aug_kernel(SmallMultiArgs ma) {
+    constexpr bool AUG = true;
+    constexpr bool PN = false;
+    constexpr SmallPointNet pnx{};
+    using MemberHow = MemberLate;
+#include "vpc_small_member.h"
+#include "vpc_small_body.h"
+}
 
-extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
-                                        const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
-                                        unsigned long long offset_mask, unsigned long long offset_eps, float inv_B,
-                                        float x_logvar, float* partE, float* partD, double* loss_partials, const long* strides,
-                                        long B, int d, int L, int order, void* stream) {
+// Reg_EDDI / vanilla_EDDI members: the same frame around the point-net tile body (step_small_eddi_kernel's).  Member g's
+// SmallPointNet is built in registers beside its MemberArgs: three pointers and K, named field by field (nothing the pass counter
+// indexes, so nothing that would be demoted to scratch).  tile_id is the member's tile: every member's tile 0 leaves ITS snapshot.
+struct SmallMultiPnArgs : SmallMultiArgs {
+    SmallPointNet pn;     // member 0's front-end parameters, (dA | dC) blocks and snapshot
+    long sP, sF, sS;      // member strides of those three, in floats
+};
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void step_small_multi_eddi_kernel(SmallMultiPnArgs ma) {
+    constexpr bool AUG = false;
+    constexpr bool PN = true;
+    using MemberHow = MemberLate;
+#include "vpc_small_member.h"
+    SmallPointNet pnx;
+    pnx.K = ma.pn.K;
+    pnx.front = ma.pn.front + mem * ma.sP;
+    pnx.partF = ma.pn.partF + mem * ma.sF;
+    pnx.snap = ma.pn.snap + mem * ma.sS;
+#include "vpc_small_body.h"
+}
+
+// The argument checks and the SmallMultiArgs of the three ensemble step entries.  d_real 0: the plain members (d is obs_dim);
+// else d is the row pitch of obs_dim d_real.  Returns VPC_OK with `ma` and `grid` filled, or the refusal.
+static int multi_prepare(SmallMultiArgs& ma, dim3& grid, const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps,
+                         const float* enc_img, const float* dec_img, const VpcMember* members, int G, int npass, int nplanes,
+                         int draw, unsigned long long offset_mask, unsigned long long offset_eps, float inv_B, float x_logvar,
+                         float* partE, float* partD, double* loss_partials, const long* strides, long B, int d, int d_real, int L,
+                         int order) {
     if (!x || !mask || !eps || !enc_img || !dec_img || !members || !partE || !partD || !loss_partials || !strides) return VPC_ERR_ARG;
     if (G < 1 || npass < 1 || npass > 2 || B <= 0 || order < 0 || order > 1) return VPC_ERR_ARG;
     if (npass == 2 ? (!mask_p || nplanes < 2 || nplanes > 3) : nplanes != 1) return VPC_ERR_ARG;
@@ -368,10 +442,9 @@ extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uin
     if ((seps != 0 && seps < ne) || seps % 4 || (draw && seps == 0 && G > 1)) return VPC_ERR_ARG;
     if (simg <= 0 || simg % 4) return VPC_ERR_ARG;
     if (sE < tiles * ENC_PART || sE % 4 || sD < tiles * DEC_PART || sD % 4 || sL < tiles * LOSS_TERMS) return VPC_ERR_ARG;
-    SmallMultiArgs ma{};
     SmallArgs& a = ma.base;
     a.x = x; a.enc_img = enc_img; a.dec_img = dec_img; a.partE = partE; a.partD = partD; a.loss_part = loss_partials;
-    a.inv_B = inv_B; a.x_logvar = x_logvar; a.B = B; a.d = d; a.L = L; a.npass = npass; a.ntiles = (int)tiles;
+    a.inv_B = inv_B; a.x_logvar = x_logvar; a.B = B; a.d = d; a.d_real = d_real; a.L = L; a.npass = npass; a.ntiles = (int)tiles;
     a.m[0] = mask;
     a.eps[0] = eps;
     if (npass == 2) { a.m[1] = mask_p; a.eps[1] = eps + B * 16; }
@@ -384,19 +457,96 @@ extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uin
     ma.members = members;
     ma.sx = sx; ma.sm = sm; ma.smp = smp; ma.seps = seps; ma.simg = simg; ma.sE = sE; ma.sD = sD; ma.sL = sL;
     ma.G = (unsigned)G; ma.tiles = (unsigned)tiles; ma.order = order;
-    const dim3 grid = order == 0 ? dim3((unsigned)tiles, (unsigned)G) : dim3((unsigned)(8 * tiles), (unsigned)((G + 7) / 8));
-    hipStream_t s = (hipStream_t)stream;
-#define VPC_CASE(T)                                                                                        \
-    case T: {                                                                                              \
-        auto kern = step_small_multi_kernel<T>;                                                            \
+    grid = order == 0 ? dim3((unsigned)tiles, (unsigned)G) : dim3((unsigned)(8 * tiles), (unsigned)((G + 7) / 8));
+    return VPC_OK;
+}
+}  // namespace vpc
+
+#define VPC_MULTI_LAUNCH(KERN, ARGS)                                                                       \
+    {                                                                                                      \
+        auto kern = KERN;                                                                                  \
         if (!lds_attr_done(reinterpret_cast<const void*>(kern), SMALL_LDS)) return VPC_ERR_HIP;            \
-        hipLaunchKernelGGL(kern, grid, dim3(THREADS), SMALL_LDS, s, ma);                             \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), SMALL_LDS, (hipStream_t)stream, ARGS);               \
         return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;                                     \
     }
-    switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
-#undef VPC_CASE
+
+extern "C" int vpc_step_small_multi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                        const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                        unsigned long long offset_mask, unsigned long long offset_eps, float inv_B,
+                                        float x_logvar, float* partE, float* partD, double* loss_partials, const long* strides,
+                                        long B, int d, int L, int order, void* stream) {
+    SmallMultiArgs ma{};
+    dim3 grid;
+    if (const int rc = multi_prepare(ma, grid, x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask,
+                                     offset_eps, inv_B, x_logvar, partE, partD, loss_partials, strides, B, d, 0, L, order))
+        return rc;
+    switch (dt_for(d)) {
+        case 1: VPC_MULTI_LAUNCH(step_small_multi_kernel<1>, ma)
+        case 2: VPC_MULTI_LAUNCH(step_small_multi_kernel<2>, ma)
+        case 4: VPC_MULTI_LAUNCH(step_small_multi_kernel<4>, ma)
+        case 8: VPC_MULTI_LAUNCH(step_small_multi_kernel<8>, ma)
+    }
     return VPC_ERR_SHAPE;
 }
+
+// The ensemble step for G Reg_VAE_mask / vanilla_VAE_mask members (vpc_step_small_aug(_draw)_f32 per member): d is the row pitch
+// 4 ceil(d_real / 4) of x and the masks - the pitch the draws are made at -, the images are those of the mask-augmented layout.
+extern "C" int vpc_step_small_multi_aug_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                            const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                            unsigned long long offset_mask, unsigned long long offset_eps, float inv_B,
+                                            float x_logvar, float* partE, float* partD, double* loss_partials, const long* strides,
+                                            long B, int d, int d_real, int L, int order, void* stream) {
+    // (the shape limits of step_small_launch's mask-augmented branch)
+    if (d_real < 1 || d_real > d || d - d_real > 3 || 2 * d_real > MAX_D) return VPC_ERR_SHAPE;
+    SmallMultiArgs ma{};
+    dim3 grid;
+    if (const int rc = multi_prepare(ma, grid, x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask,
+                                     offset_eps, inv_B, x_logvar, partE, partD, loss_partials, strides, B, d, d_real, L, order))
+        return rc;
+    switch (dt_for(2 * d_real)) {
+        case 1: VPC_MULTI_LAUNCH((step_small_multi_aug_kernel<1, 1>), ma)
+        case 2: VPC_MULTI_LAUNCH((step_small_multi_aug_kernel<2, 1>), ma)
+        case 4: VPC_MULTI_LAUNCH((step_small_multi_aug_kernel<4, 2>), ma)
+        case 8: VPC_MULTI_LAUNCH((step_small_multi_aug_kernel<8, 4>), ma)
+    }
+    return VPC_ERR_SHAPE;
+}
+
+// The ensemble step for G Reg_EDDI / vanilla_EDDI members (vpc_step_small_eddi(_draw)_f32 per member): images of the point-net
+// layout; front / front_partials / front_snapshot are member 0's, member g's lie strides[VPC_MS_PARAM] / [VPC_MS_PARTF] /
+// [VPC_MS_SNAP] floats further (`front` sits inside the member's row of the parameter stack, behind trunk and decoder).
+extern "C" int vpc_step_small_multi_eddi_f32(const float* x, const uint8_t* mask, uint8_t* mask_p, float* eps, const float* enc_img,
+                                             const float* dec_img, const VpcMember* members, int G, int npass, int nplanes, int draw,
+                                             unsigned long long offset_mask, unsigned long long offset_eps, float inv_B,
+                                             float x_logvar, float* partE, float* partD, double* loss_partials, const long* strides,
+                                             long B, int d, int d_real, int L, int K, const float* front, float* front_partials,
+                                             float* front_snapshot, int order, void* stream) {
+    // (the shape limits of step_small_launch's point-net branch, and its pointer checks)
+    if (d_real < 1 || d_real > d || d - d_real > 3 || d > 64 || K < 1 || K > 32) return VPC_ERR_SHAPE;
+    if (!front || !front_partials || !front_snapshot || (uintptr_t)front % 4 || (uintptr_t)front_partials % 4 ||
+        (uintptr_t)front_snapshot % 4)
+        return VPC_ERR_ARG;
+    SmallMultiPnArgs ma{};
+    dim3 grid;
+    if (const int rc = multi_prepare(ma, grid, x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask,
+                                     offset_eps, inv_B, x_logvar, partE, partD, loss_partials, strides, B, d, d_real, L, order))
+        return rc;
+    const long nfront = (long)d_real * K + d_real + (long)K * (2 + K) + K;
+    ma.pn = SmallPointNet{K, front, front_partials, front_snapshot};
+    ma.sP = strides[VPC_MS_PARAM]; ma.sF = strides[VPC_MS_PARTF]; ma.sS = strides[VPC_MS_SNAP];
+    // the blocks and the snapshot are written by every member: never shared; the parameters are read here, but every member has its own row
+    if (ma.sP < nfront || ma.sF < (long)ma.tiles * 2 * K * d || ma.sS < nfront) return VPC_ERR_ARG;
+    switch (4 * dt_for(K) + dt_for(d_real)) {
+        case 4 * 1 + 1: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<1, 1>), ma)
+        case 4 * 1 + 2: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<1, 2>), ma)
+        case 4 * 1 + 4: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<1, 4>), ma)
+        case 4 * 2 + 1: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<2, 1>), ma)
+        case 4 * 2 + 2: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<2, 2>), ma)
+        case 4 * 2 + 4: VPC_MULTI_LAUNCH((step_small_multi_eddi_kernel<2, 4>), ma)
+    }
+    return VPC_ERR_SHAPE;
+}
+#undef VPC_MULTI_LAUNCH
 
 // The same step for Reg_VAE_mask / vanilla_VAE_mask (src/models/VAE.py:545-555, 1031-1041; src/experiment_main/train.py:87-115):
 // encoder input [x*mask | mask] of width 2 d_real built in the kernel's input stage, images of the mask-augmented layout.  d is the

@@ -1,8 +1,9 @@
 // The step of ONE 16-row tile: the BODY of the small-batch whole-step kernels of vpc_small.hip, included as text into
 //   step_small_kernel        (a = the SmallArgs kernel argument, tile_id = blockIdx.x),
-//   step_small_aug_kernel    (the same for the mask-augmented classes) and
-//   step_small_multi_kernel  (a = member g's arguments built in registers, MemberArgs - the same fields -, tile_id = the
-//                             member's tile),
+//   step_small_aug_kernel    (the same for the mask-augmented classes), step_small_eddi_kernel (the point-net classes) and
+//   step_small_multi_kernel, step_small_multi_aug_kernel, step_small_multi_eddi_kernel
+//                            (a = member g's arguments built in registers, MemberArgs - the same fields -, tile_id = the
+//                             member's tile: vpc_small_member.h),
 // so that both run ONE piece of code - a member of an ensemble computes bit for bit what its stand-alone step computes - and
 // the single-model kernel compiles to the instructions it had as a self-contained kernel (a shared inline function is
 // simplified before it is inlined, without knowing that `a` is the kernel-argument segment, and schedules differently).

@@ -16,6 +16,9 @@ computes on its data: same tile body, same summation order, same Philox counters
     MemberTable                  the per-member records (loss coefficients, keep probability, lr, seed) on the host
     _MemberSet                   what the three classes hold of their members: stacks, device member table, fresh images, inputs
     EnsembleTrainer              the step, the read-outs and per-member views of the stacked state
+    MaskEnsembleTrainer          the same for G Reg_VAE_mask / vanilla_VAE_mask members (vpc_step_small_multi_aug_f32)
+    EDDIEnsembleTrainer          ... and for G Reg_EDDI / vanilla_EDDI members (vpc_step_small_multi_eddi_f32 +
+                                 vpc_reduce_step_adam_eddi_multi); Family says what the three differ in
 
 The sweep's evaluation (eval_vae, evaluate.py:136-297) and its active variable selection (active_learning_func,
 evaluate.py:300-511) share their launches the same way: EnsembleEvaluator over build_eval_tables, EnsembleAcquirer over
@@ -25,7 +28,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import NamedTuple
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -34,7 +37,8 @@ from . import _lib as L
 from . import ops
 from .fused import LP
 from .images import PackedImage, flat_written
-from .models import Reg_VAE, loss_coefficients, vanilla_VAE
+from .eddi import Reg_EDDI, vanilla_EDDI
+from .models import Reg_VAE, Reg_VAE_mask, loss_coefficients, vanilla_VAE, vanilla_VAE_mask
 from .ops import as_mask_u8, stride_vector
 from .trainer import draw_counters, eval_draw_counters, pad_cols, padded_width
 
@@ -98,35 +102,67 @@ def _require_stackable(m):
         raise TypeError(f"EnsembleTrainer supports Reg_VAE and vanilla_VAE members, got {type(m).__name__}")
 
 
-def validate_members(models, world_size=1):
-    """What one ensemble can hold: stackable members of ONE class, shape and reg_type, on one process.  Raises before
-    anything touches the device."""
+class Family(NamedTuple):
+    """What the member families of the ensemble step differ in on the host: who may be a member, what the members of one
+    ensemble share, the layout of their weight images and the row pitch of x / mask / mask_p in the kernels."""
+    require: Callable  # model -> None, or raises (TypeError: not this family's class; VpcError: a shape past its kernels)
+    shared: Callable  # model -> the tuple the members of one ensemble agree in
+    shared_names: str
+    layout: Callable  # model -> _lib.Layout of the images the step reads and the tail re-packs
+    pitch: Callable  # obs_dim -> row pitch
+
+
+def _require_mask(m):
+    if type(m) not in (Reg_VAE_mask, vanilla_VAE_mask):
+        raise TypeError(f"MaskEnsembleTrainer supports Reg_VAE_mask and vanilla_VAE_mask members, got {type(m).__name__}")
+    if m._wide:
+        raise L.VpcError("mask-augmented ensemble members have 2 * obs_dim <= 128 and latent_dim <= 15")
+
+
+def _require_eddi(m):
+    if type(m) not in (Reg_EDDI, vanilla_EDDI):
+        raise TypeError(f"EDDIEnsembleTrainer supports Reg_EDDI and vanilla_EDDI members, got {type(m).__name__}")
+    if ops.small_eddi_tiles(m.obs_dim, m.emb_dim) is None:
+        raise L.VpcError("point-net ensemble members have obs_dim <= 64 and emb_dim <= 32 (the small-batch step's instantiations)")
+
+
+_dense_shared = lambda m: (m.obs_dim, m.latent_dim, getattr(m, "reg_type", None))
+PLAIN = Family(_require_stackable, _dense_shared, "(obs_dim, latent_dim, reg_type)", lambda m: m._lay(), padded_width)
+MASK = Family(_require_mask, _dense_shared, "(obs_dim, latent_dim, reg_type)", lambda m: m._lay(), ops.small_aug_pitch)
+EDDI = Family(_require_eddi, lambda m: (m.obs_dim, m.emb_dim, m.latent_dim, getattr(m, "reg_type", None)),
+              "(obs_dim, emb_dim, latent_dim, reg_type)",
+              lambda m: L.pointnet_layout(m.obs_dim, m.emb_dim, m.latent_dim), ops.small_aug_pitch)
+
+
+def validate_members(models, world_size=1, family=PLAIN):
+    """What one ensemble can hold: stackable members of ONE class, shape and reg_type, on one process (`family`: the same
+    rule for the mask-augmented and the point-net members).  Raises before anything touches the device."""
     if world_size > 1:
         raise L.VpcError("EnsembleTrainer is single-process: data parallelism is not part of the ensemble step")
     if len(models) == 0:
         raise L.VpcError("an ensemble needs at least one member")
     for m in models:
-        _require_stackable(m)
+        family.require(m)
     m0 = models[0]
     for m in models[1:]:
         if type(m) is not type(m0):
             raise TypeError(f"members of one ensemble share a class: {type(m0).__name__} and {type(m).__name__}")
-        a = (m.obs_dim, m.latent_dim, getattr(m, "reg_type", None))
-        b = (m0.obs_dim, m0.latent_dim, getattr(m0, "reg_type", None))
+        a, b = family.shared(m), family.shared(m0)
         if a != b:
-            raise L.VpcError(f"members of one ensemble share (obs_dim, latent_dim, reg_type): {b} and {a}")
+            raise L.VpcError(f"members of one ensemble share {family.shared_names}: {b} and {a}")
 
 
-def stack_models(models):
+def stack_models(models, require=_require_stackable):
     """Put the trainable tensors of `models` (same parameter count, already on their device) into ONE [G, n] fp32 buffer:
     model g's tensors become views of row g in table order, so that model.flatten_parameters() returns row g through its
     fast path.  state_dict / in-place load_state_dict / the API path keep working; `.to(device)` afterwards un-stacks a
-    model (stack again).  Idempotent for the same list.  Returns the [G, n] buffer (rows 256-byte aligned)."""
+    model (stack again).  Idempotent for the same list.  Returns the [G, n] buffer (rows 256-byte aligned).
+    require: the membership rule of the caller's family (Family.require)."""
     models = list(models)
     if len(models) == 0:
         raise L.VpcError("an ensemble needs at least one member")
     for m in models:
-        _require_stackable(m)
+        require(m)
     first = models[0].__dict__.get("_stack")
     if first is not None and len(first[1]) == len(models) and all(a is b for a, b in zip(first[1], models)) and \
             all(m.flatten_parameters().data_ptr() == first[0][g].data_ptr() for g, m in enumerate(models)):
@@ -232,18 +268,18 @@ class _MemberSet:
     """What EnsembleTrainer, EnsembleEvaluator and EnsembleAcquirer hold of their members, stated once: validation (raised
     before anything touches the device), member table, parameter and image stack, image freshness, inputs at the row pitch."""
 
-    def __init__(self, models, lr, seeds, world_size):
+    def __init__(self, models, lr, seeds, world_size, family=PLAIN):
         models = list(models)
-        validate_members(models, world_size)
+        validate_members(models, world_size, family)
         self.table = MemberTable(models, lr, seeds)
         self.models = models
         self.rng_offset = 0
         # ---- device state from here on
-        self.params = stack_models(models)
+        self.params = stack_models(models, family.require)
         L.require_cuda(self.params)
         self.G, self.dev = len(models), self.params.device
-        self.lay = lay = models[0]._lay()
-        self.n_img, self.dk = lay.enc_img + lay.dec_img, padded_width(lay.d)  # (dk: row pitch of x / mask in the kernels)
+        self.lay = lay = family.layout(models[0])
+        self.n_img, self.dk = lay.enc_img + lay.dec_img, family.pitch(lay.d)  # (dk: row pitch of x / mask in the kernels)
         self._plists = [m.trainable() for m in models]
         self._pads = {}  # pad_cols buffers of this object: slot 0 = x, slot 1 = mask
 
@@ -260,6 +296,13 @@ class _MemberSet:
             self.table_dev.copy_(torch.from_numpy(self.table.rows.view(np.uint8).reshape(-1)))
             self._table_version = self.table.version
 
+    def _member_image(self, g):
+        """The PackedImage of member g that the launches read: the model's own (a row of the image stack)."""
+        return self.models[g]._img
+
+    def _repack(self, g, key):
+        self.models[g]._images(key)
+
     def _fresh_images(self, row_ptr=None):
         """Re-pack every image whose parameter key is stale (images.py) -> the keys.  row_ptr: the trainer's rows of the stack."""
         keys = []
@@ -267,8 +310,8 @@ class _MemberSet:
             key = m._param_key(self._plists[g])
             if row_ptr is not None and key[1] != row_ptr[g]:
                 raise L.VpcError(f"member {g} no longer sits in the ensemble's parameter stack (moved or re-flattened)")
-            if m._img.key != key:
-                m._images(key)
+            if self._member_image(g).key != key:
+                self._repack(g, key)
             keys.append(key)
         return keys
 
@@ -287,11 +330,13 @@ class _MemberSet:
 
 
 class EnsembleTrainer(_MemberSet):
+    family = PLAIN  # (MaskEnsembleTrainer and EDDIEnsembleTrainer below: the same frame around their families' launches)
+
     def __init__(self, models, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seeds=None, world_size=1):
         """models: G plain Reg_VAE or G plain vanilla_VAE of one (obs_dim, latent_dim, reg_type), on the GPU.  lr and seeds:
         scalars or one value per member (seeds=None: member g draws with seed g).  The step count (Adam's bias corrections)
         and the Philox offsets are shared: every member steps in every call."""
-        super().__init__(models, lr, seeds, world_size)
+        super().__init__(models, lr, seeds, world_size, self.family)
         self.betas, self.adam_eps = betas, eps
         self.step_count = 0
         G, n = self.params.shape
@@ -329,11 +374,33 @@ class EnsembleTrainer(_MemberSet):
             self.partD = torch.empty(G, tiles * lay.dec_part, device=dev)
             self.loss_part = torch.empty(G, tiles * 8, dtype=torch.float64, device=dev)
             self._tiles_cap = tiles
-        self._strides = stride_vector(ops.MS_COUNT, {  # of what the trainer owns; a step fills in those of its x and mask
+        own = {  # the strides of what the trainer owns; a step fills in those of its x and mask
             ops.MS_MASK_P: self.mask_p_buf.stride(0), ops.MS_EPS: self.eps_buf.stride(0), ops.MS_IMG: self.img.stride(0),
             ops.MS_PARTE: self.partE.stride(0), ops.MS_PARTD: self.partD.stride(0), ops.MS_LOSS: self.loss_part.stride(0),
-            ops.MS_PARAM: self.row_pitch})
+            ops.MS_PARAM: self.row_pitch, **self._family_workspaces(tiles)}
+        self._strides = stride_vector(max(own) + 1 if max(own) >= ops.MS_COUNT else ops.MS_COUNT, own)
         self._ws = (B, dk)
+
+    def _family_workspaces(self, tiles):
+        """Per-tile buffers a family's launches take besides -> {stride slot: member stride}."""
+        return {}
+
+    def _check_draws(self, draw):
+        """Whether this family can make the step's draws in the launch (raises before anything is launched or counted)."""
+
+    def _launch_step(self, x, mask, two, nplanes, draw, off_m, off_e, strides, B):
+        lay = self.lay
+        ops.step_small_multi_f32(x, mask, self.mask_p_buf if two else None, self.eps_buf, self.img[0, :lay.enc_img],
+                                 self.img[0, lay.enc_img:], self.table_dev, self.G, 2 if two else 1, nplanes, draw, off_m, off_e,
+                                 1.0 / B, self.models[0]._x_logvar_value, self.partE, self.partD, self.loss_part, strides, B,
+                                 self.dk, lay.L, self.order)
+
+    def _launch_tail(self, tiles, strides, B):
+        lay = self.lay
+        ops.reduce_step_adam_multi(self.partE, self.partD, self.loss_part, tiles, lay.enc_part, lay.dec_part, strides,
+                                   self.inv, self.table_dev, self.G, self.grad, B, lay.d, self.out9, self.accum, self.params,
+                                   self.exp_avg, self.exp_avg_sq, self.betas[0], self.betas[1], self.adam_eps,
+                                   self.step_count, self.pidx, self.img)
 
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=1.0, beta=1.0,
              beta_annealing=False, p_missingness=30):
@@ -357,6 +424,7 @@ class EnsembleTrainer(_MemberSet):
         if any(given) != all(given):
             raise L.VpcError("inject all of the step's draws (mask_p, eps_q, eps_p, eps_ml as the model uses them) or none")
         draw = not any(given)
+        self._check_draws(draw)
         x, mask, sx, smask = self._padded_inputs(x, mask, per_x, per_mask)
         self._workspaces(B, dk)
         self._sync_table()
@@ -372,17 +440,11 @@ class EnsembleTrainer(_MemberSet):
                 self.eps_buf[:, k, :, :Ld].copy_(e)
         strides = self._strides
         strides[ops.MS_X], strides[ops.MS_MASK] = sx, smask
-        ops.step_small_multi_f32(x, mask, self.mask_p_buf if two else None, self.eps_buf, self.img[0, :lay.enc_img],
-                                 self.img[0, lay.enc_img:], self.table_dev, G, 2 if two else 1, nplanes, draw, off_m, off_e,
-                                 1.0 / B, self.models[0]._x_logvar_value, self.partE, self.partD, self.loss_part, strides, B, dk,
-                                 Ld, self.order)
+        self._launch_step(x, mask, two, nplanes, draw, off_m, off_e, strides, B)
         self.step_count += 1
-        ops.reduce_step_adam_multi(self.partE, self.partD, self.loss_part, tiles, lay.enc_part, lay.dec_part, strides,
-                                   self.inv, self.table_dev, G, self.grad, B, d, self.out9, self.accum, self.params,
-                                   self.exp_avg, self.exp_avg_sq, self.betas[0], self.betas[1], self.adam_eps,
-                                   self.step_count, self.pidx, self.img)
+        self._launch_tail(tiles, strides, B)
         for g, m in enumerate(self.models):
-            flat_written(m, self._plists[g], keys[g], (m._img,))
+            flat_written(m, self._plists[g], keys[g], (self._member_image(g),))
 
     # ------------------------------------------------------------------
     def loss_values(self):
@@ -399,6 +461,99 @@ class EnsembleTrainer(_MemberSet):
     def evaluator(self):
         """An EnsembleEvaluator on this trainer's members, with their seeds: it reads the image stack the step re-packs."""
         return EnsembleEvaluator(self.models, seeds=self.table.rows["seed"].tolist())
+
+
+class _FamilyTrainer(EnsembleTrainer):
+    def evaluator(self):
+        raise L.VpcError("ensemble evaluation and acquisition cover the plain Reg_VAE / vanilla_VAE members only: evaluate "
+                         "mask-augmented and point-net members one by one (harness.eval_vae, eval_sweep does)")
+
+
+class MaskEnsembleTrainer(_FamilyTrainer):
+    """EnsembleTrainer for G Reg_VAE_mask or G vanilla_VAE_mask of one (obs_dim, latent_dim, reg_type): step(), loss_values(),
+    epoch_total() and trainers[g] as there.  Rows of x, mask and mask_p go at ops.small_aug_pitch(obs_dim) columns (mask 0 in
+    the padding) and the device draws are made in the launch at that pitch - the counters of FusedTrainer's small-batch path,
+    so member g computes bit for bit what its stand-alone FusedTrainer computes there."""
+    family = MASK
+
+    def _launch_step(self, x, mask, two, nplanes, draw, off_m, off_e, strides, B):
+        lay = self.lay
+        ops.step_small_multi_aug_f32(x, mask, self.mask_p_buf if two else None, self.eps_buf, self.img[0, :lay.enc_img],
+                                     self.img[0, lay.enc_img:], self.table_dev, self.G, 2 if two else 1, nplanes, draw, off_m,
+                                     off_e, 1.0 / B, self.models[0]._x_logvar_value, self.partE, self.partD, self.loss_part,
+                                     strides, B, self.dk, lay.d, lay.L, self.order)
+
+
+class EDDIEnsembleTrainer(_FamilyTrainer):
+    """EnsembleTrainer for G Reg_EDDI or G vanilla_EDDI of one (obs_dim, emb_dim, latent_dim, reg_type).  A row of the
+    parameter stack is [trunk | decoder | front-end] as under EDDITrainer; the image stack holds the point-net layout's
+    images of trunk and decoder (the one EDDITrainer's small-batch step packs, not model._lay()'s: the models' own images
+    stay theirs).  Draws follow EDDITrainer's small-batch rule: counters at the pitch obs_dim, so the launch can make them
+    only where obs_dim % 4 == 0 (the kernel's rows have 4 * ceil(obs_dim / 4) columns); for other widths step() takes the
+    step's draws injected - all of them, at every obs_dim <= 64 - and refuses to draw: the stand-alone stream is pinned to the
+    unpadded pitch, and one draw launch per member would undo the point of the ensemble."""
+    family = EDDI
+
+    def _image_stack_and_table(self, new_image_stack):
+        lay, n = self.lay, self.lay.n_params
+        self.img = torch.from_numpy(lay.img_template).to(self.dev).repeat(self.G, 1)
+        pidx = lay.device_tables(self.dev)[0]
+        self._images_pn = [PackedImage(self.img[g], lambda flat, buf: ops.pack_weights(flat[:n], pidx, buf))
+                           for g in range(self.G)]
+        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self._table_version = -1
+
+    def _member_image(self, g):
+        return self._images_pn[g]
+
+    def _repack(self, g, key):
+        self._images_pn[g].get(key, self.models[g]._flat)
+
+    def _family_workspaces(self, tiles):
+        K, n_front = self.lay.K, self.lay.n_front
+        if getattr(self, "_front_cap", 0) < tiles:
+            self.partF = torch.empty(self.G, tiles * 2 * K * self.dk, device=self.dev)
+            self.snap = torch.empty(self.G, _pitch(n_front), device=self.dev)
+            self._front_cap = tiles
+        return {ops.MS_PARTF: self.partF.stride(0), ops.MS_SNAP: self.snap.stride(0)}
+
+    def _check_draws(self, draw):
+        if draw and self.dk != self.lay.d:
+            raise L.VpcError(f"obs_dim {self.lay.d} is not a multiple of 4: the ensemble step cannot make a point-net member's "
+                             "draws in its launch (the stand-alone stream is drawn at the unpadded pitch, the kernel's rows "
+                             f"have {self.dk} columns); inject mask_p and the eps planes")
+
+    def _launch_step(self, x, mask, two, nplanes, draw, off_m, off_e, strides, B):
+        lay = self.lay
+        ops.step_small_multi_eddi_f32(x, mask, self.mask_p_buf if two else None, self.eps_buf, self.img[0, :lay.enc_img],
+                                      self.img[0, lay.enc_img:], self.table_dev, self.G, 2 if two else 1, nplanes, draw, off_m,
+                                      off_e, 1.0 / B, self.models[0]._x_logvar_value, self.partE, self.partD, self.loss_part,
+                                      strides, B, self.dk, lay.d, lay.L, lay.K, self.params[0, lay.n_params:], self.partF,
+                                      self.snap, self.order)
+
+    def _launch_tail(self, tiles, strides, B):
+        lay = self.lay
+        ops.reduce_step_adam_eddi_multi(self.partE, self.partD, self.loss_part, tiles, lay.enc_part, lay.dec_part, strides,
+                                        self.inv, self.table_dev, self.G, self.grad, lay.n_params, B, lay.d, self.out9,
+                                        self.accum, self.params, self.exp_avg, self.exp_avg_sq, self.betas[0], self.betas[1],
+                                        self.adam_eps, self.step_count, self.pidx, self.img, self.partF, self.snap, lay.K, self.dk)
+
+
+def sweep_family(model, vae_type, loader, obs_dim):
+    """"mask" / "eddi": train_sweep may step the mask-augmented / point-net `model` with others of its kind
+    (MaskEnsembleTrainer / EDDIEnsembleTrainer); None: it may not.  No 'with_drop' run, a shape the family's step kernels are
+    instantiated for, a first batch within the small-batch step and, for the point-net classes, obs_dim % 4 == 0
+    (EDDIEnsembleTrainer draws in its launch only there)."""
+    for name, family in (("mask", MASK), ("eddi", EDDI)):
+        try:
+            family.require(model)
+        except (TypeError, L.VpcError):
+            continue
+        if "with_drop" in vae_type or (family is EDDI and model.obs_dim % 4):
+            return None
+        first = next(iter(loader), None)
+        return name if first is not None and first[0].reshape(-1, obs_dim).shape[0] <= ops.step_small_max_rows() else None
+    return None
 
 
 # ------------------------------------------------------------------------------------------------ evaluation

@@ -24,6 +24,8 @@ data treatment and whether the loader comes alone (MNAR) or as a pair.
 """
 from __future__ import annotations
 
+import contextlib
+import io
 import itertools
 import os
 
@@ -31,7 +33,8 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .ensemble import EnsembleEvaluator, EnsembleTrainer, stackable, steps_in_ensemble
+from .ensemble import (EDDIEnsembleTrainer, EnsembleEvaluator, EnsembleTrainer, MaskEnsembleTrainer, stackable, steps_in_ensemble,
+                       sweep_family)
 from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
@@ -268,6 +271,37 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
     return model
 
 
+def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type,
+                   training_parameters, max_epochs, train_k, num_estimates, experiment_type, reg_type):
+    """{member index: key} of the mask-augmented and point-net members of a sweep that step in an ensemble: those whose key
+    (family, model class, reg_type, ml_reg term on, emb_dim) at least one other member shares.  Decided BEFORE any member
+    is built or trained, so that train_sweep still trains every other member at once, in the order of configs.  A member's
+    class is that of models[g], else of a throw-away model_loader() build; the probe and the look at the first batch leave
+    torch's generator where it was (the members' initial weights and a shuffling loader's order are what they are without it)."""
+    keys = {}
+    with torch.random.fork_rng(devices=[]):
+        for g, c in enumerate(cfgs):
+            vt = c["vae_type"]
+            if models is None and not ("mask_augm" in vt or "EDDI" in vt):  # (no other vae_type builds these classes)
+                continue
+            if models is not None:
+                m = models[g]
+            else:
+                with contextlib.redirect_stdout(io.StringIO()):
+                    m = model_loader("train", obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
+                                     max_epochs, train_k, num_estimates, experiment_type, reg_type, vt, alpha=c["alpha"],
+                                     p_missingness=c["p_missingness"])
+            loader = data_loader_train if loaders is None else loaders[g]
+            name = sweep_family(m, vt, loader[0], obs_dim)
+            if name is not None:
+                keys[g] = (name, type(m), getattr(m, "reg_type", None),
+                           getattr(m, "reg_type", None) == "ml_reg" and c["alpha"] != 0.0, getattr(m, "emb_dim", None))
+    count = {}
+    for k in keys.values():
+        count[k] = count.get(k, 0) + 1
+    return {g: k for g, k in keys.items() if count[k] >= 2}
+
+
 def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
                 experiment_type, train_k, num_estimates, max_epochs=1000, device=torch.device("cuda"), stage="train",
                 reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, save=True, verbose=True,
@@ -278,10 +312,16 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
     train() takes, shared by every member; or loaders = one such object per member (different splits), which must yield
     equal batch shapes at every step.  models (optional): one pre-built model per member, as train(model=).
     Plain Reg_VAE / vanilla_VAE members of one class and reg_type step together, one ensemble.EnsembleTrainer.step per batch
-    (a mixed list is split into such groups); every other family, and batches beyond the small-batch step, go through train()
-    one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints the
-    reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
+    (a mixed list is split into such groups).  Mask-augmented members (Reg_VAE_mask / vanilla_VAE_mask) and point-net members
+    (Reg_EDDI / vanilla_EDDI with obs_dim % 4 == 0) are grouped by class, reg_type, whether the ml_reg term is on and, for the
+    point-net classes, emb_dim: a group of two or more steps through ensemble.MaskEnsembleTrainer / EDDIEnsembleTrainer, a
+    group of one goes through train().  'with_drop' runs stay alone (train()'s loop thins their mask with a drop mask of its
+    own at every step), and so do every other family, point-net members of another width and batches beyond the small-batch
+    step: train(), one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints
+    the reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
     cfgs = _sweep_configs(configs, models, loaders)
+    fam = _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type,
+                         training_parameters, max_epochs, train_k, num_estimates, experiment_type, reg_type)
     out, keys = [], []
     for g, c in enumerate(cfgs):
         loader = data_loader_train if loaders is None else loaders[g]
@@ -290,15 +330,17 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
             num_estimates, experiment_type, reg_type, c["vae_type"], alpha=c["alpha"], p_missingness=c["p_missingness"])
         out.append(m.to(device))
         # eval_groups' key and whether the third eps plane is drawn (the members of one step agree on it), or None: alone
-        keys.append(_stack_key(m) + (getattr(m, "reg_type", None) == "ml_reg" and c["alpha"] != 0.0,)
+        keys.append(fam[g] if g in fam else
+                    _stack_key(m) + (getattr(m, "reg_type", None) == "ml_reg" and c["alpha"] != 0.0,)
                     if steps_in_ensemble(m, c["vae_type"], loader[0], obs_dim) else None)
         if keys[g] is None:  # at once: before the next member is built
             train(loader, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters, experiment_type,
                   c["vae_type"], train_k, num_estimates, max_epochs, device, c["alpha"], stage, c["p_missingness"], reg_type,
                   beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
     rows = lambda t: t.to(device).reshape(-1, obs_dim)
-    for idx in _group(keys)[0].values():
-        ens = EnsembleTrainer([out[g] for g in idx], lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
+    for key, idx in _group(keys)[0].items():
+        trainer_cls = {"mask": MaskEnsembleTrainer, "eddi": EDDIEnsembleTrainer}.get(key[0], EnsembleTrainer)
+        ens = trainer_cls([out[g] for g in idx], lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
         alphas, pms = [cfgs[g]["alpha"] for g in idx], [cfgs[g]["p_missingness"] for g in idx]
         sources = [data_loader_train[0]] if loaders is None else [loaders[g][0] for g in idx]
         for i in range(max_epochs):

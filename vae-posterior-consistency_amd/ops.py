@@ -272,6 +272,47 @@ def reduce_step_adam_multi(partE, partD, loss_part, blocks, strideE, strideD, st
                                            ptr(img), stream_ptr()), "vpc_reduce_step_adam_multi")
 
 
+# the slots the mask-augmented / point-net ensemble entries read behind the nine above (VPC_MS_PARTF, VPC_MS_SNAP)
+MS_PARTF, MS_SNAP, MS_COUNT_FAMILIES = MS_COUNT, MS_COUNT + 1, MS_COUNT + 2
+
+
+def _family_strides(strides):
+    if len(strides) < MS_COUNT_FAMILIES:
+        raise L.VpcError(f"the point-net ensemble entries read {MS_COUNT_FAMILIES} member strides, got {len(strides)}")
+    return _member_strides(strides)
+
+
+def step_small_multi_aug_f32(x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask, offset_eps,
+                             inv_B, x_logvar, partE, partD, loss_part, strides, B, d, d_real, Ld, order=0):
+    """step_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members: `d` is the row pitch small_aug_pitch(d_real) of x and
+    the masks, the images are those of the mask-augmented layout."""
+    check(lib().vpc_step_small_multi_aug_f32(ptr(x), ptr(mask), ptr(mask_p), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members),
+                                             G, npass, nplanes, int(bool(draw)), int(offset_mask), int(offset_eps), inv_B,
+                                             x_logvar, ptr(partE), ptr(partD), ptr(loss_part), _member_strides(strides), B, d,
+                                             d_real, Ld, int(order), stream_ptr()), "vpc_step_small_multi_aug_f32")
+
+
+def step_small_multi_eddi_f32(x, mask, mask_p, eps, enc_img, dec_img, members, G, npass, nplanes, draw, offset_mask, offset_eps,
+                              inv_B, x_logvar, partE, partD, loss_part, strides, B, d, d_real, Ld, K, front, partF, snap, order=0):
+    """step_small_multi_f32 for G Reg_EDDI / vanilla_EDDI members: images of the point-net layout; front / partF / snap are member
+    0's (step_small_eddi_f32), `strides` has MS_COUNT_FAMILIES slots (MS_PARAM: front, MS_PARTF, MS_SNAP)."""
+    check(lib().vpc_step_small_multi_eddi_f32(ptr(x), ptr(mask), ptr(mask_p), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members),
+                                              G, npass, nplanes, int(bool(draw)), int(offset_mask), int(offset_eps), inv_B,
+                                              x_logvar, ptr(partE), ptr(partD), ptr(loss_part), _family_strides(strides), B, d,
+                                              d_real, Ld, K, ptr(front), ptr(partF), ptr(snap), int(order), stream_ptr()),
+          "vpc_step_small_multi_eddi_f32")
+
+
+def reduce_step_adam_eddi_multi(partE, partD, loss_part, blocks, strideE, strideD, strides, inv_maps, members, G, grad, n, B, d,
+                                out9, accum, params, m, v, beta1, beta2, eps, step, pack_idx, img, partF, snap, K, d_pitch):
+    """reduce_step_adam_eddi of G members in one launch (blockIdx.y = member); n = trunk + decoder parameters of a row."""
+    check(lib().vpc_reduce_step_adam_eddi_multi(ptr(partE), ptr(partD), ptr(loss_part), blocks, strideE, strideD,
+                                                _family_strides(strides), ptr(inv_maps), ptr(members), G, ptr(grad), n, B, d,
+                                                ptr(out9), ptr(accum), ptr(params), ptr(m), ptr(v), beta1, beta2, eps, int(step),
+                                                ptr(pack_idx), ptr(img), ptr(partF), ptr(snap), K, d_pitch, stream_ptr()),
+          "vpc_reduce_step_adam_eddi_multi")
+
+
 def eval_small_multi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, part,
                          strides, d, d_real, Ld, max_blocks=0):
     """The evaluate-stage forward of G members over the tiles of a tile table (include/vpc.h: ensemble evaluation): one record of
