@@ -683,7 +683,28 @@ int vpc_eval_small_multi_f32(const float* x, const uint8_t* mask, const float* e
                              const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
                              unsigned long long offset, float x_logvar, double* part, const long* strides, int d, int d_real,
                              int L, int max_blocks, void* stream);
-/* The records -> out[G][4] = (rmse, elbo, negll, negll_imp), blockIdx.y = member, fp64, fixed summation order.  Per batch of n_b
+/* vpc_eval_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members (model.loss, evaluate stage: src/models/VAE.py:570-580,
+ * :1053-1060; the encoder input [x*mask | mask] of VAE.py:545-548 is built in the kernel's input stage): same arguments, tables,
+ * draw rule, records and chunking.  d is the row pitch 4 ceil(d_real / 4) of x and mask (mask 0 in the padding), d_real the
+ * model's obs_dim, the images are those of the mask-augmented layout (vpc_build_indices with mask_augm = 1), rows VPC_MS_IMG
+ * apart.  2 d_real > 128 or d - d_real > 3: VPC_ERR_SHAPE; otherwise limits and errors as vpc_eval_small_multi_f32. */
+int vpc_eval_small_multi_aug_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                                 const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                                 unsigned long long offset, float x_logvar, double* part, const long* strides, int d, int d_real,
+                                 int L, int max_blocks, void* stream);
+/* ... and for G Reg_EDDI / vanilla_EDDI members (VAE.py:757-767, :935-950 - vanilla_EDDI computes the imputed term in every
+ * stage; the point-net front-end of VAE.py:719-733, :903-917 runs as the kernel's input stage, folded per workgroup as in
+ * vpc_step_small_multi_eddi_f32).  Images of the point-net layout (vpc_build_indices_pointnet); K = emb_dim; `front` is member 0's
+ * front-end parameters (E [d_real][K] | t [d_real] | W [K][2 + K] | c [K]) inside its row [trunk | decoder | front-end] of the
+ * parameter stack, member g's strides[VPC_MS_PARAM] floats further - read in place, no copy.  The eps draw does not depend on the
+ * pitch of x: the entry draws at every d_real.  K < 1, K > 32 or d_real > 64: VPC_ERR_SHAPE; a front that is null or not 4-byte
+ * aligned, or a VPC_MS_PARAM stride below the front-end's size: VPC_ERR_ARG; otherwise as vpc_eval_small_multi_aug_f32. */
+int vpc_eval_small_multi_eddi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                                  const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                                  unsigned long long offset, float x_logvar, double* part, const long* strides, int d, int d_real,
+                                  int L, int K, const float* front, int max_blocks, void* stream);
+/* The records -> out[G][4] = (rmse, elbo, negll, negll_imp), blockIdx.y = member, fp64, fixed summation order (family-independent:
+ * the three forward entries above share it).  Per batch of n_b
  * rows: negll = (S_A + n_b d_real log(2 pi) / 2) / n_b and negll_imp likewise from S_I (masked entries contribute the constant,
  * as _finish / VAE.py:414-419), elbo = negll + co.bq KL / n_b, rmse = sqrt(SQ / CNT) - 0 / 0 = NaN for a batch without an
  * unobserved entry, as evaluate.py:232-234.  Then the mean over the batches of a pass and the mean over the passes

@@ -9,8 +9,8 @@ from ._lib import VpcError, LIB_PATH
 from .models import Reg_VAE, vanilla_VAE, Reg_VAE_mask, vanilla_VAE_mask, MAX_EPOCH
 from .fused import FusedTrainer
 from . import ensemble
-from .ensemble import (EDDIEnsembleTrainer, EnsembleAcquirer, EnsembleEvaluator, EnsembleTrainer, MaskEnsembleTrainer,
-                       stack_models)
+from .ensemble import (EDDIEnsembleEvaluator, EDDIEnsembleTrainer, EnsembleAcquirer, EnsembleEvaluator, EnsembleTrainer,
+                       MaskEnsembleEvaluator, MaskEnsembleTrainer, stack_models)
 from .notmiwae import REG_notMIWAE_v2, notMIWAE_myversion, NMTrainer
 from .harness import (create_missing_uci, create_missing_uci_drop_eddi, model_loader, checkpoint_path, train, train_sweep, eval_vae, eval_sweep, result_paths, eval_vae_mnar,
                       mnar_result_path, eval_miwae, miwae_result_path)
@@ -42,4 +42,5 @@ __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedT
            "flow_reward_matrix", "flow_reward_draws", "R_lindley_chain_ratio_version", "chaini_I_ratio_version",
            "chaini_II_ratio_version", "active_learning_flow", "ais", "ais_chains", "ais_trajectory", "eval_ais",
            "ensemble", "EnsembleTrainer", "stack_models", "train_sweep", "EnsembleEvaluator", "eval_sweep",
-           "EnsembleAcquirer", "active_sweep", "MaskEnsembleTrainer", "EDDIEnsembleTrainer"]
+           "EnsembleAcquirer", "active_sweep", "MaskEnsembleTrainer", "EDDIEnsembleTrainer",
+           "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator"]

@@ -78,6 +78,8 @@ _PROTOS = {
     "vpc_reduce_step_adam_eddi_multi": [P, P, P, I, L_, L_, C.POINTER(L_), P, P, I, P, I, L_, I, P, P, P, P, P, F, F, F, L_, P, P, P,
                                         P, I, I, P],
     "vpc_eval_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],
+    "vpc_eval_small_multi_aug_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P],
+    "vpc_eval_small_multi_eddi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P, I, P],
     "vpc_eval_reduce_multi": [P, P, L_, P, I, P, I, L_, L_, I, P, P],
     "vpc_impute_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, I, P, L_, C.POINTER(L_), I, I, I, I, P],
     "vpc_target_mse_multi": [P, L_, L_, I, P, L_, P],

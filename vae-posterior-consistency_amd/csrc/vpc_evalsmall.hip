@@ -12,6 +12,9 @@
 // activation buffers (X, H1, H2, ML, Z, G1, G2) of 9 216 bytes: two workgroups per CU.  A tile lies inside ONE batch (the
 // per-batch quantities are non-linear); the host's tile table says where its rows are.  Five sums per tile, one record of doubles
 // per (member, tile), no atomics.
+// eval_small_aug_kernel / eval_small_eddi_kernel: the same body for Reg_VAE_mask / vanilla_VAE_mask members (VAE.py:570-580,
+// :1053-1060: input [x*mask | mask]) and for Reg_EDDI / vanilla_EDDI members (VAE.py:757-767, :935-950: the point-net front-end,
+// folded per workgroup in the buffers that are idle until the first encoder stage); same LDS, same records, same reduce launch.
 // eval_reduce_multi_kernel: blockIdx.y = member; tiles -> batches -> passes -> out[g][4] in fp64, in a fixed order.
 // impute_small_kernel: the same forward (ONE body text, vpc_evalsmall_body.h) keeping x_hat instead of the sums - the M Monte-Carlo
 // forwards of active_learning_func (evaluate.py:380-414) for G members: x_hat per draw row, or the target column's squared error;
@@ -47,8 +50,46 @@ struct EvalArgs {
 
 // What becomes of x_hat: OUT_SUMS the five sums of the tile's record, OUT_XHAT / OUT_SQERR what impute_small_kernel writes.
 enum { OUT_SUMS = 0, OUT_XHAT, OUT_SQERR };
+// The point-net kernel's own arguments (an empty record elsewhere): the front-end is read from the members' rows of the parameter
+// stack [trunk | decoder | front-end], no copy.
+struct EvalPointNet {
+    int K;               // emb_dim
+    const float* front;  // member 0's front-end parameters (E [d_real][K] | t [d_real] | W [K][2+K] | c [K])
+    long sP;             // member stride of `front` in floats
+};
+struct EvalPnArgs : EvalArgs { EvalPointNet pn; };
+
 template <int DT>
 __global__ __launch_bounds__(THREADS) void eval_small_kernel(EvalArgs a) {
+    constexpr int DTI = DT;
+    constexpr bool AUG = false;
+    constexpr bool PN = false;
+    constexpr EvalPointNet pnx{};
+    constexpr int OUT = OUT_SUMS;
+    float* const out = nullptr;
+    const long sout = 0;
+#include "vpc_evalsmall_body.h"
+}
+// Reg_VAE_mask / vanilla_VAE_mask members (src/models/VAE.py:570-580, 1053-1060): encoder input [x*mask | mask] of DTI =
+// dt_for(2 d_real) tiles built in the input stage, decoder output of DT = dt_for(d_real) tiles; a.d is the row pitch.
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void eval_small_aug_kernel(EvalArgs a) {
+    constexpr bool AUG = true;
+    constexpr bool PN = false;
+    constexpr EvalPointNet pnx{};
+    constexpr int OUT = OUT_SUMS;
+    float* const out = nullptr;
+    const long sout = 0;
+#include "vpc_evalsmall_body.h"
+}
+// Reg_EDDI / vanilla_EDDI members (VAE.py:757-767, 935-950): the point-net front-end as the input stage, the trunk as the body's
+// encoder with DTI = dt_for(K) input tiles, decoder output of DT = dt_for(d_real) tiles.
+template <int DTI, int DT>
+__global__ __launch_bounds__(THREADS) void eval_small_eddi_kernel(EvalPnArgs pa) {
+    constexpr bool AUG = false;
+    constexpr bool PN = true;
+    const EvalArgs& a = pa;
+    const EvalPointNet& pnx = pa.pn;
     constexpr int OUT = OUT_SUMS;
     float* const out = nullptr;
     const long sout = 0;
@@ -66,6 +107,10 @@ struct ImputeArgs {
 };
 template <int DT, int MODE>
 __global__ __launch_bounds__(THREADS) void impute_small_kernel(ImputeArgs ia) {
+    constexpr int DTI = DT;  // (plain members only)
+    constexpr bool AUG = false;
+    constexpr bool PN = false;
+    constexpr EvalPointNet pnx{};
     constexpr int OUT = MODE == 0 ? OUT_XHAT : OUT_SQERR;
     const EvalArgs& a = ia.e;
     float* const out = ia.out;
@@ -222,6 +267,80 @@ extern "C" int vpc_eval_small_multi_f32(const float* x, const uint8_t* mask, con
         return true;                                                                                       \
     }
         switch (dt_for(d)) { VPC_CASE(1) VPC_CASE(2) VPC_CASE(4) VPC_CASE(8) }
+#undef VPC_CASE
+        return false;
+    });
+}
+
+// The evaluate-stage forward of G Reg_VAE_mask / vanilla_VAE_mask members: d is the row pitch 4 ceil(d_real / 4) of x and the mask,
+// the images are those of the mask-augmented layout.
+extern "C" int vpc_eval_small_multi_aug_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                            const float* dec_img, const VpcMember* members, int G, const long long* tiles,
+                                            long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
+                                            double* part, const long* strides, int d, int d_real, int L, int max_blocks,
+                                            void* stream) {
+    // (the shape limits of vpc_step_small_multi_aug_f32)
+    if (d_real < 1 || d_real > d || d - d_real > 3 || 2 * d_real > MAX_D) return VPC_ERR_SHAPE;
+    if (!part || (uintptr_t)part % 8) return VPC_ERR_ARG;
+    EvalArgs a;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, a);
+    if (rc != VPC_OK) return rc;
+    if (strides[VPC_MS_LOSS] < n_tiles * EVAL_TERMS) return VPC_ERR_ARG;
+    a.part = part;
+    a.spart = strides[VPC_MS_LOSS];
+    hipStream_t s = (hipStream_t)stream;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
+        a.tile0 = t0;
+#define VPC_CASE(TI, T)                                                                                    \
+    case TI: {                                                                                             \
+        auto kern = eval_small_aug_kernel<TI, T>;                                                          \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), EVAL_LDS)) return false;                   \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), EVAL_LDS, s, a);                                     \
+        return true;                                                                                       \
+    }
+        // (input tiles, output tiles) = (dt_for(2 d_real), dt_for(d_real)): d_real <= 8, 16, 32, 64
+        switch (dt_for(2 * d_real)) { VPC_CASE(1, 1) VPC_CASE(2, 1) VPC_CASE(4, 2) VPC_CASE(8, 4) }
+#undef VPC_CASE
+        return false;
+    });
+}
+
+// ... and of G Reg_EDDI / vanilla_EDDI members: images of the point-net layout; `front` is member 0's front-end parameters, member
+// g's lie strides[VPC_MS_PARAM] floats further (inside the member's row of the parameter stack, behind trunk and decoder).
+extern "C" int vpc_eval_small_multi_eddi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                             const float* dec_img, const VpcMember* members, int G, const long long* tiles,
+                                             long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
+                                             double* part, const long* strides, int d, int d_real, int L, int K,
+                                             const float* front, int max_blocks, void* stream) {
+    // (the shape limits of vpc_step_small_multi_eddi_f32, and its pointer checks)
+    if (d_real < 1 || d_real > 64 || d_real > d || d - d_real > 3 || d > 64 || K < 1 || K > 32) return VPC_ERR_SHAPE;
+    if (!front || (uintptr_t)front % 4) return VPC_ERR_ARG;
+    if (!part || (uintptr_t)part % 8) return VPC_ERR_ARG;
+    EvalPnArgs a;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, a);
+    if (rc != VPC_OK) return rc;
+    if (strides[VPC_MS_LOSS] < n_tiles * EVAL_TERMS) return VPC_ERR_ARG;
+    const long nfront = (long)d_real * K + d_real + (long)K * (2 + K) + K;
+    if (strides[VPC_MS_PARAM] < nfront) return VPC_ERR_ARG;  // (read only, but every member has its own row)
+    a.part = part;
+    a.spart = strides[VPC_MS_LOSS];
+    a.pn = EvalPointNet{K, front, strides[VPC_MS_PARAM]};
+    hipStream_t s = (hipStream_t)stream;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
+        a.tile0 = t0;
+#define VPC_CASE(TI, T)                                                                                    \
+    case 4 * TI + T: {                                                                                     \
+        auto kern = eval_small_eddi_kernel<TI, T>;                                                         \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), EVAL_LDS)) return false;                   \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), EVAL_LDS, s, a);                                     \
+        return true;                                                                                       \
+    }
+        // (input tiles, output tiles) = (dt_for(K), dt_for(d_real)): K <= 16, 32; d_real <= 16, 32, 64
+        switch (4 * dt_for(K) + dt_for(d_real)) {
+            VPC_CASE(1, 1) VPC_CASE(1, 2) VPC_CASE(1, 4) VPC_CASE(2, 1) VPC_CASE(2, 2) VPC_CASE(2, 4)
+        }
 #undef VPC_CASE
         return false;
     });

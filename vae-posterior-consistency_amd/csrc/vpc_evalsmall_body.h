@@ -1,15 +1,23 @@
 // The evaluate-stage forward of ONE (member, 16-row tile): the BODY of the kernels of vpc_evalsmall.hip, included as text into
-//   eval_small_kernel<DT>            (OUT = OUT_SUMS: the five sums of the tile's record) and
+//   eval_small_kernel<DT>            (OUT = OUT_SUMS: the five sums of the tile's record),
+//   eval_small_aug_kernel<DTI, DT>   (the same for Reg_VAE_mask / vanilla_VAE_mask members: AUG),
+//   eval_small_eddi_kernel<DTI, DT>  (the same for Reg_EDDI / vanilla_EDDI members: PN) and
 //   impute_small_kernel<DT, MODE>    (OUT = OUT_XHAT / OUT_SQERR: x_hat, or the target column's squared error, per draw row),
 // so that the arithmetic up to x_hat is ONE piece of code and eval_small_kernel compiles to the instructions it had as a
 // self-contained kernel (vpc_small_body.h says why this is not a shared inline function).
-// In scope at the point of inclusion: template parameter DT, `constexpr int OUT`, `a` (EvalArgs), and for OUT != OUT_SUMS `out` /
-// `sout` (member 0's output and the member stride in floats).  (No include guard: a code fragment, included once per kernel.)
+// In scope at the point of inclusion: the compile-time tile counts DT (tiles of d: x / mask words, W6, the output tiles) and DTI
+// (tiles of the encoder INPUT: W1's k-tiles, the X buffer) and the flags AUG and PN - the parameters of the training twin
+// vpc_small_body.h -, `constexpr int OUT`, `a` (EvalArgs), `pnx` (an EvalPointNet: the point-net kernel's own arguments, an empty
+// record elsewhere), and for OUT != OUT_SUMS `out` / `sout` (member 0's output and the member stride in floats).  Plain members:
+// DTI == DT, AUG and PN false.  AUG (src/models/VAE.py:545-548, 1031-1033): the encoder input is [x*mask | mask] of width
+// 2 a.d_real; PN (VAE.py:719-733, 903-917): it is the point-net aggregate [16][pnx.K] of the folded front-end (DTI = dt_for(K)).
+// Under both a.d is the row pitch of x and the mask, a.d_real obs_dim.  (No include guard: a code fragment, included once per
+// kernel.)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     auto buf = [&](int b) { return lds + b * SBUF; };
     float* red = lds + E_COUNT * SBUF;
-    constexpr int S1 = s_for_tiles(DT);
-    const EncImg ei(DT);
+    constexpr int S1 = s_for_tiles(DTI);
+    const EncImg ei(DTI);
     const DecImg di(DT);
     const unsigned mem = blockIdx.y;
     const long tile_id = a.tile0 + blockIdx.x;
@@ -54,23 +62,93 @@
     }
     int cc = c, qq = q;
     launder(cc, qq);
+    if constexpr (PN) {
+        // ================================================================ point-net front-end as the input stage (the folded form
+        // of vpc_small_body.h; VAE.py:719-733, 903-917).  The workspace lies in E_H1 .. E_G2 (6 x SBUF = 13 824 floats, contiguous),
+        // idle until the first encoder stage:
+        //   PT  [a.d][64]   folded table: PT[64 j + k] = A_j[k], PT[64 j + 32 + k] = C_j[k], zero for k >= K and j >= d_real
+        //   PPR [n_front]   member g's front-end parameters in flat order (E [d_real][K] | t [d_real] | W [K][2+K] | c [K]), read
+        //                   from its row of the parameter stack
+        //   PXS, PMQ [16][a.d]   the tile's x and mask rows as floats; rows past the valid ones and columns past d_real are 0
+        // 4 096 + 3 328 + 1 024 + 1 024 = 9 472 floats at the limits d = 64, K = 32.
+        float* const PT = buf(E_H1);
+        float* const PPR = PT + 4096;
+        float* const PXS = PPR + 3328;
+        float* const PMQ = PXS + 1024;
+        const int K = pnx.K, dr = a.d_real, dp = a.d;
+        const int nfront = dr * K + dr + K * (2 + K) + K;
+        const float* front = pnx.front + mem * pnx.sP;
+        const int tid = threadIdx.x;
+        for (int i = tid; i < nfront; i += THREADS) PPR[i] = front[i];
+        for (int i = tid; i < 16 * dp; i += THREADS) {
+            const int r = i / dp, j = i - r * dp;
+            const bool in = r < nv && j < dr;
+            const long g = (xrow0 + r) * dp + j;
+            PXS[i] = in ? xg[g] : 0.f;
+            PMQ[i] = (in && mg[g]) ? 1.f : 0.f;
+        }
+        __syncthreads();
+        // the fold of eddi_fold_kernel: A_j = w_x + W_E E_j, C_j = w_t t_j + c  (W = [w_x | W_E | w_t], VAE.py:719-727)
+        const float *pE = PPR, *ptb = pE + dr * K, *pW = ptb + dr, *pc = pW + K * (2 + K);
+        for (int i = tid; i < 32 * dp; i += THREADS) {
+            const int k = i & 31, j = i >> 5;
+            float A = 0.f, C = 0.f;
+            if (k < K && j < dr) {
+                const float* wr = pW + k * (2 + K);
+                A = wr[0];
+#pragma unroll 4
+                for (int e = 0; e < K; ++e) A += wr[1 + e] * pE[j * K + e];
+                C = wr[1 + K] * ptb[j] + pc[k];
+            }
+            PT[64 * j + k] = A;
+            PT[64 * j + 32 + k] = C;
+        }
+        __syncthreads();
+        // thread (row r, k) sums m[r][j] relu(x[r][j] A_j[k] + C_j[k]) over the features in a fixed order; columns K .. 16 DTI - 1
+        // are written as 0
+        const int r = tid >> 5, k = tid & 31;
+        float sq = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < dr; ++j) sq += PMQ[r * dp + j] * fmaxf(PXS[r * dp + j] * PT[64 * j + k] + PT[64 * j + 32 + k], 0.f);
+        if (k < 16 * DTI) buf(E_X)[r * SP + k] = k < K ? sq : 0.f;
+        // (the first encoder stage reads E_X and writes E_H1 behind its barrier: every read of the workspace is done by then)
+    }
     // ================================================================ encoder forward (phase E of the tile body, pass 0)
     {
         weights();
-        f32x4 fW1[DT], fW2[H1T], fW3[H2T], bias1 = zero4();
+        f32x4 fW1[DTI], fW2[H1T], fW3[H2T], bias1 = zero4();
         if (w < H1T) {
-            ldW<DT, S1>(W1, w, cc, qq, fW1);
+            ldW<DTI, S1>(W1, w, cc, qq, fW1);
             bias1 = *reinterpret_cast<const f32x4*>(b1 + 16 * w + 4 * qq);
         }
-        if (w < DT) st_act(buf(E_X), w, cc, qq, xv * mask_to_f32(mw));  // x.float() * mask  (VAE.py:388)
+        if constexpr (PN) {
+            // (E_X holds the aggregate already: the input stage above)
+        } else if constexpr (!AUG) {
+            if (w < DT) st_act(buf(E_X), w, cc, qq, xv * mask_to_f32(mw));  // x.float() * mask  (VAE.py:388)
+        } else {
+            // [x*mask | mask | 0] exactly as the step body writes it (VAE.py:545-548): element f < d is x_f m_f, d <= f < 2 d is
+            // m_{f-d}, 2 d <= f < 16 DTI is 0.  Column d is in general not 4-aligned, so every element is a dword store of its
+            // own; each column of the buffer has exactly one writer.  Rows past the valid ones: xv and the mask word are 0.
+            const f32x4 mk = mask_to_f32(mw), xm = xv * mk;
+            float* xrow = buf(E_X) + cc * SP;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int f = 16 * w + 4 * qq + j;
+                if (w < DT && f < a.d_real) {
+                    xrow[f] = xm[j];
+                    xrow[a.d_real + f] = mk[j];
+                }
+                if (w < DTI && f >= 2 * a.d_real) xrow[f] = 0.f;
+            }
+        }
         if (w < H2T) ldW<H1T, 128>(W2, w, cc, qq, fW2);
         lds_barrier();
         launder(cc, qq);
         if (w < H1T) {
-            f32x4 in[DT];
+            f32x4 in[DTI];
 #pragma unroll
-            for (int t = 0; t < DT; ++t) in[t] = ld_act(buf(E_X), t, cc, qq);
-            st_act(buf(E_H1), w, cc, qq, relu4(mmW<DT>(fW1, in, bias1)));
+            for (int t = 0; t < DTI; ++t) in[t] = ld_act(buf(E_X), t, cc, qq);
+            st_act(buf(E_H1), w, cc, qq, relu4(mmW<DTI>(fW1, in, bias1)));
         }
         if (w < 2) ldW<H2T, 64>(W3, w, cc, qq, fW3);
         lds_barrier();

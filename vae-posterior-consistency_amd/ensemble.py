@@ -23,6 +23,11 @@ computes on its data: same tile body, same summation order, same Philox counters
 The sweep's evaluation (eval_vae, evaluate.py:136-297) and its active variable selection (active_learning_func,
 evaluate.py:300-511) share their launches the same way: EnsembleEvaluator over build_eval_tables, EnsembleAcquirer over
 acquire_plan / acquire_draw_offsets (the shapes and Philox offsets of a run, on the host alone).
+
+    MaskEnsembleEvaluator        EnsembleEvaluator for G Reg_VAE_mask / vanilla_VAE_mask members (vpc_eval_small_multi_aug_f32)
+    EDDIEnsembleEvaluator        ... and for G Reg_EDDI / vanilla_EDDI members (vpc_eval_small_multi_eddi_f32: the front-end is read
+                                 from the parameter stack); both share vpc_eval_reduce_multi, and X.for_trainer(trainer) reads the
+                                 image stack a family trainer's tail re-packs.  Acquisition stays with the plain members.
 """
 from __future__ import annotations
 
@@ -465,8 +470,35 @@ class EnsembleTrainer(_MemberSet):
 
 class _FamilyTrainer(EnsembleTrainer):
     def evaluator(self):
-        raise L.VpcError("ensemble evaluation and acquisition cover the plain Reg_VAE / vanilla_VAE members only: evaluate "
-                         "mask-augmented and point-net members one by one (harness.eval_vae, eval_sweep does)")
+        raise L.VpcError("EnsembleEvaluator and EnsembleAcquirer cover the plain Reg_VAE / vanilla_VAE members only: evaluate "
+                         "mask-augmented and point-net members with MaskEnsembleEvaluator.for_trainer(trainer) / "
+                         "EDDIEnsembleEvaluator.for_trainer(trainer); their acquisition runs one by one (harness.active_sweep)")
+
+
+class _PointNetImages:
+    """The images a point-net member set hands to its launches: those of L.pointnet_layout (trunk and decoder of a row
+    [trunk | decoder | front-end]), kept by the set as PackedImage rows of ONE stack under the parameter-key freshness rule of
+    images.py.  The models' own images (model._lay()'s) stay theirs.  images_from: another set of the same members whose stack and
+    PackedImage rows this one shares (an evaluator on a trainer's members reads what the trainer's tail re-packs and stamps)."""
+    _images_from = None
+
+    def _image_stack_and_table(self, new_image_stack):
+        lay, n, src = self.lay, self.lay.n_params, self._images_from
+        if src is not None:
+            self.img, self._images_pn = src.img, src._images_pn
+        else:
+            self.img = torch.from_numpy(lay.img_template).to(self.dev).repeat(self.G, 1)
+            pidx = lay.device_tables(self.dev)[0]
+            self._images_pn = [PackedImage(self.img[g], lambda flat, buf: ops.pack_weights(flat[:n], pidx, buf))
+                               for g in range(self.G)]
+        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self._table_version = -1
+
+    def _member_image(self, g):
+        return self._images_pn[g]
+
+    def _repack(self, g, key):
+        self._images_pn[g].get(key, self.models[g]._flat)
 
 
 class MaskEnsembleTrainer(_FamilyTrainer):
@@ -484,7 +516,7 @@ class MaskEnsembleTrainer(_FamilyTrainer):
                                      strides, B, self.dk, lay.d, lay.L, self.order)
 
 
-class EDDIEnsembleTrainer(_FamilyTrainer):
+class EDDIEnsembleTrainer(_PointNetImages, _FamilyTrainer):
     """EnsembleTrainer for G Reg_EDDI or G vanilla_EDDI of one (obs_dim, emb_dim, latent_dim, reg_type).  A row of the
     parameter stack is [trunk | decoder | front-end] as under EDDITrainer; the image stack holds the point-net layout's
     images of trunk and decoder (the one EDDITrainer's small-batch step packs, not model._lay()'s: the models' own images
@@ -493,21 +525,6 @@ class EDDIEnsembleTrainer(_FamilyTrainer):
     step's draws injected - all of them, at every obs_dim <= 64 - and refuses to draw: the stand-alone stream is pinned to the
     unpadded pitch, and one draw launch per member would undo the point of the ensemble."""
     family = EDDI
-
-    def _image_stack_and_table(self, new_image_stack):
-        lay, n = self.lay, self.lay.n_params
-        self.img = torch.from_numpy(lay.img_template).to(self.dev).repeat(self.G, 1)
-        pidx = lay.device_tables(self.dev)[0]
-        self._images_pn = [PackedImage(self.img[g], lambda flat, buf: ops.pack_weights(flat[:n], pidx, buf))
-                           for g in range(self.G)]
-        self.table_dev = torch.zeros(self.G * MEMBER_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
-        self._table_version = -1
-
-    def _member_image(self, g):
-        return self._images_pn[g]
-
-    def _repack(self, g, key):
-        self._images_pn[g].get(key, self.models[g]._flat)
 
     def _family_workspaces(self, tiles):
         K, n_front = self.lay.K, self.lay.n_front
@@ -611,11 +628,12 @@ class EnsembleEvaluator(_MemberSet):
     vpc_eval_small_multi_f32 (forward of every member x pass x batch x 16-row tile -> five sums per tile) and
     vpc_eval_reduce_multi (tiles -> batches -> passes -> [G, 4]).  Only the q pass is computed: VAE.py:410-420 reads nothing else."""
     TABLE_CACHE = 8  # distinct (N, batch layout, M) kept on the device
+    family = PLAIN  # (MaskEnsembleEvaluator and EDDIEnsembleEvaluator below: the same frame around their families' forward launch)
 
     def __init__(self, models, seeds=None, world_size=1):
         """models: as EnsembleTrainer (validate_members), on the GPU.  seeds: one Philox seed per member (None: member g draws
         with seed g).  The evaluator owns a Philox offset: a call advances it by the groups it consumed (eval_draw_counters)."""
-        super().__init__(models, 0.0, seeds, world_size)
+        super().__init__(models, 0.0, seeds, world_size, self.family)
         self._image_stack_and_table(new_image_stack=False)
         self._tables, self._part = {}, None
         self.launches = 0  # kernel launches of the last call (the forward entry walks the tile table in chunks)
@@ -637,6 +655,17 @@ class EnsembleEvaluator(_MemberSet):
             self.img = install_image_stack(self.models, self.lay, self.dev)
         self._fresh_images()
         return image_stack_of(self.models, self.n_img, self.dev)
+
+    def _family_strides(self):
+        """Member strides a family's forward launch reads besides -> {stride slot: member stride}."""
+        return {}
+
+    def _launch_forward(self, x, mask, eps_plane, img0, tiles_dev, T, N, R, draw, offset, strides, max_blocks):
+        """THE forward launch of evaluate(): what a family's evaluator overrides."""
+        lay = self.lay
+        ops.eval_small_multi_f32(x, mask, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, self.G, tiles_dev, T,
+                                 N, R, draw, offset, self.models[0]._x_logvar_value, self._part, strides, self.dk, lay.d, lay.L,
+                                 max_blocks)
 
     def evaluate(self, x, mask, batch_size=None, M=1, *, batches=None, epoch, beta=1.0, beta_annealing=False, eps=None,
                  max_blocks=0):
@@ -663,10 +692,8 @@ class EnsembleEvaluator(_MemberSet):
             self._part = torch.empty(G, T * 5, dtype=torch.float64, device=self.dev)
         out = torch.empty(G, 4, device=self.dev)
         strides = stride_vector(ops.MS_COUNT, {ops.MS_X: sx, ops.MS_MASK: smask, ops.MS_EPS: seps, ops.MS_IMG: simg,
-                                               ops.MS_PART: self._part.stride(0)})
-        ops.eval_small_multi_f32(x, mask, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, G, tiles_dev, T, N,
-                                 R, eps is None, offset, self.models[0]._x_logvar_value, self._part, strides, dk, d, Ld,
-                                 max_blocks)
+                                               ops.MS_PART: self._part.stride(0), **self._family_strides()})
+        self._launch_forward(x, mask, eps_plane, img0, tiles_dev, T, N, R, eps is None, offset, strides, max_blocks)
         ops.eval_reduce_multi(self._part, batches_dev, tb.batches.shape[0], passes_dev, M, self.table_dev, G,
                               self._part.stride(0), T, d, out)
         self.launches = forward_launches(T, G, max_blocks) + 1
@@ -685,6 +712,66 @@ class EnsembleEvaluator(_MemberSet):
         if eps.dim() == 3:
             return [(0, buf[c]) for c in range(calls)], 0
         return [(0, buf[0, c]) for c in range(calls)], buf.stride(0)  # (the stride of the copy: eps may be an expanded view)
+
+
+class _FamilyEvaluator(EnsembleEvaluator):
+    """EnsembleEvaluator for a member family of the ensemble step other than the plain one: evaluate(), tables(), `launches` and
+    the Philox offset as there; a subclass says which forward launch runs and what its images are."""
+
+    def __init__(self, models, seeds=None, world_size=1, *, images_from=None):
+        """models, seeds: as EnsembleEvaluator, members of this class's family.  images_from: a family trainer on the same
+        members (for_trainer) whose image rows are read; the mask-augmented evaluator needs no more than that the trainer exists:
+        its members' own images ARE the trainer's rows, and it adopts them as the plain evaluator does."""
+        self._images_from = images_from
+        super().__init__(models, seeds, world_size)
+
+    @classmethod
+    def for_trainer(cls, trainer):
+        """An evaluator on a family trainer's members, with their seeds, that reads the image stack the trainer's tail re-packs:
+        an evaluation between steps sees the current weights without a re-pack."""
+        if getattr(trainer, "family", None) is not cls.family:
+            raise TypeError(f"{cls.__name__}.for_trainer takes the trainer of its own family, got {type(trainer).__name__}")
+        return cls(trainer.models, seeds=trainer.table.rows["seed"].tolist(), images_from=trainer)
+
+
+class MaskEnsembleEvaluator(_FamilyEvaluator):
+    """EnsembleEvaluator for G Reg_VAE_mask or G vanilla_VAE_mask of one (obs_dim, latent_dim, reg_type): the evaluate stage of
+    VAE.py:570-580 / :1053-1060 through vpc_eval_small_multi_aug_f32 + vpc_eval_reduce_multi.  The images are the models' own
+    (mask-augmented layout), adopted or installed as a stack exactly as the plain evaluator does - MaskEnsembleTrainer re-packs
+    these very rows -; rows of x and mask go at ops.small_aug_pitch(obs_dim) columns."""
+    family = MASK
+
+    def _launch_forward(self, x, mask, eps_plane, img0, tiles_dev, T, N, R, draw, offset, strides, max_blocks):
+        lay = self.lay
+        ops.eval_small_multi_aug_f32(x, mask, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, self.G,
+                                     tiles_dev, T, N, R, draw, offset, self.models[0]._x_logvar_value, self._part, strides,
+                                     self.dk, lay.d, lay.L, max_blocks)
+
+
+class EDDIEnsembleEvaluator(_PointNetImages, _FamilyEvaluator):
+    """EnsembleEvaluator for G Reg_EDDI or G vanilla_EDDI of one (obs_dim, emb_dim, latent_dim, reg_type): the evaluate stage of
+    VAE.py:757-767 / :935-950 through vpc_eval_small_multi_eddi_f32 + vpc_eval_reduce_multi.  The images are those of the
+    point-net layout, the evaluator's own PackedImage rows (or the trainer's: for_trainer); the front-end is read from the members'
+    rows of the parameter stack, so every member has to sit in its row still.  The eps draw does not depend on the pitch of x:
+    unlike EDDIEnsembleTrainer.step, evaluate() draws on the device at every obs_dim."""
+    family = EDDI
+
+    def __init__(self, models, seeds=None, world_size=1, *, images_from=None):
+        super().__init__(models, seeds, world_size, images_from=images_from)
+        self._row_ptr = [self.params[g].data_ptr() for g in range(self.G)]
+
+    def _images(self):
+        self._fresh_images(self._row_ptr)  # (raises for a member that left its row: the front-end is read from the stack)
+        return self.img[0], self.img.stride(0)
+
+    def _family_strides(self):
+        return {ops.MS_PARAM: self.params.stride(0)}
+
+    def _launch_forward(self, x, mask, eps_plane, img0, tiles_dev, T, N, R, draw, offset, strides, max_blocks):
+        lay = self.lay
+        ops.eval_small_multi_eddi_f32(x, mask, eps_plane, img0[:lay.enc_img], img0[lay.enc_img:], self.table_dev, self.G,
+                                      tiles_dev, T, N, R, draw, offset, self.models[0]._x_logvar_value, self._part, strides,
+                                      self.dk, lay.d, lay.L, lay.K, self.params[0, lay.n_params:], max_blocks)
 
 
 # ------------------------------------------------------------------------------------------------ acquisition

@@ -7,8 +7,9 @@
   train_sweep          src/experiment_main/imputation.py:21-39  the drivers' loops over alpha / p_missingness / split around
                                                              train(), as ensembles stepped by one pair of launches (ensemble.py)
   eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL
-  eval_sweep           src/experiment_main/imputation.py:51-59  eval_vae() of a list of runs, stackable members in one pair of
-                                                             launches per loader (ensemble.EnsembleEvaluator)
+  eval_sweep           src/experiment_main/imputation.py:51-59  eval_vae() of a list of runs, the plain, mask-augmented and
+                                                             point-net members in one pair of launches per group and loader
+                                                             (ensemble.EnsembleEvaluator and its two family subclasses)
   eval_vae_mnar        src/experiment_main/evaluate.py:13-69   importance-weighted imputation RMSE (MNAR path)
   eval_miwae           src/experiment_main/evaluate.py:72-133   importance-weighted imputation RMSE (MIWAE path)
 
@@ -33,8 +34,8 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .ensemble import (EDDIEnsembleTrainer, EnsembleEvaluator, EnsembleTrainer, MaskEnsembleTrainer, stackable, steps_in_ensemble,
-                       sweep_family)
+from .ensemble import (EDDI, MASK, EDDIEnsembleEvaluator, EDDIEnsembleTrainer, EnsembleEvaluator, EnsembleTrainer,
+                       MaskEnsembleEvaluator, MaskEnsembleTrainer, stackable, steps_in_ensemble, sweep_family)
 from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
@@ -201,6 +202,27 @@ def eval_groups(models):
     """How eval_sweep splits its members: ({(class, reg_type): [member indices]}, [indices evaluated one by one]).  Stackable
     members (ensemble.stackable) of one class and reg_type share an EnsembleEvaluator; every other family goes alone."""
     return _group([_stack_key(m) for m in models])
+
+
+def family_eval_groups(models, cfgs=None):
+    """How eval_sweep splits the members eval_groups leaves alone: ({key: [member indices]}, [indices of no family]).
+    Mask-augmented members group by ("mask", class, obs_dim, latent_dim, reg_type), point-net members by ("eddi", class, obs_dim,
+    emb_dim, latent_dim, reg_type) - what the members of one MaskEnsembleEvaluator / EDDIEnsembleEvaluator share; membership
+    follows Family.require, as in training.  cfgs (the members' configs) is not consulted: a 'with_drop' run's evaluation does
+    not differ from any other, so unlike sweep_family nothing excludes it.  eval_sweep evaluates a group of two or more
+    together and a group of one through eval_vae."""
+    def key(m):
+        for name, family in (("mask", MASK), ("eddi", EDDI)):
+            try:
+                family.require(m)
+            except (TypeError, L.VpcError):
+                continue
+            return (name, type(m)) + tuple(family.shared(m))
+        return None
+
+    single = eval_groups(models)[1]
+    groups, rest = _group([key(models[g]) for g in single])
+    return {k: [single[i] for i in idx] for k, idx in groups.items()}, [single[i] for i in rest]
 
 
 class _LoadersDiffer(L.VpcError):
@@ -461,9 +483,12 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
     member.  models (optional): one model per member, else each member's checkpoint through model_loader('test', ...).
     Plain Reg_VAE / vanilla_VAE members of one class and reg_type are evaluated together: per (loader, loader_stage) the
     loader is iterated once per MC pass (a shuffling loader gives every pass its own partition into batches), the batches
-    are gathered on the device and ONE ensemble.EnsembleEvaluator.evaluate call computes every member x pass x batch.  Every
-    other family (mask-augmented, wide, EDDI, MNAR, MIWAE, flow), and per-member loaders whose batch sizes differ, go
-    through eval_vae one by one.  Returns, per member in the order of configs, what eval_vae returns, and (save=True) writes
+    are gathered on the device and ONE ensemble.EnsembleEvaluator.evaluate call computes every member x pass x batch.  Two or
+    more Reg_VAE_mask / vanilla_VAE_mask members of one class, shape and reg_type, and two or more Reg_EDDI / vanilla_EDDI members
+    of one class, shape, emb_dim and reg_type (family_eval_groups), are evaluated the same way through MaskEnsembleEvaluator /
+    EDDIEnsembleEvaluator.  Who goes through eval_vae one by one: a mask-augmented or point-net member with no second of its kind
+    or past its family's kernels (2 obs_dim > 128; obs_dim > 64 or emb_dim > 32), every other family (wide, mnist EDDI, MNAR,
+    MIWAE, flow), and the members of a group whose per-member loaders differ in their batch sizes.  Returns, per member in the order of configs, what eval_vae returns, and (save=True) writes
     the reference's four files under result_paths(...) with that member's alpha / p_missingness.
     What differs from eval_vae for the members evaluated together: no p pass and no mask_p draw (VAE.py:410-420 never reads
     them, and under Philox there is no stream position to preserve); eps comes from the member's Philox stream (seed =
@@ -481,19 +506,17 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
                           experiment_type, c["vae_type"], max_epochs, valid_k, num_estimates, device, c["alpha"], stage,
                           c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, model=ms[g], save=save)
 
-    groups, single = eval_groups(ms)
-    for g in single:
-        alone(g)
-    for idx in groups.values():
+    def together(idx, evaluator_class):
+        """THE evaluation of a group: the passes gathered per loader stage, one evaluate call per stage, the results written."""
         stages = [s for _, s in member_loaders(idx[0])]
         gathered = [_gather_passes([list_loaders[li][0]] if loaders is None else [loaders[g][li][0] for g in idx], M, obs_dim,
                                    device) for li in range(len(stages))]
         if any(t is None for t in gathered) or any([s for _, s in member_loaders(g)] != stages for g in idx):
             for g in idx:
                 alone(g)
-            continue
+            return
         with torch.no_grad():
-            ev = EnsembleEvaluator([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
+            ev = evaluator_class([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
             for g in idx:
                 out[g] = {}
             for loader_stage, (x, mk, ranges) in zip(stages, gathered):
@@ -504,6 +527,17 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
                     if save:
                         _save_results(res, result_paths(experiment_type, data_type, cfgs[g]["vae_type"], loader_stage,
                                                         missing_rate, cfgs[g]["alpha"], cfgs[g]["p_missingness"], reg_type))
+
+    groups, single = eval_groups(ms)
+    family = {k: idx for k, idx in family_eval_groups(ms, cfgs)[0].items() if len(idx) >= 2}
+    grouped = {g for idx in family.values() for g in idx}
+    for g in single:
+        if g not in grouped:
+            alone(g)
+    for idx in groups.values():
+        together(idx, EnsembleEvaluator)
+    for key, idx in family.items():
+        together(idx, MaskEnsembleEvaluator if key[0] == "mask" else EDDIEnsembleEvaluator)
     return out
 
 

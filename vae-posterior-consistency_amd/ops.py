@@ -323,6 +323,26 @@ def eval_small_multi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_ti
           "vpc_eval_small_multi_f32")
 
 
+def eval_small_multi_aug_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, part,
+                             strides, d, d_real, Ld, max_blocks=0):
+    """eval_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members: `d` is the row pitch small_aug_pitch(d_real) of x and
+    the mask, the images are those of the mask-augmented layout."""
+    check(lib().vpc_eval_small_multi_aug_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G, ptr(tiles),
+                                             int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar, ptr(part),
+                                             _member_strides(strides), d, d_real, Ld, int(max_blocks), stream_ptr()),
+          "vpc_eval_small_multi_aug_f32")
+
+
+def eval_small_multi_eddi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, part,
+                              strides, d, d_real, Ld, K, front, max_blocks=0):
+    """eval_small_multi_f32 for G Reg_EDDI / vanilla_EDDI members: images of the point-net layout; `front` is member 0's
+    front-end parameters, member g's strides[MS_PARAM] floats further (its row of the parameter stack)."""
+    check(lib().vpc_eval_small_multi_eddi_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G, ptr(tiles),
+                                              int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar, ptr(part),
+                                              _member_strides(strides), d, d_real, Ld, int(K), ptr(front), int(max_blocks),
+                                              stream_ptr()), "vpc_eval_small_multi_eddi_f32")
+
+
 def eval_reduce_multi(part, batches, n_batches, passes, M, members, G, part_stride, n_tiles, d_real, out):
     """The tile records -> out[G][4] = (rmse, elbo, negll, negll_imp): per batch, mean over a pass's batches, mean over passes."""
     check(lib().vpc_eval_reduce_multi(ptr(part), ptr(batches), int(n_batches), ptr(passes), int(M), ptr(members), G,
