@@ -725,6 +725,23 @@ int vpc_impute_small_multi_f32(const float* x, const uint8_t* mask, const float*
                                const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
                                unsigned long long offset, float x_logvar, int mode, float* out, long out_stride,
                                const long* strides, int d, int d_real, int L, int max_blocks, void* stream);
+/* vpc_impute_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members (the forwards of evaluate.py:396-414 and :380-392 on
+ * VAE.py:570-580, :1053-1060; the encoder input [x*mask | mask] of VAE.py:545-548 is built in the kernel's input stage): the forward
+ * of vpc_eval_small_multi_aug_f32 - d the row pitch 4 ceil(d_real / 4), images of the mask-augmented layout, its shape limits and
+ * pointer checks - with mode / out / out_stride as vpc_impute_small_multi_f32. */
+int vpc_impute_small_multi_aug_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img, const float* dec_img,
+                                   const VpcMember* members, int G, const long long* tiles, long n_tiles, long N, long R, int draw,
+                                   unsigned long long offset, float x_logvar, int mode, float* out, long out_stride,
+                                   const long* strides, int d, int d_real, int L, int max_blocks, void* stream);
+/* ... and for G Reg_EDDI / vanilla_EDDI members (the same forwards on VAE.py:757-767, :935-950; front-end VAE.py:719-733, :903-917
+ * as the input stage): the forward of vpc_eval_small_multi_eddi_f32 - images of the point-net layout, K = emb_dim, `front` member
+ * 0's front-end inside its row of the parameter stack, strides[VPC_MS_PARAM] floats between members, its limits (K <= 32,
+ * d_real <= 64) and checks - with mode / out / out_stride as vpc_impute_small_multi_f32. */
+int vpc_impute_small_multi_eddi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                    const float* dec_img, const VpcMember* members, int G, const long long* tiles, long n_tiles,
+                                    long N, long R, int draw, unsigned long long offset, float x_logvar, int mode, float* out,
+                                    long out_stride, const long* strides, int d, int d_real, int L, int K, const float* front,
+                                    int max_blocks, void* stream);
 /* target_mse of evaluate.py:390-392 per member: out[g * out_stride] = mean of sq[g * sq_stride + 0..R) (the mode-1 squared errors
  * of the R = M n draw rows), accumulated in fp64 in a fixed order (no atomics), stored as float. */
 int vpc_target_mse_multi(const float* sq, long sq_stride, long R, int G, float* out, long out_stride, void* stream);
@@ -745,6 +762,28 @@ int vpc_reward_scratch_multi(int n, int d, int M, long* pre_floats, long* stat_f
 int vpc_reward_matrix_multi(const float* x, const uint8_t* mask, const float* im, const float* W1, const float* b1,
                             const float* enc_img, float* pre, float* stat, float* w1t, float* R, int G, int chunk,
                             const long* strides, int n, int d, int L, int M, void* stream);
+/* vpc_reward_matrix_ex (evaluate.py:424-433 around :514-634, the encoders of VAE.py:545-548 and :713-741) with a member dimension,
+ * for kind = VPC_REWARD_DENSE_MASK (2 d <= 128) and VPC_REWARD_POINTNET (d <= 64, K <= 32) - the members the family forwards above
+ * serve; VPC_REWARD_DENSE: VPC_ERR_ARG (vpc_reward_matrix_multi).  The three launches of vpc_reward_matrix_ex with blockIdx.y =
+ * member and its choice of kernels per kind, so R[g] is bit for bit what vpc_reward_matrix_ex gives on member g's operands.
+ * Pointers are member 0's; the stride vector has VPC_RM_COUNT_EX longs: the nine slots of vpc_reward_matrix_multi, where
+ *   VPC_RM_PARAM  W1 [100][2 d] (DENSE_MASK) or [100][K] (POINTNET) and b1 [100], rows of a parameter stack
+ *   VPC_RM_IMG    w23_img = [W2 | W3] of a packed encoder image (10240 floats, 16-byte aligned; multiple of 4)
+ *   VPC_RM_PRE, VPC_RM_STAT, VPC_RM_W1T   vpc_reward_scratch_multi_ex's sizes per member
+ * and then
+ *   VPC_RM_AC     AC [2][K][d], the folded front-end of vpc_eddi_fold_multi (POINTNET; ignored by DENSE_MASK, as AC and K are).
+ * chunk as vpc_reward_matrix_multi.  2 d > 128 / d > 64, K < 1, K > 32, L > 15: VPC_ERR_SHAPE; a member slice outside its stride, a
+ * misaligned workspace or w23_img, a null AC under POINTNET: VPC_ERR_ARG; nothing is launched in either case. */
+enum { VPC_RM_AC = VPC_RM_COUNT, VPC_RM_COUNT_EX };
+int vpc_reward_scratch_multi_ex(int kind, int n, int d, int M, int K, long* pre_floats, long* stat_floats, long* w1t_floats);
+int vpc_reward_matrix_multi_ex(int kind, const float* x, const uint8_t* mask, const float* im, const float* W1, const float* b1,
+                               const float* AC, int K, const float* w23_img, float* pre, float* stat, float* w1t, float* R, int G,
+                               int chunk, const long* strides, int n, int d, int L, int M, void* stream);
+/* The fold of the point-net front-end (VAE.py:719-727: A_j = w_x + W_E E_j, C_j = w_t t_j + c) for G members in one launch:
+ * vpc_eddi_fold on member g's front-end (E [d][K] | t [d] | W [K][2 + K] | c [K], front_stride floats after member 0's: its row of
+ * the parameter stack, read in place) -> AC0 + g * AC_stride, [2][K][d], bit for bit vpc_eddi_fold's output.  The acquisition loop
+ * calls it once per run: the parameters do not change inside one.  Limits as vpc_eddi_fold; a stride below its slice: VPC_ERR_ARG. */
+int vpc_eddi_fold_multi(const float* front0, long front_stride, float* AC0, long AC_stride, int G, int d, int K, void* stream);
 /* The acquisition of evaluate.py:435-440 per (member, row): i_opt = the lowest index among the maxima of R[g][row][0..d-1)
  * (torch.argmax on finite input), mask[g][row][i_opt] = 1 (bytes, rows mask_pitch apart; mask2, if not NULL, is the same mask kept at
  * a second row pitch - the forward reads rows padded to a multiple of 4 columns, the reward rows of d), action[g][row] = i_opt with

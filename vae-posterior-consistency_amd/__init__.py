@@ -9,8 +9,8 @@ from ._lib import VpcError, LIB_PATH
 from .models import Reg_VAE, vanilla_VAE, Reg_VAE_mask, vanilla_VAE_mask, MAX_EPOCH
 from .fused import FusedTrainer
 from . import ensemble
-from .ensemble import (EDDIEnsembleEvaluator, EDDIEnsembleTrainer, EnsembleAcquirer, EnsembleEvaluator, EnsembleTrainer,
-                       MaskEnsembleEvaluator, MaskEnsembleTrainer, stack_models)
+from .ensemble import (EDDIEnsembleAcquirer, EDDIEnsembleEvaluator, EDDIEnsembleTrainer, EnsembleAcquirer, EnsembleEvaluator,
+                       EnsembleTrainer, MaskEnsembleAcquirer, MaskEnsembleEvaluator, MaskEnsembleTrainer, stack_models)
 from .notmiwae import REG_notMIWAE_v2, notMIWAE_myversion, NMTrainer
 from .harness import (create_missing_uci, create_missing_uci_drop_eddi, model_loader, checkpoint_path, train, train_sweep, eval_vae, eval_sweep, result_paths, eval_vae_mnar,
                       mnar_result_path, eval_miwae, miwae_result_path)
@@ -43,4 +43,4 @@ __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedT
            "chaini_II_ratio_version", "active_learning_flow", "ais", "ais_chains", "ais_trajectory", "eval_ais",
            "ensemble", "EnsembleTrainer", "stack_models", "train_sweep", "EnsembleEvaluator", "eval_sweep",
            "EnsembleAcquirer", "active_sweep", "MaskEnsembleTrainer", "EDDIEnsembleTrainer",
-           "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator"]
+           "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator", "MaskEnsembleAcquirer", "EDDIEnsembleAcquirer"]

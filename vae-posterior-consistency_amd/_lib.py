@@ -82,7 +82,13 @@ _PROTOS = {
     "vpc_eval_small_multi_eddi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, P, C.POINTER(L_), I, I, I, I, P, I, P],
     "vpc_eval_reduce_multi": [P, P, L_, P, I, P, I, L_, L_, I, P, P],
     "vpc_impute_small_multi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, I, P, L_, C.POINTER(L_), I, I, I, I, P],
+    "vpc_impute_small_multi_aug_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, I, P, L_, C.POINTER(L_), I, I, I, I, P],
+    "vpc_impute_small_multi_eddi_f32": [P, P, P, P, P, P, I, P, L_, L_, L_, I, ULL, F, I, P, L_, C.POINTER(L_), I, I, I, I, P, I,
+                                        P],
     "vpc_target_mse_multi": [P, L_, L_, I, P, L_, P],
+    "vpc_reward_scratch_multi_ex": [I, I, I, I, I, C.POINTER(L_), C.POINTER(L_), C.POINTER(L_)],
+    "vpc_reward_matrix_multi_ex": [I, P, P, P, P, P, P, I, P, P, P, P, P, I, I, C.POINTER(L_), I, I, I, I, P],
+    "vpc_eddi_fold_multi": [P, L_, P, L_, I, I, I, P],
     "vpc_reward_scratch_multi": [I, I, I, C.POINTER(L_), C.POINTER(L_), C.POINTER(L_)],
     "vpc_reward_matrix_multi": [P, P, P, P, P, P, P, P, P, P, I, I, C.POINTER(L_), I, I, I, I, P],
     "vpc_acquire_multi": [P, L_, P, L_, I, P, L_, I, P, L_, I, I, I, I, P],

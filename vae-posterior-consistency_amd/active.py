@@ -19,15 +19,14 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib, ptr, stream_ptr
-from .ensemble import EnsembleAcquirer
-from .harness import _save_results, _sweep_configs, _sweep_models, draw_mask_p, eval_groups, model_loader
+from .ensemble import W23_FLOATS, EDDIEnsembleAcquirer, EnsembleAcquirer, MaskEnsembleAcquirer
+from .harness import _save_results, _sweep_configs, _sweep_models, draw_mask_p, eval_groups, family_eval_groups, model_loader
 from .images import PackedImage
 from .ops import _f32c, as_mask_u8, pack_weights
 
 
 # first-layer kinds of vpc_reward_matrix_ex (include/vpc.h)
 REWARD_DENSE, REWARD_DENSE_MASK, REWARD_POINTNET = 0, 1, 2
-W23_FLOATS = 64 * 128 + 32 * 64  # [W2 | W3] of a packed encoder image (csrc/vpc_layout.h EncImg, oW2 .. total), any width
 _H1, _H2 = 100, 50
 
 
@@ -390,9 +389,12 @@ def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate,
     harness.eval_sweep, with its conventions for configs and models.
     Members are grouped with harness.eval_groups: plain Reg_VAE / vanilla_VAE members of one class and reg_type run the whole
     loop through ONE ensemble.EnsembleAcquirer - a fixed number of launches per acquisition step whatever their number, nothing
-    read back before the end; every other family (mask-augmented, wide, EDDI) goes alone through active_learning_func, and the
-    flow models through active_learning_flow.  Returns, per member in the order of configs, the dict active_learning_func returns
-    (information_curve_CHAI [Repeat, n, d] - the scalar curve broadcast over the rows, as the reference stores it -, action_CHAI
+    read back before the end.  The members that leaves alone are split with harness.family_eval_groups: two or more Reg_VAE_mask /
+    vanilla_VAE_mask members of one class, shape and reg_type run through ONE ensemble.MaskEnsembleAcquirer, two or more Reg_EDDI /
+    vanilla_EDDI members of one class, shape, emb_dim and reg_type through ONE ensemble.EDDIEnsembleAcquirer, outputs and files
+    exactly as for the plain groups.  A mask-augmented or point-net member with no second of its kind, and every other family
+    (wide, mnist EDDI), goes alone through active_learning_func, and the flow models through active_learning_flow.
+    Returns, per member in the order of configs, the dict active_learning_func returns (information_curve_CHAI [Repeat, n, d] - the scalar curve broadcast over the rows, as the reference stores it -, action_CHAI
     [Repeat, n, d-1] float, R_hist_CHAI [Repeat, d-1, n, d-1], im_CHAI [Repeat, d-1, M, n, d]) and (save=True) writes the
     reference's four files under active_result_paths(...) with that member's alpha / p_missingness.
     What differs from active_learning_func for the members run together: what eval_sweep states for its members (no p pass,
@@ -403,7 +405,13 @@ def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate,
     ms = _sweep_models(cfgs, models, dev, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
                        max_epochs, valid_k, num_estimates, experiment_type, reg_type, alpha_annealing=alpha_annealing)
     out = [None] * len(cfgs)
-    groups, single = eval_groups(ms)
+    runs = [(EnsembleAcquirer, idx) for idx in eval_groups(ms)[0].values()]
+    family_groups, single = family_eval_groups(ms)  # (of the members eval_groups leaves alone)
+    for key, idx in family_groups.items():
+        if len(idx) >= 2:
+            runs.append((MaskEnsembleAcquirer if key[0] == "mask" else EDDIEnsembleAcquirer, idx))
+        else:
+            single = sorted(single + idx)
     for g in single:
         c = cfgs[g]
         fn = active_learning_flow if _is_flow(ms[g]) else active_learning_func
@@ -412,9 +420,9 @@ def active_sweep(data_loader_train, configs, test_data, test_mask, missing_rate,
                     stage, c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, Repeat, model=ms[g], save=save,
                     max_steps=max_steps)
     x = test_data.reshape(-1, obs_dim).float().to(dev)
-    for idx in groups.values():
+    for acquirer, idx in runs:
         with torch.no_grad():
-            acq = EnsembleAcquirer([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
+            acq = acquirer([ms[g] for g in idx], seeds=[cfgs[g]["seed"] for g in idx])
             info, action, R_hist, im_hist = [t.cpu() for t in acq.run(x, M, repeats=Repeat, max_steps=max_steps)]
         n = x.shape[0]
         for k, g in enumerate(idx):

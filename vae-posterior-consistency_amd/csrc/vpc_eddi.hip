@@ -41,6 +41,26 @@ __global__ void eddi_fold_kernel(const float* __restrict__ E, const float* __res
     AC[(long)(K + k) * d + j] = w[1 + K] * tb[j] + cp[k];
 }
 
+// The fold of member blockIdx.y's front-end, read in place from its row [trunk | decoder | front-end] of a parameter stack
+// (front = E [d][K] | t [d] | W [K][2+K] | c [K], as the point-net ensemble kernels read it): AC[g] [2][K][d], the statements of
+// eddi_fold_kernel on the member's four tensors, so AC[g] is bit for bit what vpc_eddi_fold gives on them.
+__global__ void eddi_fold_multi_kernel(const float* __restrict__ front0, long sfront, float* __restrict__ AC0, long sAC, int d,
+                                       int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d * K) return;
+    const float* __restrict__ E = front0 + blockIdx.y * sfront;
+    const float* __restrict__ tb = E + (long)d * K;
+    const float* __restrict__ Wp = tb + d;
+    const float* __restrict__ cp = Wp + (long)K * (2 + K);
+    float* __restrict__ AC = AC0 + blockIdx.y * sAC;
+    const int k = i / d, j = i % d;
+    const float* w = Wp + (long)k * (2 + K);
+    float a = w[0];
+    for (int e = 0; e < K; ++e) a += w[1 + e] * E[(long)j * K + e];
+    AC[(long)k * d + j] = a;
+    AC[(long)(K + k) * d + j] = w[1 + K] * tb[j] + cp[k];
+}
+
 // rows r = pass * B + b: the passes of one step (mask, mask_p) are stacked, x is shared
 template <int T>
 __global__ __launch_bounds__(256) void eddi_front_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m0,
@@ -397,6 +417,16 @@ int vpc_eddi_fold(const float* E, const float* tb, const float* Wp, const float*
     if (d <= 0 || d > 128 || K <= 0 || K > EDDI_MAX_K) return VPC_ERR_SHAPE;
     hipLaunchKernelGGL(eddi_fold_kernel, dim3((d * K + 255) / 256), dim3(256), 0, (hipStream_t)stream, E, tb, Wp, cp, AC, d,
                        K);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_eddi_fold_multi(const float* front0, long front_stride, float* AC0, long AC_stride, int G, int d, int K, void* stream) {
+    if (!front0 || !AC0 || (uintptr_t)front0 % 4 || (uintptr_t)AC0 % 4 || G < 1 || G > 65535) return VPC_ERR_ARG;
+    if (d <= 0 || d > 128 || K <= 0 || K > EDDI_MAX_K) return VPC_ERR_SHAPE;
+    // every member's front-end and AC inside its stride (the front-ends are read only, but each member has its own row)
+    if (front_stride < (long)d * K + d + (long)K * (2 + K) + K || AC_stride < 2L * K * d) return VPC_ERR_ARG;
+    hipLaunchKernelGGL(eddi_fold_multi_kernel, dim3((d * K + 255) / 256, (unsigned)G), dim3(256), 0, (hipStream_t)stream, front0,
+                       front_stride, AC0, AC_stride, d, K);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

@@ -17,7 +17,8 @@
 // folded per workgroup in the buffers that are idle until the first encoder stage); same LDS, same records, same reduce launch.
 // eval_reduce_multi_kernel: blockIdx.y = member; tiles -> batches -> passes -> out[g][4] in fp64, in a fixed order.
 // impute_small_kernel: the same forward (ONE body text, vpc_evalsmall_body.h) keeping x_hat instead of the sums - the M Monte-Carlo
-// forwards of active_learning_func (evaluate.py:380-414) for G members: x_hat per draw row, or the target column's squared error;
+// forwards of active_learning_func (evaluate.py:380-414) for G members: x_hat per draw row, or the target column's squared error
+// (impute_small_aug_kernel / impute_small_eddi_kernel: the same for mask-augmented and point-net members);
 // target_mse_multi_kernel: the mean of those errors per member (evaluate.py:390-392), fp64 in a fixed order.
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
@@ -115,6 +116,32 @@ __global__ __launch_bounds__(THREADS) void impute_small_kernel(ImputeArgs ia) {
     const EvalArgs& a = ia.e;
     float* const out = ia.out;
     const long sout = ia.sout;
+#include "vpc_evalsmall_body.h"
+}
+// ... for Reg_VAE_mask / vanilla_VAE_mask members: the input stage of eval_small_aug_kernel, the outputs of impute_small_kernel
+// (the body's AUG / PN stages and its OUT stage share no code: the input stage ends at E_X, the output stage starts at `pre`).
+template <int DTI, int DT, int MODE>
+__global__ __launch_bounds__(THREADS) void impute_small_aug_kernel(ImputeArgs ia) {
+    constexpr bool AUG = true;
+    constexpr bool PN = false;
+    constexpr EvalPointNet pnx{};
+    constexpr int OUT = MODE == 0 ? OUT_XHAT : OUT_SQERR;
+    const EvalArgs& a = ia.e;
+    float* const out = ia.out;
+    const long sout = ia.sout;
+#include "vpc_evalsmall_body.h"
+}
+// ... and for Reg_EDDI / vanilla_EDDI members: the input stage of eval_small_eddi_kernel.
+struct ImputePnArgs : ImputeArgs { EvalPointNet pn; };
+template <int DTI, int DT, int MODE>
+__global__ __launch_bounds__(THREADS) void impute_small_eddi_kernel(ImputePnArgs pa) {
+    constexpr bool AUG = false;
+    constexpr bool PN = true;
+    const EvalPointNet& pnx = pa.pn;
+    constexpr int OUT = MODE == 0 ? OUT_XHAT : OUT_SQERR;
+    const EvalArgs& a = pa.e;
+    float* const out = pa.out;
+    const long sout = pa.sout;
 #include "vpc_evalsmall_body.h"
 }
 
@@ -371,6 +398,81 @@ extern "C" int vpc_impute_small_multi_f32(const float* x, const uint8_t* mask, c
     }
         switch (2 * dt_for(d) + mode) {
             VPC_CASE(1, 0) VPC_CASE(2, 0) VPC_CASE(4, 0) VPC_CASE(8, 0) VPC_CASE(1, 1) VPC_CASE(2, 1) VPC_CASE(4, 1) VPC_CASE(8, 1)
+        }
+#undef VPC_CASE
+        return false;
+    });
+}
+
+// vpc_impute_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members: shape limits and pointer checks of
+// vpc_eval_small_multi_aug_f32, the out / out_stride checks of the plain impute entry.
+extern "C" int vpc_impute_small_multi_aug_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                              const float* dec_img, const VpcMember* members, int G, const long long* tiles,
+                                              long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
+                                              int mode, float* out, long out_stride, const long* strides, int d, int d_real,
+                                              int L, int max_blocks, void* stream) {
+    if (d_real < 1 || d_real > d || d - d_real > 3 || 2 * d_real > MAX_D) return VPC_ERR_SHAPE;
+    if (!out || (uintptr_t)out % 4 || mode < 0 || mode > 1) return VPC_ERR_ARG;
+    ImputeArgs ia;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, ia.e);
+    if (rc != VPC_OK) return rc;
+    if (out_stride < (mode == 0 ? R * (long)d_real : R)) return VPC_ERR_ARG;
+    ia.out = out;
+    ia.sout = out_stride;
+    hipStream_t s = (hipStream_t)stream;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
+        ia.e.tile0 = t0;
+#define VPC_CASE(TI, T, MODE)                                                                              \
+    case 2 * TI + MODE: {                                                                                  \
+        auto kern = impute_small_aug_kernel<TI, T, MODE>;                                                  \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), IMPUTE_LDS)) return false;                 \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), IMPUTE_LDS, s, ia);                                  \
+        return true;                                                                                       \
+    }
+        // (input tiles, output tiles) as vpc_eval_small_multi_aug_f32
+        switch (2 * dt_for(2 * d_real) + mode) {
+            VPC_CASE(1, 1, 0) VPC_CASE(2, 1, 0) VPC_CASE(4, 2, 0) VPC_CASE(8, 4, 0)
+            VPC_CASE(1, 1, 1) VPC_CASE(2, 1, 1) VPC_CASE(4, 2, 1) VPC_CASE(8, 4, 1)
+        }
+#undef VPC_CASE
+        return false;
+    });
+}
+
+// ... and for G Reg_EDDI / vanilla_EDDI members: limits and checks of vpc_eval_small_multi_eddi_f32.
+extern "C" int vpc_impute_small_multi_eddi_f32(const float* x, const uint8_t* mask, const float* eps, const float* enc_img,
+                                               const float* dec_img, const VpcMember* members, int G, const long long* tiles,
+                                               long n_tiles, long N, long R, int draw, unsigned long long offset, float x_logvar,
+                                               int mode, float* out, long out_stride, const long* strides, int d, int d_real,
+                                               int L, int K, const float* front, int max_blocks, void* stream) {
+    if (d_real < 1 || d_real > 64 || d_real > d || d - d_real > 3 || d > 64 || K < 1 || K > 32) return VPC_ERR_SHAPE;
+    if (!front || (uintptr_t)front % 4) return VPC_ERR_ARG;
+    if (!out || (uintptr_t)out % 4 || mode < 0 || mode > 1) return VPC_ERR_ARG;
+    ImputePnArgs ia;
+    const int rc = eval_forward_args(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar,
+                                     strides, d, d_real, L, max_blocks, ia.e);
+    if (rc != VPC_OK) return rc;
+    if (out_stride < (mode == 0 ? R * (long)d_real : R)) return VPC_ERR_ARG;
+    const long nfront = (long)d_real * K + d_real + (long)K * (2 + K) + K;
+    if (strides[VPC_MS_PARAM] < nfront) return VPC_ERR_ARG;  // (read only, but every member has its own row)
+    ia.out = out;
+    ia.sout = out_stride;
+    ia.pn = EvalPointNet{K, front, strides[VPC_MS_PARAM]};
+    hipStream_t s = (hipStream_t)stream;
+    return eval_chunks(n_tiles, G, max_blocks, [&](long t0, dim3 grid) {
+        ia.e.tile0 = t0;
+#define VPC_CASE(TI, T, MODE)                                                                              \
+    case 8 * TI + 2 * T + MODE: {                                                                          \
+        auto kern = impute_small_eddi_kernel<TI, T, MODE>;                                                 \
+        if (!lds_attr_done(reinterpret_cast<const void*>(kern), IMPUTE_LDS)) return false;                 \
+        hipLaunchKernelGGL(kern, grid, dim3(THREADS), IMPUTE_LDS, s, ia);                                  \
+        return true;                                                                                       \
+    }
+        // (input tiles, output tiles) as vpc_eval_small_multi_eddi_f32
+        switch (8 * dt_for(K) + 2 * dt_for(d_real) + mode) {
+            VPC_CASE(1, 1, 0) VPC_CASE(1, 2, 0) VPC_CASE(1, 4, 0) VPC_CASE(2, 1, 0) VPC_CASE(2, 2, 0) VPC_CASE(2, 4, 0)
+            VPC_CASE(1, 1, 1) VPC_CASE(1, 2, 1) VPC_CASE(1, 4, 1) VPC_CASE(2, 1, 1) VPC_CASE(2, 2, 1) VPC_CASE(2, 4, 1)
         }
 #undef VPC_CASE
         return false;

@@ -2,7 +2,9 @@
 //   eval_small_kernel<DT>            (OUT = OUT_SUMS: the five sums of the tile's record),
 //   eval_small_aug_kernel<DTI, DT>   (the same for Reg_VAE_mask / vanilla_VAE_mask members: AUG),
 //   eval_small_eddi_kernel<DTI, DT>  (the same for Reg_EDDI / vanilla_EDDI members: PN) and
-//   impute_small_kernel<DT, MODE>    (OUT = OUT_XHAT / OUT_SQERR: x_hat, or the target column's squared error, per draw row),
+//   impute_small_kernel<DT, MODE>    (OUT = OUT_XHAT / OUT_SQERR: x_hat, or the target column's squared error, per draw row) with
+//   impute_small_aug_kernel<DTI, DT, MODE> and impute_small_eddi_kernel<DTI, DT, MODE> (the same outputs under AUG / PN: the input
+//   stage ends at E_X and the output stage starts at the last layer's `pre`, so the two choices meet nowhere),
 // so that the arithmetic up to x_hat is ONE piece of code and eval_small_kernel compiles to the instructions it had as a
 // self-contained kernel (vpc_small_body.h says why this is not a shared inline function).
 // In scope at the point of inclusion: the compile-time tile counts DT (tiles of d: x / mask words, W6, the output tiles) and DTI

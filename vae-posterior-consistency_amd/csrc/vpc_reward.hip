@@ -29,6 +29,8 @@
 // The plain model at d <= 128 also runs with a member dimension (vpc_reward_matrix_multi: blockIdx.y = member, the kernel bodies of
 // vpc_reward_prep_body.h / vpc_reward_chain_body.h on the member's operands), followed by the acquisition itself
 // (acquire_multi_kernel: argmax per row, mask byte, action; evaluate.py:435-440): the loop of G models without a host round trip.
+// The DENSE_MASK and POINTNET kinds have the member dimension too, within the widths of their members' forward kernels
+// (vpc_reward_matrix_multi_ex: reward_prep_multi_kind_kernel / reward_chain_multi_kind_kernel).
 #include "vpc_device.h"
 #include "vpc_abi_internal.h"
 
@@ -98,11 +100,14 @@ struct RewardMultiArgs {
     int n, d, L, M, Mp;
 };
 
-__device__ __forceinline__ RewardArgs reward_member_args(const RewardMultiArgs& m, unsigned g) {
+// table: floats of the kind's first-layer table at the head of a member's w1t slice (reward_table_floats); AC, K: the member's
+// folded front-end (POINTNET; null / 0 elsewhere)
+__device__ __forceinline__ RewardArgs reward_member_args(const RewardMultiArgs& m, unsigned g, long table, const float* AC,
+                                                         int K) {
     float* w1t = m.w1t + g * m.sw1t;
-    int* cand = reinterpret_cast<int*>(w1t + (long)m.d * H1P);
-    return RewardArgs{m.w23 + g * m.simg, m.pre + g * m.spre, w1t, nullptr, m.im + g * m.sim, m.mask + g * m.sm, cand,
-                      cand + (long)m.n * m.d, m.stat + g * m.sstat, m.R + g * m.sR, m.n, m.d, m.L, m.M, m.Mp, 0};
+    int* cand = reinterpret_cast<int*>(w1t + table);
+    return RewardArgs{m.w23 + g * m.simg, m.pre + g * m.spre, w1t, AC, m.im + g * m.sim, m.mask + g * m.sm, cand,
+                      cand + (long)m.n * m.d, m.stat + g * m.sstat, m.R + g * m.sR, m.n, m.d, m.L, m.M, m.Mp, K};
 }
 
 __global__ __launch_bounds__(128) void reward_prep_multi_kernel(RewardMultiArgs m) {
@@ -126,7 +131,56 @@ __global__ __launch_bounds__(128) void reward_prep_multi_kernel(RewardMultiArgs 
 template <int MODE>
 __global__ __launch_bounds__(RW_THREADS) void reward_chain_multi_kernel(RewardMultiArgs m) {
     constexpr int KIND = RK_DENSE;
-    const RewardArgs a = reward_member_args(m, blockIdx.y);
+    const RewardArgs a = reward_member_args(m, blockIdx.y, (long)m.d * H1P, nullptr, 0);
+#include "vpc_reward_chain_body.h"
+}
+
+// ---- the member dimension for the other first-layer kinds (DENSE_MASK at 2 d <= 128, POINTNET at d <= 64): the same two wrappers
+// with the kind as a template parameter and the instantiation choice of reward_launch - WIDE prep, mode 0 always RK_DENSE, mode 1
+// the kind's - so that R[g] is what vpc_reward_matrix_ex gives on member g's operands.  m.w23 is member 0's [W2 | W3] (not an
+// encoder image), m.W1 / m.b1 the kind's first layer ([100][2 d] / [100][K]); AC: member 0's folded front-end [2][K][d], sAC apart.
+// (Kernels of their own, not a KIND parameter on the two above: the plain pair keeps its symbols and its instructions.)
+struct RewardMultiKindArgs {
+    RewardMultiArgs m;
+    const float* AC;
+    long sAC;
+    int K;
+};
+
+// floats of a kind's first-layer table at the head of w1t: W1^T [d][112], its two halves, or the W1 fragments of two groups of K
+__host__ __device__ constexpr long reward_table(int kind, int d) {
+    return kind == RK_DENSE ? (long)d * H1P : kind == RK_DENSE_MASK ? 2L * d * H1P : 2L * PN_FRAG;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(128) void reward_prep_multi_kind_kernel(RewardMultiKindArgs ma) {
+    constexpr bool WIDE = true;
+    const RewardMultiArgs& m = ma.m;
+    const unsigned g = blockIdx.y;
+    const float* __restrict__ x = m.x + g * m.sx;
+    const uint8_t* __restrict__ mask = m.mask + g * m.sm;
+    const float* __restrict__ im = m.im + g * m.sim;
+    const float* __restrict__ W1 = m.W1 + g * m.sparam;
+    const float* __restrict__ b1 = m.b1 + g * m.sparam;
+    const float* __restrict__ AC = KIND == RK_POINTNET ? ma.AC + g * ma.sAC : nullptr;
+    float* __restrict__ pre = m.pre + g * m.spre;
+    float* __restrict__ W1T = m.w1t + g * m.sw1t;
+    int* __restrict__ cand = reinterpret_cast<int*>(W1T + reward_table(KIND, m.d));
+    float* __restrict__ R = m.R + g * m.sR;
+    const int n = m.n, d = m.d, M = m.M, Mp = m.Mp, K = ma.K;
+#include "vpc_reward_prep_body.h"
+}
+
+// (three waves per SIMD asked for in the point-net MODE 1: the launch holds three workgroups per CU, and without the hint that
+// instantiation takes 152 + 36 registers, two waves per SIMD, where reward_chain_kernel<RK_POINTNET, 1> takes 117 + 36)
+template <int FKIND, int MODE>
+__global__ __launch_bounds__(RW_THREADS, (FKIND == RK_POINTNET && MODE == 1) ? 3 : 1) void reward_chain_multi_kind_kernel(
+    RewardMultiKindArgs ma) {
+    // MODE 0 runs the body as RK_DENSE for every kind (reward_chain_kernel); the candidate lists and the work counter lie behind
+    // the table of the member's kind in both modes
+    constexpr int KIND = MODE == 0 ? RK_DENSE : FKIND;
+    const RewardArgs a = reward_member_args(ma.m, blockIdx.y, reward_table(FKIND, ma.m.d),
+                                            FKIND == RK_POINTNET ? ma.AC + blockIdx.y * ma.sAC : nullptr, ma.K);
 #include "vpc_reward_chain_body.h"
 }
 
@@ -196,9 +250,7 @@ int reward_launch(const float* x, const uint8_t* mask, const float* im, const fl
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
-long reward_table_floats(int kind, int d) {
-    return kind == RK_DENSE ? (long)d * H1P : kind == RK_DENSE_MASK ? 2L * d * H1P : 2L * PN_FRAG;
-}
+long reward_table_floats(int kind, int d) { return reward_table(kind, d); }
 }  // namespace
 
 // Scratch sizes (floats) the caller must provide for vpc_reward_matrix.
@@ -299,6 +351,85 @@ extern "C" int vpc_reward_matrix_multi(const float* x, const uint8_t* mask, cons
         hipLaunchKernelGGL(reward_chain_multi_kernel<0>, dim3((unsigned)gA, gc), dim3(RW_THREADS), lds, s, m);
         hipLaunchKernelGGL(reward_chain_multi_kernel<1>, dim3((unsigned)gB, gc), dim3(RW_THREADS), lds, s, m);
         if (hipGetLastError() != hipSuccess) return VPC_ERR_HIP;
+    }
+    return VPC_OK;
+}
+
+// ---- ... for the mask-augmented and the point-net members
+namespace {
+// the shape limits of the family members' forward kernels (vpc_impute_small_multi_aug_f32 / _eddi_f32)
+int reward_multi_ex_shape(int kind, int d, int K) {
+    if (kind == RK_DENSE_MASK) return d >= 2 && 2 * d <= MAX_D ? VPC_OK : VPC_ERR_SHAPE;
+    if (kind == RK_POINTNET) return d >= 2 && d <= 64 && K >= 1 && K <= PN_MAX_K ? VPC_OK : VPC_ERR_SHAPE;
+    return VPC_ERR_ARG;  // (the plain kind has vpc_reward_matrix_multi)
+}
+
+template <int KIND>
+int reward_multi_launch(const RewardMultiKindArgs& ma, int gc, hipStream_t s) {
+    const RewardMultiArgs& m = ma.m;
+    const size_t ldsA = sizeof(float) * W23_FLOATS;
+    const size_t ldsB = ldsA + (KIND == RK_POINTNET ? sizeof(float) * ((ma.K + 15) / 16 * PN_FRAG) : 0);
+    if (!lds_attr_done(reinterpret_cast<const void*>(reward_chain_multi_kind_kernel<KIND, 0>), ldsA)) return VPC_ERR_HIP;
+    if (!lds_attr_done(reinterpret_cast<const void*>(reward_chain_multi_kind_kernel<KIND, 1>), ldsB)) return VPC_ERR_HIP;
+    // per member the grids of reward_launch, the chunk's total held to 3 workgroups per CU as in vpc_reward_matrix_multi
+    const long itemsB = (long)m.n * ((m.d - 1 + RW_CH - 1) / RW_CH);
+    const long cap = ((long)num_cus() * 3 + gc - 1) / gc;
+    long gA = (m.n + RW_WAVES - 1) / RW_WAVES, gB = (itemsB + RW_WAVES - 1) / RW_WAVES;
+    if (gA > cap) gA = cap;
+    if (gB > cap) gB = cap;
+    const int tail_blocks = KIND == RK_POINTNET ? 1 : (m.d + 7) / 8;
+    hipLaunchKernelGGL(reward_prep_multi_kind_kernel<KIND>, dim3(m.n + tail_blocks, gc), dim3(128), 0, s, ma);
+    hipLaunchKernelGGL((reward_chain_multi_kind_kernel<KIND, 0>), dim3((unsigned)gA, gc), dim3(RW_THREADS), ldsA, s, ma);
+    hipLaunchKernelGGL((reward_chain_multi_kind_kernel<KIND, 1>), dim3((unsigned)gB, gc), dim3(RW_THREADS), ldsB, s, ma);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+}  // namespace
+
+extern "C" int vpc_reward_scratch_multi_ex(int kind, int n, int d, int M, int K, long* pre_floats, long* stat_floats,
+                                           long* w1t_floats) {
+    if (n <= 0 || M <= 0) return VPC_ERR_ARG;
+    int rc = reward_multi_ex_shape(kind, d, K);
+    if (rc != VPC_OK) return rc;
+    long w1t = 0;
+    rc = vpc_reward_scratch_ex(kind, n, d, M, K, pre_floats, stat_floats, &w1t);
+    if (rc != VPC_OK) return rc;
+    if (w1t_floats) *w1t_floats = (w1t + 3) / 4 * 4;
+    return VPC_OK;
+}
+
+extern "C" int vpc_reward_matrix_multi_ex(int kind, const float* x, const uint8_t* mask, const float* im, const float* W1,
+                                          const float* b1, const float* AC, int K, const float* w23_img, float* pre, float* stat,
+                                          float* w1t, float* R, int G, int chunk, const long* strides, int n, int d, int L, int M,
+                                          void* stream) {
+    if (!x || !mask || !im || !W1 || !b1 || !w23_img || !pre || !stat || !w1t || !R || !strides) return VPC_ERR_ARG;
+    if (n <= 0 || M <= 0 || G < 1 || chunk < 1 || chunk > 65535) return VPC_ERR_ARG;
+    const int rc = reward_multi_ex_shape(kind, d, K);
+    if (rc != VPC_OK) return rc;
+    if (L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    if (kind == RK_POINTNET && (!AC || (uintptr_t)AC % 4)) return VPC_ERR_ARG;
+    if (!aligned16(pre) || !aligned16(stat) || !aligned16(w1t) || !aligned16(w23_img)) return VPC_ERR_ARG;
+    const long Mp = (M + 15) / 16 * 16, nd = (long)n * d;
+    const long sx = strides[VPC_RM_X], sm = strides[VPC_RM_MASK], sim = strides[VPC_RM_IM], sparam = strides[VPC_RM_PARAM],
+               simg = strides[VPC_RM_IMG], spre = strides[VPC_RM_PRE], sstat = strides[VPC_RM_STAT], sw1t = strides[VPC_RM_W1T],
+               sR = strides[VPC_RM_R], sAC = strides[VPC_RM_AC];
+    const long din = kind == RK_DENSE_MASK ? 2L * d : K;  // columns of W1
+    // every member's slice inside its stride; x may be shared (stride 0); the image and workspace slices stay 16-byte aligned
+    if ((sx != 0 && sx < nd) || sm < nd || sim < (long)M * nd || sparam < (long)H1 * din + H1 || sR < (long)n * (d - 1))
+        return VPC_ERR_ARG;
+    if (simg < W23_FLOATS || simg % 4 || spre < (long)n * Mp * 2 * H1P || spre % 4 || sstat < (long)n * Mp * STAT || sstat % 4 ||
+        sw1t < reward_table_floats(kind, d) + nd + 4 || sw1t % 4)
+        return VPC_ERR_ARG;
+    if (kind == RK_POINTNET && sAC < 2L * K * d) return VPC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    for (int g0 = 0; g0 < G; g0 += chunk) {
+        const int gc = G - g0 < chunk ? G - g0 : chunk;
+        const RewardMultiKindArgs ma{
+            RewardMultiArgs{x + g0 * sx, im + g0 * sim, W1 + g0 * sparam, b1 + g0 * sparam, w23_img + g0 * simg, mask + g0 * sm, pre,
+                            stat, w1t, R + g0 * sR, sx, sm, sim, sparam, simg, spre, sstat, sw1t, sR, n, d, L, M, (int)Mp},
+            kind == RK_POINTNET ? AC + g0 * sAC : nullptr, sAC, kind == RK_POINTNET ? K : 0};
+        const int lrc = kind == RK_DENSE_MASK ? reward_multi_launch<RK_DENSE_MASK>(ma, gc, s)
+                                              : reward_multi_launch<RK_POINTNET>(ma, gc, s);
+        if (lrc != VPC_OK) return lrc;
     }
     return VPC_OK;
 }

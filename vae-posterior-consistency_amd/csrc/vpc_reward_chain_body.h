@@ -1,6 +1,7 @@
 // The BODY of the reward's chain kernels (vpc_reward.hip), included as text into
 //   reward_chain_kernel<KIND, MODE>     (a = the RewardArgs kernel argument) and
-//   reward_chain_multi_kernel<MODE>     (a = member blockIdx.y's RewardArgs, built in registers; KIND = RK_DENSE),
+//   reward_chain_multi_kernel<MODE>     (a = member blockIdx.y's RewardArgs, built in registers; KIND = RK_DENSE) and
+//   reward_chain_multi_kind_kernel<FKIND, MODE>  (the same for RK_DENSE_MASK / RK_POINTNET members; KIND = FKIND in MODE 1),
 // so that a member's items run the arithmetic and the in-wave summation order of the single-model kernel, and that kernel compiles
 // to the instructions it had as a self-contained kernel (vpc_small_body.h says why this is not a shared inline function).
 // Items are handed out over blockIdx.x / gridDim.x and a.next_item: per member under the member kernels.

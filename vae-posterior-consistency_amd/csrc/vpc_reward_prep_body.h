@@ -1,6 +1,7 @@
 // The BODY of the reward's prep kernels (vpc_reward.hip), included as text into
 //   reward_prep_kernel<KIND, WIDE>   (the kernel's own arguments) and
-//   reward_prep_multi_kernel         (member g's operands, built in registers under the same names; KIND = RK_DENSE, WIDE = false),
+//   reward_prep_multi_kernel         (member g's operands, built in registers under the same names; KIND = RK_DENSE, WIDE = false)
+//   and reward_prep_multi_kind_kernel<KIND> (the same for RK_DENSE_MASK / RK_POINTNET members, WIDE = true),
 // so that both run ONE piece of code and the single-model kernel compiles to the instructions it had as a self-contained kernel (a
 // shared inline function is simplified before it is inlined and schedules differently: vpc_small_body.h).
 // In scope at the point of inclusion: KIND, WIDE, x, mask, im, W1, b1, AC, pre, W1T, cand, R, n, d, M, Mp, K.

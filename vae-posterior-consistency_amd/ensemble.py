@@ -27,7 +27,9 @@ acquire_plan / acquire_draw_offsets (the shapes and Philox offsets of a run, on 
     MaskEnsembleEvaluator        EnsembleEvaluator for G Reg_VAE_mask / vanilla_VAE_mask members (vpc_eval_small_multi_aug_f32)
     EDDIEnsembleEvaluator        ... and for G Reg_EDDI / vanilla_EDDI members (vpc_eval_small_multi_eddi_f32: the front-end is read
                                  from the parameter stack); both share vpc_eval_reduce_multi, and X.for_trainer(trainer) reads the
-                                 image stack a family trainer's tail re-packs.  Acquisition stays with the plain members.
+                                 image stack a family trainer's tail re-packs.
+    MaskEnsembleAcquirer         EnsembleAcquirer for the same two families: the family evaluator's members and images, the loop of
+    EDDIEnsembleAcquirer         EnsembleAcquirer around vpc_impute_small_multi_aug_f32 / _eddi_f32 and vpc_reward_matrix_multi_ex
 """
 from __future__ import annotations
 
@@ -472,7 +474,8 @@ class _FamilyTrainer(EnsembleTrainer):
     def evaluator(self):
         raise L.VpcError("EnsembleEvaluator and EnsembleAcquirer cover the plain Reg_VAE / vanilla_VAE members only: evaluate "
                          "mask-augmented and point-net members with MaskEnsembleEvaluator.for_trainer(trainer) / "
-                         "EDDIEnsembleEvaluator.for_trainer(trainer); their acquisition runs one by one (harness.active_sweep)")
+                         "EDDIEnsembleEvaluator.for_trainer(trainer), and run their acquisition with "
+                         "MaskEnsembleAcquirer.for_trainer(trainer) / EDDIEnsembleAcquirer.for_trainer(trainer)")
 
 
 class _PointNetImages:
@@ -842,7 +845,7 @@ class EnsembleAcquirer(EnsembleEvaluator):
     def _setup(self, x, n, M, forward=True, max_blocks=0):
         """What the launches of one call share; forward: also the device member table, the tile table, x at the row pitch."""
         d = self.lay.d
-        self.params = stack_models(self.models)  # (idempotent; a member moved since is stacked again)
+        self.params = stack_models(self.models, self.family.require)  # (idempotent; a member moved since is stacked again)
         per_x = _shared_or_per_member(x, "x", self.G, (n, d))
         x = ops._f32c(x)
         img0, simg = self._images()
@@ -879,14 +882,23 @@ class EnsembleAcquirer(EnsembleEvaluator):
         maskk[:, :, :d].copy_(as_mask_u8(mask))
         [(offset, plane)], seps = self._draws(None if eps is None else eps.unsqueeze(-3), R)
         out = torch.empty((G, M, n, d) if mode == 0 else (G, R), device=self.dev)
-        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg})
+        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg,
+                                               **self._family_strides()})
         self._forward(c, strides, maskk, plane, offset, mode, out, out.stride(0))
         self.launches = forward_launches(c.tiles_dev.shape[0], G, max_blocks)
         return out
 
+    def _once_per_call(self):
+        """What a family's reward needs once per run() / reward() call, launched here -> the launches it made."""
+        return 0
+
+    def _reward_sizes(self, n, M):
+        """Floats per member of the reward workspaces pre / stat / w1t."""
+        return ops.reward_scratch_multi(n, self.lay.d, M)
+
     def _reward_workspaces(self, n, M, ws_floats):
         """(floats per member of pre / stat / w1t, members per chunk); the buffers are kept between calls."""
-        sizes = ops.reward_scratch_multi(n, self.lay.d, M)
+        sizes = self._reward_sizes(n, M)
         chunk = reward_member_chunk(self.G, n, self.lay.d, M, ws_floats, sizes)
         key = (n, M, chunk)
         if getattr(self, "_reward_ws_key", None) != key:
@@ -921,8 +933,9 @@ class EnsembleAcquirer(EnsembleEvaluator):
         sizes, chunk = self._reward_workspaces(n, M, ws_floats)
         R = torch.empty(G, n, d - 1, device=self.dev)
         mask, im = as_mask_u8(mask), ops._f32c(im)
+        once = self._once_per_call()
         self._reward(c, self._reward_strides(c, mask, im, R, sizes), mask, im, R, chunk)
-        self.launches = 3 * ((G + chunk - 1) // chunk)
+        self.launches = once + 3 * ((G + chunk - 1) // chunk)
         return R
 
     def run(self, x, M, *, repeats=1, max_steps=None, eps=None, keep_im=True, max_blocks=0, ws_floats=REWARD_WS_FLOATS):
@@ -952,8 +965,9 @@ class EnsembleAcquirer(EnsembleEvaluator):
         maskk = mask if dk == d else torch.zeros(G, n, dk, dtype=torch.uint8, device=dev)
         sizes, chunk = self._reward_workspaces(n, M, ws_floats)
         f_launches, r_launches = forward_launches(c.tiles_dev.shape[0], G, max_blocks), 3 * ((G + chunk - 1) // chunk)
-        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg})
-
+        strides = stride_vector(ops.MS_COUNT, {ops.MS_X: c.sxk, ops.MS_MASK: maskk.stride(0), ops.MS_EPS: seps, ops.MS_IMG: c.simg,
+                                               **self._family_strides()})
+        once = self._once_per_call()
         r_strides = self._reward_strides(c, mask, im_hist[:, 0, 0] if keep_im else im_buf, R_hist[:, 0, 0], sizes)
 
         def forward(mode, out, out_stride):
@@ -979,5 +993,90 @@ class EnsembleAcquirer(EnsembleEvaluator):
                                   maskk.stride(0), dk, action[0, r, :, t:], action.stride(0), d - 1, G, n, d)
                 curve_point(r, t + 1)
         self.launches_per_step = 2 * f_launches + r_launches + 2
-        self.launches = repeats * (f_launches + 1 + steps * self.launches_per_step)
+        self.launches = once + repeats * (f_launches + 1 + steps * self.launches_per_step)
         return info, action, R_hist, im_hist
+
+
+W23_FLOATS = 64 * 128 + 32 * 64  # [W2 | W3] at the tail of a packed encoder image (csrc/vpc_layout.h EncImg, oW2 .. total), any width
+
+
+class _FamilyAcquirer(EnsembleAcquirer):
+    """EnsembleAcquirer for a member family other than the plain one: run(), impute(), reward(), the draw rule and the launch
+    accounting are EnsembleAcquirer's; members, images, pitch and for_trainer() are the family evaluator's (the class a subclass
+    names first).  A subclass says which forward launch runs (_forward), which first-layer kind the reward has and where a
+    member's W1 / b1 lie in its row of the parameter stack; [W2 | W3] is the tail of the member's encoder image."""
+    kind = None  # ops.REWARD_*
+
+    def _first_layer_cols(self):
+        """Columns of W1 [100][.], which opens a member's row of the parameter stack with b1 [100] behind it."""
+        raise NotImplementedError
+
+    def _folded(self):
+        """(AC of member 0, member stride, K) of the folded front-ends the reward reads; (None, 0, 0) for a kind without one."""
+        return None, 0, 0
+
+    def _reward_sizes(self, n, M):
+        return ops.reward_scratch_multi_ex(self.kind, n, self.lay.d, M, self.lay.K)
+
+    def _reward_strides(self, c, mask, im, R, sizes):
+        return stride_vector(ops.RM_COUNT_EX, {
+            ops.RM_X: c.sx, ops.RM_MASK: mask.stride(0), ops.RM_IM: im.stride(0), ops.RM_PARAM: self.params.stride(0),
+            ops.RM_IMG: c.simg, ops.RM_PRE: sizes[0], ops.RM_STAT: sizes[1], ops.RM_W1T: sizes[2], ops.RM_R: R.stride(0),
+            ops.RM_AC: self._folded()[1]})
+
+    def _reward(self, c, strides, mask, im, R, chunk):
+        lay = self.lay
+        w1 = self.params[0]
+        pre, stat, w1t = self._reward_ws
+        AC, _, K = self._folded()
+        ops.reward_matrix_multi_ex(self.kind, c.x, mask, im[0], w1, w1[100 * self._first_layer_cols():], AC, K,
+                                   c.img0[lay.enc_img - W23_FLOATS:lay.enc_img], pre, stat, w1t, R[0], self.G, chunk, strides, c.n,
+                                   lay.d, lay.L, c.M)
+
+
+class MaskEnsembleAcquirer(MaskEnsembleEvaluator, _FamilyAcquirer):
+    """EnsembleAcquirer for G Reg_VAE_mask or G vanilla_VAE_mask of one (obs_dim, latent_dim, reg_type): the loop of
+    active_learning_func on VAE.py:570-580 / :1053-1060 through vpc_impute_small_multi_aug_f32 and vpc_reward_matrix_multi_ex
+    (VPC_REWARD_DENSE_MASK).  W1 [100][2 obs_dim] / b1 open a member's row of the parameter stack; the images are the models' own,
+    as under MaskEnsembleEvaluator."""
+    kind = ops.REWARD_DENSE_MASK
+
+    def _first_layer_cols(self):
+        return 2 * self.lay.d
+
+    def _forward(self, c, strides, maskk, eps_plane, offset, mode, out, out_stride):
+        lay = self.lay
+        ops.impute_small_multi_aug_f32(c.xk, maskk, eps_plane, c.img0[:lay.enc_img], c.img0[lay.enc_img:], self.table_dev, self.G,
+                                       c.tiles_dev, c.tiles_dev.shape[0], c.n, c.M * c.n, eps_plane is None, offset,
+                                       self.models[0]._x_logvar_value, mode, out, out_stride, strides, c.xk.shape[-1], lay.d,
+                                       lay.L, c.max_blocks)
+
+
+class EDDIEnsembleAcquirer(EDDIEnsembleEvaluator, _FamilyAcquirer):
+    """EnsembleAcquirer for G Reg_EDDI or G vanilla_EDDI of one (obs_dim, emb_dim, latent_dim, reg_type): the loop on VAE.py:757-767
+    / :935-950 through vpc_impute_small_multi_eddi_f32 and vpc_reward_matrix_multi_ex (VPC_REWARD_POINTNET).  W1 [100][emb_dim] /
+    b1 = pnp_encoder2.0 open a member's row [trunk | decoder | front-end]; [W2 | W3] is the tail of the member's trunk image of the
+    point-net layout (the evaluator's rows, or the trunk trainer's: for_trainer); the front-end is read in place and folded to
+    AC [G][2][emb_dim][obs_dim] by ONE vpc_eddi_fold_multi launch per run() / reward() call - the parameters do not change inside
+    a call - which `launches` counts."""
+    kind = ops.REWARD_POINTNET
+
+    def _first_layer_cols(self):
+        return self.lay.K
+
+    def _folded(self):
+        return self._AC[0], self._AC.stride(0), self.lay.K
+
+    def _once_per_call(self):
+        lay = self.lay
+        if getattr(self, "_AC", None) is None:
+            self._AC = torch.empty(self.G, _pitch(2 * lay.K * lay.d), device=self.dev)
+        ops.eddi_fold_multi(self.params[0, lay.n_params:], self.params.stride(0), self._AC, self._AC.stride(0), self.G, lay.d, lay.K)
+        return 1
+
+    def _forward(self, c, strides, maskk, eps_plane, offset, mode, out, out_stride):
+        lay = self.lay
+        ops.impute_small_multi_eddi_f32(c.xk, maskk, eps_plane, c.img0[:lay.enc_img], c.img0[lay.enc_img:], self.table_dev, self.G,
+                                        c.tiles_dev, c.tiles_dev.shape[0], c.n, c.M * c.n, eps_plane is None, offset,
+                                        self.models[0]._x_logvar_value, mode, out, out_stride, strides, c.xk.shape[-1], lay.d,
+                                        lay.L, lay.K, self.params[0, lay.n_params:], c.max_blocks)

@@ -359,6 +359,26 @@ def impute_small_multi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_
                                            stream_ptr()), "vpc_impute_small_multi_f32")
 
 
+def impute_small_multi_aug_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, mode, out,
+                               out_stride, strides, d, d_real, Ld, max_blocks=0):
+    """impute_small_multi_f32 for G Reg_VAE_mask / vanilla_VAE_mask members (the forward of eval_small_multi_aug_f32)."""
+    check(lib().vpc_impute_small_multi_aug_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G,
+                                               ptr(tiles), int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar,
+                                               int(mode), ptr(out), int(out_stride), _member_strides(strides), d, d_real, Ld,
+                                               int(max_blocks), stream_ptr()), "vpc_impute_small_multi_aug_f32")
+
+
+def impute_small_multi_eddi_f32(x, mask, eps, enc_img, dec_img, members, G, tiles, n_tiles, N, R, draw, offset, x_logvar, mode, out,
+                                out_stride, strides, d, d_real, Ld, K, front, max_blocks=0):
+    """impute_small_multi_f32 for G Reg_EDDI / vanilla_EDDI members (the forward of eval_small_multi_eddi_f32: `front` is member
+    0's front-end parameters, member g's strides[MS_PARAM] floats further)."""
+    check(lib().vpc_impute_small_multi_eddi_f32(ptr(x), ptr(mask), ptr(eps), ptr(enc_img), ptr(dec_img), ptr(members), G,
+                                                ptr(tiles), int(n_tiles), int(N), int(R), int(bool(draw)), int(offset), x_logvar,
+                                                int(mode), ptr(out), int(out_stride), _member_strides(strides), d, d_real, Ld,
+                                                int(K), ptr(front), int(max_blocks), stream_ptr()),
+          "vpc_impute_small_multi_eddi_f32")
+
+
 def target_mse_multi(sq, sq_stride, R, G, out, out_stride):
     """out[g * out_stride] = mean of sq[g * sq_stride + 0..R) in fp64, fixed order."""
     check(lib().vpc_target_mse_multi(ptr(sq), int(sq_stride), int(R), G, ptr(out), int(out_stride), stream_ptr()),
@@ -377,6 +397,32 @@ def reward_matrix_multi(x, mask, im, W1, b1, enc_img, pre, stat, w1t, R, G, chun
     check(lib().vpc_reward_matrix_multi(ptr(x), ptr(mask), ptr(im), ptr(W1), ptr(b1), ptr(enc_img), ptr(pre), ptr(stat), ptr(w1t),
                                         ptr(R), G, int(chunk), _member_strides(strides), n, d, Ld, M, stream_ptr()),
           "vpc_reward_matrix_multi")
+
+
+REWARD_DENSE, REWARD_DENSE_MASK, REWARD_POINTNET = range(3)  # first-layer kinds (VPC_REWARD_* of include/vpc.h)
+RM_AC, RM_COUNT_EX = RM_COUNT, RM_COUNT + 1  # the slot reward_matrix_multi_ex reads behind the nine above (VPC_RM_AC)
+
+
+def reward_scratch_multi_ex(kind, n, d, M, K=0):
+    """(pre, stat, w1t) workspace floats PER MEMBER of reward_matrix_multi_ex."""
+    sizes = [C.c_long() for _ in range(3)]
+    check(lib().vpc_reward_scratch_multi_ex(kind, n, d, M, K, *[C.byref(s) for s in sizes]), "vpc_reward_scratch_multi_ex")
+    return tuple(s.value for s in sizes)
+
+
+def reward_matrix_multi_ex(kind, x, mask, im, W1, b1, AC, K, w23, pre, stat, w1t, R, G, chunk, strides, n, d, Ld, M):
+    """vpc_reward_matrix_ex with blockIdx.y = member (REWARD_DENSE_MASK / REWARD_POINTNET); `strides` has RM_COUNT_EX slots."""
+    if len(strides) < RM_COUNT_EX:
+        raise L.VpcError(f"reward_matrix_multi_ex reads {RM_COUNT_EX} member strides, got {len(strides)}")
+    check(lib().vpc_reward_matrix_multi_ex(kind, ptr(x), ptr(mask), ptr(im), ptr(W1), ptr(b1), ptr(AC), int(K), ptr(w23), ptr(pre),
+                                           ptr(stat), ptr(w1t), ptr(R), G, int(chunk), _member_strides(strides), n, d, Ld, M,
+                                           stream_ptr()), "vpc_reward_matrix_multi_ex")
+
+
+def eddi_fold_multi(front, front_stride, AC, AC_stride, G, d, K):
+    """AC[g] [2][K][d] = the fold of member g's front-end (eddi.eddi_fold), read in place from the parameter stack."""
+    check(lib().vpc_eddi_fold_multi(ptr(front), int(front_stride), ptr(AC), int(AC_stride), G, d, K, stream_ptr()),
+          "vpc_eddi_fold_multi")
 
 
 def acquire_multi(R, R_stride, mask, mask_stride, mask_pitch, mask2, mask2_stride, mask2_pitch, action, action_stride,
