@@ -227,6 +227,27 @@ int vpc_draw_step(const uint8_t* mask_in, uint8_t* mask_out, long n_mask, float 
 int vpc_fill_normal(float* out, long n, unsigned long long seed, unsigned long long offset, const long long* state,
                     long rows_local, long rows_global, long row_lo, int pitch, void* stream);
 
+/* The row-tiled fp32 step (8-wave kernels: d in (64, 128], d % 8 == 0, x 16-byte aligned, masks 4-byte aligned) with
+ * vpc_draw_step's two draws made by the kernels that consume them - same counters, same values, one launch less.  Both run
+ * the throughput shape (128-row tiles) at every B.
+ * vpc_encoder_fwd_draw_f32 = vpc_draw_mask + vpc_encoder_fwd(npass 2, lat_pitch 16, precision 0): pass 0 runs on mask_in,
+ * pass 1 on mask_p = mask_in AND (U < keep_prob), which the kernel draws for the mask words it holds (seed, offset_mask,
+ * state, mask_elem_lo as vpc_draw_step; mask_elem_lo % 8 == 0) and stores to mask_p_out [B][d].
+ * vpc_decoder_fused_draw_f32 = vpc_fill_normal + vpc_decoder_fused(lat_pitch 16, precision 0, wml == 0): eps[p] [B][16] is
+ * WRITTEN - the lane that forms z draws its four values (seed, offset_eps, state as vpc_draw_step; eps[p] is plane p, rows
+ * [eps_row_lo, eps_row_lo + B), of a global [npass][eps_rows_global][16] array) - and read back at the end of the pass. */
+int vpc_encoder_fwd_draw_f32(const float* x, const float* enc_img, const uint8_t* mask_in, uint8_t* mask_p_out,
+                             float* const* h1, float* const* h2, float* const* mean, float* const* logvar, long B, int d,
+                             int L, float keep_prob, unsigned long long seed, unsigned long long offset_mask,
+                             const long long* state, long mask_elem_lo, void* stream);
+int vpc_decoder_fused_draw_f32(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                               const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                               const float* const* logvar, float* const* eps, float inv_B, float x_logvar,
+                               float* const* dmean, float* const* dlogvar, float* partials, double* loss_partials,
+                               int* nblocks_out, long B, int d, int L, unsigned long long seed,
+                               unsigned long long offset_eps, const long long* state, long eps_rows_global, long eps_row_lo,
+                               void* stream);
+
 /* ---- data parallel: the step's ONE collective on the caller's stream (RCCL over xGMI) -------
  * The reference has no distributed code; these entry points exist so that the flat bucket [gradients | loss terms]
  * (37 548 + 9 floats) is all-reduced as an ordinary node of the compute stream - no hop to a communication stream,

@@ -716,12 +716,15 @@ extern "C" int vpc_decoder_bwd(const float* z, const float* dxhat, const float* 
     return dispatch<MODE_BWD>(a, vec, ts, (hipStream_t)stream);
 }
 
-extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
-                                 const uint8_t* const* maskB, const VpcLossCoef* co,
-                                 const float* const* mean, const float* const* logvar, const float* const* eps,
-                                 const float* eps_ml, float inv_B, float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
-                                 int precision, float* partials, double* loss_partials, int* nblocks_out, long B, int d,
-                                 int L, void* stream) {
+// the in-kernel eps draw of vpc_decoder_fused_draw_f32 (NULL: vpc_decoder_fused, eps is read)
+struct EpsDraw { unsigned long long seed, offset; const long long* state; long rows_global, row_lo; };
+
+static int decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                         const uint8_t* const* maskB, const VpcLossCoef* co,
+                         const float* const* mean, const float* const* logvar, const float* const* eps,
+                         const float* eps_ml, float inv_B, float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
+                         int precision, float* partials, double* loss_partials, int* nblocks_out, long B, int d,
+                         int L, void* stream, const EpsDraw* dr) {
     if (!x || !dec_img || !maskA || !co || !mean || !logvar || !dmean || !dlogvar || !partials ||
         !loss_partials)
         return VPC_ERR_ARG;
@@ -732,7 +735,7 @@ extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass
     a.inv_B = inv_B; a.x_logvar = x_logvar;
     if (lat_pitch != 16) return VPC_ERR_ARG;  // the fused kernel works on padded [B][16] latent workspaces only
     a.B = B; a.d = d; a.L = L; a.npass = npass; a.lp = lat_pitch;
-    const TileShape ts = tile_shape(B, npass);
+    const TileShape ts = tile_shape(B, npass, dr != nullptr);  // the drawing kernel exists in the throughput shape only
     a.ntiles = ts.ntiles; a.psplit = ts.small;
 #ifdef VPC_ABLATE
     if (const char* e = getenv("VPC_DEBUG")) a.dbg = atoi(e);
@@ -748,6 +751,19 @@ extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass
     set_loss_coef(a, *co, npass);
     if (a.wml != 0.f && !eps_ml) return VPC_ERR_ARG;
     if (nblocks_out) *nblocks_out = ts.nblocks;
+    if (dr) {
+        // fp32 8-wave kernel, vector layout, every consumed eps plane drawn (no ml_reg sample: that is a third plane)
+        if (precision != 0 || !vec || dt_for(d) != 8) return VPC_ERR_SHAPE;
+        DecDraw dd{};
+        if (!eps || a.wml != 0.f || dr->row_lo < 0 || dr->row_lo + B > dr->rows_global) return VPC_ERR_ARG;
+        for (int p = 0; p < npass; ++p) {
+            if (!eps[p] || !aligned16(eps[p])) return VPC_ERR_ARG;
+            dd.eps_w[p] = const_cast<float*>(eps[p]);
+        }
+        dd.seed = dr->seed; dd.off_eps = dr->offset; dd.state = dr->state;
+        dd.eps_rows_global = dr->rows_global; dd.eps_row_lo = dr->row_lo;
+        return dec8_draw_dispatch(a, dd, ts.grid_x, (hipStream_t)stream);
+    }
     // throughput shape, d in (64, 128]: the 8-wave / one-tile-per-wave kernel (vpc_dec8.hip); VPC_DEC8=0 selects the
     // 4-wave / two-tiles-per-wave kernel of this file instead (same arguments, same partial-block layout; kept for A/B
     // runs and for d <= 64).  Small-batch shape: always the 4-wave kernel with one tile per wave.
@@ -759,4 +775,27 @@ extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass
     }
     if (vec && !ts.small && dt_for(d) == 8 && !(e8 && atoi(e8) == 0)) return dec8_dispatch(a, vec, ts.grid_x, 0, (hipStream_t)stream);
     return dispatch<MODE_FUSED>(a, vec, ts, (hipStream_t)stream);
+}
+
+extern "C" int vpc_decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                                 const uint8_t* const* maskB, const VpcLossCoef* co,
+                                 const float* const* mean, const float* const* logvar, const float* const* eps,
+                                 const float* eps_ml, float inv_B, float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
+                                 int precision, float* partials, double* loss_partials, int* nblocks_out, long B, int d,
+                                 int L, void* stream) {
+    return decoder_fused(x, dec_img, npass, maskA, maskB, co, mean, logvar, eps, eps_ml, inv_B, x_logvar, dmean, dlogvar, lat_pitch,
+                         precision, partials, loss_partials, nblocks_out, B, d, L, stream, nullptr);
+}
+
+// vpc_fill_normal + vpc_decoder_fused (fp32, 8-wave row-tiled kernel) in ONE launch: see include/vpc.h
+extern "C" int vpc_decoder_fused_draw_f32(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                                          const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                                          const float* const* logvar, float* const* eps, float inv_B, float x_logvar,
+                                          float* const* dmean, float* const* dlogvar, float* partials, double* loss_partials,
+                                          int* nblocks_out, long B, int d, int L, unsigned long long seed,
+                                          unsigned long long offset_eps, const long long* state, long eps_rows_global,
+                                          long eps_row_lo, void* stream) {
+    const EpsDraw dr{seed, offset_eps, state, eps_rows_global, eps_row_lo};
+    return decoder_fused(x, dec_img, npass, maskA, maskB, co, mean, logvar, eps, nullptr, inv_B, x_logvar, dmean, dlogvar, 16, 0,
+                         partials, loss_partials, nblocks_out, B, d, L, stream, &dr);
 }

@@ -34,6 +34,17 @@ struct DecArgs {
     int dbg;  // ablation mask, only honoured by the diagnostic build (-DVPC_ABLATE); 0 in the product build
 };
 
+// In-kernel eps draw, the second argument of dec8_draw_kernel (a record of its own: DecArgs keeps its size, and with it the
+// kernel-argument offsets in every other decoder kernel): the lane that forms z draws its eps group with vpc_draw_step's
+// counter and stores it to eps_w[p] (the same array as DecArgs::eps[p]), where the pass end, dump and the draw-rule checks
+// read it
+struct DecDraw {
+    float* eps_w[2];
+    unsigned long long seed, off_eps;
+    const long long* state;          // graph replay: state[1] is added to off_eps
+    long eps_rows_global, eps_row_lo;  // row shard of the global [planes][rows_global][16] eps array (B rows from eps_row_lo)
+};
+
 constexpr int DEC_CH = 64;  // batch rows per wgrad staging chunk
 
 // VPC_DBG(bit) guards the ablation switches of the diagnostic build (tools/ablate.sh).  In the product build it
@@ -59,5 +70,6 @@ __device__ __forceinline__ int opaque_zero() {
 
 size_t dec8_lds(int DT, int prec);
 int dec8_dispatch(const DecArgs& a, bool vec, int grid, int prec, hipStream_t s);
+int dec8_draw_dispatch(const DecArgs& a, const DecDraw& dr, int grid, hipStream_t s);  // fp32, vector layout, the eps draw inside (vpc_dec8.hip)
 
 }  // namespace vpc

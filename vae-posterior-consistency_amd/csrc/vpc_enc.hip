@@ -6,6 +6,7 @@
 #include "vpc_device.h"
 #include "vpc_bf16.h"
 #include "vpc_abi_internal.h"
+#include "vpc_rng.h"
 
 namespace vpc {
 
@@ -44,6 +45,16 @@ struct EncFwdArgs {
     int d, L, npass, ntiles, lp;
     int psplit;  // 1: the passes are spread over blockIdx.y (small batches), 0: every workgroup loops over them
 };
+// In-kernel mask_p draw, the second argument of enc_fwd_draw_kernel (a record of its own: EncFwdArgs keeps its size, and with
+// it the kernel-argument offsets in every other instantiation): pass 1 runs on mask[0] & keep, drawn with vpc_draw_step's
+// counters, and stores those bytes to mask_out (= mask[1], which is not read)
+struct EncDraw {
+    uint8_t* mask_out;
+    float keep_prob;
+    unsigned long long seed, off_mask;
+    const long long* state;  // graph replay: state[1] is added to off_mask
+    long elem_lo;            // index of this shard's first mask element in the global array (row_lo * d)
+};
 
 // NW = waves per workgroup = 16-row batch tiles per workgroup iteration.  8 (two waves per SIMD, 128-row tiles): the
 // throughput shape.  4 (one wave per SIMD, 64-row tiles, passes spread over blockIdx.y): the small-batch shape - a batch
@@ -51,172 +62,24 @@ struct EncFwdArgs {
 // workgroups that each run two passes with two waves per SIMD (the step is latency-bound there, profiles/r01_notes.md).
 // PREC (vpc_bf16.h): PREC_F32 = v_mfma_f32_16x16x4_f32 on the fp32 image; PREC_BF16X3 / PREC_BF16 = v_mfma_f32_16x16x32_bf16
 // on the bf16 image (same geometry: same row pitches, b1 stays fp32), activations converted tile pair by tile pair.
+// DRAW (the 8-wave fp32 PIPE form, two passes in one workgroup): pass 1's mask is not fetched but drawn - the mask words of
+// pass 0 stay in their registers (where the prefetched words of pass 1 would sit), and at the head of pass 1 the wave draws
+// the keep bits of exactly those bytes (counter rule of draw_mask_body, lane mapping of vpc_rng.h: mask_lane_group /
+// mask_lane_call_tile), ANDs them in and stores the mask_p bytes for the decoder and the backward kernel.  Per lane and tile
+// FOUR Philox calls: lanes q and q ^ 1 hold the two halves of every group, each makes the call of one tile of a tile pair
+// and the two words the other needs cross with a 16-lane swap (ds_swizzle, no LDS memory).
 template <int DT, bool VEC, bool AUG, int NW, int PREC = PREC_F32>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_fwd_kernel(EncFwdArgs a) {
-    constexpr int TILE_ROWS = 16 * NW;  // shadows vpc::TILE_ROWS (the 8-wave value)
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-#ifdef VPC_ABLATE
-    unsigned long long T[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tlast = __builtin_amdgcn_s_memtime();
-    const unsigned long long t_begin = tlast, r_begin = __builtin_amdgcn_s_memrealtime();
-#endif
-    constexpr int S1 = s_for_tiles(DT);
-    const EncImg im(DT);
-    const float* W1 = lds + im.oW1;
-    const float* b1 = lds + im.ob1;
-    const float* W2 = lds + im.oW2;
-    const float* W3 = lds + im.oW3;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-
-    // PIPE (the vectorised fast path): x is read once per tile (both passes see the same rows, only the mask differs)
-    // and the mask words of the next pass - or x and the mask words of the next tile - are requested before this
-    // pass's MFMAs, with branch-free loads (rows past B read row 0 and are never stored; columns past d are cleared).
-    constexpr bool PIPE = VEC && !AUG;
-    f32x4 xraw[DT];
-    uint32_t mw[DT];
-    const int cq = (4 * q + 3 < a.d) ? 4 * q : 0;
-    // range-checked buffer loads relative to a tile's first row t0 (rows past B read 0)
-    const int vo = (w * 16 + c) * a.d + cq;  // element offset of this lane's row / column group inside the tile's rows
-    auto fetch_x = [&](long t0) {
-        const __amdgpu_buffer_rsrc_t rx = rows_rsrc(a.x, t0, a.B, a.d);
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-            xraw[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rx, 4 * (vo + ((t < DT / 2 || 16 * t + 4 * q + 3 < a.d) ? 16 * t : 0)), 0, 0));
-    };
-    auto fetch_m = [&](const uint8_t* m, long t0) {
-        const long rem = (a.B - t0) * (long)a.d;
-        const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(m) + t0 * a.d, 0, rem > 0xffffffffL ? 0xffffffffu : (uint32_t)rem, 0x00020000);
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-            mw[t] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
-                rm, vo + ((t < DT / 2 || 16 * t + 4 * q + 3 < a.d) ? 16 * t : 0), 0, 0);
-    };
-    const int p_lo = a.psplit ? (int)blockIdx.y : 0, p_hi = a.psplit ? p_lo + 1 : a.npass;
-    // the first tile's x / mask words are requested BEFORE the weight image: both latencies overlap
-    if (PIPE && (int)blockIdx.x < a.ntiles) {
-        fetch_x((long)blockIdx.x * TILE_ROWS);
-        fetch_m(a.mask[p_lo], (long)blockIdx.x * TILE_ROWS);
-    }
-    load_image<(NW == 8 ? 13 : 25)>(lds, a.img, im.total);
-    __syncthreads();
-    VPC_STAMP(0);
-
-    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const long row = (long)tile * TILE_ROWS + w * 16 + c;
-        const bool ok = row < a.B;
-        for (int p = p_lo; p < p_hi; ++p) {
-            // the weight image never changes after the prologue: without this compiler barrier LICM hoists
-            // every LDS weight read out of the pass loop and spills ~1 KB/lane of it to scratch
-            asm volatile("" ::: "memory");
-            int cc = c, qq = q;
-            launder(cc, qq);
-            // workspace stores go through range-checked buffer descriptors (rows past B are dropped by the hardware)
-            const long row0 = (long)tile * TILE_ROWS;
-            const int lrow = w * 16 + c;
-            const __amdgpu_buffer_rsrc_t rh1 = rows_rsrc(a.h1[p], row0, a.B, H1P), rh2 = rows_rsrc(a.h2[p], row0, a.B, H2P);
-            f32x4 xin[DT];
-            if (PIPE) {
-#pragma unroll
-                for (int t = 0; t < DT; ++t) {
-                    const uint32_t vm = opaque_mask(t < DT / 2 || 16 * t + 4 * q + 3 < a.d);
-                    xin[t] = xraw[t] * mask_to_f32(mw[t] & vm);  // x.float() * mask  (VAE.py:388)
-                }
-                if (p + 1 < p_hi) {
-                    fetch_m(a.mask[p + 1], row0);
-                } else if (tile + (int)gridDim.x < a.ntiles) {
-                    const long tn = row0 + (long)gridDim.x * TILE_ROWS;
-                    fetch_x(tn);
-                    fetch_m(a.mask[p_lo], tn);
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < DT; ++t) xin[t] = ld_input<VEC, AUG>(a.x, a.mask[p], row, a.d, t, q, ok);
-            }
-            VPC_STAMP(1);
-            f32x4 h1[H1T], h2[H2T], mu, lv;
-            if (PREC == PREC_F32) {
-#pragma unroll
-                for (int mt = 0; mt < H1T; ++mt) {
-                    f32x4 acc = *reinterpret_cast<const f32x4*>(b1 + 16 * mt + 4 * q);
-                    acc = tile_fwd<DT, S1>(W1, mt, xin, acc, cc, qq);
-                    h1[mt] = relu4(acc);
-                    st_rows(rh1, lrow, H1P, 16 * mt + 4 * q, h1[mt]);
-                }
-                VPC_STAMP(2);
-                launder(cc, qq);
-#pragma unroll
-                for (int mt = 0; mt < H2T; ++mt) {
-                    h2[mt] = relu4(tile_fwd<H1T, 128, NK1>(W2, mt, h1, zero4(), cc, qq));
-                    st_rows(rh2, lrow, H2P, 16 * mt + 4 * q, h2[mt]);
-                }
-                VPC_STAMP(3);
-                mu = tile_fwd<H2T, 64, NK2>(W3, 0, h2, zero4(), cc, qq);
-                lv = tile_fwd<H2T, 64, NK2>(W3, 1, h2, zero4(), cc, qq);
-            } else {
-                constexpr int KB1 = (DT + 1) / 2;
-                BfOp xb[KB1];
-                bf_acts<PREC, DT>(xin, xb);
-                // (fragments of tile mt + 1 in flight during tile mt: vpc_bf16.h, bf_layer_fwd)
-                // plain bf16: the h1 / h2 workspaces hold the PACKED operands (what the backward kernel's MFMAs consume
-                // anyway): rows of [k-block][q][8 x bf16], 256 / 128 bytes per row inside the same allocation - half the
-                // bytes of the fp32 rows in both directions (enc_fwd is HBM-bound in this form)
-                constexpr bool HPK = PREC == PREC_BF16;
-                bf_layer_fwd<PREC, KB1, S1, H1T, PREC == PREC_BF16 ? KB1 : (KB1 < 2 ? KB1 : 2)>(W1, xb, cc, qq, [&](int mt, f32x4 acc) {
-                    h1[mt] = relu4(acc + *reinterpret_cast<const f32x4*>(b1 + 16 * mt + 4 * q));
-                    if (!HPK) st_rows(rh1, lrow, H1P, 16 * mt + 4 * q, h1[mt]);
-                });
-                VPC_STAMP(2);
-                launder(cc, qq);
-                BfOp h1b[4];
-                bf_acts<PREC, H1T>(h1, h1b);
-                if (HPK) {
-                    const __amdgpu_buffer_rsrc_t rp = rows_rsrc(a.h1[p], row0, a.B, 64);
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) st_rows(rp, lrow, 64, 16 * kb + 4 * q, __builtin_bit_cast(f32x4, h1b[kb].hi));
-                }
-                bf_layer_fwd<PREC, 4, 128, H2T, PREC == PREC_BF16 ? 4 : 2>(W2, h1b, cc, qq, [&](int mt, f32x4 acc) {
-                    h2[mt] = relu4(acc);
-                    if (!HPK) st_rows(rh2, lrow, H2P, 16 * mt + 4 * q, h2[mt]);
-                });
-                VPC_STAMP(3);
-                BfOp h2b[2];
-                bf_acts<PREC, H2T>(h2, h2b);
-                if (HPK) {
-                    const __amdgpu_buffer_rsrc_t rp = rows_rsrc(a.h2[p], row0, a.B, 32);
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) st_rows(rp, lrow, 32, 16 * kb + 4 * q, __builtin_bit_cast(f32x4, h2b[kb].hi));
-                }
-                mu = bf_tile_fwd<PREC, 2, 64>(W3, 0, h2b, zero4(), cc, qq);
-                lv = bf_tile_fwd<PREC, 2, 64>(W3, 1, h2b, zero4(), cc, qq);
-            }
-            if (a.lp == 16) {  // padded workspaces: rows are 16 floats, features >= L are exact zeros
-                st_rows(rows_rsrc(a.mean[p], row0, a.B, 16), lrow, 16, 4 * q, mu);
-                st_rows(rows_rsrc(a.logvar[p], row0, a.B, 16), lrow, 16, 4 * q, lv);
-            } else {
-                st_tile<false>(a.mean[p], row, a.L, 4 * q, a.L, ok, mu);
-                st_tile<false>(a.logvar[p], row, a.L, 4 * q, a.L, ok, lv);
-            }
-            if (a.z[p]) {
-                f32x4 z = mu;
-                if (a.eps[p]) {
-                    const f32x4 e = ld_tile<false>(a.eps[p], row, a.L, 4 * q, a.L, ok);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) z[j] = mu[j] + e[j] * expf(lv[j] * 0.5f);  // rsample
-                }
-                st_tile<false>(a.z[p], row, a.L, 4 * q, a.L, ok, z);
-            }
-            VPC_STAMP(4);
-        }
-    }
-#ifdef VPC_ABLATE
-    if ((blockIdx.x == 0 || blockIdx.x == 100) && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < 2)
-        printf("enc_fwd blk %d wave %d cycles: prologue %llu loadx %llu L1 %llu L2 %llu L3+st %llu | total %llu cycles in %llu x 10 ns\n",
-               blockIdx.x, (int)(threadIdx.x >> 6), T[0], T[1], T[2], T[3], T[4],
-               (unsigned long long)(__builtin_amdgcn_s_memtime() - t_begin),
-               (unsigned long long)(__builtin_amdgcn_s_memrealtime() - r_begin));
-#endif
+    constexpr bool DRAW = false;
+    const EncDraw dr{};
+#include "vpc_enc_fwd_body.h"
+}
+// the 8-wave fp32 kernel with the mask_p draw inside (vpc_encoder_fwd_draw_f32)
+template <int DT>
+__global__ __launch_bounds__(512, 2) void enc_fwd_draw_kernel(EncFwdArgs a, EncDraw dr) {
+    constexpr bool VEC = true, AUG = false, DRAW = true;
+    constexpr int NW = 8, PREC = PREC_F32;
+#include "vpc_enc_fwd_body.h"
 }
 
 struct EncBwdArgs {
@@ -757,6 +620,35 @@ extern "C" int vpc_encoder_fwd(const float* x, const float* enc_img, int npass, 
 #undef VPC_CASE
 #undef VPC_LAUNCH
     return VPC_ERR_SHAPE;
+}
+
+// vpc_draw_mask + vpc_encoder_fwd (two passes, fp32, 8-wave row-tiled kernel, padded latent workspaces) in ONE launch: see
+// include/vpc.h
+extern "C" int vpc_encoder_fwd_draw_f32(const float* x, const float* enc_img, const uint8_t* mask_in, uint8_t* mask_p_out,
+                                        float* const* h1, float* const* h2, float* const* mean, float* const* logvar, long B,
+                                        int d, int L, float keep_prob, unsigned long long seed, unsigned long long offset_mask,
+                                        const long long* state, long mask_elem_lo, void* stream) {
+    if (!x || !enc_img || !mask_in || !mask_p_out || !h1 || !h2 || !mean || !logvar || B <= 0 || mask_elem_lo < 0) return VPC_ERR_ARG;
+    if (d < 1 || d > MAX_D || L < 1 || L > MAX_L) return VPC_ERR_SHAPE;
+    // a Philox group is 8 consecutive bytes: the lanes' mapping needs rows and the shard to start on a group boundary, and
+    // the kernel exists for the 16-byte-vector layout with 8 column tiles
+    if (d % 8 != 0 || mask_elem_lo % 8 != 0 || dt_for(d) != 8 || !aligned16(x) || (uintptr_t)mask_in % 4 || (uintptr_t)mask_p_out % 4)
+        return VPC_ERR_SHAPE;
+    EncFwdArgs a{};
+    a.x = x; a.img = enc_img; a.B = B; a.d = d; a.L = L; a.npass = 2; a.lp = 16;
+    const TileShape ts = tile_shape(B, 2, true);  // the drawing kernel exists in the throughput shape only
+    a.ntiles = ts.ntiles; a.psplit = 0;
+    for (int p = 0; p < 2; ++p) {
+        if (!h1[p] || !h2[p] || !mean[p] || !logvar[p] || !aligned16(h1[p]) || !aligned16(h2[p])) return VPC_ERR_ARG;
+        a.h1[p] = h1[p]; a.h2[p] = h2[p]; a.mean[p] = mean[p]; a.logvar[p] = logvar[p];
+    }
+    a.mask[0] = mask_in; a.mask[1] = mask_p_out;
+    const EncDraw dr{mask_p_out, keep_prob, seed, offset_mask, state, mask_elem_lo};
+    auto kern = enc_fwd_draw_kernel<8>;
+    const size_t lds = enc_fwd_lds(8);
+    if (!lds_attr_done(reinterpret_cast<const void*>(kern), lds)) return VPC_ERR_HIP;
+    hipLaunchKernelGGL(kern, dim3(ts.grid_x), dim3(512), lds, (hipStream_t)stream, a, dr);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
 extern "C" int vpc_encoder_bwd(const float* x, const float* enc_img, int npass, const uint8_t* const* mask,

@@ -1,8 +1,53 @@
-// Philox counter RNG and the two per-step draws of the fused steps (device code shared by vpc_misc.hip - the draw kernels - and
-// vpc_small.hip, whose small-batch step kernel draws its own tile's mask_p and eps: same counters, same values).
+// Philox counter RNG and the two per-step draws of the fused steps (device code shared by vpc_misc.hip - the draw kernels -,
+// vpc_small.hip, whose small-batch step kernel draws its own tile's mask_p and eps, and the row-tiled fp32 step's in-kernel draws:
+// enc_fwd_draw_kernel in vpc_enc.hip draws mask_p for the mask words it holds, dec8_draw_kernel in vpc_dec8.hip the eps of the
+// lane that forms z: same counters, same values).
+// The counter arithmetic of a lane (the first part of this file) is plain C++ and also compiles in a host program.
 #pragma once
+#ifdef __HIPCC__
 #include "vpc_device.h"
+#define VPC_RNG_HD __host__ __device__ __forceinline__
+#else
+#include <cstdint>
+#define VPC_RNG_HD inline
+#endif
 
+namespace vpc {
+
+// Row-sharded normal draws: `out` is [planes][rows_local][pitch] (pitch % 4 == 0), the local shard of a global
+// [planes][rows_global][pitch] array starting at row row_lo; the Philox counter of a 4-float group is its GLOBAL group
+// index + offset, so every row gets the same eps whatever the sharding.  rows_local == 0: flat array, counter = g + offset.
+struct EpsShard { long rows_local, rows_global, row_lo; int pitch; };
+VPC_RNG_HD uint64_t eps_counter(const EpsShard& sh, long g) {
+    if (sh.rows_local == 0) return (uint64_t)g;
+    const long gpr = sh.pitch >> 2, gpp = sh.rows_local * gpr;  // groups per row / per local plane
+    const long k = g / gpp, rem = g - k * gpp;
+    return (uint64_t)((k * sh.rows_global + sh.row_lo) * gpr + rem);
+}
+
+// ---- in-kernel draws of the row-tiled step: which counters belong to a lane.  Lane (q, c) of wave w holds, of LOCAL row
+// `row` (= 128 tile + 16 w + c) and column tile t, the four mask bytes of columns 16 t + 4 q .. + 3, and forms z[row][4 q .. 4 q + 3].
+// mask_p (draw_mask_body): element i of the local [rows][dk] array is element elem_lo + i of the global one, its Philox group is
+// that index / 8 and its 16-bit half that index % 8.  With dk % 8 == 0 and elem_lo = row_lo * dk no group straddles a row: the
+// lane's four bytes are halves mask_lane_half0(q) .. + 3 of group mask_lane_group(...), i.e. the two words 2 (q & 1), 2 (q & 1) + 1
+// of that call, and lanes q and q ^ 1 (same row) share the group.
+VPC_RNG_HD long mask_lane_group(long elem_lo, long row, int dk, int t, int q) {
+    return ((elem_lo + row * (long)dk) >> 3) + 2 * t + (q >> 1);
+}
+VPC_RNG_HD int mask_lane_half0(int q) { return 4 * (q & 1); }
+// The two lanes of a group split the calls of a tile PAIR (2 u, 2 u + 1): lane q makes the call of tile mask_lane_call_tile(u, q)
+// and hands the two words it does not use itself to lane q ^ 1, which needs exactly those (4 calls per lane and 8 tiles, not 8).
+VPC_RNG_HD int mask_lane_call_tile(int u, int q) { return 2 * u + (q & 1); }
+// eps: the counter (before the offset) of the group z[row][4 q .. 4 q + 3] of plane `plane`: eps_counter of its group index in
+// the local [planes][rows_local][pitch] array, without the division.
+VPC_RNG_HD uint64_t eps_lane_counter(const EpsShard& sh, int plane, long row, int q) {
+    const long gpr = sh.pitch >> 2;
+    return (uint64_t)(((long)plane * sh.rows_global + sh.row_lo + row) * gpr + q);
+}
+
+}  // namespace vpc
+
+#ifdef __HIPCC__
 namespace vpc {
 
 // Philox4x32-10 counter RNG
@@ -57,15 +102,12 @@ __device__ __forceinline__ void draw_mask_body(const uint8_t* __restrict__ in, u
     }
 }
 
-// Row-sharded normal draws: `out` is [planes][rows_local][pitch] (pitch % 4 == 0), the local shard of a global
-// [planes][rows_global][pitch] array starting at row row_lo; the Philox counter of a 4-float group is its GLOBAL group
-// index + offset, so every row gets the same eps whatever the sharding.  rows_local == 0: flat array, counter = g + offset.
-struct EpsShard { long rows_local, rows_global, row_lo; int pitch; };
-__device__ __forceinline__ uint64_t eps_counter(const EpsShard& sh, long g) {
-    if (sh.rows_local == 0) return (uint64_t)g;
-    const long gpr = sh.pitch >> 2, gpp = sh.rows_local * gpr;  // groups per row / per local plane
-    const long k = g / gpp, rem = g - k * gpp;
-    return (uint64_t)((k * sh.rows_global + sh.row_lo) * gpr + rem);
+// The keep bits of four consecutive mask bytes from the two Philox words that hold their 16-bit halves (low half first, as
+// draw_mask_body numbers them): 0x01 in byte k when half k < thr.  mask & keep_bits4 is draw_mask_body's output for 0 / 1 mask bytes.
+__device__ __forceinline__ uint32_t mask_thr(float keep_prob) { return (uint32_t)(keep_prob * 65536.f + 0.5f); }
+__device__ __forceinline__ uint32_t keep_bits4(uint32_t w0, uint32_t w1, uint32_t thr) {
+    return ((w0 & 0xffffu) < thr ? 1u : 0u) | ((w0 >> 16) < thr ? 0x100u : 0u) | ((w1 & 0xffffu) < thr ? 0x10000u : 0u) |
+           ((w1 >> 16) < thr ? 0x1000000u : 0u);
 }
 
 __device__ __forceinline__ void fill_normal_body(float* __restrict__ out, long n, uint64_t seed, uint64_t offset,
@@ -120,3 +162,4 @@ __device__ __forceinline__ float ais_uniform(long chain, int j, uint64_t seed) {
 }
 
 }  // namespace vpc
+#endif  // __HIPCC__

@@ -3,7 +3,10 @@ src/experiment_main/train.py:53-117 for Reg_VAE / vanilla_VAE:
 
     mask_p draw -> forward (2 x encoder, 2 x decoder) -> loss -> zero_grad -> backward -> Adam -> loss accumulate
 
-as 5 kernel launches (6 under data parallelism) and no B x d intermediate:
+as 5 kernel launches (6 under data parallelism) and no B x d intermediate - 4 (5) on the fp32 row-tiled path at batches
+that give every CU a 128-row tile, where the two draws are made by the kernels that consume them
+(vpc_encoder_fwd_draw_f32 draws mask_p for the mask words it holds, vpc_decoder_fused_draw_f32 the eps of the lane that
+forms z; FusedTrainer._draw_fused says when):
 
     vpc_draw_step            mask_p = mask & Bernoulli(1 - p_missingness/100) and eps_q, eps_p (, eps_ml), Philox
                              counters keyed by the GLOBAL row                        (train.py:53-55, VAE.py:389-392)
@@ -21,6 +24,8 @@ Gradients are those of the GLOBAL mean loss: seeds carry 1/B_global, so summing 
 exactly `train_loss = loss / x.shape[0]` (VAE.py:452) on the concatenated batch.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -85,6 +90,7 @@ class FusedTrainer(_FlatAdamTrainer):
                                           lambda flat, buf: ops.step_pack_weights_bf16(flat, pidx_c, buf))
         self.out9 = self.tail  # the loss terms of the step
         ncu = L.max_blocks()  # partial blocks any kernel may write (2 x CUs: small-batch shape)
+        self._draw_fused_rows = 64 * ncu  # 128 rows x CUs: from here on the row-tiled fp32 step draws in its kernels (_draw_fused)
         self.partE = torch.empty(ncu * self.lay.enc_part, device=self.dev)
         self.partD = torch.empty(ncu * self.lay.dec_part, device=self.dev)
         self.loss_part = torch.empty(ncu, 8, dtype=torch.float64, device=self.dev)
@@ -185,6 +191,19 @@ class FusedTrainer(_FlatAdamTrainer):
         # ---- flat gradient + loss terms, Adam
         self._tail(co, key, img, imgs[0] if use_step else None, nbE, nbD, B, Bg, update, _state, self.rng_offset - rng0)
 
+    def _draw_fused(self, B, dk, planes, all_drawn):
+        """Whether the row-tiled step makes its draws inside encoder_fwd / decoder_fused (one launch less, the mask read once
+        less): fp32, the 8-wave kernels (plain encoder, dk in (64, 128], VPC_DEC8 / VPC_TILE not selecting the other shape),
+        no Philox group straddling a row (dk % 8 == 0), padded latent rows, every draw made on the device, at most two eps
+        planes (the ml_reg sample is a third), and a batch that gives every CU a 128-row tile - below it the separate launch
+        stays.  VPC_DRAW_FUSED=0 keeps the separate launch, =1 takes the in-kernel draws at any batch size (tests, A/B runs)."""
+        env = os.environ.get("VPC_DRAW_FUSED", "")
+        if env == "0" or self.prec or self.lay.mask_augm or not (64 < dk <= 128) or dk % 8 or LP != 16:
+            return False
+        if not all_drawn or planes > 2 or os.environ.get("VPC_DEC8") == "0" or os.environ.get("VPC_TILE") == "64":
+            return False
+        return env == "1" or B >= self._draw_fused_rows
+
     def _draws(self, co, mask, mask_p, eps_in, B, Bg, row_lo, dk, use_small, keep_prob, _state):
         """The step's draws - mask_p into mask_p_buf, eps into eps_buf - on the device unless injected, at the counters of
         trainer.draw_counters (mask_p and eps in ONE launch when both are drawn).  All planes are drawn if any consumed
@@ -201,6 +220,10 @@ class FusedTrainer(_FlatAdamTrainer):
         if use_small and draw_mask == two and all(e is None for e in eps_in) and LP == 16:
             # small batches: the N-split kernel makes the step's draws itself (same counters, one launch less) when ALL of
             # them are drawn on the device
+            in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, _state,
+                         dr.elem_lo, dr.eps_shard)
+        elif not use_small and self._draw_fused(B, dk, planes, draw_mask == two and all(e is None for e in eps_in)):
+            # row-tiled fp32 step: encoder_fwd draws mask_p, decoder_fused draws eps (same counters; _launches)
             in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, _state,
                          dr.elem_lo, dr.eps_shard)
         elif draw_mask and draw_eps:
@@ -246,10 +269,23 @@ class FusedTrainer(_FlatAdamTrainer):
             return nb, nb
         # forward (encoder), fused decoder + loss + decoder backward, encoder backward
         enc_img, dec_img = imgs
-        self._timed("encoder_fwd", ops.encoder_fwd, x, enc_img, masks, None, self.h1, self.h2, self.mean, self.logvar,
-                    None, dk, Ld, LP, lay.mask_augm, self.prec)
-        nbD = self._timed("decoder_fused", ops.decoder_fused, x, dec_img, masks, maskB, co, self.mean, self.logvar, epss,
-                          eml, inv_B, xlv, self.dmean, self.dlogvar, self.partD, self.loss_part, dk, Ld, LP, self.prec)
+        if in_kernel is not None:
+            # the draws inside the two kernels that consume them (_draw_fused); vanilla_VAE has no mask_p: plain encoder_fwd
+            mask_in, keep_prob, _, seed, off_mask, off_eps, state, elem_lo, eps_shard = in_kernel
+            if two:
+                self._timed("encoder_fwd", ops.encoder_fwd_draw_f32, x, enc_img, mask_in, self.mask_p_buf, self.h1, self.h2,
+                            self.mean, self.logvar, dk, Ld, keep_prob, seed, off_mask, state, elem_lo)
+            else:
+                self._timed("encoder_fwd", ops.encoder_fwd, x, enc_img, masks, None, self.h1, self.h2, self.mean,
+                            self.logvar, None, dk, Ld, LP, lay.mask_augm, self.prec)
+            nbD = self._timed("decoder_fused", ops.decoder_fused_draw_f32, x, dec_img, masks, maskB, co, self.mean,
+                              self.logvar, epss, inv_B, xlv, self.dmean, self.dlogvar, self.partD, self.loss_part, dk, Ld,
+                              seed, off_eps, state, eps_shard)
+        else:
+            self._timed("encoder_fwd", ops.encoder_fwd, x, enc_img, masks, None, self.h1, self.h2, self.mean, self.logvar,
+                        None, dk, Ld, LP, lay.mask_augm, self.prec)
+            nbD = self._timed("decoder_fused", ops.decoder_fused, x, dec_img, masks, maskB, co, self.mean, self.logvar, epss,
+                              eml, inv_B, xlv, self.dmean, self.dlogvar, self.partD, self.loss_part, dk, Ld, LP, self.prec)
         nbE = self._timed("encoder_bwd", ops.encoder_bwd, x, enc_img, masks, self.h1, self.h2, self.dmean,
                           self.dlogvar, self.partE, dk, Ld, LP, lay.mask_augm, self.prec)
         return nbE, nbD

@@ -117,6 +117,30 @@ def decoder_fused(x, dec_img, maskA, maskB, co, mean, logvar, eps, eps_ml, inv_B
     return nb.value
 
 
+def encoder_fwd_draw_f32(x, enc_img, mask_in, mask_p_out, h1, h2, mean, logvar, d, Ld, keep_prob, seed, offset_mask, state=None,
+                         elem_lo=0):
+    """encoder_fwd (two passes, fp32, padded latent workspaces) that draws mask_p = mask_in & keep for the mask words it
+    holds, with vpc_draw_step's counters, and stores it to mask_p_out."""
+    check(lib().vpc_encoder_fwd_draw_f32(ptr(x), ptr(enc_img), ptr(mask_in), ptr(mask_p_out), ptr_array(h1), ptr_array(h2),
+                                         ptr_array(mean), ptr_array(logvar), x.shape[0], d, Ld, float(keep_prob), int(seed),
+                                         int(offset_mask), ptr(state), int(elem_lo), stream_ptr()), "vpc_encoder_fwd_draw_f32")
+
+
+def decoder_fused_draw_f32(x, dec_img, maskA, maskB, co, mean, logvar, eps, inv_B, x_logvar, dmean, dlogvar, partials, loss_part,
+                           d, Ld, seed, offset_eps, state=None, eps_shard=None):
+    """decoder_fused (fp32, 8-wave kernel, no ml_reg sample) that draws the eps planes it consumes, with vpc_draw_step's
+    counters, and stores them to eps (plane p = eps[p], [B][16])."""
+    n = len(maskA)
+    nb = C.c_int(0)
+    rows_local, rows_global, row_lo, _ = (x.shape[0], x.shape[0], 0, 16) if eps_shard is None else _shard4(eps_shard)
+    check(lib().vpc_decoder_fused_draw_f32(ptr(x), ptr(dec_img), n, ptr_array(maskA), ptr_array(maskB), co, ptr_array(mean),
+                                           ptr_array(logvar), ptr_array(eps), inv_B, x_logvar, ptr_array(dmean),
+                                           ptr_array(dlogvar), ptr(partials), ptr(loss_part), C.byref(nb), x.shape[0], d, Ld,
+                                           int(seed), int(offset_eps), ptr(state), rows_global, row_lo, stream_ptr()),
+          "vpc_decoder_fused_draw_f32")
+    return nb.value
+
+
 def step_small_max_rows():
     return int(lib().vpc_step_small_max_rows())
 
