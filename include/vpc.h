@@ -851,6 +851,30 @@ int vpc_miw_loss(const float* x, const float* mask, const float* mask_p, const f
                  void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum, long B, int S, int d,
                  int L, double alpha, int pairing, void* stream);
 
+/* Small-batch step of the family (csrc/vpc_miw_small.hip): the GEMM chains of the training step (VAE.py:3011-3134 /
+ * :3137-3301 forward, src/experiment_main/train.py:102-117) as two kernels and a tail, for obs_dim <= 32, latent_dim <= 16,
+ * RB = 1 .. 4 data rows per workgroup.  R = rows of the stacked passes ([q ; p] for Reg_MIWAE), S = num_samples; params =
+ * the flat parameter buffer in state_dict order; the buffers are MIWTrainer's workspace ([R][128] h1 h2, [R][2L] heads hact
+ * gh dht, [R*S][L] z and the sampling planes eps, [R*S][128] g1 g2, [R*S][3d] Y G).  Every entry returns VPC_ERR_ARG before
+ * any launch for a shape outside the limits, a NULL pointer or a short partial buffer.
+ *   vpc_miw_small_workspace  floats of the partial buffer (one block of all parameters per compute unit); 0 outside the limits
+ *   vpc_miw_small_fwd        xin, eps -> h1, h2, heads, hact = (mean | softplus), z = mean + eps * scale, g1, g2, raw heads Y
+ *   vpc_miw_small_bwd        G = d loss / d Y and gh = d loss / d hact (vpc_miw_loss, raw = 1) -> dht and one partial block
+ *                            of all twelve gradients per workgroup (persistent grid, workgroup g owns row blocks g, g + grid, ..)
+ *   vpc_miw_small_tail       partial blocks summed in workgroup order into grad (state_dict order), then flat Adam with
+ *                            vpc_adam_step's update (train.py:116) */
+long vpc_miw_small_workspace(int d, int L);
+int vpc_miw_small_fwd(const float* params, const float* xin, const float* eps, float* h1, float* h2, float* heads,
+                      float* hact, float* z, float* g1, float* g2, float* Y, long R, int S, int d, int L, int RB,
+                      void* stream);
+int vpc_miw_small_bwd(const float* params, const float* xin, const float* eps, const float* h1, const float* h2,
+                      const float* heads, const float* z, const float* g1, const float* g2, const float* G,
+                      const float* gh, float* dht, float* part, long part_floats, long R, int S, int d, int L, int RB,
+                      void* stream);
+int vpc_miw_small_tail(const float* part, long part_floats, long R, int RB, int d, int L, float* grad, float* params,
+                       float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
+                       void* stream);
+
 /* ---- flow path: VAEFlow / REG_VAEFlow (csrc/vpc_flow.hip) -------------------------------------------------------
  * Reference: src/models/VAE.py:1860-1996 and :1999-2124, posterior Flow :1816-1854 (three PiecewiseLinearCDF layers,
  * tails "linear", tail_bound 1, context t.reshape(B, 10, 10), :1781-1813, spline :1680-1774).  Encoder

@@ -67,13 +67,6 @@ struct SmallPointNet {
 };
 struct SmallPnArgs : SmallArgs { SmallPointNet pn; };
 
-// gradient tile (out tile of A-buffer `da`, in tile of B-buffer `xb`) over the 16 rows: acc[m][n] += sum_row da[row][16 ta + m] * xb[row][16 tb + n]
-__device__ __forceinline__ f32x4 wgrad16(const float* da, int ta, const float* xb, int tb, f32x4 acc, int m, int kq) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = VPC_MFMA(da[(4 * s + kq) * SP + 16 * ta + m], xb[(4 * s + kq) * SP + 16 * tb + m], acc);
-    return acc;
-}
-
 template <int DT>
 __global__ __launch_bounds__(THREADS) void step_small_kernel(SmallArgs a) {
     constexpr int DTI = DT;

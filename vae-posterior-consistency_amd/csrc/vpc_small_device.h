@@ -1,7 +1,8 @@
 // Device helpers of the N-split 16-row-tile kernels (one workgroup of 8 waves per tile, the feature tiles of a layer split
 // over the waves, activations handed from layer to layer through LDS): the LDS activation-buffer geometry, the C-layout
-// tile <-> buffer accessors and the weight-fragment request / use pair.  Shared by vpc_small.hip (the training step and its
-// ensemble form) and vpc_evalsmall.hip (the evaluate-stage forward): one definition, included by both.
+// tile <-> buffer accessors, the 16-row weight-gradient tile and the weight-fragment request / use pair.  Shared by vpc_small.hip
+// (the training step and its ensemble form), vpc_evalsmall.hip (the evaluate-stage forward) and vpc_miw_small.hip (the MIWAE
+// path's small-batch step, which reads its fragments from row-major weights instead): one definition, included by all.
 #pragma once
 #include "vpc_device.h"
 
@@ -16,6 +17,13 @@ __device__ __forceinline__ f32x4 ld_act(const float* buf, int t, int c, int q) {
 }
 __device__ __forceinline__ void st_act(float* buf, int t, int c, int q, f32x4 v) {
     *reinterpret_cast<f32x4*>(buf + c * SP + 16 * t + 4 * q) = v;
+}
+
+// gradient tile (out tile of A-buffer `da`, in tile of B-buffer `xb`) over the 16 rows: acc[m][n] += sum_row da[row][16 ta + m] * xb[row][16 tb + n]
+__device__ __forceinline__ f32x4 wgrad16(const float* da, int ta, const float* xb, int tb, f32x4 acc, int m, int kq) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = VPC_MFMA(da[(4 * s + kq) * SP + 16 * ta + m], xb[(4 * s + kq) * SP + 16 * tb + m], acc);
+    return acc;
 }
 
 // Weight fragments straight from the fp32 image in global memory (the layout of vpc_layout.h: row pitch S dwords, 16-byte slot

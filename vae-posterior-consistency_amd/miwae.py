@@ -19,6 +19,8 @@ B == 1 (eval_miwae, one row per call) the pairing is the natural one, and the ba
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -65,6 +67,29 @@ def miw_loss(x, mask, mask_p, y_q, y_p, ldy, raw, hq, hp, eq, ep, g_q, g_p, ldg,
                              ptr(scratch), scratch.numel() * scratch.element_size(), ptr(out8), ptr(loss_f32),
                              ptr(accum), int(B), int(S), int(d), int(Ld), float(alpha), int(pairing), stream_ptr()),
           "vpc_miw_loss")
+
+
+def miw_small_workspace(d, Ld):
+    """Floats of the partial buffer of the small-batch step (0: the shape is outside its limits)."""
+    return int(lib().vpc_miw_small_workspace(int(d), int(Ld)))
+
+
+def miw_small_fwd(flat, xin, eps, h1, h2, heads, hact, z, g1, g2, Y, R, S, d, Ld, RB):
+    check(lib().vpc_miw_small_fwd(ptr(flat), ptr(xin), ptr(eps), ptr(h1), ptr(h2), ptr(heads), ptr(hact), ptr(z), ptr(g1),
+                                  ptr(g2), ptr(Y), int(R), int(S), int(d), int(Ld), int(RB), stream_ptr()),
+          "vpc_miw_small_fwd")
+
+
+def miw_small_bwd(flat, xin, eps, h1, h2, heads, z, g1, g2, G, gh, dht, part, R, S, d, Ld, RB):
+    check(lib().vpc_miw_small_bwd(ptr(flat), ptr(xin), ptr(eps), ptr(h1), ptr(h2), ptr(heads), ptr(z), ptr(g1), ptr(g2),
+                                  ptr(G), ptr(gh), ptr(dht), ptr(part), part.numel(), int(R), int(S), int(d), int(Ld),
+                                  int(RB), stream_ptr()), "vpc_miw_small_bwd")
+
+
+def miw_small_tail(part, R, RB, d, Ld, grad, flat, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
+    check(lib().vpc_miw_small_tail(ptr(part), part.numel(), int(R), int(RB), int(d), int(Ld), ptr(grad), ptr(flat),
+                                   ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2, eps, int(step), stream_ptr()),
+          "vpc_miw_small_tail")
 
 
 def _joined(parts, M, W):
@@ -372,12 +397,54 @@ _DEC_WKEYS = (("dec_bwd", 2), ("dec_bwd", 1), ("dec_bwd", 0))
 _ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
 
 
+SMALL_MAX_D, SMALL_MAX_L = 32, 16  # limits of csrc/vpc_miw_small.hip
+# The row limit of the small-batch step, in decoder rows P * B * S.  The step without VPC_MIW_SMALL in the environment stays the
+# launch chain (tests/test_trainer_images.py pins the chain's launch sequence as MIWTrainer's step at the wine shape), so the
+# default is 0; SMALL_ROWS_MEASURED is the largest size at which the small path's worst block beat the chain's best block
+# (profiles/miw_small_notes.md) - the value to put into VPC_MIW_SMALL.
+SMALL_ROWS_DEFAULT = 0
+SMALL_ROWS_MEASURED = 163840
+
+
+def small_max_rows():
+    """The row limit of the small-batch step: VPC_MIW_SMALL in the environment (decoder rows P * B * S; 0 = never), read
+    per step; SMALL_ROWS_DEFAULT (0: the chain) without it."""
+    v = os.environ.get("VPC_MIW_SMALL")
+    if v is None or v == "":
+        return SMALL_ROWS_DEFAULT
+    try:
+        return int(v)
+    except ValueError:
+        raise L.VpcError(f"VPC_MIW_SMALL={v!r}: expected a number of decoder rows (0 keeps the launch chain)") from None
+
+
+def small_step_route(d, L, B, S, P, max_rows):
+    """Whether MIWTrainer.step takes the small-batch step (csrc/vpc_miw_small.hip): obs_dim <= 32, latent_dim <= 16 and
+    0 < P * B * S <= max_rows decoder rows (small_max_rows()).  Everything else keeps the launch chain."""
+    return 0 < d <= SMALL_MAX_D and 0 < L <= SMALL_MAX_L and S >= 1 and 0 < P * B * S <= max_rows
+
+
+def small_rows_per_workgroup(R, S):
+    """RB, the data rows of the stacked passes one workgroup of the small-batch step owns: the smallest of 1, 2, 4 that
+    leaves at most one workgroup per CU (the grid of the backward kernel: vpc_miw_small_workspace / n_params blocks; 256 on
+    an MI355X), 4 beyond.  Measured at S = 20 only (profiles/miw_small_notes.md): S does not enter the rule."""
+    cus = L.max_blocks() // 2
+    return 1 if R <= cus else 2 if R <= 2 * cus else 4
+
+
 class MIWTrainer(_FlatAdamTrainer):
     """The whole training step of the MIWAE path (train.py:102-117 for 'reg_MIWAE*' / the final branch for
     'vanilla_MIWAE*') as a fixed sequence of HIP launches with no host synchronisation: mask_p draw + stacked encoder
     input + Philox normals (one launch), the encoder and decoder GEMM chains with the q and p passes stacked along the
     batch (one GEMM per layer), the three loss launches on the raw decoder heads, the backward GEMM chain into one flat
     gradient, flat Adam.  fp32 only.
+
+    Small shapes (small_step_route: obs_dim <= 32, latent_dim <= 16, P * B * S <= small_max_rows() decoder rows) run the two
+    GEMM chains, the sampler and their backward passes as two kernels and close with one tail (csrc/vpc_miw_small.hip):
+    prep -> miw_small_fwd -> the three loss launches -> miw_small_bwd -> miw_small_tail (partial blocks summed in a fixed
+    order, flat Adam), seven launches of this library instead of 25, on the same workspace buffers and with the same draws.  VPC_MIW_SMALL
+    in the environment is the row limit and switches the path on (unset or 0 keeps the chain; SMALL_ROWS_MEASURED is the
+    measured value); `last_path` names what the last step ran: "small" or "chain".
 
     Single process only: the reference's row / sample pairing (module docstring) couples rows across the whole batch, so
     a step sharded over ranks cannot equal the single-process step without an all-gather of the per-row sums."""
@@ -394,6 +461,9 @@ class MIWTrainer(_FlatAdamTrainer):
         self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
         self.g = model._named_views(self.grad)
         self._B = self._v = None
+        self._part = None  # partial blocks of the small-batch step: made on its first use
+        self.small_rb = None  # rows per workgroup of the small-batch step; None: small_rows_per_workgroup
+        self.last_path = None
 
     def _ws(self, B, v=None):
         v = self.model._views() if v is None else v
@@ -456,6 +526,9 @@ class MIWTrainer(_FlatAdamTrainer):
         if eps is not None:
             self.eps.copy_(eps.reshape(self.eps.shape))
         self.rng_offset += rng_inc
+        if small_step_route(d, Ld, B, S, P, small_max_rows()):
+            return self._step_small(xf, mf, mp, R, S, d, Ld, alpha)
+        self.last_path = "chain"
         # ---- forward
         chain_fwd(self.enc_layers, self.enc_acts, R, 0, t, _T_ENC_FWD)
         t("sample", miw_sample, self.heads, self.hact, sl["es"], self.z, R, S, Ld)
@@ -471,3 +544,24 @@ class MIWTrainer(_FlatAdamTrainer):
                   names=_T_ENC_BWD)
         self._wgrad_reduce()
         self._adam()
+
+    def _step_small(self, xf, mf, mp, R, S, d, Ld, alpha):
+        """The step behind the draws as miw_small_fwd -> the loss's three launches on the raw heads -> miw_small_bwd ->
+        miw_small_tail (csrc/vpc_miw_small.hip), on the chain's workspace buffers."""
+        t, sl, flat = self._timed, self._sl, self.model._flat
+        self.last_path = "small"
+        if self._part is None:
+            self._part = torch.empty(miw_small_workspace(d, Ld), device=self.dev)
+        RB = self.small_rb if self.small_rb else small_rows_per_workgroup(R, S)
+        B = R // (2 if self.reg else 1)
+        t("small_fwd", miw_small_fwd, flat, self.xin, sl["es"], self.h1, self.h2, self.heads, self.hact, self.z, self.g1,
+          self.g2, self.Y, R, S, d, Ld, RB)
+        t("loss", miw_loss, xf, mf, mp, self.Y, sl["Yp"], 3 * d, 1, self.hact, sl["hp"], sl["eq"], sl["ep"], self.G,
+          sl["Gp"], 3 * d, self.gh, sl["ghp"], None, self.scratch, self.out8, self.tail, self.accum, B, S, d, Ld, alpha,
+          PAIR_REFERENCE)
+        t("small_bwd", miw_small_bwd, flat, self.xin, sl["es"], self.h1, self.h2, self.heads, self.z, self.g1, self.g2,
+          self.G, self.gh, self.dht, self._part, R, S, d, Ld, RB)
+        self.step_count += 1
+        t("tail", miw_small_tail, self._part, R, RB, d, Ld, self.grad, flat, self.exp_avg, self.exp_avg_sq, self.lr,
+          self.betas[0], self.betas[1], self.adam_eps, self.step_count)
+        self._flat_written(None)
