@@ -875,6 +875,26 @@ int vpc_miw_small_tail(const float* part, long part_floats, long R, int RB, int 
                        float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
                        void* stream);
 
+/* Streaming importance-weighted imputation of the family (csrc/vpc_miw_impute.hip), for obs_dim <= 32, latent_dim <= 16:
+ * what src/experiment_main/evaluate.py:89-113 computes one row at a time through the llh_eval branch of MIWAE.loss /
+ * Reg_MIWAE.loss (VAE.py:3078-3099 / :3204-3258) - x_mean of S samples weighted by the softmax of their log-weights - for B
+ * rows in two launches and without writing a decoder row: a workgroup owns one row and one chunk of s_chunk samples (rounded
+ * up to a multiple of 16 here) and leaves (running max, running sum, weighted sums) in its slot of `part`; the merge
+ * combines a row's chunks in chunk order.  Only the q side enters (:3255-3257), so there is no mask_p.  x, mask (0 / 1
+ * floats) [B][d]; params = the flat parameter buffer in state_dict order; xm [B][d]; lse [B] or NULL: the per-row
+ * log-sum-exp of the log-weights (the per-row pairing's IW bound before the mean).  eps [2][B][S][L] = the sampler's draw
+ * and the fresh draw of :3087 / :3216, or NULL: both are drawn in the kernel (Philox; counter = (offset + row0 + row) in the
+ * high word, 4 * sample + latent / 4 in the low word, one Philox stream per plane - independent of s_chunk and the grid),
+ * and vpc_miw_impute_draws writes exactly those values.  VPC_ERR_ARG before any launch for a shape outside the limits, a
+ * NULL required pointer, a short partial buffer or offset + row0 + B > 2^32.
+ *   vpc_miw_impute_scratch  floats of the partial buffer, B * ceil(S / s_chunk16) * (2 + d); 0 outside the limits */
+long vpc_miw_impute_scratch(long B, int S, int d, int L, int s_chunk);
+int vpc_miw_impute(const float* params, const float* x, const float* mask, const float* eps, unsigned long long seed,
+                   unsigned long long offset, long row0, float* part, long part_floats, float* xm, float* lse, long B, int S,
+                   int d, int L, int s_chunk, void* stream);
+int vpc_miw_impute_draws(float* eps_out, long B, int S, int L, unsigned long long seed, unsigned long long offset, long row0,
+                         void* stream);
+
 /* ---- flow path: VAEFlow / REG_VAEFlow (csrc/vpc_flow.hip) -------------------------------------------------------
  * Reference: src/models/VAE.py:1860-1996 and :1999-2124, posterior Flow :1816-1854 (three PiecewiseLinearCDF layers,
  * tails "linear", tail_bound 1, context t.reshape(B, 10, 10), :1781-1813, spline :1680-1774).  Encoder

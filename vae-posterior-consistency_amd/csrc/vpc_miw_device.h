@@ -1,7 +1,8 @@
 // Device helpers of the MIWAE path (reference src/models/VAE.py: MIWAE :3011-3134, Reg_MIWAE :3137-3301): the softplus /
 // sigmoid pairs of the sampler and the decoder heads, the Student-t log-density and the wave reductions.  Shared by
-// vpc_miw.hip (the elementwise and loss kernels) and vpc_miw_small.hip (the small-batch fused step): one definition,
-// included by both, so that the fused stages evaluate the expressions the float64 tests hold.
+// vpc_miw.hip (the elementwise and loss kernels), vpc_miw_small.hip (the small-batch fused step) and vpc_miw_impute.hip (the
+// streaming imputation): one definition, included by all, so that the fused stages evaluate the expressions the float64 tests
+// hold.
 #pragma once
 #include <hip/hip_runtime.h>
 

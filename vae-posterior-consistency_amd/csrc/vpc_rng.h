@@ -161,5 +161,22 @@ __device__ __forceinline__ float ais_uniform(long chain, int j, uint64_t seed) {
     return u01(philox(ais_ctr(chain, 0, j), AIS_KIND_U, seed).x);
 }
 
+// ---- the draws of the streaming MIWAE imputation (vpc_miw_impute.hip: miw_impute_kernel and miw_impute_draws_kernel)
+constexpr uint32_t MIW_IMP_KIND_A = 5u, MIW_IMP_KIND_B = 6u;  // Philox streams of the sampler's draw and of the fresh draw
+// Draw counter of latent components 4 group .. 4 group + 3 of sample s of GLOBAL data row grow (= row0 + row): the row, plus
+// the call's offset, in the high word, 4 s + group in the low word, the plane as the Philox stream - independent of the
+// chunk length, the grid and the workgroup that draws.  offset + grow < 2^32 and s < 2^30 (checked by the entries).
+__device__ __forceinline__ uint64_t miw_imp_ctr(uint64_t offset, long grow, int s, int group) {
+    return ((offset + (uint64_t)grow) << 32) | (uint64_t)(uint32_t)(4 * s + group);
+}
+// latent component l of that draw: the Box-Muller form of fill_normal_body
+__device__ __forceinline__ float miw_imp_normal(uint64_t seed, uint64_t offset, int plane, long grow, int s, int l) {
+    const U4 r = philox(miw_imp_ctr(offset, grow, s, l >> 2), plane ? MIW_IMP_KIND_B : MIW_IMP_KIND_A, seed);
+    const bool hi = (l & 2) != 0;
+    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01(hi ? r.z : r.x)));
+    const float t = u01(hi ? r.w : r.y);
+    return rad * ((l & 1) ? __builtin_amdgcn_sinf(t) : __builtin_amdgcn_cosf(t));
+}
+
 }  // namespace vpc
 #endif  // __HIPCC__

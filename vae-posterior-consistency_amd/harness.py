@@ -41,7 +41,7 @@ from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_ma
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
 from .eddi import EDDITrainer, Reg_EDDI, _EDDIBase, vanilla_EDDI
 from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _EDDIMnistBase
-from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase
+from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream
 from .flow import FlowTrainer, _FlowBase
 from .wide import WideTrainer
 
@@ -597,18 +597,29 @@ def miwae_result_path(experiment_type, data_type, vae_type, loader_stage, alpha=
 def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
                experiment_type, vae_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), alpha=0.5,
                stage="evaluate", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False,
-               alpha_annealing=True, model=None, save=True, max_decoder_rows=1 << 23):
+               alpha_annealing=True, model=None, save=True, max_decoder_rows=1 << 23, engine="chain", seed=None):
     """evaluate.py:72-133: for every (loader, loader_stage), M repetitions; per batch a mask_p draw (Reg_MIWAE) and the
     llh_eval imputation of every row with valid_k samples; the RMSE on ~mask per BATCH, averaged over the batches, then
     over the repetitions.  The reference imputes one row per forward; here max_decoder_rows // valid_k rows go through
     one launch sequence with the per-row pairing, which equals the single-row calls.  Returns {loader_stage: rmse} (0-dim
-    CPU tensors) and, with save=True, writes the reference's result files (miwae_result_path)."""
+    CPU tensors) and, with save=True, writes the reference's result files (miwae_result_path).
+
+    engine="stream": every batch is ONE miwae.impute_stream call (two launches, no decoder row in memory): no
+    max_decoder_rows loop, and no mask_p draw - the imputation does not read it (impute_stream's docstring).  The draws are
+    Philox streams of `seed` (None: one from torch's generator); the offset starts at 0 and advances by the batch's rows
+    after every call (trainer.impute_draw_counter), so no two calls of a run share a counter.  A model outside the
+    kernel's limits (obs_dim <= 32, latent_dim <= 16) raises VpcError: there is no fallback to the chain."""
+    if engine not in ("chain", "stream"):
+        raise L.VpcError(f"eval_miwae: engine {engine!r} (engines: 'chain', 'stream')")
     out = {}
     with torch.no_grad():
         model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
                                 p_missingness=p_missingness)
         rows = max(1, max_decoder_rows // max(1, valid_k))
+        if engine == "stream" and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        offset = 0
         for loader, loader_stage in list_loaders:
             recon = []
             for _ in range(M):
@@ -616,6 +627,11 @@ def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
                 for data_sample, mask in loader:
                     x = data_sample.to(device).float().reshape(-1, obs_dim)
                     mask = mask.to(device).reshape(-1, obs_dim)
+                    if engine == "stream":
+                        xm = impute_stream(model, x, mask, num_samples=valid_k, seed=seed, offset=offset)
+                        offset += x.shape[0]  # the call used the counter rows offset .. offset + B - 1
+                        XM.append(_rmse_unobserved(xm, x, mask))
+                        continue
                     mp = draw_mask_p(model, x.shape, mask, p_missingness, device) if model.regularised else None
                     xm = torch.empty_like(x)
                     for lo in range(0, x.shape[0], rows):

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from ._lib import VpcError, check, lib, ptr, require_cuda, stream_ptr
 from .images import FlatParams, mlp_spec
 from .linear import ACT_NONE, ACT_RELU, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now, wgrad_now_keys
 from .notmiwae import nm_mul, nm_prep
@@ -90,6 +90,23 @@ def miw_small_tail(part, R, RB, d, Ld, grad, flat, exp_avg, exp_avg_sq, lr, beta
     check(lib().vpc_miw_small_tail(ptr(part), part.numel(), int(R), int(RB), int(d), int(Ld), ptr(grad), ptr(flat),
                                    ptr(exp_avg), ptr(exp_avg_sq), lr, beta1, beta2, eps, int(step), stream_ptr()),
           "vpc_miw_small_tail")
+
+
+def miw_impute_scratch(B, S, d, Ld, s_chunk):
+    """Floats of the partial buffer of the streaming imputation, B * ceil(S / s_chunk16) * (2 + d) with s_chunk16 =
+    s_chunk rounded up to a multiple of 16 (0: the shape is outside the limits)."""
+    return int(lib().vpc_miw_impute_scratch(int(B), int(S), int(d), int(Ld), int(s_chunk)))
+
+
+def miw_impute(flat, x, mask, eps, seed, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk):
+    check(lib().vpc_miw_impute(ptr(flat), ptr(x), ptr(mask), ptr(eps), int(seed), int(offset), int(row0), ptr(part),
+                               part.numel(), ptr(xm), ptr(lse), int(B), int(S), int(d), int(Ld), int(s_chunk),
+                               stream_ptr()), "vpc_miw_impute")
+
+
+def miw_impute_draws(eps_out, B, S, Ld, seed, offset, row0):
+    check(lib().vpc_miw_impute_draws(ptr(eps_out), int(B), int(S), int(Ld), int(seed), int(offset), int(row0),
+                                     stream_ptr()), "vpc_miw_impute_draws")
 
 
 def _joined(parts, M, W):
@@ -253,6 +270,7 @@ class _MIWBase(FlatParams, nn.Module):
                                          nn.Linear(HID, 3 * d))
         self.max_epoch = 2800
         self._flat = None
+        self.last_impute_engine = None  # "chain" / "stream": what the last impute() ran
 
     @property
     def prior(self):  # VAE.py:3047 (a CPU distribution in the reference; kept for attribute parity)
@@ -330,9 +348,21 @@ class _MIWBase(FlatParams, nn.Module):
         return o, self.loss(x, o[2], o[3], o[4], o[0], o[1], mask, epoch, llh_eval=llh_eval)
 
     @torch.no_grad()
-    def impute(self, x, mask, mask_p=None, num_samples=None, pairing=PAIR_PER_ROW):
+    def impute(self, x, mask, mask_p=None, num_samples=None, pairing=PAIR_PER_ROW, engine="chain", **stream_args):
         """llh_eval imputation of every row of x with num_samples draws, rows independent (per-row pairing): what
-        eval_miwae computes one row at a time (evaluate.py:89-111), for a whole chunk of rows in one launch sequence."""
+        eval_miwae computes one row at a time (evaluate.py:89-111), for a whole chunk of rows in one launch sequence.
+        engine="stream" forwards to impute_stream (two launches, no decoder row in memory; mask_p is not read, the
+        per-row pairing is the only one, stream_args = its eps / seed / offset / row0 / s_chunk / return_lse).
+        `last_impute_engine` names what the last call ran."""
+        if engine == "stream":
+            if pairing != PAIR_PER_ROW:
+                raise L.VpcError("engine='stream' imputes with the per-row pairing only")
+            self.last_impute_engine = "stream"
+            return impute_stream(self, x, mask, num_samples=num_samples, **stream_args)
+        if engine != "chain" or stream_args:
+            raise L.VpcError(f"impute: engine {engine!r} with {sorted(stream_args)} (engines: 'chain', 'stream'; eps / seed / "
+                             "offset / row0 / s_chunk / return_lse belong to 'stream')")
+        self.last_impute_engine = "chain"
         S = self.num_samples if num_samples is None else num_samples
         z_q, mean_q, scale_q = self._encode(x, mask, S=S)
         outs_q = (*self.decoder(z_q), mean_q, scale_q)
@@ -390,6 +420,98 @@ class Reg_MIWAE(_MIWBase):
         return loss, loss
 
 
+# ------------------------------------------------------------------------------------------------ streaming imputation
+def impute_chunk(B, S, n_cu):
+    """The default s_chunk of impute_stream: the samples of a row one workgroup owns, a multiple of 16 and never below 16.
+    A rule that was measured, not derived (profiles/miw_impute_notes.md, d = 12, L = 10, S = 5 000, 256 compute units):
+
+      * B < n_cu: as few chunks per row as still give one workgroup per compute unit - the chunks of the largest multiple
+        of 16 with B * ceil(S / s_chunk) >= n_cu (every further chunk repeats the encoder and the weight-fragment loads:
+        B = 64 is fastest at 4 chunks, slower at 5, 10, 20, 40, 79) -
+      * B >= n_cu: whole rows, unless the last round of n_cu workgroups would be less than 95 % full; then 2 or 4 chunks
+        per row (B = 1 600: 6.25 rounds of whole rows, 7 % slower than 12.5 rounds of half rows),
+      * and in both cases the chunks of a row balanced: the smallest multiple of 16 that keeps that number of chunks (4
+        chunks of S = 5 000 as 3 x 1 664 + 8 are 30 % slower than as 3 x 1 264 + 1 208)."""
+    B, S, n_cu = max(int(B), 1), max(int(S), 1), max(int(n_cu), 1)
+    tiles = -(-S // 16)
+    if B < n_cu:
+        need = -(-n_cu // B)  # chunks per row for one workgroup per compute unit
+        chunks = -(-S // max(16, (S - 1) // (need - 1) // 16 * 16))
+    else:
+        for chunks in (1, 2, 4):
+            rounds = B * chunks / n_cu
+            if rounds >= 0.95 * -(-B * chunks // n_cu):
+                break
+        chunks = min(chunks, tiles)
+    return 16 * -(-(-(-S // chunks)) // 16)  # ceil(S / chunks), rounded up to a multiple of 16
+
+
+def impute_draws(B, S, L, seed, offset=0, row0=0, device=None):
+    """The draws of impute_stream(seed=seed, offset=offset, row0=row0) on B rows with S samples as [2, B, S, L]: plane 0
+    the sampler's eps, plane 1 the fresh draw of the log-weight's prior / posterior term (the counter rule of
+    trainer.impute_draw_counter).  (L, the latent width, hides the module's alias of _lib in here.)"""
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise VpcError("impute_draws runs only on the GPU (HIP kernel, no CPU fallback)")
+    if not (B >= 1 and S >= 1 and 1 <= L <= SMALL_MAX_L):
+        raise VpcError(f"impute_draws: B = {B}, S = {S}, latent_dim = {L} outside B >= 1, S >= 1, latent_dim <= {SMALL_MAX_L}")
+    eps = torch.empty(2, B, S, L, device=dev)
+    with torch.cuda.device(dev):
+        miw_impute_draws(eps, B, S, L, seed, offset, row0)
+    return eps
+
+
+@torch.no_grad()
+def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=0, row0=0, s_chunk=None,
+                  return_lse=False):
+    """The llh_eval imputation of every row of x with num_samples draws (evaluate.py:89-113 through VAE.py:3078-3099 /
+    :3204-3258, per-row pairing) in two launches: csrc/vpc_miw_impute.hip runs encoder, sampler, decoder, log-weights and
+    an online softmax per (row, chunk of s_chunk samples) and never writes a decoder row; the merge combines a row's
+    chunks in chunk order.  Returns xm [B, d], or (xm, lse [B]) with return_lse: lse = the per-row log-sum-exp of the
+    log-weights, the IW bound before the mean.
+
+    mask_p is not an argument, for Reg_MIWAE too: the reference's imputation takes the q pass's weights and the q pass's
+    x_mean only (VAE.py:3255-3257, MIWAE :3095-3098), so the whole p pass - which evaluate.py:99-104 computes and drops
+    with the loss - is skipped.
+
+    eps [2, B, S, L] injects the sampler's draw and the fresh draw of :3087 / :3216; otherwise both are drawn in the
+    kernel from (seed, offset, row0) - seed None takes one from torch's generator - by the rule of
+    trainer.impute_draw_counter, which does not depend on s_chunk: impute_draws returns those values, and rows [a, b) of
+    a call equal the call on x[a:b] with row0 = a.  s_chunk None: impute_chunk.  For a given s_chunk the result is
+    bit-reproducible.  obs_dim <= 32, latent_dim <= 16; anything else, CPU tensors, a wrong eps shape or s_chunk < 1
+    raise VpcError (no fallback)."""
+    d, Ld = model.obs_dim, model.latent_dim
+    S = model.num_samples if num_samples is None else int(num_samples)
+    require_cuda(x, mask, eps)
+    if not (1 <= d <= SMALL_MAX_D and 1 <= Ld <= SMALL_MAX_L):
+        raise L.VpcError(f"impute_stream supports obs_dim <= {SMALL_MAX_D} and latent_dim <= {SMALL_MAX_L}: got {d}, {Ld}")
+    xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
+    B = xf.shape[0]
+    if B < 1 or S < 1 or mf.shape != xf.shape:
+        raise L.VpcError(f"impute_stream: B = {B}, num_samples = {S}, mask {tuple(mf.shape)} for x {tuple(xf.shape)}")
+    if s_chunk is None:
+        s_chunk = impute_chunk(B, S, L.max_blocks() // 2)
+    if s_chunk < 1:
+        raise L.VpcError(f"impute_stream: s_chunk = {s_chunk} < 1")
+    if eps is not None:
+        if tuple(eps.shape) != (2, B, S, Ld):
+            raise L.VpcError(f"impute_stream: eps {tuple(eps.shape)}, expected {(2, B, S, Ld)}")
+        eps = _f32c(eps)
+    elif seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    n = miw_impute_scratch(B, S, d, Ld, s_chunk)
+    if n == 0:
+        raise L.VpcError(f"impute_stream: shape (B, S, d, L) = {(B, S, d, Ld)} is outside the kernel's limits")
+    flat = model.flatten_parameters()
+    require_cuda(flat)
+    with torch.cuda.device(xf.device):
+        part = torch.empty(n, device=xf.device)
+        xm = torch.empty(B, d, device=xf.device)
+        lse = torch.empty(B, device=xf.device) if return_lse else None
+        miw_impute(flat, xf, mf, eps, seed or 0, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk)
+    return (xm, lse) if return_lse else xm
+
+
 # ------------------------------------------------------------------------------------------------ fused step
 # timer names of the chain launches, per layer, and the weight gradients' (timer name, index in the trainer's workspace)
 _T_ENC_FWD, _T_ENC_BWD, _T_DEC_FWD, _T_DEC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) * 3, ("dec_fwd",) * 3, ("dec_bwd",) * 3
@@ -397,7 +519,7 @@ _DEC_WKEYS = (("dec_bwd", 2), ("dec_bwd", 1), ("dec_bwd", 0))
 _ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
 
 
-SMALL_MAX_D, SMALL_MAX_L = 32, 16  # limits of csrc/vpc_miw_small.hip
+SMALL_MAX_D, SMALL_MAX_L = 32, 16  # limits of csrc/vpc_miw_small.hip and csrc/vpc_miw_impute.hip
 # The row limit of the small-batch step, in decoder rows P * B * S.  The step without VPC_MIW_SMALL in the environment stays the
 # launch chain (tests/test_trainer_images.py pins the chain's launch sequence as MIWTrainer's step at the wine shape), so the
 # default is 0; SMALL_ROWS_MEASURED is the largest size at which the small path's worst block beat the chain's best block

@@ -45,6 +45,18 @@ def eval_draw_counters(rng_offset, draw_rows, pitch=16):
     return rng_offset, rng_offset + draw_rows * (pitch // 4)
 
 
+def impute_draw_counter(offset, row0, row, sample, latent):
+    """THE counter rule of the streaming MIWAE imputation's draws (miw_imp_ctr of csrc/vpc_rng.h):
+    the 64-bit Philox counter of latent components 4 g .. 4 g + 3 (g = latent // 4) of `sample` of data row row0 + row is
+    ((offset + row0 + row) << 32) | (4 * sample + g); the plane picks the Philox stream (5: the sampler's eps, 6: the fresh
+    draw), the component its Box-Muller output (0, 1: radius of word x, cos / sin of word y; 2, 3: words z, w).  A function
+    of (seed, offset, plane, row0 + row, sample, latent) alone - not of s_chunk, the grid or the workgroup that draws.
+    offset + row0 + B <= 2^32 and sample < 2^28.  A call on B rows uses the high words offset + row0 .. offset + row0 + B - 1,
+    so a caller that adds B to its offset after every call (harness.eval_miwae) never reuses a counter.
+    Returns (counter, component)."""
+    return ((offset + row0 + row) << 32) | (4 * sample + latent // 4), latent % 4
+
+
 def padded_width(d, mask_augm=False):
     """Row pitch of the kernels' x / mask arrays: d rounded up to a multiple of 4 columns, so that the 16-byte-vector kernel
     variants run (FusedTrainer.step says why); the mask-augmented layouts take their rows unpadded (on the row-tiled path:
