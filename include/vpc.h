@@ -240,6 +240,16 @@ int vpc_encoder_fwd_draw_f32(const float* x, const float* enc_img, const uint8_t
                              float* const* h1, float* const* h2, float* const* mean, float* const* logvar, long B, int d,
                              int L, float keep_prob, unsigned long long seed, unsigned long long offset_mask,
                              const long long* state, long mask_elem_lo, void* stream);
+/* Which kernel form the last vpc_encoder_fwd / vpc_encoder_fwd_draw_f32 call of this process launched (-1: none yet): the
+ * pass loop (one pass after the other over a tile) or the sweep (fp32, vector layout, plain encoder, d in (64, 128], two passes
+ * in one workgroup: both passes of a tile in one sweep over the weights - the same bytes in every workspace).  VPC_ENC_SWEEP=0
+ * in the environment keeps the pass loop everywhere, =1 takes the sweep wherever it is eligible; unset, only
+ * vpc_encoder_fwd_draw_f32 takes it (the form it makes faster).  For tests and A/B runs. */
+#define VPC_ENC_FWD_PASSES 0
+#define VPC_ENC_FWD_PASSES_DRAW 1
+#define VPC_ENC_FWD_SWEEP 2
+#define VPC_ENC_FWD_SWEEP_DRAW 3
+int vpc_encoder_fwd_last_form(void);
 int vpc_decoder_fused_draw_f32(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
                                const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
                                const float* const* logvar, float* const* eps, float inv_B, float x_logvar,

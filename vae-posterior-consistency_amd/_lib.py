@@ -113,6 +113,7 @@ _PROTOS = {
     "vpc_draw_step": [P, P, L_, F, P, L_, ULL, ULL, ULL, P, L_, L_, L_, L_, I, P],
     "vpc_fill_normal": [P, L_, ULL, ULL, P, L_, L_, L_, I, P],
     "vpc_encoder_fwd_draw_f32": [P, P, P, P, PP, PP, PP, PP, L_, I, I, F, ULL, ULL, P, L_, P],
+    "vpc_encoder_fwd_last_form": [],
     "vpc_decoder_fused_draw_f32": [P, P, I, PP, PP, P, PP, PP, PP, F, F, PP, PP, P, P, IP, L_, I, I, ULL, ULL, P, L_, L_, P],
     "vpc_rccl_unique_id": [P],
     "vpc_rccl_comm_init": [P, I, I, PP],

@@ -273,6 +273,41 @@ __device__ __forceinline__ f32x4 tile_fwd_p2_b(const uint32_t (&fb)[frag_nvar(S)
     }
     return acc;
 }
+// ---- a whole layer for TWO inputs of the same rows (the two passes of the encoder forward sweep, vpc_enc_sweep_body.h): every A
+// fragment feeds the two accumulator chains alternately, 8 MFMAs per ds_read_b128.  Each chain sees its k-steps in the order of
+// tile_fwd (same result, bit for bit), and successive MFMAs of one chain are 64 cycles apart - above the 40 of dependent
+// latency, so one wave alone keeps the pipe busy.  The fragment stream runs one ahead across the out tiles (the first fragment
+// of tile mt + 1, and its start value, are requested under the last MFMAs of tile mt); the sched_barrier pins each request above
+// the MFMAs it runs under.  start(mt): the accumulators' start value (a bias read, or zero4()); done(mt, acc0, acc1).
+template <int KT, int S, int MT, int NK, class Start, class Done>
+__device__ __forceinline__ void layer_fwd2_b(const uint32_t (&fb)[frag_nvar(S)], const f32x4 (&in0)[KT], const f32x4 (&in1)[KT],
+                                             Start start, Done done) {
+    static_assert(4 * (KT - 1) < NK && NK <= 4 * KT, "every k-tile holds at least one k-step");
+    f32x4 fa = frag_ld<S>(fb, 0, 0);
+    f32x4 st = start(0);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        f32x4 acc0 = st, acc1 = st;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+            f32x4 fn = fa;
+            if (kt + 1 < KT) fn = frag_ld<S>(fb, mt, kt + 1);
+            else if (mt + 1 < MT) {
+                fn = frag_ld<S>(fb, mt + 1, 0);
+                st = start(mt + 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * kt + j < NK) {
+                    acc0 = VPC_MFMA(fa[j], in0[kt][j], acc0);
+                    acc1 = VPC_MFMA(fa[j], in1[kt][j], acc1);
+                }
+            fa = fn;
+        }
+        done(mt, acc0, acc1);
+    }
+}
 // bases of the transposed fragments: one per register j (it holds the image's address) plus one per mt & 3
 template <int S>
 __device__ __forceinline__ void fragT_bases(uint32_t (&tj)[4], uint32_t (&tv)[fragT_nvar(S)], const float* W, int m, int q) {

@@ -7,6 +7,8 @@
 #include "vpc_bf16.h"
 #include "vpc_abi_internal.h"
 #include "vpc_rng.h"
+#include <atomic>
+#include <cstdlib>
 
 namespace vpc {
 
@@ -80,6 +82,13 @@ __global__ __launch_bounds__(512, 2) void enc_fwd_draw_kernel(EncFwdArgs a, EncD
     constexpr bool VEC = true, AUG = false, DRAW = true;
     constexpr int NW = 8, PREC = PREC_F32;
 #include "vpc_enc_fwd_body.h"
+}
+// Both passes of a tile in ONE sweep over the weight image (vpc_enc_sweep_body.h): the 8-wave fp32 vector kernel for two passes
+// in one workgroup and d in (64, 128], with (vpc_encoder_fwd_draw_f32) and without (vpc_encoder_fwd) the mask_p draw.  Same
+// arguments, same bytes in every workspace as the pass loop above.
+template <int DT, bool DRAW>
+__global__ __launch_bounds__(512, 2) void enc_fwd_sweep_kernel(EncFwdArgs a, EncDraw dr) {
+#include "vpc_enc_sweep_body.h"
 }
 
 struct EncBwdArgs {
@@ -555,6 +564,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void enc_bwd_kernel(EncBw
 }
 
 static size_t enc_fwd_lds(int DT) { return sizeof(float) * EncImg(DT).total; }
+// Where the sweep kernel is eligible (fp32, vector layout, plain encoder, d in (64, 128], two passes in one workgroup):
+// VPC_ENC_SWEEP=0 in the environment keeps the pass-loop kernels, =1 takes the sweep in both forms (A/B runs, tests).  Unset:
+// the drawing form sweeps (encoder_fwd 68.7 -> 62.9 us at B = 65 536, profiles/enc_fwd_sweep_notes.md), the non-drawing form
+// keeps the pass loop (62.8 against 62.2 us: inside the run-to-run spread, so the default did not move).
+static bool enc_sweep_on(bool draw) {
+    const char* e = getenv("VPC_ENC_SWEEP");
+    return e ? atoi(e) != 0 : draw;
+}
+// which form the last encoder forward of this process launched (vpc_encoder_fwd_last_form)
+static std::atomic<int> enc_fwd_form{-1};
 static size_t enc_bwd_lds(int DT, int nw) {
     const EncImg im(DT);
     return sizeof(float) * ((im.total - im.oW2) + 2 * H1P * 16 * nw + nw * 128);
@@ -564,6 +583,14 @@ template <typename K, typename A>
 static int launch(K kern, const A& args, int grid_x, int grid_y, int nw, size_t lds, hipStream_t stream) {
     if (!lds_attr_done(reinterpret_cast<const void*>(kern), lds)) return VPC_ERR_HIP;
     hipLaunchKernelGGL(kern, dim3(grid_x, grid_y), dim3(64 * nw), lds, stream, args);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+// the sweep kernels: (EncFwdArgs, EncDraw), 512 threads, one grid row
+template <typename K>
+static int launch(K kern, const EncFwdArgs& args, const EncDraw& dr, int grid_x, size_t lds, hipStream_t stream) {
+    if (!lds_attr_done(reinterpret_cast<const void*>(kern), lds)) return VPC_ERR_HIP;
+    hipLaunchKernelGGL(kern, dim3(grid_x), dim3(512), lds, stream, args, dr);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 
@@ -595,6 +622,9 @@ extern "C" int vpc_encoder_fwd(const float* x, const float* enc_img, int npass, 
     const int DT = dt_for(mask_augm ? 2 * d : d);
     const size_t lds = enc_fwd_lds(DT);
     hipStream_t s = (hipStream_t)stream;
+    const bool sweep = precision == PREC_F32 && vec && !mask_augm && DT == 8 && npass == 2 && !ts.small && enc_sweep_on(false);
+    enc_fwd_form.store(sweep ? VPC_ENC_FWD_SWEEP : VPC_ENC_FWD_PASSES, std::memory_order_relaxed);
+    if (sweep) return launch(enc_fwd_sweep_kernel<8, false>, a, EncDraw{}, ts.grid_x, lds, s);
     if (precision != PREC_F32) {  // bf16 variants: throughput shape, vector layout (d % 4 == 0), plain encoder input
         if (!vec || mask_augm) return VPC_ERR_SHAPE;
 #define VPC_CASE(T)                                                                                                    \
@@ -644,12 +674,17 @@ extern "C" int vpc_encoder_fwd_draw_f32(const float* x, const float* enc_img, co
     }
     a.mask[0] = mask_in; a.mask[1] = mask_p_out;
     const EncDraw dr{mask_p_out, keep_prob, seed, offset_mask, state, mask_elem_lo};
+    const bool sweep = enc_sweep_on(true);
+    enc_fwd_form.store(sweep ? VPC_ENC_FWD_SWEEP_DRAW : VPC_ENC_FWD_PASSES_DRAW, std::memory_order_relaxed);
+    if (sweep) return launch(enc_fwd_sweep_kernel<8, true>, a, dr, ts.grid_x, enc_fwd_lds(8), (hipStream_t)stream);
     auto kern = enc_fwd_draw_kernel<8>;
     const size_t lds = enc_fwd_lds(8);
     if (!lds_attr_done(reinterpret_cast<const void*>(kern), lds)) return VPC_ERR_HIP;
     hipLaunchKernelGGL(kern, dim3(ts.grid_x), dim3(512), lds, (hipStream_t)stream, a, dr);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
+
+extern "C" int vpc_encoder_fwd_last_form(void) { return enc_fwd_form.load(std::memory_order_relaxed); }
 
 extern "C" int vpc_encoder_bwd(const float* x, const float* enc_img, int npass, const uint8_t* const* mask,
                                const float* const* h1, const float* const* h2, const float* const* dmean,
