@@ -905,6 +905,25 @@ int vpc_miw_impute(const float* params, const float* x, const float* mask, const
 int vpc_miw_impute_draws(float* eps_out, long B, int S, int L, unsigned long long seed, unsigned long long offset, long row0,
                          void* stream);
 
+/* Streaming importance-weighted imputation of the MNAR path (csrc/vpc_nm_impute.hip), for obs_dim <= 128, latent_dim <= 16:
+ * what src/experiment_main/evaluate.py:13-69 computes one row at a time through the llh_eval branch of
+ * REG_notMIWAE_v2.loss / notMIWAE_myversion.loss (VAE.py:2398-2461 / :2774-2813) - xm = sum_k softmax(-l_w_q)_k x_recon_q[:, k]
+ * (:2458-2461 / :2810-2813) over S samples, l_w with the self-masking missingness model (:2407-2435 / :2777-2802) - for B rows
+ * in two launches and without writing a decoder row: a workgroup owns one row and one chunk of s_chunk samples (rounded up to
+ * a multiple of 16 here) and leaves (running max, running sum, weighted sums) in its slot of `part`; the merge combines a
+ * row's chunks in chunk order.  Only the q side enters, so there is no mask_p and no alpha.  regularised != 0:
+ * REG_notMIWAE_v2 (analytic KL, :2404); 0: notMIWAE_myversion (Monte-Carlo KL on a fresh draw, :2791-2798).  x, mask (0 / 1
+ * floats) [B][d]; params = the model's flat parameter buffer ([W b | encoder | decoder], the head pairs adjacent); xm
+ * [B][d]; lse [B] or NULL: the per-row log-sum-exp of -l_w.  eps [2][B][S][L] = the sampler's draw and the fresh draw (plane
+ * b is not read for the regularised class), or NULL: both are drawn in the kernel by the rule of vpc_miw_impute, and
+ * vpc_miw_impute_draws writes exactly those values.  VPC_ERR_ARG before any launch for a shape outside the limits, a NULL
+ * required pointer, a short partial buffer or offset + row0 + B > 2^32.
+ *   vpc_nm_impute_scratch  floats of the partial buffer, B * ceil(S / s_chunk16) * (2 + d); 0 outside the limits */
+long vpc_nm_impute_scratch(long B, int S, int d, int L, int s_chunk);
+int vpc_nm_impute(const float* params, const float* x, const float* mask, const float* eps, unsigned long long seed,
+                  unsigned long long offset, long row0, float* part, long part_floats, float* xm, float* lse, long B, int S,
+                  int d, int L, int s_chunk, int regularised, void* stream);
+
 /* ---- flow path: VAEFlow / REG_VAEFlow (csrc/vpc_flow.hip) -------------------------------------------------------
  * Reference: src/models/VAE.py:1860-1996 and :1999-2124, posterior Flow :1816-1854 (three PiecewiseLinearCDF layers,
  * tails "linear", tail_bound 1, context t.reshape(B, 10, 10), :1781-1813, spline :1680-1774).  Encoder

@@ -162,6 +162,9 @@ _PROTOS = {
     "vpc_miw_impute_scratch": [L_, I, I, I, I],
     "vpc_miw_impute": [P, P, P, P, ULL, ULL, L_, P, L_, P, P, L_, I, I, I, I, P],
     "vpc_miw_impute_draws": [P, L_, I, I, ULL, ULL, L_, P],
+    # streaming MNAR imputation (csrc/vpc_nm_impute.hip)
+    "vpc_nm_impute_scratch": [L_, I, I, I, I],
+    "vpc_nm_impute": [P, P, P, P, ULL, ULL, L_, P, L_, P, P, L_, I, I, I, I, I, P],
     # flow path (csrc/vpc_flow.hip)
     "vpc_flow_prep": [P, P, P, P, P, P, L_, L_, I, F, ULL, ULL, ULL, P],
     "vpc_flow_fwd": [P, L_, P, P, P, L_, L_, P],
@@ -191,7 +194,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_impute_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
 
 _lib = None
 

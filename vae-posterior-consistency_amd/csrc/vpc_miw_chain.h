@@ -1,6 +1,7 @@
 // The row-major GEMM chain of the MIWAE path's N-split kernels (vpc_miw_small.hip: the small-batch step; vpc_miw_impute.hip:
 // the streaming imputation): the layout of the flat parameter buffer, the range-checked weight-fragment request straight from
-// it, the bias tile and the fragment x LDS-activation product.  One definition, included by both.
+// it, the bias tile and the fragment x LDS-activation product.  One definition, included by both - and by vpc_nm_impute.hip,
+// the streaming imputation of the MNAR models, which has the same hidden width and its own buffer layout (NmOff).
 #pragma once
 #include "vpc_device.h"
 #include "vpc_small_device.h"

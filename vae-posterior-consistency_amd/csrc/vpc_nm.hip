@@ -14,11 +14,10 @@
 #include <mutex>
 #include <utility>
 #include "vpc_device.h"
+#include "vpc_nm_device.h"
 #include "../../include/vpc.h"
 
 namespace vpc {
-
-constexpr float NM_HALF_LOG_2PI = 0.91893853320467274f;
 
 struct NMLossArgs {
     const float* x; const float* m; const float* mp;        // [B][d]; mp = nullptr for the un-regularised model
@@ -40,15 +39,7 @@ struct NMLossArgs {
 };
 constexpr int NM_STATS = 5;  // sums over rows of: lse_q, lse_p, sum_k RE_e, sum_l kl_el, sum_k RE_q
 
-// hardware exp / log / rcp (v_exp_f32, v_log_f32, v_rcp_f32: <= 1-2 ulp) for the per-element work of the loss kernel;
-// the once-per-workgroup W transforms and the scalar log-sum-exp keep the IEEE routines
-__device__ __forceinline__ float fexp(float v) { return __expf(v); }
-__device__ __forceinline__ float frcp(float v) { return __builtin_amdgcn_rcpf(v); }
-__device__ __forceinline__ float softplus_f(float v) { return v > 20.f ? v : log1pf(expf(v)); }
-__device__ __forceinline__ float sigmoid_f(float v) {
-    const float e = expf(-fabsf(v));
-    return v >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
+// (fexp / frcp / softplus_f / sigmoid_f and NM_HALF_LOG_2PI: vpc_nm_device.h, shared with the streaming imputation)
 struct Lse {  // online log-sum-exp
     float mx = -INFINITY, s = 0.f;
     __device__ __forceinline__ void add(float v) {

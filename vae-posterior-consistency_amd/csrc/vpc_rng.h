@@ -161,7 +161,8 @@ __device__ __forceinline__ float ais_uniform(long chain, int j, uint64_t seed) {
     return u01(philox(ais_ctr(chain, 0, j), AIS_KIND_U, seed).x);
 }
 
-// ---- the draws of the streaming MIWAE imputation (vpc_miw_impute.hip: miw_impute_kernel and miw_impute_draws_kernel)
+// ---- the draws of the streaming imputations (vpc_miw_impute.hip: miw_impute_kernel and miw_impute_draws_kernel; vpc_nm_impute.hip:
+// nm_impute_kernel)
 constexpr uint32_t MIW_IMP_KIND_A = 5u, MIW_IMP_KIND_B = 6u;  // Philox streams of the sampler's draw and of the fresh draw
 // Draw counter of latent components 4 group .. 4 group + 3 of sample s of GLOBAL data row grow (= row0 + row): the row, plus
 // the call's offset, in the high word, 4 s + group in the low word, the plane as the Philox stream - independent of the

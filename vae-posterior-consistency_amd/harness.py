@@ -39,6 +39,7 @@ from .ensemble import (EDDI, MASK, EDDIEnsembleEvaluator, EDDIEnsembleTrainer, E
 from .fused import FusedTrainer
 from .models import Reg_VAE, Reg_VAE_mask, _VAEBase, vanilla_VAE, vanilla_VAE_mask
 from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
+from .notmiwae import impute_stream as nm_impute_stream
 from .eddi import EDDITrainer, Reg_EDDI, _EDDIBase, vanilla_EDDI
 from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _EDDIMnistBase
 from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream
@@ -554,12 +555,20 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
                   training_parameters, experiment_type, vae_type, max_epochs, valid_k, num_estimates,
                   device=torch.device("cuda"), alpha=0.5, stage="evaluate", p_missingness=30, reg_type="ml_reg",
                   beta=1.0, beta_annealing=False, alpha_annealing=True, not_miwae_type="changed", model=None,
-                  save=True, max_decoder_rows=1 << 20):
+                  save=True, max_decoder_rows=1 << 20, engine="chain", seed=None):
     """evaluate.py:13-69: M repetitions of the self-normalised importance-weighted imputation with valid_k samples
     per row, RMSE on the missing entries.  The reference walks the test set ONE ROW per forward (and redraws a
     full-size mask for each row); here rows are processed in chunks of max_decoder_rows / valid_k per launch
     sequence, one mask_p draw per repetition - the same estimator, row-independent, so the result has the same
-    distribution.  Returns the RMSE (0-dim CPU tensor) and, with save=True, writes the reference's result file."""
+    distribution.  Returns the RMSE (0-dim CPU tensor) and, with save=True, writes the reference's result file.
+
+    engine="stream": every repetition is ONE notmiwae.impute_stream call over all rows (two launches, no decoder row in
+    memory): no max_decoder_rows loop, and no mask_p draw - the imputation does not read it (impute_stream's docstring).
+    The draws are Philox streams of `seed` (None: one from torch's generator); the offset starts at 0 and advances by the
+    number of rows after every repetition (trainer.impute_draw_counter), so no two calls of a run share a counter.  A model
+    outside the kernel's limits (obs_dim <= 128, latent_dim <= 16) raises VpcError: there is no fallback to the chain."""
+    if engine not in ("chain", "stream"):
+        raise L.VpcError(f"eval_vae_mnar: engine {engine!r} (engines: 'chain', 'stream')")
     with torch.no_grad():
         model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
@@ -569,7 +578,13 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
         N = data_test.shape[0]
         rows = max(1, max_decoder_rows // max(1, model.num_samples))
         temp_recon = []
-        for _ in range(M):
+        if engine == "stream" and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        for rep in range(M):
+            if engine == "stream":
+                XM = nm_impute_stream(model, data_test, mask_test, seed=seed, offset=rep * N)  # model.num_samples, as the chain
+                temp_recon.append(_rmse_unobserved(XM, data_test, mask_test))
+                continue
             XM = torch.zeros_like(data_test)
             mask_p = draw_mask_p(model, data_test.shape, mask_test, p_missingness, device)  # (for both classes: evaluate.py:30-31)
             for lo in range(0, N, rows):

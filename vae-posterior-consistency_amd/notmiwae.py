@@ -437,6 +437,85 @@ class notMIWAE_myversion(_NMBase):
         return self._loss(x, mask, None, (x_recon, x_logvar, mean, logvar), None, 0.0, _f32c(eps_kl), llh_eval)
 
 
+# ------------------------------------------------------------------------------------------------ streaming imputation
+STREAM_MAX_D, STREAM_MAX_L = 128, 16  # limits of csrc/vpc_nm_impute.hip
+
+
+def nm_impute_scratch(B, S, d, Ld, s_chunk):
+    """Floats of the partial buffer of nm_impute: B * ceil(S / s_chunk16) * (2 + d); 0 for a shape outside the kernel's
+    limits (obs_dim <= 128, latent_dim <= 16, B, S, s_chunk >= 1)."""
+    return int(lib().vpc_nm_impute_scratch(int(B), int(S), int(d), int(Ld), int(s_chunk)))
+
+
+def nm_impute(flat, x, mask, eps, seed, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk, regularised):
+    check(lib().vpc_nm_impute(ptr(flat), ptr(x), ptr(mask), ptr(eps), int(seed), int(offset), int(row0), ptr(part),
+                              part.numel(), ptr(xm), ptr(lse), int(B), int(S), int(d), int(Ld), int(s_chunk),
+                              int(bool(regularised)), stream_ptr()), "vpc_nm_impute")
+
+
+def impute_chunk(B, S, n_cu):
+    """The default s_chunk of impute_stream: miwae.impute_chunk's rule (as few chunks per row as still give one workgroup
+    per compute unit, the chunks of a row balanced), kept for this kernel by the sweep of profiles/nm_impute_notes.md."""
+    from .miwae import impute_chunk as rule  # (miwae imports this module)
+    return rule(B, S, n_cu)
+
+
+@torch.no_grad()
+def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=0, row0=0, s_chunk=None,
+                  return_lse=False, missing_process="selfmasking_known"):
+    """The llh_eval imputation of every row of x with num_samples draws (evaluate.py:13-69 through VAE.py:2398-2461 /
+    :2774-2813) in two launches: csrc/vpc_nm_impute.hip runs encoder, sampler, decoder, log-weights and an online softmax
+    per (row, chunk of s_chunk samples) and never writes a decoder row; the merge combines a row's chunks in chunk order.
+    Returns xm [B, d], or (xm, lse [B]) with return_lse: lse = the per-row log-sum-exp of -l_w.
+
+    mask_p is not an argument, for REG_notMIWAE_v2 too: the reference's imputation takes the q pass's weights and the q
+    pass's x_mean only (VAE.py:2458-2461), so the whole p pass - which evaluate.py:33-42 computes and drops - is skipped.
+
+    eps [2, B, S, L] injects the sampler's draw and, for notMIWAE_myversion, the fresh draw of :2791-2798 (plane 1 is not
+    read for the regularised class); otherwise both are drawn in the kernel from (seed, offset, row0) - seed None takes
+    one from torch's generator - by the rule of trainer.impute_draw_counter, which does not depend on s_chunk:
+    miwae.impute_draws returns those values, and rows [a, b) of a call equal the call on x[a:b] with row0 = a.  s_chunk
+    None: impute_chunk.  For a given s_chunk the result is bit-reproducible.  obs_dim <= 128, latent_dim <= 16; anything
+    else, CPU tensors, a wrong eps shape, s_chunk < 1 or a missing_process other than the default raise VpcError (no
+    fallback to the chain)."""
+    if not isinstance(model, _NMBase):
+        raise L.VpcError("notmiwae.impute_stream supports REG_notMIWAE_v2 and notMIWAE_myversion")
+    if missing_process != "selfmasking_known":
+        raise L.VpcError("impute_stream: only the reference's default missing_process='selfmasking_known' is accelerated")
+    d, Ld = model.obs_dim, model.latent_dim
+    S = model.num_samples if num_samples is None else int(num_samples)
+    require_cuda(x, mask, eps)
+    if not (1 <= d <= STREAM_MAX_D and 1 <= Ld <= STREAM_MAX_L):
+        raise L.VpcError(f"impute_stream supports obs_dim <= {STREAM_MAX_D} and latent_dim <= {STREAM_MAX_L}: got {d}, {Ld}")
+    xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
+    B = xf.shape[0]
+    if B < 1 or S < 1 or mf.shape != xf.shape:
+        raise L.VpcError(f"impute_stream: B = {B}, num_samples = {S}, mask {tuple(mf.shape)} for x {tuple(xf.shape)}")
+    if s_chunk is None:
+        s_chunk = impute_chunk(B, S, L.max_blocks() // 2)
+    if s_chunk < 1:
+        raise L.VpcError(f"impute_stream: s_chunk = {s_chunk} < 1")
+    if eps is not None:
+        if tuple(eps.shape) != (2, B, S, Ld):
+            raise L.VpcError(f"impute_stream: eps {tuple(eps.shape)}, expected {(2, B, S, Ld)}")
+        eps = _f32c(eps)
+    elif seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    n = nm_impute_scratch(B, S, d, Ld, s_chunk)
+    if n == 0:
+        raise L.VpcError(f"impute_stream: shape (B, S, d, L) = {(B, S, d, Ld)} is outside the kernel's limits")
+    flat = model.flatten_parameters()
+    require_cuda(flat)
+    if flat.numel() != 2 * d + model._n_enc + model._n_dec:  # the kernel reads the buffer by the offsets of _flat_spec
+        raise L.VpcError(f"impute_stream: flat parameter buffer of {flat.numel()} floats for (d, L) = {(d, Ld)}")
+    with torch.cuda.device(xf.device):
+        part = torch.empty(n, device=xf.device)
+        xm = torch.empty(B, d, device=xf.device)
+        lse = torch.empty(B, device=xf.device) if return_lse else None
+        nm_impute(flat, xf, mf, eps, seed or 0, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk, model.regularised)
+    return (xm, lse) if return_lse else xm
+
+
 # ------------------------------------------------------------------------------------------------ fused step
 # timer names of the chain launches, per layer, and the weight gradients' (timer name, index in the trainer's workspace)
 _ENC_FWD, _ENC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) * 3
