@@ -885,6 +885,65 @@ int vpc_miw_small_tail(const float* part, long part_floats, long R, int RB, int 
                        float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, long step,
                        void* stream);
 
+/* The small-batch step for G MIWAE or G Reg_MIWAE members of one (obs_dim <= 32, latent_dim <= 16, num_samples) in the same
+ * seven kernels, whatever G: the six reg_MIWAE* / vanilla_MIWAE* lines of Data/imputation_args.json under the drivers' loops
+ * `for missing: for alpha:` (src/experiment_main/imputation.py:21-39) as one launch set per batch.  Every multi kernel runs the
+ * stand-alone kernel's body (one piece of code for both forms) on member g's slices, so member g computes bit for bit what
+ * the stand-alone entries compute for it; no float atomics.
+ * Members: G device-resident VpcMiwMember records (24 bytes, ordinary loads) - what may differ from member to member
+ * besides parameters and data.  Pointers are member 0's.  Every workspace is the dense stack [G][..] of the stand-alone
+ * buffer of that name (xin [G][R][d], eps [G][2 P][B][S][L] with the P sampling planes first, h1 h2 [G][R][128], heads hact gh
+ * dht [G][R][2L], z [G][R S][L], g1 g2 [G][R S][128], Y Gy [G][R S][3d], mask_p [G][B][d]); x and mask are [B][d] shared by all
+ * members (stride 0) or [G][..] with a member stride >= B d floats; parameters, gradient and the Adam moments are rows of
+ * [G][row_stride] stacks, row_stride >= n_params.  partial blocks: [G][blocks_per_member][n_params] floats
+ * (vpc_miw_multi_workspace; G = 64, 32 blocks and d = 12, L = 10 (n = 43 320): 355 MB).
+ *   vpc_miw_multi_prep         (train.py:102-104 mask_p draw, VAE.py:3059-3061 / :3188-3190 x * mask, the rsample() draws of
+ *                              :3066 / :3087 / :3196 / :3216 / :3237) member g: vpc_nm_prep's mask_p, stacked xin and, with draw != 0,
+ *                              all 2 P eps planes, with seed_g and keep_prob_g and the counters of an unsharded stand-alone step
+ *                              (mask: element index / 4 + offset, eps: group index + offset_eps).  draw == 0: mask_p is read
+ *                              (injected), eps is not touched.  mask_p NULL: MIWAE (P = 1).
+ *   vpc_miw_small_fwd_multi    (VAE.py:3049-3076 / :3178-3206) vpc_miw_small_fwd per member: grid = ceil(R / RB) x G workgroups
+ *   vpc_miw_loss_multi         (VAE.py:3078-3100 / :3208-3265) vpc_miw_loss(raw = 1, ldy = ldg = 3d) per member in the same
+ *                              three launches; the pairing stays inside a member; alpha = alpha_g; out8 [G][8], loss_f32 [G],
+ *                              accum [G]; scratch = G x vpc_miw_loss_scratch(B, S) bytes
+ *   vpc_miw_small_bwd_multi    (the backward of train.py:115) member g gets blocks_per_member workgroups, workgroup j walks its
+ *                              row blocks j, j + blocks_per_member, .. and writes partial block (g, j).  blocks_per_member ==
+ *                              ceil(R / RB) <= CUs is the stand-alone grid: the same bits; fewer blocks: another summation order
+ *   vpc_miw_small_tail_multi   (train.py:116) member g's partial blocks summed in block order into grad[g], flat Adam with lr_g
+ * order (fwd, bwd): 0 = grid (blocks, G), member-major; 1 = grid (8 x blocks, ceil(G / 8)), all workgroups of a member on one
+ * XCD (its parameters through one L2).  Same bits.
+ * VPC_ERR_ARG before any launch: d > 32, L > 16, RB outside 1 .. 4, a NULL pointer, G outside 1 .. VPC_MIW_MULTI_MAX_MEMBERS,
+ * a member stride below its slice (x / mask: 0 or >= B d; rows: >= n_params), a partial buffer below
+ * G x blocks_per_member x n_params floats, blocks_per_member outside 1 .. min(ceil(R / RB), CUs), a scratch below G members',
+ * or blocks x G > VPC_MIW_MULTI_MAX_BLOCKS workgroups in the forward or backward launch. */
+#define VPC_MIW_MULTI_MAX_BLOCKS 65536
+#define VPC_MIW_MULTI_MAX_MEMBERS 4096
+typedef struct VpcMiwMember {
+    unsigned long long seed; /* Philox key of the member's draws */
+    float alpha;             /* Reg_MIWAE: loss = nb_q + alpha (KL_reg - nb_q + nb_p - reg_like) */
+    float keep_prob;         /* 1 - p_missingness / 100 */
+    float lr;
+    int reserved;
+} VpcMiwMember;
+long vpc_miw_multi_workspace(int G, int blocks_per_member, int d, int L);
+int vpc_miw_multi_prep(const float* x, long x_stride, const float* mask, long mask_stride, float* mask_p, float* xin,
+                       float* eps, const VpcMiwMember* members, int G, int draw, long B, int S, int d, int L,
+                       unsigned long long offset, unsigned long long offset_eps, void* stream);
+int vpc_miw_small_fwd_multi(const float* params, long param_stride, const float* xin, const float* eps, float* h1, float* h2,
+                            float* heads, float* hact, float* z, float* g1, float* g2, float* Y, int G, long R, int S, int d,
+                            int L, int RB, int order, void* stream);
+int vpc_miw_loss_multi(const float* x, long x_stride, const float* mask, long mask_stride, const float* mask_p, const float* Y,
+                       const float* hact, const float* eps, float* Gy, float* gh, void* scratch, long scratch_bytes,
+                       double* out8, float* loss_f32, float* accum, const VpcMiwMember* members, int G, long B, int S, int d,
+                       int L, int pairing, void* stream);
+int vpc_miw_small_bwd_multi(const float* params, long param_stride, const float* xin, const float* eps, const float* h1,
+                            const float* h2, const float* heads, const float* z, const float* g1, const float* g2,
+                            const float* Gy, const float* gh, float* dht, float* part, long part_floats, int G,
+                            int blocks_per_member, long R, int S, int d, int L, int RB, int order, void* stream);
+int vpc_miw_small_tail_multi(const float* part, long part_floats, int G, int blocks_per_member, int d, int L, float* grad,
+                             float* params, float* exp_avg, float* exp_avg_sq, long row_stride, const VpcMiwMember* members,
+                             float beta1, float beta2, float eps, long step, void* stream);
+
 /* Streaming importance-weighted imputation of the family (csrc/vpc_miw_impute.hip), for obs_dim <= 32, latent_dim <= 16:
  * what src/experiment_main/evaluate.py:89-113 computes one row at a time through the llh_eval branch of MIWAE.loss /
  * Reg_MIWAE.loss (VAE.py:3078-3099 / :3204-3258) - x_mean of S samples weighted by the softmax of their log-weights - for B

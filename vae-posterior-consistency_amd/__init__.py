@@ -16,6 +16,8 @@ from .harness import (create_missing_uci, create_missing_uci_drop_eddi, model_lo
                       mnar_result_path, eval_miwae, miwae_result_path)
 from . import miwae
 from .miwae import MIWAE, Reg_MIWAE, MIWTrainer
+from . import miw_ensemble
+from .miw_ensemble import MIWEnsembleTrainer
 from . import flow
 from .flow import VAEFlow, REG_VAEFlow, FlowTrainer
 from . import notmiwae
@@ -43,4 +45,5 @@ __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedT
            "chaini_II_ratio_version", "active_learning_flow", "ais", "ais_chains", "ais_trajectory", "eval_ais",
            "ensemble", "EnsembleTrainer", "stack_models", "train_sweep", "EnsembleEvaluator", "eval_sweep",
            "EnsembleAcquirer", "active_sweep", "MaskEnsembleTrainer", "EDDIEnsembleTrainer",
-           "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator", "MaskEnsembleAcquirer", "EDDIEnsembleAcquirer"]
+           "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator", "MaskEnsembleAcquirer", "EDDIEnsembleAcquirer",
+           "miw_ensemble", "MIWEnsembleTrainer"]

@@ -158,6 +158,13 @@ _PROTOS = {
     "vpc_miw_small_fwd": [P] * 11 + [L_, I, I, I, I, P],
     "vpc_miw_small_bwd": [P] * 13 + [L_, L_, I, I, I, I, P],
     "vpc_miw_small_tail": [P, L_, L_, I, I, I, P, P, P, P, F, F, F, F, L_, P],
+    # the small-batch MIWAE step for G members (csrc/vpc_miw_small.hip, vpc_miw.hip, vpc_misc.hip)
+    "vpc_miw_multi_workspace": [I, I, I, I],
+    "vpc_miw_multi_prep": [P, L_, P, L_, P, P, P, P, I, I, L_, I, I, I, ULL, ULL, P],
+    "vpc_miw_small_fwd_multi": [P, L_] + [P] * 10 + [I, L_, I, I, I, I, I, P],
+    "vpc_miw_loss_multi": [P, L_, P, L_] + [P] * 7 + [L_, P, P, P, P, I, L_, I, I, I, I, P],
+    "vpc_miw_small_bwd_multi": [P, L_] + [P] * 12 + [L_, I, I, L_, I, I, I, I, I, P],
+    "vpc_miw_small_tail_multi": [P, L_, I, I, I, I, P, P, P, P, L_, P, F, F, F, L_, P],
     # streaming MIWAE imputation (csrc/vpc_miw_impute.hip)
     "vpc_miw_impute_scratch": [L_, I, I, I, I],
     "vpc_miw_impute": [P, P, P, P, ULL, ULL, L_, P, L_, P, P, L_, I, I, I, I, P],
@@ -194,7 +201,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_multi_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
 
 _lib = None
 

@@ -592,27 +592,40 @@ __global__ void nm_prep_kernel(const float* __restrict__ x, const float* __restr
                                float* __restrict__ xin, long n, float keep_prob, float* __restrict__ eps, long n_eps,
                                uint64_t seed, uint64_t offset, uint64_t offset_eps, unsigned gm,
                                const long long* __restrict__ state, long elem_lo, EpsShard sh) {
-    if (state) { offset += (uint64_t)state[1]; offset_eps += (uint64_t)state[1]; }
-    if (blockIdx.x >= gm) {
-        fill_normal_body(eps, n_eps, seed, offset_eps, (long)(blockIdx.x - gm) * blockDim.x + threadIdx.x, sh);
-        return;
-    }
-    offset += (uint64_t)(elem_lo >> 2);  // counter of a mask group = its index in the GLOBAL [B_global][d] array
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long i0 = g * 4;
-    if (i0 >= n) return;
-    U4 r{0, 0, 0, 0};
-    if (mp) r = philox((uint64_t)g + offset, 0u, seed);
-    const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
-    for (int j = 0; j < 4 && i0 + j < n; ++j) {
-        const float xv = x[i0 + j], mv = m[i0 + j];
-        xin[i0 + j] = xv * mv;
-        if (mp) {
-            const float pv = u01(rr[j]) < keep_prob ? mv : 0.f;
-            mp[i0 + j] = pv;
-            xin[n + i0 + j] = xv * pv;
-        }
-    }
+#define NM_PREP_DRAWS_MP mp
+#define NM_PREP_MP(drawn) drawn
+#define NM_PREP_KEEP_MP
+#include "vpc_nm_prep_body.h"
+#undef NM_PREP_DRAWS_MP
+#undef NM_PREP_MP
+#undef NM_PREP_KEEP_MP
+}
+// The prep of G MIWAE-path members in one launch (vpc_miw_multi_prep): blockIdx.y = member, which runs nm_prep_kernel's body
+// on its slices with its seed and keep probability - an unsharded batch, no device-side state, the counters of a stand-alone
+// step.  x0 / m0: member strides sx / sm (0: shared); mp0 [G][n], xin0 [G][P n], eps0 [G][n_eps] dense.  mp_given: mask_p is
+// read (injected draws), not drawn.
+__global__ void nm_prep_multi_kernel(const float* __restrict__ x0, long sx, const float* __restrict__ m0, long sm,
+                                     float* __restrict__ mp0, float* __restrict__ xin0, long n, float* __restrict__ eps0,
+                                     long n_eps, const VpcMiwMember* __restrict__ members, uint64_t offset,
+                                     uint64_t offset_eps, unsigned gm, int mp_given) {
+    const long mem = blockIdx.y;
+    const float* __restrict__ x = x0 + mem * sx;
+    const float* __restrict__ m = m0 + mem * sm;
+    float* __restrict__ mp = mp0 ? mp0 + mem * n : nullptr;
+    float* __restrict__ xin = xin0 + mem * (mp0 ? 2 : 1) * n;
+    float* __restrict__ eps = eps0 ? eps0 + mem * n_eps : nullptr;
+    const float keep_prob = members[mem].keep_prob;
+    const uint64_t seed = members[mem].seed;
+    const long long* state = nullptr;
+    const long elem_lo = 0;
+    const EpsShard sh{0, 0, 0, 4};
+#define NM_PREP_DRAWS_MP (mp && !mp_given)
+#define NM_PREP_MP(drawn) (mp_given ? mp[i0 + j] : (drawn))
+#define NM_PREP_KEEP_MP if (!mp_given)
+#include "vpc_nm_prep_body.h"
+#undef NM_PREP_DRAWS_MP
+#undef NM_PREP_MP
+#undef NM_PREP_KEEP_MP
 }
 
 }  // namespace vpc
@@ -1122,5 +1135,22 @@ extern "C" int vpc_nm_prep(const float* x, const float* mask, float* mask_p_out,
     hipLaunchKernelGGL(nm_prep_kernel, dim3(gm + gn), dim3(256), 0, (hipStream_t)stream, x, mask, mask_p_out, xin, n,
                        keep_prob, eps_out, n_eps, (uint64_t)seed, (uint64_t)offset, (uint64_t)offset_eps, gm, state,
                        elem_lo, EpsShard{eps_rows_local, eps_rows_global, eps_row_lo, eps_pitch});
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+extern "C" int vpc_miw_multi_prep(const float* x, long x_stride, const float* mask, long mask_stride, float* mask_p, float* xin,
+                                  float* eps, const VpcMiwMember* members, int G, int draw, long B, int S, int d, int L,
+                                  unsigned long long offset, unsigned long long offset_eps, void* stream) {
+    if (!x || !mask || !xin || !members || (draw && !eps)) return VPC_ERR_ARG;
+    if (G < 1 || G > VPC_MIW_MULTI_MAX_MEMBERS || B <= 0 || S <= 0 || d <= 0 || d > 32 || L <= 0 || L > 16 ||
+        B * S > (1L << 24))
+        return VPC_ERR_ARG;
+    if ((x_stride != 0 && x_stride < B * d) || (mask_stride != 0 && mask_stride < B * d)) return VPC_ERR_ARG;
+    const long n = B * d, groups = (n + 3) / 4;
+    const long n_eps = draw ? 2 * (mask_p ? 2 : 1) * B * S * L : 0, ge = (n_eps + 3) / 4;
+    const unsigned gm = (unsigned)((groups + 255) / 256), gn = (unsigned)((ge + 255) / 256);
+    hipLaunchKernelGGL(nm_prep_multi_kernel, dim3(gm + gn, (unsigned)G), dim3(256), 0, (hipStream_t)stream, x, x_stride, mask,
+                       mask_stride, mask_p, xin, n, draw ? eps : nullptr, n_eps, members, (uint64_t)offset,
+                       (uint64_t)offset_eps, gm, draw ? 0 : 1);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }

@@ -10,6 +10,9 @@
 //                    grad   per element: decoder-head gradients; per (pass, row, l): encoder-head gradients; one
 //                           workgroup reduces the loss partials in a fixed order into out8
 //
+//   miw_loss_multi the same three launches for G members of an ensemble (blockIdx.y = member; vpc_miw_loss_multi): the
+//                  kernel bodies are the text fragments vpc_miw_rows_body.h / _slots_body.h / _grad_body.h of both forms
+//
 // The pairing couples rows across the whole batch, so the exchange between the per-row sums and the per-slot
 // log-sum-exp goes through a scratch buffer between launches.  No float atomics; bit-reproducible.
 #include "vpc_abi_internal.h"
@@ -36,70 +39,15 @@ struct MiwLossArgs {
     float alpha;
 };
 
+// The three kernel bodies are text fragments shared with the ensemble kernels below (vpc_miw_*_body.h).  Stand-alone: a member's
+// array is the pointer itself.
+#define MIW_AT(p, f) (p)
+#define MIW_OUT(p, k) (p)
+#define MIW_ALPHA a.alpha
+
 // ---- launch 1: one wave per (pass, row b, sample s)
 __global__ void __launch_bounds__(256) miw_rows_kernel(MiwLossArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long N = (long)a.B * a.S;
-    const long gw = (long)blockIdx.x * MIW_WAVES + (threadIdx.x >> 6);
-    if (gw >= a.P * N) return;
-    const int p = (int)(gw / N);
-    const long r = gw - p * N;
-    const int b = (int)(r / a.S), s = (int)(r - (long)b * a.S);
-    const int d = a.d, L = a.L;
-    const float* x = a.x + (long)b * d;
-    const float* mq = a.m + (long)b * d;
-    const float* mpp = a.mp ? a.mp + (long)b * d : nullptr;
-    const float* mrow = p == 0 ? mq : mpp;
-    const float* y = a.y[p] + r * a.ldy;
-    float so = 0.f, sm = 0.f, sr = 0.f;
-    for (int k = lane; k < d; k += 64) {
-        const MiwHead h = miw_head(y, d, k, a.raw);
-        const float lp = miw_student_lp(x[k], h);
-        so += lp * mrow[k];
-        if (p == 0) {
-            sm += lp * (1.f - mq[k]);
-            if (mpp) sr += lp * mq[k] * (1.f - mpp[k]);
-        }
-    }
-    // logpz - logq of the fresh draw z2 = mean + scale * e (VAE.py:3087-3091 / :3216-3220, :3237-3240)
-    const float* hh = a.h[p] + (long)b * 2 * L;
-    const float* e = a.e[p] + r * L;
-    float slw = 0.f;
-    for (int l = lane; l < L; l += 64) {
-        const float mu = hh[l], sc = hh[L + l];
-        const float z = mu + sc * e[l];
-        const float dz = z - mu;
-        const float lpz = -0.5f * z * z - MIW_HALF_LOG_2PI;
-        const float lq = -(dz * dz) / (2.f * sc * sc) - logf(sc) - MIW_HALF_LOG_2PI;
-        slw += lpz - lq;
-    }
-    so = miw_wave_sum(so);
-    slw = miw_wave_sum(slw);
-    if (p == 0) {
-        sm = miw_wave_sum(sm);
-        sr = miw_wave_sum(sr);
-    }
-    float skl = 0.f;
-    const bool do_kl = p == 0 && a.P == 2 && s == 0;
-    if (do_kl) {  // KL(N(mean_q, scale_q) || N(mean_p, scale_p)) summed over l (VAE.py:3249, :3253-3258)
-        const float* hp = a.h[1] + (long)b * 2 * L;
-        for (int l = lane; l < L; l += 64) {
-            const float r1 = hh[L + l] / hp[L + l];
-            const float vr = r1 * r1;
-            const float t1 = (hh[l] - hp[l]) / hp[L + l];
-            skl += 0.5f * (vr + t1 * t1 - 1.f - logf(vr));
-        }
-        skl = miw_wave_sum(skl);
-    }
-    if (lane == 0) {
-        a.lpo[p][r] = so;
-        a.lw[p][r] = slw;
-        if (p == 0) {
-            a.lpm[r] = sm;
-            if (a.P == 2) a.rl[r] = sr;
-        }
-        if (do_kl) a.kl[b] = skl;
-    }
+#include "vpc_miw_rows_body.h"
 }
 
 // the row of the likelihood term in slot (i, j): reference pairing = flat index i*B + j of the [S, B] reshape of the
@@ -110,159 +58,68 @@ __device__ __forceinline__ long miw_lpo_row(int pairing, int i, int j, int B, in
 
 // ---- launch 2: one wave per slot j, both passes; four waves per workgroup -> one row of partials per workgroup
 __global__ void __launch_bounds__(256) miw_slots_kernel(MiwLossArgs a) {
-    __shared__ double sh[MIW_WAVES][5];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int j = blockIdx.x * MIW_WAVES + wv;
-    const int B = a.B, S = a.S;
-    float lse[2] = {0.f, 0.f}, srl = 0.f, skl = 0.f, slm = 0.f;
-    if (j < B) {
-        for (int p = 0; p < a.P; ++p) {
-            float mx = -INFINITY;
-            for (int i = lane; i < S; i += 64)
-                mx = fmaxf(mx, a.lpo[p][miw_lpo_row(a.pairing, i, j, B, S)] + a.lw[p][(long)j * S + i]);
-            mx = miw_wave_max(mx);
-            float se = 0.f;
-            for (int i = lane; i < S; i += 64)
-                se += expf(a.lpo[p][miw_lpo_row(a.pairing, i, j, B, S)] + a.lw[p][(long)j * S + i] - mx);
-            se = miw_wave_sum(se);
-            lse[p] = mx + logf(se);
-            // gradient seed of the slot: d loss / d a[i, j] = coef * softmax_i
-            const float coef = a.P == 2 ? (p == 0 ? -(1.f - a.alpha) : -a.alpha) / B : -1.f / B;
-            if (a.gy[0]) {
-                for (int i = lane; i < S; i += 64) {
-                    const long ro = miw_lpo_row(a.pairing, i, j, B, S), rw = (long)j * S + i;
-                    const float w = expf(a.lpo[p][ro] + a.lw[p][rw] - lse[p]);
-                    a.gpo[p][ro] = coef * w;
-                    a.gw[p][rw] = coef * w;
-                }
-            }
-        }
-        // llh_eval: the q-pass weights of slot j applied to the un-mixed x_mean[j, i, :] (VAE.py:3096-3098 / :3267-3269)
-        if (a.xm_imp) {
-            for (int k = lane; k < a.d; k += 64) {
-                float acc = 0.f;
-                for (int i = 0; i < S; ++i) {
-                    const long rw = (long)j * S + i;
-                    const float w = expf(a.lpo[0][miw_lpo_row(a.pairing, i, j, B, S)] + a.lw[0][rw] - lse[0]);
-                    const float* y = a.y[0] + rw * a.ldy;
-                    acc += w * (a.raw ? miw_sigmoid(y[k]) : y[k]);
-                }
-                a.xm_imp[(long)j * a.d + k] = acc;
-            }
-        }
-        // per-row sums of the same workgroup's rows (rows j*S .. j*S + S - 1)
-        for (int s = lane; s < S; s += 64) {
-            slm += a.lpm[(long)j * S + s];
-            if (a.P == 2) srl += a.rl[(long)j * S + s];
-        }
-        slm = miw_wave_sum(slm);
-        srl = miw_wave_sum(srl);
-        if (a.P == 2) skl = a.kl[j];
-    }
-    if (lane == 0) {
-        sh[wv][0] = lse[0]; sh[wv][1] = lse[1]; sh[wv][2] = srl; sh[wv][3] = skl; sh[wv][4] = slm;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        double t = 0.0;
-        for (int w = 0; w < MIW_WAVES; ++w) t += sh[w][threadIdx.x];
-        a.part[(long)blockIdx.x * 8 + threadIdx.x] = t;
-    }
+#include "vpc_miw_slots_body.h"
 }
 
 // ---- launch 3: gradients + the fixed-order loss reduction
 __global__ void __launch_bounds__(256) miw_grad_kernel(MiwLossArgs a, int nblk_elem, int nblk_head) {
-    const int B = a.B, S = a.S, d = a.d, L = a.L;
-    const long N = (long)B * S;
-    if ((int)blockIdx.x < nblk_elem) {
-        const long t = (long)blockIdx.x * 256 + threadIdx.x;
-        if (t >= a.P * N * d) return;
-        const int p = (int)(t / (N * d));
-        const long rem = t - p * N * d;
-        const long r = rem / d;
-        const int k = (int)(rem - r * d);
-        const int b = (int)(r / S);
-        const float mq = a.m[(long)b * d + k];
-        const float mv = p == 0 ? mq : a.mp[(long)b * d + k];
-        float g = a.gpo[p][r] * mv;
-        if (p == 0 && a.P == 2) g -= a.alpha / (float)N * mq * (1.f - a.mp[(long)b * d + k]);  // - alpha * reg_like
-        const MiwHead h = miw_head(a.y[p] + r * a.ldy, d, k, a.raw);
-        const float x = a.x[(long)b * d + k];
-        const float y = (x - h.mu) / h.sc;
-        const float tt = y * y / h.v, u = 1.f + tt;
-        float gmu = g * (h.v + 1.f) * y / (h.v * h.sc * u);
-        float gsc = g * (-1.f / h.sc + (h.v + 1.f) * tt / (h.sc * u));
-        float gv = g * (miw_half_digamma_diff(h.v) - 0.5f / h.v - 0.5f * log1pf(tt) + (h.v + 1.f) * tt / (2.f * h.v * u));
-        if (a.raw) {
-            gmu *= miw_sigmoid_d(h.a0);
-            gsc *= miw_softplus_d(h.a1);
-            gv *= miw_softplus_d(h.a2);
-        }
-        float* go = a.gy[p] + r * a.ldg;
-        go[k] = gmu;
-        go[d + k] = gsc;
-        go[2 * d + k] = gv;
-        return;
-    }
-    if ((int)blockIdx.x < nblk_elem + nblk_head) {
-        const long t = (long)(blockIdx.x - nblk_elem) * 256 + threadIdx.x;
-        if (t >= (long)a.P * B * L) return;
-        const int p = (int)(t / ((long)B * L));
-        const long rem = t - (long)p * B * L;
-        const int b = (int)(rem / L), l = (int)(rem - (long)b * L);
-        const float* hh = a.h[p] + (long)b * 2 * L;
-        const float mu = hh[l], sc = hh[L + l];
-        float gm = 0.f, gs = 0.f;
-        for (int s = 0; s < S; ++s) {  // d(logpz - logq)/d mean = -z2, d/d scale = -z2 e + 1/scale
-            const long r = (long)b * S + s;
-            const float e = a.e[p][r * L + l];
-            const float z = mu + sc * e;
-            const float w = a.gw[p][r];
-            gm -= w * z;
-            gs += w * (1.f / sc - z * e);
-        }
-        if (a.P == 2) {  // + alpha * d KL_reg, KL_reg = mean over [B, S, L] (each (b, l) S times)
-            const float* hq = a.h[0] + (long)b * 2 * L;
-            const float* hp = a.h[1] + (long)b * 2 * L;
-            const float mq = hq[l], sq = hq[L + l], mp = hp[l], sp = hp[L + l];
-            const float c = a.alpha / ((float)B * L);
-            const float dm = mq - mp, isp2 = 1.f / (sp * sp);
-            if (p == 0) {
-                gm += c * dm * isp2;
-                gs += c * (sq * isp2 - 1.f / sq);
-            } else {
-                gm -= c * dm * isp2;
-                gs += c * (1.f / sp - (sq * sq + dm * dm) * isp2 / sp);
-            }
-        }
-        float* go = a.gh[p] + (long)b * 2 * L;
-        go[l] = gm;
-        go[L + l] = gs;
-        return;
-    }
-    // the last workgroup: loss partials of the slot launch, summed in block order
-    __shared__ double tot[5];
-    if (threadIdx.x < 5) {
-        double t = 0.0;
-        for (int i = 0; i < a.nslot_blocks; ++i) t += a.part[(long)i * 8 + threadIdx.x];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double nb_q = -tot[0] / B;
-        const double nb_p = a.P == 2 ? -tot[1] / B : 0.0;
-        const double reg_like = tot[2] / (double)N;
-        const double kl = tot[3] / ((double)B * L);
-        const double al = a.alpha;
-        const double loss = a.P == 2 ? nb_q + al * (kl - nb_q + nb_p - reg_like) : nb_q;  // VAE.py:3250-3251
-        double* o = a.out8;
-        o[0] = loss; o[1] = nb_q; o[2] = nb_p; o[3] = kl; o[4] = reg_like;
-        o[5] = tot[4] / ((double)B * 5000.0);  // VAE.py:3099: logpxobsgivenz_imp.sum() / (B * 5000), a literal
-        o[6] = tot[0]; o[7] = tot[1];
-        if (a.loss_f32) a.loss_f32[0] = (float)loss;
-        if (a.accum) a.accum[0] += (float)loss;
-    }
+#include "vpc_miw_grad_body.h"
 }
+
+#undef MIW_AT
+#undef MIW_OUT
+#undef MIW_ALPHA
+
+// ---- the three launches for G members (vpc_miw_loss_multi): blockIdx.y = member; x / mask shared (stride 0) or per member,
+// every other array the dense [G][..] stack of the stand-alone one, the scratch one stand-alone scratch per member
+struct MiwLossMultiArgs {
+    MiwLossArgs base;  // member 0
+    const VpcMiwMember* members;
+    long sx, sm;       // member strides of x and mask in floats
+    long sscr;         // bytes of one member's scratch (a multiple of 64)
+};
+// where this workgroup's member sits behind the pointers of the base record, in elements of each array, and its alpha
+struct MiwLossMem {
+    long x, m, mp;   // data, mask, mask_p
+    long y, h, e;    // decoder heads and their gradients; encoder heads and theirs; the draws
+    long scr, part;  // the float arrays of the scratch; its double partials
+    long out;        // out8 (x 8), loss_f32, accum
+    float alpha;
+};
+__device__ __forceinline__ MiwLossMem miw_loss_member(const MiwLossMultiArgs& ma) {
+    const MiwLossArgs& b = ma.base;
+    const long g = blockIdx.y, N = (long)b.B * b.S, R = (long)b.P * b.B;
+    MiwLossMem mo;
+    mo.x = g * ma.sx; mo.m = g * ma.sm; mo.mp = g * b.B * b.d;
+    mo.y = g * b.P * N * 3 * b.d;  // [P B S][3 d] per member
+    mo.h = g * R * 2 * b.L;        // [P B][2 L]
+    mo.e = g * 2 * b.P * N * b.L;  // [2 P][B][S][L]
+    mo.scr = g * (ma.sscr / 4); mo.part = g * (ma.sscr / 8);
+    mo.out = g;
+    mo.alpha = ma.members[g].alpha;
+    return mo;
+}
+#define MIW_AT(p, f) ((p) + mo.f)
+#define MIW_OUT(p, k) ((p) + (k) * mo.out)
+#define MIW_ALPHA mo.alpha
+__global__ void __launch_bounds__(256) miw_rows_multi_kernel(MiwLossMultiArgs ma) {
+    const MiwLossArgs& a = ma.base;
+    const MiwLossMem mo = miw_loss_member(ma);
+#include "vpc_miw_rows_body.h"
+}
+__global__ void __launch_bounds__(256) miw_slots_multi_kernel(MiwLossMultiArgs ma) {
+    const MiwLossArgs& a = ma.base;
+    const MiwLossMem mo = miw_loss_member(ma);
+#include "vpc_miw_slots_body.h"
+}
+__global__ void __launch_bounds__(256) miw_grad_multi_kernel(MiwLossMultiArgs ma, int nblk_elem, int nblk_head) {
+    const MiwLossArgs& a = ma.base;
+    const MiwLossMem mo = miw_loss_member(ma);
+#include "vpc_miw_grad_body.h"
+}
+#undef MIW_AT
+#undef MIW_OUT
+#undef MIW_ALPHA
 
 __global__ void miw_sample_kernel(const float* __restrict__ heads, float* __restrict__ hact, const float* __restrict__ eps,
                                   float* __restrict__ z, long R, int S, int L) {
@@ -413,6 +270,53 @@ int vpc_miw_loss(const float* x, const float* mask, const float* mask_p, const f
     const long nh = grad ? ((long)a.P * B * L + 255) / 256 : 0;
     if (ne + nh + 1 > 0x7fffffffL) return VPC_ERR_ARG;
     hipLaunchKernelGGL(miw_grad_kernel, dim3((unsigned)(ne + nh + 1)), dim3(256), 0, st, a, (int)ne, (int)nh);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_miw_loss_multi(const float* x, long x_stride, const float* mask, long mask_stride, const float* mask_p, const float* Y,
+                       const float* hact, const float* eps, float* Gy, float* gh, void* scratch, long scratch_bytes,
+                       double* out8, float* loss_f32, float* accum, const VpcMiwMember* members, int G, long B, int S, int d,
+                       int L, int pairing, void* stream) {
+    if (!x || !mask || !Y || !hact || !eps || !Gy || !gh || !scratch || !out8 || !members) return VPC_ERR_ARG;
+    if (G < 1 || G > VPC_MIW_MULTI_MAX_MEMBERS || B <= 0 || S <= 0 || d <= 0 || d > 32 || L <= 0 || L > 16 ||
+        B * S > (1L << 24))
+        return VPC_ERR_ARG;
+    if (pairing != VPC_MIW_PAIR_REFERENCE && pairing != VPC_MIW_PAIR_PER_ROW) return VPC_ERR_ARG;
+    if ((x_stride != 0 && x_stride < B * d) || (mask_stride != 0 && mask_stride < B * d)) return VPC_ERR_ARG;
+    const long sscr = vpc_miw_loss_scratch(B, S);
+    if (scratch_bytes < G * sscr || ((uintptr_t)scratch & 7u)) return VPC_ERR_ARG;
+    const int P = mask_p ? 2 : 1;
+    const long N = B * S;
+    MiwLossMultiArgs ma{};
+    MiwLossArgs& a = ma.base;
+    a.x = x; a.m = mask; a.mp = mask_p;
+    a.y[0] = Y; a.y[1] = P == 2 ? Y + N * 3 * d : nullptr; a.ldy = 3 * d; a.raw = 1;
+    a.h[0] = hact; a.h[1] = P == 2 ? hact + B * 2 * L : nullptr;
+    a.e[0] = eps + P * N * L; a.e[1] = P == 2 ? eps + (P + 1) * N * L : nullptr;  // behind the P sampling planes
+    a.gy[0] = Gy; a.gy[1] = P == 2 ? Gy + N * 3 * d : nullptr; a.ldg = 3 * d;
+    a.gh[0] = gh; a.gh[1] = P == 2 ? gh + B * 2 * L : nullptr;
+    float* f = (float*)scratch;
+    for (int p = 0; p < 2; ++p) {
+        a.lpo[p] = f; f += N;
+        a.lw[p] = f; f += N;
+        a.gpo[p] = f; f += N;
+        a.gw[p] = f; f += N;
+    }
+    a.lpm = f; f += N;
+    a.rl = f; f += N;
+    a.kl = f; f += B;
+    const long fbytes = (((long)(f - (float*)scratch) * 4 + 63) / 64) * 64;
+    a.part = (double*)((char*)scratch + fbytes);
+    a.out8 = out8; a.loss_f32 = loss_f32; a.accum = accum;
+    a.B = (int)B; a.S = S; a.d = d; a.L = L; a.P = P; a.pairing = pairing;
+    a.nslot_blocks = (int)miw_slot_blocks(B);
+    ma.members = members; ma.sx = x_stride; ma.sm = mask_stride; ma.sscr = sscr;
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = P * N, ne = (P * N * d + 255) / 256, nh = ((long)P * B * L + 255) / 256;
+    const unsigned g = (unsigned)G;
+    hipLaunchKernelGGL(miw_rows_multi_kernel, dim3((unsigned)((rows + MIW_WAVES - 1) / MIW_WAVES), g), dim3(256), 0, st, ma);
+    hipLaunchKernelGGL(miw_slots_multi_kernel, dim3((unsigned)a.nslot_blocks, g), dim3(256), 0, st, ma);
+    hipLaunchKernelGGL(miw_grad_multi_kernel, dim3((unsigned)(ne + nh + 1), g), dim3(256), 0, st, ma, (int)ne, (int)nh);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

@@ -15,6 +15,10 @@
 //                          then the second loop runs the encoder backward on the same row blocks in the same registers.
 //   miw_small_tail_kernel  partial blocks summed in workgroup order into the flat gradient, flat Adam.
 //
+//   miw_small_*_multi_kernel  the three for G members of an ensemble in one launch each (miw_ensemble.MIWEnsembleTrainer): the
+//                          kernel bodies are the text fragments vpc_miw_small_fwd_body.h / vpc_miw_small_bwd_body.h, which both
+//                          forms include; the head of a multi kernel builds member g's MiwSmallArgs in registers.
+//
 // The loss between the two (vpc_miw_loss on the raw heads) stays the three launches of vpc_miw.hip: the reference's row /
 // sample pairing couples rows across the whole batch.  No float atomics, fixed summation orders: bit-reproducible.
 #include "vpc_abi_internal.h"
@@ -93,109 +97,9 @@ static_assert(F_COUNT * SBUF * 4 <= 65536, "static LDS");
 // YT = tiles of the 3 d decoder heads (1 .. 6), LT = tiles of the 2 L encoder heads (1, 2); DT = tiles of d
 template <int YT, int LT>
 __global__ __launch_bounds__(THREADS) void miw_small_fwd_kernel(MiwSmallArgs a) {
-    constexpr int DT = YT <= 3 ? 1 : 2;
-    __shared__ __attribute__((aligned(16))) float lds[F_COUNT * SBUF];
-    auto buf = [&](int b) { return lds + b * SBUF; };
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int d = a.d, L = a.L, S = a.S;
-    const MiwOff o(d, L);
-    const float* P = a.prm;
-    const long r0 = (long)blockIdx.x * a.RB;
-    const int nr = a.R - r0 < a.RB ? (int)(a.R - r0) : a.RB;
-    int cc = c, qq = q;
-    // ================================================================ encoder: one tile, rows past nr dead
-    f32x4 fW1[DT], fW2[8], fW3[8];
-    miw_ldA<DT>(P + o.We1, MIW_HID, d, w, cc, qq, fW1);
-    miw_stage(buf(F_X), a.xin, r0, nr, d, DT);
-    miw_ldA<8>(P + o.We2, MIW_HID, MIW_HID, w, cc, qq, fW2);
-    lds_barrier();
-    launder(cc, qq);
-    {
-        const f32x4 v = relu4(miw_mm<DT>(fW1, buf(F_X), cc, qq, miw_bias(P + o.be1, MIW_HID, w, qq)));
-        st_act(buf(F_H1), w, cc, qq, v);
-        if (cc < nr) *reinterpret_cast<f32x4*>(a.h1 + (r0 + cc) * MIW_HID + 16 * w + 4 * qq) = v;
-    }
-    if (w < LT) miw_ldA<8>(P + o.Wh, 2 * L, MIW_HID, w, cc, qq, fW3);
-    lds_barrier();
-    launder(cc, qq);
-    {
-        const f32x4 v = relu4(miw_mm<8>(fW2, buf(F_H1), cc, qq, miw_bias(P + o.be2, MIW_HID, w, qq)));
-        st_act(buf(F_H2), w, cc, qq, v);
-        if (cc < nr) *reinterpret_cast<f32x4*>(a.h2 + (r0 + cc) * MIW_HID + 16 * w + 4 * qq) = v;
-    }
-    // the decoder's fragments do not change from tile to tile: requested once, here
-    f32x4 fW4[1], fW5[8], fW6[8];
-    miw_ldA<1>(P + o.Wd1, MIW_HID, L, w, cc, qq, fW4);
-    miw_ldA<8>(P + o.Wd2, MIW_HID, MIW_HID, w, cc, qq, fW5);
-    if (w < YT) miw_ldA<8>(P + o.Wx, 3 * d, MIW_HID, w, cc, qq, fW6);
-    const f32x4 bias4 = miw_bias(P + o.bd1, MIW_HID, w, qq), bias5 = miw_bias(P + o.bd2, MIW_HID, w, qq);
-    const f32x4 bias6 = miw_bias(P + o.bx, 3 * d, w < YT ? w : 0, qq);
-    lds_barrier();
-    launder(cc, qq);
-    if (w < LT) {  // heads: raw to the workspace, (mean | softplus(raw)) to the workspace and to LDS for the sampler
-        const f32x4 v = miw_mm<8>(fW3, buf(F_H2), cc, qq, miw_bias(P + o.bh, 2 * L, w, qq));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int f = 16 * w + 4 * qq + j;
-            const float act = f < L ? v[j] : miw_softplus(v[j]);
-            buf(F_HD)[cc * SP + f] = act;
-            if (cc < nr && f < 2 * L) {
-                a.heads[(r0 + cc) * 2 * L + f] = v[j];
-                a.hact[(r0 + cc) * 2 * L + f] = act;
-            }
-        }
-    }
-    lds_barrier();
-    launder(cc, qq);
-    // ================================================================ decoder: the nr S rows r0 S .. in tiles of 16
-    const int nrows = nr * S;
-    const long drow0 = r0 * S;
-    const int zr = threadIdx.x >> 4, zl = threadIdx.x & 15;
-    auto eps_of = [&](int t0) {  // this thread's draw of the tile at t0: requested one tile ahead
-        return (threadIdx.x < 256 && t0 + zr < nrows && zl < L) ? a.eps[(drow0 + t0 + zr) * L + zl] : 0.f;
-    };
-    float e_next = eps_of(0);
-    for (int t0 = 0; t0 < nrows; t0 += 16) {
-        if (threadIdx.x < 256) {  // z = mean + eps * scale (miw_sample_kernel), columns past L and dead rows 0
-            const int row = t0 + zr;
-            float zv = 0.f;
-            if (row < nrows && zl < L) {
-                const int b = row / S;
-                const float mu = buf(F_HD)[b * SP + zl], sc = buf(F_HD)[b * SP + L + zl];
-                zv = mu + e_next * sc;
-                a.z[(drow0 + row) * L + zl] = zv;
-            }
-            buf(F_Z)[zr * SP + zl] = zv;
-        }
-        lds_barrier();
-        launder(cc, qq);
-        e_next = eps_of(t0 + 16);
-        const bool live = t0 + cc < nrows;
-        const long grow = drow0 + t0 + cc;
-        {
-            const f32x4 v = relu4(miw_mm<1>(fW4, buf(F_Z), cc, qq, bias4));
-            st_act(buf(F_G1), w, cc, qq, v);
-            if (live) *reinterpret_cast<f32x4*>(a.g1 + grow * MIW_HID + 16 * w + 4 * qq) = v;
-        }
-        lds_barrier();
-        launder(cc, qq);
-        {
-            const f32x4 v = relu4(miw_mm<8>(fW5, buf(F_G1), cc, qq, bias5));
-            st_act(buf(F_G2), w, cc, qq, v);
-            if (live) *reinterpret_cast<f32x4*>(a.g2 + grow * MIW_HID + 16 * w + 4 * qq) = v;
-        }
-        lds_barrier();
-        launder(cc, qq);
-        if (w < YT) {
-            const f32x4 v = miw_mm<8>(fW6, buf(F_G2), cc, qq, bias6);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int f = 16 * w + 4 * qq + j;
-                if (live && f < 3 * d) a.Y[grow * 3 * d + f] = v[j];
-            }
-        }
-        // (no barrier: the next tile's first write to a buffer lies behind a barrier every reader of this tile has passed)
-    }
+#define MIW_BLK blockIdx.x
+#include "vpc_miw_small_fwd_body.h"
+#undef MIW_BLK
 }
 
 enum { K_DP = 0, K_A2, K_A1, K_Z, K_DA2, K_DA1, K_COUNT };
@@ -203,189 +107,16 @@ static_assert(K_COUNT * SBUF * 4 <= 65536, "static LDS");
 
 template <int YT, int LT>
 __global__ __launch_bounds__(THREADS) void miw_small_bwd_kernel(MiwSmallArgs a) {
-    constexpr int DT = YT <= 3 ? 1 : 2;
-    __shared__ __attribute__((aligned(16))) float lds[K_COUNT * SBUF];
-    auto buf = [&](int b) { return lds + b * SBUF; };
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int tid = threadIdx.x;
-    const int d = a.d, L = a.L, S = a.S;
-    const MiwOff o(d, L);
-    const float* P = a.prm;
-    float* part = a.part + (long)blockIdx.x * o.n;
-    int cc = c, qq = q;
-    // ================================================================ first loop: decoder side
-    // wave w: dWx in-tile w x YT out tiles, dWd2 in-tile w x 8 out tiles, dWd1 out tile w; thread t: one bias column
-    // (t < 128: bd2, 128 <= t < 256: bd1, 256 <= t < 256 + 3 d: bx)
-    {
-        f32x4 accX[YT], acc2[8], acc1 = zero4();
-#pragma unroll
-        for (int t = 0; t < YT; ++t) accX[t] = zero4();
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc2[t] = zero4();
-        float db = 0.f;
-        for (int u = blockIdx.x; u < a.units; u += gridDim.x) {
-            const long r0 = (long)u * a.RB;
-            const int nr = a.R - r0 < a.RB ? (int)(a.R - r0) : a.RB;
-            const int nrows = nr * S;
-            const long drow0 = r0 * S;
-            // thread (rb, l) of wave 0: the row's encoder-head gradient, from the loss's own term on (miw_sample_bwd_kernel)
-            const int rb = tid >> 4, hl = tid & 15;
-            const bool hown = rb < nr && hl < L;
-            float gm = hown ? a.gh[(r0 + rb) * 2 * L + hl] : 0.f;
-            float gs = hown ? a.gh[(r0 + rb) * 2 * L + L + hl] : 0.f;
-            // the operands of a tile are requested one tile ahead (registers pG / p2 / p1 / pz / pe) and written to LDS at the top
-            // of their tile: G [16][16 YT], g2, g1 [16][128]; z and the sampling eps as tiles 0 and 3 of K_Z (dz is tile 2)
-            constexpr int NG = (256 * YT + THREADS - 1) / THREADS;
-            float pG[NG], pz = 0.f, pe = 0.f;
-            f32x4 p2 = zero4(), p1 = zero4();
-            const int sr = tid >> 5, sf = 4 * (tid & 31), zr = tid >> 4;
-            auto fetch = [&](int t0) {
-                const int nl = nrows - t0 < 16 ? nrows - t0 : 16;
-                const long row0 = drow0 + t0;
-#pragma unroll
-                for (int k = 0; k < NG; ++k) {
-                    const int i = tid + k * THREADS, r = i / (16 * YT), f = i - r * 16 * YT;
-                    pG[k] = (i < 256 * YT && r < nl && f < 3 * d) ? a.G[(row0 + r) * 3 * d + f] : 0.f;
-                }
-                p2 = sr < nl ? *reinterpret_cast<const f32x4*>(a.g2 + (row0 + sr) * MIW_HID + sf) : zero4();
-                p1 = sr < nl ? *reinterpret_cast<const f32x4*>(a.g1 + (row0 + sr) * MIW_HID + sf) : zero4();
-                const bool zok = tid < 256 && zr < nl && hl < L;
-                pz = zok ? a.z[(row0 + zr) * L + hl] : 0.f;
-                pe = zok ? a.eps[(row0 + zr) * L + hl] : 0.f;
-            };
-            auto commit = [&]() {
-#pragma unroll
-                for (int k = 0; k < NG; ++k) {
-                    const int i = tid + k * THREADS, r = i / (16 * YT), f = i - r * 16 * YT;
-                    if (i < 256 * YT) buf(K_DP)[r * SP + f] = pG[k];
-                }
-                *reinterpret_cast<f32x4*>(buf(K_A2) + sr * SP + sf) = p2;
-                *reinterpret_cast<f32x4*>(buf(K_A1) + sr * SP + sf) = p1;
-                if (tid < 256) {
-                    buf(K_Z)[zr * SP + hl] = pz;
-                    buf(K_Z)[zr * SP + 48 + hl] = pe;
-                }
-            };
-            fetch(0);
-            f32x4 fT6[YT];  // (the first stage's fragments: requested behind their last use, for the next tile)
-            miw_ldAT<YT>(P + o.Wx, 3 * d, MIW_HID, w, cc, qq, fT6);
-            for (int t0 = 0; t0 < nrows; t0 += 16) {
-                const int nl = nrows - t0 < 16 ? nrows - t0 : 16;
-                f32x4 fT5[8], fT4[8];
-                commit();
-                lds_barrier();
-                launder(cc, qq);
-                if (t0 + 16 < nrows) fetch(t0 + 16);
-                // ---- dWx | dg2 = relu'(g2) (Wx^T G) | bx
-                miw_ldAT<8>(P + o.Wd2, MIW_HID, MIW_HID, w, cc, qq, fT5);
-#pragma unroll
-                for (int mt = 0; mt < YT; ++mt) accX[mt] = wgrad16(buf(K_DP), mt, buf(K_A2), w, accX[mt], cc, qq);
-                st_act(buf(K_DA2), w, cc, qq, gate4(miw_mm<YT>(fT6, buf(K_DP), cc, qq, zero4()), ld_act(buf(K_A2), w, cc, qq)));
-                if (tid >= 256 && tid < 256 + 3 * d) db += miw_colsum(buf(K_DP), tid - 256);
-                lds_barrier();
-                launder(cc, qq);
-                // ---- dWd2 | dg1 | bd2
-                if (w == 0) miw_ldAT<8>(P + o.Wd1, MIW_HID, L, 0, cc, qq, fT4);
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt) acc2[mt] = wgrad16(buf(K_DA2), mt, buf(K_A1), w, acc2[mt], cc, qq);
-                st_act(buf(K_DA1), w, cc, qq, gate4(miw_mm<8>(fT5, buf(K_DA2), cc, qq, zero4()), ld_act(buf(K_A1), w, cc, qq)));
-                if (tid < 128) db += miw_colsum(buf(K_DA2), tid);
-                lds_barrier();
-                launder(cc, qq);
-                // ---- dWd1 | dz (wave 0, into tile 2 of K_Z) | bd1
-                if (t0 + 16 < nrows) miw_ldAT<YT>(P + o.Wx, 3 * d, MIW_HID, w, cc, qq, fT6);
-                acc1 = wgrad16(buf(K_DA1), w, buf(K_Z), 0, acc1, cc, qq);
-                if (w == 0) st_act(buf(K_Z), 2, cc, qq, miw_mm<8>(fT4, buf(K_DA1), cc, qq, zero4()));
-                if (tid >= 128 && tid < 256) db += miw_colsum(buf(K_DA1), tid - 128);
-                lds_barrier();
-                launder(cc, qq);
-                // ---- sum over the row's samples, in sample order: rows [lo, hi) of the tile are samples of data row rb
-                if (hown) {
-                    const int lo = rb * S - t0 > 0 ? rb * S - t0 : 0, hi = (rb + 1) * S - t0 < nl ? (rb + 1) * S - t0 : nl;
-                    for (int r = lo; r < hi; ++r) {
-                        const float dzv = buf(K_Z)[r * SP + 32 + hl];
-                        gm += dzv;
-                        gs += dzv * buf(K_Z)[r * SP + 48 + hl];
-                    }
-                }
-                lds_barrier();  // the next tile's operands overwrite what this stage and the last one read
-                launder(cc, qq);
-            }
-            if (hown) {
-                a.dht[(r0 + rb) * 2 * L + hl] = gm;
-                a.dht[(r0 + rb) * 2 * L + L + hl] = gs * miw_softplus_d(a.heads[(r0 + rb) * 2 * L + L + hl]);
-            }
-        }
-#pragma unroll
-        for (int mt = 0; mt < YT; ++mt) miw_put(part + o.Wx, 3 * d, MIW_HID, mt, w, c, q, accX[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) miw_put(part + o.Wd2, MIW_HID, MIW_HID, mt, w, c, q, acc2[mt]);
-        miw_put(part + o.Wd1, MIW_HID, L, w, 0, c, q, acc1);
-        if (tid < 128) part[o.bd2 + tid] = db;
-        else if (tid < 256) part[o.bd1 + tid - 128] = db;
-        else if (tid < 256 + 3 * d) part[o.bx + tid - 256] = db;
-    }
-    __syncthreads();  // dht of this workgroup's rows is in memory; every LDS buffer is free
-    launder(cc, qq);
-    // ================================================================ second loop: encoder side, the same row blocks
-    // wave w: dWh in-tile w x LT out tiles, dWe2 in-tile w x 8 out tiles, dWe1 out tile w x DT in tiles; thread t: one bias
-    // column (t < 128: be2, 128 <= t < 256: be1, 256 <= t < 256 + 2 L: bh)
-    {
-        f32x4 accH[LT], acc2[8], acc1[DT];
-#pragma unroll
-        for (int t = 0; t < LT; ++t) accH[t] = zero4();
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc2[t] = zero4();
-#pragma unroll
-        for (int t = 0; t < DT; ++t) acc1[t] = zero4();
-        float db = 0.f;
-        for (int u = blockIdx.x; u < a.units; u += gridDim.x) {
-            const long r0 = (long)u * a.RB;
-            const int nr = a.R - r0 < a.RB ? (int)(a.R - r0) : a.RB;
-            f32x4 fT3[LT], fT2[8];
-            miw_ldAT<LT>(P + o.Wh, 2 * L, MIW_HID, w, cc, qq, fT3);
-            miw_stage(buf(K_DP), a.dht, r0, nr, 2 * L, LT);
-            miw_stage128(buf(K_A2), a.h2, r0, nr);
-            miw_stage128(buf(K_A1), a.h1, r0, nr);
-            miw_stage(buf(K_Z), a.xin, r0, nr, d, DT);
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dWh | dh2 | bh
-            miw_ldAT<8>(P + o.We2, MIW_HID, MIW_HID, w, cc, qq, fT2);
-#pragma unroll
-            for (int mt = 0; mt < LT; ++mt) accH[mt] = wgrad16(buf(K_DP), mt, buf(K_A2), w, accH[mt], cc, qq);
-            st_act(buf(K_DA2), w, cc, qq, gate4(miw_mm<LT>(fT3, buf(K_DP), cc, qq, zero4()), ld_act(buf(K_A2), w, cc, qq)));
-            if (tid >= 256 && tid < 256 + 2 * L) db += miw_colsum(buf(K_DP), tid - 256);
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dWe2 | dh1 | be2
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) acc2[mt] = wgrad16(buf(K_DA2), mt, buf(K_A1), w, acc2[mt], cc, qq);
-            st_act(buf(K_DA1), w, cc, qq, gate4(miw_mm<8>(fT2, buf(K_DA2), cc, qq, zero4()), ld_act(buf(K_A1), w, cc, qq)));
-            if (tid < 128) db += miw_colsum(buf(K_DA2), tid);
-            lds_barrier();
-            launder(cc, qq);
-            // ---- dWe1 | be1
-#pragma unroll
-            for (int t = 0; t < DT; ++t) acc1[t] = wgrad16(buf(K_DA1), w, buf(K_Z), t, acc1[t], cc, qq);
-            if (tid >= 128 && tid < 256) db += miw_colsum(buf(K_DA1), tid - 128);
-            lds_barrier();  // the next row block stages into the buffers read above
-            launder(cc, qq);
-        }
-#pragma unroll
-        for (int mt = 0; mt < LT; ++mt) miw_put(part + o.Wh, 2 * L, MIW_HID, mt, w, c, q, accH[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt) miw_put(part + o.We2, MIW_HID, MIW_HID, mt, w, c, q, acc2[mt]);
-#pragma unroll
-        for (int t = 0; t < DT; ++t) miw_put(part + o.We1, MIW_HID, d, w, t, c, q, acc1[t]);
-        if (tid < 128) part[o.be2 + tid] = db;
-        else if (tid < 256) part[o.be1 + tid - 128] = db;
-        else if (tid < 256 + 2 * L) part[o.bh + tid - 256] = db;
-    }
+#define MIW_BLK blockIdx.x
+#define MIW_NBLK gridDim.x
+#include "vpc_miw_small_bwd_body.h"
+#undef MIW_BLK
+#undef MIW_NBLK
 }
 
 // gradient i = the partial blocks' entries i summed in workgroup order, then flat Adam (adam_kernel's update)
-__global__ void miw_small_tail_kernel(const float* __restrict__ part, int nblk, int n, float* __restrict__ grad, AdamFuse A) {
+__device__ __forceinline__ void miw_small_tail_body(const float* __restrict__ part, int nblk, int n, float* __restrict__ grad,
+                                                    const AdamFuse& A) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float g = 0.f;
@@ -400,6 +131,79 @@ __global__ void miw_small_tail_kernel(const float* __restrict__ part, int nblk, 
     for (; b < nblk; ++b) g += part[(long)b * n + i];
     grad[i] = g;
     adam_apply(A, i, g);
+}
+__global__ void miw_small_tail_kernel(const float* __restrict__ part, int nblk, int n, float* __restrict__ grad, AdamFuse A) {
+    miw_small_tail_body(part, nblk, n, grad, A);
+}
+
+// ================================================================================================ the ensemble forms
+// G members in one launch (include/vpc.h, vpc_miw_small_fwd_multi / _bwd_multi / _tail_multi): every workspace is the dense
+// [G][rows][width] stack of the stand-alone buffers, so a member's strides follow from (R, S, d, L); only the parameter rows
+// and the partial blocks carry a stride of their own.  base = member 0's arguments.
+struct MiwSmallMultiArgs {
+    MiwSmallArgs base;
+    long s_prm, s_part;  // floats between two members' parameter rows / partial blocks
+    int G, order, nblk;  // nblk: workgroups per member (fwd: units; bwd: blocks_per_member)
+};
+// (block, member) of this workgroup, the two orders of vpc_small_member.h: 0 = grid (nblk, G), member-major; 1 = grid
+// (8 nblk, ceil(G / 8)), all blocks of a member on ids of one residue mod 8 - one XCD, one L2 for the member's parameters
+// (false: a surplus workgroup of the last member group).
+__device__ __forceinline__ bool miw_block_member(const MiwSmallMultiArgs& ma, unsigned& blk, unsigned& mem) {
+    if (ma.order == 0) {
+        mem = blockIdx.y;
+        blk = blockIdx.x;
+        return true;
+    }
+    blk = blockIdx.x >> 3;
+    mem = 8 * blockIdx.y + (blockIdx.x & 7);
+    return mem < (unsigned)ma.G;
+}
+// member `mem`'s arguments, built in registers from the base record (uniform: scalar arithmetic)
+__device__ __forceinline__ MiwSmallArgs miw_member_args(const MiwSmallMultiArgs& ma, const unsigned mem) {
+    MiwSmallArgs a = ma.base;
+    const long g = mem, R = a.R, RS = R * a.S;
+    a.prm += g * ma.s_prm;
+    a.xin += g * R * a.d;
+    a.eps += g * 2 * RS * a.L;  // [2 P][B][S][L] per member: the sampling planes first
+    a.h1 += g * R * MIW_HID; a.h2 += g * R * MIW_HID;
+    a.heads += g * R * 2 * a.L; a.hact += g * R * 2 * a.L;
+    a.z += g * RS * a.L;
+    a.g1 += g * RS * MIW_HID; a.g2 += g * RS * MIW_HID;
+    a.Y += g * RS * 3 * a.d;
+    if (a.G) a.G += g * RS * 3 * a.d;
+    if (a.gh) a.gh += g * R * 2 * a.L;
+    if (a.dht) a.dht += g * R * 2 * a.L;
+    if (a.part) a.part += g * ma.s_part;
+    return a;
+}
+template <int YT, int LT>
+__global__ __launch_bounds__(THREADS) void miw_small_fwd_multi_kernel(MiwSmallMultiArgs ma) {
+    unsigned blk, mem;
+    if (!miw_block_member(ma, blk, mem)) return;
+    const MiwSmallArgs a = miw_member_args(ma, mem);
+#define MIW_BLK blk
+#include "vpc_miw_small_fwd_body.h"
+#undef MIW_BLK
+}
+template <int YT, int LT>
+__global__ __launch_bounds__(THREADS) void miw_small_bwd_multi_kernel(MiwSmallMultiArgs ma) {
+    unsigned blk, mem;
+    if (!miw_block_member(ma, blk, mem)) return;
+    const MiwSmallArgs a = miw_member_args(ma, mem);
+    const unsigned nblk = (unsigned)ma.nblk;
+#define MIW_BLK blk
+#define MIW_NBLK nblk
+#include "vpc_miw_small_bwd_body.h"
+#undef MIW_BLK
+#undef MIW_NBLK
+}
+// blockIdx.y = member: its partial blocks in block order into its row of the gradient stack, flat Adam with its lr
+__global__ void miw_small_tail_multi_kernel(const float* __restrict__ part, int nblk, int n, float* __restrict__ grad,
+                                            long s_row, AdamFuse A, const VpcMiwMember* __restrict__ members) {
+    const long g = blockIdx.y;
+    A.param += g * s_row; A.m += g * s_row; A.v += g * s_row;
+    A.lr = members[g].lr;
+    miw_small_tail_body(part + g * nblk * n, nblk, n, grad + g * s_row, A);
 }
 
 }  // namespace vpc
@@ -429,6 +233,33 @@ bool miw_small_shape_ok(long R, int S, int d, int L, int RB) {
     return R > 0 && S > 0 && d > 0 && d <= MIW_SMALL_MAX_D && L > 0 && L <= MIW_SMALL_MAX_L && RB >= 1 &&
            RB <= MIW_SMALL_MAX_RB && R * S <= (1L << 24);
 }
+typedef void (*MiwSmallMultiKernel)(MiwSmallMultiArgs);
+template <int LT>
+MiwSmallMultiKernel miw_small_pick_multi_y(int yt, bool bwd) {
+    switch (yt) {
+        case 1: return bwd ? miw_small_bwd_multi_kernel<1, LT> : miw_small_fwd_multi_kernel<1, LT>;
+        case 2: return bwd ? miw_small_bwd_multi_kernel<2, LT> : miw_small_fwd_multi_kernel<2, LT>;
+        case 3: return bwd ? miw_small_bwd_multi_kernel<3, LT> : miw_small_fwd_multi_kernel<3, LT>;
+        case 4: return bwd ? miw_small_bwd_multi_kernel<4, LT> : miw_small_fwd_multi_kernel<4, LT>;
+        case 5: return bwd ? miw_small_bwd_multi_kernel<5, LT> : miw_small_fwd_multi_kernel<5, LT>;
+        default: return bwd ? miw_small_bwd_multi_kernel<6, LT> : miw_small_fwd_multi_kernel<6, LT>;
+    }
+}
+MiwSmallMultiKernel miw_small_pick_multi(int d, int L, bool bwd) {
+    const int yt = (3 * d + 15) / 16;
+    return 2 * L <= 16 ? miw_small_pick_multi_y<1>(yt, bwd) : miw_small_pick_multi_y<2>(yt, bwd);
+}
+bool miw_multi_width_ok(int d, int L) { return d > 0 && d <= MIW_SMALL_MAX_D && L > 0 && L <= MIW_SMALL_MAX_L; }
+// member count, workgroup order and a row stride that holds a member's flat parameters
+bool miw_multi_ok(int G, int order, long row_stride, int d, int L) {
+    return G >= 1 && G <= VPC_MIW_MULTI_MAX_MEMBERS && (order == 0 || order == 1) && miw_multi_width_ok(d, L) &&
+           row_stride >= MiwOff(d, L).n;
+}
+// nblk workgroups for each of G members in the order of miw_block_member (nblk * G <= VPC_MIW_MULTI_MAX_BLOCKS: checked)
+dim3 miw_multi_grid(long nblk, int G, int order) {
+    return order == 0 ? dim3((unsigned)nblk, (unsigned)G) : dim3((unsigned)(8 * nblk), (unsigned)((G + 7) / 8));
+}
+
 long miw_small_units(long R, int RB) { return (R + RB - 1) / RB; }
 long miw_small_grid(long R, int RB) {
     const long u = miw_small_units(R, RB), m = num_cus();  // (a workgroup fills a CU: 8 waves at two per SIMD)
@@ -489,6 +320,68 @@ int vpc_miw_small_tail(const float* part, long part_floats, long R, int RB, int 
     const AdamFuse A{params, exp_avg, exp_avg_sq, nullptr, nullptr, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 0};
     hipLaunchKernelGGL(miw_small_tail_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, (int)grid, n,
                        grad, A);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+// ---------------------------------------------------------------------------------------------- the ensemble entries
+long vpc_miw_multi_workspace(int G, int blocks_per_member, int d, int L) {
+    if (G < 1 || G > VPC_MIW_MULTI_MAX_MEMBERS || blocks_per_member < 1 || !miw_multi_width_ok(d, L)) return 0;
+    return (long)G * blocks_per_member * MiwOff(d, L).n;
+}
+
+int vpc_miw_small_fwd_multi(const float* params, long param_stride, const float* xin, const float* eps, float* h1, float* h2,
+                            float* heads, float* hact, float* z, float* g1, float* g2, float* Y, int G, long R, int S, int d,
+                            int L, int RB, int order, void* stream) {
+    if (!miw_small_shape_ok(R, S, d, L, RB) || !miw_multi_ok(G, order, param_stride, d, L)) return VPC_ERR_ARG;
+    if (!params || !xin || !eps || !h1 || !h2 || !heads || !hact || !z || !g1 || !g2 || !Y) return VPC_ERR_ARG;
+    if (!aligned16(h1) || !aligned16(h2) || !aligned16(g1) || !aligned16(g2)) return VPC_ERR_ARG;
+    const long units = miw_small_units(R, RB);
+    if (units * G > VPC_MIW_MULTI_MAX_BLOCKS) return VPC_ERR_ARG;
+    MiwSmallMultiArgs ma{};
+    MiwSmallArgs& a = ma.base;
+    a.prm = params; a.xin = xin; a.eps = eps; a.h1 = h1; a.h2 = h2; a.heads = heads; a.hact = hact; a.z = z; a.g1 = g1;
+    a.g2 = g2; a.Y = Y;
+    a.R = (int)R; a.S = S; a.d = d; a.L = L; a.RB = RB; a.units = (int)units;
+    ma.s_prm = param_stride; ma.G = G; ma.order = order; ma.nblk = (int)units;
+    hipLaunchKernelGGL(miw_small_pick_multi(d, L, false), miw_multi_grid(units, G, order), dim3(THREADS), 0, (hipStream_t)stream,
+                       ma);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_miw_small_bwd_multi(const float* params, long param_stride, const float* xin, const float* eps, const float* h1,
+                            const float* h2, const float* heads, const float* z, const float* g1, const float* g2,
+                            const float* Gy, const float* gh, float* dht, float* part, long part_floats, int G,
+                            int blocks_per_member, long R, int S, int d, int L, int RB, int order, void* stream) {
+    if (!miw_small_shape_ok(R, S, d, L, RB) || !miw_multi_ok(G, order, param_stride, d, L)) return VPC_ERR_ARG;
+    if (!params || !xin || !eps || !h1 || !h2 || !heads || !z || !g1 || !g2 || !Gy || !gh || !dht || !part) return VPC_ERR_ARG;
+    if (!aligned16(h1) || !aligned16(h2) || !aligned16(g1) || !aligned16(g2)) return VPC_ERR_ARG;
+    const long units = miw_small_units(R, RB), n = MiwOff(d, L).n;
+    if (blocks_per_member < 1 || blocks_per_member > units || blocks_per_member > num_cus()) return VPC_ERR_ARG;
+    if ((long)blocks_per_member * G > VPC_MIW_MULTI_MAX_BLOCKS || part_floats < (long)G * blocks_per_member * n) return VPC_ERR_ARG;
+    MiwSmallMultiArgs ma{};
+    MiwSmallArgs& a = ma.base;
+    a.prm = params; a.xin = xin; a.eps = eps; a.h1 = const_cast<float*>(h1); a.h2 = const_cast<float*>(h2);
+    a.heads = const_cast<float*>(heads); a.z = const_cast<float*>(z); a.g1 = const_cast<float*>(g1);
+    a.g2 = const_cast<float*>(g2); a.G = Gy; a.gh = gh; a.dht = dht; a.part = part;
+    a.R = (int)R; a.S = S; a.d = d; a.L = L; a.RB = RB; a.units = (int)units;
+    ma.s_prm = param_stride; ma.s_part = blocks_per_member * n; ma.G = G; ma.order = order; ma.nblk = blocks_per_member;
+    hipLaunchKernelGGL(miw_small_pick_multi(d, L, true), miw_multi_grid(blocks_per_member, G, order), dim3(THREADS), 0,
+                       (hipStream_t)stream, ma);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_miw_small_tail_multi(const float* part, long part_floats, int G, int blocks_per_member, int d, int L, float* grad,
+                             float* params, float* exp_avg, float* exp_avg_sq, long row_stride, const VpcMiwMember* members,
+                             float beta1, float beta2, float eps, long step, void* stream) {
+    if (!miw_multi_ok(G, 0, row_stride, d, L) || !part || !grad || !params || !exp_avg || !exp_avg_sq || !members || step < 1)
+        return VPC_ERR_ARG;
+    const int n = MiwOff(d, L).n;
+    if (blocks_per_member < 1 || blocks_per_member > num_cus() || part_floats < (long)G * blocks_per_member * n) return VPC_ERR_ARG;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    const AdamFuse A{params, exp_avg, exp_avg_sq, nullptr, nullptr, 0.f, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), 0};
+    hipLaunchKernelGGL(miw_small_tail_multi_kernel, dim3((n + 255) / 256, G), dim3(256), 0, (hipStream_t)stream, part,
+                       blocks_per_member, n, grad, row_stride, A, members);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

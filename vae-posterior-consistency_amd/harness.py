@@ -42,7 +42,9 @@ from .notmiwae import NMTrainer, REG_notMIWAE_v2, _NMBase, notMIWAE_myversion
 from .notmiwae import impute_stream as nm_impute_stream
 from .eddi import EDDITrainer, Reg_EDDI, _EDDIBase, vanilla_EDDI
 from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _EDDIMnistBase
-from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream
+from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream, small_max_rows
+from .miw_ensemble import MIWEnsembleTrainer
+from .miw_ensemble import sweep_key as miw_sweep_key
 from .flow import FlowTrainer, _FlowBase
 from .wide import WideTrainer
 
@@ -296,8 +298,10 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
 
 def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type,
                    training_parameters, max_epochs, train_k, num_estimates, experiment_type, reg_type):
-    """{member index: key} of the mask-augmented and point-net members of a sweep that step in an ensemble: those whose key
-    (family, model class, reg_type, ml_reg term on, emb_dim) at least one other member shares.  Decided BEFORE any member
+    """{member index: key} of the mask-augmented, point-net and MIWAE-path members of a sweep that step in an ensemble: those
+    whose key - (family, model class, reg_type, ml_reg term on, emb_dim), or miw_ensemble.sweep_key's ("miw", class, obs_dim,
+    latent_dim, num_samples) for a MIWAE / Reg_MIWAE whose first batch takes the small-batch step (VPC_MIW_SMALL) - at least
+    one other member shares.  Decided BEFORE any member
     is built or trained, so that train_sweep still trains every other member at once, in the order of configs.  A member's
     class is that of models[g], else of a throw-away model_loader() build; the probe and the look at the first batch leave
     torch's generator where it was (the members' initial weights and a shuffling loader's order are what they are without it)."""
@@ -305,7 +309,9 @@ def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K
     with torch.random.fork_rng(devices=[]):
         for g, c in enumerate(cfgs):
             vt = c["vae_type"]
-            if models is None and not ("mask_augm" in vt or "EDDI" in vt):  # (no other vae_type builds these classes)
+            # (a MIWAE-path name is probed only while the small-batch step is on: with VPC_MIW_SMALL unset nothing is built or read)
+            miw_name = "MIWAE" in vt and "notMIWAE" not in vt and "with_drop" not in vt and small_max_rows() > 0
+            if models is None and not ("mask_augm" in vt or "EDDI" in vt or miw_name):  # (no other vae_type builds these classes)
                 continue
             if models is not None:
                 m = models[g]
@@ -319,6 +325,10 @@ def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K
             if name is not None:
                 keys[g] = (name, type(m), getattr(m, "reg_type", None),
                            getattr(m, "reg_type", None) == "ml_reg" and c["alpha"] != 0.0, getattr(m, "emb_dim", None))
+            elif isinstance(m, _MIWBase):
+                key = miw_sweep_key(m, vt, loader[0], obs_dim)
+                if key is not None:
+                    keys[g] = key
     count = {}
     for k in keys.values():
         count[k] = count.get(k, 0) + 1
@@ -338,10 +348,16 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
     (a mixed list is split into such groups).  Mask-augmented members (Reg_VAE_mask / vanilla_VAE_mask) and point-net members
     (Reg_EDDI / vanilla_EDDI with obs_dim % 4 == 0) are grouped by class, reg_type, whether the ml_reg term is on and, for the
     point-net classes, emb_dim: a group of two or more steps through ensemble.MaskEnsembleTrainer / EDDIEnsembleTrainer, a
-    group of one goes through train().  'with_drop' runs stay alone (train()'s loop thins their mask with a drop mask of its
-    own at every step), and so do every other family, point-net members of another width and batches beyond the small-batch
-    step: train(), one by one.  Every member is trained exactly as train(..., alpha=, p_missingness=, seed=) alone trains it, prints
-    the reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
+    group of one goes through train().  MIWAE / Reg_MIWAE members are grouped by (class, obs_dim, latent_dim, num_samples) while
+    VPC_MIW_SMALL routes their first batch to the small-batch step (miwae.small_step_route): a group of two or more steps
+    through miw_ensemble.MIWEnsembleTrainer; with the variable unset each goes through train().  'with_drop' runs of every
+    family stay alone (train()'s loop thins their mask with a drop mask of its own at every step), and so do every other
+    family, point-net members of another width and batches beyond the small-batch step: train(), one by one.
+    Every member is trained as train(..., alpha=, p_missingness=, seed=) alone trains it - bit for bit, except in a MIWAE group
+    whose members together have more row blocks than the chip has compute units (miw_ensemble.default_blocks then gives a
+    workgroup more rows and a member fewer partial blocks than the stand-alone step takes: the same draws and the same
+    math in another summation order of the weight gradients, within 2e-5 of the flat gradient per step) - prints the
+    reference's epoch line and is saved under its own checkpoint_path.  Returns the models in the order of configs."""
     cfgs = _sweep_configs(configs, models, loaders)
     fam = _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type,
                          training_parameters, max_epochs, train_k, num_estimates, experiment_type, reg_type)
@@ -362,8 +378,11 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
                   beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
     rows = lambda t: t.to(device).reshape(-1, obs_dim)
     for key, idx in _group(keys)[0].items():
-        trainer_cls = {"mask": MaskEnsembleTrainer, "eddi": EDDIEnsembleTrainer}.get(key[0], EnsembleTrainer)
+        trainer_cls = {"mask": MaskEnsembleTrainer, "eddi": EDDIEnsembleTrainer, "miw": MIWEnsembleTrainer}.get(key[0],
+                                                                                                             EnsembleTrainer)
         ens = trainer_cls([out[g] for g in idx], lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
+        # (MIWTrainer.train_step takes alpha and p_missingness from the schedule, and so does the MIWAE ensemble step)
+        schedule = (lambda i: {}) if key[0] == "miw" else (lambda i: dict(epoch=i + 1, beta=beta, beta_annealing=beta_annealing))
         alphas, pms = [cfgs[g]["alpha"] for g in idx], [cfgs[g]["p_missingness"] for g in idx]
         sources = [data_loader_train[0]] if loaders is None else [loaders[g][0] for g in idx]
         for i in range(max_epochs):
@@ -372,7 +391,7 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
                     x, mk = rows(batches[0][0]), rows(batches[0][1])
                 else:
                     x, mk = torch.stack([rows(b[0]) for b in batches]), torch.stack([rows(b[1]) for b in batches])
-                ens.step(x, mk, epoch=i + 1, alpha=alphas, beta=beta, beta_annealing=beta_annealing, p_missingness=pms)
+                ens.step(x, mk, alpha=alphas, p_missingness=pms, **schedule(i))
             totals = ens.epoch_total()
             if verbose:
                 for g, total_loss in zip(idx, totals):
