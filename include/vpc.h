@@ -258,6 +258,23 @@ int vpc_decoder_fused_draw_f32(const float* x, const float* dec_img, int npass, 
                                unsigned long long offset_eps, const long long* state, long eps_rows_global, long eps_row_lo,
                                void* stream);
 
+/* vpc_encoder_fwd_draw_f32 + vpc_decoder_fused_draw_f32(npass 2) + vpc_encoder_bwd(npass 2, lat_pitch 16, precision 0) as three
+ * phases of ONE launch (csrc/vpc_step_f32.hip): the same code per phase, the same bytes in every workspace, partial block and
+ * loss partial; two kernel boundaries less.  The arguments are the union of the three entry points' (the masks of the decoder
+ * and of the backward pass are {mask_in, mask_p_out}); nblocksE_out / nblocksD_out are the encoder / decoder partial-block
+ * counts for vpc_reduce_step*.  The phases share one persistent grid with nothing but workgroup barriers between them, so the
+ * three kernels must agree on grid and tile count: the two drawing kernels run the throughput shape at every B,
+ * vpc_encoder_bwd the shape of its batch size - force_shape != 0 runs it in the throughput shape too (tests, A/B runs).  If
+ * they disagree the call returns 4 and has launched nothing: the caller makes the three launches.  Records the sweep as the
+ * last encoder form (vpc_encoder_fwd_last_form). */
+int vpc_step_f32(const float* x, const float* enc_img, const float* dec_img, const uint8_t* mask_in, uint8_t* mask_p_out,
+                 const uint8_t* const* maskB, const VpcLossCoef* co, float* const* h1, float* const* h2, float* const* mean,
+                 float* const* logvar, float* const* eps, float* const* dmean, float* const* dlogvar, float inv_B,
+                 float x_logvar, float* partE, float* partD, double* loss_partials, int* nblocksE_out, int* nblocksD_out,
+                 long B, int d, int L, float keep_prob, unsigned long long seed, unsigned long long offset_mask,
+                 unsigned long long offset_eps, const long long* state, long mask_elem_lo, long eps_rows_global,
+                 long eps_row_lo, int force_shape, void* stream);
+
 /* ---- data parallel: the step's ONE collective on the caller's stream (RCCL over xGMI) -------
  * The reference has no distributed code; these entry points exist so that the flat bucket [gradients | loss terms]
  * (37 548 + 9 floats) is all-reduced as an ordinary node of the compute stream - no hop to a communication stream,

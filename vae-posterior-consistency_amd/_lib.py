@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VPC_LIB") or os.path.join(_HERE, "csrc", "libvpc_hip.so")  # VPC_LIB: diagnostic builds only
 
 _ERR = {1: "bad argument (null / misaligned pointer or bad count)", 2: "unsupported shape (beyond the limits of this entry point, include/vpc.h)",
-        3: "HIP runtime error"}
+        3: "HIP runtime error", 4: "the phases of the one-launch step do not share one grid (nothing was launched)"}
+ERR_PHASES = 4  # vpc_step_f32 only: the caller makes the three launches
 
 
 class VpcError(RuntimeError):
@@ -115,6 +116,8 @@ _PROTOS = {
     "vpc_encoder_fwd_draw_f32": [P, P, P, P, PP, PP, PP, PP, L_, I, I, F, ULL, ULL, P, L_, P],
     "vpc_encoder_fwd_last_form": [],
     "vpc_decoder_fused_draw_f32": [P, P, I, PP, PP, P, PP, PP, PP, F, F, PP, PP, P, P, IP, L_, I, I, ULL, ULL, P, L_, L_, P],
+    "vpc_step_f32": [P, P, P, P, P, PP, P, PP, PP, PP, PP, PP, PP, PP, F, F, P, P, P, IP, IP, L_, I, I, F, ULL, ULL, ULL, P, L_, L_,
+                     L_, I, P],
     "vpc_rccl_unique_id": [P],
     "vpc_rccl_comm_init": [P, I, I, PP],
     "vpc_allreduce_flat": [P, P, L_, P],

@@ -10,6 +10,7 @@
 #define VPC_ERR_ARG 1     // null / misaligned pointer, bad count
 #define VPC_ERR_SHAPE 2   // unsupported d / L
 #define VPC_ERR_HIP 3     // HIP runtime reported an error
+#define VPC_ERR_PHASES 4  // vpc_step_f32: its three kernels would not run one common grid - nothing was launched
 
 namespace vpc {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

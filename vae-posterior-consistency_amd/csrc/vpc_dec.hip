@@ -718,13 +718,15 @@ extern "C" int vpc_decoder_bwd(const float* z, const float* dxhat, const float* 
 
 // the in-kernel eps draw of vpc_decoder_fused_draw_f32 (NULL: vpc_decoder_fused, eps is read)
 struct EpsDraw { unsigned long long seed, offset; const long long* state; long rows_global, row_lo; };
+// what dec_fused_draw_prepare asks for instead of the launch: the drawing kernel's argument blocks and its workgroup shape
+struct DecPrep { DecArgs* a; DecDraw* dd; TileShape* ts; };
 
 static int decoder_fused(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
                          const uint8_t* const* maskB, const VpcLossCoef* co,
                          const float* const* mean, const float* const* logvar, const float* const* eps,
                          const float* eps_ml, float inv_B, float x_logvar, float* const* dmean, float* const* dlogvar, int lat_pitch,
                          int precision, float* partials, double* loss_partials, int* nblocks_out, long B, int d,
-                         int L, void* stream, const EpsDraw* dr) {
+                         int L, void* stream, const EpsDraw* dr, const DecPrep* prep = nullptr) {
     if (!x || !dec_img || !maskA || !co || !mean || !logvar || !dmean || !dlogvar || !partials ||
         !loss_partials)
         return VPC_ERR_ARG;
@@ -762,6 +764,10 @@ static int decoder_fused(const float* x, const float* dec_img, int npass, const 
         }
         dd.seed = dr->seed; dd.off_eps = dr->offset; dd.state = dr->state;
         dd.eps_rows_global = dr->rows_global; dd.eps_row_lo = dr->row_lo;
+        if (prep) {
+            *prep->a = a; *prep->dd = dd; *prep->ts = ts;
+            return VPC_OK;
+        }
         return dec8_draw_dispatch(a, dd, ts.grid_x, (hipStream_t)stream);
     }
     // throughput shape, d in (64, 128]: the 8-wave / one-tile-per-wave kernel (vpc_dec8.hip); VPC_DEC8=0 selects the
@@ -799,3 +805,17 @@ extern "C" int vpc_decoder_fused_draw_f32(const float* x, const float* dec_img, 
     return decoder_fused(x, dec_img, npass, maskA, maskB, co, mean, logvar, eps, nullptr, inv_B, x_logvar, dmean, dlogvar, 16, 0,
                          partials, loss_partials, nblocks_out, B, d, L, stream, &dr);
 }
+
+namespace vpc {
+int dec_fused_draw_prepare(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                           const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                           const float* const* logvar, float* const* eps, float inv_B, float x_logvar, float* const* dmean,
+                           float* const* dlogvar, float* partials, double* loss_partials, long B, int d, int L,
+                           unsigned long long seed, unsigned long long offset_eps, const long long* state, long eps_rows_global,
+                           long eps_row_lo, DecArgs& a, DecDraw& dd, TileShape& ts) {
+    const EpsDraw dr{seed, offset_eps, state, eps_rows_global, eps_row_lo};
+    const DecPrep prep{&a, &dd, &ts};
+    return decoder_fused(x, dec_img, npass, maskA, maskB, co, mean, logvar, eps, nullptr, inv_B, x_logvar, dmean, dlogvar, 16, 0,
+                         partials, loss_partials, nullptr, B, d, L, nullptr, &dr, &prep);
+}
+}  // namespace vpc

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include "vpc_layout.h"
+#include "vpc_abi_internal.h"
 
 namespace vpc {
 
@@ -71,5 +72,13 @@ __device__ __forceinline__ int opaque_zero() {
 size_t dec8_lds(int DT, int prec);
 int dec8_dispatch(const DecArgs& a, bool vec, int grid, int prec, hipStream_t s);
 int dec8_draw_dispatch(const DecArgs& a, const DecDraw& dr, int grid, hipStream_t s);  // fp32, vector layout, the eps draw inside (vpc_dec8.hip)
+// vpc_decoder_fused_draw_f32 up to its launch (vpc_dec.hip): the entry's checks, the drawing kernel's argument blocks and its
+// workgroup shape, for vpc_step_f32 (vpc_step_f32.hip), which runs that kernel's body as a phase
+int dec_fused_draw_prepare(const float* x, const float* dec_img, int npass, const uint8_t* const* maskA,
+                           const uint8_t* const* maskB, const VpcLossCoef* co, const float* const* mean,
+                           const float* const* logvar, float* const* eps, float inv_B, float x_logvar, float* const* dmean,
+                           float* const* dlogvar, float* partials, double* loss_partials, long B, int d, int L,
+                           unsigned long long seed, unsigned long long offset_eps, const long long* state, long eps_rows_global,
+                           long eps_row_lo, DecArgs& a, DecDraw& dd, TileShape& ts);
 
 }  // namespace vpc

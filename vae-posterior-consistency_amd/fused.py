@@ -19,6 +19,9 @@ forms z; FusedTrainer._draw_fused says when):
                              -> vpc_adam_step
     precision "bf16", obs_dim in (64, 128], throughput shape: encoder_fwd + decoder_fused + encoder_bwd are ONE launch,
     vpc_step_fused_bf16 (csrc/vpc_step.hip) - h1 / h2 / latent statistics never leave the chip
+    fp32 with the draws in the kernels and two passes, from 128 rows x CUs on: the same three are the three PHASES of one
+    launch, vpc_step_f32 (csrc/vpc_step_f32.hip) - the kernels' code and bytes, two kernel boundaries less
+    (FusedTrainer._step_f32 says when; 2 launches per step)
 
 Gradients are those of the GLOBAL mean loss: seeds carry 1/B_global, so summing the flat bucket over ranks is
 exactly `train_loss = loss / x.shape[0]` (VAE.py:452) on the concatenated batch.
@@ -131,7 +134,9 @@ class FusedTrainer(_FlatAdamTrainer):
         """Name (as in `timers`) of the launch that carries most of the step's FLOPs in the shape last stepped."""
         if getattr(self, "_used_step_small", False):
             return "step_small"
-        return "step_fused" if getattr(self, "_used_step_fused", False) else "decoder_fused"
+        if getattr(self, "_used_step_fused", False) or getattr(self, "_used_step_f32", False):
+            return "step_fused"
+        return "decoder_fused"
 
     # ------------------------------------------------------------------
     def step(self, x, mask, mask_p=None, eps_q=None, eps_p=None, eps_ml=None, *, epoch=1, alpha=1.0, beta=1.0,
@@ -204,6 +209,19 @@ class FusedTrainer(_FlatAdamTrainer):
             return False
         return env == "1" or B >= self._draw_fused_rows
 
+    def _step_f32(self, B):
+        """Whether a step whose draws are made in its kernels (_draw_fused) and that has two passes runs encoder_fwd,
+        decoder_fused and encoder_bwd as the three phases of ONE launch (ops.step_f32, csrc/vpc_step_f32.hip; timed as
+        `step_fused`): from 128 rows x CUs on, where the three kernels run one common grid, unless a switch selects another
+        form of one of them.  VPC_STEP_F32=0 keeps the three launches, =1 takes the one launch at any batch size with
+        encoder_bwd in the throughput shape (tests, A/B runs)."""
+        env = os.environ.get("VPC_STEP_F32", "")
+        if env == "0" or self.vanilla or "VPC_TILE" in os.environ:
+            return False
+        if any(os.environ.get(k) == "0" for k in ("VPC_ENC_SWEEP", "VPC_DRAW_FUSED", "VPC_DEC8")):
+            return False
+        return env == "1" or B >= self._draw_fused_rows
+
     def _draws(self, co, mask, mask_p, eps_in, B, Bg, row_lo, dk, use_small, keep_prob, _state):
         """The step's draws - mask_p into mask_p_buf, eps into eps_buf - on the device unless injected, at the counters of
         trainer.draw_counters (mask_p and eps in ONE launch when both are drawn).  All planes are drawn if any consumed
@@ -269,6 +287,17 @@ class FusedTrainer(_FlatAdamTrainer):
             return nb, nb
         # forward (encoder), fused decoder + loss + decoder backward, encoder backward
         enc_img, dec_img = imgs
+        self._used_step_f32 = False
+        if in_kernel is not None and self._step_f32(B):
+            # the three MFMA kernels as phases of one launch (same bytes everywhere); None: they would not share a grid
+            mask_in, keep_prob, _, seed, off_mask, off_eps, state, elem_lo, eps_shard = in_kernel
+            nb = self._timed("step_fused", ops.step_f32, x, enc_img, dec_img, mask_in, self.mask_p_buf, maskB, co, self.h1,
+                             self.h2, self.mean, self.logvar, epss, inv_B, xlv, self.dmean, self.dlogvar, self.partE,
+                             self.partD, self.loss_part, dk, Ld, keep_prob, seed, off_mask, off_eps, state, elem_lo, eps_shard,
+                             os.environ.get("VPC_STEP_F32") == "1")
+            if nb is not None:
+                self._used_step_f32 = True
+                return nb
         if in_kernel is not None:
             # the draws inside the two kernels that consume them (_draw_fused); vanilla_VAE has no mask_p: plain encoder_fwd
             mask_in, keep_prob, _, seed, off_mask, off_eps, state, elem_lo, eps_shard = in_kernel

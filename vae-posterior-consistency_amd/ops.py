@@ -141,6 +141,26 @@ def decoder_fused_draw_f32(x, dec_img, maskA, maskB, co, mean, logvar, eps, inv_
     return nb.value
 
 
+def step_f32(x, enc_img, dec_img, mask_in, mask_p_out, maskB, co, h1, h2, mean, logvar, eps, inv_B, x_logvar, dmean, dlogvar,
+             partE, partD, loss_part, d, Ld, keep_prob, seed, offset_mask, offset_eps, state=None, elem_lo=0, eps_shard=None,
+             force_shape=False):
+    """encoder_fwd_draw_f32 + decoder_fused_draw_f32 + encoder_bwd (two passes, fp32, padded latent workspaces) as three phases
+    of ONE launch, csrc/vpc_step_f32.hip: the same bytes everywhere.  Returns the (encoder, decoder) partial-block counts for
+    reduce_step, or None - nothing launched - when the three kernels would not run one common grid (encoder_bwd takes the
+    small-batch shape at this B and force_shape is off): the caller then makes the three launches."""
+    nbE, nbD = C.c_int(0), C.c_int(0)
+    rows_local, rows_global, row_lo, _ = (x.shape[0], x.shape[0], 0, 16) if eps_shard is None else _shard4(eps_shard)
+    rc = lib().vpc_step_f32(ptr(x), ptr(enc_img), ptr(dec_img), ptr(mask_in), ptr(mask_p_out), ptr_array(maskB), co,
+                            ptr_array(h1), ptr_array(h2), ptr_array(mean), ptr_array(logvar), ptr_array(eps), ptr_array(dmean),
+                            ptr_array(dlogvar), inv_B, x_logvar, ptr(partE), ptr(partD), ptr(loss_part), C.byref(nbE),
+                            C.byref(nbD), x.shape[0], d, Ld, float(keep_prob), int(seed), int(offset_mask), int(offset_eps),
+                            ptr(state), int(elem_lo), rows_global, row_lo, int(bool(force_shape)), stream_ptr())
+    if rc == L.ERR_PHASES:
+        return None
+    check(rc, "vpc_step_f32")
+    return nbE.value, nbD.value
+
+
 def step_small_max_rows():
     return int(lib().vpc_step_small_max_rows())
 
