@@ -156,6 +156,123 @@ def test_steady_state_launch_sequence(path, tile, make, expected, monkeypatch):
     assert rec.names == expected
 
 
+# ---- the eager path of the three chain-backed families: model.forward_loss under grad, then backward, through the encoder /
+# decoder autograd Functions.  B = 8, d = 12, latent 10, K = S = 3 (the flows: hid_dim 64).
+def _eager_model(name):
+    torch.manual_seed(0)
+    if "Flow" in name:
+        return getattr(vpc, name)(12, 64, 10, 10, {"batch_size": 8, "patience": 1}).cuda()
+    return getattr(vpc, name)(12, 500, 10, 10, {"batch_size": 8, "patience": 1}, 3, 1).cuda()
+
+
+def _eager_data():
+    x, m = _data(8, 12, 2, float_mask=True)
+    return x, m, m * (torch.rand(8, 12, generator=torch.Generator().manual_seed(3)) < 0.7).float().cuda()
+
+
+def _eager_full(model):
+    x, m, mp = _eager_data()
+
+    def run():
+        model.zero_grad()
+        _, ret = model.forward_loss(x, m, mp if model.regularised else None, epoch=1, alpha=0.5)
+        ret[1].backward()
+    return run
+
+
+def _eager_z_only(model):
+    x, m, _ = _eager_data()
+
+    def run():
+        model.zero_grad()
+        model.encoder(x, m)[0].sum().backward()
+    return run
+
+
+_ENC_FWD = {"nm": ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"],
+            "miw": ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_miw_sample"],
+            "flow": ["vpc_flow_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_flow_fwd"]}
+_DEC_FWD = {"nm": ["vpc_linear_fwd"] * 3, "miw": ["vpc_linear_fwd"] * 3 + ["vpc_miw_heads"], "flow": ["vpc_linear_fwd"] * 5}
+_ENC_BWD = {"nm": ["vpc_nm_sample_bwd"] + _SWD * 2 + _SWD[:2], "miw": ["vpc_miw_sample_bwd"] + _SWD * 2 + _SWD[:2],
+            "flow": ["vpc_flow_bwd"] + _SWD * 2 + _SWD[:2]}
+_DEC_BWD = {"nm": _SWD * 3, "miw": ["vpc_miw_heads_bwd"] + _SWD * 3, "flow": _SWD * 5}
+_LOSS = {f: [f"vpc_{f}_loss_scratch", f"vpc_{f}_loss"] for f in ("nm", "miw", "flow")}
+
+
+def _eager_expected(f, passes, flow_order=False):
+    """Forward of `passes` (encoder, decoder) pairs, the loss, then the backward of the passes from the last one down.  The
+    regularised flow runs both encoders before both decoders (flow.REG_VAEFlow.forward), and autograd mirrors that."""
+    if flow_order:
+        return _ENC_FWD[f] * 2 + _DEC_FWD[f] * 2 + _LOSS[f] + _DEC_BWD[f] * 2 + _ENC_BWD[f] * 2
+    return (_ENC_FWD[f] + _DEC_FWD[f]) * passes + _LOSS[f] + (_DEC_BWD[f] + _ENC_BWD[f]) * passes
+
+
+# recorded with _Recorder on the commit before the six encoder / decoder Functions became one pair (the lists hold C ABI calls,
+# host-side scratch queries included); the *_z_only rows backpropagate through the encoder's first output alone
+EAGER = [
+    ("REG_notMIWAE_v2", _eager_full, _eager_expected("nm", 2)),
+    ("notMIWAE_myversion", _eager_full, _eager_expected("nm", 1)),
+    ("Reg_MIWAE", _eager_full, _eager_expected("miw", 2)),
+    ("MIWAE", _eager_full, _eager_expected("miw", 1)),
+    ("REG_VAEFlow", _eager_full, _eager_expected("flow", 2, flow_order=True)),
+    ("VAEFlow", _eager_full, _eager_expected("flow", 1)),
+    ("Reg_MIWAE", _eager_z_only, _ENC_FWD["miw"] + _ENC_BWD["miw"]),
+    ("REG_VAEFlow", _eager_z_only, _ENC_FWD["flow"] + _ENC_BWD["flow"]),
+]
+
+
+@pytest.mark.parametrize("name,make,expected", EAGER, ids=[f"{e[0]}_{e[1].__name__[7:]}" for e in EAGER])
+def test_eager_launch_sequence(name, make, expected, monkeypatch):
+    """forward_loss under grad and backward issue the C ABI calls they issued when every family had its own pair of
+    autograd Functions, in the same order (second run of a model: its chains are built)."""
+    run = make(_eager_model(name))
+    run()
+    rec = _Recorder(_lib.lib())
+    monkeypatch.setattr(_lib, "_lib", rec)
+    run()
+    monkeypatch.undo()
+    assert rec.names == expected
+
+
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_joined_column_blocks(n):
+    """chainfamily._joined: the n adjacent column blocks of one [.., n W] buffer give that buffer back, in place; blocks of
+    different buffers, a gap between blocks, a row pitch wider than n W or another dtype give None."""
+    from vpc_amd.chainfamily import _joined
+    B, K, W = 3, 4, 5
+    buf = torch.arange(B * K * n * W, dtype=torch.float32, device="cuda").view(B, K, n * W)
+    parts = [buf[..., i * W:(i + 1) * W] for i in range(n)]
+    G = _joined(parts, B * K, W)
+    assert G is not None and G.data_ptr() == buf.data_ptr() and torch.equal(G, buf.view(B * K, n * W))
+    assert _joined([p.clone() for p in parts], B * K, W) is None or n == 1
+    wide = torch.zeros(B, K, (n + 1) * W, device="cuda")
+    assert _joined([wide[..., i * W:(i + 1) * W] for i in range(n)], B * K, W) is None
+    assert _joined([p.double() for p in parts], B * K, W) is None
+    if n > 1:
+        assert _joined(parts[::-1], B * K, W) is None
+        assert _joined([buf[:, 0, i * W:(i + 1) * W] for i in range(n)], B, W) is None  # rows K * n W apart
+
+
+def test_nm_encoder_one_output_gradient():
+    """Backpropagation through z alone (no gradient arrives for the heads) gives the encoder gradients of the two-output run
+    whose heads gradient is zero, bit for bit."""
+    model = _eager_model("REG_notMIWAE_v2")
+    x, m, _ = _eager_data()
+    grads = []
+    for both in (False, True):
+        model.zero_grad()
+        torch.manual_seed(1)
+        z, mean, _ = model.encoder(x, m)
+        if both:
+            torch.autograd.backward([z, mean], [torch.ones_like(z), torch.zeros_like(mean)])
+        else:
+            z.sum().backward()
+        grads.append([p.grad.clone() for p in model.seq_encoder.parameters()] + [model.q_mu[0].weight.grad.clone(),
+                                                                                  model.q_logstd[0].bias.grad.clone()])
+    assert all(g.abs().max() > 0 for g in grads[0])
+    assert all(torch.equal(a, b) for a, b in zip(*grads))
+
+
 def _reg_vae(B):
     return vpc.Reg_VAE(128, 500, 10, 10, {"batch_size": B, "patience": 1}, "exp", "kl_reg").cuda()
 

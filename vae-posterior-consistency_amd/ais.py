@@ -39,7 +39,11 @@ import torch
 
 from . import _lib as L
 from ._lib import VpcError, check, lib, ptr, stream_ptr
+from .eddi_mnist import _EDDIMnistBase
+from .flow import _FlowBase
 from .linear import ACT_RELU, ACT_SIGMOID_HARDTANH, chain
+from .models import _VAEBase
+from .notmiwae import _NMBase
 
 ENGINES = ("persistent", "gemm", "auto")
 
@@ -70,8 +74,6 @@ def log_mean_exp(x):
 
 def _decoder_image(model):
     """(decoder image, d, L, x_logvar) of a supported model; VpcError otherwise."""
-    from .eddi_mnist import _EDDIMnistBase
-    from .models import _VAEBase
     d, Ld = getattr(model, "obs_dim", None), getattr(model, "latent_dim", None)
     # _wide: the model runs on the generic GEMM path and has no packed decoder image.  That is obs_dim > 128 or
     # latent_dim > 15, and for the mask-augmented classes (encoder input [x*mask | mask]) already obs_dim > 64.
@@ -89,10 +91,6 @@ def _decoder_chain(model):
     """(layers of linear.chain, d, L, x_logvar) of a model's decoder for the GEMM engine; x_logvar None = the chain's last
     layer is the merged [mean | logvar] head.  The layers are the model's own parameters (the views its API path runs
     on), not a packed copy: nothing here can go stale."""
-    from .eddi_mnist import _EDDIMnistBase
-    from .flow import _FlowBase
-    from .models import _VAEBase
-    from .notmiwae import _NMBase
     d, Ld = getattr(model, "obs_dim", None), getattr(model, "latent_dim", None)
     if isinstance(model, _NMBase):
         return model._chains()[1], d, Ld, None

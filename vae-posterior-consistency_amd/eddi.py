@@ -18,10 +18,10 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .chainfamily import nm_sample, nm_sample_bwd
 from .images import PackedImage, mlp_spec
 from .models import _W6, MAX_EPOCH, Reg_VAE, vanilla_VAE
 from .linear import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad
-from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer, draw_counters, pad_cols
 

@@ -41,10 +41,10 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .chainfamily import nm_sample, nm_sample_bwd
 from .images import mlp_spec
 from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now
 from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
-from .notmiwae import nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer, draw_counters
 

@@ -15,6 +15,9 @@ fallback: CPU tensors raise.
 The reference's spline quirks are reproduced, not fixed (csrc/vpc_flow.hip): the context is masked in place with the
 latent mask on the bin axis, inputs outside [-1, 1] are zeroed and splined, and a pass with no inside draw is the
 identity.  latent_dim must be 10 (the reference's hard-coded 10 x 10 reshape).
+
+What this family shares with notmiwae.py and miwae.py lives in chainfamily.py: the encoder / decoder autograd frame (driven
+by FAMILY below) and the trainer frame.
 """
 from __future__ import annotations
 
@@ -23,10 +26,10 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .chainfamily import ChainDecoderFn, ChainEncoderFn, Family, _ChainTrainer
 from .images import FlatParams, mlp_spec
-from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now,
-                     wgrad_now_keys)
-from .trainer import _FlatAdamTrainer
+from .linear import ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_bwd, chain_fwd
+from .trainer import chain_draw_increment
 
 FLOW_L = 10      # VPC_FLOW_LATENT: latent dim = spline bins
 CTX = 100        # seq_encoder output = the 10 x 10 spline contexts
@@ -82,66 +85,16 @@ def _chains(v):
             chain([v[k] for k in _DEC_NAMES], (ACT_ELU,) * 4 + (ACT_SIGMOID_HARDTANH,), v["Wm"].shape[0]))
 
 
-class FlowEncoderFn(torch.autograd.Function):
-    """(x, mask, eps) -> (z, z_log_prob) [B, 10].  seq_encoder(cat[x*mask, mask]) then Flow.forward (VAE.py:1924-1931)."""
-
-    @staticmethod
-    def forward(ctx, model, x, mask, eps, *weights):
-        require_cuda(x, mask, eps, *weights)
-        d = model.obs_dim
-        B, dev = x.shape[0], x.device
-        layers = model._chains()[0]
-        acts = chain_buffers(layers, B, dev)
-        flow_prep(x, mask, None, None, acts[0], None, B, d)
-        chain_fwd(layers, acts, B)
-        z, zlp = torch.empty(B, FLOW_L, device=dev), torch.empty(B, FLOW_L, device=dev)
-        flow_fwd(acts[3], eps, z, zlp, B, B)
-        ctx.model = model
-        ctx.save_for_backward(*acts, eps)
-        return z, zlp
-
-    @staticmethod
-    def backward(ctx, dz, dzlp):
-        model = ctx.model
-        *acts, eps = ctx.saved_tensors
-        B, dev = acts[0].shape[0], acts[0].device
-        layers = model._chains()[0]
-        dacts = chain_buffers(layers, B, dev, first=False)
-        flow_bwd(acts[3], eps, None if dz is None else _f32c(dz), None, None if dzlp is None else _f32c(dzlp), dacts[3], B, B)
-        g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, _ENC_NAMES, B), input_grad=False)
-        return (None, None, None, None, *[g[k] for k in _ENC_NAMES])
+def _sample(t, eps, B, S, Ld):
+    """Flow.forward on the contexts t (VAE.py:1924-1931) -> (z, z_log_prob) [B, 10]."""
+    z, zlp = torch.empty(B, FLOW_L, device=t.device), torch.empty(B, FLOW_L, device=t.device)
+    flow_fwd(t, eps, z, zlp, B, B)
+    return z, zlp
 
 
-class FlowDecoderFn(torch.autograd.Function):
-    """z [.., 10] -> x_mean = sigmoid(decoder_mean(seq_decoder(z))) (VAE.py:1943-1948)."""
-
-    @staticmethod
-    def forward(ctx, model, z, *weights):
-        require_cuda(z, *weights)
-        d = model.obs_dim
-        lead = z.shape[:-1]
-        z2 = _f32c(z).reshape(-1, FLOW_L)
-        M = z2.shape[0]
-        layers = model._chains()[1]
-        acts = chain_buffers(layers, M, z2.device, first=z2)
-        chain_fwd(layers, acts, M)
-        ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(*acts)
-        return acts[5].view(*lead, d)
-
-    @staticmethod
-    def backward(ctx, gy):
-        model = ctx.model
-        acts = ctx.saved_tensors
-        d = model.obs_dim
-        M, dev = acts[0].shape[0], acts[0].device
-        layers = model._chains()[1]
-        dacts = chain_buffers(layers, M, dev, last=_f32c(gy).reshape(M, d))
-        g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
-        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, _DEC_NAMES, M), y_gate=acts[5],
-                  gate=ACT_SIGMOID_HARDTANH, gate_split=d)
-        return (None, dacts[0].view(*ctx.lead, FLOW_L), *[g[k] for k in _DEC_NAMES])
+# encoder input cat[x * mask, mask]; the decoder returns x_mean = sigmoid(decoder_mean(seq_decoder(z))) (VAE.py:1943-1948)
+FAMILY = Family(_ENC_NAMES, _DEC_NAMES, lambda x, mask, out, B, d: flow_prep(x, mask, None, None, out, None, B, d), _sample,
+                lambda t, eps, dz, dzlp, dt, B, S, Ld: flow_bwd(t, eps, dz, None, dzlp, dt, B, B), 1)
 
 
 class FlowLossFn(torch.autograd.Function):
@@ -246,7 +199,7 @@ class _FlowBase(FlatParams, nn.Module):
         B = xf.shape[0]
         if eps is None:
             eps = torch.randn(B, FLOW_L, device=xf.device)
-        return FlowEncoderFn.apply(self, xf, mf, _f32c(eps), *self._enc_weights())
+        return ChainEncoderFn.apply(FAMILY, self, xf, mf, _f32c(eps), 1, *self._enc_weights())
 
     def encoder(self, x, mask, sample=True):
         """VAE.py:1924-1931 / :2047-2056 -> (z, z_log_prob), each [B, 10]."""
@@ -260,7 +213,7 @@ class _FlowBase(FlatParams, nn.Module):
         """VAE.py:1943-1948 -> (x_mean, x_logvar); x_logvar is the constant obs_logvar (the decoder_logvar GEMM, whose
         result the reference discards, is not run)."""
         L.require_cuda(z_int)
-        x_mean = FlowDecoderFn.apply(self, z_int, *self._dec_weights())
+        x_mean = ChainDecoderFn.apply(FAMILY, self, z_int, *self._dec_weights())
         return x_mean, torch.full_like(x_mean, float(self.obs_logvar))
 
     def _loss(self, x, mask, mask_p, q, p, alpha, beta, stage):
@@ -342,7 +295,7 @@ _DEC_WKEYS = tuple(("dec_bwd", 4 - i) for i in range(5))
 _ENC_WKEYS = tuple(("enc_bwd", 7 - i) for i in range(3))
 
 
-class FlowTrainer(_FlatAdamTrainer):
+class FlowTrainer(_ChainTrainer):
     """The whole training step of the flow path (train.py:77-86 + :114-116) as a fixed sequence of HIP launches with no
     host synchronisation: mask_p draw + stacked encoder input + eps draws (one launch), the encoder GEMMs with the q and
     p passes stacked along the batch (one GEMM per layer), the flow, the five decoder GEMMs, the loss (two launches, the
@@ -351,29 +304,15 @@ class FlowTrainer(_FlatAdamTrainer):
 
     Single process only: the reference's torch.any(inside) (VAE.py:1698) is a predicate over the whole batch of an
     encoder call, so a sharded step would need a cross-rank vote before the flow."""
-    step_timers = True
+    family, model_base, model_names = FAMILY, _FlowBase, "VAEFlow and REG_VAEFlow"
+    single_process = ("the flow's torch.any(inside) is a predicate over the whole batch (no data-parallel form without a "
+                      "cross-rank vote)")
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
-        if not isinstance(model, _FlowBase):
-            raise TypeError("FlowTrainer supports VAEFlow and REG_VAEFlow")
-        if world_size != 1:
-            raise L.VpcError("FlowTrainer is single-process: the flow's torch.any(inside) is a predicate over the whole "
-                             "batch (no data-parallel form without a cross-rank vote)")
-        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
-        self.reg = model.regularised
-        self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        self.g = model._named_views(self.grad)
-        self._B = self._v = None
-
-    def _ws(self, B, v=None):
-        v = self.model._views() if v is None else v
-        if self._B == B and self._v is v:
-            return
+    def _buffers(self, B, e):
         m, dev = self.model, self.dev
         d, H = m.obs_dim, m.hid_dim
         P = 2 if self.reg else 1
         R = P * B
-        e = lambda *s: torch.empty(*s, device=dev)
         self.xin, self.mask_p, self.eps = e(R, 2 * d), e(B, d), e(R, FLOW_L)
         self.h1, self.h2, self.t = e(R, H), e(R, H), e(R, CTX)
         self.z, self.zlp = e(R, FLOW_L), e(R, FLOW_L)
@@ -382,19 +321,12 @@ class FlowTrainer(_FlatAdamTrainer):
         self.gz, self.gzlp, self.dzd = e(R, FLOW_L), e(R, FLOW_L), e(R, FLOW_L)
         self.dgd = [e(R, H) for _ in range(4)]
         self.dt, self.dh2, self.dh1 = e(R, CTX), e(R, H), e(R, H)
-        # the two GEMM chains on their workspaces, and the per-layer partials of the eight weight gradients in launch order
-        self.enc_layers, self.dec_layers = m._chains()
-        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.t], [None, self.dh1, self.dh2, self.dt]
-        self.dec_acts, self.dec_dacts = [self.z, *self.gd, self.Y], [self.dzd, *self.dgd, self.G]
-        g = self.g
-        back = self.dec_layers[::-1] + self.enc_layers[::-1]  # the backward pass's launch order: decoder_mean first
-        names = _DEC_NAMES[::-1] + _ENC_NAMES[::-1]           # bm, Wm, bd4, Wd4, ..
-        self._wgrad_workspace([(R, l[3], l[2]) for l in back], [(g[w], g[b]) for w, b in zip(names[1::2], names[0::2])])
         self.scratch = flow_loss_scratch(B, dev)
         pq = lambda a: (a[:B], a[B:] if self.reg else None)
         self._sl = dict(xm=pq(self.Y), z=pq(self.z), zlp=pq(self.zlp),
                         g=(*pq(self.G), *pq(self.gz), *pq(self.gzlp)))
-        self._B, self._v = B, v
+        return (R, R, [self.xin, self.h1, self.h2, self.t], [None, self.dh1, self.dh2, self.dt],
+                [self.z, *self.gd, self.Y], [self.dzd, *self.dgd, self.G])
 
     def train_step(self, x, mask, *, alpha, p_missingness, stage, **schedule):
         return self.step(x, mask, alpha=alpha, p_missingness=p_missingness, stage=stage)
@@ -420,7 +352,7 @@ class FlowTrainer(_FlatAdamTrainer):
           self.rng_offset + (1 << 40))
         if eps is not None:
             self.eps.copy_(eps.reshape(self.eps.shape))
-        self.rng_offset += (self.eps.numel() + 3) // 4 + (B * d + 3) // 4 + 1
+        self.rng_offset += chain_draw_increment(self.eps.numel(), B, d)
         # ---- forward
         chain_fwd(self.enc_layers, self.enc_acts, R, 0, t, _T_ENC_FWD)
         t("flow", flow_fwd, self.t, self.eps, self.z, self.zlp, R, B)

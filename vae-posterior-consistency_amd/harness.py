@@ -34,6 +34,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .chainfamily import stream_seed
 from .ensemble import (EDDI, MASK, EDDIEnsembleEvaluator, EDDIEnsembleTrainer, EnsembleEvaluator, EnsembleTrainer,
                        MaskEnsembleEvaluator, MaskEnsembleTrainer, stackable, steps_in_ensemble, sweep_family)
 from .fused import FusedTrainer
@@ -597,11 +598,13 @@ def eval_vae_mnar(data_test, mask_test, missing_rate, obs_dim, hid_dim, K, M, la
         N = data_test.shape[0]
         rows = max(1, max_decoder_rows // max(1, model.num_samples))
         temp_recon = []
-        if engine == "stream" and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if engine == "stream":
+            seed = stream_seed(seed)
+        offset = 0
         for rep in range(M):
             if engine == "stream":
-                XM = nm_impute_stream(model, data_test, mask_test, seed=seed, offset=rep * N)  # model.num_samples, as the chain
+                XM = nm_impute_stream(model, data_test, mask_test, seed=seed, offset=offset)  # model.num_samples, as the chain
+                offset += N  # the call used the counter rows offset .. offset + N - 1
                 temp_recon.append(_rmse_unobserved(XM, data_test, mask_test))
                 continue
             XM = torch.zeros_like(data_test)
@@ -651,8 +654,8 @@ def eval_miwae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
                                 p_missingness=p_missingness)
         rows = max(1, max_decoder_rows // max(1, valid_k))
-        if engine == "stream" and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if engine == "stream":
+            seed = stream_seed(seed)
         offset = 0
         for loader, loader_stage in list_loaders:
             recon = []

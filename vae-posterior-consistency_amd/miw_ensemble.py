@@ -32,6 +32,7 @@ from .ensemble import _per_member, _pitch, _shared_or_per_member, stack_models
 from .linear import _f32c
 from .miwae import (HID, PAIR_REFERENCE, SMALL_MAX_D, SMALL_MAX_L, MIWAE, Reg_MIWAE, small_max_rows,
                     small_step_route)
+from .trainer import chain_draw_increment
 
 # VpcMiwMember of include/vpc.h (24 bytes)
 MEMBER_DTYPE = np.dtype([("seed", "<u8"), ("alpha", "<f4"), ("keep_prob", "<f4"), ("lr", "<f4"), ("reserved", "<i4")])
@@ -294,7 +295,7 @@ class MIWEnsembleTrainer:
 
         run("vpc_miw_multi_prep", ptr(xf), sx, ptr(mf), sm, mp, ptr(self.xin), ptr(self.eps), mem, G, int(draw), B, S, d, Ld,
             self.rng_offset, self.rng_offset + (1 << 40), st)
-        self.rng_offset += (2 * P * B * S * Ld + 3) // 4 + (B * d + 3) // 4 + 1  # MIWTrainer.step's increment
+        self.rng_offset += chain_draw_increment(2 * P * B * S * Ld, B, d)
         prm, order = ptr(self.params), self.order
         run("vpc_miw_small_fwd_multi", prm, self.row_pitch, ptr(self.xin), ptr(self.eps), ptr(self.h1), ptr(self.h2),
             ptr(self.heads), ptr(self.hact), ptr(self.z), ptr(self.g1), ptr(self.g2), ptr(self.Y), G, R, S, d, Ld, rb, order, st)

@@ -16,6 +16,9 @@ data row (i*B + j) // S, sample (i*B + j) % S with the prior / posterior terms o
 and the llh_eval weights (applied to the un-mixed x_mean, :3096-3098 / :3267-3269) are those of this pairing.  With
 B == 1 (eval_miwae, one row per call) the pairing is the natural one, and the batched eval_miwae uses the per-row pairing
 (VPC_MIW_PAIR_PER_ROW), which equals N single-row calls.
+
+What this family shares with notmiwae.py and flow.py lives in chainfamily.py: the encoder / decoder autograd frame (driven
+by FAMILY below), the trainer frame and the host side of impute_stream.
 """
 from __future__ import annotations
 
@@ -25,12 +28,14 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import VpcError, check, lib, ptr, require_cuda, stream_ptr
+from . import chainfamily as cf
+from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from .chainfamily import STREAM_MAX_L, ChainDecoderFn, ChainEncoderFn, Family, _ChainTrainer, _joined, _ReferenceAttrs, nm_mul
+from .chainfamily import impute_chunk, impute_draws, miw_impute_draws  # noqa: F401  (defined in chainfamily.py only; the names
+# stay importable from here)
 from .images import FlatParams, mlp_spec
-from .linear import ACT_NONE, ACT_RELU, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now, wgrad_now_keys
-from .notmiwae import nm_mul, nm_prep
-from .ops import fill_normal
-from .trainer import _FlatAdamTrainer
+from .linear import ACT_NONE, ACT_RELU, _f32c, chain, chain_bwd, chain_fwd
+from .trainer import chain_draw_increment
 
 HID = 128  # VAE.py:3027-3042 / :3153-3168 hard-code 128 (hid_dim is ignored by the reference too)
 PAIR_REFERENCE, PAIR_PER_ROW = 0, 1
@@ -104,23 +109,6 @@ def miw_impute(flat, x, mask, eps, seed, offset, row0, part, xm, lse, B, S, d, L
                                stream_ptr()), "vpc_miw_impute")
 
 
-def miw_impute_draws(eps_out, B, S, Ld, seed, offset, row0):
-    check(lib().vpc_miw_impute_draws(ptr(eps_out), int(B), int(S), int(Ld), int(seed), int(offset), int(row0),
-                                     stream_ptr()), "vpc_miw_impute_draws")
-
-
-def _joined(parts, M, W):
-    """Three [.., W] tensors that are the adjacent column blocks of ONE [M, 3W] buffer -> that buffer, else None."""
-    a, b, c = parts
-    if not all(t.dtype == torch.float32 and t.is_cuda for t in parts):
-        return None
-    if not (a.stride() == b.stride() == c.stride() and a.stride(-1) == 1 and a.stride(-2) == 3 * W and
-            b.data_ptr() == a.data_ptr() + 4 * W and c.data_ptr() == a.data_ptr() + 8 * W and
-            all(a.stride(i) == a.stride(i + 1) * a.shape[i + 1] for i in range(a.dim() - 2))):
-        return None
-    return a.as_strided((M, 3 * W), (3 * W, 1))
-
-
 # ------------------------------------------------------------------------------------------------ autograd
 _ENC_NAMES = ("We1", "be1", "We2", "be2", "Wh", "bh")
 _DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wx", "bx")
@@ -132,76 +120,23 @@ def _chains(v):
             chain([v[k] for k in _DEC_NAMES], (ACT_RELU, ACT_RELU, ACT_NONE)))
 
 
-class MIWEncoderFn(torch.autograd.Function):
-    """(x, mask, eps) -> (z [B,S,L], hact [B, mean L | scale L]).  VAE.py:3059-3070 / :3188-3200."""
-
-    @staticmethod
-    def forward(ctx, model, x, mask, eps, S, *weights):
-        require_cuda(x, mask, eps, *weights)
-        Ld = model.latent_dim
-        B, dev = x.shape[0], x.device
-        layers = model._chains()[0]
-        acts = chain_buffers(layers, B, dev)
-        nm_mul(x, mask, acts[0])
-        hact = torch.empty(B, 2 * Ld, device=dev)
-        chain_fwd(layers, acts, B)
-        z = torch.empty(B * S, Ld, device=dev)
-        miw_sample(acts[3], hact, eps, z, B, S, Ld)
-        ctx.model, ctx.S, ctx.has_eps = model, S, eps is not None
-        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev))
-        return z.view(B, S, Ld), hact
-
-    @staticmethod
-    def backward(ctx, dz, dhact):
-        model, S = ctx.model, ctx.S
-        *acts, eps = ctx.saved_tensors
-        Ld = model.latent_dim
-        B, dev = acts[0].shape[0], acts[0].device
-        layers = model._chains()[0]
-        dacts = chain_buffers(layers, B, dev, first=False)
-        miw_sample_bwd(None if dz is None else _f32c(dz).reshape(B * S, Ld), eps if ctx.has_eps else None, acts[3],
-                       None if dhact is None else _f32c(dhact), dacts[3], B, S, Ld)
-        g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, _ENC_NAMES, B), input_grad=False)
-        return (None, None, None, None, None, *[g[k] for k in _ENC_NAMES])
+def _sample(heads, eps, B, S, Ld):
+    """-> (z [B,S,L], hact [B, mean L | scale L]).  VAE.py:3059-3070 / :3188-3200."""
+    hact, z = torch.empty(B, 2 * Ld, device=heads.device), torch.empty(B * S, Ld, device=heads.device)
+    miw_sample(heads, hact, eps, z, B, S, Ld)
+    return z.view(B, S, Ld), hact
 
 
-class MIWDecoderFn(torch.autograd.Function):
-    """z [.., L] -> (mean, scale, df) as the three column blocks of ONE activated [M, 3d] buffer.  VAE.py:3072-3076."""
+def _heads_fwd(y_raw, M, d):
+    Ya = torch.empty(M, 3 * d, device=y_raw.device)
+    miw_heads(y_raw, Ya, M, d)
+    return Ya
 
-    @staticmethod
-    def forward(ctx, model, z, *weights):
-        require_cuda(z, *weights)
-        d, Ld = model.obs_dim, model.latent_dim
-        lead = z.shape[:-1]
-        z2 = _f32c(z).reshape(-1, Ld)
-        M, dev = z2.shape[0], z2.device
-        layers = model._chains()[1]
-        acts = chain_buffers(layers, M, dev, first=z2)
-        Ya = torch.empty(M, 3 * d, device=dev)
-        chain_fwd(layers, acts, M)
-        miw_heads(acts[3], Ya, M, d)
-        ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(*acts)
-        Y3 = Ya.view(*lead, 3 * d)
-        return Y3[..., :d], Y3[..., d:2 * d], Y3[..., 2 * d:]
 
-    @staticmethod
-    def backward(ctx, gm, gs, gv):
-        model = ctx.model
-        acts = ctx.saved_tensors
-        d, Ld = model.obs_dim, model.latent_dim
-        M, dev = acts[0].shape[0], acts[0].device
-        parts = [torch.zeros(M, d, device=dev) if t is None else t for t in (gm, gs, gv)]
-        Ga = _joined(parts, M, d)
-        if Ga is None:
-            Ga = torch.cat([_f32c(t).reshape(M, d) for t in parts], 1)
-        layers = model._chains()[1]
-        dacts = chain_buffers(layers, M, dev)
-        miw_heads_bwd(acts[3], Ga, dacts[3], M, d)
-        g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
-        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, _DEC_NAMES, M))
-        return (None, dacts[0].view(*ctx.lead, Ld), *[g[k] for k in _DEC_NAMES])
+# the decoder returns (mean, scale, df) as the three column blocks of ONE activated [M, 3d] buffer (VAE.py:3072-3076)
+FAMILY = Family(_ENC_NAMES, _DEC_NAMES, lambda x, mask, out, B, d: nm_mul(x, mask, out), _sample,
+                lambda heads, eps, dz, dhact, out, B, S, Ld: miw_sample_bwd(dz, eps, heads, dhact, out, B, S, Ld), 3,
+                (_heads_fwd, miw_heads_bwd))
 
 
 class MIWLossFn(torch.autograd.Function):
@@ -241,7 +176,7 @@ class MIWLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ model classes
-class _MIWBase(FlatParams, nn.Module):
+class _MIWBase(_ReferenceAttrs, FlatParams, nn.Module):
     regularised = False
     # flat parameter buffer: [We1 be1 We2 be2 Wh bh | Wd1 bd1 Wd2 bd2 Wx bx] = state_dict order
     _flat_spec = mlp_spec(_ENC_NAMES, "seq_encoder", "enc") + mlp_spec(_DEC_NAMES, "seq_decoder", "dec")
@@ -249,19 +184,7 @@ class _MIWBase(FlatParams, nn.Module):
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
         super().__init__()
-        if obs_dim > 256 or latent_dim > 64:
-            raise L.VpcError("the MIWAE-path kernels support obs_dim <= 256 and latent_dim <= 64")
-        self.obs_dim = obs_dim
-        self.hid_dim = hid_dim
-        self.emb_dim = 10
-        self.num_samples = num_samples
-        self.num_estimates = num_estimates
-        self.latent_dim = latent_dim
-        self.batch_size = training_parameters["batch_size"]
-        self.K = K
-        self.obs_std = 0.1
-        self.number_components = 500
-        self.training_paramters = training_parameters  # (sic) VAE.py:3024
+        self._init_reference_attrs("MIWAE", obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
         d, Ld = obs_dim, latent_dim
         # created in the reference's order (same seed -> same initial weights)
         self.seq_encoder = nn.Sequential(nn.Linear(d, HID), nn.ReLU(), nn.Linear(HID, HID), nn.ReLU(),
@@ -286,7 +209,7 @@ class _MIWBase(FlatParams, nn.Module):
         B = xf.shape[0]
         if sample and eps is None:
             eps = torch.randn(B, S, Ld, device=xf.device)  # Normal(mean, scale).rsample()
-        z, hact = MIWEncoderFn.apply(self, xf, mf, _f32c(eps) if sample else None, S, *self._enc_weights())
+        z, hact = ChainEncoderFn.apply(FAMILY, self, xf, mf, _f32c(eps) if sample else None, S, *self._enc_weights())
         mean = hact[:, :Ld].unsqueeze(1).expand(B, S, Ld)
         scale = hact[:, Ld:].unsqueeze(1).expand(B, S, Ld)
         mean._vpc_hact = hact
@@ -300,7 +223,7 @@ class _MIWBase(FlatParams, nn.Module):
     def decoder(self, z_int):
         """VAE.py:3072-3076 / :3202-3206 -> (mean, scale, deg_free)."""
         L.require_cuda(z_int)
-        return MIWDecoderFn.apply(self, z_int, *self._dec_weights())
+        return ChainDecoderFn.apply(FAMILY, self, z_int, *self._dec_weights())
 
     @staticmethod
     def _hact_of(mean, scale):
@@ -421,47 +344,6 @@ class Reg_MIWAE(_MIWBase):
 
 
 # ------------------------------------------------------------------------------------------------ streaming imputation
-def impute_chunk(B, S, n_cu):
-    """The default s_chunk of impute_stream: the samples of a row one workgroup owns, a multiple of 16 and never below 16.
-    A rule that was measured, not derived (profiles/miw_impute_notes.md, d = 12, L = 10, S = 5 000, 256 compute units):
-
-      * B < n_cu: as few chunks per row as still give one workgroup per compute unit - the chunks of the largest multiple
-        of 16 with B * ceil(S / s_chunk) >= n_cu (every further chunk repeats the encoder and the weight-fragment loads:
-        B = 64 is fastest at 4 chunks, slower at 5, 10, 20, 40, 79) -
-      * B >= n_cu: whole rows, unless the last round of n_cu workgroups would be less than 95 % full; then 2 or 4 chunks
-        per row (B = 1 600: 6.25 rounds of whole rows, 7 % slower than 12.5 rounds of half rows),
-      * and in both cases the chunks of a row balanced: the smallest multiple of 16 that keeps that number of chunks (4
-        chunks of S = 5 000 as 3 x 1 664 + 8 are 30 % slower than as 3 x 1 264 + 1 208)."""
-    B, S, n_cu = max(int(B), 1), max(int(S), 1), max(int(n_cu), 1)
-    tiles = -(-S // 16)
-    if B < n_cu:
-        need = -(-n_cu // B)  # chunks per row for one workgroup per compute unit
-        chunks = -(-S // max(16, (S - 1) // (need - 1) // 16 * 16))
-    else:
-        for chunks in (1, 2, 4):
-            rounds = B * chunks / n_cu
-            if rounds >= 0.95 * -(-B * chunks // n_cu):
-                break
-        chunks = min(chunks, tiles)
-    return 16 * -(-(-(-S // chunks)) // 16)  # ceil(S / chunks), rounded up to a multiple of 16
-
-
-def impute_draws(B, S, L, seed, offset=0, row0=0, device=None):
-    """The draws of impute_stream(seed=seed, offset=offset, row0=row0) on B rows with S samples as [2, B, S, L]: plane 0
-    the sampler's eps, plane 1 the fresh draw of the log-weight's prior / posterior term (the counter rule of
-    trainer.impute_draw_counter).  (L, the latent width, hides the module's alias of _lib in here.)"""
-    dev = torch.device("cuda") if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise VpcError("impute_draws runs only on the GPU (HIP kernel, no CPU fallback)")
-    if not (B >= 1 and S >= 1 and 1 <= L <= SMALL_MAX_L):
-        raise VpcError(f"impute_draws: B = {B}, S = {S}, latent_dim = {L} outside B >= 1, S >= 1, latent_dim <= {SMALL_MAX_L}")
-    eps = torch.empty(2, B, S, L, device=dev)
-    with torch.cuda.device(dev):
-        miw_impute_draws(eps, B, S, L, seed, offset, row0)
-    return eps
-
-
-@torch.no_grad()
 def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=0, row0=0, s_chunk=None,
                   return_lse=False):
     """The llh_eval imputation of every row of x with num_samples draws (evaluate.py:89-113 through VAE.py:3078-3099 /
@@ -480,36 +362,8 @@ def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=
     a call equal the call on x[a:b] with row0 = a.  s_chunk None: impute_chunk.  For a given s_chunk the result is
     bit-reproducible.  obs_dim <= 32, latent_dim <= 16; anything else, CPU tensors, a wrong eps shape or s_chunk < 1
     raise VpcError (no fallback)."""
-    d, Ld = model.obs_dim, model.latent_dim
-    S = model.num_samples if num_samples is None else int(num_samples)
-    require_cuda(x, mask, eps)
-    if not (1 <= d <= SMALL_MAX_D and 1 <= Ld <= SMALL_MAX_L):
-        raise L.VpcError(f"impute_stream supports obs_dim <= {SMALL_MAX_D} and latent_dim <= {SMALL_MAX_L}: got {d}, {Ld}")
-    xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
-    B = xf.shape[0]
-    if B < 1 or S < 1 or mf.shape != xf.shape:
-        raise L.VpcError(f"impute_stream: B = {B}, num_samples = {S}, mask {tuple(mf.shape)} for x {tuple(xf.shape)}")
-    if s_chunk is None:
-        s_chunk = impute_chunk(B, S, L.max_blocks() // 2)
-    if s_chunk < 1:
-        raise L.VpcError(f"impute_stream: s_chunk = {s_chunk} < 1")
-    if eps is not None:
-        if tuple(eps.shape) != (2, B, S, Ld):
-            raise L.VpcError(f"impute_stream: eps {tuple(eps.shape)}, expected {(2, B, S, Ld)}")
-        eps = _f32c(eps)
-    elif seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    n = miw_impute_scratch(B, S, d, Ld, s_chunk)
-    if n == 0:
-        raise L.VpcError(f"impute_stream: shape (B, S, d, L) = {(B, S, d, Ld)} is outside the kernel's limits")
-    flat = model.flatten_parameters()
-    require_cuda(flat)
-    with torch.cuda.device(xf.device):
-        part = torch.empty(n, device=xf.device)
-        xm = torch.empty(B, d, device=xf.device)
-        lse = torch.empty(B, device=xf.device) if return_lse else None
-        miw_impute(flat, xf, mf, eps, seed or 0, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk)
-    return (xm, lse) if return_lse else xm
+    return cf.impute_stream(model, x, mask, num_samples, eps, seed, offset, row0, s_chunk, return_lse, SMALL_MAX_D,
+                            SMALL_MAX_L, miw_impute_scratch, miw_impute)
 
 
 # ------------------------------------------------------------------------------------------------ fused step
@@ -519,7 +373,7 @@ _DEC_WKEYS = (("dec_bwd", 2), ("dec_bwd", 1), ("dec_bwd", 0))
 _ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
 
 
-SMALL_MAX_D, SMALL_MAX_L = 32, 16  # limits of csrc/vpc_miw_small.hip and csrc/vpc_miw_impute.hip
+SMALL_MAX_D, SMALL_MAX_L = 32, STREAM_MAX_L  # limits of csrc/vpc_miw_small.hip and csrc/vpc_miw_impute.hip
 # The row limit of the small-batch step, in decoder rows P * B * S.  The step without VPC_MIW_SMALL in the environment stays the
 # launch chain (tests/test_trainer_images.py pins the chain's launch sequence as MIWTrainer's step at the wine shape), so the
 # default is 0; SMALL_ROWS_MEASURED is the largest size at which the small path's worst block beat the chain's best block
@@ -554,7 +408,7 @@ def small_rows_per_workgroup(R, S):
     return 1 if R <= cus else 2 if R <= 2 * cus else 4
 
 
-class MIWTrainer(_FlatAdamTrainer):
+class MIWTrainer(_ChainTrainer):
     """The whole training step of the MIWAE path (train.py:102-117 for 'reg_MIWAE*' / the final branch for
     'vanilla_MIWAE*') as a fixed sequence of HIP launches with no host synchronisation: mask_p draw + stacked encoder
     input + Philox normals (one launch), the encoder and decoder GEMM chains with the q and p passes stacked along the
@@ -570,55 +424,34 @@ class MIWTrainer(_FlatAdamTrainer):
 
     Single process only: the reference's row / sample pairing (module docstring) couples rows across the whole batch, so
     a step sharded over ranks cannot equal the single-process step without an all-gather of the per-row sums."""
-    step_timers = True
+    family, model_base, model_names = FAMILY, _MIWBase, "MIWAE and Reg_MIWAE"
+    single_process = ("the reference's row/sample pairing couples rows across the global batch (no data-parallel form "
+                      "without an all-gather)")
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0):
-        if not isinstance(model, _MIWBase):
-            raise TypeError("MIWTrainer supports MIWAE and Reg_MIWAE")
-        if world_size != 1:
-            raise L.VpcError("MIWTrainer is single-process: the reference's row/sample pairing couples rows across the "
-                             "global batch (no data-parallel form without an all-gather)")
-        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
-        self.reg = model.regularised
-        self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        self.g = model._named_views(self.grad)
-        self._B = self._v = None
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank)
         self._part = None  # partial blocks of the small-batch step: made on its first use
         self.small_rb = None  # rows per workgroup of the small-batch step; None: small_rows_per_workgroup
         self.last_path = None
 
-    def _ws(self, B, v=None):
-        v = self.model._views() if v is None else v
-        if self._B == B and self._v is v:
-            return
-        m, dev = self.model, self.dev
+    def _buffers(self, B, e):
+        m = self.model
         d, Ld, S = m.obs_dim, m.latent_dim, m.num_samples
         P = 2 if self.reg else 1
         R, M = P * B, P * B * S
-        e = lambda *s: torch.empty(*s, device=dev)
         self.xin, self.mask_p = e(R, d), e(B, d)
         self.h1, self.h2, self.heads, self.hact = e(R, HID), e(R, HID), e(R, 2 * Ld), e(R, 2 * Ld)
         self.eps = e(2 * P, B, S, Ld)  # sampling draws of the P passes, then the loss-time draws
         self.z, self.g1, self.g2, self.Y = e(M, Ld), e(M, HID), e(M, HID), e(M, 3 * d)
         self.G, self.gh, self.dht = e(M, 3 * d), e(R, 2 * Ld), e(R, 2 * Ld)
         self.dg2, self.dg1, self.dz, self.dh2, self.dh1 = e(M, HID), e(M, HID), e(M, Ld), e(R, HID), e(R, HID)
-        # the two GEMM chains on their workspaces, and the per-layer partials of the six weight gradients in launch order
-        self.enc_layers, self.dec_layers = m._chains()
-        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht]
-        self.dec_acts, self.dec_dacts = [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G]
-        g = self.g
-        self._wgrad_workspace([(M, 3 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)],
-                              [(g[w], g[b]) for w, b in (("Wx", "bx"), ("Wd2", "bd2"), ("Wd1", "bd1"), ("Wh", "bh"),
-                                                         ("We2", "be2"), ("We1", "be1"))])
-        self.scratch = miw_loss_scratch(B, S, dev)
+        self.scratch = miw_loss_scratch(B, S, self.dev)
         BS = B * S
         self._sl = dict(Yp=self.Y[BS:] if self.reg else None, Gp=self.G[BS:] if self.reg else None,
                         hp=self.hact[B:] if self.reg else None, ghp=self.gh[B:] if self.reg else None,
                         eq=self.eps[P], ep=self.eps[P + 1] if self.reg else None, es=self.eps[:P])
-        self._B, self._v = B, v
-
-    def train_step(self, x, mask, *, alpha, p_missingness, **schedule):
-        return self.step(x, mask, alpha=alpha, p_missingness=p_missingness)
+        return (R, M, [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht],
+                [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G])
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30):
         """One optimiser step.  mask_p [B,d] and eps ([4,B,S,L] = forward q, forward p, loss q, loss p for Reg_MIWAE;
@@ -634,20 +467,7 @@ class MIWTrainer(_FlatAdamTrainer):
         P = 2 if reg else 1
         R, M = P * B, P * B * S
         t, sl = self._timed, self._sl
-        rng_inc = (self.eps.numel() + 3) // 4 + (B * d + 3) // 4 + 1
-        if reg and mask_p is not None:
-            mp = _f32c(mask_p.reshape(-1, d))
-            nm_mul(xf, mf, self.xin[:B])
-            nm_mul(xf, mp, self.xin[B:])
-            if eps is None:
-                fill_normal(self.eps, self.seed, self.rng_offset + (1 << 40))
-        else:
-            mp = self.mask_p if reg else None
-            t("prep", nm_prep, xf, mf, mp, self.xin, B, d, 1.0 - p_missingness / 100.0, self.seed, self.rng_offset,
-              self.eps if eps is None else None, self.rng_offset + (1 << 40))
-        if eps is not None:
-            self.eps.copy_(eps.reshape(self.eps.shape))
-        self.rng_offset += rng_inc
+        mp = self._draw_inputs(xf, mf, mask_p, eps, B, d, p_missingness, chain_draw_increment(self.eps.numel(), B, d))
         if small_step_route(d, Ld, B, S, P, small_max_rows()):
             return self._step_small(xf, mf, mp, R, S, d, Ld, alpha)
         self.last_path = "chain"

@@ -9,6 +9,9 @@ regularised class, the unused float64 `logits.0`).  Every layer runs as an fp32 
 importance-weighted loss with the self-masking missingness model and all of its gradients in one fused kernel
 (csrc/vpc_nm.hip).  The two heads of the encoder (q_mu | q_logstd) and of the decoder (x_mean | x_logvar) are
 adjacent in one flat parameter buffer, so each pair is ONE GEMM.  No CPU fallback: CPU tensors raise.
+
+What this family shares with miwae.py and flow.py lives in chainfamily.py: the encoder / decoder autograd frame (driven by
+FAMILY below), the trainer frame, the host side of impute_stream, and the nm_* elementwise ops, which started here.
 """
 from __future__ import annotations
 
@@ -19,41 +22,22 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from . import chainfamily as cf
+from .chainfamily import STREAM_MAX_L, ChainDecoderFn, ChainEncoderFn, Family, _ChainTrainer, _ReferenceAttrs
+from .chainfamily import impute_chunk, nm_mul, nm_prep, nm_sample, nm_sample_bwd  # noqa: F401  (defined in chainfamily.py
+# only; the names stay importable from here)
 from .images import FlatParams, PackedImage
-from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now,
-                     wgrad_now_keys)
+from .linear import ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_bwd, chain_fwd
 from .linear import ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad, wgrad_reduce  # noqa: F401  (the GEMM ops were first
 # reached as vpc_amd.notmiwae.linear_*: the names stay importable from here; they are defined in linear.py only)
 from .models import Reg_VAE, vanilla_VAE
-from .ops import PRECISIONS, fill_normal, step_pack_weights_bf16
-from .trainer import _FlatAdamTrainer
+from .ops import PRECISIONS, step_pack_weights_bf16
+from .trainer import chain_draw_increment
 
 HID = 128  # VAE.py:2343-2363 hard-codes 128 (hid_dim is ignored by the reference too)
 
 
 # ------------------------------------------------------------------------------------------------ raw ops
-def nm_sample(heads, eps, z, B, K, Ld):
-    check(lib().vpc_nm_sample(ptr(heads), 2 * Ld, ptr(eps), ptr(z), Ld, B, K, Ld, stream_ptr()), "vpc_nm_sample")
-
-
-def nm_sample_bwd(dz, eps, heads, g_heads, out, B, K, Ld):
-    check(lib().vpc_nm_sample_bwd(ptr(dz), Ld, ptr(eps), ptr(heads), 2 * Ld, ptr(g_heads), 2 * Ld, ptr(out), 2 * Ld, B,
-                                  K, Ld, stream_ptr()), "vpc_nm_sample_bwd")
-
-
-def nm_mul(x, mask, out):
-    check(lib().vpc_nm_mul(ptr(x), ptr(mask), ptr(out), out.numel(), stream_ptr()), "vpc_nm_mul")
-
-
-def nm_prep(x, mask, mask_p_out, xin, B, d, keep_prob, seed, offset, eps_out=None, offset_eps=0, state=None,
-            elem_lo=0, eps_shard=None):
-    """eps_shard = (rows_local, rows_global, row_lo, pitch) of eps_out as rows of a global batch (None: flat)."""
-    sh = (0, 0, 0, 4) if eps_shard is None else tuple(int(v) for v in eps_shard)
-    check(lib().vpc_nm_prep(ptr(x), ptr(mask), ptr(mask_p_out), ptr(xin), B, d, float(keep_prob), ptr(eps_out),
-                            0 if eps_out is None else eps_out.numel(), int(seed), int(offset), int(offset_eps),
-                            ptr(state), int(elem_lo), *sh, stream_ptr()), "vpc_nm_prep")
-
-
 def nm_loss(x, mask, mask_p, xm_q, xl_q, ldq, xm_p, xl_p, ldp, hq, hp, W, b, eps_kl, g_xm_q, g_xl_q, g_xm_p, g_xl_p,
             ldg, ghq, ghp, gW, gb, xm_imp, scratch, out8, loss_f32, accum, B, B_global, K, d, Ld, alpha, state=None,
             rng_inc=0, gated=False):
@@ -128,88 +112,29 @@ def _rows_view(t, B, K, d):
 
 
 # ------------------------------------------------------------------------------------------------ autograd
+_ENC_NAMES = ("We1", "be1", "We2", "be2", "Wh", "bh")
+_DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wx", "bx")
+
+
 def _chains(v):
     """(encoder, decoder) chains on the named views v: ELU between layers, raw heads | Sigmoid on x_mean, Hardtanh on x_logvar."""
-    return (chain((v["We1"], v["be1"], v["We2"], v["be2"], v["Wh"], v["bh"]), (ACT_ELU, ACT_ELU, ACT_NONE)),
-            chain((v["Wd1"], v["bd1"], v["Wd2"], v["bd2"], v["Wx"], v["bx"]), (ACT_ELU, ACT_ELU, ACT_SIGMOID_HARDTANH),
-                  v["Wxm"].shape[0]))
+    return (chain([v[k] for k in _ENC_NAMES], (ACT_ELU, ACT_ELU, ACT_NONE)),
+            chain([v[k] for k in _DEC_NAMES], (ACT_ELU, ACT_ELU, ACT_SIGMOID_HARDTANH), v["Wxm"].shape[0]))
 
 
-class NMEncoderFn(torch.autograd.Function):
-    """(x, mask, eps) -> (z [B,K,L], heads [B, mean L | logvar L]).  VAE.py:2378-2391 / :2749-2765."""
-
-    @staticmethod
-    def forward(ctx, model, x, mask, eps, K, *weights):
-        require_cuda(x, mask, eps, *weights)
-        Ld = model.latent_dim
-        B, dev = x.shape[0], x.device
-        layers = model._chains()[0]
-        acts = chain_buffers(layers, B, dev)
-        nm_mul(x, mask, acts[0])
-        chain_fwd(layers, acts, B)
-        heads = acts[3]
-        z = torch.empty(B * K, Ld, device=dev)
-        nm_sample(heads, eps, z, B, K, Ld)
-        ctx.model, ctx.K = model, K
-        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev))
-        ctx.has_eps = eps is not None
-        return z.view(B, K, Ld), heads
-
-    @staticmethod
-    def backward(ctx, dz, dheads):
-        model, K = ctx.model, ctx.K
-        *acts, eps = ctx.saved_tensors
-        eps = eps if ctx.has_eps else None
-        Ld = model.latent_dim
-        B, dev = acts[0].shape[0], acts[0].device
-        layers = model._chains()[0]
-        dacts = chain_buffers(layers, B, dev, first=False)
-        nm_sample_bwd(_f32c(dz).reshape(B * K, Ld), eps, acts[3], _f32c(dheads), dacts[3], B, K, Ld)
-        g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, ("We1", "be1", "We2", "be2", "Wh", "bh"), B),
-                  input_grad=False)
-        return (None, None, None, None, None, *[g[k] for k in model._segment_names("enc")])
+def _sample(heads, eps, B, K, Ld):
+    """-> (z [B,K,L], heads [B, mean L | logvar L]).  VAE.py:2378-2391 / :2749-2765."""
+    z = torch.empty(B * K, Ld, device=heads.device)
+    nm_sample(heads, eps, z, B, K, Ld)
+    return z.view(B, K, Ld), heads
 
 
-class NMDecoderFn(torch.autograd.Function):
-    """z [.., L] -> (x_mean, x_logvar) as the two halves of ONE [M, 2d] buffer.  VAE.py:2393-2397 / :2767-2772."""
+def _sample_bwd(heads, eps, dz, dheads, out, B, K, Ld):
+    nm_sample_bwd(torch.zeros(B * K, Ld, device=heads.device) if dz is None else dz, eps, heads, dheads, out, B, K, Ld)
 
-    @staticmethod
-    def forward(ctx, model, z, *weights):
-        require_cuda(z, *weights)
-        d, Ld = model.obs_dim, model.latent_dim
-        lead = z.shape[:-1]
-        z2 = _f32c(z).reshape(-1, Ld)
-        M = z2.shape[0]
-        layers = model._chains()[1]
-        acts = chain_buffers(layers, M, z2.device, first=z2)
-        chain_fwd(layers, acts, M)
-        ctx.model, ctx.lead = model, lead
-        ctx.save_for_backward(*acts)
-        Y3 = acts[3].view(*lead, 2 * d)
-        return Y3[..., :d], Y3[..., d:]
 
-    @staticmethod
-    def backward(ctx, gxm, gxl):
-        model = ctx.model
-        acts = ctx.saved_tensors
-        d, Ld = model.obs_dim, model.latent_dim
-        M, dev = acts[0].shape[0], acts[0].device
-        # the fused loss hands back the two halves of one [M, 2d] buffer: use it in place
-        G = None
-        if (gxm.dtype == torch.float32 and gxl.dtype == torch.float32 and gxm.dim() >= 2
-                and gxm.stride() == gxl.stride() and gxm.stride(-1) == 1 and gxm.stride(-2) == 2 * d
-                and gxl.data_ptr() == gxm.data_ptr() + 4 * d
-                and all(gxm.stride(i) == gxm.stride(i + 1) * gxm.shape[i + 1] for i in range(gxm.dim() - 2))):
-            G = gxm.as_strided((M, 2 * d), (2 * d, 1))
-        if G is None:
-            G = torch.cat([_f32c(gxm).reshape(M, d), _f32c(gxl).reshape(M, d)], 1)
-        layers = model._chains()[1]
-        dacts = chain_buffers(layers, M, dev, last=G)
-        g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
-        chain_bwd(layers, acts, dacts, M, wgrad_now, wgrad_now_keys(layers, g, ("Wd1", "bd1", "Wd2", "bd2", "Wx", "bx"), M),
-                  y_gate=acts[3], gate=ACT_SIGMOID_HARDTANH, gate_split=d)
-        return (None, dacts[0].view(*ctx.lead, Ld), *[g[k] for k in model._segment_names("dec")])
+# the decoder returns (x_mean, x_logvar) as the two halves of ONE [M, 2d] buffer (VAE.py:2393-2397 / :2767-2772)
+FAMILY = Family(_ENC_NAMES, _DEC_NAMES, lambda x, mask, out, B, d: nm_mul(x, mask, out), _sample, _sample_bwd, 2)
 
 
 class NMLossFn(torch.autograd.Function):
@@ -281,7 +206,7 @@ class NMLossFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ model classes
-class _NMBase(FlatParams, nn.Module):
+class _NMBase(_ReferenceAttrs, FlatParams, nn.Module):
     regularised = False
     # flat parameter buffer: [W b | We1 be1 We2 be2 Wmu Wls bmu bls | Wd1 bd1 Wd2 bd2 Wxm Wxl bxm bxl]; the two heads of the
     # encoder and of the decoder are adjacent, so each pair is one GEMM operand (Wh / bh, Wx / bx)
@@ -299,19 +224,7 @@ class _NMBase(FlatParams, nn.Module):
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates):
         super().__init__()
-        if obs_dim > 256 or latent_dim > 64:
-            raise L.VpcError("the MNAR-path kernels support obs_dim <= 256 and latent_dim <= 64")
-        self.obs_dim = obs_dim
-        self.hid_dim = hid_dim
-        self.emb_dim = 10
-        self.num_samples = num_samples
-        self.num_estimates = num_estimates
-        self.latent_dim = latent_dim
-        self.batch_size = training_parameters["batch_size"]
-        self.K = K
-        self.obs_std = 0.1
-        self.number_components = 500
-        self.training_paramters = training_parameters  # (sic) VAE.py:2341
+        self._init_reference_attrs("MNAR", obs_dim, hid_dim, K, latent_dim, training_parameters, num_samples, num_estimates)
         d, Ld = obs_dim, latent_dim
         # parameter containers, created in the reference's order (same seed -> same initial weights)
         self.seq_encoder = nn.Sequential(nn.Linear(d, HID), nn.ELU(), nn.Linear(HID, HID), nn.ELU())
@@ -338,7 +251,7 @@ class _NMBase(FlatParams, nn.Module):
         B = xf.shape[0]
         if sample and eps is None:
             eps = torch.randn(B, K, Ld, device=xf.device)  # Normal(mean, std).rsample(), VAE.py:2387 / :2761
-        z, heads = NMEncoderFn.apply(self, xf, mf, _f32c(eps) if sample else None, K, *self._enc_weights())
+        z, heads = ChainEncoderFn.apply(FAMILY, self, xf, mf, _f32c(eps) if sample else None, K, *self._enc_weights())
         mean = heads[:, :Ld].unsqueeze(1).expand(B, K, Ld)
         log_var = heads[:, Ld:].unsqueeze(1).expand(B, K, Ld)
         mean._vpc_heads = heads
@@ -352,7 +265,7 @@ class _NMBase(FlatParams, nn.Module):
     def decoder(self, z_int):
         """VAE.py:2393-2397 / :2767-2772 -> (x_mean, x_logvar)."""
         L.require_cuda(z_int)
-        return NMDecoderFn.apply(self, z_int, *self._dec_weights())
+        return ChainDecoderFn.apply(FAMILY, self, z_int, *self._dec_weights())
 
     @staticmethod
     def _heads_of(mean, logvar):
@@ -438,7 +351,7 @@ class notMIWAE_myversion(_NMBase):
 
 
 # ------------------------------------------------------------------------------------------------ streaming imputation
-STREAM_MAX_D, STREAM_MAX_L = 128, 16  # limits of csrc/vpc_nm_impute.hip
+STREAM_MAX_D = 128  # obs_dim limit of csrc/vpc_nm_impute.hip (latent_dim: chainfamily.STREAM_MAX_L)
 
 
 def nm_impute_scratch(B, S, d, Ld, s_chunk):
@@ -453,14 +366,6 @@ def nm_impute(flat, x, mask, eps, seed, offset, row0, part, xm, lse, B, S, d, Ld
                               int(bool(regularised)), stream_ptr()), "vpc_nm_impute")
 
 
-def impute_chunk(B, S, n_cu):
-    """The default s_chunk of impute_stream: miwae.impute_chunk's rule (as few chunks per row as still give one workgroup
-    per compute unit, the chunks of a row balanced), kept for this kernel by the sweep of profiles/nm_impute_notes.md."""
-    from .miwae import impute_chunk as rule  # (miwae imports this module)
-    return rule(B, S, n_cu)
-
-
-@torch.no_grad()
 def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=0, row0=0, s_chunk=None,
                   return_lse=False, missing_process="selfmasking_known"):
     """The llh_eval imputation of every row of x with num_samples draws (evaluate.py:13-69 through VAE.py:2398-2461 /
@@ -483,37 +388,13 @@ def impute_stream(model, x, mask, num_samples=None, eps=None, seed=None, offset=
     if missing_process != "selfmasking_known":
         raise L.VpcError("impute_stream: only the reference's default missing_process='selfmasking_known' is accelerated")
     d, Ld = model.obs_dim, model.latent_dim
-    S = model.num_samples if num_samples is None else int(num_samples)
-    require_cuda(x, mask, eps)
-    if not (1 <= d <= STREAM_MAX_D and 1 <= Ld <= STREAM_MAX_L):
-        raise L.VpcError(f"impute_stream supports obs_dim <= {STREAM_MAX_D} and latent_dim <= {STREAM_MAX_L}: got {d}, {Ld}")
-    xf, mf = _f32c(x.reshape(-1, d)), _f32c(mask.reshape(-1, d))
-    B = xf.shape[0]
-    if B < 1 or S < 1 or mf.shape != xf.shape:
-        raise L.VpcError(f"impute_stream: B = {B}, num_samples = {S}, mask {tuple(mf.shape)} for x {tuple(xf.shape)}")
-    if s_chunk is None:
-        s_chunk = impute_chunk(B, S, L.max_blocks() // 2)
-    if s_chunk < 1:
-        raise L.VpcError(f"impute_stream: s_chunk = {s_chunk} < 1")
-    if eps is not None:
-        if tuple(eps.shape) != (2, B, S, Ld):
-            raise L.VpcError(f"impute_stream: eps {tuple(eps.shape)}, expected {(2, B, S, Ld)}")
-        eps = _f32c(eps)
-    elif seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    n = nm_impute_scratch(B, S, d, Ld, s_chunk)
-    if n == 0:
-        raise L.VpcError(f"impute_stream: shape (B, S, d, L) = {(B, S, d, Ld)} is outside the kernel's limits")
-    flat = model.flatten_parameters()
-    require_cuda(flat)
-    if flat.numel() != 2 * d + model._n_enc + model._n_dec:  # the kernel reads the buffer by the offsets of _flat_spec
-        raise L.VpcError(f"impute_stream: flat parameter buffer of {flat.numel()} floats for (d, L) = {(d, Ld)}")
-    with torch.cuda.device(xf.device):
-        part = torch.empty(n, device=xf.device)
-        xm = torch.empty(B, d, device=xf.device)
-        lse = torch.empty(B, device=xf.device) if return_lse else None
-        nm_impute(flat, xf, mf, eps, seed or 0, offset, row0, part, xm, lse, B, S, d, Ld, s_chunk, model.regularised)
-    return (xm, lse) if return_lse else xm
+
+    def launch(flat, *args):
+        if flat.numel() != 2 * d + model._n_enc + model._n_dec:  # the kernel reads the buffer by the offsets of _flat_spec
+            raise L.VpcError(f"impute_stream: flat parameter buffer of {flat.numel()} floats for (d, L) = {(d, Ld)}")
+        nm_impute(flat, *args, model.regularised)
+    return cf.impute_stream(model, x, mask, num_samples, eps, seed, offset, row0, s_chunk, return_lse, STREAM_MAX_D,
+                            STREAM_MAX_L, nm_impute_scratch, launch)
 
 
 # ------------------------------------------------------------------------------------------------ fused step
@@ -524,44 +405,34 @@ _DEC_WKEYS = (("dec_wgrad1", 2), ("dec_wgrad2", 1), ("dec_wgrad3", 0))
 _ENC_WKEYS = (("enc_bwd", 5), ("enc_bwd", 4), ("enc_bwd", 3))
 
 
-class NMTrainer(_FlatAdamTrainer):
+class NMTrainer(_ChainTrainer):
     """The whole training step of the MNAR path (train.py:28-117 for 'reg_notMIWAE*' / 'vanilla_notMIWAE*') as a
     fixed sequence of HIP launches, no host synchronisation: float mask_p draw + stacked encoder input, Philox
     normals, encoder / decoder GEMM chains with the q and p passes STACKED along the batch (one GEMM per layer for
     both passes), the fused loss kernel, the backward GEMM chain writing straight into one flat gradient buffer,
     one all-reduce of [grads | loss] under data parallelism, flat Adam."""
-    step_timers = True
+    family, model_base, model_names = FAMILY, _NMBase, "REG_notMIWAE_v2 and notMIWAE_myversion"
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=1, rank=0,
                  precision="f32"):
         """precision: "f32", "bf16x3" or "bf16" for the 17 GEMMs of the step (csrc/vpc_bf16.h; operands stay fp32 in
         memory and are converted in registers); the loss kernel and Adam are fp32 in every mode.  (`eps` is Adam's
         epsilon, `self.adam_eps`; `self.eps` is the step's workspace of normals.)"""
-        if not isinstance(model, _NMBase):
-            raise TypeError("NMTrainer supports REG_notMIWAE_v2 and notMIWAE_myversion")
+        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank)
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r}: expected one of {sorted(PRECISIONS)}")
-        super().__init__(model, lr, betas, eps, seed, process_group, world_size, rank, 1)
-        self.reg = model.regularised
         self.precision, self.prec = precision, PRECISIONS[precision]
         self.loss = self.tail  # [grads | loss] -> ONE all-reduce per step
-        self.out8 = torch.zeros(8, dtype=torch.float64, device=self.dev)
-        self.g = model._named_views(self.grad)
-        self._B = self._v = None
 
     def invalidate_image(self):
         """Alias of model.invalidate_images(): after writing parameters behind torch's version counters."""
         self.model.invalidate_images()
 
-    def _ws(self, B, v=None):
-        v = self.model._views() if v is None else v
-        if self._B == B and self._v is v:
-            return
+    def _buffers(self, B, e):
         m, dev = self.model, self.dev
         d, Ld, K = m.obs_dim, m.latent_dim, m.num_samples
         P = 2 if self.reg else 1
         R, M = P * B, P * B * K
-        e = lambda *s: torch.empty(*s, device=dev)
         self.xin, self.mask_p = e(R, d), e(B, d)
         self.h1, self.h2, self.heads = e(R, HID), e(R, HID), e(R, 2 * Ld)
         self.eps = e(2, B, K, Ld)  # reg: eps_q, eps_p; vanilla: eps (sampling), eps_kl (MC KL)
@@ -573,14 +444,6 @@ class NMTrainer(_FlatAdamTrainer):
         self.dg2, self.dg1, self.dz = e(Mg, HID), e(Mg, HID), e(Mg, Ld)
         Rg = 0 if self.use_nmdec else R     # (the fused path's encoder backward is one kernel too: nmenc_bwd)
         self.dh2, self.dh1 = e(Rg, HID), e(Rg, HID)
-        # the two GEMM chains on their workspaces, and the per-layer partial buffers of the six weight gradients in launch order
-        self.enc_layers, self.dec_layers = m._chains()
-        self.enc_acts, self.enc_dacts = [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht]
-        self.dec_acts, self.dec_dacts = [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G]
-        g = self.g
-        self._wgrad_workspace([(M, 2 * d, HID), (M, HID, HID), (M, HID, Ld), (R, 2 * Ld, HID), (R, HID, HID), (R, HID, d)],
-                              [(g["Wx"], g["bx"]), (g["Wd2"], g["bd2"]), (g["Wd1"], g["bd1"]), (g["Wh"], g["bh"]),
-                               (g["We2"], g["be2"]), (g["We1"], g["be1"])], sized=not self.use_nmdec)
         nbytes = int(lib().vpc_nm_loss_scratch(B, d))
         self.scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         # the slices the step passes to its launches, made once per batch size (a tensor view costs 1-3 us of host time, and the
@@ -603,10 +466,8 @@ class NMTrainer(_FlatAdamTrainer):
             self.nd_part = e(nblk.value * npart.value)
             self.ne_part = e(nblk.value * int(self._nd_tables[3].numel()))  # the encoder-backward kernel's blocks (fused tail)
             self.nd_stat = torch.empty(nblk.value * 5, dtype=torch.float64, device=dev)
-        self._B, self._v = B, v
-
-    def train_step(self, x, mask, *, alpha, p_missingness, **schedule):
-        return self.step(x, mask, alpha=alpha, p_missingness=p_missingness)
+        return (R, M, [self.xin, self.h1, self.h2, self.heads], [None, self.dh1, self.dh2, self.dht],
+                [self.z, self.g1, self.g2, self.Y], [self.dz, self.dg1, self.dg2, self.G])
 
     def step(self, x, mask, mask_p=None, eps=None, *, alpha=1.0, p_missingness=30, global_batch=None, row_lo=None,
              _state=None):
@@ -626,26 +487,14 @@ class NMTrainer(_FlatAdamTrainer):
         P = 2 if reg else 1
         R, M, BK = P * B, P * B * K, B * K
         t = self._timed
-        rng_inc = (2 * Bg * K * Ld + 3) // 4 + (Bg * d + 3) // 4 + 1  # what the GLOBAL batch consumes
+        rng_inc = chain_draw_increment(2 * Bg * K * Ld, Bg, d)  # what the GLOBAL batch consumes
         sharded = (row_lo * d) % 4 == 0 and (K * Ld) % 4 == 0
         # shapes whose shards do not start on a Philox group: per-rank counter streams instead of global-row counters
         rank_off = 0 if sharded else (self.rank << 44)
         eps_shard = (B, Bg, row_lo, K * Ld) if sharded else None
         # ---- inputs
-        if reg and mask_p is not None:
-            mp = _f32c(mask_p.reshape(-1, d))
-            nm_mul(xf, mf, self.xin[:B])
-            nm_mul(xf, mp, self.xin[B:])
-            if eps is None:
-                fill_normal(self.eps, self.seed, self.rng_offset + (1 << 40) + rank_off, _state, eps_shard)
-        else:
-            mp = self.mask_p if reg else None
-            t("prep", nm_prep, xf, mf, mp, self.xin, B, d, 1.0 - p_missingness / 100.0, self.seed,
-              self.rng_offset + rank_off, self.eps if eps is None else None, self.rng_offset + (1 << 40) + rank_off,
-              _state, row_lo * d if sharded else 0, eps_shard)
-        if eps is not None:
-            self.eps.copy_(eps)
-        self.rng_offset += rng_inc
+        mp = self._draw_inputs(xf, mf, mask_p, eps, B, d, p_missingness, rng_inc, _state, rank_off, eps_shard,
+                               row_lo * d if sharded else 0)
         # ---- forward
         # single device, eager: everything behind the encoder forward is three launches (decoder tiles, encoder-backward tiles, one tail
         # that reduces both sets of blocks, applies Adam and re-packs the image: vpc_nm_fused_bwd_step) and the pack launch goes

@@ -1,7 +1,9 @@
 """What the step trainers (FusedTrainer, NMTrainer, EDDITrainer, WideTrainer, MIWTrainer, FlowTrainer, EDDIMnistTrainer)
 share: Adam state on one flat parameter buffer and the Adam launch that closes a step, the flat bucket [grads | loss tail]
 that data parallelism all-reduces in ONE collective, the deferred weight gradients of the GEMM chains (per-layer partials,
-one reduction launch), timers, the loss readers and the capture / replay of a step as a HIP graph."""
+one reduction launch), timers, the loss readers and the capture / replay of a step as a HIP graph; and the counter rules of
+the device draws, one function per rule.  (What NMTrainer, MIWTrainer and FlowTrainer share beyond this base - constructor,
+workspace guard, chain wiring, input draws - is chainfamily._ChainTrainer.)"""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -34,6 +36,16 @@ def draw_counters(rng_offset, draw_mask, planes, rows_local, rows_global, row_lo
     offset_eps = rng_offset + ((rows_global * row_width + 7) // 8 + 1 if draw_mask else 0)
     return Draws(rng_offset, offset_eps, offset_eps + planes * rows_global * (pitch // 4), row_lo * row_width,
                  (rows_local, rows_global, row_lo, pitch))
+
+
+def chain_draw_increment(eps_floats, rows, row_width):
+    """THE counter rule of the chain-backed steps' draws (NMTrainer, MIWTrainer, FlowTrainer, MIWEnsembleTrainer): what one
+    step adds to the trainer's rng_offset.  The eps planes sit on their own stream position (rng_offset + 2^40) and take one
+    Philox call per 4 floats of `eps_floats`, rounded up; the float mask_p draw takes one call per 4 elements of the
+    [rows, row_width] array, rounded up, and one more.  Both streams advance by the sum, so no step reuses a counter of
+    either.  Data parallel (NMTrainer): eps_floats and rows are those of the GLOBAL batch, so all ranks stay on one stream;
+    every other caller passes its own."""
+    return (eps_floats + 3) // 4 + (rows * row_width + 3) // 4 + 1
 
 
 def eval_draw_counters(rng_offset, draw_rows, pitch=16):

@@ -16,8 +16,8 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .chainfamily import nm_mul, nm_sample, nm_sample_bwd
 from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, _f32c, linear_dgrad, linear_fwd, linear_wgrad
-from .notmiwae import nm_mul, nm_sample, nm_sample_bwd
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer, draw_counters
 
