@@ -602,7 +602,6 @@ def test_eddi_trainer_vs_port(L, d, K, B, kind, monkeypatch):
 @pytest.mark.parametrize("d,L,B", lc.WIDE_CASES, ids=[f"L{L}-d{d}-B{B}" for d, L, B in lc.WIDE_CASES])
 def test_wide_path_by_latent_width(d, L, B):
     """test_wide.test_reg_api_and_trainer_vs_oracle with the latent width passed in.  (14, 16, 37) is wide because of L alone."""
-    from vpc_amd.wide import WideDecoderFn, WideEncoderFn
     seed = lc.case_seed(L, d, B)
     params = O.init_params(d, L, seed=seed)
     x, mask, mask_p, eq, ep, _ = lc.synth(B, d, L, seed=seed + 1)
@@ -613,10 +612,10 @@ def test_wide_path_by_latent_width(d, L, B):
     t = m.trainable()
     xd, mkd, mpd = x.to(DEV), mask.to(DEV), mask_p.to(DEV)
     md, mpu = ops.as_mask_u8(mkd), ops.as_mask_u8(mpd)
-    zq, mq, lq = WideEncoderFn.apply(m, xd, md, eq.to(DEV), *t[:6])
-    xq = WideDecoderFn.apply(m, zq, *t[6:])
-    zp, mp_, lp = WideEncoderFn.apply(m, xd, mpu, ep.to(DEV), *t[:6])
-    xp = WideDecoderFn.apply(m, zp, *t[6:])
+    zq, mq, lq = m._encode(xd, md, eps=eq.to(DEV))
+    xq = m.decoder(zq)[0]
+    zp, mp_, lp = m._encode(xd, mpu, eps=ep.to(DEV))
+    xp = m.decoder(zp)[0]
     for got, want in ((mp_, outs[0]), (lp, outs[1]), (xp, outs[2]), (mq, outs[4]), (lq, outs[5]), (xq, outs[6])):
         e = float((got.detach().cpu() - want).abs().max())
         lc.record("11_wide", "forward", e, lc.FWD_ATOL)

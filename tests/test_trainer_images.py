@@ -45,6 +45,14 @@ def _eddi():
     return lambda: tr.step(x, mk, alpha=0.5, p_missingness=30)
 
 
+def _eddi_small(d):
+    torch.manual_seed(3)
+    m = ed.Reg_EDDI(d, 500, 10, 10, {"batch_size": 5, "patience": 1}, "exp", "kl_reg").cuda()
+    tr = ed.EDDITrainer(m, seed=9)
+    x, mk = _data(5, d, 6)
+    return lambda: tr.step(x, mk, alpha=0.5, p_missingness=30)
+
+
 def _wide():
     torch.manual_seed(7)
     m = vpc.Reg_VAE(200, 500, 10, 10, {"batch_size": 96, "patience": 1}, "exp", "kl_reg").cuda()
@@ -104,6 +112,11 @@ LAUNCHES = [
      ["vpc_pack_weights", "vpc_draw_step", "vpc_eddi_fold", "vpc_eddi_front_fwd"] + ["vpc_linear_fwd"] * 3 +
      ["vpc_decoder_fused", "vpc_reduce_partials", "vpc_loss_finalize"] + _GEMM_BWD +
      ["vpc_linear_wgrad_reduce", "vpc_eddi_front_scratch", "vpc_eddi_front_bwd", "vpc_adam_step"]),
+    # the small-batch step at B = 5: obs_dim % 4 == 0 draws inside the kernel, else the chain's draw launch on the unpadded rows
+    ("eddi_small_b5_d12", None, lambda: _eddi_small(12),
+     _SMALL + ["vpc_step_small_eddi_draw_f32", "vpc_reduce_step_adam_eddi"]),
+    ("eddi_small_b5_d14", None, lambda: _eddi_small(14),
+     _SMALL + ["vpc_draw_step", "vpc_step_small_eddi_f32", "vpc_reduce_step_adam_eddi"]),
     ("wide", None, _wide,
      ["vpc_draw_mask", "vpc_fill_normal"] + _WIDE_FWD * 2 + ["vpc_loss_fwd_bwd", "vpc_loss_finalize"] + _WIDE_BWD * 2 +
      ["vpc_adam_step"]),
@@ -156,22 +169,41 @@ def test_steady_state_launch_sequence(path, tile, make, expected, monkeypatch):
     assert rec.names == expected
 
 
-# ---- the eager path of the three chain-backed families: model.forward_loss under grad, then backward, through the encoder /
-# decoder autograd Functions.  B = 8, d = 12, latent 10, K = S = 3 (the flows: hid_dim 64).
+# ---- the eager path of the GEMM-backed families: model.forward_loss under grad, then backward, through the encoder /
+# decoder autograd Functions.  The chain-backed six: B = 8, d = 12, latent 10, K = S = 3 (the flows: hid_dim 64).  The dense
+# classes at the three ways a model is wide, and the point-net classes (the mnist pair fed as [B, 4, 5]): B = 5.
+_TP5 = {"batch_size": 5, "patience": 1}
+_EAGER_B5 = {  # name -> (constructor, input shape, bool masks)
+    "Reg_VAE_d129": (lambda: vpc.Reg_VAE(129, 500, 10, 10, _TP5, "exp", "kl_reg"), (5, 129), False),
+    "vanilla_VAE_mask_d65": (lambda: vpc.vanilla_VAE_mask(65, 500, 10, 10, _TP5, "exp"), (5, 65), False),
+    "Reg_VAE_d14_L16": (lambda: vpc.Reg_VAE(14, 500, 10, 16, _TP5, "exp", "kl_reg"), (5, 14), False),
+    "Reg_EDDI": (lambda: vpc.Reg_EDDI(14, 500, 10, 10, _TP5, "exp", "kl_reg"), (5, 14), False),
+    "vanilla_EDDI": (lambda: vpc.vanilla_EDDI(14, 500, 10, 10, _TP5, "exp"), (5, 14), False),
+    "Reg_EDDI_mnist": (lambda: vpc.Reg_EDDI_mnist(20, 500, 4, 3, _TP5, "exp", "kl_reg"), (5, 4, 5), True),
+    "vanilla_EDDI_mnist": (lambda: vpc.vanilla_EDDI_mnist(20, 500, 4, 3, _TP5, "exp"), (5, 4, 5), False),
+}
+
+
 def _eager_model(name):
     torch.manual_seed(0)
+    if name in _EAGER_B5:
+        return _EAGER_B5[name][0]().cuda()
     if "Flow" in name:
         return getattr(vpc, name)(12, 64, 10, 10, {"batch_size": 8, "patience": 1}).cuda()
     return getattr(vpc, name)(12, 500, 10, 10, {"batch_size": 8, "patience": 1}, 3, 1).cuda()
 
 
-def _eager_data():
-    x, m = _data(8, 12, 2, float_mask=True)
-    return x, m, m * (torch.rand(8, 12, generator=torch.Generator().manual_seed(3)) < 0.7).float().cuda()
+def _eager_data(name=None):
+    _, shape, bool_masks = _EAGER_B5.get(name, (None, (8, 12), False))
+    g = torch.Generator().manual_seed(2)
+    x, m = torch.rand(*shape, generator=g), torch.rand(*shape, generator=g) < 0.7
+    mp = m & (torch.rand(*shape, generator=torch.Generator().manual_seed(3)) < 0.7)
+    return x.cuda(), (m if bool_masks else m.float()).cuda(), (mp if bool_masks else mp.float()).cuda()
 
 
-def _eager_full(model):
-    x, m, mp = _eager_data()
+def _eager_full(name):
+    model = _eager_model(name)
+    x, m, mp = _eager_data(name)
 
     def run():
         model.zero_grad()
@@ -180,8 +212,9 @@ def _eager_full(model):
     return run
 
 
-def _eager_z_only(model):
-    x, m, _ = _eager_data()
+def _eager_z_only(name):
+    model = _eager_model(name)
+    x, m, _ = _eager_data(name)
 
     def run():
         model.zero_grad()
@@ -189,26 +222,37 @@ def _eager_z_only(model):
     return run
 
 
+_PN_BWD = lambda p: [f"vpc_{p}_front_scratch", f"vpc_{p}_front_bwd"]  # noqa: E731
 _ENC_FWD = {"nm": ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"],
             "miw": ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_miw_sample"],
-            "flow": ["vpc_flow_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_flow_fwd"]}
-_DEC_FWD = {"nm": ["vpc_linear_fwd"] * 3, "miw": ["vpc_linear_fwd"] * 3 + ["vpc_miw_heads"], "flow": ["vpc_linear_fwd"] * 5}
+            "flow": ["vpc_flow_prep"] + ["vpc_linear_fwd"] * 3 + ["vpc_flow_fwd"],
+            "wide": ["vpc_nm_mul"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"],
+            "eddi": ["vpc_eddi_fold", "vpc_eddi_front_fwd"] + ["vpc_linear_fwd"] * 3 + ["vpc_nm_sample"],
+            "eddiw": ["vpc_eddiw_fold", "vpc_eddiw_front_fwd"] + ["vpc_linear_fwd"] * 4 + ["vpc_nm_sample"]}
+_DEC_FWD = {"nm": ["vpc_linear_fwd"] * 3, "miw": ["vpc_linear_fwd"] * 3 + ["vpc_miw_heads"], "flow": ["vpc_linear_fwd"] * 5,
+            "wide": ["vpc_linear_fwd"] * 3, "eddi": ["vpc_decoder_fwd"], "eddiw": ["vpc_linear_fwd"] * 4}
 _ENC_BWD = {"nm": ["vpc_nm_sample_bwd"] + _SWD * 2 + _SWD[:2], "miw": ["vpc_miw_sample_bwd"] + _SWD * 2 + _SWD[:2],
-            "flow": ["vpc_flow_bwd"] + _SWD * 2 + _SWD[:2]}
-_DEC_BWD = {"nm": _SWD * 3, "miw": ["vpc_miw_heads_bwd"] + _SWD * 3, "flow": _SWD * 5}
+            "flow": ["vpc_flow_bwd"] + _SWD * 2 + _SWD[:2], "wide": ["vpc_nm_sample_bwd"] + _SWD * 2 + _SWD[:2],
+            "eddi": ["vpc_nm_sample_bwd"] + _SWD * 3 + _PN_BWD("eddi"),  # (the trunk's input, the aggregate, takes a gradient)
+            "eddiw": ["vpc_nm_sample_bwd"] + _SWD * 4 + _PN_BWD("eddiw")}
+_DEC_BWD = {"nm": _SWD * 3, "miw": ["vpc_miw_heads_bwd"] + _SWD * 3, "flow": _SWD * 5, "wide": _SWD * 3,
+            "eddi": ["vpc_decoder_bwd", "vpc_reduce_partials"], "eddiw": _SWD * 4}
 _LOSS = {f: [f"vpc_{f}_loss_scratch", f"vpc_{f}_loss"] for f in ("nm", "miw", "flow")}
+_LOSS.update({f: ["vpc_loss_fwd_bwd", "vpc_loss_finalize"] for f in ("wide", "eddi", "eddiw")})
 
 
 def _eager_expected(f, passes, flow_order=False):
     """Forward of `passes` (encoder, decoder) pairs, the loss, then the backward of the passes from the last one down.  The
-    regularised flow runs both encoders before both decoders (flow.REG_VAEFlow.forward), and autograd mirrors that."""
+    regularised flow runs both encoders before both decoders (flow.REG_VAEFlow.forward), and autograd mirrors that; so does
+    Reg_VAE.forward, which the wide dense classes and Reg_EDDI run pass by pass."""
     if flow_order:
         return _ENC_FWD[f] * 2 + _DEC_FWD[f] * 2 + _LOSS[f] + _DEC_BWD[f] * 2 + _ENC_BWD[f] * 2
     return (_ENC_FWD[f] + _DEC_FWD[f]) * passes + _LOSS[f] + (_DEC_BWD[f] + _ENC_BWD[f]) * passes
 
 
-# recorded with _Recorder on the commit before the six encoder / decoder Functions became one pair (the lists hold C ABI calls,
-# host-side scratch queries included); the *_z_only rows backpropagate through the encoder's first output alone
+# recorded with _Recorder on the commit before the encoder / decoder Functions of a family became the one pair (the first eight
+# rows before the MNAR, MIWAE and flow classes moved, the others before the wide and point-net classes did; the lists hold C ABI
+# calls, host-side scratch queries included); the *_z_only rows backpropagate through the encoder's first output alone
 EAGER = [
     ("REG_notMIWAE_v2", _eager_full, _eager_expected("nm", 2)),
     ("notMIWAE_myversion", _eager_full, _eager_expected("nm", 1)),
@@ -218,6 +262,16 @@ EAGER = [
     ("VAEFlow", _eager_full, _eager_expected("flow", 1)),
     ("Reg_MIWAE", _eager_z_only, _ENC_FWD["miw"] + _ENC_BWD["miw"]),
     ("REG_VAEFlow", _eager_z_only, _ENC_FWD["flow"] + _ENC_BWD["flow"]),
+    ("Reg_VAE_d129", _eager_full, _eager_expected("wide", 2, flow_order=True)),
+    ("vanilla_VAE_mask_d65", _eager_full, _eager_expected("wide", 1)),
+    ("Reg_VAE_d14_L16", _eager_full, _eager_expected("wide", 2, flow_order=True)),
+    ("Reg_EDDI", _eager_full, _eager_expected("eddi", 2, flow_order=True)),
+    ("vanilla_EDDI", _eager_full, _eager_expected("eddi", 1)),
+    ("Reg_EDDI_mnist", _eager_full, _eager_expected("eddiw", 2)),
+    ("vanilla_EDDI_mnist", _eager_full, _eager_expected("eddiw", 1)),
+    ("Reg_VAE_d129", _eager_z_only, _ENC_FWD["wide"] + _ENC_BWD["wide"]),
+    ("Reg_EDDI", _eager_z_only, _ENC_FWD["eddi"] + _ENC_BWD["eddi"]),
+    ("Reg_EDDI_mnist", _eager_z_only, _ENC_FWD["eddiw"] + _ENC_BWD["eddiw"]),
 ]
 
 
@@ -225,7 +279,7 @@ EAGER = [
 def test_eager_launch_sequence(name, make, expected, monkeypatch):
     """forward_loss under grad and backward issue the C ABI calls they issued when every family had its own pair of
     autograd Functions, in the same order (second run of a model: its chains are built)."""
-    run = make(_eager_model(name))
+    run = make(name)
     run()
     rec = _Recorder(_lib.lib())
     monkeypatch.setattr(_lib, "_lib", rec)
@@ -271,6 +325,28 @@ def test_nm_encoder_one_output_gradient():
                                                                                   model.q_logstd[0].bias.grad.clone()])
     assert all(g.abs().max() > 0 for g in grads[0])
     assert all(torch.equal(a, b) for a, b in zip(*grads))
+
+
+@pytest.mark.parametrize("name", ["Reg_VAE_d129", "Reg_EDDI", "Reg_EDDI_mnist"])
+def test_encoder_one_output_gradient(name):
+    """The same for a wide dense class and a point-net class of either width: every parameter the encoder reads, the point-net
+    front-end's four tensors included, gets the two-output run's gradient, bit for bit."""
+    model = _eager_model(name)
+    x, m, _ = _eager_data(name)
+    grads = []
+    for both in (False, True):
+        model.zero_grad()
+        torch.manual_seed(1)
+        z, mean, _ = model.encoder(x, m)
+        if both:
+            torch.autograd.backward([z, mean], [torch.ones_like(z), torch.zeros_like(mean)])
+        else:
+            z.sum().backward()
+        grads.append({k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None})
+    want = {k for k, p in model.named_parameters() if p.requires_grad and not k.startswith("seq_decoder")}
+    assert set(grads[0]) == set(grads[1]) == want
+    assert all(g.abs().max() > 0 for g in grads[0].values())
+    assert all(torch.equal(grads[0][k], grads[1][k]) for k in want)
 
 
 def _reg_vae(B):

@@ -43,13 +43,12 @@ def test_reg_api_and_trainer_vs_oracle(d, B, augm):
     m = _model(cls, d, params, "kl_reg")
     assert m._wide
     # API path with injected eps
-    from vpc_amd.wide import WideDecoderFn, WideEncoderFn
     t = m.trainable()
     xd, md, mpd = x.cuda(), vpc.ops.as_mask_u8(mask.cuda()), vpc.ops.as_mask_u8(mask_p.cuda())
-    zq, mq, lq = WideEncoderFn.apply(m, xd, md, eq.cuda(), *t[:6])
-    xq = WideDecoderFn.apply(m, zq, *t[6:])
-    zp, mp_, lp = WideEncoderFn.apply(m, xd, mpd, ep.cuda(), *t[:6])
-    xp = WideDecoderFn.apply(m, zp, *t[6:])
+    zq, mq, lq = m._encode(xd, md, eps=eq.cuda())
+    xq = m.decoder(zq)[0]
+    zp, mp_, lp = m._encode(xd, mpd, eps=ep.cuda())
+    xp = m.decoder(zp)[0]
     for got, want in ((mp_, outs[0]), (lp, outs[1]), (xp, outs[2]), (mq, outs[4]), (lq, outs[5]), (xq, outs[6])):
         assert torch.allclose(got.detach().cpu(), want, atol=2e-5)
     _, tl = m.loss(xd, xp, m.x_logvar, mp_, lp, xq, m.x_logvar, mq, lq, mask.cuda(), mask_p.cuda(), 1, beta=0.9, alpha=0.8)

@@ -41,7 +41,6 @@ from . import _lib as L
 from ._lib import VpcError, check, lib, ptr, stream_ptr
 from .eddi_mnist import _EDDIMnistBase
 from .flow import _FlowBase
-from .linear import ACT_RELU, ACT_SIGMOID_HARDTANH, chain
 from .models import _VAEBase
 from .notmiwae import _NMBase
 
@@ -94,13 +93,8 @@ def _decoder_chain(model):
     d, Ld = getattr(model, "obs_dim", None), getattr(model, "latent_dim", None)
     if isinstance(model, _NMBase):
         return model._chains()[1], d, Ld, None
-    if isinstance(model, _FlowBase):
-        return model._chains()[1], d, Ld, float(model.obs_logvar)
-    if isinstance(model, _EDDIMnistBase):
-        return model._chains()[1], d, Ld, model._x_logvar_value
-    if isinstance(model, _VAEBase):
-        w = model.trainable()[6:12]
-        return chain(w, (ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), d), d, Ld, model._x_logvar_value
+    if isinstance(model, (_FlowBase, _VAEBase)):  # (_VAEBase: the dense classes at any width and both point-net pairs)
+        return model._chains()[1], d, Ld, float(model.obs_logvar) if isinstance(model, _FlowBase) else model._x_logvar_value
     raise VpcError("AIS needs a decoder that returns a Gaussian (mean, logvar) (AIS.py:125-140): "
                    f"{type(model).__name__} has none (MIWAE / Reg_MIWAE return the three tensors of a Student-t)")
 

@@ -2,9 +2,10 @@
 FlatParams model whose encoder and decoder are GEMM chains, with the family's sampler between them and its loss behind them,
 and a trainer that runs the q and p passes stacked along the batch.  Here, once:
 
-  * the elementwise ops every family borrows (nm_mul, nm_prep, nm_sample, nm_sample_bwd),
+  * the elementwise ops every family borrows (nm_mul, nm_prep, nm_sample, nm_sample_bwd, the one-sample Gaussian sampler),
   * ChainEncoderFn / ChainDecoderFn: the autograd frame (buffers, walkers, save_for_backward, gradient views), driven by the
-    family's `Family` record, which states the launches that differ,
+    family's `Family` record, which states the launches that differ.  The eager path of the wide dense classes (wide.py) and
+    of the two point-net families (eddi.py, eddi_mnist.py) runs on it too; their trainers keep their own frames,
   * _ChainTrainer: constructor, workspace guard, chain wiring, weight-gradient workspace, the inject-or-draw input step,
   * impute_stream: the host side of the streaming imputation kernels, with impute_chunk and impute_draws,
   * _ReferenceAttrs: the constructor prologue of the MNAR and MIWAE model classes.
@@ -33,6 +34,18 @@ def nm_sample(heads, eps, z, B, K, Ld):
 def nm_sample_bwd(dz, eps, heads, g_heads, out, B, K, Ld):
     check(lib().vpc_nm_sample_bwd(ptr(dz), Ld, ptr(eps), ptr(heads), 2 * Ld, ptr(g_heads), 2 * Ld, ptr(out), 2 * Ld, B,
                                   K, Ld, stream_ptr()), "vpc_nm_sample_bwd")
+
+
+def gauss_sample(heads, eps, B, S, Ld):
+    """The sampler of the dense and point-net families: one z = mean + eps * exp(logvar / 2) per row (eps None: the mean)
+    -> (z [B, L], heads [B, mean L | logvar L]); encoder() splits the heads.  VAE.py:387-395."""
+    z = torch.empty(B, Ld, device=heads.device)
+    nm_sample(heads, eps, z, B, 1, Ld)
+    return z, heads
+
+
+def gauss_sample_bwd(heads, eps, dz, dheads, out, B, S, Ld):
+    nm_sample_bwd(torch.zeros(B, Ld, device=heads.device) if dz is None else dz, eps, heads, dheads, out, B, 1, Ld)
 
 
 def nm_mul(x, mask, out):
@@ -71,12 +84,15 @@ class Family(NamedTuple):
     """What differs between the families in the encoder / decoder Functions; one instance per family, next to its raw ops."""
     enc_names: tuple  # W1, b1, W2, b2, .. of the encoder chain in the model's named views
     dec_names: tuple
-    enc_input: object  # (x, mask, out, B, d): the launch that writes the encoder chain's input
+    enc_input: object  # (x, mask, out, B, d, *front weights): the launch that writes the encoder chain's input
     sample: object  # (heads, eps, B, S, Ld) -> the encoder's two outputs (allocates z, launches the sampler)
     sample_bwd: object  # (heads, eps, dz, d_second, out, B, S, Ld); dz / d_second: contiguous fp32 or None
     dec_blocks: int  # the decoder returns this many column blocks, obs_dim wide, of one buffer
     dec_heads: object = None  # None: the chain's last activation is an output gate passed to chain_bwd (Sigmoid | Hardtanh);
     # else (fwd(y_raw, M, d) -> activated buffer, bwd(y_raw, g_act, g_raw, M, d)): a head-activation launch pair
+    input_bwd: object = None  # the point-net families, whose input op has n_front parameters of its own (the segment "front",
+    n_front: int = 0  # the LAST weights of apply()): enc_input returns the tensors its backward reads again, and
+    # input_bwd(saved, d_input, g, B, d) writes the front gradients g[name] from the gradient of the chain's input
 
 
 class ChainEncoderFn(torch.autograd.Function):
@@ -88,25 +104,30 @@ class ChainEncoderFn(torch.autograd.Function):
         B, dev = x.shape[0], x.device
         layers = model._chains()[0]
         acts = chain_buffers(layers, B, dev)
-        fam.enc_input(x, mask, acts[0], B, model.obs_dim)
+        front = fam.enc_input(x, mask, acts[0], B, model.obs_dim, *weights[len(weights) - fam.n_front:])
         chain_fwd(layers, acts, B)
         out = fam.sample(acts[-1], eps, B, S, model.latent_dim)
-        ctx.fam, ctx.model, ctx.S, ctx.has_eps, ctx.nw = fam, model, S, eps is not None, len(weights)
-        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev))
+        ctx.fam, ctx.model, ctx.S, ctx.has_eps, ctx.nw, ctx.layers = fam, model, S, eps is not None, len(weights), layers
+        ctx.save_for_backward(*acts, eps if eps is not None else torch.empty(0, device=dev), *(front or ()))
         return out
 
     @staticmethod
     def backward(ctx, dz, d2):
-        fam, model = ctx.fam, ctx.model
-        *acts, eps = ctx.saved_tensors
+        fam, model, layers = ctx.fam, ctx.model, ctx.layers  # (the forward's chain, kept: model._chains() is a flatten check per call)
+        saved, n = ctx.saved_tensors, len(layers) + 1
+        acts, eps, front = saved[:n], saved[n], saved[n + 1:]  # (front: what enc_input returned; empty but for the point-nets)
         B, dev = acts[0].shape[0], acts[0].device
-        layers = model._chains()[0]
-        dacts = chain_buffers(layers, B, dev, first=False)
+        dacts = chain_buffers(layers, B, dev, first=None if front else False)
         fam.sample_bwd(acts[-1], eps if ctx.has_eps else None, None if dz is None else _f32c(dz),
                        None if d2 is None else _f32c(d2), dacts[-1], B, ctx.S, model.latent_dim)
         g = model._segment_views(torch.empty(model._n_enc, device=dev), "enc")
-        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, fam.enc_names, B), input_grad=False)
-        return (None,) * 6 + tuple(g.values())[:ctx.nw]  # (_segment_views: the segment's tensors in order, then the aliases)
+        chain_bwd(layers, acts, dacts, B, wgrad_now, wgrad_now_keys(layers, g, fam.enc_names, B), input_grad=bool(front))
+        grads = tuple(g.values())[:ctx.nw - fam.n_front]  # (_segment_views: the segment's tensors in order, then the aliases)
+        if front:
+            g = model._segment_views(torch.empty(model._flat_table()[2]["front"][3], device=dev), "front")
+            fam.input_bwd(front, dacts[0], g, B, model.obs_dim)
+            grads += tuple(g.values())
+        return (None,) * 6 + grads
 
 
 class ChainDecoderFn(torch.autograd.Function):
@@ -117,29 +138,32 @@ class ChainDecoderFn(torch.autograd.Function):
         require_cuda(z, *weights)
         d, n = model.obs_dim, fam.dec_blocks
         lead = z.shape[:-1]
-        z2 = _f32c(z).reshape(-1, model.latent_dim)
+        z2 = _f32c(z)
+        if z2.dim() != 2:  # (a view per call is 1 - 2 us of host time: made only where the shape asks for one)
+            z2 = z2.reshape(-1, model.latent_dim)
         M = z2.shape[0]
         layers = model._chains()[1]
         acts = chain_buffers(layers, M, z2.device, first=z2)
         chain_fwd(layers, acts, M)
         Y = acts[-1] if fam.dec_heads is None else fam.dec_heads[0](acts[-1], M, d)
-        ctx.fam, ctx.model, ctx.lead, ctx.nw = fam, model, lead, len(weights)
+        ctx.fam, ctx.model, ctx.lead, ctx.nw, ctx.layers = fam, model, lead, len(weights), layers
         ctx.save_for_backward(*acts)
-        Y3 = Y.view(*lead, n * d)
+        Y3 = Y if len(lead) == 1 else Y.view(*lead, n * d)
         return Y3 if n == 1 else tuple(Y3[..., i * d:(i + 1) * d] for i in range(n))
 
     @staticmethod
     def backward(ctx, *grads):
-        fam, model = ctx.fam, ctx.model
+        fam, model, layers = ctx.fam, ctx.model, ctx.layers
         acts = ctx.saved_tensors
         d = model.obs_dim
         M, dev = acts[0].shape[0], acts[0].device
         # the fused losses hand back the column blocks of one [M, blocks * d] buffer: use it in place
         parts = [torch.zeros(M, d, device=dev) if t is None else t for t in grads]
-        G = _f32c(parts[0]).reshape(M, d) if len(parts) == 1 else _joined(parts, M, d)
+        G = _f32c(parts[0]) if len(parts) == 1 else _joined(parts, M, d)
+        if len(parts) == 1 and G.dim() != 2:
+            G = G.reshape(M, d)
         if G is None:
             G = torch.cat([_f32c(t).reshape(M, d) for t in parts], 1)
-        layers = model._chains()[1]
         g = model._segment_views(torch.empty(model._n_dec, device=dev), "dec")
         wkeys = wgrad_now_keys(layers, g, fam.dec_names, M)
         if fam.dec_heads is None:
@@ -149,7 +173,8 @@ class ChainDecoderFn(torch.autograd.Function):
             dacts = chain_buffers(layers, M, dev)
             fam.dec_heads[1](acts[-1], G, dacts[-1], M, d)
             chain_bwd(layers, acts, dacts, M, wgrad_now, wkeys)
-        return (None, None, dacts[0].view(*ctx.lead, model.latent_dim)) + tuple(g.values())[:ctx.nw]
+        dz = dacts[0] if len(ctx.lead) == 1 else dacts[0].view(*ctx.lead, model.latent_dim)
+        return (None, None, dz) + tuple(g.values())[:ctx.nw]
 
 
 # ------------------------------------------------------------------------------------------------ model classes

@@ -8,6 +8,9 @@ Same constructor arguments, `encoder` / `decoder` / `forward` / `loss` signature
 and loss are those of Reg_VAE / vanilla_VAE (same HIP kernels, inherited); the encoder is the point-net front-end
 (csrc/vpc_eddi.hip: folded per-feature affine + ReLU + mask-weighted sum, nothing of size B*d*(2+K) materialised)
 followed by pnp_encoder2 as three fp32 MFMA GEMMs (csrc/vpc_gemm.hip).  No CPU fallback.
+
+On the API path the encoder is chainfamily.ChainEncoderFn with the point-net Family record (the front-end is its input op).
+Shared with the image-width pair of eddi_mnist.py, and here once: front_ops, pointnet_family and _PointNet.
 """
 from __future__ import annotations
 
@@ -17,108 +20,97 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .chainfamily import nm_sample, nm_sample_bwd
+from ._lib import check, lib, ptr, stream_ptr
+from .chainfamily import ChainEncoderFn, Family, gauss_sample, gauss_sample_bwd
 from .images import PackedImage, mlp_spec
+from .linear import chain_bwd, chain_fwd
 from .models import _W6, MAX_EPOCH, Reg_VAE, vanilla_VAE
-from .linear import ACT_NONE, ACT_RELU, linear_dgrad, linear_fwd, linear_wgrad
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer, draw_counters, pad_cols
 
 H1, H2 = 100, 50  # VAE.py:694-698 hard-codes 100 / 50
 
 
-def eddi_fold(E, tb, Wp, cp, AC, d, K):
-    check(lib().vpc_eddi_fold(ptr(E), ptr(tb), ptr(Wp), ptr(cp), ptr(AC), d, K, stream_ptr()), "vpc_eddi_fold")
+# ------------------------------------------------------------------------------------------------ the point-net front-end
+def front_ops(prefix):
+    """(fold, front_fwd, front_bwd) on the kernels vpc_<prefix>_* of csrc/vpc_eddi.hip: "eddi" the narrow front-end (obs_dim <=
+    128), "eddiw" the image-width one.  front_fwd writes agg [B][K], or [2B][K] when a second mask is given: the q and p passes
+    of a step stacked."""
+    n_fold, n_fwd, n_scratch, n_bwd = (f"vpc_{prefix}_{k}" for k in ("fold", "front_fwd", "front_scratch", "front_bwd"))
+
+    def fold(E, tb, Wp, cp, AC, d, K):
+        check(getattr(lib(), n_fold)(ptr(E), ptr(tb), ptr(Wp), ptr(cp), ptr(AC), d, K, stream_ptr()), n_fold)
+
+    def front_fwd(x, mask_u8, AC, agg, B, d, K, mask2_u8=None):
+        check(getattr(lib(), n_fwd)(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(agg), B, d, K, stream_ptr()), n_fwd)
+
+    def front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K, accumulate=False, mask2_u8=None, scratch=None):
+        rows = B * (2 if mask2_u8 is not None else 1)
+        need = int(getattr(lib(), n_scratch)(rows, d, K))
+        sc = scratch if scratch is not None and scratch.numel() >= need else torch.empty(need, device=x.device)
+        check(getattr(lib(), n_bwd)(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(dagg), ptr(E), ptr(tb), ptr(Wp), ptr(sc),
+                                    sc.numel(), ptr(gE), ptr(gtb), ptr(gWp), ptr(gcp), int(accumulate), B, d, K, stream_ptr()),
+              n_bwd)
+
+    return fold, front_fwd, front_bwd
 
 
-def eddi_front_fwd(x, mask_u8, AC, agg, B, d, K, mask2_u8=None):
-    """agg [B][K] (or [2B][K] when a second mask is given: the two passes of a step stacked)."""
-    check(lib().vpc_eddi_front_fwd(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(agg), B, d, K, stream_ptr()),
-          "vpc_eddi_front_fwd")
+eddi_fold, eddi_front_fwd, eddi_front_bwd = front_ops("eddi")
 
 
-def eddi_front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K, accumulate=False, mask2_u8=None,
-                   scratch=None):
-    rows = B * (2 if mask2_u8 is not None else 1)
-    need = int(lib().vpc_eddi_front_scratch(rows, d, K))
-    sc = scratch if scratch is not None and scratch.numel() >= need else torch.empty(need, device=x.device)
-    check(lib().vpc_eddi_front_bwd(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(dagg), ptr(E), ptr(tb), ptr(Wp),
-                                   ptr(sc), sc.numel(), ptr(gE), ptr(gtb), ptr(gWp), ptr(gcp), int(accumulate), B, d, K,
-                                   stream_ptr()), "vpc_eddi_front_bwd")
+def pointnet_family(ops3, enc_names, dec_names):
+    """The Family record of a point-net family on `ops3` = front_ops(..): the input op folds the four front-end tensors (E, tb,
+    Wp, cp: the last weights of apply()) and writes the aggregate, the trunk's input; its backward takes its gradient to theirs."""
+    fold, front_fwd, front_bwd = ops3
+
+    def enc_input(x, mask_u8, agg, B, d, E, tb, Wp, cp):
+        K = E.shape[1]
+        AC = torch.empty(2, K, d, device=x.device)
+        fold(E, tb, Wp, cp, AC, d, K)
+        front_fwd(x, mask_u8, AC, agg, B, d, K)
+        return x, mask_u8, AC, E, tb, Wp
+
+    def input_bwd(saved, dagg, g, B, d):
+        x, mask_u8, AC, E, tb, Wp = saved
+        front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, g["E"], g["tb"], g["Wp"], g["cp"], B, d, E.shape[1])
+
+    return Family(enc_names, dec_names, enc_input, gauss_sample, gauss_sample_bwd, 1, input_bwd=input_bwd, n_front=4)
 
 
-class EDDIEncoderFn(torch.autograd.Function):
-    """(x, mask, eps) -> (z, mean, logvar).  Reference: VAE.py:713-741 / 897-925."""
+FAMILY = pointnet_family((eddi_fold, eddi_front_fwd, eddi_front_bwd), _W6[:6], _W6[6:])
 
-    @staticmethod
-    def forward(ctx, model, x, mask_u8, eps, W1, b1, W2, b2, W3, b3, E, tb, Wp, cp):
-        require_cuda(x, mask_u8, eps, W1, E)
-        d, Ld, K = model.obs_dim, model.latent_dim, model.emb_dim
-        B, dev = x.shape[0], x.device
-        AC = torch.empty(2, K, d, device=dev)
-        eddi_fold(E, tb, Wp, cp, AC, d, K)
-        agg = torch.empty(B, K, device=dev)
-        eddi_front_fwd(x, mask_u8, AC, agg, B, d, K)
-        h1 = torch.empty(B, H1, device=dev)
-        h2 = torch.empty(B, H2, device=dev)
-        heads = torch.empty(B, 2 * Ld, device=dev)
-        linear_fwd(agg, W1, b1, h1, B, H1, K, ACT_RELU)
-        linear_fwd(h1, W2, b2, h2, B, H2, H1, ACT_RELU)
-        linear_fwd(h2, W3, b3, heads, B, 2 * Ld, H2, ACT_NONE)
-        z = torch.empty(B, Ld, device=dev)
-        nm_sample(heads, eps, z, B, 1, Ld)
-        ctx.model = model
-        ctx.has_eps = eps is not None
-        ctx.save_for_backward(x, mask_u8, AC, agg, h1, h2, heads, eps if eps is not None else torch.empty(0, device=dev),
-                              W1, W2, W3, E, tb, Wp)
-        return z, heads[:, :Ld], heads[:, Ld:]
-
-    @staticmethod
-    def backward(ctx, dz, dmean, dlogvar):
-        model = ctx.model
-        x, mask_u8, AC, agg, h1, h2, heads, eps, W1, W2, W3, E, tb, Wp = ctx.saved_tensors
-        eps = eps if ctx.has_eps else None
-        d, Ld, K = model.obs_dim, model.latent_dim, model.emb_dim
-        B, dev = x.shape[0], x.device
-        gh = torch.cat([dmean, dlogvar], 1).float().contiguous()
-        dht = torch.empty(B, 2 * Ld, device=dev)
-        nm_sample_bwd(dz.float().contiguous(), eps, heads, gh, dht, B, 1, Ld)
-        e = lambda *s: torch.empty(*s, device=dev)
-        gW1, gb1, gW2, gb2, gW3, gb3 = e(H1, K), e(H1), e(H2, H1), e(H2), e(2 * Ld, H2), e(2 * Ld)
-        dh2, dh1, dagg = e(B, H2), e(B, H1), e(B, K)
-        linear_wgrad(dht, h2, gW3, gb3, B, 2 * Ld, H2)
-        linear_dgrad(dht, W3, dh2, B, 2 * Ld, H2, x_out=h2, act_prev=ACT_RELU)
-        linear_wgrad(dh2, h1, gW2, gb2, B, H2, H1)
-        linear_dgrad(dh2, W2, dh1, B, H2, H1, x_out=h1, act_prev=ACT_RELU)
-        linear_wgrad(dh1, agg, gW1, gb1, B, H1, K)
-        linear_dgrad(dh1, W1, dagg, B, H1, K)
-        gE, gtb, gWp, gcp = e(d, K), e(d, 1), e(K, 2 + K), e(K)
-        eddi_front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K)
-        return None, None, None, None, gW1, gb1, gW2, gb2, gW3, gb3, gE, gtb, gWp, gcp
+_FRONT_SPEC = (("E", "type_pars1", "front"), ("tb", "type_bias1", "front")) + mlp_spec(("Wp", "cp"), "pnp_encoder1", "front")
 
 
-class _EDDIBase:
-    """Shared construction / parameter plumbing; mixed in BEFORE Reg_VAE / vanilla_VAE, whose decoder(), forward()
-    and loss() (and the kernels behind them) are reused unchanged."""
+def _mlp(widths, *last):
+    """nn.Sequential of Linear layers widths[0] -> widths[1] -> .. with a ReLU between them and `last` behind."""
+    mods = [m for a, b in zip(widths, widths[1:]) for m in (nn.Linear(a, b), nn.ReLU())]
+    return nn.Sequential(*mods[:-1], *last)
+
+
+class _PointNet:
+    """What the two point-net pairs (_EDDIBase here, eddi_mnist._EDDIMnistBase) share: the constructor prologue and the
+    encoder on the chain-family frame.  A pair states `family`, `_kernels` / `_limits` (the VpcError past them) and the hidden
+    widths `_trunk_hidden` / `_dec_hidden` of pnp_encoder2 (K -> .. -> 2L) and seq_decoder (L -> .. -> d, Sigmoid)."""
 
     def _build(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples, num_estimates):
         nn.Module.__init__(self)
-        if obs_dim > 128 or latent_dim > 15 or K > 32:
-            raise L.VpcError("the gfx950 EDDI kernels support obs_dim <= 128, latent_dim <= 15 and K (emb_dim) <= 32")
-        self.obs_dim, self.hid_dim, self.emb_dim, self.latent_dim = obs_dim, hid_dim, K, latent_dim
-        self.K = K
+        max_d, max_l, max_k = self._limits
+        if obs_dim > max_d or latent_dim > max_l or K > max_k:
+            raise L.VpcError(f"the gfx950 {self._kernels} kernels support obs_dim <= {max_d}, latent_dim <= {max_l} and "
+                             f"K (emb_dim) <= {max_k}")
+        self.obs_dim, self.hid_dim, self.emb_dim, self.latent_dim, self.K = obs_dim, hid_dim, K, latent_dim, K
         self.batch_size = training_parameters["batch_size"]
-        self.training_parameters = training_parameters
-        self.experiment_type = experiment_type
+        self.training_parameters, self.experiment_type = training_parameters, experiment_type
         self.num_samples, self.num_estimates = num_samples, num_estimates
-        # containers in the reference's construction order (same seed -> same initial weights), VAE.py:687-709
+
+    def _build_modules(self):
+        # containers in the reference's construction order (same seed -> same initial weights), VAE.py:687-709 / 27-56
+        K, latent_dim, obs_dim = self.emb_dim, self.latent_dim, self.obs_dim
         self.pnp_encoder1 = nn.Sequential(nn.Linear(2 + K, K), nn.ReLU())
-        self.pnp_encoder2 = nn.Sequential(nn.Linear(K, H1), nn.ReLU(), nn.Linear(H1, H2), nn.ReLU(),
-                                          nn.Linear(H2, 2 * latent_dim))
-        self.seq_decoder = nn.Sequential(nn.Linear(latent_dim, H2), nn.ReLU(), nn.Linear(H2, H1), nn.ReLU(),
-                                         nn.Linear(H1, obs_dim), nn.Sigmoid())
-        xlv = torch.log(torch.square(torch.Tensor([0.1 * np.sqrt(2)])))
+        self.pnp_encoder2 = _mlp((K, *self._trunk_hidden, 2 * latent_dim))
+        self.seq_decoder = _mlp((latent_dim, *self._dec_hidden, obs_dim), nn.Sigmoid())
+        xlv = torch.log(torch.square(torch.Tensor([0.1 * np.sqrt(2)])))  # log 0.02, shape (1,)
         self.register_buffer("x_logvar", xlv, persistent=False)
         self._x_logvar_value = float(xlv.item())
         self.type_pars1 = nn.Parameter(torch.zeros(obs_dim, K), requires_grad=True)
@@ -128,14 +120,38 @@ class _EDDIBase:
         self.prior_mean = nn.Parameter(torch.zeros(latent_dim), requires_grad=False)
         self.prior_std = nn.Parameter(torch.ones(latent_dim), requires_grad=False)
         self.max_epoch = MAX_EPOCH
-        self._layout = None
-        self._img = None
+        self._layout = self._img = None
         self._part = {}
+
+    def encoder(self, x, mask, sample=True):
+        """VAE.py:713-741 / 897-925 / 62-84 / 255-277: returns (z, mean, logvar)."""
+        return self._encode(x, mask, sample)
+
+    def _encode(self, x, mask, sample=True, eps=None):
+        """encoder() with an injectable eps [B, L] (sample and no eps: drawn on the device)."""
+        L.require_cuda(x)
+        if mask.shape[0] == 0:  # VAE.py:717-718 / 66-67: ten columns whatever latent_dim is
+            return torch.empty(0, 10), torch.empty(0, 10), torch.empty(0, 10)
+        self._images()
+        xf = ops._f32c(x.reshape(-1, self.obs_dim))
+        m = as_mask_u8(mask.reshape(-1, self.obs_dim).to(x.device))
+        if sample and eps is None:
+            eps = torch.randn(xf.shape[0], self.latent_dim, device=xf.device)
+        z, heads = ChainEncoderFn.apply(self.family, self, xf, m, ops._f32c(eps) if sample else None, 1, *self._enc_weights(),
+                                        *self._segment_params("front"))
+        return (z, *heads.chunk(2, dim=1))  # mean first; one split node, whose backward is one cat
+
+
+class _EDDIBase(_PointNet):
+    """Shared construction / parameter plumbing; mixed in BEFORE Reg_VAE / vanilla_VAE, whose decoder(), forward()
+    and loss() (and the kernels behind them) are reused unchanged."""
+    family = FAMILY
+    _kernels, _limits = "EDDI", (128, 15, 32)
+    _trunk_hidden, _dec_hidden = (H1, H2), (H2, H1)
 
     # flat order: [pnp_encoder2 (6) | seq_decoder (6) | type_pars1, type_bias1, pnp_encoder1 (2)] - the decoder sits at
     # indices 6..11 as in the VAE classes, which is what DecoderFn's gradient split assumes
-    _flat_spec = mlp_spec(_W6[:6], "pnp_encoder2", "enc") + mlp_spec(_W6[6:], "seq_decoder", "dec") + \
-        (("E", "type_pars1", "front"), ("tb", "type_bias1", "front")) + mlp_spec(("Wp", "cp"), "pnp_encoder1", "front")
+    _flat_spec = mlp_spec(_W6[:6], "pnp_encoder2", "enc") + mlp_spec(_W6[6:], "seq_decoder", "dec") + _FRONT_SPEC
 
     def _new_image(self, device):
         """Only the DECODER half of the packed image is used (the encoder is the front-end + GEMM trunk)."""
@@ -153,18 +169,6 @@ class _EDDIBase:
         self._images()
         return ops.DecoderFn.apply(self, z_int, *self.trainable()[6:12]), self.x_logvar
 
-    def encoder(self, x, mask, sample=True):
-        """VAE.py:713-741 / 897-925: returns (z, mean, logvar)."""
-        L.require_cuda(x)
-        if mask.shape[0] == 0:  # VAE.py:717-718
-            return torch.empty(0, 10), torch.empty(0, 10), torch.empty(0, 10)
-        self._images()
-        xf = ops._f32c(x.reshape(-1, self.obs_dim))
-        m = as_mask_u8(mask.reshape(-1, self.obs_dim).to(x.device))
-        eps = torch.randn(xf.shape[0], self.latent_dim, device=xf.device) if sample else None
-        t = self.trainable()
-        return EDDIEncoderFn.apply(self, xf, m, eps, *t[:6], *t[12:])
-
 
 class Reg_EDDI(_EDDIBase, Reg_VAE):
     """Reference: src/models/VAE.py:670-853."""
@@ -172,6 +176,7 @@ class Reg_EDDI(_EDDIBase, Reg_VAE):
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, reg_type, num_samples=1,
                  num_estimates=1):
         self._build(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples, num_estimates)
+        self._build_modules()
         self.reg_type = reg_type
 
     def forward(self, data, mask, mask_p, stage="train"):
@@ -192,6 +197,7 @@ class vanilla_EDDI(_EDDIBase, vanilla_VAE):
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples=1,
                  num_estimates=1):
         self._build(obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples, num_estimates)
+        self._build_modules()
 
     def loss(self, x, x_recon_q, x_logvar_q, mean_q, logvar_q, epoch, mask, vae_elbo=False, llh_eval=False, MI=False,
              beta_annealing=False, beta=1.0, alpha=0.5, stage="train"):
@@ -234,6 +240,15 @@ class _SmallStep:
         self.B = None
 
 
+_TRUNK_WKEYS = ((None, 2), (None, 1), (None, 0))  # (no timer, workspace index) of the trunk's layers 0, 1, 2
+
+
+def param_chains(model):
+    """(trunk, decoder) chains of a point-net model for its step trainer: the class's _build_chains on the Parameters
+    themselves, which follow every re-assignment of p.data (the API path's model._chains() holds views of one flat buffer)."""
+    return model._build_chains(dict(zip(*model._flat_table()[:2])))
+
+
 class EDDITrainer(_FlatAdamTrainer):
     """The EDDI training step (train.py:28-117 for 'reg_EDDI*' / 'vanilla_EDDI*') as a fixed launch sequence without
     host synchronisation: [decoder image re-pack] -> mask_p + eps draws -> fold -> front-end (both passes) ->
@@ -271,6 +286,39 @@ class EDDITrainer(_FlatAdamTrainer):
         self._small_shape = world_size == 1 and ops.small_eddi_tiles(model.obs_dim, model.emb_dim) is not None
         self.last_path = None
 
+    def _draws(self, mask, mask_p, eps_in, co, keep_prob, B, Bg, row_lo, in_kernel_ok=False):
+        """THE inject-or-draw rule of the step, for both paths, on self.eps_buf [3][B][LP] and self.mask_p_buf.  eps_in =
+        (eps_q, eps_p, eps_ml); the planes the step consumes are q, then p (regularised), then ml_reg's third.  eps is drawn
+        together with mask_p whenever mask_p is absent (injected planes are copied over it), else unless eps_q is injected.
+        in_kernel_ok (the small path at obs_dim % 4 == 0) and every draw made on the device: no launch here, the step's kernel
+        makes them.  Returns (mask_p as uint8 or None, whether the third plane is read, the in-kernel arguments or None)."""
+        d, Ld = self.model.obs_dim, self.model.latent_dim
+        two = not self.vanilla
+        need_ml = two and co.ml_on
+        planes = 3 if need_ml else 2 if two else 1
+        eps_view, eps_in = self.eps_buf[:planes], eps_in[:planes]
+        draw_mask = two and mask_p is None
+        draw_eps = draw_mask or eps_in[0] is None
+        dr = draw_counters(self.rng_offset, draw_mask, planes if draw_eps else 0, B, Bg, row_lo, LP, d)  # GLOBAL row (SURVEY 8e)
+        self.rng_offset = dr.next_offset
+        in_kernel = None
+        if in_kernel_ok and draw_mask == two and all(e is None for e in eps_in):
+            in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
+                         dr.eps_shard)
+        elif draw_mask:
+            ops.draw_step(mask, self.mask_p_buf, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
+                          dr.eps_shard)
+        elif draw_eps:
+            ops.fill_normal(eps_view, self.seed, dr.offset_eps, None, dr.eps_shard)
+        if draw_mask:
+            mask_p = self.mask_p_buf
+        elif two:
+            mask_p = as_mask_u8(mask_p.reshape(-1, d))
+        for plane, e in enumerate(eps_in):
+            if e is not None:
+                self.eps_buf[plane, :, :Ld].copy_(e)
+        return mask_p, need_ml, in_kernel
+
     def _ws(self, B):
         if self._B == B:
             return
@@ -279,21 +327,23 @@ class EDDITrainer(_FlatAdamTrainer):
         P = 1 if self.vanilla else 2
         e = lambda *s: torch.empty(*s, device=dev)
         self.AC = e(2, K, d)
-        self.agg, self.h1, self.h2, self.heads = e(P * B, K), e(P * B, H1), e(P * B, H2), e(P * B, 2 * Ld)
+        self.trunk = param_chains(m)[0]
+        self.enc = [e(P * B, K), e(P * B, H1), e(P * B, H2), e(P * B, 2 * Ld)]    # agg, h1, h2, heads
+        self.denc = [e(P * B, K), e(P * B, H1), e(P * B, H2), e(P * B, 2 * Ld)]   # dagg, dh1, dh2, dheads
         self.lat = torch.zeros(P, 2, B, LP, device=dev)    # [pass][mean | logvar][B][16]
         self.dlat = torch.zeros(P, 2, B, LP, device=dev)
-        self.dheads, self.dh2, self.dh1, self.dagg = e(P * B, 2 * Ld), e(P * B, H2), e(P * B, H1), e(P * B, K)
         self.eps_buf = e(3, B, LP)
         self.mask_p_buf = torch.empty(B, d, dtype=torch.uint8, device=dev)
         self.front_scratch = e(int(lib().vpc_eddi_front_scratch(P * B, d, K)))
-        # per-layer partial buffers of the trunk's three weight gradients: summed by ONE launch (vpc_linear_wgrad_reduce)
+        # per-layer partial buffers of the trunk's three weight gradients, last layer first (_TRUNK_WKEYS): summed by ONE launch
+        # (vpc_linear_wgrad_reduce)
         R, g = P * B, self.g
         self._wgrad_workspace([(R, 2 * Ld, H2), (R, H2, H1), (R, H1, K)], [(g[4], g[5]), (g[2], g[3]), (g[0], g[1])])
         # the slices the step passes to its launches, made once per batch size (1-3 us of host time each; the step is host-paced)
         self._sl = dict(mean=[self.lat[p_, 0] for p_ in range(P)], logvar=[self.lat[p_, 1] for p_ in range(P)],
                         dmean=[self.dlat[p_, 0] for p_ in range(P)], dlogvar=[self.dlat[p_, 1] for p_ in range(P)],
                         eps=[self.eps_buf[p_] for p_ in range(3)], lat_dst=self.lat[..., :Ld],
-                        heads_src=self.heads.view(P, B, 2, Ld).permute(0, 2, 1, 3), dheads_dst=self.dheads.view(P, B, 2, Ld),
+                        heads_src=self.enc[3].view(P, B, 2, Ld).permute(0, 2, 1, 3), dheads_dst=self.denc[3].view(P, B, 2, Ld),
                         dlat_src=self.dlat[..., :Ld].permute(0, 2, 1, 3),
                         gdec=self.grad[self.n_trunk:self.n_trunk + self.n_dec], gidx_dec=self.gidx[self.lay.n_enc:])
         self._B = B
@@ -318,40 +368,15 @@ class EDDITrainer(_FlatAdamTrainer):
         two = not self.vanilla
         P = 2 if two else 1
         t = self._plist
-        W1, b1, W2, b2, W3, b3 = t[:6]
         E, tb, Wp, cp = t[12:]
         dec_img = m._images(m._param_key(t))[lay.enc_img:]  # re-packed after the previous step's Adam
-        # ---- draws
-        need_ml = two and co.ml_on
-        eps_view = self.eps_buf[: (3 if need_ml else 2 if two else 1)]
-        # eps is drawn together with mask_p whenever mask_p is absent (injected planes are copied over it), else unless injected
-        draw_mask = two and mask_p is None
-        dr = draw_counters(self.rng_offset, draw_mask, eps_view.shape[0] if (draw_mask or eps_q is None) else 0, B, Bg,
-                           row_lo, LP, d)
-        self.rng_offset = dr.next_offset
-        if draw_mask:
-            ops.draw_step(mask, self.mask_p_buf, 1.0 - p_missingness / 100.0, eps_view, self.seed, dr.offset_mask,
-                          dr.offset_eps, None, dr.elem_lo, dr.eps_shard)
-            mask_p = self.mask_p_buf
-        else:
-            if two:
-                mask_p = as_mask_u8(mask_p.reshape(-1, d))
-            if eps_q is None:
-                ops.fill_normal(eps_view, self.seed, dr.offset_eps, None, dr.eps_shard)
-        if eps_q is not None:
-            self.eps_buf[0, :, :Ld].copy_(eps_q)
-        if two and eps_p is not None:
-            self.eps_buf[1, :, :Ld].copy_(eps_p)
-        if need_ml and eps_ml is not None:
-            self.eps_buf[2, :, :Ld].copy_(eps_ml)
+        mask_p, need_ml, _ = self._draws(mask, mask_p, (eps_q, eps_p, eps_ml), co, 1.0 - p_missingness / 100.0, B, Bg, row_lo)
         masks = [mask, mask_p] if two else [mask]
         # ---- encoder: front-end per pass, trunk on the stacked passes
         eddi_fold(E, tb, Wp, cp, self.AC, d, K)
-        eddi_front_fwd(x, masks[0], self.AC, self.agg, B, d, K, masks[1] if two else None)  # both passes, one launch
+        eddi_front_fwd(x, masks[0], self.AC, self.enc[0], B, d, K, masks[1] if two else None)  # both passes, one launch
         R = P * B
-        linear_fwd(self.agg, W1, b1, self.h1, R, H1, K, ACT_RELU)
-        linear_fwd(self.h1, W2, b2, self.h2, R, H2, H1, ACT_RELU)
-        linear_fwd(self.h2, W3, b3, self.heads, R, 2 * Ld, H2, ACT_NONE)
+        chain_fwd(self.trunk, self.enc, R)
         sl = self._sl
         sl["lat_dst"].copy_(sl["heads_src"])
         mean, logvar, dmean, dlogvar = sl["mean"], sl["logvar"], sl["dmean"], sl["dlogvar"]
@@ -366,15 +391,11 @@ class EDDITrainer(_FlatAdamTrainer):
         # ---- encoder backward
         sl["dheads_dst"].copy_(sl["dlat_src"])
         g = self.g
-        # (the three weight gradients leave their GEMMs as partials and are summed by ONE launch: two launches less per step)
-        self._wgrad((None, 0), self.dheads, self.h2)
-        linear_dgrad(self.dheads, W3, self.dh2, R, 2 * Ld, H2, x_out=self.h2, act_prev=ACT_RELU)
-        self._wgrad((None, 1), self.dh2, self.h1)
-        linear_dgrad(self.dh2, W2, self.dh1, R, H2, H1, x_out=self.h1, act_prev=ACT_RELU)
-        self._wgrad((None, 2), self.dh1, self.agg)
-        linear_dgrad(self.dh1, W1, self.dagg, R, H1, K)
+        # (the three weight gradients leave their GEMMs as partials and are summed by ONE launch: two launches less per step;
+        # the aggregate is a sum of ReLUs, not a ReLU output: its dgrad has no gate)
+        chain_bwd(self.trunk, self.enc, self.denc, R, self._wgrad, _TRUNK_WKEYS)
         self._wgrad_reduce()
-        eddi_front_bwd(x, masks[0], self.AC, self.dagg, E, tb, Wp, g[12], g[13], g[14], g[15], B, d, K,
+        eddi_front_bwd(x, masks[0], self.AC, self.denc[0], E, tb, Wp, g[12], g[13], g[14], g[15], B, d, K,
                        mask2_u8=masks[1] if two else None, scratch=self.front_scratch)
         if self.world_size > 1:
             self._allreduce()
@@ -398,31 +419,9 @@ class EDDITrainer(_FlatAdamTrainer):
         Bg, row_lo = self._batch_rows(B, global_batch, row_lo)
         key = m._param_key(self._plist)
         img = s.img.get(key, m._flat)
-        # ---- draws: the chain's counters and its rule for which planes are drawn (step), at the chain's pitch d.  obs_dim % 4 == 0
-        # and every draw made on the device: the kernel makes them; else the chain's launches, on the unpadded rows
-        need_ml = two and co.ml_on
-        planes = 3 if need_ml else 2 if two else 1
-        eps_view, eps_in = self.eps_buf[:planes], eps_in[:planes]
-        draw_mask = two and mask_p is None
-        draw_eps = draw_mask or eps_in[0] is None
-        dr = draw_counters(self.rng_offset, draw_mask, planes if draw_eps else 0, B, Bg, row_lo, LP, d)
-        self.rng_offset = dr.next_offset
-        in_kernel = None
-        if dk == d and draw_mask == two and all(e is None for e in eps_in):
-            in_kernel = (mask if two else None, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
-                         dr.eps_shard)
-        elif draw_mask:
-            ops.draw_step(mask, self.mask_p_buf, keep_prob, eps_view, self.seed, dr.offset_mask, dr.offset_eps, None, dr.elem_lo,
-                          dr.eps_shard)
-        elif draw_eps:
-            ops.fill_normal(eps_view, self.seed, dr.offset_eps, None, dr.eps_shard)
-        if draw_mask:
-            mask_p = self.mask_p_buf
-        elif two:
-            mask_p = as_mask_u8(mask_p.reshape(-1, d))
-        for plane, e in enumerate(eps_in):
-            if e is not None:
-                self.eps_buf[plane, :, :Ld].copy_(e)
+        # ---- draws (_draws).  obs_dim % 4 == 0 and every draw made on the device: the kernel makes them; else the chain's
+        # launches, on the unpadded rows
+        mask_p, need_ml, in_kernel = self._draws(mask, mask_p, eps_in, co, keep_prob, B, Bg, row_lo, in_kernel_ok=dk == d)
         if dk != d:  # the kernel's rows: 4 * ceil(d / 4) columns, mask 0 in the padding
             x, mask = pad_cols(s.pads, x, dk, 0, dev), pad_cols(s.pads, mask, dk, 1, dev)
             if two:

@@ -30,21 +30,22 @@ Reference behaviour that is reproduced, not fixed:
     Reg_EDDI_mnist minus the p pass;
   * vanilla_EDDI_mnist.forward takes no `stage` (VAE.py:342); vanilla_EDDI_mnist.loss has no `alpha_annealing`;
   * an unknown reg_type prints 'Not implemented!' (VAE.py:145-147); here it then raises instead of failing in backward.
-`EDDIMnistTrainer` is the training step (train.py:28-117 with data_type == 'mnist') as one fixed launch sequence.
+`EDDIMnistTrainer` is the training step (train.py:28-117 with data_type == 'mnist') as one fixed launch sequence.  Front-end
+wrappers, the Family record of the API path and the constructor prologue are eddi.py's (front_ops("eddiw"), pointnet_family,
+_PointNet); this module states the widths, the chains, the limits and the step.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
-from .chainfamily import nm_sample, nm_sample_bwd
+from ._lib import lib
+from .chainfamily import ChainDecoderFn, nm_sample, nm_sample_bwd
+from .eddi import _FRONT_SPEC, _PointNet, front_ops, param_chains, pointnet_family
 from .images import mlp_spec
-from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain, chain_buffers, chain_bwd, chain_fwd, wgrad_now
-from .models import MAX_EPOCH, Reg_VAE, vanilla_VAE
+from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain, chain_bwd, chain_fwd
+from .models import Reg_VAE, vanilla_VAE
 from .ops import as_mask_u8
 from .trainer import _FlatAdamTrainer, draw_counters
 
@@ -54,160 +55,28 @@ MAX_D, MAX_K, MAX_L = 1024, 32, 15
 _TRUNK_NAMES = ("We1", "be1", "We2", "be2", "We3", "be3", "We4", "be4")
 _DEC_NAMES = ("Wd1", "bd1", "Wd2", "bd2", "Wd3", "bd3", "Wd4", "bd4")
 
-
-def eddiw_fold(E, tb, Wp, cp, AC, d, K):
-    check(lib().vpc_eddiw_fold(ptr(E), ptr(tb), ptr(Wp), ptr(cp), ptr(AC), d, K, stream_ptr()), "vpc_eddiw_fold")
-
-
-def eddiw_front_fwd(x, mask_u8, AC, agg, B, d, K, mask2_u8=None):
-    """agg [B][K] (or [2B][K] when a second mask is given: the q and p passes of a step stacked)."""
-    check(lib().vpc_eddiw_front_fwd(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(agg), B, d, K, stream_ptr()),
-          "vpc_eddiw_front_fwd")
+eddiw_fold, eddiw_front_fwd, eddiw_front_bwd = front_ops("eddiw")
+# the decoder returns xhat, one [M, d] buffer behind the chain's Sigmoid gate (VAE.py:86-90)
+FAMILY = pointnet_family((eddiw_fold, eddiw_front_fwd, eddiw_front_bwd), _TRUNK_NAMES, _DEC_NAMES)
 
 
-def eddiw_front_bwd(x, mask_u8, AC, dagg, E, tb, Wp, gE, gtb, gWp, gcp, B, d, K, accumulate=False, mask2_u8=None,
-                    scratch=None):
-    rows = B * (2 if mask2_u8 is not None else 1)
-    need = int(lib().vpc_eddiw_front_scratch(rows, d, K))
-    sc = scratch if scratch is not None and scratch.numel() >= need else torch.empty(need, device=x.device)
-    check(lib().vpc_eddiw_front_bwd(ptr(x), ptr(mask_u8), ptr(mask2_u8), ptr(AC), ptr(dagg), ptr(E), ptr(tb), ptr(Wp),
-                                    ptr(sc), sc.numel(), ptr(gE), ptr(gtb), ptr(gWp), ptr(gcp), int(accumulate), B, d, K,
-                                    stream_ptr()), "vpc_eddiw_front_bwd")
-
-
-def _chains(trunk, dec):
-    """(trunk, decoder) chains on [W1, b1, ..]: pnp_encoder2.{0,2,4,6} = K-500-500-200-2L with ReLU between layers, seq_decoder
-    L-200-500-500-d with a Sigmoid on every output (split = d)."""
-    return (chain(trunk, (ACT_RELU, ACT_RELU, ACT_RELU, ACT_NONE)),
-            chain(dec, (ACT_RELU, ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), dec[6].shape[0]))
-
-
-def _fresh_grads(layers, M, device):
-    """New (dw, db) per layer as wgrad_now keys, and the flat list [dw1, db1, dw2, ..] an autograd backward returns."""
-    keys = [(torch.empty(l[3], l[2], device=device), torch.empty(l[3], device=device), M, l[3], l[2]) for l in layers]
-    return keys, [t for k in keys for t in k[:2]]
-
-
-class EDDIMnistEncoderFn(torch.autograd.Function):
-    """(x, mask, eps) -> (z, mean, logvar).  Reference: VAE.py:62-84 / 255-277."""
-
-    @staticmethod
-    def forward(ctx, model, x, mask_u8, eps, E, tb, Wp, cp, *trunk):
-        require_cuda(x, mask_u8, eps, E, trunk[0])
-        d, Ld, K = model.obs_dim, model.latent_dim, model.emb_dim
-        B, dev = x.shape[0], x.device
-        AC = torch.empty(2, K, d, device=dev)
-        eddiw_fold(E, tb, Wp, cp, AC, d, K)
-        layers = model._chains()[0]
-        acts = chain_buffers(layers, B, dev)
-        eddiw_front_fwd(x, mask_u8, AC, acts[0], B, d, K)
-        chain_fwd(layers, acts, B)
-        heads = acts[-1]
-        z = torch.empty(B, Ld, device=dev)
-        nm_sample(heads, eps, z, B, 1, Ld)  # z = mean + eps * exp(logvar / 2); eps None -> z = mean
-        ctx.model = model
-        ctx.has_eps = eps is not None
-        ctx.save_for_backward(x, mask_u8, AC, *acts, eps if eps is not None else torch.empty(0, device=dev), E, tb, Wp)
-        return z, heads[:, :Ld], heads[:, Ld:]
-
-    @staticmethod
-    def backward(ctx, dz, dmean, dlogvar):
-        model = ctx.model
-        x, mask_u8, AC, agg, h1, h2, h3, heads, eps, E, tb, Wp = ctx.saved_tensors
-        eps = eps if ctx.has_eps else None
-        d, Ld, K = model.obs_dim, model.latent_dim, model.emb_dim
-        B, dev = x.shape[0], x.device
-        e = lambda *s: torch.empty(*s, device=dev)
-        gh = torch.zeros(B, 2 * Ld, device=dev)
-        if dmean is not None:
-            gh[:, :Ld] += dmean
-        if dlogvar is not None:
-            gh[:, Ld:] += dlogvar
-        layers = model._chains()[0]
-        dacts = chain_buffers(layers, B, dev)
-        dzc = ops._f32c(dz) if dz is not None else torch.zeros(B, Ld, device=dev)
-        nm_sample_bwd(dzc, eps, heads, gh, dacts[-1], B, 1, Ld)
-        keys, grads = _fresh_grads(layers, B, dev)
-        chain_bwd(layers, [agg, h1, h2, h3], dacts, B, wgrad_now, keys)  # (agg is a sum of ReLUs, not a ReLU output: no gate)
-        gE, gtb, gWp, gcp = e(d, K), e(d, 1), e(K, 2 + K), e(K)
-        eddiw_front_bwd(x, mask_u8, AC, dacts[0], E, tb, Wp, gE, gtb, gWp, gcp, B, d, K)
-        return (None, None, None, None, gE, gtb, gWp, gcp, *grads)
-
-
-class EDDIMnistDecoderFn(torch.autograd.Function):
-    """(z, 8 decoder tensors) -> xhat = sigmoid(MLP(z)).  VAE.py:86-90."""
-
-    @staticmethod
-    def forward(ctx, model, z, *w):
-        require_cuda(z, w[0])
-        z = ops._f32c(z)
-        B = z.shape[0]
-        layers = model._chains()[1]
-        acts = chain_buffers(layers, B, z.device, first=z)
-        chain_fwd(layers, acts, B)
-        ctx.model = model
-        ctx.save_for_backward(*acts)
-        return acts[-1]
-
-    @staticmethod
-    def backward(ctx, dxhat):
-        z, g1, g2, g3, xhat = ctx.saved_tensors
-        B, dev, d = z.shape[0], z.device, xhat.shape[1]
-        layers = ctx.model._chains()[1]
-        dacts = chain_buffers(layers, B, dev, last=ops._f32c(dxhat))
-        keys, grads = _fresh_grads(layers, B, dev)
-        chain_bwd(layers, [z, g1, g2, g3], dacts, B, wgrad_now, keys, y_gate=xhat, gate=ACT_SIGMOID_HARDTANH,
-                  gate_split=d)  # dpre = dxhat xhat (1 - xhat)
-        return (None, dacts[0], *grads)
-
-
-class _EDDIMnistBase:
+class _EDDIMnistBase(_PointNet):
     """Shared construction / parameter plumbing; mixed in BEFORE Reg_VAE / vanilla_VAE, whose loss() (the K4 kernel behind
     it) and flat-parameter plumbing are reused unchanged."""
     _wide = False
     _eddi_mnist = True  # active.reward_matrix refuses these classes (d = 784 active learning is not a reference configuration)
+    family = FAMILY
+    _kernels, _limits = "image-width EDDI", (MAX_D, MAX_L, MAX_K)
+    _trunk_hidden, _dec_hidden = (H1, H2, H3), (H3, H2, H1)
     # the 20 trainable tensors in state_dict (= flat) order: front-end (4) | trunk (8) | decoder (8)
-    _flat_spec = (("E", "type_pars1", "front"), ("tb", "type_bias1", "front")) + \
-        mlp_spec(("Wp", "cp"), "pnp_encoder1", "front") + \
-        mlp_spec(_TRUNK_NAMES, "pnp_encoder2", "enc") + mlp_spec(_DEC_NAMES, "seq_decoder", "dec")
+    _flat_spec = _FRONT_SPEC + mlp_spec(_TRUNK_NAMES, "pnp_encoder2", "enc") + mlp_spec(_DEC_NAMES, "seq_decoder", "dec")
 
     @staticmethod
     def _build_chains(v):
-        return _chains([v[k] for k in _TRUNK_NAMES], [v[k] for k in _DEC_NAMES])
-
-    def _build(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples, num_estimates):
-        nn.Module.__init__(self)
-        if obs_dim > MAX_D or latent_dim > MAX_L or K > MAX_K:
-            raise L.VpcError(f"the gfx950 image-width EDDI kernels support obs_dim <= {MAX_D}, K (emb_dim) <= {MAX_K} and "
-                             f"latent_dim <= {MAX_L}")
-        self.obs_dim, self.hid_dim, self.emb_dim, self.latent_dim = obs_dim, hid_dim, K, latent_dim
-        self.K = K
-        self.batch_size = training_parameters["batch_size"]
-        self.training_parameters = training_parameters
-        self.experiment_type = experiment_type
-        self.num_samples, self.num_estimates = num_samples, num_estimates
-
-    def _build_modules(self):
-        # containers in the reference's construction order (same seed -> same initial weights), VAE.py:27-56
-        K, latent_dim, obs_dim = self.emb_dim, self.latent_dim, self.obs_dim
-        self.pnp_encoder1 = nn.Sequential(nn.Linear(2 + K, K), nn.ReLU())
-        self.pnp_encoder2 = nn.Sequential(nn.Linear(K, H1), nn.ReLU(), nn.Linear(H1, H2), nn.ReLU(), nn.Linear(H2, H3),
-                                          nn.ReLU(), nn.Linear(H3, 2 * latent_dim))
-        self.seq_decoder = nn.Sequential(nn.Linear(latent_dim, H3), nn.ReLU(), nn.Linear(H3, H2), nn.ReLU(),
-                                         nn.Linear(H2, H1), nn.ReLU(), nn.Linear(H1, obs_dim), nn.Sigmoid())
-        xlv = torch.log(torch.square(torch.Tensor([0.1 * np.sqrt(2)])))  # log 0.02, shape (1,)
-        self.register_buffer("x_logvar", xlv, persistent=False)
-        self._x_logvar_value = float(xlv.item())
-        self.type_pars1 = nn.Parameter(torch.zeros(obs_dim, K), requires_grad=True)
-        nn.init.xavier_uniform_(self.type_pars1)
-        self.type_bias1 = nn.Parameter(torch.zeros(obs_dim, 1), requires_grad=True)
-        nn.init.xavier_uniform_(self.type_bias1)
-        self.prior_mean = nn.Parameter(torch.zeros(latent_dim), requires_grad=False)
-        self.prior_std = nn.Parameter(torch.ones(latent_dim), requires_grad=False)
-        self.max_epoch = MAX_EPOCH
-        self._layout = None
-        self._img = None
-        self._part = {}
+        """(trunk, decoder) chains on the named views v: pnp_encoder2.{0,2,4,6} = K-500-500-200-2L with ReLU between layers,
+        seq_decoder L-200-500-500-d with a Sigmoid on every output (split = d)."""
+        return (chain([v[k] for k in _TRUNK_NAMES], (ACT_RELU, ACT_RELU, ACT_RELU, ACT_NONE)),
+                chain([v[k] for k in _DEC_NAMES], (ACT_RELU, ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), v["Wd4"].shape[0]))
 
     def _images(self, key=None):  # no packed weight images: every layer reads the flat parameters
         return None
@@ -215,19 +84,7 @@ class _EDDIMnistBase:
     def decoder(self, z_int):
         """VAE.py:86-90: returns (x_mean, x_logvar) with x_logvar the shape-(1,) constant log 0.02."""
         L.require_cuda(z_int)
-        self.flatten_parameters()
-        return EDDIMnistDecoderFn.apply(self, z_int, *self.trainable()[12:]), self.x_logvar
-
-    def encoder(self, x, mask, sample=True):
-        """VAE.py:62-84 / 255-277: returns (z, mean, logvar)."""
-        L.require_cuda(x)
-        if mask.shape[0] == 0:  # VAE.py:66-67
-            return torch.empty(0, 10), torch.empty(0, 10), torch.empty(0, 10)
-        self.flatten_parameters()
-        xf = ops._f32c(x.reshape(-1, self.obs_dim))
-        m = as_mask_u8(mask.reshape(-1, self.obs_dim).to(x.device))
-        eps = torch.randn(xf.shape[0], self.latent_dim, device=xf.device) if sample else None
-        return EDDIMnistEncoderFn.apply(self, xf, m, eps, *self.trainable()[:12])
+        return ChainDecoderFn.apply(FAMILY, self, z_int, *self._dec_weights()), self.x_logvar
 
 
 class Reg_EDDI_mnist(_EDDIMnistBase, Reg_VAE):
@@ -331,8 +188,8 @@ class EDDIMnistTrainer(_FlatAdamTrainer):
         self.mask_p_buf = torch.empty(B, d, dtype=torch.uint8, device=dev)
         self.front_scratch = e(int(lib().vpc_eddiw_front_scratch(R, d, K)))
         # the two GEMM chains, and the per-layer partial buffers of their eight weight gradients: summed by ONE launch
-        t, g = self._plist, self.g
-        self.trunk, self.dec_layers = _chains(t[4:12], t[12:20])
+        g = self.g
+        self.trunk, self.dec_layers = param_chains(m)
         self._wgrad_workspace([(R, l[3], l[2]) for l in self.trunk + self.dec_layers],
                               [(g[4 + 2 * i], g[5 + 2 * i]) for i in range(8)])
         self._sl = dict(mean=[self.lat[p_, 0] for p_ in range(P)], logvar=[self.lat[p_, 1] for p_ in range(P)],

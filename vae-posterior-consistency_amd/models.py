@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .images import FlatParams, PackedImage, mlp_spec
+from .linear import ACT_NONE, ACT_RELU, ACT_SIGMOID_HARDTANH, chain
 from .ops import DecoderFn, EncoderFn, LossFn, as_mask_u8
 
 MAX_EPOCH = 2800  # VAE.py:384
@@ -58,6 +59,13 @@ class _VAEBase(FlatParams, nn.Module):
     mask_augm = False  # True: encoder input is [x*mask | mask] (the reference's *_mask classes)
     # the 12 trainable tensors in state_dict (= flat) order
     _flat_spec = mlp_spec(_W6[:6], "seq_encoder", "enc") + mlp_spec(_W6[6:], "seq_decoder", "dec")
+
+    @staticmethod
+    def _build_chains(v):
+        """(encoder, decoder) chains of linear.py on the named views v: * -> 100 -> 50 -> 2L with ReLU between layers, L -> 50 ->
+        100 -> d with a Sigmoid on every output (split = d).  Reg_EDDI / vanilla_EDDI use the same six names for their trunk."""
+        return (chain([v[k] for k in _W6[:6]], (ACT_RELU, ACT_RELU, ACT_NONE)),
+                chain([v[k] for k in _W6[6:]], (ACT_RELU, ACT_RELU, ACT_SIGMOID_HARDTANH), v["W6"].shape[0]))
 
     def __init__(self, obs_dim, hid_dim, K, latent_dim, training_parameters, experiment_type, num_samples=1,
                  num_estimates=1):
@@ -136,15 +144,21 @@ class _VAEBase(FlatParams, nn.Module):
     # ------------------------------------------------------------------ reference API
     def encoder(self, x, mask, sample=True):
         """VAE.py:387-395: returns (z, mean, logvar); eps ~ N(0,1) drawn on the device when sample=True."""
+        return self._encode(x, mask, sample)
+
+    def _encode(self, x, mask, sample=True, eps=None):
+        """encoder() with an injectable eps [B, L] (sample and no eps: drawn on the device)."""
         L.require_cuda(x)
         x = x.reshape(-1, self.obs_dim)
         xf = x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
         m = as_mask_u8(mask.reshape(-1, self.obs_dim).to(x.device))
-        eps = torch.randn(xf.shape[0], self.latent_dim, device=xf.device) if sample else None
+        if not sample:
+            eps = None
+        elif eps is None:
+            eps = torch.randn(xf.shape[0], self.latent_dim, device=xf.device)
         if self._wide:
-            from .wide import WideEncoderFn
-            self.flatten_parameters()
-            return WideEncoderFn.apply(self, xf, m, eps, *self.trainable()[:6])
+            from .wide import encode
+            return encode(self, xf, m, eps)
         self._lay()
         self._images()
         return EncoderFn.apply(self, xf, m, eps, *self.trainable()[:6])
@@ -153,9 +167,8 @@ class _VAEBase(FlatParams, nn.Module):
         """VAE.py:397-401: returns (x_mean, x_logvar) with x_logvar the shape-(1,) constant."""
         L.require_cuda(z_int)
         if self._wide:
-            from .wide import WideDecoderFn
-            self.flatten_parameters()
-            return WideDecoderFn.apply(self, z_int, *self.trainable()[6:]), self.x_logvar
+            from .wide import decode
+            return decode(self, z_int), self.x_logvar
         self._lay()
         self._images()
         return DecoderFn.apply(self, z_int, *self.trainable()[6:]), self.x_logvar
