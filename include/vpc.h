@@ -352,6 +352,30 @@ int vpc_linear_wgrad(const float* dy, long lddy, const float* y_gate, long ldyg,
 int vpc_linear_wgrad_reduce(int n_layers, const float* const* scratch, const long* M, const int* N, const int* K,
                             float* const* dw, float* const* db, const int* accumulate, void* stream);
 
+/* ---- the same layer for FEW rows (csrc/vpc_rows.hip): M <= vpc_rows_max_rows() = 128 rows, 1 <= N, K <= 1024, fp32 only.
+ * The split is over output features, the contraction of the weight gradient (at most 128 rows) stays inside one wave, and
+ * nothing is summed by a second launch: there is neither `precision` nor `scratch`.  Activation codes, the gate, the row
+ * pitches and the 16-byte / scalar access rule are those of vpc_linear_*.  M < 1, N < 1, K < 1, a pitch below its width or
+ * a NULL mandatory pointer: bad argument; M > 128, N > 1024 or K > 1024: unsupported shape.  Nothing is launched then.
+ * Results are bitwise reproducible (no atomics, one summation order). */
+int vpc_rows_max_rows(void);
+
+/* y[M][N] = act(x[M][K] w[N][K]^T + bias[N])            nn.Linear + activation (VAE.py:1878-1900, :2343-2363); bias may be
+ * NULL. */
+int vpc_rows_fwd(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long M, int N, int K,
+                 int act, int act_split, void* stream);
+
+/* One layer's whole backward in ONE launch (autograd of the same layer: what vpc_linear_dgrad, vpc_linear_wgrad and
+ * vpc_linear_wgrad_reduce do in three):
+ *   dw[N][K] (+)= (dy * gate'(y_gate))^T x,  db[N] (+)= column sums     (dw == NULL: skipped, x / db unused; db may be NULL)
+ *   dx[M][K]  = ((dy * gate'(y_gate)) w[N][K]) * act_prev'(x_out)       (dx == NULL: skipped, w / x_out unused)
+ * x [M][K] (pitch ldx) is the layer's input; x_out (pitch ldxo, may be NULL) is the same activations as the data gradient
+ * gates with them, activation code act_prev.  y_gate may be NULL (dy is the pre-activation gradient).  accumulate != 0
+ * adds to dw / db.  dw and dx both NULL: bad argument. */
+int vpc_rows_bwd(const float* dy, long lddy, const float* y_gate, long ldyg, int gate, int gate_split, const float* w,
+                 const float* x, long ldx, const float* x_out, long ldxo, int act_prev, float* dx, long lddx, float* dw,
+                 float* db, long M, int N, int K, int accumulate, void* stream);
+
 /* z[b*K+k][:] = mean[b] + eps[b][k] * exp(logvar[b]/2), heads = [mean L | logvar L]; eps NULL -> z = mean
  * (encoder, VAE.py:2382-2391 / :2753-2765) and its backward (sum over the K replicas, plus g_heads if given). */
 int vpc_nm_sample(const float* heads, long ldh, const float* eps, float* z, long ldz, long B, int K, int L,

@@ -17,13 +17,14 @@
 // (tools/lds_conflicts.py).  Global loads of chunk i+1 are in flight while chunk i is multiplied.
 #include "vpc_abi_internal.h"
 #include "vpc_device.h"
+#include "vpc_act.h"
 #include "vpc_bf16.h"
 #include "../../include/vpc.h"
 
 namespace vpc {
 
 enum { LIN_FWD = 0, LIN_DGRAD = 1, LIN_WGRAD = 2 };
-enum { ACT_NONE = 0, ACT_ELU = 1, ACT_SIGMOID_HARDTANH = 2, ACT_RELU = 3 };
+// (activation codes, act_fwd / act_grad / act_dispatch: vpc_act.h)
 
 struct LinArgs {
     const float* A; long lda;      // fwd: W [N][K]       dgrad: W [N][K]       wgrad: dY [M][N]
@@ -39,36 +40,6 @@ struct LinArgs {
     int rows_per_split;            // wgrad
     int vecA, vecB, vecC, vecX;    // 16-byte path usable for the operand / output / aux
 };
-
-// The activation code is a kernel ARGUMENT; it is dispatched ONCE per tile (act_dispatch) into code specialised on it,
-// never per element: a per-element `switch` costs a branch forest per value (the first build of the epilogue spent as
-// long in it as in the MFMAs of a K = 128 layer).
-template <int ACT>
-__device__ __forceinline__ float act_fwd(float v, bool second) {
-    // hardware exp / rcp (v_exp_f32, v_rcp_f32): |abs err| < 2e-7 on outputs in (-1, 1)
-    if (ACT == ACT_ELU) return v > 0.f ? v : __expf(v) - 1.f;
-    if (ACT == ACT_SIGMOID_HARDTANH) return second ? __builtin_amdgcn_fmed3f(v, -10.f, 0.f) : __builtin_amdgcn_rcpf(1.f + __expf(-v));
-    if (ACT == ACT_RELU) return fmaxf(v, 0.f);
-    return v;
-}
-// derivative of the activation expressed through its OUTPUT y
-template <int ACT>
-__device__ __forceinline__ float act_grad(float y, bool second) {
-    if (ACT == ACT_ELU) return y > 0.f ? 1.f : y + 1.f;
-    if (ACT == ACT_SIGMOID_HARDTANH) return second ? ((y > -10.f && y < 0.f) ? 1.f : 0.f) : y * (1.f - y);
-    if (ACT == ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    return 1.f;
-}
-template <int V> struct ActC { static constexpr int value = V; };
-template <typename F>
-__device__ __forceinline__ void act_dispatch(int act, F&& f) {
-    switch (act) {
-        case ACT_ELU: f(ActC<ACT_ELU>{}); break;
-        case ACT_SIGMOID_HARDTANH: f(ActC<ACT_SIGMOID_HARDTANH>{}); break;
-        case ACT_RELU: f(ActC<ACT_RELU>{}); break;
-        default: f(ActC<ACT_NONE>{}); break;
-    }
-}
 
 constexpr int LIN_THREADS = 512;  // 8 waves: 4 (A-operand index) x 2 (B-operand index); a wave owns 32 x 64 outputs
 constexpr int LIN_TILE = 8192;    // floats per (full) LDS tile

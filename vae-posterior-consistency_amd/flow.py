@@ -21,6 +21,8 @@ by FAMILY below) and the trainer frame.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -28,7 +30,8 @@ from . import _lib as L
 from ._lib import check, lib, ptr, require_cuda, stream_ptr
 from .chainfamily import ChainDecoderFn, ChainEncoderFn, Family, _ChainTrainer
 from .images import FlatParams, mlp_spec
-from .linear import ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_bwd, chain_fwd
+from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_bwd, chain_bwd_rows, chain_fwd,
+                     chain_fwd_rows)
 from .trainer import chain_draw_increment
 
 FLOW_L = 10      # VPC_FLOW_LATENT: latent dim = spline bins
@@ -294,6 +297,33 @@ _T_ENC_FWD, _T_ENC_BWD, _T_DEC_FWD, _T_DEC_BWD = ("enc_fwd",) * 3, ("enc_bwd",) 
 _DEC_WKEYS = tuple(("dec_bwd", 4 - i) for i in range(5))
 _ENC_WKEYS = tuple(("enc_bwd", 7 - i) for i in range(3))
 
+SMALL_MAX_ROWS, SMALL_MAX_WIDTH = 128, 1024  # limits of csrc/vpc_rows.hip (vpc_rows_max_rows(); N, K <= 1024)
+# The row limit of the small-batch step, in stacked rows R = P * B.  The step without VPC_FLOW_SMALL in the environment stays the
+# launch chain (tests/test_trainer_images.py pins the chain's 29 calls as FlowTrainer's step at B = 64), so the default is 0;
+# SMALL_ROWS_MEASURED is the largest R at which the small path's worst block beat the chain's best block
+# (profiles/flow_small_notes.md) - the value to put into VPC_FLOW_SMALL.
+SMALL_ROWS_DEFAULT = 0
+SMALL_ROWS_MEASURED = 128
+
+
+def small_max_rows():
+    """The row limit of the small-batch step: VPC_FLOW_SMALL in the environment (stacked rows P * B; 0 = never), read per
+    step; SMALL_ROWS_DEFAULT (0: the chain) without it."""
+    v = os.environ.get("VPC_FLOW_SMALL")
+    if v is None or v == "":
+        return SMALL_ROWS_DEFAULT
+    try:
+        return int(v)
+    except ValueError:
+        raise L.VpcError(f"VPC_FLOW_SMALL={v!r}: expected a number of stacked rows (0 keeps the launch chain)") from None
+
+
+def small_step_route(R, d, hid, max_rows):
+    """Whether FlowTrainer.step takes the small-batch step (the few-row layer ops of csrc/vpc_rows.hip): 0 < R <= max_rows
+    stacked rows (small_max_rows()) and at most 128, every layer at most 1024 wide (the encoder input 2 d, hid_dim).
+    Everything else keeps the launch chain."""
+    return 0 < R <= min(max_rows, SMALL_MAX_ROWS) and 0 < 2 * d <= SMALL_MAX_WIDTH and 0 < hid <= SMALL_MAX_WIDTH
+
 
 class FlowTrainer(_ChainTrainer):
     """The whole training step of the flow path (train.py:77-86 + :114-116) as a fixed sequence of HIP launches with no
@@ -302,11 +332,33 @@ class FlowTrainer(_ChainTrainer):
     gradients gated through Sigmoid'), the backward GEMM chain with the flow backward between decoder and encoder, the
     eight weight gradients summed by one launch, flat Adam.  fp32 only; 30 launches.
 
+    Few rows (small_step_route: R = P * B <= small_max_rows() and <= 128 stacked rows, layers at most 1024 wide) run the same
+    step on the few-row layer ops (csrc/vpc_rows.hip): a forward launch per layer split over output features, and ONE
+    backward launch per layer that writes the complete weight gradient next to the data gradient - no partials, no
+    reduction launch: prep, 3 + 5 rows_fwd around the flow, the loss, 5 + 3 rows_bwd around the flow backward, Adam = 21 calls,
+    22 launches, on the chain's workspace buffers and with the same draws.  VPC_FLOW_SMALL in the environment is the row
+    limit and switches the path on (unset or 0 keeps the chain; SMALL_ROWS_MEASURED is the measured value); `last_path`
+    names what the last step ran: "small" or "chain".
+
     Single process only: the reference's torch.any(inside) (VAE.py:1698) is a predicate over the whole batch of an
     encoder call, so a sharded step would need a cross-rank vote before the flow."""
     family, model_base, model_names = FAMILY, _FlowBase, "VAEFlow and REG_VAEFlow"
     single_process = ("the flow's torch.any(inside) is a predicate over the whole batch (no data-parallel form without a "
                       "cross-rank vote)")
+
+    last_path = None
+
+    def _wgrad_workspace(self, shapes, grads, sized=True):
+        """The per-layer partials are the chain path's alone: allocated by its first step on this workspace
+        (_chain_workspace), never for a trainer that only takes the small path, whose rows_bwd launches write the complete
+        gradients `grads` (backward order: the decoder's last layer first, then the encoder's)."""
+        self._wg_spec, self._wg = (shapes, grads), None
+        n = len(self.dec_layers)
+        self._dec_grads, self._enc_grads = grads[:n][::-1], grads[n:][::-1]
+
+    def _chain_workspace(self):
+        if self._wg is None:
+            super()._wgrad_workspace(*self._wg_spec)
 
     def _buffers(self, B, e):
         m, dev = self.model, self.dev
@@ -353,6 +405,10 @@ class FlowTrainer(_ChainTrainer):
         if eps is not None:
             self.eps.copy_(eps.reshape(self.eps.shape))
         self.rng_offset += chain_draw_increment(self.eps.numel(), B, d)
+        if small_step_route(R, d, H, small_max_rows()):
+            return self._step_small(xf, mf, mp, R, B, d, alpha, beta, stage)
+        self.last_path = "chain"
+        self._chain_workspace()
         # ---- forward
         chain_fwd(self.enc_layers, self.enc_acts, R, 0, t, _T_ENC_FWD)
         t("flow", flow_fwd, self.t, self.eps, self.z, self.zlp, R, B)
@@ -367,4 +423,20 @@ class FlowTrainer(_ChainTrainer):
         chain_bwd(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._wgrad, _ENC_WKEYS, input_grad=False, run=t,
                   names=_T_ENC_BWD)
         self._wgrad_reduce()
+        self._adam()
+
+    def _step_small(self, xf, mf, mp, R, B, d, alpha, beta, stage):
+        """The step behind the draws on the few-row layer ops, on the chain's workspace buffers: every rows_bwd writes its
+        layer's complete weight gradient into the flat gradient, so Adam follows the last of them."""
+        t, sl = self._timed, self._sl
+        self.last_path = "small"
+        chain_fwd_rows(self.enc_layers, self.enc_acts, R, t, _T_ENC_FWD)
+        t("flow", flow_fwd, self.t, self.eps, self.z, self.zlp, R, B)
+        chain_fwd_rows(self.dec_layers, self.dec_acts, R, t, _T_DEC_FWD)
+        t("loss", flow_loss, xf, mf, mp, sl["xm"], sl["z"], sl["zlp"], sl["g"], self.scratch, self.out8, self.tail,
+          self.accum, B, d, STAGE_TRAIN if stage == "train" else STAGE_EVAL, alpha, beta, 1.0 / B, 1)
+        chain_bwd_rows(self.dec_layers, self.dec_acts, self.dec_dacts, R, self._dec_grads, run=t, names=_T_DEC_BWD)
+        t("flow_bwd", flow_bwd, self.t, self.eps, self.dzd, self.gz, self.gzlp, self.dt, R, B)
+        chain_bwd_rows(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._enc_grads, input_grad=False, run=t,
+                       names=_T_ENC_BWD)
         self._adam()

@@ -1,5 +1,6 @@
-"""The generic fp32 MFMA GEMM layer ops (csrc/vpc_gemm.hip) and the two walkers of an MLP chain built from them.  A leaf
-module: every model family imports from here.
+"""The generic fp32 MFMA GEMM layer ops (csrc/vpc_gemm.hip), their few-row form (csrc/vpc_rows.hip: M <= 128 rows, split over
+output features, one backward launch per layer) and the walkers of an MLP chain built from either.  A leaf module: every model
+family imports from here.
 
 A chain is an ordered list of layers `(w, b, K_in, N_out, act, split)`; its activations are a list `acts` with `acts[0]` the
 chain's input and `acts[i + 1]` the output of layer i, and `dacts` the gradients laid out the same way (`dacts[i + 1]` is
@@ -74,6 +75,28 @@ def wgrad_reduce(layers, cache=None):
     check(lib().vpc_linear_wgrad_reduce(n, sc, Ms, Ns, Ks, dw, db, acc, stream_ptr()), "vpc_linear_wgrad_reduce")
 
 
+# ------------------------------------------------------------------------------------------------ few-row layer ops
+def rows_max_rows():
+    """The row limit of rows_fwd / rows_bwd (csrc/vpc_rows.hip): 128."""
+    return int(lib().vpc_rows_max_rows())
+
+
+def rows_fwd(x, w, b, y, M, N, K, act=ACT_NONE, split=0, ldx=None, ldy=None):
+    """linear_fwd for M <= 128 rows and N, K <= 1024 (fp32): split over output features, one launch."""
+    check(lib().vpc_rows_fwd(ptr(x), ldx or K, ptr(w), ptr(b), ptr(y), ldy or N, M, N, K, act, split, stream_ptr()),
+          "vpc_rows_fwd")
+
+
+def rows_bwd(dy, w, x, dx, dw, db, M, N, K, y_gate=None, gate=ACT_NONE, gate_split=0, x_out=None, act_prev=ACT_NONE,
+             accumulate=False, lddy=None, ldyg=None, ldx=None, ldxo=None, lddx=None):
+    """One layer's whole backward in one launch for M <= 128 rows: dw / db (+)= the weight gradient, written complete (dw None:
+    skipped), and dx = the data gradient gated by act_prev'(x_out) (dx None: skipped).  x is the layer's input, x_out the same
+    activations where the data gradient is gated with them.  Pitches default as in linear_dgrad / linear_wgrad."""
+    check(lib().vpc_rows_bwd(ptr(dy), lddy or N, ptr(y_gate), ldyg or lddy or N, gate, gate_split, ptr(w), ptr(x), ldx or K,
+                             ptr(x_out), ldxo or ldx or K, act_prev, ptr(dx), lddx or K, ptr(dw), ptr(db), M, N, K,
+                             int(accumulate), stream_ptr()), "vpc_rows_bwd")
+
+
 # ------------------------------------------------------------------------------------------------ MLP chains
 def chain(weights, acts, split=0):
     """[W1, b1, W2, b2, ..] (each W [N, K]) + the activation of every layer -> the chain's layers.  `split`: the column
@@ -128,4 +151,32 @@ def chain_bwd(layers, acts, dacts, M, wgrad, wkeys, input_grad=True, y_gate=None
             else:
                 run(names[i], linear_dgrad, dy, w, dacts[i], M, N, K, y_gate, gate, gate_split, x_out, act_prev,
                     precision=precision)
+        y_gate, gate, gate_split = None, ACT_NONE, 0
+
+
+def chain_fwd_rows(layers, acts, M, run=None, names=None):
+    """chain_fwd on the few-row ops: one rows_fwd per layer (M <= rows_max_rows() rows)."""
+    for i, (w, b, K, N, act, split) in enumerate(layers):
+        if run is None:
+            rows_fwd(acts[i], w, b, acts[i + 1], M, N, K, act, split)
+        else:
+            run(names[i], rows_fwd, acts[i], w, b, acts[i + 1], M, N, K, act, split)
+
+
+def chain_bwd_rows(layers, acts, dacts, M, grads, input_grad=True, y_gate=None, gate=ACT_NONE, gate_split=0, run=None,
+                   names=None):
+    """chain_bwd on the few-row ops, from the last layer down: one rows_bwd per layer writes the complete weight gradient
+    into grads[i] = (dw, db) - views of the flat gradient - and the data gradient, gated by the activation of the layer
+    below, into dacts[i].  The output gate applies to the last layer only; input_grad False: the first layer has no data
+    gradient."""
+    for i in range(len(layers) - 1, -1, -1):
+        w, _, K, N, _, _ = layers[i]
+        dw, db = grads[i]
+        dx = dacts[i] if (i > 0 or input_grad) else None
+        x_out, act_prev = (acts[i], layers[i - 1][4]) if i > 0 else (None, ACT_NONE)
+        if run is None:
+            rows_bwd(dacts[i + 1], w, acts[i], dx, dw, db, M, N, K, y_gate, gate, gate_split, x_out, act_prev)
+        else:
+            run(names[i], rows_bwd, dacts[i + 1], w, acts[i], dx, dw, db, M, N, K, y_gate, gate, gate_split, x_out,
+                act_prev)
         y_gate, gate, gate_split = None, ACT_NONE, 0
