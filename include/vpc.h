@@ -1066,6 +1066,75 @@ int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const 
                   float* g_z_log_prob_p, void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum,
                   long B, int d, int stage, float alpha, float beta, float gscale, int gated, void* stream);
 
+/* ---- an ensemble of G flow models of ONE shape: the few-row step with a member axis ----------------------------------
+ * Replaces the drivers' loops around train() (src/experiment_main/imputation.py:21-39: `for missing: for alpha:`) for the
+ * runs vanilla_flow1..3 / reg_flow1..3 (Data/imputation_args.json:7-12): the G members step in the launches of ONE
+ * stand-alone few-row step (FlowTrainer._step_small: 21 calls, 22 launches), whatever G.  Every entry is its stand-alone
+ * entry with a member axis on the grid: workgroup (.., g) runs the stand-alone kernel's body on member g's arrays
+ * (base + g * stride floats), so member g computes bit for bit what the stand-alone call on its arrays computes, whatever G
+ * and wherever its workgroups run.  No atomics, no traffic between workgroups.
+ * Members: G device-resident VpcFlowMember records (32 bytes, ordinary loads) - what may differ from member to member
+ * besides the data.  Every entry checks its arguments before any launch and launches nothing on failure: VPC_ERR_ARG for a
+ * NULL mandatory pointer, G outside 1 .. VPC_FLOW_MULTI_MAX_MEMBERS, a member stride below the member's slice (the
+ * strides of x / mask may be 0: one batch read by every member) and what the stand-alone entry refuses; VPC_ERR_SHAPE
+ * for what the stand-alone entry calls an unsupported shape and for a grid past the launch limits. */
+#define VPC_FLOW_MULTI_MAX_MEMBERS 4096
+#define VPC_ROWS_MULTI_MAX_MEMBERS 4096
+typedef struct VpcFlowMember {
+    unsigned long long seed; /* Philox seed of the member's mask_p and eps draws (train.py:102-104, VAE.py:1824-1827) */
+    float alpha;             /* REG_VAEFlow loss weight (VAE.py:2086-2093) */
+    float beta;              /* KL weight (VAE.py:1962, :2084) */
+    float keep_prob;         /* 1 - p_missingness / 100 of the mask_p draw (train.py:102-104) */
+    float lr;                /* Adam learning rate (train.py:21) */
+    int reserved[2];         /* 0 */
+} VpcFlowMember;
+
+/* vpc_rows_fwd (nn.Linear + activation, VAE.py:1878-1900) for G members: grid (slabs, row blocks, G).  w / bias are member
+ * 0's layer inside the stacked flat parameters, wb_stride the stack's row pitch; x / y member 0's activations.
+ * order: 0 = member-major; 1 = all workgroups of a member on one XCD (grid (8 x workgroups, ceil(G / 8)); same bits), so a
+ * member's weights are re-read through one L2.  The 16-byte or scalar build is chosen as vpc_rows_fwd chooses it on member
+ * 0's operands; EVERY member stride must therefore be a multiple of 4 floats (VPC_ERR_ARG otherwise), and none may be 0. */
+int vpc_rows_fwd_multi(const float* x, long ldx, long x_stride, const float* w, const float* bias, long wb_stride, float* y,
+                       long ldy, long y_stride, int G, long M, int N, int K, int act, int act_split, int order, void* stream);
+/* vpc_rows_bwd (autograd of the same layer) for G members: the 1-D grid of one member x G (blockIdx.y = member under order 0).
+ * w, dw and db share wb_stride (the parameter and the gradient stack have one row pitch).  Strides of arrays that are
+ * NULL are ignored; the stride rule and `order` as in vpc_rows_fwd_multi. */
+int vpc_rows_bwd_multi(const float* dy, long lddy, long dy_stride, const float* y_gate, long ldyg, long yg_stride, int gate,
+                       int gate_split, const float* w, const float* x, long ldx, long x_stride, const float* x_out, long ldxo,
+                       long xo_stride, int act_prev, float* dx, long lddx, long dx_stride, float* dw, float* db, long wb_stride,
+                       int G, long M, int N, int K, int accumulate, int order, void* stream);
+/* vpc_flow_prep (train.py:53-55, :102-104 + VAE.py:1924-1931) for G members: member g's xin [R][2d] from its x / mask and,
+ * with a second pass (R == 2 B; mask_p mandatory then, NULL otherwise), its mask_p [B][d].  draw != 0: mask_p and eps
+ * [R][10] are drawn with seed_g and keep_prob_g at the counters of the stand-alone entry (offset, offset_eps); draw == 0:
+ * mask_p is read and eps left alone. */
+int vpc_flow_multi_prep(const float* x, long x_stride, const float* mask, long mask_stride, float* mask_p, long mask_p_stride,
+                        float* xin, long xin_stride, float* eps, long eps_stride, const VpcFlowMember* members, int G, int draw,
+                        long R, long B, int d, unsigned long long offset, unsigned long long offset_eps, void* stream);
+/* vpc_flow_fwd / vpc_flow_bwd (Flow.forward, VAE.py:1816-1831, and its autograd) for G members.  stride10: floats between
+ * two members' [R][10] arrays (eps, z, z_log_prob, dz, dz2, dz_log_prob).  torch.any(inside) (VAE.py:1698) is taken per
+ * (member, pass): over member g's eps rows of that pass only. */
+int vpc_flow_fwd_multi(const float* t, long ldt, long t_stride, const float* eps, float* z, float* z_log_prob, long stride10,
+                       int G, long R, long B, void* stream);
+int vpc_flow_bwd_multi(const float* t, long ldt, long t_stride, const float* eps, const float* dz, const float* dz2,
+                       const float* dz_log_prob, long stride10, float* dt, long lddt, long dt_stride, int G, long R, long B,
+                       void* stream);
+/* vpc_flow_loss (VAE.py:1950-1969 / :2075-2111) for G members, both launches with blockIdx.y = member: alpha_g and beta_g
+ * from the member table; out8 [G][8], loss_f32 [G], accum [G]; scratch of vpc_flow_loss_multi_scratch(G, B) bytes.  A
+ * member's x_mean, z, z_log_prob and gradient arrays hold its q rows and then its p rows (the *_q / *_p pointers are member
+ * 0's), x_mean_stride / g_stride / stride10 apart. */
+long vpc_flow_loss_multi_scratch(int G, long B);
+int vpc_flow_loss_multi(const float* x, long x_stride, const float* mask, long mask_stride, const float* mask_p,
+                        long mask_p_stride, const float* x_mean_q, const float* x_mean_p, long ldxm, long x_mean_stride,
+                        const float* z_q, const float* z_p, const float* z_log_prob_q, const float* z_log_prob_p,
+                        float* g_x_mean_q, float* g_x_mean_p, long ldg, long g_stride, float* g_z_q, float* g_z_p,
+                        float* g_z_log_prob_q, float* g_z_log_prob_p, long stride10, void* scratch, long scratch_bytes,
+                        double* out8, float* loss_f32, float* accum, const VpcFlowMember* members, int G, long B, int d,
+                        int stage, float gscale, int gated, void* stream);
+/* vpc_adam_step (torch.optim.Adam, train.py:21, :116) on the rows of [G][row_stride] stacks in ONE launch: per element the
+ * arithmetic of vpc_adam_step with lr_g; the host step count, betas and eps are shared. */
+int vpc_adam_step_multi(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long row_stride, int n,
+                        const VpcFlowMember* members, int G, float beta1, float beta2, float eps, long step, void* stream);
+
 /* ---- config 5 reward of the flow models (csrc/vpc_flowreward.hip) ------------------------------------------------
  * Replaces the flow branch of active_learning_func's candidate loop (src/experiment_main/evaluate.py:416-422) and the
  * functions it calls: R_lindley_chain_ratio_version (:637-665), chaini_I_ratio_version (:669-684),

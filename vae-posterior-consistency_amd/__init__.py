@@ -20,6 +20,8 @@ from . import miw_ensemble
 from .miw_ensemble import MIWEnsembleTrainer
 from . import flow
 from .flow import VAEFlow, REG_VAEFlow, FlowTrainer
+from . import flow_ensemble
+from .flow_ensemble import FlowEnsembleTrainer
 from . import notmiwae
 from . import eddi
 from .eddi import Reg_EDDI, vanilla_EDDI, EDDITrainer
@@ -46,4 +48,4 @@ __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedT
            "ensemble", "EnsembleTrainer", "stack_models", "train_sweep", "EnsembleEvaluator", "eval_sweep",
            "EnsembleAcquirer", "active_sweep", "MaskEnsembleTrainer", "EDDIEnsembleTrainer",
            "MaskEnsembleEvaluator", "EDDIEnsembleEvaluator", "MaskEnsembleAcquirer", "EDDIEnsembleAcquirer",
-           "miw_ensemble", "MIWEnsembleTrainer"]
+           "miw_ensemble", "MIWEnsembleTrainer", "flow_ensemble", "FlowEnsembleTrainer"]

@@ -185,6 +185,16 @@ _PROTOS = {
     "vpc_flow_bwd": [P, L_, P, P, P, P, P, L_, L_, L_, P],
     "vpc_flow_loss_scratch": [L_],
     "vpc_flow_loss": [P, P, P, P, P, L_, P, P, P, P, P, P, L_, P, P, P, P, P, L_, P, P, P, L_, I, I, F, F, F, I, P],
+    # the few-row flow step with a member axis (csrc/vpc_rows.hip, vpc_flow.hip, vpc_misc.hip)
+    "vpc_rows_fwd_multi": [P, L_, L_, P, P, L_, P, L_, L_, I, L_, I, I, I, I, I, P],
+    "vpc_rows_bwd_multi": [P, L_, L_, P, L_, L_, I, I, P, P, L_, L_, P, L_, L_, I, P, L_, L_, P, P, L_, I, L_, I, I, I, I, P],
+    "vpc_flow_multi_prep": [P, L_, P, L_, P, L_, P, L_, P, L_, P, I, I, L_, L_, I, ULL, ULL, P],
+    "vpc_flow_fwd_multi": [P, L_, L_, P, P, P, L_, I, L_, L_, P],
+    "vpc_flow_bwd_multi": [P, L_, L_, P, P, P, P, L_, P, L_, L_, I, L_, L_, P],
+    "vpc_flow_loss_multi_scratch": [I, L_],
+    "vpc_flow_loss_multi": [P, L_, P, L_, P, L_, P, P, L_, L_, P, P, P, P, P, P, L_, L_, P, P, P, P, L_, P, L_, P, P, P, P, I, L_,
+                            I, I, F, I, P],
+    "vpc_adam_step_multi": [P, P, P, P, L_, I, P, I, F, F, F, L_, P],
     # config 5 reward of the flow models (csrc/vpc_flowreward.hip)
     "vpc_flow_reward_scratch": [I, I, I, I, I, C.POINTER(L_)],
     "vpc_flow_reward_matrix": [P, P, P, P, P, P, P, P, P, P, ULL, P, L_, P, I, I, I, I, I, P],
@@ -208,7 +218,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_multi_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_multi_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_flow_loss_multi_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
 
 _lib = None
 

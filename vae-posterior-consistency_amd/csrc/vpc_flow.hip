@@ -60,90 +60,14 @@ __device__ __forceinline__ void flow_flags(const float* __restrict__ eps, long R
 __global__ void __launch_bounds__(256) flow_fwd_kernel(const float* __restrict__ t, long ldt,
                                                        const float* __restrict__ eps, float* __restrict__ z,
                                                        float* __restrict__ zlp, long R, long B) {
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long row0 = (long)blockIdx.x * blockDim.x / FLOW_L, row1 = ((long)blockIdx.x + 1) * blockDim.x / FLOW_L;
-    bool f0, f1;
-    flow_flags(eps, R, B, row0, row1, f0, f1);
-    if (g >= R * FLOW_L) return;
-    const long r = g / FLOW_L;
-    const int i = (int)(g - r * FLOW_L);
-    const float e = eps[g];
-    const float lp = -(e * e) / 2.f - FLOW_HALF_LOG_2PI;  // Normal(0, 1).log_prob (:1826-1828)
-    if (!(r < B ? f0 : f1)) {  // no inside element in this pass: every layer is the identity with logabsdet 0 (:1698)
-        z[g] = e;
-        zlp[g] = lp;
-        return;
-    }
-    float m[FLOW_L];
-    flow_mask(eps + r * FLOW_L, m);
-    FlowPdf s;
-    flow_pdf(t + r * ldt + i * FLOW_L, m, s);
-    float in = fabsf(e) <= 1.f ? e : 0.f;  // outside inputs are zeroed, then splined (:1694)
-    float ld = 0.f;
-#pragma unroll
-    for (int l = 0; l < 3; ++l) {
-        const FlowStep st = flow_step(s, in);
-        in = flow_out(st);
-        ld += flow_lad(st);
-    }
-    z[g] = in;
-    zlp[g] = lp - ld;
+#include "vpc_flow_fwd_body.h"
 }
 
 __global__ void __launch_bounds__(256) flow_bwd_kernel(const float* __restrict__ t, long ldt,
                                                        const float* __restrict__ eps, const float* __restrict__ dz,
                                                        const float* __restrict__ dz2, const float* __restrict__ dzlp,
                                                        float* __restrict__ dt, long lddt, long R, long B) {
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long row0 = (long)blockIdx.x * blockDim.x / FLOW_L, row1 = ((long)blockIdx.x + 1) * blockDim.x / FLOW_L;
-    bool f0, f1;
-    flow_flags(eps, R, B, row0, row1, f0, f1);
-    if (g >= R * FLOW_L) return;
-    const long r = g / FLOW_L;
-    const int i = (int)(g - r * FLOW_L);
-    float* o = dt + r * lddt + i * FLOW_L;
-    if (!(r < B ? f0 : f1)) {  // identity layers: t is not read
-#pragma unroll
-        for (int j = 0; j < FLOW_L; ++j) o[j] = 0.f;
-        return;
-    }
-    float m[FLOW_L];
-    flow_mask(eps + r * FLOW_L, m);
-    FlowPdf s;
-    flow_pdf(t + r * ldt + i * FLOW_L, m, s);
-    FlowStep st[3];
-    float in = fabsf(eps[g]) <= 1.f ? eps[g] : 0.f;
-#pragma unroll
-    for (int l = 0; l < 3; ++l) {
-        st[l] = flow_step(s, in);
-        in = flow_out(st[l]);
-    }
-    float gout = (dz ? dz[g] : 0.f) + (dz2 ? dz2[g] : 0.f);
-    const float glad = dzlp ? -dzlp[g] : 0.f;  // z_log_prob = log_prob - sum of the three logabsdet
-    float du[FLOW_L];
-#pragma unroll
-    for (int j = 0; j < FLOW_L; ++j) du[j] = 0.f;
-#pragma unroll
-    for (int l = 2; l >= 0; --l) {
-        // out = clamp(cdf[bin] + alpha pdf[bin], 0, 1) * 2 - 1; clamp passes the gradient on [0, 1] (torch.clamp)
-        const float go = (st[l].o >= 0.f && st[l].o <= 1.f) ? 2.f * gout : 0.f;
-        const int bin = st[l].bin;
-        float cb = 0.f;
-#pragma unroll
-        for (int j = 0; j < FLOW_L; ++j)
-            if (j == bin) cb = s.cdf[j];
-        const float ap = st[l].alpha * st[l].pb;
-#pragma unroll
-        for (int j = 0; j < FLOW_L; ++j) {
-            const float pj = s.pdf[j];
-            const float djb = j == bin ? 1.f : 0.f;
-            // d cdf[bin] / d u_j = pdf_j ([j < bin] - cdf[bin]),  d pdf[bin] / d u_j = pdf[bin] ([j == bin] - pdf_j)
-            du[j] += go * (pj * ((j < bin ? 1.f : 0.f) - cb) + ap * (djb - pj)) + glad * (djb - pj);
-        }
-        gout = go * (float)FLOW_L * 0.5f * st[l].pb;  // d out / d in = 10 pdf[bin]; layer 1's input (eps) is a leaf
-    }
-#pragma unroll
-    for (int j = 0; j < FLOW_L; ++j) o[j] = du[j] * m[j];  // the in-place context mask of layer 1
+#include "vpc_flow_bwd_body.h"
 }
 
 __global__ void __launch_bounds__(256) flow_prep_kernel(const float* __restrict__ x, const float* __restrict__ m,
@@ -151,35 +75,7 @@ __global__ void __launch_bounds__(256) flow_prep_kernel(const float* __restrict_
                                                         float* __restrict__ xin, long B, int d, float keep_prob,
                                                         float* __restrict__ eps, long n_eps, uint64_t seed,
                                                         uint64_t offset, uint64_t offset_eps, unsigned gm) {
-    if (blockIdx.x >= gm) {
-        fill_normal_body(eps, n_eps, seed, offset_eps, (long)(blockIdx.x - gm) * blockDim.x + threadIdx.x,
-                         EpsShard{0, 0, 0, 4});
-        return;
-    }
-    const long n = B * d;
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long i0 = g * 4;
-    if (i0 >= n) return;
-    const bool two = mp_in || mp_out;
-    U4 r{0, 0, 0, 0};
-    if (mp_out && !mp_in) r = philox((uint64_t)g + offset, 0u, seed);  // the counters of vpc_nm_prep's mask_p draw
-    const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
-    for (int j = 0; j < 4 && i0 + j < n; ++j) {
-        const long e = i0 + j;
-        const long b = e / d;
-        const int k = (int)(e - b * d);
-        const float xv = x[e], mv = m[e];
-        float* q = xin + b * 2 * d;
-        q[k] = xv * mv;
-        q[d + k] = mv;
-        if (two) {
-            const float pv = mp_in ? mp_in[e] : (u01(rr[j]) < keep_prob ? mv : 0.f);
-            if (mp_out) mp_out[e] = pv;
-            float* pp = xin + (B + b) * 2 * d;
-            pp[k] = xv * pv;
-            pp[d + k] = pv;
-        }
-    }
+#include "vpc_flow_prep_body.h"
 }
 
 struct FlowLossArgs {
@@ -203,119 +99,100 @@ __device__ __forceinline__ float flow_nll(const FlowLossArgs& a, float x, float 
 // ---- launch 1: one wave per data row b (both passes)
 // partial columns: 0 RE_q, 1 RE_p, 2 KL_q, 3 KL_p, 4 KL_reg, 5 NLL of x*mask*~mask_p, 6 RE_q on ~mask
 __global__ void __launch_bounds__(256) flow_loss_rows_kernel(FlowLossArgs a) {
-    __shared__ float sh[FLOW_WAVES][7];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.x * FLOW_WAVES + wv;
-    const int d = a.d, B = a.B;
-    const bool reg = a.P == 2, train = !a.eval;
-    const bool pp = reg && train;  // the p pass enters the loss
-    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (b < B) {
-        const float* x = a.x + (long)b * d;
-        const float* mq = a.m + (long)b * d;
-        const float* mpp = reg ? a.mp + (long)b * d : nullptr;
-        const float* xq = a.xm[0] + (long)b * a.ldxm;
-        const float* xp = pp ? a.xm[1] + (long)b * a.ldxm : nullptr;
-        const float al = a.alpha;
-        // coefficients of the unscaled loss: REG train loss_q + alpha (KL_reg - loss_q + loss_p + NLL_r) (:2086-2093)
-        const float c_q = pp ? 1.f - al : 1.f, c_r = pp ? al : 0.f, c_p = pp ? al : 0.f;
-        const float gs = a.gscale / a.var;
-        for (int k = lane; k < d; k += 64) {
-            const float xv = x[k], m = mq[k], rq = xq[k];
-            acc[0] += flow_nll(a, xv, rq, m);
-            acc[6] += flow_nll(a, xv, rq, 1.f - m);
-            float wr = 0.f;
-            if (reg) {
-                wr = m * (1.f - mpp[k]);
-                acc[5] += flow_nll(a, xv, rq, wr);
-            }
-            if (a.gxm[0]) {
-                float gq = (c_q * m + c_r * wr) * (rq - xv) * gs;
-                if (a.gated) gq *= rq * (1.f - rq);
-                a.gxm[0][(long)b * a.ldg + k] = gq;
-                if (a.gxm[1]) {
-                    float gp = 0.f;
-                    if (pp) {
-                        const float rp = xp[k];
-                        gp = c_p * mpp[k] * (rp - xv) * gs;
-                        if (a.gated) gp *= rp * (1.f - rp);
-                    }
-                    a.gxm[1][(long)b * a.ldg + k] = gp;
-                }
-            }
-            if (pp) acc[1] += flow_nll(a, xv, xp[k], mpp[k]);
-        }
-        if (lane < FLOW_L) {
-            const long iq = (long)b * FLOW_L + lane;
-            const float zq = a.z[0][iq], lq = a.zlp[0][iq];
-            acc[2] = lq - (-(zq * zq) / 2.f - FLOW_HALF_LOG_2PI);  // z_log_prob - prior.log_prob(z)
-            float sgn = 0.f;
-            if (pp) {
-                const float zp = a.z[1][iq], lpp = a.zlp[1][iq];
-                acc[3] = lpp - (-(zp * zp) / 2.f - FLOW_HALF_LOG_2PI);
-                acc[4] = fabsf(lq - lpp);
-                sgn = lq > lpp ? 1.f : (lq < lpp ? -1.f : 0.f);
-                if (a.gz[1]) {
-                    a.gz[1][iq] = a.gscale * c_p * a.beta * zp;
-                    a.gzlp[1][iq] = a.gscale * (c_p * a.beta - al * sgn);
-                }
-            } else if (a.gz[1]) {  // REG evaluate stage: the p pass does not enter the loss
-                a.gz[1][iq] = 0.f;
-                a.gzlp[1][iq] = 0.f;
-            }
-            if (a.gz[0]) {
-                a.gz[0][iq] = a.gscale * c_q * a.beta * zq;
-                a.gzlp[0][iq] = a.gscale * (c_q * a.beta + al * sgn);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 7; ++c) acc[c] = flow_wave_sum(acc[c]);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) sh[wv][c] = acc[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        double s = 0.0;
-        for (int w = 0; w < FLOW_WAVES; ++w) s += (double)sh[w][threadIdx.x];
-        a.part[(long)blockIdx.x * 8 + threadIdx.x] = s;
-    }
+#include "vpc_flow_loss_rows_body.h"
 }
 
 // ---- launch 2: one workgroup; column c of the partials summed by 32 lanes in a strided fixed order, then in lane order
 __global__ void __launch_bounds__(256) flow_loss_reduce_kernel(FlowLossArgs a) {
-    __shared__ double sh[8][33];
-    const int c = threadIdx.x >> 5, l = threadIdx.x & 31;
-    double s = 0.0;
-    if (c < 7)
-        for (int i = l; i < a.nblk; i += 32) s += a.part[(long)i * 8 + c];
-    sh[c][l] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t[7];
-        for (int k = 0; k < 7; ++k) {
-            double u = 0.0;
-            for (int j = 0; j < 32; ++j) u += sh[k][j];
-            t[k] = u;
-        }
-        const double al = a.alpha, be = a.beta;
-        const double loss_q = t[0] + be * t[2];
-        double loss = loss_q;
-        if (a.P == 2 && !a.eval) loss = loss_q + al * (t[4] - loss_q + (t[1] + be * t[3]) + t[5]);
-        double* o = a.out8;
-        o[0] = loss;   // unscaled; train_loss = loss / B
-        o[1] = t[0];   // RE_q (VAEFlow: RE_)
-        o[2] = t[1];   // RE_p
-        o[3] = t[2];   // KL_q
-        o[4] = t[3];   // KL_p
-        o[5] = t[4];   // KL_reg
-        o[6] = t[5];   // NLL of x * mask * ~mask_p
-        o[7] = t[6];   // RE_q_imputed (NLL on ~mask)
-        const float tl = (float)(loss / a.B);
-        if (a.loss_f32) a.loss_f32[0] = tl;
-        if (a.accum) a.accum[0] += tl;
+#include "vpc_flow_loss_reduce_body.h"
+}
+
+// ================================================================================================ the ensemble forms
+// G members in one launch (include/vpc.h, vpc_flow_*_multi): blockIdx.y = member, blockIdx.x = the workgroup's index among the
+// member's workgroups.  A workgroup runs the stand-alone body on member g's arrays (base + g * stride), so a member's result
+// does not depend on G.  torch.any(inside) (:1698) becomes a predicate per (member, pass): flow_pass_inside sees member g's
+// eps rows of that pass only.
+__global__ void __launch_bounds__(256) flow_fwd_multi_kernel(const float* __restrict__ t0, long ldt, long s_t,
+                                                             const float* __restrict__ eps0, float* __restrict__ z0,
+                                                             float* __restrict__ zlp0, long s10, long R, long B) {
+    const long mem = blockIdx.y;
+    const float* __restrict__ t = t0 + mem * s_t;
+    const float* __restrict__ eps = eps0 + mem * s10;
+    float* __restrict__ z = z0 + mem * s10;
+    float* __restrict__ zlp = zlp0 + mem * s10;
+#include "vpc_flow_fwd_body.h"
+}
+
+__global__ void __launch_bounds__(256) flow_bwd_multi_kernel(const float* __restrict__ t0, long ldt, long s_t,
+                                                             const float* __restrict__ eps0, const float* __restrict__ dz0,
+                                                             const float* __restrict__ dz20, const float* __restrict__ dzlp0,
+                                                             long s10, float* __restrict__ dt0, long lddt, long sdt, long R,
+                                                             long B) {
+    const long mem = blockIdx.y;
+    const float* __restrict__ t = t0 + mem * s_t;
+    const float* __restrict__ eps = eps0 + mem * s10;
+    const float* __restrict__ dz = dz0 ? dz0 + mem * s10 : nullptr;
+    const float* __restrict__ dz2 = dz20 ? dz20 + mem * s10 : nullptr;
+    const float* __restrict__ dzlp = dzlp0 ? dzlp0 + mem * s10 : nullptr;
+    float* __restrict__ dt = dt0 + mem * sdt;
+#include "vpc_flow_bwd_body.h"
+}
+
+// member g draws mask_p and eps with seed_g and keep_prob_g at the counters of the stand-alone prep
+__global__ void __launch_bounds__(256) flow_prep_multi_kernel(const float* __restrict__ x0, long sx, const float* __restrict__ m0,
+                                                              long sm, float* __restrict__ mp0, long smp, int draw,
+                                                              float* __restrict__ xin0, long sxin, long B, int d,
+                                                              float* __restrict__ eps0, long n_eps, long seps,
+                                                              const VpcFlowMember* __restrict__ members, uint64_t offset,
+                                                              uint64_t offset_eps, unsigned gm) {
+    const long mem = blockIdx.y;
+    const VpcFlowMember* rec = members + mem;  // (uniform address: scalar loads)
+    const float* __restrict__ x = x0 + mem * sx;
+    const float* __restrict__ m = m0 + mem * sm;
+    float* mp = mp0 ? mp0 + mem * smp : nullptr;
+    const float* __restrict__ mp_in = draw ? nullptr : mp;
+    float* __restrict__ mp_out = draw ? mp : nullptr;
+    float* __restrict__ xin = xin0 + mem * sxin;
+    float* __restrict__ eps = eps0 ? eps0 + mem * seps : nullptr;
+    const float keep_prob = rec->keep_prob;
+    const uint64_t seed = rec->seed;
+#include "vpc_flow_prep_body.h"
+}
+
+struct FlowLossMultiArgs {
+    FlowLossArgs base;                 // member 0's arrays; alpha / beta come from the member table
+    long sx, sm, smp, sxm, s10, sg;    // floats between two members' x / mask / mask_p / x_mean / [B][10] arrays / g_x_mean
+    const VpcFlowMember* members;
+};
+__device__ __forceinline__ FlowLossArgs flow_loss_member(const FlowLossMultiArgs& ma, const long mem) {
+    FlowLossArgs a = ma.base;
+    const VpcFlowMember* r = ma.members + mem;
+    a.x += mem * ma.sx; a.m += mem * ma.sm;
+    if (a.mp) a.mp += mem * ma.smp;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (a.xm[p]) a.xm[p] += mem * ma.sxm;
+        if (a.z[p]) a.z[p] += mem * ma.s10;
+        if (a.zlp[p]) a.zlp[p] += mem * ma.s10;
+        if (a.gxm[p]) a.gxm[p] += mem * ma.sg;
+        if (a.gz[p]) a.gz[p] += mem * ma.s10;
+        if (a.gzlp[p]) a.gzlp[p] += mem * ma.s10;
     }
+    a.part += mem * a.nblk * 8;
+    a.out8 += mem * 8;
+    if (a.loss_f32) a.loss_f32 += mem;
+    if (a.accum) a.accum += mem;
+    a.alpha = r->alpha;
+    a.beta = r->beta;
+    return a;
+}
+__global__ void __launch_bounds__(256) flow_loss_rows_multi_kernel(FlowLossMultiArgs ma) {
+    const FlowLossArgs a = flow_loss_member(ma, blockIdx.y);
+#include "vpc_flow_loss_rows_body.h"
+}
+__global__ void __launch_bounds__(256) flow_loss_reduce_multi_kernel(FlowLossMultiArgs ma) {
+    const FlowLossArgs a = flow_loss_member(ma, blockIdx.y);
+#include "vpc_flow_loss_reduce_body.h"
 }
 
 }  // namespace vpc
@@ -361,11 +238,13 @@ int vpc_flow_bwd(const float* t, long ldt, const float* eps, const float* dz, co
 
 long vpc_flow_loss_scratch(long B) { return B > 0 ? flow_loss_blocks(B) * 8 * 8 : 0; }
 
-int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const float* x_mean_q, const float* x_mean_p,
-                  long ldxm, const float* z_q, const float* z_p, const float* z_log_prob_q, const float* z_log_prob_p,
-                  float* g_x_mean_q, float* g_x_mean_p, long ldg, float* g_z_q, float* g_z_p, float* g_z_log_prob_q,
-                  float* g_z_log_prob_p, void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum,
-                  long B, int d, int stage, float alpha, float beta, float gscale, int gated, void* stream) {
+// argument checks and the kernels' record of vpc_flow_loss and vpc_flow_loss_multi (one member's arrays)
+static int flow_loss_setup(const float* x, const float* mask, const float* mask_p, const float* x_mean_q, const float* x_mean_p,
+                           long ldxm, const float* z_q, const float* z_p, const float* z_log_prob_q,
+                           const float* z_log_prob_p, float* g_x_mean_q, float* g_x_mean_p, long ldg, float* g_z_q,
+                           float* g_z_p, float* g_z_log_prob_q, float* g_z_log_prob_p, void* scratch, double* out8,
+                           float* loss_f32, float* accum, long B, int d, int stage, float alpha, float beta, float gscale,
+                           int gated, FlowLossArgs& a) {
     if (!x || !mask || !x_mean_q || !z_q || !z_log_prob_q || !scratch || !out8 || B <= 0 || d <= 0 || ldxm < d ||
         B > (1L << 26) || (stage != VPC_FLOW_TRAIN && stage != VPC_FLOW_EVAL))
         return VPC_ERR_ARG;
@@ -374,8 +253,8 @@ int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const 
     const bool grad = g_x_mean_q != nullptr;
     if (grad && (!g_z_q || !g_z_log_prob_q || ldg < d)) return VPC_ERR_ARG;
     if (grad && reg && (!g_x_mean_p || !g_z_p || !g_z_log_prob_p)) return VPC_ERR_ARG;
-    if (scratch_bytes < vpc_flow_loss_scratch(B) || ((uintptr_t)scratch & 7u)) return VPC_ERR_ARG;
-    FlowLossArgs a{};
+    if ((uintptr_t)scratch & 7u) return VPC_ERR_ARG;
+    a = FlowLossArgs{};
     a.x = x; a.m = mask; a.mp = mask_p;
     a.xm[0] = x_mean_q; a.xm[1] = x_mean_p; a.ldxm = ldxm;
     a.z[0] = z_q; a.z[1] = z_p; a.zlp[0] = z_log_prob_q; a.zlp[1] = z_log_prob_p;
@@ -392,9 +271,104 @@ int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const 
     const float sc = expf(-8.f / 2.f);  // x_logvar = obs_logvar * ones = -8 (:1943-1948); scale = exp(logvar / 2)
     a.var = sc * sc;
     a.logs = logf(sc);
+    return VPC_OK;
+}
+
+int vpc_flow_loss(const float* x, const float* mask, const float* mask_p, const float* x_mean_q, const float* x_mean_p,
+                  long ldxm, const float* z_q, const float* z_p, const float* z_log_prob_q, const float* z_log_prob_p,
+                  float* g_x_mean_q, float* g_x_mean_p, long ldg, float* g_z_q, float* g_z_p, float* g_z_log_prob_q,
+                  float* g_z_log_prob_p, void* scratch, long scratch_bytes, double* out8, float* loss_f32, float* accum,
+                  long B, int d, int stage, float alpha, float beta, float gscale, int gated, void* stream) {
+    FlowLossArgs a;
+    const int rc = flow_loss_setup(x, mask, mask_p, x_mean_q, x_mean_p, ldxm, z_q, z_p, z_log_prob_q, z_log_prob_p, g_x_mean_q,
+                                   g_x_mean_p, ldg, g_z_q, g_z_p, g_z_log_prob_q, g_z_log_prob_p, scratch, out8, loss_f32,
+                                   accum, B, d, stage, alpha, beta, gscale, gated, a);
+    if (rc != VPC_OK) return rc;
+    if (scratch_bytes < vpc_flow_loss_scratch(B)) return VPC_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(flow_loss_rows_kernel, dim3((unsigned)a.nblk), dim3(256), 0, st, a);
     hipLaunchKernelGGL(flow_loss_reduce_kernel, dim3(1), dim3(256), 0, st, a);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+// ---- the ensemble entries
+static inline bool flow_members_ok(const void* members, int G) { return members && G >= 1 && G <= VPC_FLOW_MULTI_MAX_MEMBERS; }
+// a member stride that holds the member's slice; shared = true admits 0 (one array read by every member)
+static inline bool flow_stride_ok(long stride, long slice, bool shared = false) {
+    return stride >= slice || (shared && stride == 0);
+}
+
+int vpc_flow_multi_prep(const float* x, long x_stride, const float* mask, long mask_stride, float* mask_p, long mask_p_stride,
+                        float* xin, long xin_stride, float* eps, long eps_stride, const VpcFlowMember* members, int G, int draw,
+                        long R, long B, int d, unsigned long long offset, unsigned long long offset_eps, void* stream) {
+    if (!x || !mask || !xin || B <= 0 || d <= 0 || B * d > (1L << 31) || !flow_rows_ok(R, B) || !flow_members_ok(members, G))
+        return VPC_ERR_ARG;
+    const bool two = R == 2 * B;
+    if ((two && !mask_p) || (!two && mask_p) || (draw && !eps)) return VPC_ERR_ARG;
+    if (!flow_stride_ok(x_stride, B * d, true) || !flow_stride_ok(mask_stride, B * d, true) ||
+        (two && !flow_stride_ok(mask_p_stride, B * d)) || !flow_stride_ok(xin_stride, R * 2 * d) ||
+        (draw && !flow_stride_ok(eps_stride, R * FLOW_L)))
+        return VPC_ERR_ARG;
+    const long n_eps = draw ? R * FLOW_L : 0;
+    const long groups = (B * d + 3) / 4, ge = (n_eps + 3) / 4;
+    const unsigned gm = (unsigned)((groups + 255) / 256), gn = (unsigned)((ge + 255) / 256);
+    hipLaunchKernelGGL(flow_prep_multi_kernel, dim3(gm + gn, (unsigned)G), dim3(256), 0, (hipStream_t)stream, x, x_stride, mask,
+                       mask_stride, mask_p, mask_p_stride, draw != 0, xin, xin_stride, B, d, draw ? eps : nullptr, n_eps,
+                       eps_stride, members, (uint64_t)offset, (uint64_t)offset_eps, gm);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_flow_fwd_multi(const float* t, long ldt, long t_stride, const float* eps, float* z, float* z_log_prob, long stride10,
+                       int G, long R, long B, void* stream) {
+    if (!t || !eps || !z || !z_log_prob || ldt < FLOW_CTX || !flow_rows_ok(R, B) || G < 1 || G > VPC_FLOW_MULTI_MAX_MEMBERS)
+        return VPC_ERR_ARG;
+    if (!flow_stride_ok(t_stride, (R - 1) * ldt + FLOW_CTX) || !flow_stride_ok(stride10, R * FLOW_L)) return VPC_ERR_ARG;
+    const long n = R * FLOW_L;
+    hipLaunchKernelGGL(flow_fwd_multi_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)G), dim3(256), 0, (hipStream_t)stream,
+                       t, ldt, t_stride, eps, z, z_log_prob, stride10, R, B);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_flow_bwd_multi(const float* t, long ldt, long t_stride, const float* eps, const float* dz, const float* dz2,
+                       const float* dz_log_prob, long stride10, float* dt, long lddt, long dt_stride, int G, long R, long B,
+                       void* stream) {
+    if (!t || !eps || !dt || ldt < FLOW_CTX || lddt < FLOW_CTX || !flow_rows_ok(R, B) || G < 1 ||
+        G > VPC_FLOW_MULTI_MAX_MEMBERS)
+        return VPC_ERR_ARG;
+    if (!flow_stride_ok(t_stride, (R - 1) * ldt + FLOW_CTX) || !flow_stride_ok(dt_stride, (R - 1) * lddt + FLOW_CTX) ||
+        !flow_stride_ok(stride10, R * FLOW_L))
+        return VPC_ERR_ARG;
+    const long n = R * FLOW_L;
+    hipLaunchKernelGGL(flow_bwd_multi_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)G), dim3(256), 0, (hipStream_t)stream,
+                       t, ldt, t_stride, eps, dz, dz2, dz_log_prob, stride10, dt, lddt, dt_stride, R, B);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+long vpc_flow_loss_multi_scratch(int G, long B) { return G > 0 ? G * vpc_flow_loss_scratch(B) : 0; }
+
+int vpc_flow_loss_multi(const float* x, long x_stride, const float* mask, long mask_stride, const float* mask_p,
+                        long mask_p_stride, const float* x_mean_q, const float* x_mean_p, long ldxm, long x_mean_stride,
+                        const float* z_q, const float* z_p, const float* z_log_prob_q, const float* z_log_prob_p,
+                        float* g_x_mean_q, float* g_x_mean_p, long ldg, long g_stride, float* g_z_q, float* g_z_p,
+                        float* g_z_log_prob_q, float* g_z_log_prob_p, long stride10, void* scratch, long scratch_bytes,
+                        double* out8, float* loss_f32, float* accum, const VpcFlowMember* members, int G, long B, int d,
+                        int stage, float gscale, int gated, void* stream) {
+    FlowLossMultiArgs ma{};
+    const int rc = flow_loss_setup(x, mask, mask_p, x_mean_q, x_mean_p, ldxm, z_q, z_p, z_log_prob_q, z_log_prob_p, g_x_mean_q,
+                                   g_x_mean_p, ldg, g_z_q, g_z_p, g_z_log_prob_q, g_z_log_prob_p, scratch, out8, loss_f32,
+                                   accum, B, d, stage, 0.f, 0.f, gscale, gated, ma.base);
+    if (rc != VPC_OK) return rc;
+    if (!flow_members_ok(members, G) || scratch_bytes < vpc_flow_loss_multi_scratch(G, B)) return VPC_ERR_ARG;
+    const long Rm = (mask_p ? 2 : 1) * B;  // a member's x_mean / z / gradient arrays hold the q rows, then the p rows
+    if (!flow_stride_ok(x_stride, B * d, true) || !flow_stride_ok(mask_stride, B * d, true) ||
+        (mask_p && !flow_stride_ok(mask_p_stride, B * d)) || !flow_stride_ok(x_mean_stride, (Rm - 1) * ldxm + d) ||
+        (g_x_mean_q && !flow_stride_ok(g_stride, (Rm - 1) * ldg + d)) || !flow_stride_ok(stride10, Rm * FLOW_L))
+        return VPC_ERR_ARG;
+    ma.sx = x_stride; ma.sm = mask_stride; ma.smp = mask_p_stride; ma.sxm = x_mean_stride; ma.s10 = stride10; ma.sg = g_stride;
+    ma.members = members;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(flow_loss_rows_multi_kernel, dim3((unsigned)ma.base.nblk, (unsigned)G), dim3(256), 0, st, ma);
+    hipLaunchKernelGGL(flow_loss_reduce_multi_kernel, dim3(1, (unsigned)G), dim3(256), 0, st, ma);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

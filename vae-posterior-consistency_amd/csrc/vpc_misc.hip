@@ -148,6 +148,18 @@ __global__ void adam_kernel(float* __restrict__ param, const float* __restrict__
     adam_apply(AdamFuse{param, m, v, pack_idx, img, lr, b1, b2, eps, bc1, bc2_sqrt, 0}, i, grad[i]);
 }
 
+// adam_kernel on row blockIdx.y of the [G][row_stride] stacks with that member's lr (vpc_adam_step_multi): the same update per
+// element, the bias corrections from the shared host step count
+__global__ void adam_multi_kernel(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
+                                  float* __restrict__ v, long row_stride, int n, const VpcFlowMember* __restrict__ members,
+                                  float b1, float b2, float eps, float bc1, float bc2_sqrt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long o = (long)blockIdx.y * row_stride;
+    adam_apply(AdamFuse{param + o, m + o, v + o, nullptr, nullptr, members[blockIdx.y].lr, b1, b2, eps, bc1, bc2_sqrt, 0}, i,
+               grad[o + i]);
+}
+
 // loss_part[nblocks][8] doubles -> out[9] floats; out[0] = train loss (already / B), out[1..8] = raw sums;
 // accum += loss.  256 threads: thread (term, g) sums blocks g, g+32, ...; fixed-order combine.
 struct LossCoef {
@@ -847,6 +859,19 @@ extern "C" int vpc_adam_step(float* params, const float* grads, float* exp_avg, 
     hipLaunchKernelGGL(adam_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, params, grads,
                        exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), pack_idx,
                        img, step_dev, loss_in, accum);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+extern "C" int vpc_adam_step_multi(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long row_stride,
+                                   int n, const VpcFlowMember* members, int G, float beta1, float beta2, float eps, long step,
+                                   void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !members || n <= 0 || step < 1 || row_stride < n || G < 1 ||
+        G > VPC_FLOW_MULTI_MAX_MEMBERS)
+        return VPC_ERR_ARG;
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((n + 255) / 256, (unsigned)G), dim3(256), 0, (hipStream_t)stream, params, grads,
+                       exp_avg, exp_avg_sq, row_stride, n, members, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2));
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

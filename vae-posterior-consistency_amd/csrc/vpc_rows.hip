@@ -7,6 +7,8 @@
 //   rows_bwd_kernel   dW[n][k] (+)= sum_m dY~[m][n] X[m][k],  db[n] (+)= sum_m dY~[m][n]      (workgroups [0, wg_blocks))
 //                     dX[m][k] = ( sum_n dY~[m][n] W[n][k] ) * act_prev'(Xout[m][k])           (the remaining workgroups)
 //   dY~ = dY * gate'(Y) formed on load when y_gate is given.
+//   rows_fwd_multi_kernel / rows_bwd_multi_kernel   the same bodies (vpc_rows_{fwd,bwd}_body.h) for G members of an ensemble: a
+//                     member axis on the grid, member g's operands = member 0's + g * stride (include/vpc.h, vpc_rows_*_multi)
 //
 // The split is over output FEATURES.  The MFMA is v_mfma_f32_16x16x4_f32 used "transposed" as everywhere in this library: the
 // D tile is [feature 4q+j][row or column c].  No operand goes through LDS: every fragment is read from global memory (L2: the
@@ -131,55 +133,11 @@ __device__ __forceinline__ void rows_slab(int nrt, int nchunk, int wave, LoadA l
 
 template <bool VEC>
 __global__ __launch_bounds__(64 * ROWS_WAVES) void rows_fwd_kernel(RowsFwdArgs a) {
-    __shared__ f32x4 red[ROWS_WAVES][ROWS_RT][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = lane & 15, q = lane >> 4;
-    const int f0 = blockIdx.x * 16, m0 = blockIdx.y * 16 * ROWS_RT;
-    const int nrt = min(ROWS_RT, (a.M - m0 + 15) / 16);
-    const int nchunk = (a.K + 15) / 16;
-    const int fw = f0 + c;
-    const bool fw_ok = fw < a.N;
-    f32x4 acc[ROWS_RT];
-#pragma unroll
-    for (int rt = 0; rt < ROWS_RT; ++rt) acc[rt] = zero4();
-    // lane (c, q): A = W[f0 + c][16 ch + 4 q + j], B = X[m0 + 16 rt + c][16 ch + 4 q + j] in k-step j of chunk ch
-    rows_slab<ROWS_GROUP>(nrt, nchunk, wave,
-              [&](int ch) {
-                  const int k = 16 * ch + 4 * q;
-                  return rows_ld4<VEC>(a.w, (long)fw * a.K + k, fw_ok ? a.K - k : 0);
-              },
-              [&](int ch, int rt) {
-                  const int k = 16 * ch + 4 * q, row = m0 + 16 * rt + c;
-                  return rows_ld4<VEC>(a.x, (long)row * a.ldx + k, row < a.M ? a.K - k : 0);
-              }, acc);
-#pragma unroll
-    for (int rt = 0; rt < ROWS_RT; ++rt) red[wave][rt][lane] = acc[rt];
-    __syncthreads();
-    // waves 0, 1: the epilogue of row tile `wave`.  s[e] = Y[m0 + 16 wave + c][f0 + 4 q + e] before bias and activation
-    if (wave >= nrt) return;
-    const f32x4 s = rows_sum(red, min(ROWS_WAVES, nchunk), wave, lane);
-    const int f = f0 + 4 * q, row = m0 + 16 * wave + c;
-    if (f >= a.N || row >= a.M) return;
-    f32x4 bv = zero4();
-    if (a.bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (f + e < a.N) bv[e] = a.bias[f + e];
-    }
-    act_dispatch(a.act, [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = act_fwd<ACT>(s[e] + bv[e], f + e >= a.split);
-        float* py = a.y + (long)row * a.ldy + f;
-        if (a.vecY && f + 3 < a.N) {
-            *reinterpret_cast<f32x4*>(py) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (f + e < a.N) py[e] = v[e];
-        }
-    });
+#define ROWS_BX blockIdx.x
+#define ROWS_BY blockIdx.y
+#include "vpc_rows_fwd_body.h"
+#undef ROWS_BX
+#undef ROWS_BY
 }
 
 // The MFMAs of one weight-gradient unit over NMB 16-row blocks of the batch (blocks past M multiply zeros).  The X fragments
@@ -266,113 +224,106 @@ __device__ __forceinline__ void rows_wgrad_unit(const RowsBwdArgs& a, int slab, 
 // VN: 16-byte loads of dy / y_gate along N (data gradient).  VK: 16-byte loads of x along K (weight gradient).
 template <bool VN, bool VK>
 __global__ __launch_bounds__(64 * ROWS_WAVES) void rows_bwd_kernel(RowsBwdArgs a) {
-    __shared__ f32x4 red[ROWS_WAVES][ROWS_RT][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = lane & 15, q = lane >> 4;
-    if ((int)blockIdx.x < a.wg_blocks) {  // ---- weight gradient: unit = (slab of 16 features, group of 64 columns) per wave
-        const int unit = ROWS_WG_UNITS * blockIdx.x + wave;
-        if (wave >= ROWS_WG_UNITS || unit >= a.wg_units) return;
-        const int ng = (a.K + 63) / 64;
-        rows_wgrad_unit<VK>(a, unit / ng, unit % ng, c, q);
-        return;
+#define ROWS_BX blockIdx.x
+#include "vpc_rows_bwd_body.h"
+#undef ROWS_BX
+}
+
+// ================================================================================================ the ensemble forms
+// G members in one launch (include/vpc.h, vpc_rows_fwd_multi / vpc_rows_bwd_multi): base = member 0's arguments, member g's
+// arrays lie g * stride floats behind them.  A workgroup runs the stand-alone body on its member's arguments, so a member's
+// bits do not depend on G, on the order or on where its workgroups run.
+struct RowsFwdMultiArgs {
+    RowsFwdArgs base;
+    long sx, sw, sy;   // floats between two members' x / (w, bias) / y
+    int G, order, nx;  // nx: 16-feature slabs of the layer (order 1 folds (slab, row block) into blockIdx.x)
+};
+struct RowsBwdMultiArgs {
+    RowsBwdArgs base;
+    long sdy, syg, sx, sxo, sdx, sw;  // sw: w, dw and db (the parameter and the gradient stack share their row pitch)
+    int G, order;
+};
+// The member of this workgroup and its index `blk` among the member's workgroups.  order 0: the member is the grid's last axis
+// (member-major: a member's workgroups are dealt over all 8 XCDs).  order 1: grid.x = 8 x the member's workgroups,
+// blk = x / 8, member = 8 y + x % 8 - workgroups go round-robin over the XCDs by their linear id, so all workgroups of a member
+// sit on one XCD and its weights are re-read through ONE L2 (false: a surplus workgroup of the last member group).
+__device__ __forceinline__ bool rows_block_member(int G, int order, unsigned last_axis, unsigned& blk, unsigned& mem) {
+    if (order == 0) {
+        blk = blockIdx.x;
+        mem = last_axis;
+        return true;
     }
-    // ---- data gradient: slab of 16 input features x 32 rows, the waves split the contraction over N
-    const int b = blockIdx.x - a.wg_blocks, nsk = (a.K + 15) / 16;
-    const int kf0 = 16 * (b % nsk), m0 = 16 * ROWS_RT * (b / nsk);
-    const int nrt = min(ROWS_RT, (a.M - m0 + 15) / 16);
-    const int nchunk = (a.N + 15) / 16;
-    const int kf = kf0 + c;
-    const bool kf_ok = kf < a.K;
-    f32x4 acc[ROWS_RT];
-#pragma unroll
-    for (int rt = 0; rt < ROWS_RT; ++rt) acc[rt] = zero4();
-    // lane (c, q): A = W[16 ch + 4 q + j][kf0 + c], B = dY~[m0 + 16 rt + c][16 ch + 4 q + j] in k-step j of chunk ch
-    act_dispatch(a.gate, [&](auto gc) {
-        constexpr int G = decltype(gc)::value;
-        rows_slab<(G == ACT_NONE ? ROWS_GROUP : ROWS_GROUP / 2)>(nrt, nchunk, wave,
-                  [&](int ch) { return rows_ld4_col(a.w, a.K, 16 * ch + 4 * q, a.N, kf, kf_ok); },
-                  [&](int ch, int rt) {
-                      const int n = 16 * ch + 4 * q, row = m0 + 16 * rt + c;
-                      const int nv = row < a.M ? a.N - n : 0;
-                      f32x4 d = rows_ld4<VN>(a.dy, (long)row * a.lddy + n, nv);
-                      if (G != ACT_NONE) {
-                          const f32x4 y = rows_ld4<VN>(a.yg, (long)row * a.ldyg + n, nv);
-#pragma unroll
-                          for (int j = 0; j < 4; ++j) d[j] *= act_grad<G>(y[j], n + j >= a.gate_split);
-                      }
-                      return d;
-                  }, acc);
-    });
-#pragma unroll
-    for (int rt = 0; rt < ROWS_RT; ++rt) red[wave][rt][lane] = acc[rt];
-    __syncthreads();
-    // wave rt: s[e] = (dY~ W)[m0 + 16 rt + c][kf0 + 4 q + e]
-    if (wave >= nrt) return;
-    f32x4 v = rows_sum(red, min(ROWS_WAVES, nchunk), wave, lane);
-    const int f = kf0 + 4 * q, row = m0 + 16 * wave + c;
-    if (f >= a.K || row >= a.M) return;
-    const bool full4 = f + 3 < a.K;
-    if (a.xo) {
-        const float* px = a.xo + (long)row * a.ldxo + f;
-        f32x4 xo = zero4();
-        if (a.vecXo && full4) {
-            xo = *reinterpret_cast<const f32x4*>(px);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (f + e < a.K) xo[e] = px[e];
-        }
-        act_dispatch(a.act_prev, [&](auto actc) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= act_grad<decltype(actc)::value>(xo[e], false);
-        });
+    blk = blockIdx.x >> 3;
+    mem = 8 * blockIdx.y + (blockIdx.x & 7);
+    return mem < (unsigned)G;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(64 * ROWS_WAVES) void rows_fwd_multi_kernel(RowsFwdMultiArgs ma) {
+    unsigned bx, by = blockIdx.y, mem;
+    if (!rows_block_member(ma.G, ma.order, blockIdx.z, bx, mem)) return;
+    if (ma.order != 0) {
+        by = bx / (unsigned)ma.nx;
+        bx -= by * (unsigned)ma.nx;
     }
-    float* pd = a.dx + (long)row * a.lddx + f;
-    if (a.vecDx && full4) {
-        *reinterpret_cast<f32x4*>(pd) = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (f + e < a.K) pd[e] = v[e];
-    }
+    RowsFwdArgs a = ma.base;  // (uniform: scalar arithmetic)
+    a.x += mem * ma.sx;
+    a.w += mem * ma.sw;
+    if (a.bias) a.bias += mem * ma.sw;
+    a.y += mem * ma.sy;
+#define ROWS_BX bx
+#define ROWS_BY by
+#include "vpc_rows_fwd_body.h"
+#undef ROWS_BX
+#undef ROWS_BY
+}
+
+template <bool VN, bool VK>
+__global__ __launch_bounds__(64 * ROWS_WAVES) void rows_bwd_multi_kernel(RowsBwdMultiArgs ma) {
+    unsigned bx, mem;
+    if (!rows_block_member(ma.G, ma.order, blockIdx.y, bx, mem)) return;
+    RowsBwdArgs a = ma.base;
+    a.dy += mem * ma.sdy;
+    if (a.yg) a.yg += mem * ma.syg;
+    if (a.w) a.w += mem * ma.sw;
+    if (a.x) a.x += mem * ma.sx;
+    if (a.xo) a.xo += mem * ma.sxo;
+    if (a.dx) a.dx += mem * ma.sdx;
+    if (a.dw) a.dw += mem * ma.sw;
+    if (a.db) a.db += mem * ma.sw;
+#define ROWS_BX bx
+#include "vpc_rows_bwd_body.h"
+#undef ROWS_BX
 }
 
 static bool rows_vec(const void* p, long ld, int width) { return aligned16(p) && (ld % 4) == 0 && (width % 4) == 0; }
 
-}  // namespace vpc
-
-using namespace vpc;
-
-extern "C" {
-
-int vpc_rows_max_rows(void) { return ROWS_MAX_M; }
-
-int vpc_rows_fwd(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long M, int N, int K,
-                 int act, int act_split, void* stream) {
+// ---- what the stand-alone entry and the ensemble entry share on the host: argument checks, the kernel's record, the grid of
+// ONE member and the 16-byte / scalar choice (taken on member 0's operands)
+static int rows_fwd_setup(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long M, int N, int K,
+                          int act, int act_split, RowsFwdArgs& a, dim3& grid, bool& vec) {
     if (!x || !w || !y || M < 1 || N < 1 || K < 1 || ldx < K || ldy < N) return VPC_ERR_ARG;
     if (act < ACT_NONE || act > ACT_RELU) return VPC_ERR_ARG;
     if (M > ROWS_MAX_M || N > ROWS_MAX_F || K > ROWS_MAX_F) return VPC_ERR_SHAPE;
-    RowsFwdArgs a{};
+    a = RowsFwdArgs{};
     a.x = x; a.ldx = ldx; a.w = w; a.bias = bias; a.y = y; a.ldy = ldy;
     a.M = (int)M; a.N = N; a.K = K; a.act = act; a.split = act == ACT_SIGMOID_HARDTANH ? act_split : N;
     a.vecY = aligned16(y) && (ldy % 4) == 0;
-    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 16 * ROWS_RT - 1) / (16 * ROWS_RT)));
-    const dim3 block(64 * ROWS_WAVES);
-    hipStream_t st = (hipStream_t)stream;
-    if (rows_vec(x, ldx, K) && rows_vec(w, K, K)) hipLaunchKernelGGL(rows_fwd_kernel<true>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(rows_fwd_kernel<false>, grid, block, 0, st, a);
-    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+    grid = dim3((unsigned)((N + 15) / 16), (unsigned)((M + 16 * ROWS_RT - 1) / (16 * ROWS_RT)));
+    vec = rows_vec(x, ldx, K) && rows_vec(w, K, K);
+    return VPC_OK;
 }
 
-int vpc_rows_bwd(const float* dy, long lddy, const float* y_gate, long ldyg, int gate, int gate_split, const float* w,
-                 const float* x, long ldx, const float* x_out, long ldxo, int act_prev, float* dx, long lddx, float* dw,
-                 float* db, long M, int N, int K, int accumulate, void* stream) {
+static int rows_bwd_setup(const float* dy, long lddy, const float* y_gate, long ldyg, int gate, int gate_split, const float* w,
+                          const float* x, long ldx, const float* x_out, long ldxo, int act_prev, float* dx, long lddx,
+                          float* dw, float* db, long M, int N, int K, int accumulate, RowsBwdArgs& a, unsigned& blocks,
+                          bool& vn, bool& vk) {
     if (!dy || M < 1 || N < 1 || K < 1 || lddy < N || (!dw && !dx)) return VPC_ERR_ARG;
     if ((dw && (!x || ldx < K)) || (dx && (!w || lddx < K))) return VPC_ERR_ARG;
     if ((y_gate && ldyg < N) || (dx && x_out && ldxo < K)) return VPC_ERR_ARG;
     if (gate < ACT_NONE || gate > ACT_RELU || act_prev < ACT_NONE || act_prev > ACT_RELU) return VPC_ERR_ARG;
     if (M > ROWS_MAX_M || N > ROWS_MAX_F || K > ROWS_MAX_F) return VPC_ERR_SHAPE;
-    RowsBwdArgs a{};
+    a = RowsBwdArgs{};
     a.dy = dy; a.lddy = lddy; a.yg = y_gate; a.ldyg = ldyg;
     a.gate = y_gate ? gate : ACT_NONE;  // (no outputs to gate with: dy is the pre-activation gradient)
     a.gate_split = gate == ACT_SIGMOID_HARDTANH ? gate_split : N;
@@ -385,14 +336,109 @@ int vpc_rows_bwd(const float* dy, long lddy, const float* y_gate, long ldyg, int
     a.vecDx = dx && aligned16(dx) && (lddx % 4) == 0;
     a.vecXo = a.xo && aligned16(a.xo) && (ldxo % 4) == 0;
     const int dg_blocks = dx ? ((K + 15) / 16) * (((int)M + 16 * ROWS_RT - 1) / (16 * ROWS_RT)) : 0;
-    const bool vn = rows_vec(dy, lddy, N) && (!y_gate || rows_vec(y_gate, ldyg, N));
-    const bool vk = !dw || rows_vec(x, ldx, K);
-    const dim3 grid((unsigned)(a.wg_blocks + dg_blocks)), block(64 * ROWS_WAVES);
+    vn = rows_vec(dy, lddy, N) && (!y_gate || rows_vec(y_gate, ldyg, N));
+    vk = !dw || rows_vec(x, ldx, K);
+    blocks = (unsigned)(a.wg_blocks + dg_blocks);
+    return VPC_OK;
+}
+
+// a member stride of the ensemble entries: at least the member's slice ((rows - 1) ld + width floats) and a multiple of 4
+// floats, so that the 16-byte / scalar choice taken on member 0's operands holds for every member
+static bool rows_stride_ok(long stride, long rows, long ld, long width) {
+    return stride >= (rows - 1) * ld + width && (stride % 4) == 0;
+}
+static bool rows_multi_ok(int G, int order) { return G >= 1 && G <= VPC_ROWS_MULTI_MAX_MEMBERS && (order == 0 || order == 1); }
+// the grid of G members with `per` workgroups each, in the order of rows_block_member; false: past the launch limits
+static bool rows_multi_grid(dim3 one, int G, int order, bool member_on_z, dim3& grid) {
+    const unsigned long per = (unsigned long)one.x * one.y;
+    if (order == 0) grid = member_on_z ? dim3(one.x, one.y, (unsigned)G) : dim3(one.x, (unsigned)G);
+    else grid = dim3((unsigned)(8 * per), (unsigned)((G + 7) / 8));
+    return 8 * per <= 0x7fffffffUL && grid.y <= 65535u && grid.z <= 65535u;
+}
+
+}  // namespace vpc
+
+using namespace vpc;
+
+extern "C" {
+
+int vpc_rows_max_rows(void) { return ROWS_MAX_M; }
+
+int vpc_rows_fwd(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long M, int N, int K,
+                 int act, int act_split, void* stream) {
+    RowsFwdArgs a;
+    dim3 grid;
+    bool vec;
+    const int rc = rows_fwd_setup(x, ldx, w, bias, y, ldy, M, N, K, act, act_split, a, grid, vec);
+    if (rc != VPC_OK) return rc;
+    const dim3 block(64 * ROWS_WAVES);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(rows_fwd_kernel<true>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(rows_fwd_kernel<false>, grid, block, 0, st, a);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_rows_bwd(const float* dy, long lddy, const float* y_gate, long ldyg, int gate, int gate_split, const float* w,
+                 const float* x, long ldx, const float* x_out, long ldxo, int act_prev, float* dx, long lddx, float* dw,
+                 float* db, long M, int N, int K, int accumulate, void* stream) {
+    RowsBwdArgs a;
+    unsigned blocks;
+    bool vn, vk;
+    const int rc = rows_bwd_setup(dy, lddy, y_gate, ldyg, gate, gate_split, w, x, ldx, x_out, ldxo, act_prev, dx, lddx, dw, db,
+                                  M, N, K, accumulate, a, blocks, vn, vk);
+    if (rc != VPC_OK) return rc;
+    const dim3 grid(blocks), block(64 * ROWS_WAVES);
     hipStream_t st = (hipStream_t)stream;
     if (vn && vk) hipLaunchKernelGGL((rows_bwd_kernel<true, true>), grid, block, 0, st, a);
     else if (vn) hipLaunchKernelGGL((rows_bwd_kernel<true, false>), grid, block, 0, st, a);
     else if (vk) hipLaunchKernelGGL((rows_bwd_kernel<false, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((rows_bwd_kernel<false, false>), grid, block, 0, st, a);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_rows_fwd_multi(const float* x, long ldx, long x_stride, const float* w, const float* bias, long wb_stride, float* y,
+                       long ldy, long y_stride, int G, long M, int N, int K, int act, int act_split, int order, void* stream) {
+    RowsFwdMultiArgs ma{};
+    dim3 one, grid;
+    bool vec;
+    const int rc = rows_fwd_setup(x, ldx, w, bias, y, ldy, M, N, K, act, act_split, ma.base, one, vec);
+    if (rc != VPC_OK) return rc;
+    if (!rows_multi_ok(G, order) || !rows_stride_ok(x_stride, M, ldx, K) || !rows_stride_ok(wb_stride, N, K, K) ||
+        !rows_stride_ok(y_stride, M, ldy, N))
+        return VPC_ERR_ARG;
+    if (!rows_multi_grid(one, G, order, true, grid)) return VPC_ERR_SHAPE;
+    ma.sx = x_stride; ma.sw = wb_stride; ma.sy = y_stride; ma.G = G; ma.order = order; ma.nx = (int)one.x;
+    const dim3 block(64 * ROWS_WAVES);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(rows_fwd_multi_kernel<true>, grid, block, 0, st, ma);
+    else hipLaunchKernelGGL(rows_fwd_multi_kernel<false>, grid, block, 0, st, ma);
+    return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
+}
+
+int vpc_rows_bwd_multi(const float* dy, long lddy, long dy_stride, const float* y_gate, long ldyg, long yg_stride, int gate,
+                       int gate_split, const float* w, const float* x, long ldx, long x_stride, const float* x_out, long ldxo,
+                       long xo_stride, int act_prev, float* dx, long lddx, long dx_stride, float* dw, float* db, long wb_stride,
+                       int G, long M, int N, int K, int accumulate, int order, void* stream) {
+    RowsBwdMultiArgs ma{};
+    unsigned blocks;
+    bool vn, vk;
+    const int rc = rows_bwd_setup(dy, lddy, y_gate, ldyg, gate, gate_split, w, x, ldx, x_out, ldxo, act_prev, dx, lddx, dw, db,
+                                  M, N, K, accumulate, ma.base, blocks, vn, vk);
+    if (rc != VPC_OK) return rc;
+    if (!rows_multi_ok(G, order) || !rows_stride_ok(dy_stride, M, lddy, N) || (y_gate && !rows_stride_ok(yg_stride, M, ldyg, N)) ||
+        ((dw || dx) && !rows_stride_ok(wb_stride, N, K, K)) || (dw && !rows_stride_ok(x_stride, M, ldx, K)) ||
+        (dx && x_out && !rows_stride_ok(xo_stride, M, ldxo, K)) || (dx && !rows_stride_ok(dx_stride, M, lddx, K)))
+        return VPC_ERR_ARG;
+    dim3 grid;
+    if (!rows_multi_grid(dim3(blocks), G, order, false, grid)) return VPC_ERR_SHAPE;
+    ma.sdy = dy_stride; ma.syg = yg_stride; ma.sx = x_stride; ma.sxo = xo_stride; ma.sdx = dx_stride; ma.sw = wb_stride;
+    ma.G = G; ma.order = order;
+    const dim3 block(64 * ROWS_WAVES);
+    hipStream_t st = (hipStream_t)stream;
+    if (vn && vk) hipLaunchKernelGGL((rows_bwd_multi_kernel<true, true>), grid, block, 0, st, ma);
+    else if (vn) hipLaunchKernelGGL((rows_bwd_multi_kernel<true, false>), grid, block, 0, st, ma);
+    else if (vk) hipLaunchKernelGGL((rows_bwd_multi_kernel<false, true>), grid, block, 0, st, ma);
+    else hipLaunchKernelGGL((rows_bwd_multi_kernel<false, false>), grid, block, 0, st, ma);
     return hipGetLastError() == hipSuccess ? VPC_OK : VPC_ERR_HIP;
 }
 

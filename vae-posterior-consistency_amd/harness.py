@@ -47,6 +47,10 @@ from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream, small_
 from .miw_ensemble import MIWEnsembleTrainer
 from .miw_ensemble import sweep_key as miw_sweep_key
 from .flow import FlowTrainer, _FlowBase
+from .flow import small_max_rows as flow_small_max_rows
+from .flow_ensemble import MIN_GROUP as FLOW_MIN_GROUP
+from .flow_ensemble import FlowEnsembleTrainer
+from .flow_ensemble import sweep_key as flow_sweep_key
 from .wide import WideTrainer
 
 _seed_counter = [0]
@@ -299,10 +303,11 @@ def train(data_loader_train, missing_rate, obs_dim, hid_dim, K, M, latent_dim, d
 
 def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type,
                    training_parameters, max_epochs, train_k, num_estimates, experiment_type, reg_type):
-    """{member index: key} of the mask-augmented, point-net and MIWAE-path members of a sweep that step in an ensemble: those
-    whose key - (family, model class, reg_type, ml_reg term on, emb_dim), or miw_ensemble.sweep_key's ("miw", class, obs_dim,
-    latent_dim, num_samples) for a MIWAE / Reg_MIWAE whose first batch takes the small-batch step (VPC_MIW_SMALL) - at least
-    one other member shares.  Decided BEFORE any member
+    """{member index: key} of the mask-augmented, point-net, MIWAE-path and flow members of a sweep that step in an ensemble:
+    those whose key - (family, model class, reg_type, ml_reg term on, emb_dim), or miw_ensemble.sweep_key's ("miw", class, obs_dim,
+    latent_dim, num_samples) for a MIWAE / Reg_MIWAE whose first batch takes the small-batch step (VPC_MIW_SMALL), or
+    flow_ensemble.sweep_key's ("flow", class, obs_dim, hid_dim) for a VAEFlow / REG_VAEFlow whose first batch takes the few-row
+    step (VPC_FLOW_SMALL) - at least one other member shares (flow: FLOW_MIN_GROUP members in all).  Decided BEFORE any member
     is built or trained, so that train_sweep still trains every other member at once, in the order of configs.  A member's
     class is that of models[g], else of a throw-away model_loader() build; the probe and the look at the first batch leave
     torch's generator where it was (the members' initial weights and a shuffling loader's order are what they are without it)."""
@@ -330,10 +335,15 @@ def _family_groups(cfgs, models, data_loader_train, loaders, obs_dim, hid_dim, K
                 key = miw_sweep_key(m, vt, loader[0], obs_dim)
                 if key is not None:
                     keys[g] = key
+            # (a flow member - model_loader builds none: they come in `models` - is probed only while the few-row step is on)
+            elif isinstance(m, _FlowBase) and flow_small_max_rows() > 0:
+                key = flow_sweep_key(m, vt, loader[0], obs_dim)
+                if key is not None:
+                    keys[g] = key
     count = {}
     for k in keys.values():
         count[k] = count.get(k, 0) + 1
-    return {g: k for g, k in keys.items() if count[k] >= 2}
+    return {g: k for g, k in keys.items() if count[k] >= (FLOW_MIN_GROUP if k[0] == "flow" else 2)}
 
 
 def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
@@ -351,7 +361,10 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
     point-net classes, emb_dim: a group of two or more steps through ensemble.MaskEnsembleTrainer / EDDIEnsembleTrainer, a
     group of one goes through train().  MIWAE / Reg_MIWAE members are grouped by (class, obs_dim, latent_dim, num_samples) while
     VPC_MIW_SMALL routes their first batch to the small-batch step (miwae.small_step_route): a group of two or more steps
-    through miw_ensemble.MIWEnsembleTrainer; with the variable unset each goes through train().  'with_drop' runs of every
+    through miw_ensemble.MIWEnsembleTrainer; with the variable unset each goes through train().  VAEFlow / REG_VAEFlow members
+    (given in `models`) are grouped by (class, obs_dim, hid_dim) while VPC_FLOW_SMALL routes their first batch to the few-row
+    step (flow.small_step_route): a group of flow_ensemble.MIN_GROUP or more steps through flow_ensemble.FlowEnsembleTrainer,
+    bit for bit as train() steps each member; with the variable unset each goes through train().  'with_drop' runs of every
     family stay alone (train()'s loop thins their mask with a drop mask of its own at every step), and so do every other
     family, point-net members of another width and batches beyond the small-batch step: train(), one by one.
     Every member is trained as train(..., alpha=, p_missingness=, seed=) alone trains it - bit for bit, except in a MIWAE group
@@ -379,11 +392,13 @@ def train_sweep(data_loader_train, configs, missing_rate, obs_dim, hid_dim, K, M
                   beta, beta_annealing, alpha_annealing, seed=c["seed"], save=save, verbose=verbose, model=m)
     rows = lambda t: t.to(device).reshape(-1, obs_dim)
     for key, idx in _group(keys)[0].items():
-        trainer_cls = {"mask": MaskEnsembleTrainer, "eddi": EDDIEnsembleTrainer, "miw": MIWEnsembleTrainer}.get(key[0],
-                                                                                                             EnsembleTrainer)
+        trainer_cls = {"mask": MaskEnsembleTrainer, "eddi": EDDIEnsembleTrainer, "miw": MIWEnsembleTrainer,
+                       "flow": FlowEnsembleTrainer}.get(key[0], EnsembleTrainer)
         ens = trainer_cls([out[g] for g in idx], lr=0.001, seeds=[cfgs[g]["seed"] for g in idx])
         # (MIWTrainer.train_step takes alpha and p_missingness from the schedule, and so does the MIWAE ensemble step)
-        schedule = (lambda i: {}) if key[0] == "miw" else (lambda i: dict(epoch=i + 1, beta=beta, beta_annealing=beta_annealing))
+        # (FlowTrainer.train_step takes alpha, p_missingness and stage: beta stays the step's default)
+        schedule = (lambda i: {}) if key[0] == "miw" else (lambda i: dict(stage=stage)) if key[0] == "flow" else \
+            (lambda i: dict(epoch=i + 1, beta=beta, beta_annealing=beta_annealing))
         alphas, pms = [cfgs[g]["alpha"] for g in idx], [cfgs[g]["p_missingness"] for g in idx]
         sources = [data_loader_train[0]] if loaders is None else [loaders[g][0] for g in idx]
         for i in range(max_epochs):
