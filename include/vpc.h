@@ -1135,6 +1135,42 @@ int vpc_flow_loss_multi(const float* x, long x_stride, const float* mask, long m
 int vpc_adam_step_multi(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long row_stride, int n,
                         const VpcFlowMember* members, int G, float beta1, float beta2, float eps, long step, void* stream);
 
+/* ---- batched evaluation of a flow model (csrc/vpc_floweval.hip) ----------------------------------------------------
+ * Replaces the loops of eval_vae's flow branch (src/experiment_main/evaluate.py:189-200 inside :160-245: `for _ in range(M):
+ * for data_sample, mask in loader:`): the rows of every batch of every Monte-Carlo pass stand behind each other (R stacked
+ * rows), the layers run once over all of them (vpc_linear_fwd), and these entries do what is not row-independent, with a
+ * table of batches ("tiles"): tile t = rows [tile_row0[t], tile_row0[t + 1]) of the stacked arrays, tile_row0[0] = 0, strictly
+ * ascending, tile_row0[n_tiles] = R.  Every table is given twice: on the HOST (checked before anything is launched; sizes the
+ * grids) and as a DEVICE copy of the same int64 values (what the kernels read, clamped to [0, R], so that a copy that differs
+ * cannot take a kernel out of bounds).  fp32, no float atomics, every sum in a fixed order.  VPC_ERR_ARG: a NULL mandatory
+ * pointer, n_tiles < 1, a host table that is not of that form, short or misaligned scratch, n_tiles > 65535
+ * (vpc_flow_eval_tiles), R > 2^26. */
+/* Flow.forward (VAE.py:1816-1831) on R stacked rows with torch.any(|eps| <= 1) (:1698) taken per tile: the rows of tile t are,
+ * bit for bit, what vpc_flow_fwd(R = B = the tile's rows) writes for them.  One launch: a workgroup takes the predicate of
+ * every tile that its 25.6 rows touch. */
+int vpc_flow_fwd_tiles(const float* t, long ldt, const float* eps, float* z, float* z_log_prob, long R, const long* tile_row0,
+                       const long* tile_row0_dev, long n_tiles, void* stream);
+/* The evaluate-stage loss terms (VAEFlow.loss, VAE.py:1950-1969; REG_VAEFlow.loss with stage != 'train', :2099-2104: loss_q,
+ * which reads nothing of the p pass) and the RMSE sums of evaluate.py:232-235, per tile.  stats (device doubles)
+ * [n_tiles][8] = loss sum RE_q + beta KL_q, RE_q (NLL on mask), KL_q, RE_q_imputed (NLL on 1 - mask),
+ * sum((x_mean - x)^2 (1 - mask)), sum(1 - mask), rows, 0.  Columns 0, 1, 3 of tile t equal, bit for bit, out8[0], out8[1],
+ * out8[7] of vpc_flow_loss(mask_p = NULL, forward only, the same beta) on the tile's rows: one wave per row, four rows per
+ * double partial, the partials of a tile summed as vpc_flow_loss sums them; columns 4 and 5 are summed in the same shape.
+ * x, mask [R][d]; x_mean [R][ldxm >= d]; z, z_log_prob [R][10].  Two launches (grid (ceil(max tile rows / 4), n_tiles), then
+ * one workgroup per tile) through `scratch` (vpc_flow_eval_tiles_scratch bytes, 8-byte aligned). */
+long vpc_flow_eval_tiles_scratch(long max_tile_rows, long n_tiles);
+int vpc_flow_eval_tiles(const float* x, const float* mask, const float* x_mean, long ldxm, const float* z,
+                        const float* z_log_prob, long R, int d, const long* tile_row0, const long* tile_row0_dev, long n_tiles,
+                        float beta, void* scratch, long scratch_bytes, double* stats, void* stream);
+/* The estimator of evaluate.py:232-245 from the tile statistics: per tile rmse = sqrt(col4 / col5) (0 / 0 = NaN for a tile
+ * with no unobserved entry, as the reference's division gives), elbo = col0 / rows, negll = col1 / rows, negll_imp =
+ * col3 / rows; the mean over the tiles [pass_tile0[p], pass_tile0[p + 1]) of every pass, then the mean over the M passes,
+ * both in table order (M > 256: thread j sums the passes j, j + 256, .., then the threads in order).  pass_tile0 [M + 1]:
+ * pass_tile0[0] = 0, strictly ascending, pass_tile0[M] = n_tiles.  out4 (device doubles) = rmse, elbo, negll, negll_imp.
+ * One workgroup. */
+int vpc_flow_eval_finalize(const double* stats, long n_tiles, const long* pass_tile0, const long* pass_tile0_dev, long M,
+                           double* out4, void* stream);
+
 /* ---- config 5 reward of the flow models (csrc/vpc_flowreward.hip) ------------------------------------------------
  * Replaces the flow branch of active_learning_func's candidate loop (src/experiment_main/evaluate.py:416-422) and the
  * functions it calls: R_lindley_chain_ratio_version (:637-665), chaini_I_ratio_version (:669-684),

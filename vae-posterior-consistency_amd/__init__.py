@@ -19,7 +19,7 @@ from .miwae import MIWAE, Reg_MIWAE, MIWTrainer
 from . import miw_ensemble
 from .miw_ensemble import MIWEnsembleTrainer
 from . import flow
-from .flow import VAEFlow, REG_VAEFlow, FlowTrainer
+from .flow import VAEFlow, REG_VAEFlow, FlowTrainer, FlowEvaluator
 from . import flow_ensemble
 from .flow_ensemble import FlowEnsembleTrainer
 from . import notmiwae
@@ -41,7 +41,7 @@ from .ais import ais_chains, ais_trajectory, eval_ais
 __all__ = ["Reg_VAE", "vanilla_VAE", "Reg_VAE_mask", "vanilla_VAE_mask", "FusedTrainer", "REG_notMIWAE_v2",
            "notMIWAE_myversion", "NMTrainer", "notmiwae", "eddi", "Reg_EDDI", "vanilla_EDDI", "EDDITrainer", "eval_vae_mnar", "mnar_result_path", "create_missing_uci", "create_missing_uci_drop_eddi", "model_loader", "checkpoint_path", "train", "eval_vae", "result_paths",
            "VpcError", "ops", "dp", "LIB_PATH", "MAX_EPOCH", "active", "reward_matrix", "R_lindley_chain", "chaini_I",
-           "chaini_II", "miwae", "MIWAE", "Reg_MIWAE", "MIWTrainer", "eval_miwae", "miwae_result_path", "flow", "VAEFlow", "REG_VAEFlow", "FlowTrainer",
+           "chaini_II", "miwae", "MIWAE", "Reg_MIWAE", "MIWTrainer", "eval_miwae", "miwae_result_path", "flow", "VAEFlow", "REG_VAEFlow", "FlowTrainer", "FlowEvaluator",
            "eddi_mnist", "Reg_EDDI_mnist", "vanilla_EDDI_mnist", "EDDIMnistTrainer",
            "flow_reward_matrix", "flow_reward_draws", "R_lindley_chain_ratio_version", "chaini_I_ratio_version",
            "chaini_II_ratio_version", "active_learning_flow", "ais", "ais_chains", "ais_trajectory", "eval_ais",

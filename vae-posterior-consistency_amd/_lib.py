@@ -195,6 +195,11 @@ _PROTOS = {
     "vpc_flow_loss_multi": [P, L_, P, L_, P, L_, P, P, L_, L_, P, P, P, P, P, P, L_, L_, P, P, P, P, L_, P, L_, P, P, P, P, I, L_,
                             I, I, F, I, P],
     "vpc_adam_step_multi": [P, P, P, P, L_, I, P, I, F, F, F, L_, P],
+    # batched evaluation of a flow model (csrc/vpc_floweval.hip); every table as (host, device copy)
+    "vpc_flow_fwd_tiles": [P, L_, P, P, P, L_, P, P, L_, P],
+    "vpc_flow_eval_tiles_scratch": [L_, L_],
+    "vpc_flow_eval_tiles": [P, P, P, L_, P, P, L_, I, P, P, L_, F, P, L_, P, P],
+    "vpc_flow_eval_finalize": [P, L_, P, P, L_, P, P],
     # config 5 reward of the flow models (csrc/vpc_flowreward.hip)
     "vpc_flow_reward_scratch": [I, I, I, I, I, C.POINTER(L_)],
     "vpc_flow_reward_matrix": [P, P, P, P, P, P, P, P, P, P, ULL, P, L_, P, I, I, I, I, I, P],
@@ -218,7 +223,7 @@ _PROTOS = {
     "vpc_eddiw_front_scratch": [L_, I, I],
     "vpc_eddiw_front_bwd": [P, P, P, P, P, P, P, P, P, L_, P, P, P, P, I, L_, I, I, P],
 }
-_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_multi_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_flow_loss_multi_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
+_RESTYPE_LONG = {"vpc_step_small_max_rows", "vpc_step_workspace_floats", "vpc_linear_wgrad_scratch", "vpc_nm_loss_scratch", "vpc_eddi_front_scratch", "vpc_miw_loss_scratch", "vpc_miw_small_workspace", "vpc_miw_multi_workspace", "vpc_miw_impute_scratch", "vpc_nm_impute_scratch", "vpc_flow_loss_scratch", "vpc_flow_loss_multi_scratch", "vpc_flow_eval_tiles_scratch", "vpc_eddiw_front_scratch", "vpc_ais_state_floats", "vpc_aisg_workspace_floats"}
 
 _lib = None
 

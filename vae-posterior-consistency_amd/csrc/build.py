@@ -5,7 +5,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["vpc_enc.hip", "vpc_dec.hip", "vpc_dec8.hip", "vpc_step_f32.hip", "vpc_step.hip", "vpc_small.hip", "vpc_evalsmall.hip", "vpc_misc.hip", "vpc_reward.hip", "vpc_gemm.hip", "vpc_rows.hip", "vpc_nm.hip", "vpc_nm_impute.hip", "vpc_nmdec.hip", "vpc_eddi.hip", "vpc_miw.hip", "vpc_miw_small.hip", "vpc_miw_impute.hip", "vpc_flow.hip", "vpc_flowreward.hip", "vpc_ais.hip", "vpc_aisg.hip", "vpc_rccl.hip"]
+SRCS = ["vpc_enc.hip", "vpc_dec.hip", "vpc_dec8.hip", "vpc_step_f32.hip", "vpc_step.hip", "vpc_small.hip", "vpc_evalsmall.hip", "vpc_misc.hip", "vpc_reward.hip", "vpc_gemm.hip", "vpc_rows.hip", "vpc_nm.hip", "vpc_nm_impute.hip", "vpc_nmdec.hip", "vpc_eddi.hip", "vpc_miw.hip", "vpc_miw_small.hip", "vpc_miw_impute.hip", "vpc_flow.hip", "vpc_floweval.hip", "vpc_flowreward.hip", "vpc_ais.hip", "vpc_aisg.hip", "vpc_rccl.hip"]
 HDRS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + ["../../include/vpc.h"]
 LIB = os.path.join(HERE, "libvpc_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -19,34 +19,10 @@
 // holds an inside element - one chunk for any non-degenerate draw.  No extra launch, no atomics, no host sync.
 // No float atomics anywhere; every reduction has a fixed order, so the results are bit-reproducible.
 #include "vpc_abi_internal.h"
-#include "vpc_flow_device.h"
+#include "vpc_flow_loss_args.h"
 #include "vpc_rng.h"
 
 namespace vpc {
-
-constexpr int FLOW_WAVES = 4;
-
-__device__ __forceinline__ float flow_wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// torch.any(|eps| <= 1) over the B x 10 draws of one pass; uniform across the workgroup (every thread must call it)
-__device__ bool flow_pass_inside(const float* __restrict__ eps, long B, int* sh) {
-    const long n = B * FLOW_L;
-    const int nw = (int)(blockDim.x >> 6), wv = (int)(threadIdx.x >> 6);
-    for (long c = 0; c < n; c += blockDim.x) {
-        const long i = c + threadIdx.x;
-        const int v = __any(i < n && fabsf(eps[i]) <= 1.f);
-        if ((threadIdx.x & 63) == 0) sh[wv] = v;
-        __syncthreads();
-        int any = 0;
-        for (int w = 0; w < nw; ++w) any |= sh[w];
-        __syncthreads();  // sh is rewritten by the next chunk
-        if (any) return true;
-    }
-    return false;
-}
 
 // the per-pass flags (f0: pass 0, f1: pass 1) of the rows [row0, row1] this workgroup covers (R = P * B, P <= 2)
 __device__ __forceinline__ void flow_flags(const float* __restrict__ eps, long R, long B, long row0, long row1,
@@ -76,24 +52,6 @@ __global__ void __launch_bounds__(256) flow_prep_kernel(const float* __restrict_
                                                         float* __restrict__ eps, long n_eps, uint64_t seed,
                                                         uint64_t offset, uint64_t offset_eps, unsigned gm) {
 #include "vpc_flow_prep_body.h"
-}
-
-struct FlowLossArgs {
-    const float* x; const float* m; const float* mp;   // [B][d]; mp = nullptr for VAEFlow
-    const float* xm[2]; long ldxm;                     // x_mean of the q / p pass, [B][ldxm]
-    const float* z[2]; const float* zlp[2];            // [B][10] each
-    float* gxm[2]; long ldg; float* gz[2]; float* gzlp[2];  // gradients (gxm[0] nullptr: forward only)
-    double* part;                                      // [nblk][8]
-    double* out8; float* loss_f32; float* accum;
-    int B, d, P, eval, gated, nblk;
-    float alpha, beta, gscale, var, logs;
-};
-
-// -Normal(loc * w, exp(-8 w / 2)).log_prob(x * w) for a 0/1 weight w (neg_gaussian_log_likelihood, :1987-1989)
-__device__ __forceinline__ float flow_nll(const FlowLossArgs& a, float x, float xr, float w) {
-    if (w == 0.f) return FLOW_HALF_LOG_2PI;
-    const float dv = x - xr;
-    return dv * dv / (2.f * a.var) + a.logs + FLOW_HALF_LOG_2PI;
 }
 
 // ---- launch 1: one wave per data row b (both passes)
@@ -199,8 +157,6 @@ __global__ void __launch_bounds__(256) flow_loss_reduce_multi_kernel(FlowLossMul
 
 using namespace vpc;
 
-static inline long flow_loss_blocks(long B) { return (B + FLOW_WAVES - 1) / FLOW_WAVES; }
-
 static inline bool flow_rows_ok(long R, long B) { return R > 0 && B > 0 && R % B == 0 && R / B <= 2 && R <= (1L << 26); }
 
 extern "C" {
@@ -268,9 +224,7 @@ static int flow_loss_setup(const float* x, const float* mask, const float* mask_
     a.B = (int)B; a.d = d; a.P = mask_p ? 2 : 1; a.eval = stage == VPC_FLOW_EVAL; a.gated = gated;
     a.nblk = (int)flow_loss_blocks(B);
     a.alpha = alpha; a.beta = beta; a.gscale = gscale;
-    const float sc = expf(-8.f / 2.f);  // x_logvar = obs_logvar * ones = -8 (:1943-1948); scale = exp(logvar / 2)
-    a.var = sc * sc;
-    a.logs = logf(sc);
+    flow_loss_obs(a);
     return VPC_OK;
 }
 

@@ -9,24 +9,5 @@
     if (g >= R * FLOW_L) return;
     const long r = g / FLOW_L;
     const int i = (int)(g - r * FLOW_L);
-    const float e = eps[g];
-    const float lp = -(e * e) / 2.f - FLOW_HALF_LOG_2PI;  // Normal(0, 1).log_prob (:1826-1828)
-    if (!(r < B ? f0 : f1)) {  // no inside element in this pass: every layer is the identity with logabsdet 0 (:1698)
-        z[g] = e;
-        zlp[g] = lp;
-        return;
-    }
-    float m[FLOW_L];
-    flow_mask(eps + r * FLOW_L, m);
-    FlowPdf s;
-    flow_pdf(t + r * ldt + i * FLOW_L, m, s);
-    float in = fabsf(e) <= 1.f ? e : 0.f;  // outside inputs are zeroed, then splined (:1694)
-    float ld = 0.f;
-#pragma unroll
-    for (int l = 0; l < 3; ++l) {
-        const FlowStep st = flow_step(s, in);
-        in = flow_out(st);
-        ld += flow_lad(st);
-    }
-    z[g] = in;
-    zlp[g] = lp - ld;
+    const bool any_inside = r < B ? f0 : f1;  // the predicate of the row's pass
+#include "vpc_flow_fwd_elem_body.h"

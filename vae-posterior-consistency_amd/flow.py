@@ -16,6 +16,9 @@ The reference's spline quirks are reproduced, not fixed (csrc/vpc_flow.hip): the
 latent mask on the bin axis, inputs outside [-1, 1] are zeroed and splined, and a pass with no inside draw is the
 identity.  latent_dim must be 10 (the reference's hard-coded 10 x 10 reshape).
 
+FlowEvaluator (below, csrc/vpc_floweval.hip) is eval_vae's estimator for one flow model with every batch of every Monte-Carlo
+pass in one set of launches: eval_vae(engine="batched").
+
 What this family shares with notmiwae.py and miwae.py lives in chainfamily.py: the encoder / decoder autograd frame (driven
 by FAMILY below) and the trainer frame.
 """
@@ -32,7 +35,7 @@ from .chainfamily import ChainDecoderFn, ChainEncoderFn, Family, _ChainTrainer
 from .images import FlatParams, mlp_spec
 from .linear import (ACT_ELU, ACT_NONE, ACT_SIGMOID_HARDTANH, _f32c, chain, chain_bwd, chain_bwd_rows, chain_fwd,
                      chain_fwd_rows)
-from .trainer import chain_draw_increment
+from .trainer import chain_draw_increment, flow_eval_draw_counters
 
 FLOW_L = 10      # VPC_FLOW_LATENT: latent dim = spline bins
 CTX = 100        # seq_encoder output = the 10 x 10 spline contexts
@@ -71,6 +74,36 @@ def flow_loss(x, mask, mask_p, xm, z, zlp, g, scratch, out8, loss_f32, accum, B,
                               *[ptr(t) for t in g[2:]], ptr(scratch), scratch.numel() * scratch.element_size(),
                               ptr(out8), ptr(loss_f32), ptr(accum), int(B), int(d), int(stage), float(alpha),
                               float(beta), float(gscale), int(gated), stream_ptr()), "vpc_flow_loss")
+
+
+def _host_table(values):
+    """A table as the batched-evaluation entries take its host side: an int64 CPU tensor (the library checks it before it
+    launches anything; the kernels read a device copy)."""
+    return torch.tensor([int(v) for v in values], dtype=torch.int64)
+
+
+def flow_fwd_tiles(t, eps, z, zlp, R, tab, tab_dev, ldt=CTX):
+    """tab / tab_dev: tile_row0 [n_tiles + 1] as an int64 CPU tensor and its device copy."""
+    check(lib().vpc_flow_fwd_tiles(ptr(t), int(ldt), ptr(eps), ptr(z), ptr(zlp), int(R), ptr(tab), ptr(tab_dev),
+                                   (0 if tab is None else tab.numel()) - 1, stream_ptr()), "vpc_flow_fwd_tiles")
+
+
+def flow_eval_tiles_scratch(max_tile_rows, n_tiles, device):
+    nbytes = int(lib().vpc_flow_eval_tiles_scratch(int(max_tile_rows), int(n_tiles)))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def flow_eval_tiles(x, mask, xm, z, zlp, R, d, tab, tab_dev, beta, scratch, stats, ldxm=None):
+    check(lib().vpc_flow_eval_tiles(ptr(x), ptr(mask), ptr(xm), int(ldxm or d), ptr(z), ptr(zlp), int(R), int(d), ptr(tab),
+                                    ptr(tab_dev), (0 if tab is None else tab.numel()) - 1, float(beta), ptr(scratch),
+                                    0 if scratch is None else scratch.numel() * scratch.element_size(), ptr(stats),
+                                    stream_ptr()), "vpc_flow_eval_tiles")
+
+
+def flow_eval_finalize(stats, n_tiles, ptab, ptab_dev, out4):
+    check(lib().vpc_flow_eval_finalize(ptr(stats), int(n_tiles), ptr(ptab), ptr(ptab_dev),
+                                       (0 if ptab is None else ptab.numel()) - 1, ptr(out4), stream_ptr()),
+          "vpc_flow_eval_finalize")
 
 
 def _mask_f32(m, d, device):
@@ -440,3 +473,151 @@ class FlowTrainer(_ChainTrainer):
         chain_bwd_rows(self.enc_layers, self.enc_acts, self.enc_dacts, R, self._enc_grads, input_grad=False, run=t,
                        names=_T_ENC_BWD)
         self._adam()
+
+
+# ------------------------------------------------------------------------------------------------ batched evaluation
+# Rows per chunk of FlowEvaluator's layer chain when the caller names none.  A MEMORY bound, not a measured optimum: a chunk row
+# holds 6 hid_dim + 120 + obs_dim activation floats (two encoder and four decoder hidden layers, the contexts, z, z_log_prob,
+# x_mean), 12.5 KB at hid_dim 500 and obs_dim 12, so a full chunk of 131 072 rows is 1.6 GB (a workspace is sized by its
+# longest chunk, not by this bound).  What was measured (profiles/flow_eval_notes.md; 80 000 rows = M 50 x 1 600, d 12, hid 500):
+# chunks of at most 8 192 / 32 768 / 65 536 / 131 072 rows took 3.47 / 2.42 / 2.27 / 2.18 ms - fewer chunks were never slower, so
+# the bound is the largest of the four, under which that evaluation is one chunk; nothing above 80 000 rows was measured.
+EVAL_MAX_ROWS = 1 << 17
+
+
+def tile_tables(batches):
+    """The tables of a batched evaluation from harness._gather_passes' ranges (M lists of (row_lo, row_hi) that follow each
+    other without a gap, starting at row 0) -> (tile_row0 [n_tiles + 1], pass_tile0 [M + 1]) as lists: tile t = rows
+    tile_row0[t] .. tile_row0[t + 1] - 1, pass p = tiles pass_tile0[p] .. pass_tile0[p + 1] - 1."""
+    tile_row0, pass_tile0 = [0], [0]
+    for ranges in batches:
+        for lo, hi in ranges:
+            if int(lo) != tile_row0[-1] or int(hi) <= int(lo):
+                raise L.VpcError(f"batch ({lo}, {hi}) does not follow row {tile_row0[-1]}: the batches of all passes must "
+                                 "lie behind each other, none of them empty")
+            tile_row0.append(int(hi))
+        if len(tile_row0) - 1 == pass_tile0[-1]:
+            raise L.VpcError("a Monte-Carlo pass without a batch")
+        pass_tile0.append(len(tile_row0) - 1)
+    if len(pass_tile0) < 2:
+        raise L.VpcError("no Monte-Carlo pass")
+    return tile_row0, pass_tile0
+
+
+def eval_chunks(tile_row0, max_rows):
+    """Split the tiles into runs of at most max_rows rows, greedily and at tile boundaries only -> [(tile_lo, tile_hi)].  A
+    single tile above max_rows raises: a batch is the unit of the flow's predicate and of the statistics."""
+    out, lo = [], 0
+    n = len(tile_row0) - 1
+    for t in range(n):
+        rows = tile_row0[t + 1] - tile_row0[t]
+        if rows > max_rows:
+            raise L.VpcError(f"tile {t} has {rows} rows, max_rows is {max_rows}: a chunk breaks only at tile boundaries")
+        if tile_row0[t + 1] - tile_row0[lo] > max_rows:
+            out.append((lo, t))
+            lo = t
+    return out + [(lo, n)]
+
+
+class _EvalChunk:
+    """One chunk's tiles [t0, t1) = stacked rows [r0, r1): its tile table counted from its own first row, host and device."""
+
+    def __init__(self, tile_row0, t0, t1, dev):
+        self.t0, self.t1, self.r0, self.r1 = t0, t1, tile_row0[t0], tile_row0[t1]
+        self.rows = self.r1 - self.r0
+        self.tab = _host_table(v - self.r0 for v in tile_row0[t0:t1 + 1])
+        self.tab_dev = self.tab.to(dev)
+
+
+class FlowEvaluator:
+    """eval_vae's estimator for ONE VAEFlow / REG_VAEFlow model with every batch of every Monte-Carlo pass in one set of
+    launches (csrc/vpc_floweval.hip): the rows of all batches stand behind each other, the eight layers
+    run once over all of them, and a tile table keeps what is per batch per batch - the flow's torch.any(inside) (VAE.py:1698)
+    and the statistics, whose means over a pass's batches and then over the passes are evaluate.py:232-245's.  One evaluate
+    call that fits in one chunk is 12 library calls: prep, 3 encoder GEMMs, the flow, 5 decoder GEMMs, the tile statistics (2
+    launches), the finalize - whatever M and the number of batches.
+
+    What differs from eval_vae(engine="chain"): no p pass and no mask_p draw - the evaluate-stage loss of REG_VAEFlow is loss_q
+    (VAE.py:2099-2104), which reads nothing of the p pass, and under Philox there is no stream position that the unused draws
+    would have to preserve; eps comes from the evaluator's Philox stream (flow_eval_draw_counters), not from torch.randn.  The
+    estimator and its distribution are the same.  The reference's drivers pass neither beta nor epoch into the flow losses
+    (forward_loss): beta = 1.
+
+    seed: of the Philox stream (None: 0); the evaluator owns an offset that every drawing call advances.  max_rows: rows per
+    chunk of the layer chain (None: EVAL_MAX_ROWS).  tile_stats: the [n_tiles][8] table of the last call (vpc.h,
+    vpc_flow_eval_tiles) and eps: the [R][10] normals it used, both valid until the next call on the same layout."""
+
+    def __init__(self, model, seed=None, max_rows=None):
+        if not isinstance(model, _FlowBase):
+            raise L.VpcError(f"FlowEvaluator evaluates VAEFlow and REG_VAEFlow, not {type(model).__name__}")
+        self.model = model
+        self.seed = 0 if seed is None else int(seed)
+        self.max_rows = EVAL_MAX_ROWS if max_rows is None else int(max_rows)
+        if self.max_rows < 1:
+            raise L.VpcError(f"max_rows = {max_rows}")
+        self.rng_offset = 0
+        self.tile_stats = self.eps = None
+        self._layouts = {}
+
+    def _layout(self, tile_row0, pass_tile0, dev):
+        """The workspace of a layout, kept for the next call on it: tables, chunks, activation buffers, scratch, statistics."""
+        key = (tuple(tile_row0), tuple(pass_tile0), str(dev))
+        ws = self._layouts.get(key)
+        if ws is not None:
+            return ws
+        m = self.model
+        d, H = m.obs_dim, m.hid_dim
+        R, n_tiles = tile_row0[-1], len(tile_row0) - 1
+        ws = self._layouts[key] = {}
+        chunks = ws["chunks"] = [_EvalChunk(tile_row0, t0, t1, dev) for t0, t1 in eval_chunks(tile_row0, self.max_rows)]
+        C = max(c.rows for c in chunks)
+        e = lambda *s: torch.empty(*s, device=dev)
+        ws["ptab"] = _host_table(pass_tile0)
+        ws["ptab_dev"] = ws["ptab"].to(dev)
+        ws["xin"], ws["eps"] = e(R, 2 * d), e(R, FLOW_L)
+        ws["enc"] = [None, e(C, H), e(C, H), e(C, CTX)]
+        ws["dec"] = [e(C, FLOW_L), *[e(C, H) for _ in range(4)], e(C, d)]
+        ws["zlp"] = e(C, FLOW_L)
+        ws["scratch"] = flow_eval_tiles_scratch(max(tile_row0[t + 1] - tile_row0[t] for t in range(n_tiles)), n_tiles, dev)
+        ws["stats"] = torch.zeros(n_tiles, 8, dtype=torch.float64, device=dev)
+        ws["out4"] = torch.empty(4, dtype=torch.float64, device=dev)
+        return ws
+
+    def evaluate(self, x, mask, batches, eps=None):
+        """x, mask: [R, d], the batches of all passes behind each other (harness._gather_passes); batches: M lists of
+        (row_lo, row_hi).  eps: [R, 10] normals, or None: drawn on the device at the next flow_eval_draw_counters offset.
+        Returns a float64 tensor [4] on the device = (rmse on ~mask, elbo, negll, negll_imp) as eval_vae averages them; no host
+        synchronisation."""
+        m = self.model
+        d = m.obs_dim
+        xf = _f32c(x.reshape(-1, d))
+        L.require_cuda(xf)
+        dev = xf.device
+        mf = _mask_f32(mask, d, dev)
+        tile_row0, pass_tile0 = tile_tables(batches)
+        R, n_tiles = tile_row0[-1], len(tile_row0) - 1
+        if xf.shape[0] != R or mf.shape[0] != R:
+            raise L.VpcError(f"x has {xf.shape[0]} rows and mask {mf.shape[0]}, the batches cover {R}")
+        ws = self._layout(tile_row0, pass_tile0, dev)
+        if eps is None:
+            off, self.rng_offset = flow_eval_draw_counters(self.rng_offset, R)
+            flow_prep(xf, mf, None, None, ws["xin"], ws["eps"], R, d, 1.0, self.seed, 0, off)
+            ef = ws["eps"]
+        else:
+            ef = _f32c(eps.reshape(-1, FLOW_L).to(dev))
+            if ef.shape[0] != R:
+                raise L.VpcError(f"eps has {ef.shape[0]} rows, the batches cover {R}")
+            flow_prep(xf, mf, None, None, ws["xin"], None, R, d)
+        enc, dec = m._build_chains(m._views())
+        ea, da, zlp, stats = ws["enc"], ws["dec"], ws["zlp"], ws["stats"]
+        for c in ws["chunks"]:
+            n = c.rows
+            ea[0] = ws["xin"][c.r0:c.r1]
+            chain_fwd(enc, ea, n)
+            flow_fwd_tiles(ea[3], ef[c.r0:c.r1], da[0], zlp, n, c.tab, c.tab_dev)
+            chain_fwd(dec, da, n)
+            flow_eval_tiles(xf[c.r0:c.r1], mf[c.r0:c.r1], da[5], da[0], zlp, n, d, c.tab, c.tab_dev, 1.0, ws["scratch"],
+                            stats[c.t0:c.t1])
+        flow_eval_finalize(stats, n_tiles, ws["ptab"], ws["ptab_dev"], ws["out4"])
+        self.tile_stats, self.eps = stats, ef
+        return ws["out4"].clone()

@@ -6,7 +6,9 @@
   train                src/experiment_main/train.py:13-133   epoch / batch loop, Adam(lr=1e-3), save at end
   train_sweep          src/experiment_main/imputation.py:21-39  the drivers' loops over alpha / p_missingness / split around
                                                              train(), as ensembles stepped by one pair of launches (ensemble.py)
-  eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL
+  eval_vae             src/experiment_main/evaluate.py:136-297  M MC passes: imputation RMSE on ~mask, ELBO, NLL; engine="batched"
+                                                             (flow models): all passes and batches in one launch set
+                                                             (flow.FlowEvaluator)
   eval_sweep           src/experiment_main/imputation.py:51-59  eval_vae() of a list of runs, the plain, mask-augmented and
                                                              point-net members in one pair of launches per group and loader
                                                              (ensemble.EnsembleEvaluator and its two family subclasses)
@@ -46,7 +48,7 @@ from .eddi_mnist import EDDIMnistTrainer, Reg_EDDI_mnist, vanilla_EDDI_mnist, _E
 from .miwae import MIWAE, MIWTrainer, Reg_MIWAE, _MIWBase, impute_stream, small_max_rows
 from .miw_ensemble import MIWEnsembleTrainer
 from .miw_ensemble import sweep_key as miw_sweep_key
-from .flow import FlowTrainer, _FlowBase
+from .flow import FlowEvaluator, FlowTrainer, _FlowBase
 from .flow import small_max_rows as flow_small_max_rows
 from .flow_ensemble import MIN_GROUP as FLOW_MIN_GROUP
 from .flow_ensemble import FlowEnsembleTrainer
@@ -446,17 +448,44 @@ def _save_results(res, paths):  # the files of one result dict: res[k] under pat
 def eval_vae(list_loaders, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
              experiment_type, vae_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), alpha=0.5,
              stage="evaluate", p_missingness=30, reg_type="ml_reg", beta=1.0, beta_annealing=False,
-             alpha_annealing=True, model=None, save=True):
+             alpha_annealing=True, model=None, save=True, engine="chain", seed=None):
     """evaluate.py:136-297 for reg_vae* / vanilla_vae* and, given as `model`, VAEFlow / REG_VAEFlow (the flow branch,
     evaluate.py:189-200): reload the checkpoint (or use `model`), and for every
     (loader, loader_stage): M Monte-Carlo passes of forward + loss(llh_eval=True, stage) per batch; RMSE of the
     imputations on the UNobserved entries, mean ELBO, NLL on observed and on imputed entries.  Returns
-    {loader_stage: dict(rmse, elbo, negll, negll_imp)} and (save=True) writes the reference's four files."""
+    {loader_stage: dict(rmse, elbo, negll, negll_imp)} and (save=True) writes the reference's four files.
+
+    engine="chain" (the default) walks the passes and batches as the reference does.  engine="batched" (flow models only,
+    given as `model`): per (loader, loader_stage) the loader is iterated once per pass, the batches are gathered on the
+    device and ONE flow.FlowEvaluator.evaluate call computes every pass x batch (12 library calls whatever M is), one .cpu().
+    No p pass and no mask_p draw (FlowEvaluator says why), eps from the Philox stream of `seed`, beta = 1 as the reference's
+    drivers leave it for the flows; same estimator, same files.  No fallback: a model of another family raises VpcError, and
+    so does REG_VAEFlow with stage="train", whose loss reads the p pass."""
+    if engine not in ("chain", "batched"):
+        raise L.VpcError(f"engine={engine!r}: 'chain' or 'batched'")
     out = {}
     with torch.no_grad():
         model = _model_for_eval(model, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
                                 max_epochs, valid_k, num_estimates, experiment_type, reg_type, vae_type, alpha=alpha,
                                 p_missingness=p_missingness)
+        if engine == "batched":
+            if not isinstance(model, _FlowBase):
+                raise L.VpcError(f"engine='batched' evaluates VAEFlow and REG_VAEFlow, not {type(model).__name__} "
+                                 "(eval_sweep evaluates the other families' sweeps together)")
+            if model.regularised and stage == "train":
+                raise L.VpcError("engine='batched' with stage='train': REG_VAEFlow's train-stage loss reads the p pass "
+                                 "(VAE.py:2081-2097), which the batched engine does not run")
+            ev = FlowEvaluator(model, seed=seed)
+            for loader, loader_stage in list_loaders:
+                gathered = _gather_passes([loader], M, obs_dim, device)
+                if gathered is None:
+                    raise L.VpcError(f"loader stage {loader_stage!r}: a Monte-Carlo pass without a batch")
+                r = ev.evaluate(*gathered).cpu()
+                out[loader_stage] = dict(rmse=r[0].clone(), elbo=r[1].clone(), negll=r[2].clone(), negll_imp=r[3].clone())
+                if save:
+                    _save_results(out[loader_stage], result_paths(experiment_type, data_type, vae_type, loader_stage,
+                                                                  missing_rate, alpha, p_missingness, reg_type))
+            return out
         for loader, loader_stage in list_loaders:
             recon, res, res_negll, res_negll_imp = [], [], [], []
             for _ in range(M):
@@ -512,7 +541,8 @@ def _gather_passes(sources, M, obs_dim, device):
 
 def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
                experiment_type, max_epochs, valid_k, num_estimates, device=torch.device("cuda"), stage="evaluate",
-               reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, models=None, loaders=None, save=True):
+               reg_type="ml_reg", beta=1.0, beta_annealing=False, alpha_annealing=True, models=None, loaders=None, save=True,
+               engine="chain"):
     """eval_vae() for a LIST of runs - the evaluation that follows every train() of the drivers' loops
     (src/experiment_main/imputation.py:51-59 around evaluate.py:136-297) as one call; the twin of train_sweep, with its
     conventions for configs.  list_loaders: what eval_vae takes, shared by every member; or loaders = one such list per
@@ -524,12 +554,17 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
     of one class, shape, emb_dim and reg_type (family_eval_groups), are evaluated the same way through MaskEnsembleEvaluator /
     EDDIEnsembleEvaluator.  Who goes through eval_vae one by one: a mask-augmented or point-net member with no second of its kind
     or past its family's kernels (2 obs_dim > 128; obs_dim > 64 or emb_dim > 32), every other family (wide, mnist EDDI, MNAR,
-    MIWAE, flow), and the members of a group whose per-member loaders differ in their batch sizes.  Returns, per member in the order of configs, what eval_vae returns, and (save=True) writes
+    MIWAE; flow under the default engine), and the members of a group whose per-member loaders differ in their batch sizes.  Returns, per member in the order of configs, what eval_vae returns, and (save=True) writes
     the reference's four files under result_paths(...) with that member's alpha / p_missingness.
     What differs from eval_vae for the members evaluated together: no p pass and no mask_p draw (VAE.py:410-420 never reads
     them, and under Philox there is no stream position to preserve); eps comes from the member's Philox stream (seed =
     the config's seed), not from torch.randn; a shared loader is iterated once per pass for the whole group, not once per
-    member.  The estimator and its distribution are the same."""
+    member.  The estimator and its distribution are the same.
+    engine="batched": every VAEFlow / REG_VAEFlow member goes through eval_vae(engine="batched", seed = the config's seed) - still
+    one member after the other (DESIGN.md section 2.35 says why there is no member axis), each in 12 library calls per loader
+    stage; every other member is routed as under the default "chain"."""
+    if engine not in ("chain", "batched"):
+        raise L.VpcError(f"engine={engine!r}: 'chain' or 'batched'")
     cfgs = _sweep_configs(configs, models, loaders)
     member_loaders = (lambda g: loaders[g]) if loaders is not None else (lambda g: list_loaders)
     ms = _sweep_models(cfgs, models, device, obs_dim, hid_dim, K, latent_dim, missing_rate, data_type, training_parameters,
@@ -540,7 +575,9 @@ def eval_sweep(list_loaders, configs, missing_rate, obs_dim, hid_dim, K, M, late
         c = cfgs[g]
         out[g] = eval_vae(member_loaders(g), missing_rate, obs_dim, hid_dim, K, M, latent_dim, data_type, training_parameters,
                           experiment_type, c["vae_type"], max_epochs, valid_k, num_estimates, device, c["alpha"], stage,
-                          c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, model=ms[g], save=save)
+                          c["p_missingness"], reg_type, beta, beta_annealing, alpha_annealing, model=ms[g], save=save,
+                          **(dict(engine="batched", seed=c["seed"]) if engine == "batched" and isinstance(ms[g], _FlowBase)
+                             else {}))
 
     def together(idx, evaluator_class):
         """THE evaluation of a group: the passes gathered per loader stage, one evaluate call per stage, the results written."""

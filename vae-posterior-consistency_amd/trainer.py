@@ -57,6 +57,16 @@ def eval_draw_counters(rng_offset, draw_rows, pitch=16):
     return rng_offset, rng_offset + draw_rows * (pitch // 4)
 
 
+def flow_eval_draw_counters(rng_offset, rows):
+    """THE counter rule of the batched flow evaluation's draws (flow.FlowEvaluator): one evaluate call
+    draws eps [rows][10] for every row of every batch of every MC pass, in tile-table order, as ONE flat array of 10 * rows
+    floats on the eps stream with the evaluator's seed: one Philox call per 4 floats, the group of flat floats 4 q .. 4 q + 3 at
+    counter offset + q - what ops.fill_normal(flat [10 * rows], seed, offset) writes.  A draw is a function of (seed, offset,
+    flat index) alone: not of the tile table, nor of how the evaluator splits the rows into chunks.
+    Returns (offset of this call, the evaluator's rng_offset after it = offset + ceil(10 * rows / 4))."""
+    return rng_offset, rng_offset + (10 * rows + 3) // 4
+
+
 def impute_draw_counter(offset, row0, row, sample, latent):
     """THE counter rule of the streaming MIWAE imputation's draws (miw_imp_ctr of csrc/vpc_rng.h):
     the 64-bit Philox counter of latent components 4 g .. 4 g + 3 (g = latent // 4) of `sample` of data row row0 + row is
